@@ -16,7 +16,7 @@ N = 1 workload: BASELINE.json configs[1] -- W8A8 SDXL-Turbo UNet, 1024x1024 (lat
 step loop).  `--baseline-config 3` is BASELINE.json configs[3] as named: GLOBAL batch 64 sharded
 over the N ranks (64 / N per GPU), 4 UNet forwards per image -- strong scaling.
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0): the timed region is exactly --steps steps.  Extra objects, with --extras:
   roofline      dominant kernel (an igemm_kernel<BM,BN,BK,CONV> instantiation): the launches of ONE
                 forward of the graph that was timed are recorded (mixdq_amd._C.RECORD), replayed
                 per kernel instantiation from a hipGraph and bracketed by HIP events on the launch
@@ -106,7 +106,21 @@ def parse_args():
     ap.add_argument("--profile-ranges", action="store_true",
                     help="after the timed region: 3 eager iterations with roctx ranges per block "
                          "(quantize_sdxl.py:387-429), for rocprofv3 --marker-trace")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps: what the timed path returned in its last step (rank 0), as "
+                         "DIR/<name>.npy in float32 -- at most 64 MB in all; a larger output is a fixed seeded "
+                         "sample of its elements, their flat indices in DIR/<name>_index.npy (float64)")
+    ap.add_argument("--extras", action="store_true",
+                    help="also run the comparison legs: the FP16 network, the roofline sweep, batch 8, the drop-in "
+                         "and LayerNorm-in-GEMM graphs (each times steps of its own) and the CPU baseline; the --no-* "
+                         "flags above still drop single legs.  Without it the run times exactly --steps steps of the "
+                         "benchmarked path and nothing else")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (ms_per_step is the timed region over this many steps)")
+    if not args.extras:
+        args.no_fp16 = args.no_roofline = args.no_batch8 = args.no_dropin = args.no_lnchain = True
+        args.no_cpu_baseline = True
     if args.baseline_config == 2:
         args.w_config, args.a_config, args.w4_kernel = "weight/weight_4.00", "act/act_7.77", True
     elif args.baseline_config == 3:
@@ -139,6 +153,35 @@ def time_steps(fn, steps, warmup, device):
         shard.barrier()
         dt = time.perf_counter() - t0
     return shard.max_over_ranks(dt, device)
+
+
+DUMP_BUDGET_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES, seed=0):
+    """Write {name: tensor} as out_dir/<name>.npy in float32, at most `budget` bytes in all.  Arrays that do not fit
+    whole are sampled: the same elements on every run (seeded, sorted flat indices, also written as
+    <name>_index.npy in float64), so that two builds can be compared element for element.  Returns what was
+    written: {name: {"shape", "elements", "sampled"}}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.size for a in host.values())
+    fits = total * 4 <= budget
+    info = {}
+    for name, a in host.items():
+        flat = a.reshape(-1)
+        if fits:
+            np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+            info[name] = {"shape": list(a.shape), "elements": int(a.size), "sampled": False}
+            continue
+        # each array gets its share of the budget; values (4 B) + index (8 B) per sampled element
+        n = max(1, min(flat.size, int(budget * flat.size / total) // 12))
+        idx = np.sort(np.random.default_rng(seed).choice(flat.size, size=n, replace=False))
+        np.save(os.path.join(out_dir, name + ".npy"), flat[idx].astype(np.float32))
+        np.save(os.path.join(out_dir, name + "_index.npy"), idx.astype(np.float64))
+        info[name] = {"shape": list(a.shape), "elements": int(n), "sampled": True}
+    return info
 
 
 def layer_shapes(unet, inputs):
@@ -661,8 +704,17 @@ def main():
             return v[:n] if v.dim() > 0 and v.shape[0] == B else v
         return {a: first_rows(b, n) for a, b in v.items()} if isinstance(v, dict) else v
     calib_inputs = {k: first_rows(v, 2) for k, v in inputs.items()} if B > 2 else inputs
-    ckpt = calibrate(unet, [calib_inputs], bos=not args.no_bos)
-    bos_dict = precompute_bos(unet, inputs["encoder_hidden_states"])
+    # The scales are inputs of the timed path as much as the latents are, so they must be the same on every run with
+    # the same arguments (--dump-outputs compares builds output for output).  The calibration forward runs stock
+    # FP16 ops, and MIOpen's default convolutions do not give the same bits twice; its deterministic algorithms do.
+    # Only here: the legs that are timed run with the setting the process had.
+    det_was = (torch.are_deterministic_algorithms_enabled(), torch.is_deterministic_algorithms_warn_only_enabled())
+    torch.use_deterministic_algorithms(True, warn_only=True)
+    try:
+        ckpt = calibrate(unet, [calib_inputs], bos=not args.no_bos)
+        bos_dict = precompute_bos(unet, inputs["encoder_hidden_states"])
+    finally:
+        torch.use_deterministic_algorithms(det_was[0], warn_only=det_was[1])
 
     # --vary-timestep: the pipeline's sampling loop -- each step hands the UNet another timestep
     # VALUE (a 0-dim device tensor, as the scheduler does); the graph cache keys on shapes and
@@ -735,9 +787,18 @@ def main():
     if not args.no_graph:
         hip_graph_opt(unet)
     setup_s = time.perf_counter() - t_setup
-    dt = time_steps(run_once, args.steps, args.warmup, device)
+    last_out = [None]
+
+    def run_once_kept():
+        last_out[0] = run_once()
+    dt = time_steps(run_once_kept if args.dump_outputs else run_once, args.steps, args.warmup, device)
     ms = 1e3 * dt / args.steps
     value = global_batch * args.steps / dt / fpi / rows_per_image
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # now, before any later leg runs: in a hipGraph the step's output is the graph's static buffer, which the
+        # next replay overwrites
+        dumped = dump_outputs(args.dump_outputs, {"sample": last_out[0]})
     graphs_cached = None if args.no_graph else len(unet.forward._cached)
     memory["w4a8_mixed" if args.w4_kernel else "w8a8"] = q_meter.report()
 
@@ -950,6 +1011,8 @@ def main():
             out["speedup_vs_fp16_dropin_glue_own_quantize"] = fp16["ms_per_step"] / dropin["dropin_glue_own_quantize_ms_per_step"]
     if ln_in_gemm:
         out["ln_in_gemm"] = ln_in_gemm
+    if dumped is not None:
+        out["dump_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "arrays": dumped}
     if world == 1:
         out["multi_gpu"] = ("unmeasured: no multi-GPU node was available to this build; RCCL has run under this "
                             "code at world size 1 only (tests/test_dist_gpu.py)")

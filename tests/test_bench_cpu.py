@@ -55,3 +55,48 @@ def test_a_failing_rank_fails_the_parent():
     proc = _bench("--gpus", "2", env_extra={"MIXDQ_DIST_BACKEND": "no-such-backend"}, timeout=300)
     assert proc.returncode != 0
     assert not [ln for ln in proc.stdout.splitlines() if ln.startswith("{")]
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("mixdq_bench", os.path.join(ROOT, "bench.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_steps_below_one_is_refused():
+    proc = _bench("--steps", "0")
+    assert proc.returncode != 0 and "--steps must be at least 1" in proc.stderr
+
+
+def test_dump_outputs_writes_float32_whole_when_it_fits(tmp_path):
+    import numpy as np
+    import torch
+    b = _bench_module()
+    x = torch.randn(2, 4, 16, 16, generator=torch.Generator().manual_seed(1)).half()
+    info = b.dump_outputs(str(tmp_path), {"sample": x})
+    got = np.load(tmp_path / "sample.npy")
+    assert got.dtype == np.float32 and got.shape == (2, 4, 16, 16)
+    assert np.array_equal(got, x.float().numpy())
+    assert info == {"sample": {"shape": [2, 4, 16, 16], "elements": x.numel(), "sampled": False}}
+    assert not (tmp_path / "sample_index.npy").exists()
+
+
+def test_dump_outputs_samples_the_same_elements_within_the_budget(tmp_path):
+    import numpy as np
+    import torch
+    b = _bench_module()
+    x = torch.randn(64, 1000, generator=torch.Generator().manual_seed(2))
+    budget = 12 * 1000                                   # room for 1000 (value, index) pairs, not 64000 values
+    runs = []
+    for d in ("a", "b"):
+        info = b.dump_outputs(str(tmp_path / d), {"sample": x}, budget=budget)
+        vals, idx = np.load(tmp_path / d / "sample.npy"), np.load(tmp_path / d / "sample_index.npy")
+        assert info["sample"]["sampled"] and info["sample"]["shape"] == [64, 1000]
+        assert vals.dtype == np.float32 and idx.dtype == np.float64
+        assert vals.nbytes + idx.nbytes <= budget and vals.size == idx.size == info["sample"]["elements"]
+        assert (np.diff(idx) > 0).all()
+        assert np.array_equal(vals, x.numpy().reshape(-1)[idx.astype(np.int64)])
+        runs.append(idx)
+    assert np.array_equal(runs[0], runs[1])

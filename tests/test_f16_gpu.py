@@ -51,8 +51,7 @@ def test_linear_f16_vs_fp32_reference(C, M, K, N, bias):
     assert torch.equal(out, C.linear_f16(x, w, b))   # deterministic
 
 
-@pytest.mark.parametrize("cfg", __import__("mixdq_amd._C", fromlist=["x"]).F16_CONFIGS
-                         if torch.cuda.is_available() else [])
+@pytest.mark.parametrize("cfg", __import__("mixdq_amd._C", fromlist=["x"]).F16_CONFIGS)   # the same ids with or without a GPU
 def test_linear_and_conv_f16_every_configuration(C, cfg):
     for (M, K, N) in ((203, 1232, 136), (331, 1280, 424)):
         x, w, b = rnd((M, K), 4), rnd((N, K), 5, 0.05), rnd((N,), 6)

@@ -539,8 +539,7 @@ def test_qconv2d_halo_kernel_range(C):
         C.qconv2d_w8_a8_ohalf(x, w, v, scal(1), scal(0), v, ws, None, None, 1, 1, _cfg=90)
 
 
-@pytest.mark.parametrize("cfg", sorted(__import__("mixdq_amd._C", fromlist=["x"]).IGEMM_CONFIGS)
-                         if torch.cuda.is_available() else [])
+@pytest.mark.parametrize("cfg", sorted(__import__("mixdq_amd._C", fromlist=["x"]).IGEMM_CONFIGS))   # the same ids with or without a GPU
 def test_every_kernel_configuration_is_bit_exact(C, oracle, cfg):
     """All tile / stage configurations of the igemm family give the oracle's bits (linear with a
     ragged M, K tail for BK = 128; padded conv with odd spatial size)."""

@@ -18,13 +18,14 @@ generated assembly of every AQ kernel:
   4. no AQ kernel uses scratch memory (a spill of an in-flight register would be caught by 2; spills
      elsewhere are reported because they cost the prefetch its registers).
 
-    python tools/check_aq_isa.py [igemm_aq.s]     (default: build it with hipcc -S into /tmp)
+    python tools/check_aq_isa.py [igemm_aq.s]     (default: build it with hipcc -S into a temporary directory)
 Exit status 0 = every AQ kernel passes.
 """
 import os
 import re
 import subprocess
 import sys
+import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -151,8 +152,11 @@ def check_kernel(name, body):
 
 
 def main():
-    path = sys.argv[1] if len(sys.argv) > 1 else build_asm("/tmp/igemm_aq_check.s")
-    asm = open(path).read()
+    if len(sys.argv) > 1:
+        asm = open(sys.argv[1]).read()
+    else:     # a private directory: a fixed shared path fails when another user has written it first
+        with tempfile.TemporaryDirectory(prefix="mixdq_aq_check_") as tmp:
+            asm = open(build_asm(os.path.join(tmp, "igemm_aq.s"))).read()
     bad = 0
     n = 0
     for name, body, scratch in kernels(asm):
