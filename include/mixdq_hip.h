@@ -53,8 +53,11 @@ enum mixdq_status {
   MIXDQ_ERR_GEGLU_SHAPE = 6,     /* mixdq_qlinear_w8a8_geglu: N % 32, K % 16 or pointer alignment */
   MIXDQ_ERR_PADDING = 7,         /* conv: padding >= kernel size (a window with no in-image tap)  */
   MIXDQ_ERR_ROWMAP_RESIDUAL = 8, /* output row map and residual in one call                       */
-  MIXDQ_ERR_SHAPE = 9            /* shape outside a fused kernel's range (head_dim != 64, GroupNorm
+  MIXDQ_ERR_SHAPE = 9,           /* shape outside a fused kernel's range (head_dim != 64, GroupNorm
                                     geometry, LayerNorm width, tensor rank)                       */
+  MIXDQ_ERR_W2_SHAPE = 10        /* MIXDQ_FLAG_W2: K % 64 != 0, an operand pointer not 16-byte
+                                    aligned, or a forced tile W2 does not take (ids 42, 43, 44, 45,
+                                    56: weight stage not whole 1-KiB pieces; 27)                  */
 };
 
 /* Bit flags accepted by the compute entry points. */
@@ -77,7 +80,17 @@ enum mixdq_flags {
      MIXDQ_ERR_SHAPE.  No reference counterpart. */
   MIXDQ_FLAG_UPSAMPLE2X = 4,
   /* mixdq_qlinear_f16in_w8a8 only: the FP16 operand's rows follow the output row map (see there). */
-  MIXDQ_FLAG_A_ROWMAP = 8
+  MIXDQ_FLAG_A_ROWMAP = 8,
+  /* The weight operand of mixdq_qlinear_w8a8[_rows] / _geglu / _attn / _grouped is PACKED signed 2-bit
+     ("crumb-planar per 16": within every group of 16 consecutive k, byte j (0..3) of the group's dword
+     holds k[16g+j] in bits 7:6, k[16g+4+j] in 5:4, k[16g+8+j] in 3:2 and k[16g+12+j] in 1:0, two's
+     complement; [N, K/4] bytes).  Values in [-2, 1]; needs K % 64 == 0 (MIXDQ_ERR_W2_SHAPE otherwise).
+     Results equal the W8 / W4 paths run on the unpacked values, bit for bit; bias0 / scale are those of
+     the unpacked integers.  Linear only: conv, FP16, GEMM + LayerNorm and FP16-operand entry points
+     refuse it (MIXDQ_ERR_UNSUPPORTED; mixdq_qlinear_f16in_w8a8 and the LayerNorm launch: MIXDQ_ERR_SHAPE,
+     the caller then quantizes and runs the GEMM).  Together with MIXDQ_FLAG_W4: MIXDQ_ERR_INVALID_ARG.
+     No reference counterpart: the reference stores its 2-bit layers as 4-bit (TODO in its loader). */
+  MIXDQ_FLAG_W2 = 16
   /* bits 8..15: force a kernel configuration id (tuning / tests); 0 = automatic */
 };
 
@@ -350,7 +363,7 @@ int mixdq_qlinear_w8a8_attn(const int8_t* A, const int8_t* W, const float* bias0
  * `groups_device`: DEVICE array of members; N may differ per member (max_N = the largest).  The
  * row map is shared.  K % 16 == 0 (W4: % 32) and N % 4 == 0. */
 typedef struct mixdq_gemm_group {
-  const int8_t* W;               /* [N, K] (MIXDQ_FLAG_W4: [N, K/2] packed) */
+  const int8_t* W;               /* [N, K] (MIXDQ_FLAG_W4: [N, K/2], MIXDQ_FLAG_W2: [N, K/4] packed) */
   const float* bias0;            /* [N] */
   const float* scale;            /* [N] */
   const void* bias_f16_or_null;  /* [N] */
@@ -446,10 +459,15 @@ int mixdq_igemm_select(int64_t M, int N, int k_align, int k_total, int* bm, int*
 int mixdq_igemm_select_id(int64_t M, int N, int k_align, int k_total);
 /* The same for a packed-W4 weight operand (MIXDQ_FLAG_W4); -1 = invalid (k_align % 32 != 0). */
 int mixdq_igemm_select_id_w4(int64_t M, int N, int k_align, int k_total);
+/* The same for a packed-W2 weight operand (MIXDQ_FLAG_W2); -1 = invalid (K % 64 != 0).  Never one of the
+ * ids W2 cannot take (27, 42, 43, 44, 45, 56). */
+int mixdq_igemm_select_id_w2(int64_t M, int N, int k_align, int k_total);
 /* The same for the GEMM + GEGLU + quantize launch (mixdq_qlinear_w8a8_geglu), whose tiles hold whole
  * 32-column value | gate groups (BN % 32 == 0); from 1.5 workgroups of 256x256 per CU on it runs on the
  * four-phase 256x256 tile (id 70) like a plain Linear. */
 int mixdq_igemm_select_id_geglu(int64_t M, int N, int k_total, int w4);
+/* ... and for the GEMM + GEGLU launch on packed-W2 weights; -1 = invalid (N % 32 or K % 64 != 0). */
+int mixdq_igemm_select_id_geglu_w2(int64_t M, int N, int k_total);
 
 /* Tile id of the LDS-resident-halo kernel (csrc/iconv.hip) that mixdq_qconv2d_w8a8[_table] runs this
  * INT8 conv on when no tile is forced -- 90: 8 x 16 output pixels x 80 channels per workgroup, 91:

@@ -73,12 +73,22 @@ _lib.mixdq_igemm_select_id_w4.restype = _i32
 
 _lib.mixdq_igemm_select_id_geglu.argtypes = [_i64, _i32, _i32, _i32]
 _lib.mixdq_igemm_select_id_geglu.restype = _i32
+_lib.mixdq_igemm_select_id_w2.argtypes = [_i64, _i32, _i32, _i32]
+_lib.mixdq_igemm_select_id_w2.restype = _i32
+_lib.mixdq_igemm_select_id_geglu_w2.argtypes = [_i64, _i32, _i32]
+_lib.mixdq_igemm_select_id_geglu_w2.restype = _i32
 
 
 def igemm_select_id(M: int, N: int, k_align: int, k_total: int = 0, w4: bool = False,
-                    geglu: bool = False) -> int:
+                    geglu: bool = False, w2: bool = False) -> int:
     """Configuration id (IGEMM_CONFIGS key) the automatic choice makes for this problem
-    (`w4`: for packed 4-bit weights, MIXDQ_FLAG_W4; `geglu`: for the GEMM + GEGLU launch)."""
+    (`w4` / `w2`: for packed 4- / 2-bit weights, MIXDQ_FLAG_W4 / _W2; `geglu`: for the GEMM + GEGLU
+    launch)."""
+    _check(not (w4 and w2), "w4 and w2 are exclusive")
+    if w2:
+        if geglu:
+            return int(_lib.mixdq_igemm_select_id_geglu_w2(M, N, k_total or k_align))
+        return int(_lib.mixdq_igemm_select_id_w2(M, N, k_align, k_total or k_align))
     if geglu:
         return int(_lib.mixdq_igemm_select_id_geglu(M, N, k_total or k_align, int(w4)))
     if w4:
@@ -122,7 +132,23 @@ IGEMM_WAVES = {1: (2, 2, 1, 32), 3: (2, 2, 1, 32), 4: (2, 2, 1, 32), 13: (4, 2, 
                56: (4, 1, 2, 16), 70: (2, 4, 1, 16), 71: (2, 4, 1, 16)}
 
 FLAG_W4 = 2   # MIXDQ_FLAG_W4: the weight tensor holds packed signed 4-bit values
+FLAG_W2 = 16  # MIXDQ_FLAG_W2: the weight tensor holds packed signed 2-bit values ([N, K/4])
 FLAG_UPSAMPLE2X = 4   # MIXDQ_FLAG_UPSAMPLE2X: the conv input is read through a nearest 2x upsampling
+# configuration ids a packed-W2 launch cannot take (the weight stage is not whole 1-KiB pieces; 27: see
+# csrc/igemm.hip w2_tile_ok)
+W2_INADMISSIBLE = (27, 42, 43, 44, 45, 56)
+
+
+def _wflag(w4, w2):
+    """MIXDQ_FLAG_W4 / _W2 for a launch on packed weights (never both)."""
+    _check(not (w4 and w2), "_w4 and _w2 are exclusive")
+    return FLAG_W2 if w2 else FLAG_W4 if w4 else 0
+
+
+def _kmul(w4, w2):
+    """Weights per stored byte: K = weight.size(1) * _kmul(...)."""
+    return 4 if w2 else 2 if w4 else 1
+
 
 # Rounding variant of the fused multiply-adds (SURVEY.md Appendix B): "A" (default) = FMA,
 # "B" = separate multiply and add.  Read once at import; no other global state.
@@ -132,10 +158,17 @@ FLAGS = 1 if os.environ.get("MIXDQ_EPILOGUE_VARIANT", "A").upper() == "B" else 0
 # Launch recorder (measurement only: bench.py's roofline leg, tools/).  While `RECORD` is a list,
 # every INT8 GEMM / conv entry point appends (name, (M, N, K, k_align), w4, replay) to it, where
 # replay() re-issues the very same launch on the same device tensors.  None = off (the default).
+# Each entry is a Launch: that 4-tuple, plus `.wbits` -- 8, 4 or 2, the stored weight width (a W2 launch
+# records w4 = False; its `.wbits` tells it apart).
 RECORD = None
 
 
-def _record(name, M, N, K, k_align, w4, fn, args, kwargs):
+class Launch(tuple):
+    """(name, (M, N, K, k_align), w4, replay) with the stored weight width as `.wbits`."""
+    wbits = 8
+
+
+def _record(name, M, N, K, k_align, w4, fn, args, kwargs, w2=False):
     if RECORD is None:
         return
     def replay():
@@ -145,7 +178,9 @@ def _record(name, M, N, K, k_align, w4, fn, args, kwargs):
             return fn(*args, **kwargs)
         finally:
             RECORD = saved
-    RECORD.append((name, (int(M), int(N), int(K), int(k_align)), bool(w4), replay))
+    entry = Launch((name, (int(M), int(N), int(K), int(k_align)), bool(w4), replay))
+    entry.wbits = 2 if w2 else 4 if w4 else 8
+    RECORD.append(entry)
 
 
 class PrefetchContext:
@@ -278,7 +313,7 @@ def quantize_per_tensor_to_int8_vectorized(input, scale_inv, zero_point):
 def qlinear_w8_a8_ohalf(input_int8, weight_int8, weight_scale, input_scale, input_zero_point,
                         weight_sum_by_input_channels, scale, bias0, bias=None, *,
                         _out=None, _row_map=None, _cfg=0, _residual=None, _residual_div=1,
-                        _w4=False):
+                        _w4=False, _w2=False):
     _trace_w(weight_int8)
     _check(input_int8.is_cuda, "Input should be on GPU.")
     dev = input_int8.device
@@ -305,7 +340,8 @@ def qlinear_w8_a8_ohalf(input_int8, weight_int8, weight_scale, input_scale, inpu
         _check(bias.dtype == torch.float16, "Currently only support bias with float16 type")
     _check(scale.dtype == torch.float32 and bias0.dtype == torch.float32,
            "scale and bias0 should be float32")
-    N, K = weight_int8.size(0), weight_int8.size(1) * (2 if _w4 else 1)   # _w4: packed nibbles
+    wflag = _wflag(_w4, _w2)
+    N, K = weight_int8.size(0), weight_int8.size(1) * _kmul(_w4, _w2)   # _w4 / _w2: packed
     _check(weight_scale.numel() == N,
            "The size of the weight_scale vector should be equal to output_channels.")
     _check(weight_sum_by_input_channels.numel() == N,
@@ -334,12 +370,12 @@ def qlinear_w8_a8_ohalf(input_int8, weight_int8, weight_scale, input_scale, inpu
             (input_int8, weight_int8, weight_scale, input_scale, input_zero_point,
              weight_sum_by_input_channels, scale, bias0, bias),
             dict(_out=_out, _row_map=_row_map, _cfg=_cfg, _residual=_residual,
-                 _residual_div=_residual_div, _w4=_w4))
+                 _residual_div=_residual_div, _w4=_w4, _w2=_w2), w2=_w2)
     with torch.cuda.device(dev):
         code = _lib.mixdq_qlinear_w8a8_rows(a.data_ptr(), w.data_ptr(), b0.data_ptr(),
                                             sc.data_ptr(), _ptr(bs), D.data_ptr(), M, N, K,
                                             rm[0], rm[1], rm[2], _ptr(_residual), _residual_div,
-                                            FLAGS | (_cfg << 8) | (FLAG_W4 if _w4 else 0),
+                                            FLAGS | (_cfg << 8) | wflag,
                                             _stream())
     _status(code, "qlinear_w8_a8_ohalf")
     return D
@@ -395,8 +431,13 @@ def _rows_view(x: torch.Tensor, K: int):
     return M, lda, lead
 
 
-def qlinear_f16in_supported(x: torch.Tensor, N: int, K: int, *, w4: bool = False, bos: bool = False) -> bool:
-    """True if qlinear_f16in takes `x` (fp16 [..., K]; bos: [B, T, K] whose tokens 1.. are the operand)."""
+def qlinear_f16in_supported(x: torch.Tensor, N: int, K: int, *, w4: bool = False, bos: bool = False,
+                            w2: bool = False) -> bool:
+    """True if qlinear_f16in takes `x` (fp16 [..., K]; bos: [B, T, K] whose tokens 1.. are the operand).
+    Packed-W2 weights (`w2`): never -- the quantizing family is not built for them; the caller quantizes
+    and runs the GEMM."""
+    if w2:
+        return False
     if not (x.is_cuda and x.dtype == torch.float16 and x.data_ptr() % 16 == 0):
         return False
     if bos:
@@ -411,10 +452,11 @@ def qlinear_f16in_supported(x: torch.Tensor, N: int, K: int, *, w4: bool = False
     return bool(_lib.mixdq_qlinear_f16in_supported(M, N, K, lda, M, int(w4)))
 
 
-def qlinear_f16in_wanted(x: torch.Tensor, N: int, K: int, *, w4: bool = False, bos: bool = False) -> bool:
+def qlinear_f16in_wanted(x: torch.Tensor, N: int, K: int, *, w4: bool = False, bos: bool = False,
+                         w2: bool = False) -> bool:
     """What the modules ask: fuse this layer's quantize into its GEMM?  Supported, and -- under the default
     MIXDQ_F16IN=auto -- expected to be cheaper than the two launches (mixdq_qlinear_f16in_preferred)."""
-    if F16IN == "0" or not qlinear_f16in_supported(x, N, K, w4=w4, bos=bos):
+    if F16IN == "0" or not qlinear_f16in_supported(x, N, K, w4=w4, bos=bos, w2=w2):
         return False
     if F16IN == "1":
         return True
@@ -423,7 +465,8 @@ def qlinear_f16in_wanted(x: torch.Tensor, N: int, K: int, *, w4: bool = False, b
 
 
 def qlinear_f16in(input_f16, scale_inv, zero_point, weight_int8, scale, bias0, bias=None, *,
-                  _out=None, _bos=False, _cfg=0, _residual=None, _residual_div=1, _w4=False, _trace=None):
+                  _out=None, _bos=False, _cfg=0, _residual=None, _residual_div=1, _w4=False, _trace=None,
+                  _w2=False):
     """quantize_per_tensor_to_int8(input, scale_inv, zero_point) -> qlinear_w8_a8_ohalf(...) in ONE launch
     (bit-identical to the pair).  `input_f16`: fp16 [..., K] readable in place as rows a constant stride
     apart; `_bos`: input is [B, T, K] and tokens 1.. are the operand, written to rows 1.. of `_out`
@@ -442,7 +485,8 @@ def qlinear_f16in(input_f16, scale_inv, zero_point, weight_int8, scale, bias0, b
     _check(weight_int8.dtype == torch.int8, "weight_int8 should be int8 type")
     _check(scale.dtype == torch.float32 and bias0.dtype == torch.float32,
            "scale and bias0 should be float32")
-    N, K = weight_int8.size(0), weight_int8.size(1) * (2 if _w4 else 1)
+    wflag = _wflag(_w4, _w2)
+    N, K = weight_int8.size(0), weight_int8.size(1) * _kmul(_w4, _w2)
     _check(scale.numel() == N and bias0.numel() == N,
            "The size of scale and bias0 should be equal to output_channels.")
     if bias is not None:
@@ -472,13 +516,13 @@ def qlinear_f16in(input_f16, scale_inv, zero_point, weight_int8, scale, bias0, b
     _record("linear_f16in", M, N, K, K, _w4, qlinear_f16in,
             (input_f16, scale_inv, zero_point, weight_int8, scale, bias0, bias),
             dict(_out=_out, _bos=_bos, _cfg=_cfg, _residual=_residual, _residual_div=_residual_div,
-                 _w4=_w4))
+                 _w4=_w4, _w2=_w2), w2=_w2)
     with torch.cuda.device(dev):
         code = _lib.mixdq_qlinear_f16in_w8a8(
             input_f16.data_ptr(), lda, scale_inv.data_ptr(), zero_point.data_ptr(), w.data_ptr(),
             b0.data_ptr(), sc.data_ptr(), _ptr(bs), D.data_ptr(), M, N, K, rm[0], rm[1], rm[2],
             _ptr(_residual), _residual_div,
-            FLAGS | flags | (_cfg << 8) | (FLAG_W4 if _w4 else 0), _stream())
+            FLAGS | flags | (_cfg << 8) | wflag, _stream())
     _status(code, "qlinear_f16in")
     return D
 
@@ -491,12 +535,19 @@ class GemmGroupTable:
     """Device array of `mixdq_gemm_group` members (include/mixdq_hip.h) for qlinear_grouped.
     members: iterable of (weight_int8 [N, K], bias0 [N], scale [N], bias fp16 [N] or None,
     out fp16 tensor whose data_ptr() is the member's output base).  The table keeps references to
-    every tensor it points at; `key` identifies the storage it was built for."""
+    every tensor it points at; `key` identifies the storage it was built for.  `wbits`: how every
+    member's weight is stored -- 8 (int8), 4 (packed W4, [N, K/2]) or 2 (packed W2, [N, K/4]);
+    `w4=True` is the older spelling of wbits=4."""
 
-    def __init__(self, members, w4=False):
+    def __init__(self, members, w4=False, wbits=None):
         import numpy as np
         self.members = [tuple(m) for m in members]
-        self.w4 = bool(w4)
+        if wbits is None:
+            wbits = 4 if w4 else 8
+        _check(wbits in (8, 4, 2) and not (w4 and wbits != 4), "wbits: 8, 4 or 2")
+        self.wbits = int(wbits)
+        self.w4 = self.wbits == 4
+        self.w2 = self.wbits == 2
         rows, keep = [], []
         for w, b0, sc, bias, out in self.members:
             _check(w.is_cuda and w.dtype == torch.int8 and w.is_contiguous(), "member weight: int8")
@@ -518,7 +569,7 @@ class GemmGroupTable:
             rows.append([w.data_ptr(), b0.data_ptr(), sc.data_ptr(),
                          0 if bias is None else bias.data_ptr(), out.data_ptr(), N])
         self._keep = keep
-        self.K = self.members[0][0].size(1) * (2 if w4 else 1)
+        self.K = self.members[0][0].size(1) * (8 // self.wbits)
         _check(all(m[0].size(1) == self.members[0][0].size(1) for m in self.members),
                "members of a grouped launch share K")
         self.max_N = max(r[5] for r in rows)
@@ -538,11 +589,11 @@ def qlinear_grouped(input_int8, table: "GemmGroupTable", *, _row_map=None, _cfg=
     rm = _row_map or (0, 0, 0)
     _record("linear_grouped", M, sum(m[0].size(0) for m in table.members), table.K, table.K,
             table.w4, qlinear_grouped,
-            (input_int8, table), dict(_row_map=_row_map, _cfg=_cfg))
+            (input_int8, table), dict(_row_map=_row_map, _cfg=_cfg), w2=table.w2)
     with torch.cuda.device(a.device):
         code = _lib.mixdq_qlinear_w8a8_grouped(a.data_ptr(), table.table.data_ptr(), table.n, M,
                                                table.max_N, table.K, rm[0], rm[1], rm[2],
-                                               FLAGS | (_cfg << 8) | (FLAG_W4 if table.w4 else 0),
+                                               FLAGS | (_cfg << 8) | _wflag(table.w4, table.w2),
                                                _stream())
     _status(code, "qlinear_grouped")
 
@@ -560,7 +611,7 @@ def qlinear_attention_supported(x_shape, N, K, k) -> bool:
 
 
 def qlinear_attention(input_int8, weight_int8, scale, bias0, k, v, scale_inv=None, zero_point=None,
-                      softmax_scale=None, *, _w4=False):
+                      softmax_scale=None, *, _w4=False, _w2=False):
     """attn2.to_q (INT8 GEMM, no bias) and the cross-attention core in one launch
     (mixdq_qlinear_w8a8_attn): input int8 [B, T, K], weight [N, K], k / v fp16 [B, Tkv <= 128, N]
     with unit stride along N.  Returns the attention output [B, T, N]: int8 (to_out.0's operand)
@@ -570,7 +621,8 @@ def qlinear_attention(input_int8, weight_int8, scale, bias0, k, v, scale_inv=Non
     _check(input_int8.is_cuda and input_int8.dtype == torch.int8 and input_int8.dim() == 3,
            "input_int8 should be an int8 [B, T, K] GPU tensor")
     _check(weight_int8.dtype == torch.int8, "weight_int8 should be int8 type")
-    N, K = weight_int8.size(0), weight_int8.size(1) * (2 if _w4 else 1)
+    wflag = _wflag(_w4, _w2)
+    N, K = weight_int8.size(0), weight_int8.size(1) * _kmul(_w4, _w2)
     B, T, _ = input_int8.shape
     _check(input_int8.size(-1) == K, "The last dimension of input and weight should match")
     for t, n in ((k, "k"), (v, "v")):
@@ -586,13 +638,13 @@ def qlinear_attention(input_int8, weight_int8, scale, bias0, k, v, scale_inv=Non
     ss = float(softmax_scale) if softmax_scale is not None else 0.125
     _record("linear_attn", B * T, N, K, K, _w4, qlinear_attention,
             (input_int8, weight_int8, scale, bias0, k, v, scale_inv, zero_point, softmax_scale),
-            dict(_w4=_w4))
+            dict(_w4=_w4, _w2=_w2), w2=_w2)
     with torch.cuda.device(a.device):
         code = _lib.mixdq_qlinear_w8a8_attn(
             a.data_ptr(), w.data_ptr(), b0.data_ptr(), sc.data_ptr(), k.data_ptr(), v.data_ptr(),
             out.data_ptr(), B * T, N, K, T, k.shape[1], k.stride(0), k.stride(1), v.stride(0),
             v.stride(1), ss, _ptr(scale_inv), _ptr(zero_point),
-            FLAGS | (FLAG_W4 if _w4 else 0), _stream())
+            FLAGS | wflag, _stream())
     _status(code, "qlinear_attention")
     return out
 
@@ -636,14 +688,15 @@ def geglu_row_order(D: int, device=None) -> torch.Tensor:
 
 
 def qlinear_geglu(input_int8, weight_int8, scale, bias0, bias, out_scale_inv, out_zero_point, *,
-                  _cfg=0, _w4=False, _out=None):
+                  _cfg=0, _w4=False, _out=None, _w2=False):
     """int8 [..., K] x value/gate-interleaved W [2D, K] -> int8 [..., D]: ff.net.0.proj + GEGLU +
     the quantizer of ff.net.2 in one launch (include/mixdq_hip.h: mixdq_qlinear_w8a8_geglu).
     `_out`: a contiguous int8 tensor of the result's size to write into (8-byte aligned)."""
     _trace_w(weight_int8)
     _check(input_int8.is_cuda and input_int8.dtype == torch.int8, "input_int8 should be int8 on GPU")
     _check(weight_int8.dtype == torch.int8, "weight_int8 should be int8 type")
-    N, K = weight_int8.size(0), weight_int8.size(1) * (2 if _w4 else 1)
+    wflag = _wflag(_w4, _w2)
+    N, K = weight_int8.size(0), weight_int8.size(1) * _kmul(_w4, _w2)
     _check(input_int8.size(-1) == K, "The last dimension of input and weight should match")
     _check(scale.numel() == N and bias0.numel() == N, "scale and bias0 should have 2D elements")
     a, w = input_int8.contiguous(), weight_int8.contiguous()
@@ -656,12 +709,12 @@ def qlinear_geglu(input_int8, weight_int8, scale, bias0, bias, out_scale_inv, ou
     bs = None if bias is None else bias.contiguous()
     _record("linear_geglu", M, N, K, K, _w4, qlinear_geglu,
             (input_int8, weight_int8, scale, bias0, bias, out_scale_inv, out_zero_point),
-            dict(_cfg=_cfg, _w4=_w4))
+            dict(_cfg=_cfg, _w4=_w4, _w2=_w2), w2=_w2)
     with torch.cuda.device(a.device):
         code = _lib.mixdq_qlinear_w8a8_geglu(a.data_ptr(), w.data_ptr(), b0.data_ptr(),
                                              sc.data_ptr(), _ptr(bs), out.data_ptr(), M, N, K,
                                              _ptr(out_scale_inv), _ptr(out_zero_point),
-                                             FLAGS | (_cfg << 8) | (FLAG_W4 if _w4 else 0),
+                                             FLAGS | (_cfg << 8) | wflag,
                                              _stream())
     _status(code, "qlinear_geglu")
     return out

@@ -308,8 +308,45 @@ inline int select_cfg_w4(int64_t M, int N, int Ktot, bool whole64 = false) {
   return Ktot >= 2048 ? 37 : 4;
 }
 
-template <bool CONV, bool W4>
+// Packed-W2 weights (MIXDQ_FLAG_W2): a tile takes them when its weight stage is whole 1-KiB DMA pieces at a
+// quarter of the bytes (BN * BK / 4 % 1024 == 0) -- not the 80- / 240-column tiles 42, 43, 44, 45, 56 -- and
+// not tile 27 (128x320 on 8 x 2 waves of 16x16x64): its W2 instantiation needs 8-12 bytes of scratch where the
+// W8 and W4 ones need none, and the packed-weight rules never choose it (25 / 28 are the same tile shape).
+constexpr bool w2_tile_ok(int id, int bn, int bk) { return (bn * bk / 4) % 1024 == 0 && id != 27; }
+inline bool w2_cfg_ok(int id) {
+  for (const TileCfg& c : kTileCfgs)
+    if (c.id == id) return w2_tile_ok(c.id, c.bn, c.bk);
+  return false;
+}
+
+// Tuned on the 2-bit Linear families of weight_4.00 at batch 1 and 8 (tools/bench_w2.py --sweep: every tile W2
+// takes, graph-timed launches; profiles/w2_sweep.json).  Three rules of the W8 choice that the W4 rule drops pay
+// for W2, whose unpack is one dword per fragment: the exact-fit 128x320 tile on 4 x 4 waves of 32x80 for long K
+// ((8192, 1280, 5120) 53.9 vs 66.5 us on 128x128, (8192, 1280, 1280) 19.1 vs 23.3, (32768, 640, 2560) 59.6 vs
+// 70.2), 128x128 on three stages for short K and few columns ((32768, 640, 640) 24.3 vs 25.5 on 256x128x64), and
+// 64x128 for the M = 1024 layers up to K = 6144 ((1024, 1280, 5120) 15.7 vs 16.4 on the k-split 64x64).  Then
+// the W4 rule, with the tiles W2 does not take mapped: 128x80 -> 64x64x128 ((4096, 640, 2560) 12.9 vs 17.9 on
+// 128x128x64), 128x320 on 8 x 2 waves -> the same tile on 8 waves of 32x32, the 64x80 / 64x240 tiles -> 64x128.
+// MIXDQ_IGEMM_TUNE applies (its admissible entries; an inadmissible one is mapped the same way).
+inline int select_cfg_w2(int64_t M, int N, int Ktot, bool whole64 = false) {
+  if (const int c = tuned_cfg(M, N, Ktot, whole64)) if (w2_cfg_ok(c)) return c;
+  auto blocks = [&](int tm, int tn) {
+    return ((M + tm - 1) / tm) * (int64_t)((N + tn - 1) / tn);
+  };
+  const int64_t b320 = blocks(128, 320);
+  if (!whole64 && N % 320 == 0 && Ktot % 128 == 0 && Ktot >= 1024 && (b320 == kNumCU || b320 == 2 * kNumCU))
+    return 28;
+  if (!whole64 && Ktot <= 640 && N <= 640 && blocks(128, 128) >= 4 * kNumCU) return 35;
+  if (!whole64 && blocks(64, 64) < 2 * kNumCU && Ktot > 2048 && Ktot <= 6144 && N % 128 == 0) return 41;
+  const int c = select_cfg_w4(M, N, Ktot, whole64);
+  if (w2_cfg_ok(c)) return c;
+  return c == 44 ? 4 : c == 27 ? 25 : 41;
+}
+
+template <bool CONV, int WBITS>
 int dispatch(IgemmParams& p, hipStream_t stream, int forced_cfg) {
+  constexpr bool W4 = WBITS == 4, W2 = WBITS == 2;
+  static_assert(!(CONV && W2), "packed W2 is a Linear format");
   if (p.M <= 0 || p.N <= 0) return MIXDQ_OK;
   const int align_k = CONV ? p.C : p.Ktot;
   if (align_k % 4 != 0 || p.N % 4 != 0) return MIXDQ_ERR_ALIGNMENT;
@@ -317,7 +354,9 @@ int dispatch(IgemmParams& p, hipStream_t stream, int forced_cfg) {
                       ((uintptr_t)p.D % 16 == 0) && ((uintptr_t)p.scale % 16 == 0) &&
                       ((uintptr_t)p.bias0 % 16 == 0) && ((uintptr_t)p.table % 16 == 0) &&
                       ((uintptr_t)p.bias % 8 == 0) && ((uintptr_t)p.res % 16 == 0);
-  if constexpr (W4) {
+  if constexpr (W2) {
+    if (align_k % 64 != 0 || !ptr_ok) return MIXDQ_ERR_W2_SHAPE;   // packed pieces span 64 k
+  } else if constexpr (W4) {
     if (align_k % 32 != 0 || !ptr_ok) return MIXDQ_ERR_W4_SHAPE;   // packed pieces span 32 k
   } else {
     if (align_k % 16 != 0 || !ptr_ok) {
@@ -332,17 +371,22 @@ int dispatch(IgemmParams& p, hipStream_t stream, int forced_cfg) {
                          (uint64_t)p.M * (uint64_t)p.Ktot < (1ull << 32) &&
                          (uint64_t)p.N * (uint64_t)p.Ktot < (1ull << 32);
   const int cfg = forced_cfg > 0 ? forced_cfg
-                                 : (W4 ? select_cfg_w4(p.M, p.N, p.Ktot, whole64)
-                                       : select_cfg(p.M, p.N, p.Ktot, whole64, phased_ok));
+                                 : (W2 ? select_cfg_w2(p.M, p.N, p.Ktot, whole64)
+                                       : W4 ? select_cfg_w4(p.M, p.N, p.Ktot, whole64)
+                                            : select_cfg(p.M, p.N, p.Ktot, whole64, phased_ok));
   // the four-phase 256 x 256 tile as ONE workgroup per CU walking its tiles (csrc/igemm_pp.h: the next tile's first
   // K-tile lands under the current tile's epilogue; same arithmetic, same bits) wherever a CU has more than one tile
-  if constexpr (!CONV && !W4) {
+  if constexpr (!CONV && WBITS == 8) {
     if (cfg == 71 && phased_ok && pp_ok(p))
       return whole64 ? launch_pp<true>(p, stream) : launch_pp<false>(p, stream);
   }
   switch (cfg) {
 #define X(ID, BM, BN, BK, ST, WM, WN, KS, MT, PH) \
-  case ID: return launch_tile<BM, BN, BK, ST, WM, WN, CONV, W4, KS, MT, false, PH>(p, stream);
+  case ID:                                                                                         \
+    if constexpr (!W2 || w2_tile_ok(ID, BN, BK))                                                   \
+      return launch_tile<BM, BN, BK, ST, WM, WN, CONV, WBITS, KS, MT, false, PH>(p, stream);       \
+    else                                                                                           \
+      return MIXDQ_ERR_W2_SHAPE;
     MIXDQ_IGEMM_CONFIGS(X)
 #undef X
     default: return MIXDQ_ERR_INVALID_ARG;
@@ -351,14 +395,14 @@ int dispatch(IgemmParams& p, hipStream_t stream, int forced_cfg) {
 
 // to_q GEMM + cross-attention epilogue: the 64x128x128 8-wave tile (two heads per tile), Linear
 // fast path only.
-template <bool W4>
+template <int WBITS>
 int launch_att(IgemmParams& p, hipStream_t stream) {
   constexpr int BM = 64, BN = 128, BK = 128, ST = 3;
   constexpr int SMEM = ((igemm_smem_bytes<BM, BN, BK, ST>() + 1023) / 1024) * 1024 + 4 * kStageBytes;
   static_assert(SMEM <= 160 * 1024, "LDS is 160 KiB per CU");
   static bool seen[64] = {};
   if (const int st = lds_opt_in(
-          reinterpret_cast<const void*>(&igemm_kernel<BM, BN, BK, ST, 2, 4, false, true, W4, 1, 32, false, true>),
+          reinterpret_cast<const void*>(&igemm_kernel<BM, BN, BK, ST, 2, 4, false, true, WBITS, 1, 32, false, true>),
           SMEM, seen))
     return st;
   p.tiles_m = (int)((p.M + BM - 1) / BM);
@@ -366,7 +410,7 @@ int launch_att(IgemmParams& p, hipStream_t stream) {
   p.gm = tile_map_gm();
   const int64_t grid = (int64_t)p.tiles_m * p.tiles_n;
   if (grid <= 0 || grid > 0x7fffffff || p.tiles_m >= (1 << 24)) return MIXDQ_ERR_INVALID_ARG;
-  igemm_kernel<BM, BN, BK, ST, 2, 4, false, true, W4, 1, 32, false, true>
+  igemm_kernel<BM, BN, BK, ST, 2, 4, false, true, WBITS, 1, 32, false, true>
       <<<dim3((unsigned)grid), 512, SMEM, stream>>>(MIXDQ_IGEMM_HEAD_ARGS(p) p);
   return launch_status();
 }
@@ -381,12 +425,16 @@ int launch_att(IgemmParams& p, hipStream_t stream) {
   X(41, 64, 128, 128, 3, 2, 4, 1, 32)     \
   X(56, 64, 80, 128, 6, 4, 1, 2, 16)
 
-template <bool W4>
+template <int WBITS>
 int dispatch_grouped(IgemmParams& p, int ngroups, hipStream_t stream, int cfg) {
   p.ngroups_launch = ngroups;
   switch (cfg) {
-#define X(ID, BM, BN, BK, ST, WM, WN, KS, MT) \
-  case ID: return launch_tile<BM, BN, BK, ST, WM, WN, false, W4, KS, MT, false, false, true>(p, stream);
+#define X(ID, BM, BN, BK, ST, WM, WN, KS, MT)                                                     \
+  case ID:                                                                                         \
+    if constexpr (WBITS != 2 || w2_tile_ok(ID, BN, BK))                                            \
+      return launch_tile<BM, BN, BK, ST, WM, WN, false, WBITS, KS, MT, false, false, true>(p, stream); \
+    else                                                                                           \
+      return MIXDQ_ERR_W2_SHAPE;
     MIXDQ_GROUPED_CONFIGS(X)
 #undef X
     default: return MIXDQ_ERR_INVALID_ARG;
@@ -480,7 +528,7 @@ int dispatch_f16(IgemmParams& p, hipStream_t stream, int forced_cfg) {
   const int cfg = forced_cfg > 0 ? forced_cfg : select_cfg_f16(p.M, p.N, p.Ktot);
   switch (cfg) {
 #define X(ID, BM, BN, BK, ST, WM, WN, KS, MT) \
-  case ID: return launch_tile<BM, BN, BK, ST, WM, WN, CONV, false, KS, MT, true>(p, stream);
+  case ID: return launch_tile<BM, BN, BK, ST, WM, WN, CONV, 8, KS, MT, true>(p, stream);
     MIXDQ_F16_CONFIGS(X)
 #undef X
     default: return MIXDQ_ERR_INVALID_ARG;
@@ -511,8 +559,10 @@ extern "C" int mixdq_qlinear_w8a8_rows(const int8_t* A, const int8_t* W, const f
   p.res_div = residual_row_div > 0 ? residual_row_div : 1;
   if (p.res && group_rows > 0) return MIXDQ_ERR_ROWMAP_RESIDUAL;   // residual rows follow m, not D_row
   p.unfused = (flags & MIXDQ_FLAG_UNFUSED) ? 1 : 0;
-  if (flags & MIXDQ_FLAG_W4) return dispatch<false, true>(p, (hipStream_t)stream, (flags >> 8) & 0xff);
-  return dispatch<false, false>(p, (hipStream_t)stream, (flags >> 8) & 0xff);
+  if ((flags & MIXDQ_FLAG_W4) && (flags & MIXDQ_FLAG_W2)) return MIXDQ_ERR_INVALID_ARG;
+  if (flags & MIXDQ_FLAG_W2) return dispatch<false, 2>(p, (hipStream_t)stream, (flags >> 8) & 0xff);
+  if (flags & MIXDQ_FLAG_W4) return dispatch<false, 4>(p, (hipStream_t)stream, (flags >> 8) & 0xff);
+  return dispatch<false, 8>(p, (hipStream_t)stream, (flags >> 8) & 0xff);
 }
 
 extern "C" int mixdq_qlinear_w8a8_geglu(const int8_t* A, const int8_t* W, const float* bias0,
@@ -525,6 +575,7 @@ extern "C" int mixdq_qlinear_w8a8_geglu(const int8_t* A, const int8_t* W, const 
   if (!A || !W || !bias0 || !scale || !out_i8 || !out_scale_inv || !out_zero_point)
     return MIXDQ_ERR_INVALID_ARG;
   // whole value/gate groups per tile, the LDS-DMA kernels only, 8-byte output stores
+  if ((flags & MIXDQ_FLAG_W4) && (flags & MIXDQ_FLAG_W2)) return MIXDQ_ERR_INVALID_ARG;
   if (N % 32 != 0 || K % 16 != 0 || ((uintptr_t)out_i8 & 7)) return MIXDQ_ERR_GEGLU_SHAPE;
   if (((uintptr_t)A | (uintptr_t)W | (uintptr_t)scale | (uintptr_t)bias0) & 15)
     return MIXDQ_ERR_GEGLU_SHAPE;
@@ -537,8 +588,9 @@ extern "C" int mixdq_qlinear_w8a8_geglu(const int8_t* A, const int8_t* W, const 
   p.H = p.W = p.P = p.Q = 1; p.C = K; p.R = p.S = 1; p.stride = 1; p.pad = 0;
   p.res_div = 1;
   p.unfused = (flags & MIXDQ_FLAG_UNFUSED) ? 1 : 0;
-  if (flags & MIXDQ_FLAG_W4) return dispatch<false, true>(p, (hipStream_t)stream, (flags >> 8) & 0xff);
-  return dispatch<false, false>(p, (hipStream_t)stream, (flags >> 8) & 0xff);
+  if (flags & MIXDQ_FLAG_W2) return dispatch<false, 2>(p, (hipStream_t)stream, (flags >> 8) & 0xff);
+  if (flags & MIXDQ_FLAG_W4) return dispatch<false, 4>(p, (hipStream_t)stream, (flags >> 8) & 0xff);
+  return dispatch<false, 8>(p, (hipStream_t)stream, (flags >> 8) & 0xff);
 }
 
 extern "C" int mixdq_qlinear_w8a8_grouped(const int8_t* A, const mixdq_gemm_group* groups_device,
@@ -548,7 +600,9 @@ extern "C" int mixdq_qlinear_w8a8_grouped(const int8_t* A, const mixdq_gemm_grou
   if (M < 0 || max_N < 0 || K < 0 || ngroups < 0) return MIXDQ_ERR_INVALID_ARG;
   if (M == 0 || max_N == 0 || ngroups == 0) return MIXDQ_OK;
   if (!A || !groups_device || ngroups > 65535) return MIXDQ_ERR_INVALID_ARG;
-  const bool w4 = flags & MIXDQ_FLAG_W4;
+  const bool w4 = flags & MIXDQ_FLAG_W4, w2 = flags & MIXDQ_FLAG_W2;
+  if (w4 && w2) return MIXDQ_ERR_INVALID_ARG;
+  if (w2 && (K % 64 != 0 || max_N % 4 != 0 || ((uintptr_t)A & 15))) return MIXDQ_ERR_W2_SHAPE;
   if (K % (w4 ? 32 : 16) != 0 || max_N % 4 != 0 || ((uintptr_t)A & 15))
     return w4 ? MIXDQ_ERR_W4_SHAPE : MIXDQ_ERR_ALIGNMENT;   // the LDS-DMA kernels only
   IgemmParams p{};
@@ -562,8 +616,9 @@ extern "C" int mixdq_qlinear_w8a8_grouped(const int8_t* A, const mixdq_gemm_grou
   // the members are independent problems: the tile only has to suit one of them, the grid
   // (x ngroups) fills the chip.  M <= 64: 64x64 k-split tiles, else 128x128 (8 waves).
   if (cfg == 0) cfg = M <= 64 ? 37 : 35;
-  return w4 ? dispatch_grouped<true>(p, ngroups, (hipStream_t)stream, cfg)
-            : dispatch_grouped<false>(p, ngroups, (hipStream_t)stream, cfg);
+  return w2 ? dispatch_grouped<2>(p, ngroups, (hipStream_t)stream, cfg)
+       : w4 ? dispatch_grouped<4>(p, ngroups, (hipStream_t)stream, cfg)
+            : dispatch_grouped<8>(p, ngroups, (hipStream_t)stream, cfg);
 }
 
 extern "C" int mixdq_qlinear_w8a8_attn(const int8_t* A, const int8_t* W, const float* bias0,
@@ -579,7 +634,8 @@ extern "C" int mixdq_qlinear_w8a8_attn(const int8_t* A, const int8_t* W, const f
   if (!A || !W || !bias0 || !scale || !k_f16 || !v_f16 || !out) return MIXDQ_ERR_INVALID_ARG;
   if ((out_scale_inv_or_null == nullptr) != (out_zero_point_or_null == nullptr))
     return MIXDQ_ERR_INVALID_ARG;
-  const bool w4 = flags & MIXDQ_FLAG_W4;
+  const bool w4 = flags & MIXDQ_FLAG_W4, w2 = flags & MIXDQ_FLAG_W2;
+  if (w4 && w2) return MIXDQ_ERR_INVALID_ARG;
   // whole head pairs per tile, whole 64-row tiles per image, at most two key tiles, fast staging
   if (N % 128 != 0 || K % 128 != 0 || rows_per_image % 64 != 0 || M % rows_per_image != 0 ||
       tkv > 2 * kKeys || (uint64_t)M * (uint64_t)K >= (1ull << 32) ||
@@ -601,7 +657,8 @@ extern "C" int mixdq_qlinear_w8a8_attn(const int8_t* A, const int8_t* W, const f
   p.att_tkv = tkv; p.att_tq = rows_per_image;
   p.att_scale_log2 = softmax_scale * 1.4426950408889634f;
   p.att_out = out; p.att_sinv = out_scale_inv_or_null; p.att_zp = out_zero_point_or_null;
-  return w4 ? launch_att<true>(p, (hipStream_t)stream) : launch_att<false>(p, (hipStream_t)stream);
+  return w2 ? launch_att<2>(p, (hipStream_t)stream)
+       : w4 ? launch_att<4>(p, (hipStream_t)stream) : launch_att<8>(p, (hipStream_t)stream);
 }
 
 extern "C" int mixdq_qlinear_w8a8(const int8_t* A, const int8_t* W, const float* bias0,
@@ -636,6 +693,7 @@ extern "C" int mixdq_qconv2d_w8a8_table(const int8_t* X, const int8_t* Wt, const
   if (N < 0 || H <= 0 || W <= 0 || C <= 0 || K <= 0 || R <= 0 || S <= 0 || stride <= 0 || pad < 0)
     return MIXDQ_ERR_INVALID_ARG;
   if (!X || !Wt || !scale || !D) return MIXDQ_ERR_INVALID_ARG;
+  if (flags & MIXDQ_FLAG_W2) return MIXDQ_ERR_UNSUPPORTED;   // packed W2 is a Linear format
   if (pad > 0 ? (!table_or_null || !zero_point) : !bias0_or_null) return MIXDQ_ERR_INVALID_ARG;
   // every output pixel's window must overlap the image (border classes are non-empty rectangles)
   if (pad >= R || pad >= S) return MIXDQ_ERR_PADDING;
@@ -683,8 +741,8 @@ extern "C" int mixdq_qconv2d_w8a8_table(const int8_t* X, const int8_t* Wt, const
   p.res = (const __half*)residual_f16_or_null;
   p.res_div = residual_row_div > 0 ? residual_row_div : 1;
   p.unfused = (flags & MIXDQ_FLAG_UNFUSED) ? 1 : 0;
-  if (flags & MIXDQ_FLAG_W4) return dispatch<true, true>(p, (hipStream_t)stream, (flags >> 8) & 0xff);
-  return dispatch<true, false>(p, (hipStream_t)stream, (flags >> 8) & 0xff);
+  if (flags & MIXDQ_FLAG_W4) return dispatch<true, 4>(p, (hipStream_t)stream, (flags >> 8) & 0xff);
+  return dispatch<true, 8>(p, (hipStream_t)stream, (flags >> 8) & 0xff);
 }
 
 extern "C" int mixdq_qconv2d_w8a8(const int8_t* X, const int8_t* Wt, const float* scale,
@@ -742,6 +800,7 @@ extern "C" int mixdq_linear_f16(const void* A_f16, const void* W_f16, const void
   if (M < 0 || N < 0 || K < 0) return MIXDQ_ERR_INVALID_ARG;
   if (M == 0 || N == 0) return MIXDQ_OK;
   if (!A_f16 || !W_f16 || !D_f16) return MIXDQ_ERR_INVALID_ARG;
+  if (flags & MIXDQ_FLAG_W2) return MIXDQ_ERR_UNSUPPORTED;   // FP16 weights
   if ((int64_t)K * 2 > 0x7fffffff) return MIXDQ_ERR_SHAPE;
   IgemmParams p{};
   p.A = (const int8_t*)A_f16; p.Wt = (const int8_t*)W_f16; p.bias = (const __half*)bias_f16_or_null;
@@ -760,6 +819,7 @@ extern "C" int mixdq_conv2d_f16(const void* X_f16, const void* Wt_f16, const voi
   if (N < 0 || H <= 0 || W <= 0 || C <= 0 || K <= 0 || R <= 0 || S <= 0 || stride <= 0 || pad < 0)
     return MIXDQ_ERR_INVALID_ARG;
   if (!X_f16 || !Wt_f16 || !D_f16) return MIXDQ_ERR_INVALID_ARG;
+  if (flags & MIXDQ_FLAG_W2) return MIXDQ_ERR_UNSUPPORTED;   // FP16 weights
   const int P = (H + 2 * pad - (R - 1) - 1) / stride + 1;
   const int Q = (W + 2 * pad - (S - 1) - 1) / stride + 1;
   if (P <= 0 || Q <= 0 || N == 0) return MIXDQ_OK;
@@ -793,6 +853,9 @@ extern "C" const char* mixdq_status_string(int status) {
       return "unsupported configuration (an output row map and a residual cannot be combined)";
     case MIXDQ_ERR_SHAPE:
       return "unsupported configuration (shape outside this fused kernel's range)";
+    case MIXDQ_ERR_W2_SHAPE:
+      return "unsupported configuration (packed 2-bit weights need K % 64 == 0, 16-byte aligned operands "
+             "and a tile that takes them -- not ids 27, 42, 43, 44, 45, 56)";
     default: return "unknown status";
   }
 }
@@ -837,6 +900,16 @@ extern "C" int mixdq_conv_halo_select(int N, int H, int W, int C, int K, int R, 
 extern "C" int mixdq_igemm_select_id_w4(int64_t M, int N, int k_align, int k_total) {
   if (M <= 0 || N <= 0 || k_align % 32 != 0 || N % 4 != 0) return -1;
   return select_cfg_w4(M, N, k_total);
+}
+
+extern "C" int mixdq_igemm_select_id_w2(int64_t M, int N, int k_align, int k_total) {
+  if (M <= 0 || N <= 0 || k_align % 64 != 0 || k_total % 64 != 0 || N % 4 != 0) return -1;
+  return select_cfg_w2(M, N, k_total);
+}
+
+extern "C" int mixdq_igemm_select_id_geglu_w2(int64_t M, int N, int k_total) {
+  if (M <= 0 || N <= 0 || N % 32 != 0 || k_total % 64 != 0) return -1;
+  return select_cfg_w2(M, N, k_total, true);
 }
 
 extern "C" int mixdq_igemm_select_id_geglu(int64_t M, int N, int k_total, int w4) {

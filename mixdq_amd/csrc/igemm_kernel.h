@@ -120,6 +120,14 @@ __device__ __forceinline__ int swz(int row) {
   return BK == 64 ? ((row >> 2) & 3) : BK == 128 ? ((row >> 1) & 7) : (row & 15);
 }
 
+// Packed W2 weights: KSP 16-byte pieces of 64 k per tile row.  The fragment reads are 8-byte reads (bank = 8-byte
+// unit mod 32): 16 consecutive tile rows hit 16 distinct 16-byte slots mod 256 B when the rows that share a 16-slot
+// span keep their pieces in place and the next span swaps them.
+template <int KSP>
+__device__ __forceinline__ int w2_swz(int row) {
+  return (row / (16 / KSP)) & (KSP - 1);
+}
+
 __device__ __forceinline__ void glds16(const void* gsrc, char* lds_wave_base) {
   __builtin_amdgcn_global_load_lds(
       (const __attribute__((address_space(1))) void*)gsrc,
@@ -342,6 +350,21 @@ __device__ __forceinline__ uint32_t add_f16x2(uint32_t a, uint32_t b) {
 //     lo = (w << 4) & 0xF0F0F0F0   -> int8 values 16 * q[8g+4 .. 8g+7]
 // i.e. the MFMA runs on 16*q (still int8, |16 q| <= 128) and the epilogue uses bias0 * 16 and
 // scale / 16 -- power-of-two factors, so every FP32 rounding is that of the unscaled arithmetic.
+// W2 (WBITS = 2): packed signed 2-bit values, "crumb-planar per 16": within every group of 16 consecutive k,
+// byte j (0..3) of the group's dword holds k[16g+j] in bits 7:6, k[16g+4+j] in 5:4, k[16g+8+j] in 3:2 and
+// k[16g+12+j] in 1:0 (two's complement).  A lane's 16-byte DMA piece is 64 k of one row (KSP = BK / 64 pieces
+// per row, swizzled by w2_swz); one 16-k fragment is one packed dword, unpacked in 7 VALU operations with no
+// cross-byte correction:
+//     r0 = w & 0xC0C0C0C0,  r1 = (w << 2) & 0xC0C0C0C0,  r2 = (w << 4) & ...,  r3 = (w << 6) & ...
+// -> int8 values 64 * q (in [-128, 64]) in natural k order (r0 = k[0..3], r1 = k[4..7], ...).  Exactness:
+// (1) the INT32 accumulator is exactly 64 * acc, since |acc| <= K * 128 * 128 < 2^31 for K <= 131072;
+// (2) bias0 * 64 and scale / 64 are power-of-two rescalings, which commute with every FP32 rounding of
+// (f32(acc) - bias0) * scale (+ bias), fused or not, as long as nothing overflows or goes subnormal (the UNet's
+// scale / 64 is ~1e-8, far above the subnormal range).  The fragment is read with a ds_read_b64 of the aligned
+// dword pair that holds it (twice the banks per cycle of ds_read_b32: a 32-row group costs 2-way, a 16-row
+// group of the 16x16x64 tiles is conflict-free).  Shape limits: K % 64 == 0 and whole 1-KiB weight pieces per
+// stage (BN * BK / 4 % 1024 == 0): the 80- / 240-column tiles (ids 42, 43, 44, 45, 56) cannot take W2
+// (nor, by the dispatcher's choice, tile 27: csrc/igemm.hip w2_tile_ok).
 // KSPLIT = 2 (64x64 tiles only): two groups of WM x WN waves share the tile and split every K-tile's
 // k-steps between them; group 1's accumulators are added to group 0's through LDS before the
 // epilogue (int32: exact, order-free).  Twice the waves for the same tile halves the per-K-tile
@@ -387,7 +410,7 @@ __device__ __forceinline__ void aq_wait4(v4i& a, v4i& b, v4i& c, v4i& d) {
                : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(N), "n"(SLOT) : "memory");
 }
 
-template <int BM, int BN, int BK, int STAGES, int WM, int WN, bool CONV, bool FAST, bool W4,
+template <int BM, int BN, int BK, int STAGES, int WM, int WN, bool CONV, bool FAST, int WBITS,
           int KSPLIT = 1, int MT = 32, bool F16 = false, bool ATT = false, bool PHASED = false,
           bool GROUPED = false, bool AQ = false, bool LNQ = false>
 __global__ __launch_bounds__(
@@ -395,8 +418,11 @@ __global__ __launch_bounds__(
     (ATT ? 2 : igemm_waves_per_simd<BM, BN, BK, STAGES, WM * WN * KSPLIT,
                                     (BM / WM / MT) * (BN / WN / MT) * (MT == 32 ? 16 : 4), AQ>()))
 void igemm_kernel(MIXDQ_IGEMM_HEAD_PARAMS const IgemmParams p_in) {
+  // WBITS: bits per stored weight -- 8 (int8), 4 (packed W4) or 2 (packed W2; see the W2 note above)
+  static_assert(WBITS == 8 || WBITS == 4 || WBITS == 2, "weights are stored in 8, 4 or 2 bits");
+  constexpr bool W4 = WBITS == 4, W2 = WBITS == 2;
   static_assert(!PHASED || (BM == 256 && BN == 256 && BK == 128 && STAGES == 2 &&
-                            WM == 2 && WN == 4 && KSPLIT == 1 && MT == 16 && FAST && !CONV && !W4 &&
+                            WM == 2 && WN == 4 && KSPLIT == 1 && MT == 16 && FAST && !CONV && WBITS == 8 &&
                             !F16 && !ATT),
                 "the phased loops are written for the 256x256 tile, 2 x 4 waves of 128x64");
   static_assert(MT == 32 || BK == 128 || PHASED, "the 16x16x64 fragment reads are laid out for 128-byte rows");
@@ -411,7 +437,7 @@ void igemm_kernel(MIXDQ_IGEMM_HEAD_PARAMS const IgemmParams p_in) {
   // ahead of its use; the weights stay on LDS-DMA.  Fragment reads, MFMAs and epilogue are unchanged.
   static_assert(!AQ || (FAST && !CONV && !F16 && !ATT && !PHASED && !GROUPED),
                 "the quantizing activation stage is built for the Linear fast path");
-  static_assert(!LNQ || (FAST && !CONV && !F16 && !ATT && !PHASED && !GROUPED && !AQ && !W4 && BN % 16 == 0),
+  static_assert(!LNQ || (FAST && !CONV && !F16 && !ATT && !PHASED && !GROUPED && !AQ && WBITS == 8 && BN % 16 == 0),
                 "the LayerNorm epilogue is built for the exact-fit Linear tiles");
   // every argument requested at once (common.h): 1.2-2.6 us from wave start to the first DMA before.
   // LATE_ARGS (Linear fast path with preloaded head arguments): the tile map, the per-lane staging offsets
@@ -489,7 +515,7 @@ void igemm_kernel(MIXDQ_IGEMM_HEAD_PARAMS const IgemmParams p_in) {
     nwg = p.tiles_m * p.tiles_n;
     if ((int)blockIdx.x >= nwg) return;   // the grid is sized for the widest member
   }
-  static_assert(!(F16 && W4), "packed weights are an INT8-path format");
+  static_assert(!(F16 && WBITS != 8), "packed weights are an INT8-path format");
   static_assert(MT == 32 || MT == 16, "MFMA shapes: 32x32x32 or 16x16x64");
   constexpr int NWAVES = WM * WN * KSPLIT, NTHREADS = 64 * NWAVES;
   // registers per lane the launch bound leaves this kernel (512 per SIMD lane over the waves per SIMD)
@@ -500,11 +526,11 @@ void igemm_kernel(MIXDQ_IGEMM_HEAD_PARAMS const IgemmParams p_in) {
   constexpr int KSTEP = MT == 32 ? 32 : 64;       // k-values one MFMA consumes
   constexpr int CPS = KSTEP / 16;                 // 16-byte fragment chunks per k-step
   constexpr int ACC = MT == 32 ? 16 : 4;          // accumulator registers per MFMA tile
-  constexpr int WB = W4 ? 2 : 1;                  // weights per stored byte
+  constexpr int WB = 8 / WBITS;                   // weights per stored byte
   constexpr int A_STAGE = BM * BK, B_STAGE = BN * BK / WB, STAGE = A_STAGE + B_STAGE;
   // LDS-DMA pieces (1 KiB = one wave-instruction).  Activations: the same count on every wave.
   // Weights: piece q goes to wave q % NWAVES, so any piece count works (BN = 80, 240, 320; packed
-  // W4 stages of half the bytes); waves below PB % NWAVES issue one more and wait for one more.
+  // W4 / W2 stages of half / a quarter of the bytes); waves below PB % NWAVES issue one more and wait for one more.
   constexpr int A_NI = A_STAGE / 1024 / NWAVES;
   constexpr int PB = B_STAGE / 1024;
   constexpr int B_LO = PB / NWAVES, B_REM = PB % NWAVES, B_NI = B_LO + (B_REM ? 1 : 0);
@@ -671,7 +697,14 @@ void igemm_kernel(MIXDQ_IGEMM_HEAD_PARAMS const IgemmParams p_in) {
     // waves: its state is computed on clamped rows and never used)
     const int byte = (wid + NWAVES * j) * 1024 + lane * 16;
     int row, koff, boff;          // tile row; first k of this lane's 16-byte piece; its byte offset
-    if constexpr (!W4) {
+    if constexpr (W2) {           // packed W2: a 16-byte piece = 64 k-values of a row
+      constexpr int KSP = BK / 64;
+      const int piece = byte >> 4;
+      row = piece / KSP;
+      const int ks = (piece % KSP) ^ w2_swz<KSP>(row);
+      koff = ks * 64;
+      boff = ks * 16;
+    } else if constexpr (!W4) {
       row = byte / BK;
       const int lc = ((byte % BK) >> 4) ^ swz<BK>(row);
       koff = lc * 16;
@@ -888,8 +921,25 @@ void igemm_kernel(MIXDQ_IGEMM_HEAD_PARAMS const IgemmParams p_in) {
       else return __builtin_amdgcn_mfma_i32_16x16x64_i8(w, x, c, 0, 0, 0);
     }
   };
+  // W2: which dword of the 8-byte pair b_rd points at holds this lane's fragment -- dword (c & 1) with
+  // c = ks * CPS + lkq and CPS even, i.e. (lkq & 1) for EVERY fragment of the lane: one lane mask, held in
+  // scalar registers, instead of per-fragment address arithmetic (which kept one more register per fragment
+  // live across the K loop)
+  static_assert(CPS % 2 == 0, "a lane's W2 fragments sit in the same half of their dword pairs");
+  const bool w2_hi = (lkq & 1) != 0;
   auto load_w = [&](const char* S0, int off) -> v4i {
-    if constexpr (!W4) {
+    if constexpr (W2) {
+      // one ds_read_b64 of the 8-byte-aligned pair holding this lane's fragment: twice the banks of a
+      // ds_read_b32 per lane-group cycle (see the W2 note above); the other dword is dropped
+      const uint64_t w2 = *reinterpret_cast<const uint64_t*>(S0 + off);
+      const uint32_t w = w2_hi ? (uint32_t)(w2 >> 32) : (uint32_t)w2;
+      v4i r;
+      r[0] = (int)(w & 0xC0C0C0C0u);
+      r[1] = (int)((w << 2) & 0xC0C0C0C0u);
+      r[2] = (int)((w << 4) & 0xC0C0C0C0u);
+      r[3] = (int)((w << 6) & 0xC0C0C0C0u);
+      return r;
+    } else if constexpr (!W4) {
       return *reinterpret_cast<const v4i*>(S0 + off);
     } else {
       const uint2 w = *reinterpret_cast<const uint2*>(S0 + off);
@@ -1037,7 +1087,10 @@ void igemm_kernel(MIXDQ_IGEMM_HEAD_PARAMS const IgemmParams p_in) {
     for (int i = 0; i < KS; ++i) {
       const int ks = kg * KS + i;
       const int c = ks * CPS + lkq;   // this lane's 16-k chunk of the K-tile
-      if constexpr (!W4) {
+      if constexpr (W2) {   // packed W2: 16 k-values = 4 bytes, dword (c & 3) of the 64-k piece c >> 2 --
+        constexpr int KSP = BK / 64;   // b_rd addresses its 8-byte pair (c & 2), load_w picks the dword (w2_hi)
+        b_rd[t][i] = A_STAGE + row * (BK / 4) + (((c >> 2) ^ w2_swz<KSP>(row)) << 4) + (c & 2) * 4;
+      } else if constexpr (!W4) {
         b_rd[t][i] = A_STAGE + row * BK + ((c ^ swz<BK>(row)) << 4);
       } else {   // packed: 16 k-values = 8 bytes, half (c & 1) of the 32-k piece c >> 1
         constexpr int KSP = BK / 32;
@@ -1388,6 +1441,7 @@ void igemm_kernel(MIXDQ_IGEMM_HEAD_PARAMS const IgemmParams p_in) {
             const int e0 = MT == 32 ? 4 * ((oq & 1) + 2 * half) : 0;
             v4f b0q = b0[j], scq = sc[j];
             if constexpr (W4) { b0q = b0q * 16.0f; scq = scq * 0.0625f; }   // exact: the MFMA ran on 16*q
+            if constexpr (W2) { b0q = b0q * 64.0f; scq = scq * 0.015625f; }   // exact: the MFMA ran on 64*q
             v4f bs = {0.f, 0.f, 0.f, 0.f};
             if constexpr (MODE != 0) bs = __builtin_convertvector(bsh[j], v4f);
             uint32_t packed[2];
@@ -1532,6 +1586,7 @@ void igemm_kernel(MIXDQ_IGEMM_HEAD_PARAMS const IgemmParams p_in) {
           }
           v4f sc = *reinterpret_cast<const v4f*>(P_SC + nl);
           if constexpr (W4) { b0 = b0 * 16.0f; sc = sc * 0.0625f; }   // exact: the MFMA ran on 16*q
+          if constexpr (W2) { b0 = b0 * 64.0f; sc = sc * 0.015625f; }   // exact: the MFMA ran on 64*q
           v4f bs = {0.f, 0.f, 0.f, 0.f};
           if constexpr (MODE != 0)
             bs = __builtin_convertvector(*reinterpret_cast<const v4h*>(P_BS + nl), v4f);   // exact
@@ -2049,7 +2104,7 @@ inline int tile_map_gm() {
   return gm;
 }
 
-template <int BM, int BN, int BK, int STAGES, int WM, int WN, bool CONV, bool FAST, bool W4, int KSPLIT,
+template <int BM, int BN, int BK, int STAGES, int WM, int WN, bool CONV, bool FAST, int WBITS, int KSPLIT,
           int MT, bool F16 = false, bool PHASED = false, bool GROUPED = false, bool AQ = false, bool LNQ = false>
 int launch_kernel(IgemmParams& p, hipStream_t stream) {
   // (LNQ: the LDS request is padded past half a CU's LDS, so that no two workgroups share a CU: the tiles of a
@@ -2063,7 +2118,7 @@ int launch_kernel(IgemmParams& p, hipStream_t stream) {
     static bool seen[64] = {};
     if (const int st = lds_opt_in(
             reinterpret_cast<const void*>(
-                &igemm_kernel<BM, BN, BK, STAGES, WM, WN, CONV, FAST, W4, KSPLIT, MT, F16, false, PHASED, GROUPED, AQ, LNQ>),
+                &igemm_kernel<BM, BN, BK, STAGES, WM, WN, CONV, FAST, WBITS, KSPLIT, MT, F16, false, PHASED, GROUPED, AQ, LNQ>),
             SMEM, seen))
       return st;
   }
@@ -2089,41 +2144,41 @@ int launch_kernel(IgemmParams& p, hipStream_t stream) {
       int n = 0, per_cu = 0;
       if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return MIXDQ_ERR_LAUNCH;
       if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
-              &per_cu, igemm_kernel<BM, BN, BK, STAGES, WM, WN, CONV, FAST, W4, KSPLIT, MT, F16, false, PHASED, GROUPED, AQ, LNQ>,
+              &per_cu, igemm_kernel<BM, BN, BK, STAGES, WM, WN, CONV, FAST, WBITS, KSPLIT, MT, F16, false, PHASED, GROUPED, AQ, LNQ>,
               64 * WM * WN * KSPLIT, SMEM) != hipSuccess)
         return MIXDQ_ERR_LAUNCH;
       cus[dev] = per_cu >= 1 ? n : -1;
     }
     if (cus[dev] < 0 || grid > cus[dev]) return MIXDQ_ERR_SHAPE;
   }
-  igemm_kernel<BM, BN, BK, STAGES, WM, WN, CONV, FAST, W4, KSPLIT, MT, F16, false, PHASED, GROUPED, AQ, LNQ>
+  igemm_kernel<BM, BN, BK, STAGES, WM, WN, CONV, FAST, WBITS, KSPLIT, MT, F16, false, PHASED, GROUPED, AQ, LNQ>
       <<<dim3((unsigned)grid, (unsigned)ny), 64 * WM * WN * KSPLIT, SMEM, stream>>>(MIXDQ_IGEMM_HEAD_ARGS(p) p);
   return launch_status();
 }
 
-template <int BM, int BN, int BK, int STAGES, int WM, int WN, bool CONV, bool W4, int KSPLIT, int MT,
+template <int BM, int BN, int BK, int STAGES, int WM, int WN, bool CONV, int WBITS, int KSPLIT, int MT,
           bool F16 = false, bool PHASED = false, bool GROUPED = false>
 int launch_tile(IgemmParams& p, hipStream_t stream) {
   if constexpr (!CONV) {
     const bool fits32 = (uint64_t)p.M * (uint64_t)p.Ktot < (1ull << 32) &&
                         (uint64_t)p.N * (uint64_t)p.Ktot < (1ull << 32);
     if (p.Ktot % BK == 0 && fits32) {
-      if constexpr (PHASED && !W4 && !F16)
-        return launch_kernel<BM, BN, BK, STAGES, WM, WN, false, true, false, KSPLIT, MT, false, true>(p, stream);
+      if constexpr (PHASED && WBITS == 8 && !F16)
+        return launch_kernel<BM, BN, BK, STAGES, WM, WN, false, true, 8, KSPLIT, MT, false, true>(p, stream);
       else if constexpr (!PHASED)
-        return launch_kernel<BM, BN, BK, STAGES, WM, WN, false, true, W4, KSPLIT, MT, F16, false, GROUPED>(p, stream);
+        return launch_kernel<BM, BN, BK, STAGES, WM, WN, false, true, WBITS, KSPLIT, MT, F16, false, GROUPED>(p, stream);
     }
   }
   if constexpr (PHASED)   // convs, packed weights, K tails: the same tile on the one-phase loop
-    return launch_kernel<BM, BN, BK, STAGES, 4, 2, CONV, false, W4, 1, 32, F16>(p, stream);
+    return launch_kernel<BM, BN, BK, STAGES, 4, 2, CONV, false, WBITS, 1, 32, F16>(p, stream);
   else
-    return launch_kernel<BM, BN, BK, STAGES, WM, WN, CONV, false, W4, KSPLIT, MT, F16, false, GROUPED>(p, stream);
+    return launch_kernel<BM, BN, BK, STAGES, WM, WN, CONV, false, WBITS, KSPLIT, MT, F16, false, GROUPED>(p, stream);
 }
 
 // AQ launches: the Linear fast path only -- whole K-tiles and 32-bit byte offsets into the FP16 operand
 // (its last addressed row starts below 4 GiB).  Anything else: MIXDQ_ERR_SHAPE; the caller then runs the
 // reference's two launches (quantize, GEMM).
-template <int BM, int BN, int BK, int STAGES, int WM, int WN, bool W4, int KSPLIT, int MT>
+template <int BM, int BN, int BK, int STAGES, int WM, int WN, int WBITS, int KSPLIT, int MT>
 int launch_tile_aq(IgemmParams& p, hipStream_t stream) {
   const uint64_t rows = p.a_rowmap && p.grp_rows > 0
                             ? ((uint64_t)(p.M + p.grp_rows - 1) / p.grp_rows) * (uint64_t)p.grp_stride + p.grp_off
@@ -2131,7 +2186,7 @@ int launch_tile_aq(IgemmParams& p, hipStream_t stream) {
   const bool fits32 = rows * (uint64_t)p.a_ld * 2 + 2 * (uint64_t)p.Ktot < (1ull << 32) &&
                       (uint64_t)p.N * (uint64_t)p.Ktot < (1ull << 32);
   if (p.Ktot % BK != 0 || !fits32) return MIXDQ_ERR_SHAPE;
-  return launch_kernel<BM, BN, BK, STAGES, WM, WN, false, true, W4, KSPLIT, MT, false, false, false, true>(p, stream);
+  return launch_kernel<BM, BN, BK, STAGES, WM, WN, false, true, WBITS, KSPLIT, MT, false, false, false, true>(p, stream);
 }
 
 // LNQ launches (GEMM + residual + LayerNorm + quantize): the Linear fast path on an exact-fit tile.
@@ -2140,7 +2195,7 @@ int launch_tile_ln(IgemmParams& p, hipStream_t stream) {
   const bool fits32 = (uint64_t)p.M * (uint64_t)p.Ktot < (1ull << 32) &&
                       (uint64_t)p.N * (uint64_t)p.Ktot < (1ull << 32);
   if (p.Ktot % BK != 0 || !fits32) return MIXDQ_ERR_SHAPE;
-  return launch_kernel<BM, BN, BK, STAGES, WM, WN, false, true, false, KSPLIT, MT, false, false, false, false, true>(p, stream);
+  return launch_kernel<BM, BN, BK, STAGES, WM, WN, false, true, 8, KSPLIT, MT, false, false, false, false, true>(p, stream);
 }
 
 }  // namespace

@@ -76,7 +76,7 @@ extern "C" int mixdq_qlinear_w8a8_ln(const int8_t* A, const int8_t* W, const flo
   if (!A || !W || !bias0 || !scale || !D_f16 || !gamma_f16 || !beta_f16 || !workspace ||
       (n_out == 0 && !out_f16_or_null))
     return MIXDQ_ERR_INVALID_ARG;
-  if (flags & MIXDQ_FLAG_W4) return MIXDQ_ERR_SHAPE;
+  if (flags & (MIXDQ_FLAG_W4 | MIXDQ_FLAG_W2)) return MIXDQ_ERR_SHAPE;
   int cfg = (flags >> 8) & 0xff;
   if (cfg == 0) cfg = mixdq_qlinear_ln_select_id(M, N, K);
   if (cfg <= 0) return MIXDQ_ERR_SHAPE;

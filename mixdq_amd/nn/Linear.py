@@ -21,7 +21,7 @@ import torch.nn.functional as F
 from torch.ao.quantization import QConfig
 
 from mixdq_amd.nn.glue import tagged_operand
-from mixdq_amd.nn.utils import create_qparams_from_dtype, pack_w4, unpack_w4
+from mixdq_amd.nn.utils import create_qparams_from_dtype, pack_w2, pack_w4, unpack_w2, unpack_w4
 from mixdq_amd.op.quant import quantize_per_tensor_vectorized
 from mixdq_amd.op.qlinear import qlinear
 
@@ -51,18 +51,26 @@ class QuantizedLinear(nn.Module):
     # MFMA kernels with an in-kernel unpack.  Set per float module (`mod.w4_kernel = True`) or via
     # quantize_unet(..., w4_kernel=True).
     w4_kernel = False
+    # W2A8 storage (off by default; independent of w4_kernel).  True: a layer with 2-bit weights
+    # (w_bit == 2, quint4x2 qparams -- the reference treats 2 bits as 4, quantize_sdxl.py's bw_to_dtype)
+    # and in_features % 64 == 0 stores its Path A integers clamp(round(w / delta), -2, 1) as packed
+    # signed 2-bit values (weight_int2 [N, K/4], include/mixdq_hip.h MIXDQ_FLAG_W2) and runs on the
+    # INT8 MFMA kernels with an in-kernel unpack.  Set per float module or via
+    # quantize_unet(..., w2_kernel=True).
+    w2_kernel = False
 
     def __init__(self, in_features: int, out_features: int, bias: bool = True, device=None,
-                 w_qparams=None, a_qparams=None, module_name=None, w4_kernel=False) -> None:
+                 w_qparams=None, a_qparams=None, module_name=None, w4_kernel=False,
+                 w2_kernel=False, w_bit=None) -> None:
         super().__init__()
         self.module_name = module_name
         self.in_features = in_features
         self.out_features = out_features
         self.device = device
-        self.w_packed4 = bool(w4_kernel and w_qparams is not None
-                              and w_qparams.dtype == torch.quint4x2)
-        self.valid_for_acceleration = _w8a8_ok(w_qparams, a_qparams, w4_kernel)
-        if self.valid_for_acceleration and self.w_packed4 and in_features % 32 != 0:
+        packable = w_qparams is not None and w_qparams.dtype == torch.quint4x2
+        w2 = bool(w2_kernel and packable and w_bit is not None and int(w_bit) == 2 and in_features % 64 == 0)
+        self.valid_for_acceleration = _w8a8_ok(w_qparams, a_qparams, w4_kernel or w2)
+        if self.valid_for_acceleration and w4_kernel and packable and not w2 and in_features % 32 != 0:
             self.valid_for_acceleration = False      # packed pieces span 32 input channels
         if self.valid_for_acceleration and (in_features % 4 != 0 or out_features % 4 != 0):
             logging.warning(
@@ -70,6 +78,9 @@ class QuantizedLinear(nn.Module):
                 f"{out_features} cannot use quantized kernel due to misalignment. "
                 "Falling back to FP kernels")
             self.valid_for_acceleration = False
+        # decided on the final validity: an FP-fallback layer stores no integers and is not W2
+        self.w_packed2 = w2 and self.valid_for_acceleration
+        self.w_packed4 = bool(w4_kernel and packable) and not self.w_packed2
         if self.valid_for_acceleration:
             self.register_buffer("weight_scales", w_qparams.scales.to(device).float())
             self.register_buffer("weight_zero_points", w_qparams.zero_points.to(device).float())
@@ -96,19 +107,25 @@ class QuantizedLinear(nn.Module):
         new_mod = cls(float_mod.in_features, float_mod.out_features, float_mod.bias is not None,
                       device=device, w_qparams=w_qparams, a_qparams=a_qparams,
                       module_name=float_mod.module_name,
-                      w4_kernel=getattr(float_mod, "w4_kernel", cls.w4_kernel))
+                      w4_kernel=getattr(float_mod, "w4_kernel", cls.w4_kernel),
+                      w2_kernel=getattr(float_mod, "w2_kernel", cls.w2_kernel),
+                      w_bit=getattr(float_mod, "w_bit", None))
         weight = float_mod.weight.detach()
         name = float_mod.module_name
         if "attn2" in name and ("to_k" in name or "to_v" in name):
             new_mod.bos = float_mod.bos
             new_mod.register_buffer("bos_pre_computed", float_mod.bos_pre_computed)
-        if new_mod.valid_for_acceleration and new_mod.w_packed4:
+        if new_mod.valid_for_acceleration and (new_mod.w_packed4 or new_mod.w_packed2):
             # the Path A integers (base_quantizer.py:119-127: sym, clamp to the layer's own bit
-            # width -- a 2-bit layer loads the 2-bit delta and clamps to [-2, 1]; storage is 4-bit)
+            # width -- a 2-bit layer loads the 2-bit delta and clamps to [-2, 1]; storage is 4-bit,
+            # or 2-bit with w2_kernel)
             lim = 2 ** (int(getattr(float_mod, "w_bit", 4)) - 1)
             weight_int = torch.clamp(torch.round(weight.float() / new_mod.weight_scales[:, None]),
                                      -lim, lim - 1).to(torch.int8)
-            new_mod.register_buffer("weight_int4", pack_w4(weight_int))
+            if new_mod.w_packed2:
+                new_mod.register_buffer("weight_int2", pack_w2(weight_int))
+            else:
+                new_mod.register_buffer("weight_int4", pack_w4(weight_int))
         elif new_mod.valid_for_acceleration:
             weight_int = torch.quantize_per_channel(
                 weight.float(), new_mod.weight_scales, new_mod.weight_zero_points,
@@ -131,16 +148,38 @@ class QuantizedLinear(nn.Module):
     def _get_name(self):
         if not self.valid_for_acceleration:
             return "QuantizedLinearFPFallback"
+        if getattr(self, "w_packed2", False):
+            return "QuantizedLinearW2A8"
         return "QuantizedLinearW4A8" if self.w_packed4 else "QuantizedLinearW8A8"
 
     def _weight_values(self):
+        if getattr(self, "w_packed2", False):
+            return unpack_w2(self.weight_int2)
         return unpack_w4(self.weight_int4) if self.w_packed4 else self.weight_int
+
+    def weight_storage(self):
+        """(stored weight tensor, bits per stored value: 8, 4 or 2) of an accelerated layer."""
+        if getattr(self, "w_packed2", False):
+            return self.weight_int2, 2
+        if self.w_packed4:
+            return self.weight_int4, 4
+        return self.weight_int, 8
+
+    def _wkw(self):
+        """The packed-weight keywords of the _C entry points for this layer's storage."""
+        bits = self.weight_storage()[1]
+        return dict(_w4=bits == 4, _w2=bits == 2)
 
     def forward_fallback(self, x):
         w = (self._weight_values().float() * self.weight_scales[:, None]).to(x.dtype)
         return F.linear(x, w, self.bias.to(x.dtype) if self.bias is not None else None)
 
     def _gemm(self, x_int, out=None, row_map=None, residual=None):
+        if getattr(self, "w_packed2", False):
+            return qlinear(x_int, self.weight_int2, self.weight_scales, self.act_scales,
+                           self.act_zero_points, self.weight_sum_by_input_channels, self.scale,
+                           self.bias0, self.bias, _out=out, _row_map=row_map, _residual=residual,
+                           _w2=True)
         if self.w_packed4:
             return qlinear(x_int, self.weight_int4, self.weight_scales, self.act_scales,
                            self.act_zero_points, self.weight_sum_by_input_channels, self.scale,
@@ -158,7 +197,7 @@ class QuantizedLinear(nn.Module):
         return self._gemm(x_int, residual=residual)
 
     # per-output-channel tensors, reordered together by permute_output_rows_
-    _ROW_TENSORS = ("weight_int", "weight_int4", "weight", "weight_scales", "weight_zero_points",
+    _ROW_TENSORS = ("weight_int", "weight_int4", "weight_int2", "weight", "weight_scales", "weight_zero_points",
                     "weight_sum_by_input_channels", "scale", "bias0", "bias")
 
     @torch.no_grad()
@@ -178,9 +217,9 @@ class QuantizedLinear(nn.Module):
         fp16(gelu(gate))) of this layer's fp16 output, in one launch."""
         from mixdq_amd._C import qlinear_geglu
         assert self.valid_for_acceleration and not getattr(self, "bos", False)
-        w = self.weight_int4 if self.w_packed4 else self.weight_int
+        w = self.weight_storage()[0]
         return qlinear_geglu(x_int, w, self.scale, self.bias0, self.bias, consumer.act_scales_inv,
-                             consumer.act_zero_points, _w4=self.w_packed4)
+                             consumer.act_zero_points, **self._wkw())
 
     def forward_bos_quantized(self, x_int_tail: torch.Tensor, B: int, T: int,
                               out: torch.Tensor = None) -> torch.Tensor:
@@ -216,9 +255,9 @@ class QuantizedLinear(nn.Module):
         """quant_op(x) -> _gemm in ONE launch (mixdq_qlinear_f16in_w8a8: the GEMM quantizes its FP16
         operand in its staging path; bit-identical to the pair)."""
         from mixdq_amd._C import qlinear_f16in
-        w = self.weight_int4 if self.w_packed4 else self.weight_int
+        w = self.weight_storage()[0]
         return qlinear_f16in(x, self.act_scales_inv, self.act_zero_points, w, self.scale, self.bias0,
-                             self.bias, _out=out, _bos=bos, _residual=residual, _w4=self.w_packed4)
+                             self.bias, _out=out, _bos=bos, _residual=residual, **self._wkw())
 
     def forward(self, x: torch.Tensor, _bos_out: torch.Tensor = None) -> torch.Tensor:
         """`_bos_out` (BOS layers): a caller-owned [B, T, N] FP16 buffer whose row 0 already holds
@@ -237,7 +276,7 @@ class QuantizedLinear(nn.Module):
                 return self._gemm(x_int)
             # the reference's two launches (nn/Linear.py:162-176) as one wherever the quantizing GEMM
             # takes the shape; otherwise literally: quantize, then GEMM
-            if qlinear_f16in_wanted(x, N, K, w4=self.w_packed4):
+            if qlinear_f16in_wanted(x, N, K, w4=self.w_packed4, w2=getattr(self, "w_packed2", False)):
                 return self._gemm_f16in(x)
             return self._gemm(quant_op(x, self.act_scales_inv, self.act_zero_points))
         # BOS carve-out: token 0 is a precomputed FP16 row, tokens 1.. go through the kernels
@@ -245,7 +284,7 @@ class QuantizedLinear(nn.Module):
         if out is not None and not (out.shape == (x.shape[0], x.shape[1], N) and out.dtype == torch.float16
                                     and out.device == x.device and out.is_contiguous()):
             out = None
-        if qlinear_f16in_wanted(x, N, K, w4=self.w_packed4, bos=True):
+        if qlinear_f16in_wanted(x, N, K, w4=self.w_packed4, bos=True, w2=getattr(self, "w_packed2", False)):
             if out is None:
                 out = torch.empty((x.shape[0], x.shape[1], N), dtype=torch.float16, device=x.device)
                 out[:, :1, :] = self.bos_pre_computed

@@ -212,7 +212,8 @@ def _project_kv(to_k, to_v, ctx):
         from mixdq_amd.unet import _quantizer_groups
         ids = _quantizer_groups(to_k.__dict__.setdefault("_mixdq_memo", {}), "glue_kv", [to_k, to_v])
         if ids[0] == ids[1] and not any(
-                _C.qlinear_f16in_wanted(ctx, m.out_features, m.in_features, w4=m.w_packed4, bos=True)
+                _C.qlinear_f16in_wanted(ctx, m.out_features, m.in_features, w4=m.w_packed4, bos=True,
+                                        w2=getattr(m, "w_packed2", False))
                 for m in (to_k, to_v)):
             B, T = ctx.shape[0], ctx.shape[1]
             from mixdq_amd.op.quant import quantize_per_tensor_vectorized as quant_op
@@ -277,7 +278,7 @@ def _self_qkv(attn, x):
     if x_int is None:
         x_int = _operand(x, q0)
     qkv = qlinear(x_int, pack["w"], pack["wscale"], q0.act_scales, q0.act_zero_points, pack["wsum"], pack["scale"],
-                  pack["bias0"], None, _w4=pack["w4"])
+                  pack["bias0"], None, _w4=pack["w4"], _w2=pack.get("w2", False))
     n = pack["C"]
     return qkv[..., :n], qkv[..., n:2 * n], qkv[..., 2 * n:]
 
@@ -298,8 +299,8 @@ def _cross_one_launch(attn, x, k, v):
             and x.shape[0] * x.shape[1] <= CROSS_FUSE_MAX_ROWS
             and _C.qlinear_attention_supported(x.shape, q.out_features, q.in_features, k)):
         return None
-    o_int = _C.qlinear_attention(_operand(x, q), q.weight_int4 if q.w_packed4 else q.weight_int, q.scale, q.bias0,
-                                 k, v, out.act_scales_inv, out.act_zero_points, _w4=q.w_packed4)
+    o_int = _C.qlinear_attention(_operand(x, q), q.weight_storage()[0], q.scale, q.bias0,
+                                 k, v, out.act_scales_inv, out.act_zero_points, **q._wkw())
     return out._gemm(o_int)
 
 

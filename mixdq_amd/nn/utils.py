@@ -132,3 +132,29 @@ def unpack_w4(packed: torch.Tensor) -> torch.Tensor:
     v = torch.stack([hi, lo], dim=-2)                         # [.., group, half, j]
     v = torch.where(v >= 8, v - 16, v)
     return v.to(torch.int8).reshape(*packed.shape[:-1], packed.shape[-1] * 2)
+
+
+# ---- W2 storage of this build ("crumb-planar per 16", include/mixdq_hip.h MIXDQ_FLAG_W2) ------
+# The reference stores its 2-bit layers as 4-bit (its loader: "2 is not supported, treat as 4").
+# Within every group of 16 consecutive k, byte j (0..3) of the group's 4 bytes holds k[j] in bits
+# 7:6, k[4+j] in 5:4, k[8+j] in 3:2 and k[12+j] in 1:0 (two's complement): the kernel's unpack of one
+# packed dword is then 4 masks of (w << 2i) & 0xC0C0C0C0, giving 64 * q in natural k order.
+# Linear [N, K] only; packed last dimension = K / 4, K % 64 == 0 (one 16-byte DMA piece = 64 k).
+def pack_w2(q: torch.Tensor) -> torch.Tensor:
+    """int8 values in [-2, 1], last dim % 64 == 0  ->  int8 packed, last dim / 4."""
+    if q.dtype != torch.int8 or q.shape[-1] % 64 != 0:
+        raise ValueError("pack_w2: int8 values with a last dimension that is a multiple of 64")
+    if q.numel() and (int(q.min()) < -2 or int(q.max()) > 1):
+        raise ValueError("W2 values must be in [-2, 1]")
+    g = q.reshape(*q.shape[:-1], q.shape[-1] // 16, 4, 4).to(torch.int16)   # [.., group, plane, j]
+    packed = (((g[..., 0, :] & 3) << 6) | ((g[..., 1, :] & 3) << 4) | ((g[..., 2, :] & 3) << 2)
+              | (g[..., 3, :] & 3))
+    return packed.to(torch.uint8).view(torch.int8).reshape(*q.shape[:-1], q.shape[-1] // 4)
+
+
+def unpack_w2(packed: torch.Tensor) -> torch.Tensor:
+    """Inverse of pack_w2: int8 packed [..., K/4] -> int8 values [..., K]."""
+    b = packed.view(torch.uint8).to(torch.int16).reshape(*packed.shape[:-1], packed.shape[-1] // 4, 4)
+    v = torch.stack([(b >> 6) & 3, (b >> 4) & 3, (b >> 2) & 3, b & 3], dim=-2)   # [.., group, plane, j]
+    v = torch.where(v >= 2, v - 4, v)
+    return v.to(torch.int8).reshape(*packed.shape[:-1], packed.shape[-1] * 4)

@@ -114,31 +114,45 @@ _PACK_VECS = (("wscale", "weight_scales"), ("wsum", "weight_sum_by_input_channel
               ("scale", "scale"), ("bias0", "bias0"))
 
 
+def _wbits(m) -> int:
+    """Bits per stored weight value of a quantized Linear: 8 (int8), 4 (packed W4) or 2 (packed W2)."""
+    return 2 if getattr(m, "w_packed2", False) else 4 if m.w_packed4 else 8
+
+
+_WBUF = {8: "weight_int", 4: "weight_int4", 2: "weight_int2"}
+
+
 def _uniform_storage(layers) -> bool:
-    """Layers that are to share one GEMM must store their weights alike (all int8 or all packed
-    4-bit).  A pure check: the forward never changes a module's buffers -- mixed groups are
-    unified once, by `unify_packed_storage_` from `SDXLUNet.set_fused`, or run unpacked."""
-    return len({bool(m.w_packed4) for m in layers}) == 1
+    """Layers that are to share one GEMM must store their weights alike (all int8, all packed
+    4-bit or all packed 2-bit).  A pure check: the forward never changes a module's buffers -- mixed
+    groups are unified once, by `unify_packed_storage_` from `SDXLUNet.set_fused`, or run unpacked."""
+    return len({_wbits(m) for m in layers}) == 1
 
 
 def unify_packed_storage_(layers) -> bool:
     """Explicit post-conversion step (SDXLUNet.set_fused -> prepare_fused_): in a mixed-precision
-    config to_q / to_k / to_v (or to_k / to_v) may be a mix of int8 and packed 4-bit layers; the
-    packed ones are widened to int8 STORAGE (the values stay the 4-bit integers, so every output
-    is unchanged) -- one launch instead of three is worth more than those layers' halved bytes.
-    Replaces the `weight_int4` buffer by `weight_int`: state-dict keys change HERE, once, on every
+    config to_q / to_k / to_v (or to_k / to_v) may mix int8, packed 4-bit and packed 2-bit layers.
+    With an int8 member every packed one is widened to int8 STORAGE; a mix of 2- and 4-bit only widens
+    the 2-bit members to W4 (the values stay the layers' own integers, so every output is unchanged) --
+    one launch instead of three is worth more than those layers' smaller bytes.  Replaces the
+    `weight_int4` / `weight_int2` buffer by the wider one: state-dict keys change HERE, once, on every
     rank alike, never inside a forward.  Returns whether the group is uniform afterwards."""
     if _uniform_storage(layers):
         return True
-    if any(getattr(m, "weight_int4", None) is None and m.w_packed4 for m in layers):
+    if any(getattr(m, _WBUF[_wbits(m)], None) is None for m in layers):
         return False
+    from mixdq_amd.nn.utils import pack_w4
+    target = min(8, max(_wbits(m) for m in layers))
     with torch.no_grad():
         for m in layers:
-            if m.w_packed4:
-                w = m._weight_values().contiguous()
-                del m.weight_int4
-                m.register_buffer("weight_int", w)
-                m.w_packed4 = False
+            bits = _wbits(m)
+            if bits == target:
+                continue
+            w = m._weight_values().contiguous()
+            delattr(m, _WBUF[bits])
+            m.register_buffer(_WBUF[target], w if target == 8 else pack_w4(w))
+            m.w_packed2 = False
+            m.w_packed4 = target == 4
     return True
 
 
@@ -146,9 +160,9 @@ def _pack_rows(layers):
     """Row-concatenate the weights and per-channel epilogue vectors of Linear layers that read the
     same INT8 operand: one GEMM against [sum N_i, K] computes every output element exactly as the
     separate launches do.  The concatenated tensors are the storage; the layers keep views."""
-    w4 = bool(layers[0].w_packed4)
-    names = (("w", "weight_int4" if w4 else "weight_int"),) + _PACK_VECS
-    pack = dict(w4=w4, C=layers[0].out_features, layers=tuple(weakref.ref(m) for m in layers),
+    wbits = _wbits(layers[0])
+    names = (("w", _WBUF[wbits]),) + _PACK_VECS
+    pack = dict(w4=wbits == 4, w2=wbits == 2, wbits=wbits, C=layers[0].out_features, layers=tuple(weakref.ref(m) for m in layers),
                 names=names)
     with torch.no_grad():
         for key, name in names:
@@ -318,7 +332,7 @@ def _gemm_res_ln(layer, x_int, residual, next_ln):
     norm, consumers, owner = next_ln
     N, K = layer.out_features, layer.in_features
     M = x_int.numel() // K
-    if (not DEFUSE and _accel(layer) and not layer.w_packed4 and x_int.dtype == torch.int8
+    if (not DEFUSE and _accel(layer) and _wbits(layer) == 8 and x_int.dtype == torch.int8
             and (residual is None or residual.is_contiguous())
             and norm.weight.dtype == torch.float16 and _C.qlinear_ln_supported(M, N, K)):
         groups, slot = _ln_plan(norm, consumers)
@@ -528,8 +542,8 @@ class Attention(nn.Module):
         if _cross_fusable(self, feed_q, k, v, residual):
             from mixdq_amd import _C
             q, out = self.to_q, self.to_out[0]
-            o_int = _C.qlinear_attention(feed_q[0], q.weight_int4 if q.w_packed4 else q.weight_int,
-                                         q.scale, q.bias0, k, v, *_qp(out), _w4=q.w_packed4)
+            o_int = _C.qlinear_attention(feed_q[0], q.weight_storage()[0],
+                                         q.scale, q.bias0, k, v, *_qp(out), **q._wkw())
             return _gemm_res_ln(out, o_int, residual, next_ln)
         return self.attend_out(_run(self.to_q, feed_q), k, v, residual, next_ln=next_ln)
 
@@ -788,7 +802,8 @@ class BasicTransformerBlock(nn.Module):
             from mixdq_amd.op.qlinear import qlinear
             q0 = a.to_q
             qkv = qlinear(feeds[0][0], pack["w"], pack["wscale"], q0.act_scales, q0.act_zero_points,
-                          pack["wsum"], pack["scale"], pack["bias0"], None, _w4=pack["w4"])
+                          pack["wsum"], pack["scale"], pack["bias0"], None, _w4=pack["w4"],
+                          _w2=pack.get("w2", False))
             C = pack["C"]
             x, f2 = a.attend_out(qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:], x, next_ln=ln2)
         else:
@@ -1002,14 +1017,15 @@ class SDXLUNet(nn.Module):
 
     fused = False
 
-    def _grouped(self, name, key, members, w4):
-        """Cached device table of a grouped launch (rebuilt when any member's storage changed)."""
+    def _grouped(self, name, key, members, wbits):
+        """Cached device table of a grouped launch (rebuilt when any member's storage changed).
+        `wbits`: the members' weight storage, 8 / 4 / 2 bits."""
         from mixdq_amd._C import GemmGroupTable
         tables = self.__dict__.setdefault("_group_tables", {})
         want = tuple(m[0].data_ptr() for m in members) + tuple(m[4].data_ptr() for m in members)
         t = tables.get((name, key))
-        if t is None or t.key != want or t.w4 != bool(w4):
-            t = tables[(name, key)] = GemmGroupTable(members, w4=w4)
+        if t is None or t.key != want or t.wbits != wbits:
+            t = tables[(name, key)] = GemmGroupTable(members, wbits=wbits)
         return t
 
     def _project_context_ahead(self, context):
@@ -1066,7 +1082,7 @@ class SDXLUNet(nn.Module):
                     slot[0] = bos_key
                 o = slot[1]
                 blk._kv = (o[..., :pack["C"]], o[..., pack["C"]:], None)
-                grouped.setdefault((gid[id(lk)], lk.in_features, pack["w4"]), []).append(
+                grouped.setdefault((gid[id(lk)], lk.in_features, pack["wbits"]), []).append(
                     (lk, pack, o))
                 continue
             outs = []
@@ -1088,17 +1104,17 @@ class SDXLUNet(nn.Module):
             blk._kv = (outs[0], outs[1], None)
         from mixdq_amd import _C
         from mixdq_amd.op.qlinear import qlinear
-        for (g, K, w4), members in grouped.items():
+        for (g, K, wb), members in grouped.items():
             lk0 = members[0][0]
             x_int = ctx_int8(lk0)
             if len(members) == 1:
                 pack, o = members[0][1], members[0][2]
                 qlinear(x_int, pack["w"], pack["wscale"], lk0.act_scales, lk0.act_zero_points,
                         pack["wsum"], pack["scale"], pack["bias0"], None, _out=o,
-                        _row_map=(T - 1, T, 1), _w4=w4)
+                        _row_map=(T - 1, T, 1), _w4=wb == 4, _w2=wb == 2)
                 continue
-            table = self._grouped("kv", (g, K, w4, B, T), [
-                (pk["w"], pk["bias0"], pk["scale"], None, o) for _, pk, o in members], w4)
+            table = self._grouped("kv", (g, K, wb, B, T), [
+                (pk["w"], pk["bias0"], pk["scale"], None, o) for _, pk, o in members], wb)
             _C.qlinear_grouped(x_int, table, _row_map=(T - 1, T, 1))
 
     @staticmethod
@@ -1151,10 +1167,10 @@ class SDXLUNet(nn.Module):
                 buf = bufs[(B, s.device)] = torch.empty((B, layer.out_features),
                                                         dtype=torch.float16, device=s.device)
             res._t = (buf, None)
-            grouped.setdefault((gid[id(layer)], layer.in_features, bool(layer.w_packed4)),
+            grouped.setdefault((gid[id(layer)], layer.in_features, _wbits(layer)),
                                []).append((layer, buf))
         from mixdq_amd import _C
-        for (g, K, w4), members in grouped.items():
+        for (g, K, wb), members in grouped.items():
             from mixdq_amd.nn.Linear import quant_op
             if g not in shared:
                 shared[g] = quant_op(s, *_qp(members[0][0]))
@@ -1162,9 +1178,9 @@ class SDXLUNet(nn.Module):
             if len(members) == 1:
                 members[0][0]._gemm(x_int, out=members[0][1])
                 continue
-            table = self._grouped("temb", (g, K, w4, B), [
-                (m.weight_int4 if w4 else m.weight_int, m.bias0, m.scale, m.bias, buf)
-                for m, buf in members], w4)
+            table = self._grouped("temb", (g, K, wb, B), [
+                (m.weight_storage()[0], m.bias0, m.scale, m.bias, buf)
+                for m, buf in members], wb)
             _C.qlinear_grouped(x_int, table)
 
     def refresh_derived_(self):

@@ -164,8 +164,8 @@ def main():
             continue
         n += 1
         errs = check_kernel(name, body)
-        tag = re.search(r"igemm_kernelILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELb\dELb\dELb(\d)ELi(\d+)ELi(\d+)", name)
-        short = "igemm<%s,%s,%s,st%s,%sx%s,w4=%s,ks%s,mt%s>" % tag.groups() if tag else name
+        tag = re.search(r"igemm_kernelILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELb\dELb\dELi(\d)ELi(\d+)ELi(\d+)", name)
+        short = "igemm<%s,%s,%s,st%s,%sx%s,wbits=%s,ks%s,mt%s>" % tag.groups() if tag else name
         status = "ok" if not errs else "FAIL"
         print(f"{short}: {status}  scratch={scratch} B")
         for e in errs[:8]:
