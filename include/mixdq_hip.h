@@ -90,9 +90,22 @@ enum mixdq_flags {
      refuse it (MIXDQ_ERR_UNSUPPORTED; mixdq_qlinear_f16in_w8a8 and the LayerNorm launch: MIXDQ_ERR_SHAPE,
      the caller then quantizes and runs the GEMM).  Together with MIXDQ_FLAG_W4: MIXDQ_ERR_INVALID_ARG.
      No reference counterpart: the reference stores its 2-bit layers as 4-bit (TODO in its loader). */
-  MIXDQ_FLAG_W2 = 16
+  MIXDQ_FLAG_W2 = 16,
   /* bits 8..15: force a kernel configuration id (tuning / tests); 0 = automatic */
+  /* A 4-bit activation quantizer in slot i (i = 0, 1, 2: the i-th quantizer of a launch; entry points with one
+     quantizer use slot 0): the INT8 operand is the int8 quantizer with a narrower clamp,
+       q = clamp(rint(fma(f32(x), *scale_inv, *zero_point)), -128, -113)
+     -- Path A's clamp(round(x / delta) + zp_u, 0, 15) shifted by -128, as zero_point is for 8 bits.  The GEMMs
+     read such an operand unchanged (acc - bias0 = sum w (q - zp) holds for any clamp).  Honoured by
+     mixdq_quantize_f16_i8, mixdq_layernorm_quantize (per slot), mixdq_geglu_quantize, mixdq_attention_f16[_prefetch]
+     and mixdq_qlinear_w8a8_attn; every other entry point that quantizes refuses them (MIXDQ_ERR_UNSUPPORTED: the
+     caller then asks for FP16 and quantizes in a launch of its own).  No reference counterpart: the reference's
+     kernels cannot take a 4-bit activation and run such a layer in FP16 (nn/Linear.py:31,133-134). */
+  MIXDQ_FLAG_A4_0 = 1 << 16,
+  MIXDQ_FLAG_A4_1 = 1 << 17,
+  MIXDQ_FLAG_A4_2 = 1 << 18
 };
+#define MIXDQ_FLAG_A4_ANY (MIXDQ_FLAG_A4_0 | MIXDQ_FLAG_A4_1 | MIXDQ_FLAG_A4_2)
 
 const char* mixdq_status_string(int status);
 int mixdq_abi_version(void);

@@ -134,6 +134,11 @@ IGEMM_WAVES = {1: (2, 2, 1, 32), 3: (2, 2, 1, 32), 4: (2, 2, 1, 32), 13: (4, 2, 
 FLAG_W4 = 2   # MIXDQ_FLAG_W4: the weight tensor holds packed signed 4-bit values
 FLAG_W2 = 16  # MIXDQ_FLAG_W2: the weight tensor holds packed signed 2-bit values ([N, K/4])
 FLAG_UPSAMPLE2X = 4   # MIXDQ_FLAG_UPSAMPLE2X: the conv input is read through a nearest 2x upsampling
+# MIXDQ_FLAG_A4_<i>: quantizer slot i of a launch is a 4-bit one -- q clamped to [-128, -113] (Path A's [0, 15]
+# shifted by -128); the GEMMs read the operand unchanged
+FLAG_A4_0, FLAG_A4_1, FLAG_A4_2 = 1 << 16, 1 << 17, 1 << 18
+FLAG_A4 = (FLAG_A4_0, FLAG_A4_1, FLAG_A4_2)
+ACT_BITS = (8, 4)          # the activation widths the producers take
 # configuration ids a packed-W2 launch cannot take (the weight stage is not whole 1-KiB pieces; 27: see
 # csrc/igemm.hip w2_tile_ok)
 W2_INADMISSIBLE = (27, 42, 43, 44, 45, 56)
@@ -143,6 +148,12 @@ def _wflag(w4, w2):
     """MIXDQ_FLAG_W4 / _W2 for a launch on packed weights (never both)."""
     _check(not (w4 and w2), "_w4 and _w2 are exclusive")
     return FLAG_W2 if w2 else FLAG_W4 if w4 else 0
+
+
+def _aflag(abits, slot=0):
+    """MIXDQ_FLAG_A4_<slot> for a 4-bit quantizer, 0 for an 8-bit one."""
+    _check(abits in ACT_BITS, f"activation bits must be 8 or 4, got {abits!r}")
+    return FLAG_A4[slot] if abits == 4 else 0
 
 
 def _kmul(w4, w2):
@@ -276,7 +287,7 @@ def _f32vec(t: torch.Tensor) -> torch.Tensor:
     return t
 
 
-def _quantize(input, scale_inv, zero_point):
+def _quantize(input, scale_inv, zero_point, abits=8):
     _check(input.is_cuda, "input should be on CUDA")
     _check(input.device == scale_inv.device, "input and scale should be on the same device")
     _check(input.device == zero_point.device,
@@ -294,20 +305,21 @@ def _quantize(input, scale_inv, zero_point):
     with torch.cuda.device(input.device):
         code = _lib.mixdq_quantize_f16_i8(input.data_ptr(), out.data_ptr(), _i64arr(sizes),
                                           _i64arr(xs), _i64arr(os_), len(sizes),
-                                          scale_inv.data_ptr(), zero_point.data_ptr(), FLAGS,
-                                          _stream())
+                                          scale_inv.data_ptr(), zero_point.data_ptr(),
+                                          FLAGS | _aflag(abits), _stream())
     _status(code, "quantize_per_tensor_to_int8")
     return out
 
 
-def quantize_per_tensor_to_int8(input, scale_inv, zero_point):
-    """Quantize to int 8 per tensor with scale and zero point."""
-    return _quantize(input, scale_inv, zero_point)
+def quantize_per_tensor_to_int8(input, scale_inv, zero_point, *, _abits=8):
+    """Quantize to int 8 per tensor with scale and zero point.  `_abits=4`: a 4-bit activation quantizer
+    (MIXDQ_FLAG_A4_0): the same INT8 operand clamped to [-128, -113]."""
+    return _quantize(input, scale_inv, zero_point, _abits)
 
 
-def quantize_per_tensor_to_int8_vectorized(input, scale_inv, zero_point):
+def quantize_per_tensor_to_int8_vectorized(input, scale_inv, zero_point, *, _abits=8):
     """Same kernel family as quantize_per_tensor_to_int8 (every path here is vectorised)."""
-    return _quantize(input, scale_inv, zero_point)
+    return _quantize(input, scale_inv, zero_point, _abits)
 
 
 def qlinear_w8_a8_ohalf(input_int8, weight_int8, weight_scale, input_scale, input_zero_point,
@@ -432,11 +444,11 @@ def _rows_view(x: torch.Tensor, K: int):
 
 
 def qlinear_f16in_supported(x: torch.Tensor, N: int, K: int, *, w4: bool = False, bos: bool = False,
-                            w2: bool = False) -> bool:
+                            w2: bool = False, abits: int = 8) -> bool:
     """True if qlinear_f16in takes `x` (fp16 [..., K]; bos: [B, T, K] whose tokens 1.. are the operand).
-    Packed-W2 weights (`w2`): never -- the quantizing family is not built for them; the caller quantizes
-    and runs the GEMM."""
-    if w2:
+    Packed-W2 weights (`w2`) or a 4-bit activation quantizer (`abits=4`): never -- the quantizing family is
+    not built for them; the caller quantizes and runs the GEMM."""
+    if w2 or abits != 8:
         return False
     if not (x.is_cuda and x.dtype == torch.float16 and x.data_ptr() % 16 == 0):
         return False
@@ -453,10 +465,10 @@ def qlinear_f16in_supported(x: torch.Tensor, N: int, K: int, *, w4: bool = False
 
 
 def qlinear_f16in_wanted(x: torch.Tensor, N: int, K: int, *, w4: bool = False, bos: bool = False,
-                         w2: bool = False) -> bool:
+                         w2: bool = False, abits: int = 8) -> bool:
     """What the modules ask: fuse this layer's quantize into its GEMM?  Supported, and -- under the default
     MIXDQ_F16IN=auto -- expected to be cheaper than the two launches (mixdq_qlinear_f16in_preferred)."""
-    if F16IN == "0" or not qlinear_f16in_supported(x, N, K, w4=w4, bos=bos, w2=w2):
+    if F16IN == "0" or not qlinear_f16in_supported(x, N, K, w4=w4, bos=bos, w2=w2, abits=abits):
         return False
     if F16IN == "1":
         return True
@@ -611,12 +623,12 @@ def qlinear_attention_supported(x_shape, N, K, k) -> bool:
 
 
 def qlinear_attention(input_int8, weight_int8, scale, bias0, k, v, scale_inv=None, zero_point=None,
-                      softmax_scale=None, *, _w4=False, _w2=False):
+                      softmax_scale=None, *, _w4=False, _w2=False, _abits=8):
     """attn2.to_q (INT8 GEMM, no bias) and the cross-attention core in one launch
     (mixdq_qlinear_w8a8_attn): input int8 [B, T, K], weight [N, K], k / v fp16 [B, Tkv <= 128, N]
     with unit stride along N.  Returns the attention output [B, T, N]: int8 (to_out.0's operand)
     when scale_inv / zero_point are given, else fp16.  Bit-identical to qlinear_w8_a8_ohalf
-    followed by attention_f16."""
+    followed by attention_f16.  `_abits=4`: to_out.0's quantizer is a 4-bit one."""
     _trace_w(weight_int8)
     _check(input_int8.is_cuda and input_int8.dtype == torch.int8 and input_int8.dim() == 3,
            "input_int8 should be an int8 [B, T, K] GPU tensor")
@@ -638,13 +650,13 @@ def qlinear_attention(input_int8, weight_int8, scale, bias0, k, v, scale_inv=Non
     ss = float(softmax_scale) if softmax_scale is not None else 0.125
     _record("linear_attn", B * T, N, K, K, _w4, qlinear_attention,
             (input_int8, weight_int8, scale, bias0, k, v, scale_inv, zero_point, softmax_scale),
-            dict(_w4=_w4, _w2=_w2), w2=_w2)
+            dict(_w4=_w4, _w2=_w2, _abits=_abits), w2=_w2)
     with torch.cuda.device(a.device):
         code = _lib.mixdq_qlinear_w8a8_attn(
             a.data_ptr(), w.data_ptr(), b0.data_ptr(), sc.data_ptr(), k.data_ptr(), v.data_ptr(),
             out.data_ptr(), B * T, N, K, T, k.shape[1], k.stride(0), k.stride(1), v.stride(0),
             v.stride(1), ss, _ptr(scale_inv), _ptr(zero_point),
-            FLAGS | wflag, _stream())
+            FLAGS | wflag | _aflag(_abits), _stream())
     _status(code, "qlinear_attention")
     return out
 
@@ -1082,15 +1094,21 @@ def groupnorm_silu_quantize(x, num_groups, weight, bias, eps, scale_inv=None, ze
     return out_q, out_h
 
 
-def layernorm_quantize(x, weight, bias, eps, qparams, want_f16=False):
+def layernorm_quantize(x, weight, bias, eps, qparams, want_f16=False, *, _abits=None):
     """x: fp16 [..., C] contiguous; qparams: up to three (scale_inv, zero_point) device-scalar
-    pairs.  Returns ([int8 ...], fp16 or None)."""
+    pairs.  Returns ([int8 ...], fp16 or None).  `_abits`: the width of each quantizer, e.g. (8, 4, 8)
+    (default: all 8)."""
     _check(x.is_cuda and x.dtype == torch.float16 and x.is_contiguous(),
            "x should be a contiguous fp16 GPU tensor")
     C = x.shape[-1]
     M = x.numel() // C if C else 0
     n = len(qparams)
     _check(n <= 3 and (n > 0 or want_f16), "layernorm_quantize: 1..3 quantizers or want_f16")
+    abits = (8,) * n if _abits is None else tuple(_abits)
+    _check(len(abits) == n, "layernorm_quantize: one width per quantizer")
+    aflags = 0
+    for i, b in enumerate(abits):
+        aflags |= _aflag(b, i)
     outs = [torch.empty_like(x, dtype=torch.int8) for _ in range(n)]
     out_h = torch.empty_like(x) if want_f16 else None
     arr = ctypes.c_void_p * max(n, 1)
@@ -1101,7 +1119,7 @@ def layernorm_quantize(x, weight, bias, eps, qparams, want_f16=False):
     _check(w.dtype == torch.float16 and b.dtype == torch.float16, "gamma/beta should be fp16")
     with torch.cuda.device(x.device):
         code = _lib.mixdq_layernorm_quantize(x.data_ptr(), w.data_ptr(), b.data_ptr(), float(eps),
-                                             M, C, n, si, zp, oq, _ptr(out_h), FLAGS, _stream())
+                                             M, C, n, si, zp, oq, _ptr(out_h), FLAGS | aflags, _stream())
     _status(code, "layernorm_quantize")
     return outs, out_h
 
@@ -1189,8 +1207,9 @@ def qlinear_ln(input_int8, weight_int8, scale, bias0, bias, residual, ln_weight,
     return D, outs, out_h
 
 
-def geglu_quantize(h, scale_inv=None, zero_point=None, want_f16=False):
-    """h: fp16 [..., 2D] contiguous -> (int8 [..., D] or None, fp16 [..., D] or None)."""
+def geglu_quantize(h, scale_inv=None, zero_point=None, want_f16=False, *, _abits=8):
+    """h: fp16 [..., 2D] contiguous -> (int8 [..., D] or None, fp16 [..., D] or None).
+    `_abits=4`: the output quantizer is a 4-bit one."""
     _check(h.is_cuda and h.dtype == torch.float16 and h.is_contiguous(),
            "h should be a contiguous fp16 GPU tensor")
     D = h.shape[-1] // 2
@@ -1202,7 +1221,7 @@ def geglu_quantize(h, scale_inv=None, zero_point=None, want_f16=False):
     out_h = torch.empty(shape, dtype=torch.float16, device=h.device) if want_f16 else None
     with torch.cuda.device(h.device):
         code = _lib.mixdq_geglu_quantize(h.data_ptr(), M, D, _ptr(scale_inv), _ptr(zero_point),
-                                         _ptr(out_q), _ptr(out_h), FLAGS, _stream())
+                                         _ptr(out_q), _ptr(out_h), FLAGS | _aflag(_abits), _stream())
     _status(code, "geglu_quantize")
     return out_q, out_h
 
@@ -1219,7 +1238,8 @@ if hasattr(_lib, "mixdq_attention_f16_prefetch"):     # (absent in older builds 
 PREFETCH_MAX_RANGES = 16
 
 
-def attention_f16(q, k, v, heads, scale_inv=None, zero_point=None, softmax_scale=None, _cfg=0, _prefetch=None):
+def attention_f16(q, k, v, heads, scale_inv=None, zero_point=None, softmax_scale=None, _cfg=0, _prefetch=None,
+                  _abits=8):
     """FP16 attention core (the reference's get_attention_scores + bmm, quant_block.py:630-637).
 
     q [B, Tq, C], k/v [B, Tkv, C] fp16 with unit stride along C (column slices of a fused projection
@@ -1228,6 +1248,7 @@ def attention_f16(q, k, v, heads, scale_inv=None, zero_point=None, softmax_scale
     `_prefetch`: up to 16 GPU tensors (the weights of the layers behind this attention) that payload
     workgroups of the launch read while the attention runs (mixdq_attention_f16_prefetch); no effect
     on the result.
+    `_abits=4`: to_out.0's quantizer is a 4-bit one (the INT8 output clamped to [-128, -113]).
     """
     for t, n in ((q, "q"), (k, "k"), (v, "v")):
         _check(t.is_cuda and t.dtype == torch.float16 and t.dim() == 3 and t.stride(-1) == 1,
@@ -1239,7 +1260,7 @@ def attention_f16(q, k, v, heads, scale_inv=None, zero_point=None, softmax_scale
     # (measurement only) recorded as ("attention", (B * heads * Tq, Tkv, 64, 64)): 4 * M * N * K FLOPs
     _record("attention", B * heads * Tq, k.shape[1], 64, 64, False, attention_f16,
             (q, k, v, heads), dict(scale_inv=scale_inv, zero_point=zero_point,
-                                   softmax_scale=softmax_scale, _cfg=_cfg))     # (measured without the payload)
+                                   softmax_scale=softmax_scale, _cfg=_cfg, _abits=_abits))     # (measured without the payload)
     out = torch.empty((B, Tq, C), dtype=torch.int8 if quant else torch.float16, device=q.device)
     sc = float(softmax_scale) if softmax_scale is not None else 0.125
     ctx = getattr(_TLS, "ctx", None)
@@ -1259,12 +1280,12 @@ def attention_f16(q, k, v, heads, scale_inv=None, zero_point=None, softmax_scale
                 q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, heads, 64, Tq, k.shape[1],
                 q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1),
                 out.stride(0), out.stride(1), sc, _ptr(scale_inv), _ptr(zero_point), ptrs, sizes, len(pf),
-                FLAGS | (int(_cfg) << 8), _stream())
+                FLAGS | (int(_cfg) << 8) | _aflag(_abits), _stream())
         else:
             code = _lib.mixdq_attention_f16(
                 q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, heads, 64, Tq, k.shape[1],
                 q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1),
                 out.stride(0), out.stride(1), sc, _ptr(scale_inv), _ptr(zero_point),
-                FLAGS | (int(_cfg) << 8), _stream())
+                FLAGS | (int(_cfg) << 8) | _aflag(_abits), _stream())
     _status(code, "attention_f16")
     return out

@@ -290,7 +290,8 @@ __device__ __forceinline__ void attn_tile_step(AttnState& st, v16f (&sc)[2], v16
   st.m_i = m_new;
 }
 
-template <int WAVES, int STAGES, bool QUANT, bool RAGGED>
+// A4: the output quantizer is a 4-bit one (MIXDQ_FLAG_A4_0; common.h quantize_pack8<., true>).
+template <int WAVES, int STAGES, bool QUANT, bool RAGGED, bool A4 = false>
 __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2, 2))) void attn_fwd_kernel(const AttnParams p) {
   MIXDQ_ARGS_NOW(p.q, p.k, p.v, p.out, p.q_bs, p.q_rs, p.k_bs, p.k_rs, p.v_bs, p.v_rs, p.o_bs, p.o_rs,
                  p.tq, p.tkv, p.heads, p.qblocks);
@@ -498,7 +499,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2, 2
 #pragma unroll
       for (int j = 0; j < 8; ++j) x[j] = __half2float(hv[j]);
       *reinterpret_cast<uint2*>(reinterpret_cast<int8_t*>(p.out) + off) =
-          p.unfused ? quantize_pack8<true>(x, s_inv, zp) : quantize_pack8<false>(x, s_inv, zp);
+          p.unfused ? quantize_pack8<true, A4>(x, s_inv, zp) : quantize_pack8<false, A4>(x, s_inv, zp);
     }
   }
   MIXDQ_ATTN_STAMP(7);                           // rows stored (issued)
@@ -512,7 +513,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2, 2
 // tile by tile, unpipelined, exactly the sequence of the fused epilogue in igemm.hip -- in <= 128
 // registers: four workgroups per CU, 32 KB of LDS each.  Bit-identical to attn_fwd_kernel
 // (tests/test_attention_gpu.py).
-template <bool QUANT>
+template <bool QUANT, bool A4 = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void attn_short_kernel(const AttnParams p) {
   MIXDQ_ARGS_NOW(p.q, p.k, p.v, p.out, p.q_bs, p.q_rs, p.k_bs, p.k_rs, p.v_bs, p.v_rs, p.o_bs, p.o_rs,
                  p.tq, p.tkv, p.heads, p.qblocks);
@@ -682,17 +683,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 #pragma unroll
       for (int j = 0; j < 8; ++j) x[j] = __half2float(hv[j]);
       *reinterpret_cast<uint2*>(reinterpret_cast<int8_t*>(p.out) + off) =
-          p.unfused ? quantize_pack8<true>(x, s_inv, zp) : quantize_pack8<false>(x, s_inv, zp);
+          p.unfused ? quantize_pack8<true, A4>(x, s_inv, zp) : quantize_pack8<false, A4>(x, s_inv, zp);
     }
   }
 }
 
-int launch_attn_short(AttnParams& p, int batch, bool quant, hipStream_t stream) {
+int launch_attn_short(AttnParams& p, int batch, bool quant, bool a4, hipStream_t stream) {
   if ((long)p.qblocks * p.heads * batch > 0x7fffffffl) return MIXDQ_ERR_INVALID_ARG;
   const int grid = p.qblocks * p.heads * batch;
   p.attn_blocks = grid;
   const int smem = 2 * kStageBytes;                  // two K | V tiles; the output staging overlays them
-  if (quant) hipLaunchKernelGGL((attn_short_kernel<true>), dim3(grid), dim3(256), smem, stream, p);
+  if (quant && a4) hipLaunchKernelGGL((attn_short_kernel<true, true>), dim3(grid), dim3(256), smem, stream, p);
+  else if (quant) hipLaunchKernelGGL((attn_short_kernel<true>), dim3(grid), dim3(256), smem, stream, p);
   else hipLaunchKernelGGL((attn_short_kernel<false>), dim3(grid), dim3(256), smem, stream, p);
   return launch_status();
 }
@@ -704,7 +706,7 @@ constexpr int attn_smem_bytes(int waves, int stages) {
 }
 
 template <int WAVES, int STAGES>
-int launch_attn(AttnParams& p, int batch, bool quant, hipStream_t stream) {
+int launch_attn(AttnParams& p, int batch, bool quant, bool a4, hipStream_t stream) {
   p.attn_blocks = p.qblocks * p.heads * batch;
   if (p.n_pf == 0) p.pf_blocks = 0;
   if ((long)p.attn_blocks + p.pf_blocks > 0x7fffffffl) return MIXDQ_ERR_INVALID_ARG;
@@ -712,10 +714,11 @@ int launch_attn(AttnParams& p, int batch, bool quant, hipStream_t stream) {
   const int smem = attn_smem_bytes(WAVES, STAGES);
   const dim3 g(grid), b(WAVES * 64);
   const bool ragged = (p.tkv & (kKeys - 1)) != 0;   // whole key tiles: no masking code at all
-#define MIXDQ_ATTN_LAUNCH(Q, R) \
-  hipLaunchKernelGGL((attn_fwd_kernel<WAVES, STAGES, Q, R>), g, b, smem, stream, p)
-  if (quant) { if (ragged) MIXDQ_ATTN_LAUNCH(true, true); else MIXDQ_ATTN_LAUNCH(true, false); }
-  else       { if (ragged) MIXDQ_ATTN_LAUNCH(false, true); else MIXDQ_ATTN_LAUNCH(false, false); }
+#define MIXDQ_ATTN_LAUNCH(Q, R, A4) \
+  hipLaunchKernelGGL((attn_fwd_kernel<WAVES, STAGES, Q, R, A4>), g, b, smem, stream, p)
+  if (quant && a4) { if (ragged) MIXDQ_ATTN_LAUNCH(true, true, true); else MIXDQ_ATTN_LAUNCH(true, false, true); }
+  else if (quant)  { if (ragged) MIXDQ_ATTN_LAUNCH(true, true, false); else MIXDQ_ATTN_LAUNCH(true, false, false); }
+  else             { if (ragged) MIXDQ_ATTN_LAUNCH(false, true, false); else MIXDQ_ATTN_LAUNCH(false, false, false); }
 #undef MIXDQ_ATTN_LAUNCH
   return launch_status();
 }
@@ -742,6 +745,8 @@ static int attention_f16_impl(const void* q, const void* k, const void* v, void*
   if (batch == 0 || tq == 0) return MIXDQ_OK;       // nothing to write (pointers may be null)
   if (!q || !k || !v || !out) return MIXDQ_ERR_INVALID_ARG;
   const bool quant = out_scale_inv != nullptr;
+  if (flags & (MIXDQ_FLAG_A4_1 | MIXDQ_FLAG_A4_2)) return MIXDQ_ERR_UNSUPPORTED;   // one quantizer: slot 0
+  const bool a4 = quant && (flags & MIXDQ_FLAG_A4_0);
   // 16-byte vector accesses: rows of 8 halfs, bases and strides multiples of 8 elements
   const int64_t strides[] = {q_batch_stride, q_row_stride, k_batch_stride, k_row_stride,
                              v_batch_stride, v_row_stride, out_batch_stride, out_row_stride};
@@ -799,13 +804,13 @@ static int attention_f16_impl(const void* q, const void* k, const void* v, void*
   static const bool short_on = [] { const char* e = getenv("MIXDQ_ATTN_SHORT"); return !(e && e[0] == '0'); }();   // A/B runs
   if (force == 1 || (force == 0 && short_on && tkv <= 2 * kKeys)) {   // cross-attention: 77 keys
     p.qblocks = (tq + 127) / 128;
-    return launch_attn_short(p, batch, quant, stream);
+    return launch_attn_short(p, batch, quant, a4, stream);
   }
   const long blocks128 = (long)((tq + 127) / 128) * heads;
   const bool big = force ? force == 4 : blocks128 >= kNumCU / 2;
   p.qblocks = big ? (tq + 127) / 128 : (tq + 63) / 64;
-  if (big) return launch_attn<4, 4>(p, batch, quant, stream);
-  return launch_attn<2, 4>(p, batch, quant, stream);
+  if (big) return launch_attn<4, 4>(p, batch, quant, a4, stream);
+  return launch_attn<2, 4>(p, batch, quant, a4, stream);
 }
 
 extern "C" int mixdq_attention_f16(const void* q, const void* k, const void* v, void* out,

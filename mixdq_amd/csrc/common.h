@@ -43,24 +43,33 @@ inline int lds_opt_in(const void* kernel, int bytes, bool (&seen)[64]) {
 // Quantize one value: q = clamp(rint(x * s_inv + zp)).  rint = round-half-to-even (v_rndne_f32),
 // the float->int conversion saturates and maps NaN to 0 (v_cvt_i32_f32), as cvt.rni does on the
 // reference's hardware.  FUSED = one FMA (variant A); otherwise mul then add (variant B).
-template <bool UNFUSED>
+// A4: a 4-bit activation quantizer (MIXDQ_FLAG_A4_*): the same value clamped to [-128, -113] instead of 127 --
+// Path A's [0, 15] shifted by -128.  One more min in front of the clamp / packing; A4 = false is today's code.
+template <bool UNFUSED, bool A4 = false>
 __device__ __forceinline__ int quantize_one(float x, float s_inv, float zp) {
   float t = UNFUSED ? __fadd_rn(__fmul_rn(x, s_inv), zp) : __builtin_fmaf(x, s_inv, zp);
   int i = (int)__builtin_rintf(t);
+  if constexpr (A4) i = min(i, -113);
   return min(max(i, -128), 127);
 }
 
 // Eight values at once, packed: the same arithmetic (v_rndne_f32, v_cvt_i32_f32: saturating, NaN -> 0), the clamp
 // and the packing by v_ashr_pk_i8_i32 (gfx950: two INT32 -> two saturated INT8 in one instruction) + v_perm_b32 --
 // 3.75 vector instructions per element where the scalar form with min / max / mask / shift / or spends ~7.
-template <bool UNFUSED>
+// A4: each INT32 is first limited to -113 (v_min_i32); the packing's saturation supplies the lower bound.
+template <bool UNFUSED, bool A4 = false>
 __device__ __forceinline__ uint2 quantize_pack8(const float (&x)[8], float s_inv, float zp) {
   uint32_t w[4];
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     const float t0 = UNFUSED ? __fadd_rn(__fmul_rn(x[2 * e], s_inv), zp) : __builtin_fmaf(x[2 * e], s_inv, zp);
     const float t1 = UNFUSED ? __fadd_rn(__fmul_rn(x[2 * e + 1], s_inv), zp) : __builtin_fmaf(x[2 * e + 1], s_inv, zp);
-    w[e] = __builtin_amdgcn_ashr_pk_i8_i32((int)__builtin_rintf(t0), (int)__builtin_rintf(t1), 0);
+    int i0 = (int)__builtin_rintf(t0), i1 = (int)__builtin_rintf(t1);
+    if constexpr (A4) {
+      i0 = min(i0, -113);
+      i1 = min(i1, -113);
+    }
+    w[e] = __builtin_amdgcn_ashr_pk_i8_i32(i0, i1, 0);
   }
   return make_uint2(__builtin_amdgcn_perm(w[1], w[0], 0x05040100u), __builtin_amdgcn_perm(w[3], w[2], 0x05040100u));
 }

@@ -492,7 +492,8 @@ __device__ __forceinline__ float ln_tree(float t, int U) {
 // wave walks 4 or 8 consecutive rows and requests row r + 1 before it reduces row r -- was built and
 // measured SLOWER: [8192, 1280] 11.4 vs 9.9 us, [32768, 640] 28.2 vs 21.3: fewer, longer waves put fewer
 // bytes in flight than one round of short ones.  Removed.)
-template <bool UNFUSED, int NQ, bool WANT_H, int ROWS>
+// A4M: bit i set = quantizer slot i is a 4-bit one (MIXDQ_FLAG_A4_i; common.h quantize_pack8<., true>).
+template <bool UNFUSED, int NQ, bool WANT_H, int ROWS, int A4M = 0>
 __global__ __launch_bounds__(256) void ln_quant_kernel(
     const __half* __restrict__ x, const __half* __restrict__ gamma, const __half* __restrict__ beta,
     float eps, int64_t M, int C, const float* __restrict__ s_inv0, const float* __restrict__ zp0,
@@ -606,9 +607,9 @@ __global__ __launch_bounds__(256) void ln_quant_kernel(
           if constexpr (WANT_H) put_half(oh, j, y[j]);
         }
         const int64_t off = (row0 + r) * C + 8 * c;     // (quantize_pack8: clamp and packing in 3 instructions per pair)
-        if constexpr (NQ > 0) *reinterpret_cast<uint2*>(q0 + off) = quantize_pack8<UNFUSED>(y, si0, z0);
-        if constexpr (NQ > 1) *reinterpret_cast<uint2*>(q1 + off) = quantize_pack8<UNFUSED>(y, si1, z1);
-        if constexpr (NQ > 2) *reinterpret_cast<uint2*>(q2 + off) = quantize_pack8<UNFUSED>(y, si2, z2);
+        if constexpr (NQ > 0) *reinterpret_cast<uint2*>(q0 + off) = quantize_pack8<UNFUSED, (A4M >> 0) & 1>(y, si0, z0);
+        if constexpr (NQ > 1) *reinterpret_cast<uint2*>(q1 + off) = quantize_pack8<UNFUSED, (A4M >> 1) & 1>(y, si1, z1);
+        if constexpr (NQ > 2) *reinterpret_cast<uint2*>(q2 + off) = quantize_pack8<UNFUSED, (A4M >> 2) & 1>(y, si2, z2);
         if constexpr (WANT_H) *reinterpret_cast<Half8*>(out_h + off) = oh;
       }
     }
@@ -617,7 +618,7 @@ __global__ __launch_bounds__(256) void ln_quant_kernel(
 
 // ------------------------------------------------------------------------------- GEGLU
 // h [M, 2D] (ff.net.0.proj output): y = fp16(fp16(h[:, :D]) * fp16(gelu(h[:, D:]))) -> quantize.
-template <bool UNFUSED>
+template <bool UNFUSED, bool A4 = false>
 __global__ __launch_bounds__(256) void geglu_quant_kernel(
     const __half* __restrict__ h, int64_t M, int D, const float* __restrict__ s_inv_p,
     const float* __restrict__ zp_p, int8_t* __restrict__ out_q, __half* __restrict__ out_h) {
@@ -645,7 +646,7 @@ __global__ __launch_bounds__(256) void geglu_quant_kernel(
         y8[j + e] = y;
       }
     }
-    if (want_q) *reinterpret_cast<uint2*>(out_q + m * D + 8 * c) = quantize_pack8<UNFUSED>(y8, s_inv, zp);
+    if (want_q) *reinterpret_cast<uint2*>(out_q + m * D + 8 * c) = quantize_pack8<UNFUSED, A4>(y8, s_inv, zp);
     if (out_h) *reinterpret_cast<Half8*>(out_h + m * D + 8 * c) = oh;
   }
 }
@@ -689,7 +690,7 @@ inline int ensure_gelu_table_fn(hipStream_t stream) {      // (the logic of ensu
   return MIXDQ_OK;
 }
 
-template <bool UNFUSED>
+template <bool UNFUSED, bool A4 = false>
 __global__ __launch_bounds__(1024) void geglu_quant_tab_kernel(
     const __half* __restrict__ h, int64_t M, int D, const float* __restrict__ s_inv_p,
     const float* __restrict__ zp_p, int8_t* __restrict__ out_q, __half* __restrict__ out_h) {
@@ -745,7 +746,7 @@ __global__ __launch_bounds__(1024) void geglu_quant_tab_kernel(
       put_half(oh, j, y);
       y8[j] = y;
     }
-    if (want_q) *reinterpret_cast<uint2*>(out_q + m * D + 8 * c) = quantize_pack8<UNFUSED>(y8, s_inv, zp);
+    if (want_q) *reinterpret_cast<uint2*>(out_q + m * D + 8 * c) = quantize_pack8<UNFUSED, A4>(y8, s_inv, zp);
     if (out_h) *reinterpret_cast<Half8*>(out_h + m * D + 8 * c) = oh;
   }
 }
@@ -812,6 +813,7 @@ extern "C" int mixdq_groupnorm_silu_quantize3(const void* x_nhwc, int C1, const 
                                               int8_t* const* raw_q, void* workspace, int N,
                                               int64_t HW, int C, int G, int flags,
                                               mixdq_stream_t stream_) {
+  if (flags & MIXDQ_FLAG_A4_ANY) return MIXDQ_ERR_UNSUPPORTED;   // 8-bit quantizers only (no 4-bit conv consumer)
   GnRaw raw = {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};
   if (raw_q != nullptr) {
     for (int i = 0; i < 2; ++i) {
@@ -967,22 +969,34 @@ extern "C" int mixdq_layernorm_quantize(const void* x, const void* gamma, const 
   const int rows = rows_forced == 1 || rows_forced == 2 ? rows_forced   // (tuning runs)
                                                         : (M >= 8192 ? 2 : 1);   // rows per wave (see the kernel)
   const int grid = (int)((M + 4 * rows - 1) / (4 * rows));
-#define LN_LAUNCH(U, NQ, H)                                                                          \
-  do {                                                                                               \
-    if (rows == 2)                                                                                   \
-      ln_quant_kernel<U, NQ, H, 2><<<grid, 256, 0, stream>>>(                                        \
-          (const __half*)x, (const __half*)gamma, (const __half*)beta, eps, M, C, si[0], zp[0], q[0], \
-          si[1], zp[1], q[1], si[2], zp[2], q[2], (__half*)out_f16_or_null);                         \
-    else                                                                                             \
-      ln_quant_kernel<U, NQ, H, 1><<<grid, 256, 0, stream>>>(                                        \
-          (const __half*)x, (const __half*)gamma, (const __half*)beta, eps, M, C, si[0], zp[0], q[0], \
-          si[1], zp[1], q[1], si[2], zp[2], q[2], (__half*)out_f16_or_null);                         \
+  const int a4m = (flags >> 16) & 7;
+  if (a4m >> n_out) return MIXDQ_ERR_UNSUPPORTED;                  // an A4 bit for a slot the launch does not have
+#define LN_ARGS                                                                                      \
+  (const __half*)x, (const __half*)gamma, (const __half*)beta, eps, M, C, si[0], zp[0], q[0], si[1], \
+      zp[1], q[1], si[2], zp[2], q[2], (__half*)out_f16_or_null
+#define LN_LAUNCH(U, NQ, H, A)                                                                      \
+  do {                                                                                              \
+    if (rows == 2) ln_quant_kernel<U, NQ, H, 2, A><<<grid, 256, 0, stream>>>(LN_ARGS);              \
+    else ln_quant_kernel<U, NQ, H, 1, A><<<grid, 256, 0, stream>>>(LN_ARGS);                        \
   } while (0)
-#define LN_BY_H(U, NQ) do { if (want_h) LN_LAUNCH(U, NQ, true); else LN_LAUNCH(U, NQ, false); } while (0)
+#define LN_BY_A(U, NQ, H)                                                                           \
+  do {                                                                                              \
+    switch (a4m) {                                                                                  \
+      case 0: LN_LAUNCH(U, NQ, H, 0); break;                                                        \
+      case 1: LN_LAUNCH(U, NQ, H, (NQ > 0 ? 1 : 0)); break;                                         \
+      case 2: LN_LAUNCH(U, NQ, H, (NQ > 1 ? 2 : 0)); break;                                         \
+      case 3: LN_LAUNCH(U, NQ, H, (NQ > 1 ? 3 : 0)); break;                                         \
+      case 4: LN_LAUNCH(U, NQ, H, (NQ > 2 ? 4 : 0)); break;                                         \
+      case 5: LN_LAUNCH(U, NQ, H, (NQ > 2 ? 5 : 0)); break;                                         \
+      case 6: LN_LAUNCH(U, NQ, H, (NQ > 2 ? 6 : 0)); break;                                         \
+      default: LN_LAUNCH(U, NQ, H, (NQ > 2 ? 7 : 0)); break;                                        \
+    }                                                                                               \
+  } while (0)
+#define LN_BY_H(U, NQ) do { if (want_h) LN_BY_A(U, NQ, true); else LN_BY_A(U, NQ, false); } while (0)
 #define LN_BY_NQ(U)                                                                \
   do {                                                                             \
     switch (n_out) {                                                               \
-      case 0: LN_LAUNCH(U, 0, true); break;   /* n_out == 0 implies the FP16 copy */ \
+      case 0: LN_LAUNCH(U, 0, true, 0); break;   /* n_out == 0 implies the FP16 copy */ \
       case 1: LN_BY_H(U, 1); break;                                                \
       case 2: LN_BY_H(U, 2); break;                                                \
       default: LN_BY_H(U, 3); break;                                               \
@@ -991,7 +1005,9 @@ extern "C" int mixdq_layernorm_quantize(const void* x, const void* gamma, const 
   if (unfused) LN_BY_NQ(true); else LN_BY_NQ(false);
 #undef LN_BY_NQ
 #undef LN_BY_H
+#undef LN_BY_A
 #undef LN_LAUNCH
+#undef LN_ARGS
   return launch_status();
 }
 
@@ -1005,6 +1021,8 @@ extern "C" int mixdq_geglu_quantize(const void* h, int64_t M, int D, const float
   if (out_q_or_null && (!scale_inv || !zero_point)) return MIXDQ_ERR_INVALID_ARG;
   if (((uintptr_t)h | (uintptr_t)out_f16_or_null) % 16 || (uintptr_t)out_q_or_null % 8)
     return MIXDQ_ERR_ALIGNMENT;
+  if (flags & (MIXDQ_FLAG_A4_1 | MIXDQ_FLAG_A4_2)) return MIXDQ_ERR_UNSUPPORTED;   // one quantizer: slot 0
+  const bool a4 = out_q_or_null && (flags & MIXDQ_FLAG_A4_0);
   int64_t blocks = (M * (D / 8) + 255) / 256;
   if (blocks > kNumCU * 8) blocks = kNumCU * 8;
   hipStream_t stream = (hipStream_t)stream_;
@@ -1013,26 +1031,30 @@ extern "C" int mixdq_geglu_quantize(const void* h, int64_t M, int D, const float
   static const int tab_mode = [] { const char* e = getenv("MIXDQ_GEGLU_TAB"); return e ? atoi(e) : -1; }();
   if (tab_mode != 0 && (tab_mode == 1 || M * (int64_t)D >= ((int64_t)2 << 20))) {
     if (const int st = ensure_gelu_table_fn(stream)) return st;
-    static bool seen_g[2][64] = {};
+    static bool seen_g[4][64] = {};
     const bool unf = flags & MIXDQ_FLAG_UNFUSED;
-    const void* kern = unf ? reinterpret_cast<const void*>(&geglu_quant_tab_kernel<true>)
-                           : reinterpret_cast<const void*>(&geglu_quant_tab_kernel<false>);
-    if (const int st = lds_opt_in(kern, kGeluTabBytesFn, seen_g[unf ? 1 : 0])) return st;
+    const void* kern = a4 ? (unf ? reinterpret_cast<const void*>(&geglu_quant_tab_kernel<true, true>)
+                                 : reinterpret_cast<const void*>(&geglu_quant_tab_kernel<false, true>))
+                          : (unf ? reinterpret_cast<const void*>(&geglu_quant_tab_kernel<true>)
+                                 : reinterpret_cast<const void*>(&geglu_quant_tab_kernel<false>));
+    if (const int st = lds_opt_in(kern, kGeluTabBytesFn, seen_g[(unf ? 1 : 0) + (a4 ? 2 : 0)])) return st;
     int64_t tb = (M * (D / 8) + 1023) / 1024;
     if (tb > 2 * kNumCU) tb = 2 * kNumCU;
-    if (unf)
-      geglu_quant_tab_kernel<true><<<(int)tb, 1024, kGeluTabBytesFn, stream>>>(
-          (const __half*)h, M, D, scale_inv, zero_point, out_q_or_null, (__half*)out_f16_or_null);
-    else
-      geglu_quant_tab_kernel<false><<<(int)tb, 1024, kGeluTabBytesFn, stream>>>(
-          (const __half*)h, M, D, scale_inv, zero_point, out_q_or_null, (__half*)out_f16_or_null);
+#define GEGLU_TAB(U, A)                                                                                    \
+    geglu_quant_tab_kernel<U, A><<<(int)tb, 1024, kGeluTabBytesFn, stream>>>(                               \
+        (const __half*)h, M, D, scale_inv, zero_point, out_q_or_null, (__half*)out_f16_or_null)
+    if (a4) { if (unf) GEGLU_TAB(true, true); else GEGLU_TAB(false, true); }
+    else if (unf) GEGLU_TAB(true, false);
+    else GEGLU_TAB(false, false);
+#undef GEGLU_TAB
     return launch_status();
   }
-  if (flags & MIXDQ_FLAG_UNFUSED)
-    geglu_quant_kernel<true><<<(int)blocks, 256, 0, stream>>>(
-        (const __half*)h, M, D, scale_inv, zero_point, out_q_or_null, (__half*)out_f16_or_null);
-  else
-    geglu_quant_kernel<false><<<(int)blocks, 256, 0, stream>>>(
-        (const __half*)h, M, D, scale_inv, zero_point, out_q_or_null, (__half*)out_f16_or_null);
+#define GEGLU(U, A)                                                                                        \
+  geglu_quant_kernel<U, A><<<(int)blocks, 256, 0, stream>>>(                                                \
+      (const __half*)h, M, D, scale_inv, zero_point, out_q_or_null, (__half*)out_f16_or_null)
+  if (a4) { if (flags & MIXDQ_FLAG_UNFUSED) GEGLU(true, true); else GEGLU(false, true); }
+  else if (flags & MIXDQ_FLAG_UNFUSED) GEGLU(true, false);
+  else GEGLU(false, false);
+#undef GEGLU
   return launch_status();
 }

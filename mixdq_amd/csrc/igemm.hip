@@ -395,14 +395,15 @@ int dispatch(IgemmParams& p, hipStream_t stream, int forced_cfg) {
 
 // to_q GEMM + cross-attention epilogue: the 64x128x128 8-wave tile (two heads per tile), Linear
 // fast path only.
-template <int WBITS>
+template <int WBITS, bool A4 = false>
 int launch_att(IgemmParams& p, hipStream_t stream) {
   constexpr int BM = 64, BN = 128, BK = 128, ST = 3;
   constexpr int SMEM = ((igemm_smem_bytes<BM, BN, BK, ST>() + 1023) / 1024) * 1024 + 4 * kStageBytes;
   static_assert(SMEM <= 160 * 1024, "LDS is 160 KiB per CU");
   static bool seen[64] = {};
   if (const int st = lds_opt_in(
-          reinterpret_cast<const void*>(&igemm_kernel<BM, BN, BK, ST, 2, 4, false, true, WBITS, 1, 32, false, true>),
+          reinterpret_cast<const void*>(
+              &igemm_kernel<BM, BN, BK, ST, 2, 4, false, true, WBITS, 1, 32, false, true, false, false, false, false, A4>),
           SMEM, seen))
     return st;
   p.tiles_m = (int)((p.M + BM - 1) / BM);
@@ -410,7 +411,7 @@ int launch_att(IgemmParams& p, hipStream_t stream) {
   p.gm = tile_map_gm();
   const int64_t grid = (int64_t)p.tiles_m * p.tiles_n;
   if (grid <= 0 || grid > 0x7fffffff || p.tiles_m >= (1 << 24)) return MIXDQ_ERR_INVALID_ARG;
-  igemm_kernel<BM, BN, BK, ST, 2, 4, false, true, WBITS, 1, 32, false, true>
+  igemm_kernel<BM, BN, BK, ST, 2, 4, false, true, WBITS, 1, 32, false, true, false, false, false, false, A4>
       <<<dim3((unsigned)grid), 512, SMEM, stream>>>(MIXDQ_IGEMM_HEAD_ARGS(p) p);
   return launch_status();
 }
@@ -570,6 +571,8 @@ extern "C" int mixdq_qlinear_w8a8_geglu(const int8_t* A, const int8_t* W, const 
                                         int8_t* out_i8, int64_t M, int N, int K,
                                         const float* out_scale_inv, const float* out_zero_point,
                                         int flags, mixdq_stream_t stream) {
+  // 8-bit output quantizer only (incl. the persistent tile): the caller runs the GEMM to FP16 and mixdq_geglu_quantize
+  if (flags & MIXDQ_FLAG_A4_ANY) return MIXDQ_ERR_UNSUPPORTED;
   if (M < 0 || N < 0 || K < 0) return MIXDQ_ERR_INVALID_ARG;
   if (M == 0 || N == 0) return MIXDQ_OK;
   if (!A || !W || !bias0 || !scale || !out_i8 || !out_scale_inv || !out_zero_point)
@@ -657,6 +660,10 @@ extern "C" int mixdq_qlinear_w8a8_attn(const int8_t* A, const int8_t* W, const f
   p.att_tkv = tkv; p.att_tq = rows_per_image;
   p.att_scale_log2 = softmax_scale * 1.4426950408889634f;
   p.att_out = out; p.att_sinv = out_scale_inv_or_null; p.att_zp = out_zero_point_or_null;
+  if (flags & (MIXDQ_FLAG_A4_1 | MIXDQ_FLAG_A4_2)) return MIXDQ_ERR_UNSUPPORTED;   // one quantizer: slot 0
+  if (out_scale_inv_or_null && (flags & MIXDQ_FLAG_A4_0))
+    return w2 ? launch_att<2, true>(p, (hipStream_t)stream)
+         : w4 ? launch_att<4, true>(p, (hipStream_t)stream) : launch_att<8, true>(p, (hipStream_t)stream);
   return w2 ? launch_att<2>(p, (hipStream_t)stream)
        : w4 ? launch_att<4>(p, (hipStream_t)stream) : launch_att<8>(p, (hipStream_t)stream);
 }

@@ -412,7 +412,7 @@ __device__ __forceinline__ void aq_wait4(v4i& a, v4i& b, v4i& c, v4i& d) {
 
 template <int BM, int BN, int BK, int STAGES, int WM, int WN, bool CONV, bool FAST, int WBITS,
           int KSPLIT = 1, int MT = 32, bool F16 = false, bool ATT = false, bool PHASED = false,
-          bool GROUPED = false, bool AQ = false, bool LNQ = false>
+          bool GROUPED = false, bool AQ = false, bool LNQ = false, bool ATT_A4 = false>
 __global__ __launch_bounds__(
     64 * WM * WN * KSPLIT,
     (ATT ? 2 : igemm_waves_per_simd<BM, BN, BK, STAGES, WM * WN * KSPLIT,
@@ -429,6 +429,8 @@ void igemm_kernel(MIXDQ_IGEMM_HEAD_PARAMS const IgemmParams p_in) {
   static_assert(!ATT || (BM == 64 && BN == 128 && NWAVES_OF(WM, WN, KSPLIT) == 8 && MT == 32 && !CONV &&
                          !F16), "the attention epilogue is written for the 64x128 8-wave tile");
   static_assert(!(CONV && FAST), "the fast staging path is for Linear");
+  // ATT_A4: the attention output is to_out.0's operand for a 4-bit activation quantizer (MIXDQ_FLAG_A4_0)
+  static_assert(!ATT_A4 || ATT, "the 4-bit output clamp belongs to the attention epilogue");
   // AQ -- quantize-in-prologue (replaces the reference's quantize launch in front of every layer,
   // nn/Linear.py:162-176): the activation operand is read as FP16 into registers (16 bytes = 8 values per
   // lane and load), quantized there -- q = sat8(rint(fma(x, s_inv, zp))), the arithmetic of
@@ -1776,7 +1778,7 @@ void igemm_kernel(MIXDQ_IGEMM_HEAD_PARAMS const IgemmParams p_in) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) x[j] = __half2float(hv[j]);
         *reinterpret_cast<uint2*>(reinterpret_cast<int8_t*>(p.att_out) + off) =
-            unf ? quantize_pack8<true>(x, s_inv, zpq) : quantize_pack8<false>(x, s_inv, zpq);
+            unf ? quantize_pack8<true, ATT_A4>(x, s_inv, zpq) : quantize_pack8<false, ATT_A4>(x, s_inv, zpq);
       }
     }
     return;

@@ -14,7 +14,7 @@ namespace {
 struct alignas(16) Half8 { uint32_t w[4]; };
 struct alignas(8) Char8 { uint32_t w[2]; };
 
-template <bool UNFUSED>
+template <bool UNFUSED, bool A4>
 __device__ __forceinline__ Char8 quantize8(const Half8& h, float s_inv, float zp) {
   float x[8];
 #pragma unroll
@@ -24,20 +24,20 @@ __device__ __forceinline__ Char8 quantize8(const Half8& h, float s_inv, float zp
     hr.x = (unsigned short)((j & 1) ? (w >> 16) : (w & 0xffffu));
     x[j] = __half2float(__half(hr));
   }
-  const uint2 q = quantize_pack8<UNFUSED>(x, s_inv, zp);     // common.h: clamp + packing by v_ashr_pk_i8_i32 / v_perm_b32
+  const uint2 q = quantize_pack8<UNFUSED, A4>(x, s_inv, zp);     // common.h: clamp + packing by v_ashr_pk_i8_i32 / v_perm_b32
   Char8 out;
   out.w[0] = q.x;
   out.w[1] = q.y;
   return out;
 }
 
-template <bool UNFUSED>
+template <bool UNFUSED, bool A4>
 __device__ __forceinline__ int8_t quantize1(const __half* p, float s_inv, float zp) {
-  return (int8_t)quantize_one<UNFUSED>(__half2float(*p), s_inv, zp);
+  return (int8_t)quantize_one<UNFUSED, A4>(__half2float(*p), s_inv, zp);
 }
 
 // Dense: x and out are linear over numel elements.
-template <bool UNFUSED>
+template <bool UNFUSED, bool A4 = false>
 __global__ __launch_bounds__(256) void quantize_dense_kernel(const __half* __restrict__ x,
                                                              int8_t* __restrict__ out,
                                                              const float* __restrict__ s_inv_p,
@@ -53,16 +53,16 @@ __global__ __launch_bounds__(256) void quantize_dense_kernel(const __half* __res
   // 4 independent 16-B loads in flight per lane
   for (; i + 3 * stride < nvec; i += 4 * stride) {
     Half8 a = xv[i], b = xv[i + stride], c = xv[i + 2 * stride], d = xv[i + 3 * stride];
-    ov[i] = quantize8<UNFUSED>(a, s_inv, zp);
-    ov[i + stride] = quantize8<UNFUSED>(b, s_inv, zp);
-    ov[i + 2 * stride] = quantize8<UNFUSED>(c, s_inv, zp);
-    ov[i + 3 * stride] = quantize8<UNFUSED>(d, s_inv, zp);
+    ov[i] = quantize8<UNFUSED, A4>(a, s_inv, zp);
+    ov[i + stride] = quantize8<UNFUSED, A4>(b, s_inv, zp);
+    ov[i + 2 * stride] = quantize8<UNFUSED, A4>(c, s_inv, zp);
+    ov[i + 3 * stride] = quantize8<UNFUSED, A4>(d, s_inv, zp);
   }
-  for (; i < nvec; i += stride) ov[i] = quantize8<UNFUSED>(xv[i], s_inv, zp);
+  for (; i < nvec; i += stride) ov[i] = quantize8<UNFUSED, A4>(xv[i], s_inv, zp);
   // tail (numel % 8 elements), by the first threads of block 0
   const int64_t tail0 = nvec << 3;
   if (blockIdx.x == 0 && threadIdx.x < (numel - tail0)) {
-    out[tail0 + threadIdx.x] = quantize1<UNFUSED>(x + tail0 + threadIdx.x, s_inv, zp);
+    out[tail0 + threadIdx.x] = quantize1<UNFUSED, A4>(x + tail0 + threadIdx.x, s_inv, zp);
   }
 }
 
@@ -73,7 +73,7 @@ struct StridedArgs {
 };
 
 // Strided, inner dimension contiguous on both sides and vectorisable by 8.
-template <bool UNFUSED>
+template <bool UNFUSED, bool A4 = false>
 __global__ __launch_bounds__(256) void quantize_rows_kernel(const __half* __restrict__ x,
                                                             int8_t* __restrict__ out,
                                                             const float* __restrict__ s_inv_p,
@@ -94,12 +94,12 @@ __global__ __launch_bounds__(256) void quantize_rows_kernel(const __half* __rest
     const __half* xp = x + i0 * a.xs[0] + i1 * a.xs[1] + i2 * a.xs[2] + v * 8;
     int8_t* op = out + i0 * a.os[0] + i1 * a.os[1] + i2 * a.os[2] + v * 8;
     *reinterpret_cast<Char8*>(op) =
-        quantize8<UNFUSED>(*reinterpret_cast<const Half8*>(xp), s_inv, zp);
+        quantize8<UNFUSED, A4>(*reinterpret_cast<const Half8*>(xp), s_inv, zp);
   }
 }
 
 // Fully general: one element per thread-step.
-template <bool UNFUSED>
+template <bool UNFUSED, bool A4 = false>
 __global__ __launch_bounds__(256) void quantize_scalar_kernel(const __half* __restrict__ x,
                                                               int8_t* __restrict__ out,
                                                               const float* __restrict__ s_inv_p,
@@ -116,7 +116,7 @@ __global__ __launch_bounds__(256) void quantize_scalar_kernel(const __half* __re
     r /= a.size[2];
     int64_t i1 = r % a.size[1];
     int64_t i0 = r / a.size[1];
-    out[i0 * a.os[0] + i1 * a.os[1] + i2 * a.os[2] + i3 * a.os[3]] = quantize1<UNFUSED>(
+    out[i0 * a.os[0] + i1 * a.os[1] + i2 * a.os[2] + i3 * a.os[3]] = quantize1<UNFUSED, A4>(
         x + i0 * a.xs[0] + i1 * a.xs[1] + i2 * a.xs[2] + i3 * a.xs[3], s_inv, zp);
   }
 }
@@ -140,7 +140,8 @@ extern "C" int mixdq_quantize_f16_i8(const void* x_f16, int8_t* out, const int64
                                      int flags, mixdq_stream_t stream_) {
   if (ndim < 0 || ndim > 8 || !scale_inv || !zero_point) return MIXDQ_ERR_INVALID_ARG;
   hipStream_t stream = (hipStream_t)stream_;
-  const bool unfused = flags & MIXDQ_FLAG_UNFUSED;
+  if (flags & (MIXDQ_FLAG_A4_1 | MIXDQ_FLAG_A4_2)) return MIXDQ_ERR_UNSUPPORTED;   // one quantizer: slot 0
+  const bool unfused = flags & MIXDQ_FLAG_UNFUSED, a4 = flags & MIXDQ_FLAG_A4_0;
   // ---- sort dims by x stride (descending), drop size-1 dims, collapse mergeable neighbours ----
   int64_t sz[8], xs[8], os[8];
   int n = 0;
@@ -176,10 +177,14 @@ extern "C" int mixdq_quantize_f16_i8(const void* x_f16, int8_t* out, const int64
 
   if (m == 1 && xs[0] == 1 && os[0] == 1 && aligned) {
     int grid = grid_for((numel >> 3) + 1);
-    if (unfused)
-      quantize_dense_kernel<true><<<grid, 256, 0, stream>>>(x, out, scale_inv, zero_point, numel);
-    else
-      quantize_dense_kernel<false><<<grid, 256, 0, stream>>>(x, out, scale_inv, zero_point, numel);
+#define Q_LAUNCH(K, ...)                                                              \
+  do {                                                                                \
+    if (a4) { if (unfused) K<true, true><<<grid, 256, 0, stream>>>(__VA_ARGS__);     \
+              else K<false, true><<<grid, 256, 0, stream>>>(__VA_ARGS__); }          \
+    else if (unfused) K<true><<<grid, 256, 0, stream>>>(__VA_ARGS__);                 \
+    else K<false><<<grid, 256, 0, stream>>>(__VA_ARGS__);                             \
+  } while (0)
+    Q_LAUNCH(quantize_dense_kernel, x, out, scale_inv, zero_point, numel);
     return launch_status();
   }
   StridedArgs a;
@@ -192,16 +197,11 @@ extern "C" int mixdq_quantize_f16_i8(const void* x_f16, int8_t* out, const int64
     if (a.size[i] > 1 && (a.xs[i] % 8 != 0 || a.os[i] % 8 != 0)) rows_ok = false;
   if (rows_ok) {
     int grid = grid_for(numel >> 3);
-    if (unfused)
-      quantize_rows_kernel<true><<<grid, 256, 0, stream>>>(x, out, scale_inv, zero_point, a);
-    else
-      quantize_rows_kernel<false><<<grid, 256, 0, stream>>>(x, out, scale_inv, zero_point, a);
+    Q_LAUNCH(quantize_rows_kernel, x, out, scale_inv, zero_point, a);
   } else {
     int grid = grid_for(numel);
-    if (unfused)
-      quantize_scalar_kernel<true><<<grid, 256, 0, stream>>>(x, out, scale_inv, zero_point, a);
-    else
-      quantize_scalar_kernel<false><<<grid, 256, 0, stream>>>(x, out, scale_inv, zero_point, a);
+    Q_LAUNCH(quantize_scalar_kernel, x, out, scale_inv, zero_point, a);
   }
+#undef Q_LAUNCH
   return launch_status();
 }

@@ -32,13 +32,16 @@ quant_op = quantize_per_tensor_vectorized
 _INT8 = (torch.qint8, torch.quint8)
 
 
-def _w8a8_ok(w_qparams, a_qparams, w4_kernel=False) -> bool:
+def _w8a8_ok(w_qparams, a_qparams, w4_kernel=False, a4=False) -> bool:
     """nn/Linear.py:27-36: per-channel symmetric int8 weights, per-tensor int8 activations.
-    With w4_kernel (this build's W4A8 path, off by default) 4-bit weights qualify too."""
+    With w4_kernel (this build's W4A8 path, off by default) 4-bit weights qualify too; with `a4` (a 4-bit
+    activation layer under a4_kernel) per-tensor quint4x2 activations do."""
     w_ok = w_qparams is not None and (
         w_qparams.dtype in _INT8 or (w4_kernel and w_qparams.dtype == torch.quint4x2))
+    a_ok = a_qparams is not None and (
+        a_qparams.dtype in _INT8 or (a4 and a_qparams.dtype == torch.quint4x2))
     return bool(
-        w_ok and a_qparams is not None and a_qparams.dtype in _INT8
+        w_ok and a_ok
         and w_qparams.qscheme == torch.per_channel_affine
         and a_qparams.qscheme == torch.per_tensor_affine
         and torch.all(w_qparams.zero_points == 0.0).item())
@@ -58,10 +61,17 @@ class QuantizedLinear(nn.Module):
     # INT8 MFMA kernels with an in-kernel unpack.  Set per float module or via
     # quantize_unet(..., w2_kernel=True).
     w2_kernel = False
+    # 4-bit activations on the INT8 kernels (off by default).  False = the reference's behaviour: a layer whose
+    # activation quantizer is 4-bit (a_bit == 4, quint4x2) keeps its FP16 weight and runs F.linear.  True: such a
+    # layer qualifies whenever its weight does under the weight flags (int8; 4-bit with w4_kernel; 2-bit with
+    # w2_kernel) and its INT8 operand is the int8 quantizer clamped to [-128, -113] -- Path A's 4-bit quantizer
+    # (include/mixdq_hip.h MIXDQ_FLAG_A4_0).  Set per float module or via quantize_unet(..., a4_kernel=True).
+    a4_kernel = False
+    act_bits = 8        # width of the activation quantizer of an accelerated layer (4: a4_kernel)
 
     def __init__(self, in_features: int, out_features: int, bias: bool = True, device=None,
                  w_qparams=None, a_qparams=None, module_name=None, w4_kernel=False,
-                 w2_kernel=False, w_bit=None) -> None:
+                 w2_kernel=False, w_bit=None, a4_kernel=False, a_bit=None) -> None:
         super().__init__()
         self.module_name = module_name
         self.in_features = in_features
@@ -69,7 +79,9 @@ class QuantizedLinear(nn.Module):
         self.device = device
         packable = w_qparams is not None and w_qparams.dtype == torch.quint4x2
         w2 = bool(w2_kernel and packable and w_bit is not None and int(w_bit) == 2 and in_features % 64 == 0)
-        self.valid_for_acceleration = _w8a8_ok(w_qparams, a_qparams, w4_kernel or w2)
+        a4 = bool(a4_kernel and a_bit is not None and int(a_bit) == 4 and a_qparams is not None
+                  and a_qparams.dtype == torch.quint4x2)
+        self.valid_for_acceleration = _w8a8_ok(w_qparams, a_qparams, w4_kernel or w2, a4)
         if self.valid_for_acceleration and w4_kernel and packable and not w2 and in_features % 32 != 0:
             self.valid_for_acceleration = False      # packed pieces span 32 input channels
         if self.valid_for_acceleration and (in_features % 4 != 0 or out_features % 4 != 0):
@@ -81,6 +93,8 @@ class QuantizedLinear(nn.Module):
         # decided on the final validity: an FP-fallback layer stores no integers and is not W2
         self.w_packed2 = w2 and self.valid_for_acceleration
         self.w_packed4 = bool(w4_kernel and packable) and not self.w_packed2
+        if a4 and self.valid_for_acceleration:
+            self.act_bits = 4
         if self.valid_for_acceleration:
             self.register_buffer("weight_scales", w_qparams.scales.to(device).float())
             self.register_buffer("weight_zero_points", w_qparams.zero_points.to(device).float())
@@ -109,7 +123,9 @@ class QuantizedLinear(nn.Module):
                       module_name=float_mod.module_name,
                       w4_kernel=getattr(float_mod, "w4_kernel", cls.w4_kernel),
                       w2_kernel=getattr(float_mod, "w2_kernel", cls.w2_kernel),
-                      w_bit=getattr(float_mod, "w_bit", None))
+                      w_bit=getattr(float_mod, "w_bit", None),
+                      a4_kernel=getattr(float_mod, "a4_kernel", cls.a4_kernel),
+                      a_bit=getattr(float_mod, "a_bit", None))
         weight = float_mod.weight.detach()
         name = float_mod.module_name
         if "attn2" in name and ("to_k" in name or "to_v" in name):
@@ -148,9 +164,14 @@ class QuantizedLinear(nn.Module):
     def _get_name(self):
         if not self.valid_for_acceleration:
             return "QuantizedLinearFPFallback"
-        if getattr(self, "w_packed2", False):
-            return "QuantizedLinearW2A8"
-        return "QuantizedLinearW4A8" if self.w_packed4 else "QuantizedLinearW8A8"
+        w = 2 if getattr(self, "w_packed2", False) else 4 if self.w_packed4 else 8
+        return f"QuantizedLinearW{w}A{self.act_bits}"
+
+    def _quant(self, x):
+        """quant_op(x) with this layer's quantizer (a 4-bit one: the _abits=4 form)."""
+        if self.act_bits == 4:
+            return quant_op(x, self.act_scales_inv, self.act_zero_points, _abits=4)
+        return quant_op(x, self.act_scales_inv, self.act_zero_points)
 
     def _weight_values(self):
         if getattr(self, "w_packed2", False):
@@ -276,18 +297,20 @@ class QuantizedLinear(nn.Module):
                 return self._gemm(x_int)
             # the reference's two launches (nn/Linear.py:162-176) as one wherever the quantizing GEMM
             # takes the shape; otherwise literally: quantize, then GEMM
-            if qlinear_f16in_wanted(x, N, K, w4=self.w_packed4, w2=getattr(self, "w_packed2", False)):
+            if qlinear_f16in_wanted(x, N, K, w4=self.w_packed4, w2=getattr(self, "w_packed2", False),
+                                    abits=self.act_bits):
                 return self._gemm_f16in(x)
-            return self._gemm(quant_op(x, self.act_scales_inv, self.act_zero_points))
+            return self._gemm(self._quant(x))
         # BOS carve-out: token 0 is a precomputed FP16 row, tokens 1.. go through the kernels
         out = _bos_out
         if out is not None and not (out.shape == (x.shape[0], x.shape[1], N) and out.dtype == torch.float16
                                     and out.device == x.device and out.is_contiguous()):
             out = None
-        if qlinear_f16in_wanted(x, N, K, w4=self.w_packed4, bos=True, w2=getattr(self, "w_packed2", False)):
+        if qlinear_f16in_wanted(x, N, K, w4=self.w_packed4, bos=True, w2=getattr(self, "w_packed2", False),
+                                abits=self.act_bits):
             if out is None:
                 out = torch.empty((x.shape[0], x.shape[1], N), dtype=torch.float16, device=x.device)
                 out[:, :1, :] = self.bos_pre_computed
             return self._gemm_f16in(x, out=out, bos=True)
-        x_int = quant_op(x[:, 1:, :], self.act_scales_inv, self.act_zero_points)
+        x_int = self._quant(x[:, 1:, :])
         return self.forward_bos_quantized(x_int, x.shape[0], x.shape[1], out=out)

@@ -42,7 +42,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 _ACT_TAG = "_mixdq_silu_applied"
-_OPS_TAG = "_mixdq_operands"        # on an FP16 tensor: (its _version, [(scale_inv, zero_point, int8 tensor), ...])
+_OPS_TAG = "_mixdq_operands"        # on an FP16 tensor: (its _version, [(scale_inv, zero_point, bits, int8), ...])
 _CONSUMERS = "_mixdq_consumers"     # in a swapped producer's __dict__: the layers its parent hands its output to
 
 
@@ -57,6 +57,11 @@ def _takes_operand(m) -> bool:
                 and not getattr(m, "split", 0) and hasattr(m, "act_scales_inv"))
 
 
+def _abits(m) -> int:
+    """Width of a layer's activation quantizer (8, or 4: QuantizedLinear.act_bits under a4_kernel)."""
+    return getattr(m, "act_bits", 8)
+
+
 def _consumers(mod, width, device):
     """The linked layers that would quantize a [.., width] tensor on `device` with a quantizer that lives there."""
     return [c for c in mod.__dict__.get(_CONSUMERS, ())
@@ -65,21 +70,22 @@ def _consumers(mod, width, device):
 
 
 def _attach(y, consumers, ints):
-    """`ints[i]`: quantize(y) with consumers[i]'s quantizer (or None)."""
-    ops = [(c.act_scales_inv, c.act_zero_points, q) for c, q in zip(consumers, ints) if q is not None]
+    """`ints[i]`: quantize(y) with consumers[i]'s quantizer, at its width (or None)."""
+    ops = [(c.act_scales_inv, c.act_zero_points, _abits(c), q) for c, q in zip(consumers, ints) if q is not None]
     if ops:
         setattr(y, _OPS_TAG, (y._version, ops))
     return y
 
 
 def tagged_operand(x, layer):
-    """The INT8 operand a swapped producer attached to `x` for `layer`'s activation quantizer, or None."""
+    """The INT8 operand a swapped producer attached to `x` for `layer`'s activation quantizer, or None.  The width
+    is part of the quantizer: an operand clamped to 8 bits is never handed to a 4-bit layer, nor the reverse."""
     tag = getattr(x, _OPS_TAG, None)
     if tag is None or tag[0] != x._version:
         return None
-    s, z = layer.act_scales_inv, layer.act_zero_points
-    for ts, tz, q in tag[1]:
-        if ts is s and tz is z and q.shape == x.shape and q.device == x.device:
+    s, z, b = layer.act_scales_inv, layer.act_zero_points, _abits(layer)
+    for ts, tz, tb, q in tag[1]:
+        if ts is s and tz is z and tb == b and q.shape == x.shape and q.device == x.device:
             return q
     return None
 
@@ -96,7 +102,8 @@ class HipGroupNorm(nn.GroupNorm):
                 and x.is_contiguous(memory_format=torch.channels_last)
                 and _C.groupnorm_supported(x.shape[0], x.shape[2] * x.shape[3], x.shape[1], self.num_groups)):
             # (the consumer reads silu(norm(x)): its operand can ride along only where the SiLU does)
-            cons = _consumers(self, x.shape[1], x.device)[:1] if self.fuse_silu else []
+            # (8-bit quantizers only: the GroupNorm launch refuses a 4-bit clamp)
+            cons = [c for c in _consumers(self, x.shape[1], x.device) if _abits(c) == 8][:1] if self.fuse_silu else []
             qp = (cons[0].act_scales_inv, cons[0].act_zero_points) if cons else (None, None)
             q, y = _C.groupnorm_silu_quantize(x, self.num_groups, self.weight, self.bias, self.eps, *qp,
                                               silu=self.fuse_silu, want_f16=True)[:2]
@@ -135,7 +142,7 @@ class HipLayerNorm(nn.LayerNorm):
             order = sorted(first)[:3]
             outs, y = _C.layernorm_quantize(x, self.weight, self.bias, self.eps,
                                             [(first[i].act_scales_inv, first[i].act_zero_points) for i in order],
-                                            want_f16=True)
+                                            want_f16=True, _abits=[_abits(first[i]) for i in order])
             return _attach(y, cons, [outs[order.index(i)] if i in order else None for i in ids])
         return super().forward(x)
 
@@ -151,7 +158,7 @@ class _HipGEGLU:
         if _f16_cuda(h) and h.is_contiguous() and h.shape[-1] % 16 == 0:
             cons = _consumers(self, h.shape[-1] // 2, h.device)[:1]
             qp = (cons[0].act_scales_inv, cons[0].act_zero_points) if cons else (None, None)
-            q, y = _C.geglu_quantize(h, *qp, want_f16=True)
+            q, y = _C.geglu_quantize(h, *qp, want_f16=True, _abits=_abits(cons[0]) if cons else 8)
             return _attach(y, cons, [q])
         v, g = h.chunk(2, dim=-1)
         return v * F.gelu(g)
@@ -213,11 +220,10 @@ def _project_kv(to_k, to_v, ctx):
         ids = _quantizer_groups(to_k.__dict__.setdefault("_mixdq_memo", {}), "glue_kv", [to_k, to_v])
         if ids[0] == ids[1] and not any(
                 _C.qlinear_f16in_wanted(ctx, m.out_features, m.in_features, w4=m.w_packed4, bos=True,
-                                        w2=getattr(m, "w_packed2", False))
+                                        w2=getattr(m, "w_packed2", False), abits=_abits(m))
                 for m in (to_k, to_v)):
             B, T = ctx.shape[0], ctx.shape[1]
-            from mixdq_amd.op.quant import quantize_per_tensor_vectorized as quant_op
-            x_int = quant_op(ctx[:, 1:, :], to_k.act_scales_inv, to_k.act_zero_points)
+            x_int = to_k._quant(ctx[:, 1:, :])          # (equal ids: equal quantizers of equal width)
             # (out=None: forward_bos_quantized allocates and fills row 0 itself, as the reference does)
             return (to_k.forward_bos_quantized(x_int, B, T, out=_bos_buffer(to_k, ctx)),
                     to_v.forward_bos_quantized(x_int, B, T, out=_bos_buffer(to_v, ctx)))
@@ -240,7 +246,7 @@ def _attention_core(q, k, v, heads, out_layer=None):
         if (_takes_operand(out_layer) and getattr(out_layer, "in_features", None) == C
                 and out_layer.act_scales_inv.device == q.device):
             return out_layer._gemm(_C.attention_f16(q, k, v, heads, out_layer.act_scales_inv,
-                                                    out_layer.act_zero_points))
+                                                    out_layer.act_zero_points, _abits=_abits(out_layer)))
         return out_layer(_C.attention_f16(q, k, v, heads))
     return _C.attention_f16(q, k, v, heads)
 
@@ -249,8 +255,7 @@ def _operand(x, layer):
     """quantize(x) with `layer`'s quantizer: the one its producer attached, else the layer's own quantize launch."""
     q = tagged_operand(x, layer)
     if q is None:
-        from mixdq_amd.op.quant import quantize_per_tensor_vectorized as quant_op
-        q = quant_op(x, layer.act_scales_inv, layer.act_zero_points)
+        q = layer._quant(x)
     return q
 
 
@@ -300,7 +305,7 @@ def _cross_one_launch(attn, x, k, v):
             and _C.qlinear_attention_supported(x.shape, q.out_features, q.in_features, k)):
         return None
     o_int = _C.qlinear_attention(_operand(x, q), q.weight_storage()[0], q.scale, q.bias0,
-                                 k, v, out.act_scales_inv, out.act_zero_points, **q._wkw())
+                                 k, v, out.act_scales_inv, out.act_zero_points, **q._wkw(), _abits=_abits(out))
     return out._gemm(o_int)
 
 

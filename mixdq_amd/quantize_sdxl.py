@@ -98,7 +98,7 @@ def convert_to_quantized(unet, ckpt):
 
 
 def quantize_unet(unet, args, ckpt, bos, bos_dict, w4_kernel=False, swap_glue=False, swap_attention=None,
-                  swap_operands=True, w2_kernel=False):
+                  swap_operands=True, w2_kernel=False, a4_kernel=False):
     """The reference's call (quantize_sdxl.py:154-156) plus three options it does not have:
     `w4_kernel=True`: 4-/2-bit weight layers run the packed-W4 INT8 kernels instead of falling back to FP16
     (mixdq_amd.nn.QuantizedLinear.w4_kernel);
@@ -106,6 +106,9 @@ def quantize_unet(unet, args, ckpt, bos, bos_dict, w4_kernel=False, swap_glue=Fa
     run the packed-W2 INT8 kernels (mixdq_amd.nn.QuantizedLinear.w2_kernel; independent of `w4_kernel`, which
     keeps deciding what the 4-bit layers -- and 2-bit layers W2 cannot take -- do; the reference stores 2 bits
     as 4, the TODO in its loader's bw_to_dtype);
+    `a4_kernel=True`: Linears with a 4-bit activation quantizer run the INT8 kernels on an operand clamped to the
+    4-bit range, as Path A's simulation quantizes them, instead of falling back to FP16 as the reference's kernel
+    path does (mixdq_amd.nn.QuantizedLinear.a4_kernel; the weight still qualifies by the two flags above);
     `swap_glue=True`: the stock glue modules BETWEEN the quantized layers -- nn.GroupNorm (+ the nn.SiLU behind
     it), nn.LayerNorm, GEGLU -- are swapped by type for this repo's FP16-output kernels, and (`swap_attention`,
     default: as `swap_glue`) the FP16 attention core for mixdq_attention_f16: same graph, same names, same
@@ -121,6 +124,10 @@ def quantize_unet(unet, args, ckpt, bos, bos_dict, w4_kernel=False, swap_glue=Fa
         for mod in unet.modules():
             if getattr(mod, "w_bit", 8) == 2:
                 mod.w2_kernel = True
+    if a4_kernel:
+        for mod in unet.modules():
+            if getattr(mod, "a_bit", 8) == 4 and isinstance(mod, nn.Linear):
+                mod.a4_kernel = True
     convert_to_quantized(unet, ckpt)
     if swap_glue or swap_attention:
         from mixdq_amd.nn.glue import swap_glue_modules

@@ -65,11 +65,23 @@ def _qp(m):
     return (m.act_scales_inv, m.act_zero_points)
 
 
+def _abits(m) -> int:
+    """Width of a layer's activation quantizer: 8, or 4 for an a4_kernel layer (QuantizedLinear.act_bits).  A
+    producer that writes the layer's INT8 operand must clamp to it (include/mixdq_hip.h MIXDQ_FLAG_A4_0)."""
+    return getattr(m, "act_bits", 8)
+
+
+def _a8(m) -> bool:
+    """The layer's quantizer is an 8-bit one: the producers that refuse a 4-bit clamp (GroupNorm, GEMM + GEGLU,
+    GEMM + LayerNorm) may write its operand."""
+    return _abits(m) == 8
+
+
 def _same_qparams(a, b) -> bool:
-    """Host comparison of two layers' activation qparams (a device sync: cached by callers, and
-    only ever evaluated in the eager warm-up that precedes graph capture)."""
+    """Host comparison of two layers' activation quantizers -- qparams AND width (a device sync: cached by
+    callers, and only ever evaluated in the eager warm-up that precedes graph capture)."""
     return bool(torch.equal(a.act_scales_inv, b.act_scales_inv)
-                and torch.equal(a.act_zero_points, b.act_zero_points))
+                and torch.equal(a.act_zero_points, b.act_zero_points) and _abits(a) == _abits(b))
 
 
 def _fusable_f16(x) -> bool:
@@ -87,11 +99,12 @@ def _fusable_f16(x) -> bool:
 #     updates reach the packed launch -- and every captured graph -- by construction.
 # ---------------------------------------------------------------------------------------------
 def _quantizer_groups(holder: dict, key, layers):
-    """Group id per layer: equal activation qparams <=> equal id.  One device->host copy (a sync:
-    only ever taken in the eager warm-up that precedes graph capture), memoised in `holder[key]`
-    against the identity and in-place version of the qparam tensors."""
+    """Group id per layer: equal activation quantizers -- qparams and width (8 / 4 bits) -- <=> equal id.  One
+    device->host copy (a sync: only ever taken in the eager warm-up that precedes graph capture), memoised in
+    `holder[key]` against the identity and in-place version of the qparam tensors and the layers' widths."""
     src = [t for m in layers for t in (m.act_scales_inv, m.act_zero_points)]
-    ver = tuple(t._version for t in src)
+    bits = [_abits(m) for m in layers]
+    ver = tuple(t._version for t in src) + tuple(bits)
     e = holder.get(key)
     if (e is not None and len(e[0]) == len(src) and all(a is b for a, b in zip(e[0], src))
             and e[1] == ver):
@@ -101,7 +114,7 @@ def _quantizer_groups(holder: dict, key, layers):
         vals = torch.stack([t.detach().reshape(-1)[0].float() for t in src]).cpu().tolist()
         seen = {}
         for i in range(len(layers)):
-            ids.append(seen.setdefault((vals[2 * i], vals[2 * i + 1]), len(seen)))
+            ids.append(seen.setdefault((vals[2 * i], vals[2 * i + 1], bits[i]), len(seen)))
     holder[key] = (src, ver, ids)
     return ids
 
@@ -221,7 +234,7 @@ def _gn_feed(norm: nn.GroupNorm, x, consumer, silu: bool, x2=None, raw_for=None)
             raw_qp = [(raw_for.act_scales_inv, raw_for.act_zero_points)]
             if x2 is not None:
                 raw_qp.append((raw_for.act_scales_inv_0, raw_for.act_zero_points_0))
-        if _accel(consumer):
+        if _accel(consumer) and _a8(consumer):      # (the GroupNorm launch writes 8-bit operands only)
             out = _C.groupnorm_silu_quantize(x, norm.num_groups, norm.weight, norm.bias, norm.eps,
                                              *_qp(consumer), silu=silu, x2=x2, raw_qparams=raw_qp)
             res = (out[0], True)
@@ -268,15 +281,16 @@ def _ln_feed(norm: nn.LayerNorm, x, consumers):
     if not (_fusable_f16(x) and x.is_contiguous() and C % 16 == 0 and C <= 2048):
         h = F.layer_norm(x, norm.normalized_shape, norm.weight, norm.bias, norm.eps)
         return [(h, False)] * len(consumers)
-    groups, slot = _ln_plan(norm, consumers)
+    groups, slot, bits = _ln_plan(norm, consumers)
     want_f16 = any(s < 0 for s in slot)
-    outs, h = _C.layernorm_quantize(x, norm.weight, norm.bias, norm.eps, groups, want_f16=want_f16)
+    outs, h = _C.layernorm_quantize(x, norm.weight, norm.bias, norm.eps, groups, want_f16=want_f16, _abits=bits)
     return [((outs[s], True) if s >= 0 else (h, False)) for s in slot]
 
 
 def _ln_plan(norm, consumers):
     """(distinct (scale_inv, zero_point) pairs among the accelerated consumers, slot of each consumer in that
-    list or -1 for one that takes the FP16 tensor) -- cached on the norm, re-derived when the layers change."""
+    list or -1 for one that takes the FP16 tensor, the width of each distinct quantizer) -- cached on the norm,
+    re-derived when the layers change."""
     acc = [c for c in consumers if _accel(c)]
     ids = _quantizer_groups(_memo(norm), "ln", acc)
     plan = norm.__dict__.get("_mixdq_plan")
@@ -293,8 +307,9 @@ def _ln_plan(norm, consumers):
         # weak references: a plan must not keep swapped-out float layers (and their FP16
         # weights) alive until the next forward
         plan = norm.__dict__["_mixdq_plan"] = (tuple(weakref.ref(c) for c in consumers),
-                                               [_qp(groups[g]) for g in sorted(groups)], slot, ids)
-    return plan[1], plan[2]
+                                               [_qp(groups[g]) for g in sorted(groups)], slot, ids,
+                                               tuple(_abits(groups[g]) for g in sorted(groups)))
+    return plan[1], plan[2], plan[4]
 
 
 # the largest problem a GEMM + LayerNorm launch takes (csrc/igemm_ln.hip select_ln: one 64 x 80 or 128 x 80 tile
@@ -334,8 +349,9 @@ def _gemm_res_ln(layer, x_int, residual, next_ln):
     M = x_int.numel() // K
     if (not DEFUSE and _accel(layer) and _wbits(layer) == 8 and x_int.dtype == torch.int8
             and (residual is None or residual.is_contiguous())
-            and norm.weight.dtype == torch.float16 and _C.qlinear_ln_supported(M, N, K)):
-        groups, slot = _ln_plan(norm, consumers)
+            and norm.weight.dtype == torch.float16 and _C.qlinear_ln_supported(M, N, K)
+            and all(_a8(c) for c in consumers if _accel(c))):     # (8-bit quantizers only in that launch)
+        groups, slot, _ = _ln_plan(norm, consumers)
         want_f16 = any(s_ < 0 for s_ in slot)
         y, outs, h = _C.qlinear_ln(x_int, layer.weight_int, layer.scale, layer.bias0, layer.bias, residual,
                                    norm.weight, norm.bias, norm.eps, groups,
@@ -364,8 +380,7 @@ def _fp_layer(layer) -> bool:
 def _linear_res(layer, x, residual):
     """layer(x) + residual with the add folded into the GEMM epilogue when the layer is W8A8."""
     if _accel(layer) and _fusable_f16(x) and residual.is_contiguous():
-        from mixdq_amd.nn.Linear import quant_op
-        return layer.forward_quantized(quant_op(x, *_qp(layer)), residual=residual)
+        return layer.forward_quantized(layer._quant(x), residual=residual)
     if _fp_layer(layer) and _fusable_f16(x) and not DEFUSE:
         return layer.forward_fp(x, residual=residual)
     return layer(x) + residual
@@ -543,7 +558,7 @@ class Attention(nn.Module):
             from mixdq_amd import _C
             q, out = self.to_q, self.to_out[0]
             o_int = _C.qlinear_attention(feed_q[0], q.weight_storage()[0],
-                                         q.scale, q.bias0, k, v, *_qp(out), **q._wkw())
+                                         q.scale, q.bias0, k, v, *_qp(out), **q._wkw(), _abits=_abits(out))
             return _gemm_res_ln(out, o_int, residual, next_ln)
         return self.attend_out(_run(self.to_q, feed_q), k, v, residual, next_ln=next_ln)
 
@@ -562,7 +577,7 @@ class Attention(nn.Module):
         if not ok:
             return plain(_linear_res(out, self.attend(q, k, v), residual))
         if _accel(out) and residual.is_contiguous():
-            o_int = _C.attention_f16(q, k, v, self.heads, *_qp(out), _prefetch=prefetch)
+            o_int = _C.attention_f16(q, k, v, self.heads, *_qp(out), _prefetch=prefetch, _abits=_abits(out))
             return _gemm_res_ln(out, o_int, residual, next_ln)
         return plain(_linear_res(out, _C.attention_f16(q, k, v, self.heads, _prefetch=prefetch), residual))
 
@@ -695,13 +710,14 @@ class FeedForward(nn.Module):
     def set_interleaved(self, on: bool):
         """Store ff.net.0.proj's rows as value|gate groups of 16 (on) or in the ordinary
         [values | gates] order (off).  Interleaved, one GEMM launch produces net.2's INT8 operand
-        (GEMM + GEGLU + quantize); only W8A8 pairs qualify."""
+        (GEMM + GEGLU + quantize); only pairs whose net.2 has an 8-bit activation quantizer qualify (that
+        launch refuses a 4-bit one: net.2 then gets its operand from the stand-alone GEGLU launch)."""
         from mixdq_amd import _C
         proj, out_layer = self.net[0].proj, self.net[2]
         have = bool(self.__dict__.get("_interleaved"))
         if on == have:
             return
-        if on and not (_accel(proj) and _accel(out_layer) and proj.out_features % 64 == 0
+        if on and not (_accel(proj) and _accel(out_layer) and _a8(out_layer) and proj.out_features % 64 == 0
                        and proj.in_features % 16 == 0 and proj.weight_scales.is_cuda):
             return
         perm = _C.geglu_row_order(proj.out_features // 2, proj.weight_scales.device)
@@ -736,7 +752,7 @@ class FeedForward(nn.Module):
         D = h.shape[-1] // 2
         if _fusable_f16(h) and h.is_contiguous() and D % 8 == 0:
             if _accel(out_layer):
-                q, _ = _C.geglu_quantize(h, *_qp(out_layer))
+                q, _ = _C.geglu_quantize(h, *_qp(out_layer), _abits=_abits(out_layer))
                 return out_layer.forward_quantized(q, residual=residual)
             _, g = _C.geglu_quantize(h, want_f16=True)
             return _run(out_layer, (g, False), residual)
@@ -1055,10 +1071,8 @@ class SDXLUNet(nn.Module):
 
         def ctx_int8(layer):
             g = gid[id(layer)]
-            if g not in shared:
-                from mixdq_amd.nn.Linear import quant_op
-                shared[g] = quant_op(context[:, 1:, :], layer.act_scales_inv,
-                                     layer.act_zero_points)
+            if g not in shared:          # (the group is the quantizer AND its width)
+                shared[g] = layer._quant(context[:, 1:, :])
             return shared[g]
 
         grouped = {}                      # (quantizer group, K, w4) -> [(block, pack)]
@@ -1171,9 +1185,8 @@ class SDXLUNet(nn.Module):
                                []).append((layer, buf))
         from mixdq_amd import _C
         for (g, K, wb), members in grouped.items():
-            from mixdq_amd.nn.Linear import quant_op
             if g not in shared:
-                shared[g] = quant_op(s, *_qp(members[0][0]))
+                shared[g] = members[0][0]._quant(s)
             x_int = shared[g]
             if len(members) == 1:
                 members[0][0]._gemm(x_int, out=members[0][1])
