@@ -30,24 +30,39 @@ quantize launch, and to_q + attention + to_out.0's quantizer are one launch -- t
 each bit-identical to the chain it replaces (tests/test_fused_gpu.py).
 
 The swap changes `module.__class__` to a subclass of the module's own class: parameters, buffers, hooks, names and
-`isinstance` checks are untouched, `unswap_glue_modules` restores the stock classes.  A swapped module falls back to
-its stock forward (PyTorch's op: still the GPU, never a CPU path) for inputs the kernel does not take (FP32, NCHW
-memory, C % 16 != 0 ...).  Arithmetic: each kernel is within one FP16 ulp per rounding point of PyTorch's
-FP32-reference op and bit-equal to the fused graph's `out_h` of the same kernel (tests/test_glue_gpu.py).
+`isinstance` checks are untouched, `unswap_glue_modules` restores the stock classes.  Hooks keep their meaning: a
+forward hook or pre-hook on a module that a folded or direct path would bypass or look past (the GroupNorm and its
+SiLU; to_q / to_k / to_v / to_out.0 inside a swapped attention; or any global module hook) turns that path off, and the
+modules run one by one, each through its own `__call__` -- the module-by-module launch count, the same bits.  A
+swapped module falls back to its stock forward (PyTorch's op: still the GPU, never a CPU path) for inputs the kernel
+does not take (FP32, NCHW memory, C % 16 != 0 ...).  Arithmetic: each kernel is within one FP16 ulp per rounding
+point of PyTorch's FP32-reference op and bit-equal to the fused graph's `out_h` of the same kernel
+(tests/test_glue_gpu.py).
 """
 from __future__ import annotations
+
+import weakref
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+from torch.nn.modules import module as _module
 
-_ACT_TAG = "_mixdq_silu_applied"
+_ACT_TAG = "_mixdq_silu_applied"     # on an FP16 tensor: its _version when HipGroupNorm's launch applied the SiLU
+_SILU_PAIR = "_mixdq_silu_module"    # in a folding HipGroupNorm's __dict__: a weak reference to the SiLU it folds
 _OPS_TAG = "_mixdq_operands"        # on an FP16 tensor: (its _version, [(scale_inv, zero_point, bits, int8), ...])
 _CONSUMERS = "_mixdq_consumers"     # in a swapped producer's __dict__: the layers its parent hands its output to
 
 
 def _f16_cuda(x) -> bool:
     return torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float16
+
+
+def _hooked(*mods) -> bool:
+    """Forward hooks or forward pre-hooks on any of `mods`, or global ones: something may observe or replace a
+    module's input or output, so every module has to run through its own `__call__`."""
+    return bool(_module._global_forward_hooks or _module._global_forward_pre_hooks
+                or any(m._forward_hooks or m._forward_pre_hooks for m in mods))
 
 
 def _takes_operand(m) -> bool:
@@ -93,31 +108,44 @@ def tagged_operand(x, layer):
 class HipGroupNorm(nn.GroupNorm):
     """nn.GroupNorm on the HIP kernel (statistics -> finalize -> apply, fixed reduction order).  `fuse_silu`: the
     parent applies an nn.SiLU to this module's output and to nothing else of it; the activation then runs in the
-    apply pass and the output is tagged so that the (swapped) nn.SiLU module passes it through."""
+    apply pass and the output is tagged so that the (swapped) nn.SiLU module passes it through.  Only while nothing
+    can step in between (`_folds`): a forward hook on this module, or a forward pre-hook on that SiLU, sees or
+    replaces the tensor between the two -- then this launch is the plain norm and the SiLU module does its job."""
     fuse_silu = False
+
+    def _folds(self) -> bool:
+        act = self.__dict__.get(_SILU_PAIR)
+        act = act() if act is not None else None
+        return bool(self.fuse_silu and act is not None and not _hooked(self) and not act._forward_pre_hooks)
 
     def forward(self, x):
         from mixdq_amd import _C
         if (_f16_cuda(x) and x.dim() == 4 and self.affine and self.weight.dtype == torch.float16
                 and x.is_contiguous(memory_format=torch.channels_last)
                 and _C.groupnorm_supported(x.shape[0], x.shape[2] * x.shape[3], x.shape[1], self.num_groups)):
+            silu = self._folds()
             # (the consumer reads silu(norm(x)): its operand can ride along only where the SiLU does)
             # (8-bit quantizers only: the GroupNorm launch refuses a 4-bit clamp)
-            cons = [c for c in _consumers(self, x.shape[1], x.device) if _abits(c) == 8][:1] if self.fuse_silu else []
+            cons = [c for c in _consumers(self, x.shape[1], x.device) if _abits(c) == 8][:1] if silu else []
             qp = (cons[0].act_scales_inv, cons[0].act_zero_points) if cons else (None, None)
             q, y = _C.groupnorm_silu_quantize(x, self.num_groups, self.weight, self.bias, self.eps, *qp,
-                                              silu=self.fuse_silu, want_f16=True)[:2]
-            if self.fuse_silu:
-                setattr(y, _ACT_TAG, True)
+                                              silu=silu, want_f16=True)[:2]
+            if silu:
+                setattr(y, _ACT_TAG, y._version)
             return _attach(y, cons, [q])
         return super().forward(x)
 
 
 class HipSiLU(nn.SiLU):
-    """nn.SiLU that passes through a tensor whose activation already ran in HipGroupNorm's launch."""
+    """nn.SiLU that passes through a tensor whose activation already ran in HipGroupNorm's launch.  A tagged tensor
+    modified in place since is an error: silu(norm(x)) edited can no longer be turned into silu(edited norm(x))."""
 
     def forward(self, x):
-        if getattr(x, _ACT_TAG, False):
+        tag = getattr(x, _ACT_TAG, None)
+        if tag is not None:
+            if tag != x._version:
+                raise RuntimeError("HipSiLU: the output of a SiLU-folding HipGroupNorm was modified in place before "
+                                   "its SiLU module ran; the activation cannot be applied in the right place")
             return x
         return super().forward(x)
 
@@ -178,8 +206,9 @@ def _project_context(layer, ctx):
     row 0 was filled once -- the reference's `out[:, :1] = bos_pre_computed` copy per call (140 launches per step)
     disappears.  Safe HERE because the swapped attention consumes k / v before it returns; every buffer ever handed
     out stays alive with the layer (a captured hipGraph holds its address), and row 0 is re-filled in place when
-    the BOS row changes (load_state_dict: the buffer's in-place version)."""
-    if not _is_bos_layer(layer, ctx):
+    the BOS row changes (load_state_dict: the buffer's in-place version).  A hooked layer gets the plain call: a
+    hook may keep its output, which the next forward would overwrite in a kept buffer."""
+    if _hooked(layer) or not _is_bos_layer(layer, ctx):
         return layer(ctx)
     return layer(ctx, _bos_out=_bos_buffer(layer, ctx))        # (None past BOS_BUFFERS_MAX shapes: the plain call)
 
@@ -214,7 +243,8 @@ def _project_kv(to_k, to_v, ctx):
     """(to_k(ctx), to_v(ctx)) for a swapped attention.  Two BOS layers with EQUAL activation quantizers (they are
     calibrated on the same tensor) share one quantize launch of the context's tokens 1.. -- the reference runs it
     once per layer -- unless the measured table prefers the quantizing GEMM for the shape."""
-    if _is_bos_layer(to_k, ctx) and _is_bos_layer(to_v, ctx) and to_k.in_features == to_v.in_features:
+    if (not _hooked(to_k, to_v) and _is_bos_layer(to_k, ctx) and _is_bos_layer(to_v, ctx)
+            and to_k.in_features == to_v.in_features):
         from mixdq_amd import _C
         from mixdq_amd.unet import _quantizer_groups
         ids = _quantizer_groups(to_k.__dict__.setdefault("_mixdq_memo", {}), "glue_kv", [to_k, to_v])
@@ -243,7 +273,7 @@ def _attention_core(q, k, v, heads, out_layer=None):
                 and t.stride(1) % 8 == 0 and t.data_ptr() % 16 == 0):
             return None
     if out_layer is not None:
-        if (_takes_operand(out_layer) and getattr(out_layer, "in_features", None) == C
+        if (not _hooked(out_layer) and _takes_operand(out_layer) and getattr(out_layer, "in_features", None) == C
                 and out_layer.act_scales_inv.device == q.device):
             return out_layer._gemm(_C.attention_f16(q, k, v, heads, out_layer.act_scales_inv,
                                                     out_layer.act_zero_points, _abits=_abits(out_layer)))
@@ -267,8 +297,8 @@ def _self_qkv(attn, x):
     shapes and values of the state_dict are unchanged).  None where the layers do not qualify."""
     layers = [attn.to_q, attn.to_k, attn.to_v]
     C = x.shape[-1]
-    if not (x.is_contiguous() and all(_takes_operand(m) and m.bias is None and m.in_features == C
-                                      and m.act_scales_inv.device == x.device for m in layers)):
+    if _hooked(*layers) or not (x.is_contiguous() and all(_takes_operand(m) and m.bias is None and m.in_features == C
+                                                          and m.act_scales_inv.device == x.device for m in layers)):
         return None
     from mixdq_amd.op.qlinear import qlinear
     from mixdq_amd.unet import _pack_rows, _pack_valid, _quantizer_groups, _uniform_storage
@@ -295,7 +325,7 @@ def _cross_one_launch(attn, x, k, v):
     from mixdq_amd import _C
     from mixdq_amd.unet import CROSS_FUSE_MAX_ROWS
     q, out = attn.to_q, attn.to_out[0]
-    if not (_takes_operand(q) and q.bias is None and _takes_operand(out) and x.is_contiguous()
+    if _hooked(q, out) or not (_takes_operand(q) and q.bias is None and _takes_operand(out) and x.is_contiguous()
             and q.in_features == x.shape[-1] and attn.heads * 64 == q.out_features == out.in_features
             and q.act_scales_inv.device == x.device and out.act_scales_inv.device == x.device
             and all(_f16_cuda(z) and z.dim() == 3 and z.stride(-1) == 1 and z.stride(0) % 8 == 0
@@ -314,7 +344,9 @@ def _attention_hand_off(attn, x, context):
     output inside this function (nothing escapes: kept buffers and INT8 intermediates are safe): self-attention =
     one q | k | v GEMM + the attention launch writing to_out.0's operand; cross-attention = k / v into kept BOS
     buffers from one shared quantize launch + (to_q, attention, to_out.0's quantizer) in one launch.  Each step
-    falls back to the module-by-module form where its conditions do not hold; None: not an input of the kernels."""
+    falls back to the module-by-module form where its conditions do not hold -- among them: a forward hook or
+    pre-hook on a layer the step reads directly (or a global one), so that every hook fires once per module and
+    forward and sees what the module-by-module form would hand it; None: not an input of the kernels."""
     if not (_f16_cuda(x) and x.dim() == 3 and getattr(attn.to_q, "out_features", None) == attn.heads * 64):
         return None                                     # (decided before anything is launched)
     if context is None:
@@ -404,6 +436,8 @@ def _is_geglu(mod) -> bool:
 # `norms`, and to nothing else of it: diffusers' and this repo's ResnetBlock2D (norm1 / norm2 -> nonlinearity) and the
 # UNet itself (conv_norm_out -> conv_act).  Only there is the SiLU folded into the GroupNorm's launch: a parent that
 # applied F.silu itself, or used the GroupNorm's output twice, would get the activation twice or in the wrong place.
+# `norm2` only where the block's `time_embedding_norm` is "default" (or absent): diffusers' "scale_shift" block
+# applies the SiLU to norm2(h) * (1 + scale) + shift.
 SILU_PAIRS = {"ResnetBlock2D": (("norm1", "norm2"), "nonlinearity"),
               "UNet2DConditionModel": (("conv_norm_out",), "conv_act"),
               "SDXLUNet": (("conv_norm_out",), "conv_act")}
@@ -449,8 +483,11 @@ def swap_glue_modules(unet: nn.Module, attention: bool = True, silu_pairs=None, 
                 continue
             for nm in norms:
                 g = kids.get(nm)
+                if nm == "norm2" and getattr(parent, "time_embedding_norm", "default") != "default":
+                    continue        # ('scale_shift': silu(norm2(h) * (1 + scale) + shift), not silu(norm2(h)))
                 if g is not None and type(g) in (nn.GroupNorm, HipGroupNorm) and not g.__dict__.get("fuse_silu"):
                     g.__dict__["fuse_silu"] = True
+                    g.__dict__[_SILU_PAIR] = weakref.ref(a)
                     n["silu_folded"] += 1
             if type(a) is nn.SiLU:
                 a.__class__ = HipSiLU
@@ -504,6 +541,7 @@ def unswap_glue_modules(unet: nn.Module) -> None:
             mod.__dict__.pop("_qkv", None)      # (_self_qkv's pack record; the layers' buffers stay views of the pack)
         if type(mod) is HipGroupNorm:
             mod.__dict__.pop("fuse_silu", None)
+            mod.__dict__.pop(_SILU_PAIR, None)
             mod.__class__ = nn.GroupNorm
         elif type(mod) is HipSiLU:
             mod.__class__ = nn.SiLU

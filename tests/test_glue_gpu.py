@@ -320,3 +320,231 @@ def test_operand_hand_off_is_quantize_of_the_fp16_output_and_only_for_that_tenso
     assert tagged_operand(blk.norm1(x), a.to_v) is None
     unswap_glue_modules(blk)
     assert tagged_operand(blk.norm1(x), a.to_q) is None
+
+
+# ---- the fold and the direct paths give way to hooks and to blocks of another order (nn/glue.py) ----------------
+
+class ResnetBlock2D(nn.Module):                  # (the class NAME is what SILU_PAIRS keys on)
+    """diffusers' ResnetBlock2D in its own order of operations, FP16 convolutions: `time_embedding_norm` "default"
+    (norm2 of h + temb) or "scale_shift" (silu(norm2(h) * (1 + scale) + shift): the SiLU does NOT act on norm2's
+    output)."""
+
+    def __init__(self, c, g, temb_dim, mode):
+        super().__init__()
+        self.time_embedding_norm = mode
+        self.norm1 = nn.GroupNorm(g, c, eps=1e-5)
+        self.conv1 = nn.Conv2d(c, c, 3, 1, 1)
+        self.time_emb_proj = nn.Linear(temb_dim, 2 * c if mode == "scale_shift" else c)
+        self.norm2 = nn.GroupNorm(g, c, eps=1e-5)
+        self.conv2 = nn.Conv2d(c, c, 3, 1, 1)
+        self.nonlinearity = nn.SiLU()
+
+    def forward(self, x, temb):
+        h = self.conv1(self.nonlinearity(self.norm1(x)))
+        t = self.time_emb_proj(self.nonlinearity(temb))[:, :, None, None]
+        if self.time_embedding_norm == "default":
+            h = self.norm2((h + t).contiguous(memory_format=torch.channels_last))
+        else:
+            scale, shift = t.chunk(2, dim=1)
+            h = self.norm2(h) * (1 + scale) + shift
+        return x + self.conv2(self.nonlinearity(h))
+
+
+@pytest.mark.parametrize("mode", ["scale_shift", "default"])
+def test_swapped_resnet_block_keeps_diffusers_order_vs_float64(C, mode):
+    """The swapped block (norm1 folded; norm2 folded only under "default") against the block evaluated in float64:
+    no further from it than twice the stock FP16 block plus a few FP16 ulps.  Folding norm2 of a "scale_shift"
+    block would compute silu(silu(norm2(h)) * (1 + scale) + shift): an O(1) error."""
+    import copy
+    from mixdq_amd.nn.glue import swap_glue_modules
+    N, H, W, Cc, G = 2, 16, 16, 320, 32
+    assert C.groupnorm_supported(N, H * W, Cc, G)
+    torch.manual_seed(0)
+    blk = ResnetBlock2D(Cc, G, 1280, mode).half().to(DEV).to(memory_format=torch.channels_last).eval()
+    with torch.no_grad():
+        for norm in (blk.norm1, blk.norm2):
+            norm.weight.copy_(t((dd.normal_f16(91, (Cc,), 0.3).astype(np.float32) + 1).astype(np.float16)))
+            norm.bias.copy_(t(dd.normal_f16(92, (Cc,), 0.2)))
+    ref_blk = copy.deepcopy(blk).double().cpu()
+    x = t(dd.normal_f16(93, (N, H, W, Cc), 1.0)).permute(0, 3, 1, 2)      # NCHW view of NHWC memory
+    temb = t(dd.normal_f16(94, (N, 1280), 1.0))
+    with torch.no_grad():
+        ref = ref_blk(x.double().cpu(), temb.double().cpu())
+        stock = blk(x, temb).double().cpu()
+        n = swap_glue_modules(blk)
+        swapped = blk(x, temb).double().cpu()
+    e_stock = (stock - ref).abs().max().item()
+    err = (swapped - ref).abs()
+    bound = 2 * e_stock + 4 * ulp_f16(ref.float()).double()
+    assert (err <= bound).all(), f"{mode}: max error {err.max().item():.4g} vs stock FP16 {e_stock:.4g}"
+    assert n["silu_folded"] == (1 if mode == "scale_shift" else 2) and blk.norm2.fuse_silu == (mode == "default")
+
+
+class _NormAct(nn.Module):
+    """norm1 -> nonlinearity: the module pair a folded GroupNorm + SiLU stands for."""
+
+    def __init__(self, c, g):
+        super().__init__()
+        self.norm1 = nn.GroupNorm(g, c, eps=1e-5)
+        self.nonlinearity = nn.SiLU()
+
+    def forward(self, x):
+        return self.nonlinearity(self.norm1(x))
+
+
+def _norm_act_pair(Cc, G):
+    """(folded, unfolded): the same block swapped with and without the SiLU folded into the GroupNorm's launch."""
+    import copy
+    from mixdq_amd.nn.glue import swap_glue_modules
+    m = _NormAct(Cc, G).half().to(DEV)
+    with torch.no_grad():
+        m.norm1.weight.copy_(t((dd.normal_f16(101, (Cc,), 0.3).astype(np.float32) + 1).astype(np.float16)))
+        m.norm1.bias.copy_(t(dd.normal_f16(102, (Cc,), 0.2)))
+    plain = copy.deepcopy(m)
+    assert swap_glue_modules(m, silu_pairs={"_NormAct": (("norm1",), "nonlinearity")})["silu_folded"] == 1
+    assert swap_glue_modules(plain, silu_pairs={})["silu_folded"] == 0
+    return m, plain
+
+
+def _hook_clone(mod, args, y):
+    return y.clone()
+
+
+def _hook_scale_in_place(mod, args, y):
+    y.mul_(2)                                    # (returns None: the module's output object, edited)
+
+
+def _pre_hook_times_one(mod, args):
+    return (args[0] * 1,)
+
+
+@pytest.mark.parametrize("N,H,W,Cc,G", [(2, 8, 8, 640, 32), (1, 16, 16, 320, 32)])
+@pytest.mark.parametrize("hook", ["norm_forward_clone", "silu_pre_times_one", "norm_forward_in_place"])
+def test_groupnorm_silu_fold_gives_way_to_hooks(C, N, H, W, Cc, G, hook):
+    """A hook between a folded GroupNorm and its SiLU module sees (or replaces) the tensor between the two: the fold
+    is off while it is registered, and the block == the same swapped block with nothing folded, bit for bit."""
+    assert C.groupnorm_supported(N, H * W, Cc, G)
+    m, plain = _norm_act_pair(Cc, G)
+    x = t(dd.normal_f16(103, (N, H, W, Cc), 1.5)).permute(0, 3, 1, 2)
+    for blk in (m, plain):
+        if hook == "norm_forward_clone":
+            blk.norm1.register_forward_hook(_hook_clone)
+        elif hook == "silu_pre_times_one":
+            blk.nonlinearity.register_forward_pre_hook(_pre_hook_times_one)
+        else:
+            blk.norm1.register_forward_hook(_hook_scale_in_place)
+    with torch.no_grad():
+        got, want = m(x), plain(x)
+    d = (got.float() - want.float()).abs()
+    assert torch.equal(got.view(torch.int16), want.view(torch.int16)), \
+        f"{hook}: {int((d > 0).sum())} of {d.numel()} differ, max {d.max().item():.4g}"
+    if hook == "norm_forward_in_place":          # (the reference value, spelled out: silu(2 * norm(x)))
+        pre = C.groupnorm_silu_quantize(x, G, m.norm1.weight, m.norm1.bias, 1e-5, silu=False, want_f16=True)[1]
+        assert torch.equal(got, F.silu(pre * 2))
+
+
+def test_groupnorm_silu_fold_stays_on_without_hooks_and_a_modified_tagged_tensor_raises(C):
+    m, _ = _norm_act_pair(640, 32)
+    x = t(dd.normal_f16(104, (2, 8, 8, 640), 1.5)).permute(0, 3, 1, 2)
+    with torch.no_grad():
+        y = m.norm1(x)
+        assert getattr(y, "_mixdq_silu_applied", None) is not None         # folded: one launch
+        want = C.groupnorm_silu_quantize(x, 32, m.norm1.weight, m.norm1.bias, 1e-5, silu=True, want_f16=True)[1]
+        assert torch.equal(y, want) and m.nonlinearity(y) is y
+        y.add_(1)                                # silu(norm(x)) + 1 cannot become silu(norm(x) + 1)
+        with pytest.raises(RuntimeError):
+            m.nonlinearity(y)
+
+
+def _tiny_glue_unet():
+    """The tiny UNet with 64-wide heads (this repo's attention kernels and the launch forms of _attention_hand_off),
+    W8A8 + BOS, Linear / Conv2d swapped as the reference does."""
+    import bench
+    from mixdq_amd.calib import calibrate, precompute_bos
+    from mixdq_amd.quantize_sdxl import example_inputs, quantize_unet
+    from mixdq_amd.unet import build_unet, quantizable_layers
+    unet = build_unet(DEV, cfg=dict(bench.TINY_CFG, block_out_channels=(64, 128, 256), head_dim=64))
+    inputs = example_inputs(2, 32, DEV, seed=7)
+    ckpt = calibrate(unet, [inputs])
+    names = list(quantizable_layers(unet))
+    quantize_unet(unet, bench.Cfg({n: 8 for n in names}, {n: 8 for n in names if n not in ("conv_in", "conv_out")}),
+                  ckpt, bos=True, bos_dict=precompute_bos(unet, inputs["encoder_hidden_states"]))
+    return unet, inputs
+
+
+def _attention_layers(unet):
+    from mixdq_amd.unet import Attention
+    attns = [m for m in unet.modules() if isinstance(m, Attention)]
+    return [((i, nm), getattr(a, nm) if nm != "to_out.0" else a.to_out[0])
+            for i, a in enumerate(attns) for nm in ("to_q", "to_k", "to_v", "to_out.0")]
+
+
+def _count_and_capture(unet, calls, outs):
+    handles = []
+    for key, layer in _attention_layers(unet):
+        def pre(mod, args, key=key):
+            calls[("pre",) + key] = calls.get(("pre",) + key, 0) + 1
+
+        def post(mod, args, y, key=key):
+            calls[("fwd",) + key] = calls.get(("fwd",) + key, 0) + 1
+            outs[key] = y.clone()
+        handles += [layer.register_forward_pre_hook(pre), layer.register_forward_hook(post)]
+    return handles
+
+
+def test_hooks_on_attention_projections_fire_once_and_see_module_by_module_outputs(C):
+    """A forward hook and a pre-hook on each of to_q / to_k / to_v / to_out.0 of every swapped attention module
+    (self- and cross-attention) fire exactly once per module and forward; what they see == what they see on the
+    module-by-module form (operands=False); the network output is unchanged by them."""
+    from mixdq_amd.nn.glue import _HipAttend, swap_glue_modules
+    unet, inputs = _tiny_glue_unet()
+    swap_glue_modules(unet, operands=False)
+    ref_calls, ref_outs = {}, {}
+    handles = _count_and_capture(unet, ref_calls, ref_outs)
+    with torch.no_grad():
+        ref = unet(**inputs)[0].clone()
+    for h in handles:
+        h.remove()
+    n_layers = len(_attention_layers(unet))
+    assert n_layers > 0 and set(ref_calls.values()) == {1} and len(ref_calls) == 2 * n_layers
+    swap_glue_modules(unet)
+    attns = [m for m in unet.modules() if isinstance(m, _HipAttend)]
+    assert all(a.hand_off for a in attns)
+    assert {a.to_k.in_features == a.to_q.in_features for a in attns} == {True, False}     # self- and cross-attention
+    with torch.no_grad():
+        glue = unet(**inputs)[0].clone()
+    calls, outs = {}, {}
+    handles = _count_and_capture(unet, calls, outs)
+    with torch.no_grad():
+        hooked = unet(**inputs)[0].clone()
+    for h in handles:
+        h.remove()
+    missing = sorted(k for k in ref_calls if calls.get(k) != 1)
+    assert not missing and len(calls) == len(ref_calls), f"hooks that did not fire exactly once: {missing[:8]}"
+    for key, y in ref_outs.items():
+        assert torch.equal(outs[key].view(torch.int16), y.view(torch.int16)), key
+    assert torch.equal(glue.view(torch.int16), ref.view(torch.int16))
+    assert torch.equal(hooked.view(torch.int16), glue.view(torch.int16))
+
+
+def test_a_hook_never_holds_a_kept_bos_buffer(C):
+    """A forward hook on a cross-attention's to_k / to_v keeps the tensor it is handed: the layer then allocates it,
+    so a later forward (another text context) leaves it as it was."""
+    from mixdq_amd.nn.glue import _HipAttend, swap_glue_modules
+    from mixdq_amd.quantize_sdxl import example_inputs
+    unet, inputs = _tiny_glue_unet()
+    swap_glue_modules(unet)
+    cross = [a for a in unet.modules() if isinstance(a, _HipAttend) and a.to_k.in_features != a.to_q.in_features]
+    assert cross and all(getattr(a.to_k, "bos", False) for a in cross)
+    kept = []
+    for a in cross:
+        for layer in (a.to_k, a.to_v):
+            layer.register_forward_hook(lambda mod, args, y: kept.append((y, y.clone())))
+    other = dict(inputs, encoder_hidden_states=example_inputs(2, 32, DEV, seed=8)["encoder_hidden_states"])
+    with torch.no_grad():
+        unet(**inputs)
+        assert len(kept) == 2 * len(cross)
+        unet(**other)
+    assert len(kept) == 4 * len(cross)
+    for y, y0 in kept[:2 * len(cross)]:
+        assert torch.equal(y, y0)

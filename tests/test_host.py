@@ -732,6 +732,35 @@ def test_swap_glue_modules_by_type_keeps_names_and_state_and_undoes():
     assert not any(type(m).__name__ == "HipAttention" for m in unet.modules())
 
 
+def test_swap_glue_folds_norm2_only_into_a_default_time_embedding_norm_block():
+    """diffusers' ResnetBlock2D(time_embedding_norm="scale_shift") computes silu(norm2(h) * (1 + scale) + shift): the
+    SiLU there does not act on norm2's output, so only norm1 is folded (norm2 stays a plain HipGroupNorm, and the SiLU
+    module still applies its activation after the scale / shift)."""
+    from mixdq_amd.nn.glue import HipGroupNorm, HipSiLU, swap_glue_modules, unswap_glue_modules
+
+    class ResnetBlock2D(nn.Module):             # (the class NAME is what SILU_PAIRS keys on)
+        def __init__(self, mode):
+            super().__init__()
+            self.norm1, self.norm2 = nn.GroupNorm(8, 64), nn.GroupNorm(8, 64)
+            self.nonlinearity = nn.SiLU()
+            if mode is not None:
+                self.time_embedding_norm = mode
+
+    for mode, folded in (("scale_shift", 1), ("default", 2), (None, 2)):
+        blk = ResnetBlock2D(mode)
+        n = swap_glue_modules(blk)
+        assert n["groupnorm"] == 2 and n["silu_folded"] == folded, (mode, n)
+        assert type(blk.norm1) is HipGroupNorm and blk.norm1.fuse_silu and type(blk.nonlinearity) is HipSiLU
+        assert type(blk.norm2) is HipGroupNorm and blk.norm2.fuse_silu == (folded == 2)
+        assert blk.norm1.__dict__["_mixdq_silu_module"]() is blk.nonlinearity
+        x = torch.randn(2, 64, 4, 4)
+        with torch.no_grad():                   # (CPU, FP32: the stock ops, activation applied by the SiLU module)
+            want = torch.nn.functional.group_norm(x, 8, blk.norm2.weight, blk.norm2.bias)
+            assert torch.equal(blk.nonlinearity(blk.norm2(x)), torch.nn.functional.silu(want))
+        unswap_glue_modules(blk)
+        assert type(blk.norm2) is nn.GroupNorm and "_mixdq_silu_module" not in blk.norm1.__dict__
+
+
 def test_pack_static_moves_every_tensor_into_one_allocation_and_keeps_the_network():
     """mixdq_amd/arena.py: same tensor objects, names, values, aliasing (row packs) -- one storage."""
     import bench

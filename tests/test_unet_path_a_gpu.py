@@ -3,8 +3,9 @@
 The 794-layer SDXL UNet at 512 px, batch 1, `uniform_8` + `act_8.00` with the BOS carve-out runs twice on
 the SAME seeded weights, inputs and calibrated quantizer state:
 
-  * on the GPU: the module-swapped network on the HIP kernels, fused graph (the benchmarked path) and
-    unfused (the drop-in);
+  * on the GPU: the module-swapped network on the HIP kernels, fused graph (the benchmarked path),
+    unfused (the drop-in), and the drop-in with its glue swapped (`swap_glue_modules`: `glue`, and
+    `glue_torch_sdpa` with PyTorch's SDPA kept);
   * on the host, FP32: the same graph with `oracle/fakequant.quant_layer_forward` -- the restatement of
     the reference's qdiff `QuantLayer.forward` (quant_layer.py:63-103, base_quantizer.py:119-129),
     pinned bit-for-bit by tests/golden/fakequant.npz -- in place of every accelerated layer.  This is
@@ -94,10 +95,18 @@ def test_full_unet_512px_hip_path_matches_host_path_a_within_quantization_noise(
     accelerated = {n: bool(getattr(mods[n], "valid_for_acceleration", False)) for n in split_of}
     assert sum(accelerated.values()) == 785                        # 794 - 9 act-protected
     assert all(isinstance(mods[n], (QuantizedLinear, QuantizedConv2d)) for n in split_of)
+    from mixdq_amd.nn.glue import swap_glue_modules, unswap_glue_modules
     with torch.no_grad():
         unfused = unet(**inp)[0].float().cpu()
         unet.set_fused(True)
         fused = unet(**inp)[0].float().cpu()
+        # the drop-in network with its glue swapped (quantize_unet(..., swap_glue=True)), then with PyTorch's SDPA kept
+        unet.set_fused(False)
+        swap_glue_modules(unet)
+        glue = unet(**inp)[0].float().cpu()
+        unswap_glue_modules(unet)
+        swap_glue_modules(unet, attention=False)
+        glue_torch_sdpa = unet(**inp)[0].float().cpu()
     del unet
     torch.cuda.empty_cache()
 
@@ -113,7 +122,7 @@ def test_full_unet_512px_hip_path_matches_host_path_a_within_quantization_noise(
     n_mean, n_max = dist(path_a, ref32)                            # Path A's own quantization noise
     f_mean, f_max = dist(ref16, ref32)                             # what FP16 arithmetic alone costs
     report = {}
-    for tag, out in (("fused", fused), ("unfused", unfused)):
+    for tag, out in (("fused", fused), ("unfused", unfused), ("glue", glue), ("glue_torch_sdpa", glue_torch_sdpa)):
         assert torch.isfinite(out).all()
         d_mean, d_max = dist(out, path_a)                          # HIP path vs Path A
         e_mean, e_max = dist(out, ref32)                           # HIP path vs the FP32 network
