@@ -16,7 +16,8 @@ N = 1 workload: BASELINE.json configs[1] -- W8A8 SDXL-Turbo UNet, 1024x1024 (lat
 step loop).  `--baseline-config 3` is BASELINE.json configs[3] as named: GLOBAL batch 64 sharded
 over the N ranks (64 / N per GPU), 4 UNet forwards per image -- strong scaling.
 
-Prints ONE JSON line (rank 0): the timed region is exactly --steps steps.  Extra objects, with --extras:
+Prints ONE JSON line (rank 0): the timed region is exactly --steps steps.  A plain run does only what that line
+needs: set-up, the warm-up, the timed steps and --dump-outputs.  Extra objects, with --full:
   roofline      dominant kernel (an igemm_kernel<BM,BN,BK,CONV> instantiation): the launches of ONE
                 forward of the graph that was timed are recorded (mixdq_amd._C.RECORD), replayed
                 per kernel instantiation from a hipGraph and bracketed by HIP events on the launch
@@ -110,7 +111,7 @@ def parse_args():
                     help="after the timed steps: what the timed path returned in its last step (rank 0), as "
                          "DIR/<name>.npy in float32 -- at most 64 MB in all; a larger output is a fixed seeded "
                          "sample of its elements, their flat indices in DIR/<name>_index.npy (float64)")
-    ap.add_argument("--extras", action="store_true",
+    ap.add_argument("--full", action="store_true",
                     help="also run the comparison legs: the FP16 network, the roofline sweep, batch 8, the drop-in "
                          "and LayerNorm-in-GEMM graphs (each times steps of its own) and the CPU baseline; the --no-* "
                          "flags above still drop single legs.  Without it the run times exactly --steps steps of the "
@@ -118,7 +119,7 @@ def parse_args():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1 (ms_per_step is the timed region over this many steps)")
-    if not args.extras:
+    if not args.full:
         args.no_fp16 = args.no_roofline = args.no_batch8 = args.no_dropin = args.no_lnchain = True
         args.no_cpu_baseline = True
     if args.baseline_config == 2:
@@ -182,6 +183,80 @@ def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES, seed=0):
         np.save(os.path.join(out_dir, name + "_index.npy"), idx.astype(np.float64))
         info[name] = {"shape": list(a.shape), "elements": int(n), "sampled": True}
     return info
+
+
+def build_synthetic_unet(device, cfg=None, seed=42, std=0.02):
+    """mixdq_amd.unet.build_unet(device, cfg=cfg), the same parameters bit for bit, in a fraction of its time.
+    build_unet builds the FP32 network on the host with torch's default initialisation, overwrites every Linear /
+    Conv2d with init_synthetic_weights' seeded draws one layer after the other, then converts and copies it: ~20 s of
+    host time at SDXL size.  Here the modules are created without storage, the parameters are allocated in FP16 on
+    `device`, the norms get their default ones / zeros, and the draws run in a thread pool: every layer has a
+    generator of its own (seed + layer index), so their order does not matter.  A draw is scaled in FP32 and rounded
+    to FP16 once, as build_unet's .to(float16) rounds it."""
+    from concurrent.futures import ThreadPoolExecutor
+    from mixdq_amd.unet import SDXLUNet, quantizable_layers
+    with torch.device("meta"):
+        unet = SDXLUNet(cfg)
+    layers = list(quantizable_layers(unet).values())
+    drawn = {id(p) for m in layers for p in m.parameters(recurse=False)}
+    others = {type(m) for m in unet.modules() for p in m.parameters(recurse=False) if id(p) not in drawn}
+    assert others <= {nn.GroupNorm, nn.LayerNorm}, f"parameters left to a default initialisation: {others}"
+    unet = unet.to(dtype=torch.float16).to_empty(device=device)
+    for m in unet.modules():
+        if isinstance(m, (nn.GroupNorm, nn.LayerNorm)):
+            m.reset_parameters()
+
+    def draw(idx):
+        mod = layers[idx]
+        g = torch.Generator(device="cpu").manual_seed(seed + idx)
+        w = (torch.randn(mod.weight.shape, generator=g) * std).half()
+        b = None if mod.bias is None else (torch.randn(mod.bias.shape, generator=g) * std).half()
+        return w, b
+
+    with torch.no_grad(), ThreadPoolExecutor(max(1, torch.get_num_threads())) as pool:
+        for mod, (w, b) in zip(layers, pool.map(draw, range(len(layers)))):
+            mod.weight.copy_(w)
+            if b is not None:
+                mod.bias.copy_(b)
+    return unet.to(memory_format=torch.channels_last).eval()
+
+
+def conv2d_f64_sum(x, weight, bias, stride, padding, dilation):
+    """F.conv2d(x, weight, bias, stride, padding, dilation) of FP16 tensors as torch.use_deterministic_algorithms has
+    it computed on this stack: MIOpen's deterministic forward convolution is ConvDirectNaiveConvFwd, which sums the
+    FP16 products in float64, rounds the sum to FP32 and then to FP16, and torch adds the bias in FP16.  Here the sum
+    is one float64 GEMM over the im2col matrix.  Every product of two FP16 values is exact in float64 and a multiple of
+    2^-48, so the sum is exact, in any order, while its partial sums stay below 32 in magnitude; beyond that the orders
+    can differ only in the last bits of float64, 29 bits below the FP32 rounding.  Output in channels-last order, as
+    F.conv2d gives it for the network's channels-last weights."""
+    import torch.nn.functional as F
+    N, _, H, W = x.shape
+    OC, C, R, S = weight.shape
+    P = (H + 2 * padding[0] - dilation[0] * (R - 1) - 1) // stride[0] + 1
+    Q = (W + 2 * padding[1] - dilation[1] * (S - 1) - 1) // stride[1] + 1
+    cols = F.unfold(x, (R, S), dilation=dilation, padding=padding, stride=stride)       # [N, C*R*S, P*Q]
+    y = torch.matmul(weight.reshape(OC, C * R * S).double(), cols.double())
+    y = y.float().half().view(N, OC, P, Q).contiguous(memory_format=torch.channels_last)
+    return y if bias is None else y + bias.view(1, OC, 1, 1)
+
+
+class Float64SumConvs:
+    """While entered, every nn.Conv2d of `net` runs conv2d_f64_sum instead of F.conv2d.  The calibration forward
+    needs F.conv2d's deterministic bits, and MIOpen's kernel for them is slow to get: it is compiled for every new
+    shape (~35 s for the SDXL UNet's 27 shapes on a fresh home directory) and runs at ~0.2 TFLOP/s (~9 s a forward)."""
+
+    def __init__(self, net):
+        self.convs = [m for m in net.modules() if isinstance(m, nn.Conv2d)]
+
+    def __enter__(self):
+        for m in self.convs:
+            assert m.groups == 1 and m.padding_mode == "zeros" and not isinstance(m.padding, str)
+            m.forward = lambda x, m=m: conv2d_f64_sum(x, m.weight, m.bias, m.stride, m.padding, m.dilation)
+        return self
+
+    def __exit__(self, *exc):
+        for m in self.convs:
+            del m.forward
 
 
 def layer_shapes(unet, inputs):
@@ -680,7 +755,6 @@ def main():
     from mixdq_amd.nn import QuantizedConv2d, QuantizedLinear
     from mixdq_amd.quantize_sdxl import (MemoryMeter, example_inputs, hip_graph_opt,
                                          layers_roctx_annotate, quantize_unet)
-    from mixdq_amd.unet import build_unet
 
     L = args.px // 8
     strong = args.global_batch is not None
@@ -692,7 +766,7 @@ def main():
         B, global_batch = args.batch, world * args.batch
     fpi = max(1, args.forwards_per_image)
     t_setup = time.perf_counter()
-    unet = build_unet(device, cfg=TINY_CFG if args.tiny else None)
+    unet = build_synthetic_unet(device, cfg=TINY_CFG if args.tiny else None)
     fp16_meter = MemoryMeter(device)              # static = the FP16 network, resident
     inputs = example_inputs(B, L, device, seed=42 + rank)
     # static per-tensor scales come from a calibration set, not from the batch that is served
@@ -707,11 +781,13 @@ def main():
     # The scales are inputs of the timed path as much as the latents are, so they must be the same on every run with
     # the same arguments (--dump-outputs compares builds output for output).  The calibration forward runs stock
     # FP16 ops, and MIOpen's default convolutions do not give the same bits twice; its deterministic algorithms do.
+    # Their convolution bits are computed by conv2d_f64_sum, without MIOpen's slow kernel.
     # Only here: the legs that are timed run with the setting the process had.
     det_was = (torch.are_deterministic_algorithms_enabled(), torch.is_deterministic_algorithms_warn_only_enabled())
     torch.use_deterministic_algorithms(True, warn_only=True)
     try:
-        ckpt = calibrate(unet, [calib_inputs], bos=not args.no_bos)
+        with Float64SumConvs(unet):
+            ckpt = calibrate(unet, [calib_inputs], bos=not args.no_bos)
         bos_dict = precompute_bos(unet, inputs["encoder_hidden_states"])
     finally:
         torch.use_deterministic_algorithms(det_was[0], warn_only=det_was[1])

@@ -100,3 +100,46 @@ def test_dump_outputs_samples_the_same_elements_within_the_budget(tmp_path):
         assert np.array_equal(vals, x.numpy().reshape(-1)[idx.astype(np.int64)])
         runs.append(idx)
     assert np.array_equal(runs[0], runs[1])
+
+
+def test_plain_run_drops_every_extra_leg_and_full_keeps_them(monkeypatch):
+    b = _bench_module()
+    legs = ("no_fp16", "no_roofline", "no_batch8", "no_dropin", "no_lnchain", "no_cpu_baseline")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1"])
+    plain = b.parse_args()
+    assert not plain.full and all(getattr(plain, k) for k in legs)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--full", "--no-batch8"])
+    full = b.parse_args()
+    assert full.full and full.no_batch8 and not any(getattr(full, k) for k in legs if k != "no_batch8")
+
+
+def test_synthetic_unet_is_build_unet_bit_for_bit():
+    import torch
+    from mixdq_amd.unet import build_unet
+    b = _bench_module()
+    want, got = build_unet("cpu", cfg=b.TINY_CFG), b.build_synthetic_unet("cpu", cfg=b.TINY_CFG)
+    assert not got.training
+    sw, sg = want.state_dict(), got.state_dict()
+    assert list(sw) == list(sg)
+    for k in sw:
+        assert sg[k].dtype == sw[k].dtype == torch.float16 and sg[k].stride() == sw[k].stride(), k
+        assert torch.equal(sg[k].view(torch.int16), sw[k].view(torch.int16)), k
+
+
+def test_conv2d_f64_sum_is_the_float64_convolution_rounded_through_fp32():
+    # the indexing of the im2col GEMM (kernel taps, stride, padding, batch) against torch's own float64 convolution;
+    # tests/test_bench_gpu.py compares it with F.conv2d on the GPU
+    import torch
+    import torch.nn.functional as F
+    b = _bench_module()
+    g = torch.Generator().manual_seed(3)
+    for cin, cout, k, stride, pad, hw, n in ((4, 32, 3, 1, 1, 16, 1), (64, 48, 3, 2, 1, 17, 2),
+                                             (96, 40, 1, 1, 0, 9, 1), (40, 24, 3, 1, 1, 8, 2)):
+        cl = torch.channels_last
+        x = (torch.randn(n, cin, hw, hw, generator=g) * 3).half().contiguous(memory_format=cl)
+        w = (torch.randn(cout, cin, k, k, generator=g) * 0.05).half().contiguous(memory_format=cl)
+        bias = (torch.randn(cout, generator=g) * 0.1).half()
+        got = b.conv2d_f64_sum(x, w, bias, (stride, stride), (pad, pad), (1, 1))
+        want = F.conv2d(x.double(), w.double(), None, stride, pad).float().half() + bias.view(1, -1, 1, 1)
+        assert got.is_contiguous(memory_format=cl) and got.shape == want.shape
+        assert torch.equal(got.view(torch.int16), want.view(torch.int16))

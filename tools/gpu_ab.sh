@@ -9,7 +9,7 @@ out=gpurun_out/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:?}"
 for rep in 1 2 3; do i=0; for E in "${envs[@]}"; do i=$((i+1))
-  env $E timeout 900 python bench.py --no-fp16 --no-cpu-baseline --no-roofline --no-dropin --no-lnchain "$@" > $out/bench_${i}_$rep.json 2> $out/bench_${i}_$rep.err
+  env $E timeout 900 python bench.py --full --no-fp16 --no-cpu-baseline --no-roofline --no-dropin --no-lnchain "$@" > $out/bench_${i}_$rep.json 2> $out/bench_${i}_$rep.err
   python - $out/bench_${i}_$rep.json "$E" $rep <<'PY'
 import json, sys
 try:

@@ -7,7 +7,7 @@ mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:?}"
 for rep in 1 2 3; do for v in base new; do
   lib=$PWD/mixdq_amd/libmixdq_hip.so; [ $v = base ] && lib=$PWD/build/ab_base/libmixdq_hip.so
-  MIXDQ_HIP_LIB=$lib timeout 900 python bench.py --no-fp16 --no-cpu-baseline --no-roofline --no-dropin --no-lnchain --steps 40 "$@" > $out/bench_${v}_$rep.json 2> $out/bench_${v}_$rep.err
+  MIXDQ_HIP_LIB=$lib timeout 900 python bench.py --full --no-fp16 --no-cpu-baseline --no-roofline --no-dropin --no-lnchain --steps 40 "$@" > $out/bench_${v}_$rep.json 2> $out/bench_${v}_$rep.err
   python - $out/bench_${v}_$rep.json $v $rep <<'PY'
 import json, sys
 try:

@@ -4,8 +4,8 @@ out=gpurun_out/check
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:?}"
 ( time timeout 1500 python -m pytest tests -q -m gpu -x 2>&1 | tail -6 ) > $out/pytest.txt 2>&1
-timeout 900 python bench.py --batch 8 --steps 10 --no-fp16 --no-cpu-baseline > $out/bench_bs8.json 2> $out/bench_bs8.err
-timeout 900 python bench.py --no-fp16 --no-cpu-baseline > $out/bench_bs1.json 2> $out/bench_bs1.err
+timeout 900 python bench.py --full --batch 8 --steps 10 --no-fp16 --no-cpu-baseline > $out/bench_bs8.json 2> $out/bench_bs8.err
+timeout 900 python bench.py --full --no-fp16 --no-cpu-baseline > $out/bench_bs1.json 2> $out/bench_bs1.err
 timeout 900 python bench.py --baseline-config 4 --forwards-per-image 20 --steps 20 --warmup 2 --no-fp16 --no-cpu-baseline --no-roofline > $out/bench_cfg4.json 2> $out/bench_cfg4.err
 cat $out/pytest.txt
 python - <<PY

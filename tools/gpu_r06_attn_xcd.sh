@@ -32,7 +32,7 @@ unset MIXDQ_ATTN_XCD
 cp $(find $out/raw -name "*counter_collection.csv") $out/ 2>/dev/null
 rm -rf $out/raw
 for rep in 1 2; do for x in 0 1; do
-  MIXDQ_ATTN_XCD=$x timeout 900 python bench.py --no-fp16 --no-cpu-baseline --no-roofline --no-dropin --no-lnchain --steps 40 > $out/bench_x${x}_$rep.json 2> $out/bench_x${x}_$rep.err
+  MIXDQ_ATTN_XCD=$x timeout 900 python bench.py --full --no-fp16 --no-cpu-baseline --no-roofline --no-dropin --no-lnchain --steps 40 > $out/bench_x${x}_$rep.json 2> $out/bench_x${x}_$rep.err
   python3 - $out/bench_x${x}_$rep.json $x $rep <<'PY' | tee -a $out/step_ab.txt
 import json, sys
 try:

@@ -5,7 +5,7 @@ out=gpurun_out/r06_glue
 rm -rf $out; mkdir -p $out
 timeout 900 python -m pytest tests/test_glue_gpu.py -x -q -m gpu > $out/pytest.txt 2>&1
 tail -15 $out/pytest.txt
-timeout 1500 python bench.py > $out/bench_bs1.json 2> $out/bench_bs1.err
+timeout 1500 python bench.py --full > $out/bench_bs1.json 2> $out/bench_bs1.err
 tail -3 $out/bench_bs1.err
 python3 - $out/bench_bs1.json <<'PY'
 import json, sys

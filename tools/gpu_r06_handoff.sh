@@ -6,7 +6,7 @@ out=gpurun_out/r06_handoff
 rm -rf $out; mkdir -p $out
 timeout 900 python -m pytest tests/test_glue_gpu.py tests/test_modules_gpu.py tests/test_unet_gpu.py tests/test_f16in_gpu.py -q -m gpu 2>&1 | tail -15 | tee $out/pytest.txt
 for rep in 1; do
-  timeout 900 python bench.py --no-cpu-baseline --no-roofline --no-batch8 --no-lnchain --steps 20 > $out/bench_$rep.json 2> $out/bench_$rep.err
+  timeout 900 python bench.py --full --no-cpu-baseline --no-roofline --no-batch8 --no-lnchain --steps 20 > $out/bench_$rep.json 2> $out/bench_$rep.err
   python3 - $out/bench_$rep.json <<'PY' | tee -a $out/ab.txt
 import json, sys
 try:

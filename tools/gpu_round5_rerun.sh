@@ -6,8 +6,8 @@ out=gpurun_out/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:?}"
 ( time timeout 2400 python -m pytest tests -q -m gpu 2>&1 | tail -8 ) > $out/pytest_gpu.txt 2>&1
-timeout 1500 python bench.py > $out/bench_default.json 2> $out/bench_default.err
-timeout 900 python bench.py --baseline-config 2 --no-fp16 --no-cpu-baseline > $out/bench_w4a8_mixed_bs1.json 2> $out/bench_cfg2.err
+timeout 1500 python bench.py --full > $out/bench_default.json 2> $out/bench_default.err
+timeout 900 python bench.py --full --baseline-config 2 --no-fp16 --no-cpu-baseline > $out/bench_w4a8_mixed_bs1.json 2> $out/bench_cfg2.err
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof1 -o bench -- python3 bench.py --no-fp16 --no-cpu-baseline --no-roofline --no-batch8 --no-dropin --no-lnchain --steps 20 --batch 1 > $out/bench_prof_bs1.json 2> $out/bench_prof_bs1.err
 python3 tools/step_breakdown.py $(ls $out/prof1/*/*kernel_trace.csv $out/prof1/*kernel_trace.csv 2>/dev/null | head -1) 45 > $out/step_breakdown_bs1.txt 2>&1
 cp $(ls $out/prof1/*/*kernel_stats.csv $out/prof1/*kernel_stats.csv 2>/dev/null | head -1) $out/bench_kernel_stats_bs1.csv 2>/dev/null
