@@ -401,11 +401,13 @@ int mixdq_qlinear_w8a8_geglu(const int8_t* A, const int8_t* W_interleaved, const
                              int64_t M, int N, int K, const float* out_scale_inv,
                              const float* out_zero_point, int flags, mixdq_stream_t stream);
 
-/* FP16 attention core, head_dim 64: out[b, t, h*64 + d] = softmax_k(q . k * softmax_scale) v, per
+/* FP16 attention core, head_dim D = 64, 40, 80 or 160 (MIXDQ_ERR_SHAPE otherwise; 40 / 80 / 160: SD 1.5's heads, one
+ * kernel whose forms are 4 and 2; a payload of mixdq_attention_f16_prefetch is ignored there):
+ * out[b, t, h*D + d] = softmax_k(q . k * softmax_scale) v, per
  * head h.  The reference keeps these matmuls in FP16 (quant_block.py:630-637: get_attention_scores
  * + torch.bmm; diffusers' AttnProcessor at run time) — only to_q/to_k/to_v/to_out.0 are quantized
  * Linears — so this is a floating-point op with a tolerance oracle, not an integer one.
- * q [batch, tq, heads*64], k/v [batch, tkv, heads*64] fp16 with arbitrary batch/row strides in
+ * q [batch, tq, heads*D], k/v [batch, tkv, heads*D] fp16 with arbitrary batch/row strides in
  * ELEMENTS (multiples of 8; column slices of a fused q|k|v projection are fine).  Softmax in FP32,
  * P rounded to FP16 for the second product, output rounded to FP16.
  * out: fp16 rows (out_scale_inv == null), or — fused producer of to_out.0's INT8 operand — int8

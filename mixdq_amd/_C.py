@@ -1238,12 +1238,17 @@ if hasattr(_lib, "mixdq_attention_f16_prefetch"):     # (absent in older builds 
 PREFETCH_MAX_RANGES = 16
 
 
+# head widths of mixdq_attention_f16 (64: the SDXL kernels; 40, 80, 160: SD 1.5's, csrc/attention.hip attn_hd_kernel)
+ATTENTION_HEAD_DIMS = (40, 64, 80, 160)
+
+
 def attention_f16(q, k, v, heads, scale_inv=None, zero_point=None, softmax_scale=None, _cfg=0, _prefetch=None,
                   _abits=8):
     """FP16 attention core (the reference's get_attention_scores + bmm, quant_block.py:630-637).
 
     q [B, Tq, C], k/v [B, Tkv, C] fp16 with unit stride along C (column slices of a fused projection
-    are read in place); C = heads * 64.  Returns fp16 [B, Tq, C], or — when `scale_inv`/`zero_point`
+    are read in place); C = heads * D, head width D in ATTENTION_HEAD_DIMS (64: SDXL; 40, 80, 160: SD 1.5).
+    `softmax_scale` defaults to D ** -0.5.  Returns fp16 [B, Tq, C], or — when `scale_inv`/`zero_point`
     (to_out.0's activation quantizer) are given — its int8 quantization.
     `_prefetch`: up to 16 GPU tensors (the weights of the layers behind this attention) that payload
     workgroups of the launch read while the attention runs (mixdq_attention_f16_prefetch); no effect
@@ -1255,16 +1260,18 @@ def attention_f16(q, k, v, heads, scale_inv=None, zero_point=None, softmax_scale
                f"{n} should be a [B, T, C] fp16 GPU tensor with unit stride along C")
     B, Tq, C = q.shape
     _check(k.shape == v.shape and k.shape[0] == B and k.shape[2] == C, "q/k/v shapes disagree")
-    _check(C == heads * 64, "head_dim must be 64")
+    D = C // heads if heads > 0 else 0
+    _check(C == heads * D and D in ATTENTION_HEAD_DIMS, "head_dim must be 64, 40, 80 or 160")
     quant = scale_inv is not None
-    # (measurement only) recorded as ("attention", (B * heads * Tq, Tkv, 64, 64)): 4 * M * N * K FLOPs
-    _record("attention", B * heads * Tq, k.shape[1], 64, 64, False, attention_f16,
+    # (measurement only) recorded as ("attention", (B * heads * Tq, Tkv, D, D)): 4 * M * N * K FLOPs
+    _record("attention", B * heads * Tq, k.shape[1], D, D, False, attention_f16,
             (q, k, v, heads), dict(scale_inv=scale_inv, zero_point=zero_point,
                                    softmax_scale=softmax_scale, _cfg=_cfg, _abits=_abits))     # (measured without the payload)
     out = torch.empty((B, Tq, C), dtype=torch.int8 if quant else torch.float16, device=q.device)
-    sc = float(softmax_scale) if softmax_scale is not None else 0.125
+    sc = float(softmax_scale) if softmax_scale is not None else (0.125 if D == 64 else D ** -0.5)
     ctx = getattr(_TLS, "ctx", None)
-    if k.shape[1] > 128 and ctx is not None and ctx.device == q.device:   # a launch that can carry a payload
+    # a launch that can carry a payload (head_dim 64 only: the other widths' kernel ignores one)
+    if D == 64 and k.shape[1] > 128 and ctx is not None and ctx.device == q.device:
         ctx.trace.append(("attn", B * Tq, k.shape[1]))
         planned = ctx.payload()
         if _prefetch is None:
@@ -1277,13 +1284,13 @@ def attention_f16(q, k, v, heads, scale_inv=None, zero_point=None, softmax_scale
             ptrs = (ctypes.c_void_p * len(pf))(*[t.data_ptr() for t in pf])
             sizes = (ctypes.c_int64 * len(pf))(*[t.numel() * t.element_size() for t in pf])
             code = _lib.mixdq_attention_f16_prefetch(
-                q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, heads, 64, Tq, k.shape[1],
+                q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, heads, D, Tq, k.shape[1],
                 q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1),
                 out.stride(0), out.stride(1), sc, _ptr(scale_inv), _ptr(zero_point), ptrs, sizes, len(pf),
                 FLAGS | (int(_cfg) << 8) | _aflag(_abits), _stream())
         else:
             code = _lib.mixdq_attention_f16(
-                q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, heads, 64, Tq, k.shape[1],
+                q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, heads, D, Tq, k.shape[1],
                 q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1),
                 out.stride(0), out.stride(1), sc, _ptr(scale_inv), _ptr(zero_point),
                 FLAGS | (int(_cfg) << 8) | _aflag(_abits), _stream())

@@ -1,4 +1,5 @@
-// FP16 attention core for gfx950 (head_dim 64): O = softmax(Q K^T * scale) V, flash-style.
+// FP16 attention core for gfx950 (head_dim 64; 40, 80 and 160 in attn_hd_kernel below): O = softmax(Q K^T * scale) V,
+// flash-style.
 //
 // The reference keeps the attention matmuls in FP16 in both of its paths (SURVEY.md §0:
 // quant_block.py:630-637 — plain get_attention_scores + torch.bmm; only to_q/to_k/to_v/to_out.0 are
@@ -24,6 +25,7 @@
 // sums accumulated in FP32 from that rounded P (a third MFMA with a ones operand); O staged through LDS and stored as whole 128-B rows.
 #include "common.h"
 #include <cstdlib>
+#include <type_traits>
 #include "attn_core.h"
 
 namespace mixdq {
@@ -723,6 +725,264 @@ int launch_attn(AttnParams& p, int batch, bool quant, bool a4, hipStream_t strea
   return launch_status();
 }
 
+// ---- head widths 40, 80, 160 (SD 1.5 UNets: 8 heads at every level) --------------------------------------------
+// A sibling of the kernels above, which stay exactly as they were (head_dim 64).  One arithmetic for every form:
+// per 64-key tile, unpipelined -- S^T = K Q^T, mask, row maximum, FP32 exponentials rounded to FP16, rescale, then
+// O^T += V^T P^T and the row sums -- with the MFMA operand layouts of attn_short_kernel, generalised to D:
+//   Q K^T  KS = ceil(D / 16) k-steps.  D = 40 pads to 48: the half-step d 40..47 (lanes 32..63 of k-step 2) is an
+//          exact zero in BOTH operands (Q never loaded, K fragment replaced by zeros after the read).
+//   P V    DB = ceil(D / 32) 32-column tiles of O^T; at D = 40 / 80 the last one is partial: its rows d >= D read
+//          the V image's padding and are never stored (MFMA rows are independent).
+// LDS images, no swizzle -- padded pitches:
+//   K  pitch PCK x 16 B, PCK = (D / 8) | 1, odd: the 16 rows of a ds_read_b128 lane group fall in 16 distinct
+//      16-B bank quads.  D = 40: 80 B, 80: 176 B, 160: 336 B.
+//   V  pitch PCV x 16 B = 64 + 128 j bytes, the smallest that holds a row: the four rows of a ds_read_b64_tr_b16
+//      half-wave (64 B each) start 16 banks apart.  D = 40: 192 B, 80: 192 B, 160: 320 B.
+// Two stages (K | V of 64 keys each): LDS-DMA of tile t + 1 under the arithmetic of tile t, one barrier per tile.
+// Padding slots of an image receive a copy of the row's first chunk (every LDS-DMA lane writes; finite bytes).
+// Workgroups of WAVES x 32 query rows (4 or 2, chosen from ONE image as for head_dim 64); a wave's arithmetic does
+// not depend on WAVES or on the batch, so every form and every batch row give the same bits.
+template <int D>
+struct AttnHd {
+  static constexpr int DC = D / 8;                                   // 16-B chunks of a head row
+  static constexpr int KS = (D + 15) / 16;
+  static constexpr int DB = (D + 31) / 32;
+  static constexpr int PCK = DC | 1;
+  static constexpr int PCV = DC <= 4 ? 4 : 4 + 8 * ((DC - 4 + 7) / 8);
+  static constexpr int PK = 16 * PCK, PV = 16 * PCV;
+  static constexpr int SB = kKeys * (PK + PV);                       // one stage: K image then V image
+  static constexpr int PO = DB * 64 + 16;                            // output staging row
+  static constexpr int smem(int waves) { return 2 * SB > waves * 32 * PO ? 2 * SB : waves * 32 * PO; }
+  static_assert(D % 8 == 0 && DB * 64 <= PV && 2 * D <= PK, "geometry");
+};
+
+template <int I, int N, class F>
+__device__ __forceinline__ void static_for(F&& f) {
+  if constexpr (I < N) {
+    f(std::integral_constant<int, I>{});
+    static_for<I + 1, N>(f);
+  }
+}
+
+template <int OFF0, int OFF1>
+__device__ __forceinline__ void tr_read2_at(VFrag& f, unsigned addr) {
+  asm volatile("ds_read_b64_tr_b16 %0, %2 offset:%3\n\tds_read_b64_tr_b16 %1, %2 offset:%4"
+               : "=&v"(f.r.lo), "=&v"(f.r.hi)
+               : "v"(addr), "n"(OFF0), "n"(OFF1)
+               : "memory");
+}
+
+template <int D, int WAVES, bool QUANT, bool A4 = false>
+__global__ __launch_bounds__(WAVES * 64) void attn_hd_kernel(const AttnParams p) {
+  using G = AttnHd<D>;
+  float s_inv = 0.f, zp = 0.f;
+  if constexpr (QUANT) {
+    s_inv = *(const __attribute__((address_space(4))) float*)p.s_inv;
+    zp = *(const __attribute__((address_space(4))) float*)p.zp;
+  }
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l32 = lane & 31, hh = lane >> 5;
+  const int blk = p.xcd_map ? attn_block_of(blockIdx.x, p.attn_blocks) : (int)blockIdx.x;
+  const int qb = blk % p.qblocks;
+  const int head = (blk / p.qblocks) % p.heads;
+  const int b = blk / (p.qblocks * p.heads);
+  const int q0 = qb * (WAVES * 32) + wave * 32;
+  const int ntiles = (p.tkv + kKeys - 1) / kKeys;
+  const v8h zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+
+  // Q^T fragments: lane's query row, d = 16 ks + 8 h .. + 7 (zeros past D)
+  v8h qf[G::KS];
+  {
+    const int qr = min(q0 + l32, p.tq - 1);
+    const __half* qrow = p.q + b * p.q_bs + (long)qr * p.q_rs + head * D + hh * 8;
+#pragma unroll
+    for (int ks = 0; ks < G::KS; ++ks)
+      qf[ks] = 16 * ks + 8 * hh < D ? *reinterpret_cast<const v8h*>(qrow + ks * 16) : zero8;
+  }
+
+  // LDS-DMA staging of tile t into stage `buf`: wave-instruction i fills slots 64 i .. 64 i + 63 of the stage
+  // (K image: instructions 0 .. PCK - 1, V image: the rest); slot -> (row, chunk) of its image.  Keys past the
+  // end re-read the last key: finite data whose scores are masked to -inf.
+  const char* kbase = reinterpret_cast<const char*>(p.k + b * p.k_bs + head * D);
+  const char* vbase = reinterpret_cast<const char*>(p.v + b * p.v_bs + head * D);
+  const unsigned krs = 2u * (unsigned)p.k_rs, vrs = 2u * (unsigned)p.v_rs;
+  auto stage = [&](int buf, int t) {
+    char* dst = smem + buf * G::SB;
+    for (int i = wave; i < G::PCK + G::PCV; i += WAVES) {   // wave-uniform
+      const bool isv = i >= G::PCK;
+      const int pc = isv ? G::PCV : G::PCK;
+      const int s = (isv ? i - G::PCK : i) * 64 + lane;
+      const int row = s / pc;
+      int ch = s - row * pc;
+      if (ch >= G::DC) ch = 0;                          // pitch padding: a copy of the row's first chunk
+      const unsigned key = (unsigned)min(t * kKeys + row, p.tkv - 1);
+      glds16((isv ? vbase : kbase) + (key * (isv ? vrs : krs) + (unsigned)ch * 16), dst + i * 1024);
+    }
+  };
+
+  const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
+  const int q4 = (lane & 15) >> 2, pp = lane & 3, g16 = (lane >> 4) & 1;
+  const unsigned k_a = lds0 + l32 * G::PK + hh * 16;                         // row l32, chunk 2 ks + h
+  const unsigned v_a = lds0 + kKeys * G::PK + (4 * hh + q4) * G::PV + 32 * g16 + 8 * pp;
+
+  v16f o[G::DB], lsum;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+#pragma unroll
+    for (int db = 0; db < G::DB; ++db) o[db][i] = 0.f;
+    lsum[i] = 0.f;
+  }
+  float m_i = -INFINITY;
+  const float c = p.scale_log2;
+  v8h ones;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) ones[i] = (_Float16)1.f;
+
+  stage(0, 0);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  for (int t = 0; t < ntiles; ++t) {
+    const unsigned sbuf = (unsigned)(t & 1) * G::SB;
+    if (t + 1 < ntiles) stage((t + 1) & 1, t + 1);    // its stage was last read in tile t - 1 (barrier since)
+    v16f sc[2];
+    static_for<0, 2>([&](auto kbc) {
+      constexpr int kb = decltype(kbc)::value;
+      v8h kf[G::KS];
+      static_for<0, G::KS>([&](auto ksc) {
+        constexpr int ks = decltype(ksc)::value;
+        lds_read128_imm<kb * 32 * G::PK + ks * 32>(kf[ks], k_a + sbuf);
+      });
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+      for (int ks = 0; ks < G::KS; ++ks) asm volatile("" : "+v"(kf[ks]));
+      if constexpr (D % 16 != 0) kf[G::KS - 1] = hh ? zero8 : kf[G::KS - 1];   // d D .. KS * 16 - 1: zeros
+#pragma unroll
+      for (int i = 0; i < 16; ++i) sc[kb][i] = 0.f;
+#pragma unroll
+      for (int ks = 0; ks < G::KS; ++ks)
+        sc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[ks], qf[ks], sc[kb], 0, 0, 0);
+    });
+    if (t == ntiles - 1 && (p.tkv & (kKeys - 1)) != 0) {     // mask the absent keys
+      const int lim = p.tkv - t * kKeys - 4 * hh;
+#pragma unroll
+      for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          if (32 * kb + 8 * (r >> 2) + (r & 3) >= lim) sc[kb][r] = -INFINITY;
+    }
+    float mx = sc[0][0];
+#pragma unroll
+    for (int r = 1; r < 16; ++r) mx = fmaxf(mx, sc[0][r]);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) mx = fmaxf(mx, sc[1][r]);
+    mx = half_max(mx);
+    const float m_new = fmaxf(m_i, mx);
+    const bool grew = m_new > m_i;
+    const float mc = m_new * c;
+    v8h pf[2][2];
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        pf[kb][r >> 3][r & 7] = (_Float16)__builtin_amdgcn_exp2f(__builtin_fmaf(sc[kb][r], c, -mc));
+    if (__builtin_amdgcn_ballot_w64(grew)) {
+      const float alpha = __builtin_amdgcn_exp2f((m_i - m_new) * c);
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+#pragma unroll
+        for (int db = 0; db < G::DB; ++db) o[db][i] *= alpha;
+      }
+      lsum[0] *= alpha;
+    }
+    m_i = m_new;
+    // O^T += V^T P^T, 16 keys at a time (k-slot order of attn_pv_tile)
+    static_for<0, 4>([&](auto gc) {
+      constexpr int kb = decltype(gc)::value >> 1, u = decltype(gc)::value & 1;
+      constexpr int r0 = 32 * kb + 16 * u;
+      VFrag vf[G::DB];
+      static_for<0, G::DB>([&](auto dbc) {
+        constexpr int db = decltype(dbc)::value;
+        tr_read2_at<r0 * G::PV + 64 * db, (r0 + 8) * G::PV + 64 * db>(vf[db], v_a + sbuf);
+      });
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+      for (int db = 0; db < G::DB; ++db) asm volatile("" : "+v"(vf[db].h));
+#pragma unroll
+      for (int db = 0; db < G::DB; ++db)
+        o[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[db].h, pf[kb][u], o[db], 0, 0, 0);
+      lsum = __builtin_amdgcn_mfma_f32_32x32x16_f16(ones, pf[kb][u], lsum, 0, 0, 0);
+    });
+    // tile t + 1 has landed (every wave's pieces) and every wave is done with tile t's stage
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+  }
+
+  // ---- normalise, stage through LDS (wave-private rows of PO bytes), store whole rows ----
+  const float inv = 1.f / lsum[0];
+  char* Os = smem + wave * (32 * G::PO);
+#pragma unroll
+  for (int db = 0; db < G::DB; ++db)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      if (32 * db + 8 * g >= D) continue;              // (compile-time) columns past the head
+      v4h w;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) w[j] = (_Float16)(o[db][4 * g + j] * inv);
+      *reinterpret_cast<v4h*>(Os + l32 * G::PO + (32 * db + 8 * g + 4 * hh) * 2) = w;
+    }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  constexpr int NCH = 32 * G::DC;                     // 16-B chunks of the wave's 32 output rows
+#pragma unroll
+  for (int i = 0; i < (NCH + 63) / 64; ++i) {
+    const int id = lane + 64 * i, row = id / G::DC, ch = id - row * G::DC;
+    if (id >= NCH || q0 + row >= p.tq) continue;
+    const uint4 w = *reinterpret_cast<const uint4*>(Os + row * G::PO + ch * 16);
+    const long off = b * p.o_bs + (long)(q0 + row) * p.o_rs + head * D + ch * 8;
+    if constexpr (!QUANT) {
+      *reinterpret_cast<uint4*>(reinterpret_cast<__half*>(p.out) + off) = w;
+    } else {
+      const __half* hv = reinterpret_cast<const __half*>(&w);
+      float x[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) x[j] = __half2float(hv[j]);
+      *reinterpret_cast<uint2*>(reinterpret_cast<int8_t*>(p.out) + off) =
+          p.unfused ? quantize_pack8<true, A4>(x, s_inv, zp) : quantize_pack8<false, A4>(x, s_inv, zp);
+    }
+  }
+}
+
+template <int D, int WAVES>
+int launch_attn_hd(AttnParams& p, int batch, bool quant, bool a4, hipStream_t stream) {
+  if ((long)p.qblocks * p.heads * batch > 0x7fffffffl) return MIXDQ_ERR_INVALID_ARG;
+  p.attn_blocks = p.qblocks * p.heads * batch;
+  p.pf_blocks = 0; p.n_pf = 0;                       // no payload workgroups at these widths
+  constexpr int smem = AttnHd<D>::smem(WAVES);
+  static bool seen[3][64] = {};
+#define MIXDQ_ATTN_HD_LAUNCH(Q, A, S)                                                                          \
+  do {                                                                                                         \
+    if (smem > 65536)                                                                                          \
+      if (const int st = lds_opt_in(reinterpret_cast<const void*>(&attn_hd_kernel<D, WAVES, Q, A>), smem,     \
+                                    seen[S])) return st;                                                       \
+    hipLaunchKernelGGL((attn_hd_kernel<D, WAVES, Q, A>), dim3(p.attn_blocks), dim3(WAVES * 64), smem, stream, p); \
+  } while (0)
+  if (quant && a4) MIXDQ_ATTN_HD_LAUNCH(true, true, 2);
+  else if (quant) MIXDQ_ATTN_HD_LAUNCH(true, false, 1);
+  else MIXDQ_ATTN_HD_LAUNCH(false, false, 0);
+#undef MIXDQ_ATTN_HD_LAUNCH
+  return launch_status();
+}
+
+template <int D>
+int launch_attn_hd_form(AttnParams& p, int batch, int heads, int tq, int force, bool quant, bool a4,
+                        hipStream_t stream) {
+  // 128-query workgroups when ONE image has at least half a chip of them (the head_dim 64 rule), else 64
+  const bool big = force ? force == 4 : (long)((tq + 127) / 128) * heads >= kNumCU / 2;
+  p.qblocks = big ? (tq + 127) / 128 : (tq + 63) / 64;
+  return big ? launch_attn_hd<D, 4>(p, batch, quant, a4, stream) : launch_attn_hd<D, 2>(p, batch, quant, a4, stream);
+}
+
 }  // namespace
 }  // namespace mixdq
 
@@ -741,7 +1001,8 @@ static int attention_f16_impl(const void* q, const void* k, const void* v, void*
   if (n_pf < 0 || n_pf > 16 || (n_pf > 0 && (!pf_ptrs || !pf_bytes))) return MIXDQ_ERR_INVALID_ARG;
   if (batch < 0 || heads <= 0 || tq < 0 || tkv <= 0) return MIXDQ_ERR_INVALID_ARG;
   if ((out_scale_inv == nullptr) != (out_zero_point == nullptr)) return MIXDQ_ERR_INVALID_ARG;
-  if (head_dim != kHeadDim) return MIXDQ_ERR_SHAPE;
+  const bool hd = head_dim == 40 || head_dim == 80 || head_dim == 160;   // attn_hd_kernel's widths
+  if (head_dim != kHeadDim && !hd) return MIXDQ_ERR_SHAPE;
   if (batch == 0 || tq == 0) return MIXDQ_OK;       // nothing to write (pointers may be null)
   if (!q || !k || !v || !out) return MIXDQ_ERR_INVALID_ARG;
   const bool quant = out_scale_inv != nullptr;
@@ -772,7 +1033,7 @@ static int attention_f16_impl(const void* q, const void* k, const void* v, void*
   static const int xcd_on = [] { const char* e = getenv("MIXDQ_ATTN_XCD"); return !(e && e[0] == '0'); }();   // A/B runs
   p.xcd_map = xcd_on;
   for (int i = 0; i < 16; ++i) { p.pf_ptr[i] = nullptr; p.pf_bytes[i] = 0; }
-  for (int i = 0; i < n_pf; ++i) {
+  for (int i = 0; i < (hd ? 0 : n_pf); ++i) {     // (no payload at the other widths: ignored)
     if (!pf_ptrs[i] || pf_bytes[i] < 16) continue;
     // the payload is a hint and must never fail a launch: a range that does not start on a 16-byte boundary
     // (a weight view at an odd offset) is rounded inward to the part that 16-byte loads can read
@@ -800,6 +1061,12 @@ static int attention_f16_impl(const void* q, const void* k, const void* v, void*
   // and, merging two partial softmaxes, it made a batch-1 result differ in its last bits from the
   // same image inside a batch.)
   const int force = (flags >> 8) & 0xff;         // 4 / 2: waves per workgroup of the pipelined kernel; 1: the short-key kernel
+  if (hd) {                                       // one kernel, 4- or 2-wave workgroups; no short-key form
+    if (force != 0 && force != 2 && force != 4) return MIXDQ_ERR_SHAPE;
+    if (head_dim == 40) return launch_attn_hd_form<40>(p, batch, heads, tq, force, quant, a4, stream);
+    if (head_dim == 80) return launch_attn_hd_form<80>(p, batch, heads, tq, force, quant, a4, stream);
+    return launch_attn_hd_form<160>(p, batch, heads, tq, force, quant, a4, stream);
+  }
   if (force == 1 && tkv > 2 * kKeys) return MIXDQ_ERR_SHAPE;
   static const bool short_on = [] { const char* e = getenv("MIXDQ_ATTN_SHORT"); return !(e && e[0] == '0'); }();   // A/B runs
   if (force == 1 || (force == 0 && short_on && tkv <= 2 * kKeys)) {   // cross-attention: 77 keys

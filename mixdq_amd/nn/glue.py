@@ -260,13 +260,35 @@ def _project_kv(to_k, to_v, ctx):
     return _project_context(to_k, ctx), _project_context(to_v, ctx)
 
 
-def _attention_core(q, k, v, heads, out_layer=None):
-    """FP16 attention on [B, T, C] tensors (heads of 64 columns), or None where the kernel does not take them.
-    `out_layer` (to_out.0): where it is a quantized layer that takes an operand, the launch writes that layer's
-    INT8 operand instead of the FP16 tensor and the return value is the layer's OUTPUT."""
+# head widths of the attention kernel (mixdq_amd._C.ATTENTION_HEAD_DIMS): 64 (SDXL), 40 / 80 / 160 (SD 1.5)
+ATTENTION_HEAD_DIMS = (40, 64, 80, 160)
+
+
+def attention_head_dim(C, heads):
+    """The head width of a [.., C] attention operand split into `heads` heads, or None where the kernel has none."""
+    if not (isinstance(C, int) and isinstance(heads, int) and heads > 0 and C % heads == 0):
+        return None
+    d = C // heads
+    return d if d in ATTENTION_HEAD_DIMS else None
+
+
+def kernel_takes_scale(head_dim, scale) -> bool:
+    """Whether HipAttnProcessor runs an attention module of softmax scale `scale` on the kernel: at head width 64
+    (or one not known) the scale must be 1 / 8, as it always was; at 40, 80 and 160 it must be diffusers' default
+    head_dim ** -0.5.  Anything else goes to the processor it replaced."""
+    if head_dim is None or head_dim == 64:
+        return scale == 0.125
+    return head_dim in ATTENTION_HEAD_DIMS and scale == head_dim ** -0.5
+
+
+def _attention_core(q, k, v, heads, out_layer=None, softmax_scale=None):
+    """FP16 attention on [B, T, C] tensors (heads of 64, 40, 80 or 160 columns), or None where the kernel does not
+    take them.  `out_layer` (to_out.0): where it is a quantized layer that takes an operand, the launch writes that
+    layer's INT8 operand instead of the FP16 tensor and the return value is the layer's OUTPUT.  `softmax_scale`:
+    None = the kernel's default, head_dim ** -0.5."""
     from mixdq_amd import _C
     C = q.shape[-1]
-    if C != heads * 64:
+    if attention_head_dim(C, heads) is None:
         return None
     for t in (q, k, v):
         if not (_f16_cuda(t) and t.dim() == 3 and t.stride(-1) == 1 and t.stride(0) % 8 == 0
@@ -276,9 +298,10 @@ def _attention_core(q, k, v, heads, out_layer=None):
         if (not _hooked(out_layer) and _takes_operand(out_layer) and getattr(out_layer, "in_features", None) == C
                 and out_layer.act_scales_inv.device == q.device):
             return out_layer._gemm(_C.attention_f16(q, k, v, heads, out_layer.act_scales_inv,
-                                                    out_layer.act_zero_points, _abits=_abits(out_layer)))
-        return out_layer(_C.attention_f16(q, k, v, heads))
-    return _C.attention_f16(q, k, v, heads)
+                                                    out_layer.act_zero_points, softmax_scale=softmax_scale,
+                                                    _abits=_abits(out_layer)))
+        return out_layer(_C.attention_f16(q, k, v, heads, softmax_scale=softmax_scale))
+    return _C.attention_f16(q, k, v, heads, softmax_scale=softmax_scale)
 
 
 def _operand(x, layer):
@@ -347,14 +370,15 @@ def _attention_hand_off(attn, x, context):
     falls back to the module-by-module form where its conditions do not hold -- among them: a forward hook or
     pre-hook on a layer the step reads directly (or a global one), so that every hook fires once per module and
     forward and sees what the module-by-module form would hand it; None: not an input of the kernels."""
-    if not (_f16_cuda(x) and x.dim() == 3 and getattr(attn.to_q, "out_features", None) == attn.heads * 64):
+    if not (_f16_cuda(x) and x.dim() == 3
+            and attention_head_dim(getattr(attn.to_q, "out_features", None), attn.heads) is not None):
         return None                                     # (decided before anything is launched)
     if context is None:
         qkv = _self_qkv(attn, x)
         q, k, v = qkv if qkv is not None else (attn.to_q(x), attn.to_k(x), attn.to_v(x))
     else:
         k, v = _project_kv(attn.to_k, attn.to_v, context)
-        y = _cross_one_launch(attn, x, k, v)
+        y = _cross_one_launch(attn, x, k, v)           # (head width 64 only; else to_q + the attention launch)
         if y is not None:
             return y
         q = attn.to_q(x)
@@ -385,7 +409,8 @@ class HipAttnProcessor:
     AttnProcessor2_0) whose softmax(q k^T) v runs on mixdq_attention_f16; the projections stay the (quantized)
     modules of `attn`.  Installed by `attn.set_processor(HipAttnProcessor())` for every module that has one.
     Covers what the SDXL UNet uses: no attention mask, no group / spatial norm inside the attention, no added
-    key / value projections, residual_connection False, softmax scale 1 / 8 -- anything else goes to the processor
+    key / value projections, residual_connection False, softmax scale 1 / 8 -- and SD 1.5's heads of 40, 80 or 160
+    columns at diffusers' default scale head_dim ** -0.5 (kernel_takes_scale) -- anything else goes to the processor
     it replaced."""
 
     def __init__(self, fallback=None, hand_off=False):
@@ -398,8 +423,10 @@ class HipAttnProcessor:
                  and getattr(attn, "group_norm", None) is None and getattr(attn, "spatial_norm", None) is None
                  and getattr(attn, "norm_q", None) is None and getattr(attn, "norm_k", None) is None
                  and not getattr(attn, "residual_connection", False)
-                 and getattr(attn, "rescale_output_factor", 1.0) == 1.0
-                 and getattr(attn, "scale", 0.125) == 0.125)       # (the kernel's softmax scale: 64 ** -0.5)
+                 and getattr(attn, "rescale_output_factor", 1.0) == 1.0)
+        scale = getattr(attn, "scale", 0.125)
+        plain = plain and kernel_takes_scale(
+            attention_head_dim(getattr(attn.to_q, "out_features", None), attn.heads), scale)
         if plain:
             ctx = hidden_states if encoder_hidden_states is None else encoder_hidden_states
             if encoder_hidden_states is not None and getattr(attn, "norm_cross", False):
@@ -408,7 +435,8 @@ class HipAttnProcessor:
             if self.hand_off:
                 o = _attention_hand_off(attn, hidden_states, None if encoder_hidden_states is None else ctx)
             if o is None:
-                o = _attention_core(attn.to_q(hidden_states), attn.to_k(ctx), attn.to_v(ctx), attn.heads)
+                o = _attention_core(attn.to_q(hidden_states), attn.to_k(ctx), attn.to_v(ctx), attn.heads,
+                                    softmax_scale=scale)
                 if o is not None:
                     o = attn.to_out[0](o)
             if o is not None:

@@ -569,17 +569,22 @@ class Attention(nn.Module):
         from mixdq_amd import _C
         out = self.to_out[0]
         C = q.shape[-1]
-        ok = (C == self.heads * 64 and all(_fusable_f16(t) and t.dim() == 3 and t.stride(-1) == 1
-                                           and t.stride(0) % 8 == 0 and t.stride(1) % 8 == 0
-                                           and t.data_ptr() % 16 == 0 for t in (q, k, v)))
+        D = C // self.heads
+        ok = (C == self.heads * D and D in _C.ATTENTION_HEAD_DIMS
+              and all(_fusable_f16(t) and t.dim() == 3 and t.stride(-1) == 1
+                      and t.stride(0) % 8 == 0 and t.stride(1) % 8 == 0
+                      and t.data_ptr() % 16 == 0 for t in (q, k, v)))
         def plain(y):          # (y, feeds of the LayerNorm that reads y) by two launches
             return y, (None if next_ln is None else _ln_feed(next_ln[0], y, next_ln[1]))
         if not ok:
             return plain(_linear_res(out, self.attend(q, k, v), residual))
+        sc = None if D == 64 else D ** -0.5          # (SDPA's default scale, as in attend)
         if _accel(out) and residual.is_contiguous():
-            o_int = _C.attention_f16(q, k, v, self.heads, *_qp(out), _prefetch=prefetch, _abits=_abits(out))
+            o_int = _C.attention_f16(q, k, v, self.heads, *_qp(out), softmax_scale=sc, _prefetch=prefetch,
+                                     _abits=_abits(out))
             return _gemm_res_ln(out, o_int, residual, next_ln)
-        return plain(_linear_res(out, _C.attention_f16(q, k, v, self.heads, _prefetch=prefetch), residual))
+        return plain(_linear_res(out, _C.attention_f16(q, k, v, self.heads, softmax_scale=sc, _prefetch=prefetch),
+                                 residual))
 
 
 CROSS_FUSE_MAX_ROWS = int(__import__("os").environ.get("MIXDQ_CROSS_FUSE_MAX_ROWS", "4096"))
