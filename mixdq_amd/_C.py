@@ -114,9 +114,9 @@ IGEMM_CONFIGS = {1: (64, 64, 64, 2), 3: (128, 128, 64, 2), 4: (64, 64, 128, 3),
                  28: (128, 320, 128, 2),   # ... on 16 waves of 32 x 80 (7 fragment reads per 10 MFMAs instead of 11)
                  35: (128, 128, 64, 3), 37: (64, 64, 128, 3), 41: (64, 128, 128, 3),
                  # 16x16x64-MFMA tiles (exactly one workgroup per CU on the UNet's M = 1024 / 4096
-                 # layers; 45 / 56: deeper pipelines) and the 4-stage 128x320 tile
+                 # layers; 45 / 56: deeper pipelines) and the 4- and 5-stage 128x320x64 tiles
                  42: (64, 80, 128, 3), 43: (64, 240, 128, 3), 44: (128, 80, 128, 3),
-                 45: (64, 80, 128, 4), 46: (128, 320, 64, 4), 56: (64, 80, 128, 6),
+                 45: (64, 80, 128, 4), 46: (128, 320, 64, 4), 47: (128, 320, 64, 5), 56: (64, 80, 128, 6),
                  # 256x256x128 on the four-phase loop (2 x 4 waves of 128x64, 16x16x64 MFMAs)
                  70: (256, 256, 128, 2),
                  # ... and its persistent form: one workgroup per CU walking its tiles (csrc/igemm_pp.h); what the
@@ -589,6 +589,9 @@ class GemmGroupTable:
         # struct mixdq_gemm_group: 5 pointers, int32 N, int32 reserved = 6 x 8 bytes
         self.table = torch.from_numpy(np.asarray(rows, dtype=np.int64)).to(self.members[0][0].device)
         self.key = tuple(r[0] for r in rows) + tuple(r[4] for r in rows)
+
+
+GROUPED_CONFIGS = (4, 35, 37, 41, 56)   # csrc/igemm.hip MIXDQ_GROUPED_CONFIGS: the ids qlinear_grouped's _cfg takes
 
 
 def qlinear_grouped(input_int8, table: "GemmGroupTable", *, _row_map=None, _cfg=0):
