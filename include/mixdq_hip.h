@@ -401,8 +401,10 @@ int mixdq_qlinear_w8a8_geglu(const int8_t* A, const int8_t* W_interleaved, const
                              int64_t M, int N, int K, const float* out_scale_inv,
                              const float* out_zero_point, int flags, mixdq_stream_t stream);
 
-/* FP16 attention core, head_dim D = 64, 40, 80 or 160 (MIXDQ_ERR_SHAPE otherwise; 40 / 80 / 160: SD 1.5's heads, one
- * kernel whose forms are 4 and 2; a payload of mixdq_attention_f16_prefetch is ignored there):
+/* FP16 attention core, head_dim D = 64, 40, 80 or 160 (MIXDQ_ERR_SHAPE otherwise; 40 / 80 / 160: SD 1.5's heads --
+ * forms 4 and 2 are one kernel, form 1 its short-key sibling for tkv <= 128, which is what a launch with so few keys
+ * gets by default (MIXDQ_ATTN_HD_SHORT=0 in the environment: forms 4 / 2 there too, for A/B runs); all forms give the
+ * same bits; a payload of mixdq_attention_f16_prefetch is ignored at these widths):
  * out[b, t, h*D + d] = softmax_k(q . k * softmax_scale) v, per
  * head h.  The reference keeps these matmuls in FP16 (quant_block.py:630-637: get_attention_scores
  * + torch.bmm; diffusers' AttnProcessor at run time) — only to_q/to_k/to_v/to_out.0 are quantized
@@ -413,7 +415,7 @@ int mixdq_qlinear_w8a8_geglu(const int8_t* A, const int8_t* W_interleaved, const
  * out: fp16 rows (out_scale_inv == null), or — fused producer of to_out.0's INT8 operand — int8
  * rows q = sat8(rint(f16_out * scale_inv + zero_point)) (same arithmetic as mixdq_quantize_f16_i8).
  * flags: MIXDQ_FLAG_UNFUSED selects the unfused quantize variant; bits 8..15 force the workgroup
- * shape (4 = 128 query rows, 2 = 64). */
+ * shape (4 = 128 query rows, 2 = 64; 1 = the short-key kernel, at every width: MIXDQ_ERR_SHAPE when tkv > 128). */
 int mixdq_attention_f16(const void* q_f16, const void* k_f16, const void* v_f16, void* out,
                         int batch, int heads, int head_dim, int tq, int tkv,
                         int64_t q_batch_stride, int64_t q_row_stride,

@@ -1257,6 +1257,10 @@ def attention_f16(q, k, v, heads, scale_inv=None, zero_point=None, softmax_scale
     workgroups of the launch read while the attention runs (mixdq_attention_f16_prefetch); no effect
     on the result.
     `_abits=4`: to_out.0's quantizer is a 4-bit one (the INT8 output clamped to [-128, -113]).
+    `_cfg`: 0 = the library's choice; 4 / 2 = 128- / 64-query workgroups of the tiled kernel; 1 = the short-key
+    kernel (Tkv <= 128: every key of a head staged once), at every head width -- what `_cfg=0` picks for so few
+    keys (MIXDQ_ATTN_SHORT=0 at width 64, MIXDQ_ATTN_HD_SHORT=0 at 40 / 80 / 160 keep the tiled kernel: A/B runs).
+    `_cfg=1` with more keys is refused (MIXDQ_ERR_SHAPE).  Every form gives the same bits.
     """
     for t, n in ((q, "q"), (k, "k"), (v, "v")):
         _check(t.is_cuda and t.dtype == torch.float16 and t.dim() == 3 and t.stride(-1) == 1,

@@ -753,6 +753,9 @@ struct AttnHd {
   static constexpr int SB = kKeys * (PK + PV);                       // one stage: K image then V image
   static constexpr int PO = DB * 64 + 16;                            // output staging row
   static constexpr int smem(int waves) { return 2 * SB > waves * 32 * PO ? 2 * SB : waves * 32 * PO; }
+  // the short-key form: waves per SIMD its register budget is compiled for (D = 160 keeps O^T alone in 80 registers)
+  static constexpr int SHORT_WPE = D <= 40 ? 4 : D <= 80 ? 3 : 2;
+  static constexpr int smem_short(int ntiles) { return ntiles * SB > 4 * 32 * PO ? ntiles * SB : 4 * 32 * PO; }
   static_assert(D % 8 == 0 && DB * 64 <= PV && 2 * D <= PK, "geometry");
 };
 
@@ -953,6 +956,190 @@ __global__ __launch_bounds__(WAVES * 64) void attn_hd_kernel(const AttnParams p)
   }
 }
 
+// SHORT key sequences at these widths (tkv <= 128: SD 1.5's cross-attention, 77 keys), the sibling of
+// attn_short_kernel: every key and value of the head is staged ONCE (one or two 64-key stages of attn_hd_kernel's
+// images, no ring), one barrier, then each wave runs attn_hd_kernel's tile arithmetic in attn_hd_kernel's order
+// with no further synchronisation until the output staging overlays the images.  Four waves x 32 queries.  The
+// register budget follows the width (AttnHd<D>::SHORT_WPE waves per SIMD); LDS is
+// ntiles stages (at least the output staging).  Bit-identical to attn_hd_kernel.
+template <int D, bool QUANT, bool A4 = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(AttnHd<D>::SHORT_WPE, AttnHd<D>::SHORT_WPE)))
+void attn_hd_short_kernel(const AttnParams p) {
+  using G = AttnHd<D>;
+  constexpr int WAVES = 4;
+  float s_inv = 0.f, zp = 0.f;
+  if constexpr (QUANT) {
+    s_inv = *(const __attribute__((address_space(4))) float*)p.s_inv;
+    zp = *(const __attribute__((address_space(4))) float*)p.zp;
+  }
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l32 = lane & 31, hh = lane >> 5;
+  const int blk = p.xcd_map ? attn_block_of(blockIdx.x, p.attn_blocks) : (int)blockIdx.x;
+  const int qb = blk % p.qblocks;
+  const int head = (blk / p.qblocks) % p.heads;
+  const int b = blk / (p.qblocks * p.heads);
+  const int q0 = qb * (WAVES * 32) + wave * 32;
+  const int ntiles = (p.tkv + kKeys - 1) / kKeys;      // 1 or 2
+  const v8h zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+
+  // Q^T fragments: lane's query row, d = 16 ks + 8 h .. + 7 (zeros past D)
+  v8h qf[G::KS];
+  {
+    const int qr = min(q0 + l32, p.tq - 1);
+    const __half* qrow = p.q + b * p.q_bs + (long)qr * p.q_rs + head * D + hh * 8;
+#pragma unroll
+    for (int ks = 0; ks < G::KS; ++ks)
+      qf[ks] = 16 * ks + 8 * hh < D ? *reinterpret_cast<const v8h*>(qrow + ks * 16) : zero8;
+  }
+
+  // staging as attn_hd_kernel (same images, same slot map), every tile at once: tile t lives in stage t
+  const char* kbase = reinterpret_cast<const char*>(p.k + b * p.k_bs + head * D);
+  const char* vbase = reinterpret_cast<const char*>(p.v + b * p.v_bs + head * D);
+  const unsigned krs = 2u * (unsigned)p.k_rs, vrs = 2u * (unsigned)p.v_rs;
+  auto stage = [&](int buf, int t) {
+    char* dst = smem + buf * G::SB;
+    for (int i = wave; i < G::PCK + G::PCV; i += WAVES) {   // wave-uniform
+      const bool isv = i >= G::PCK;
+      const int pc = isv ? G::PCV : G::PCK;
+      const int s = (isv ? i - G::PCK : i) * 64 + lane;
+      const int row = s / pc;
+      int ch = s - row * pc;
+      if (ch >= G::DC) ch = 0;                          // pitch padding: a copy of the row's first chunk
+      const unsigned key = (unsigned)min(t * kKeys + row, p.tkv - 1);
+      glds16((isv ? vbase : kbase) + (key * (isv ? vrs : krs) + (unsigned)ch * 16), dst + i * 1024);
+    }
+  };
+
+  const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
+  const int q4 = (lane & 15) >> 2, pp = lane & 3, g16 = (lane >> 4) & 1;
+  const unsigned k_a = lds0 + l32 * G::PK + hh * 16;                         // row l32, chunk 2 ks + h
+  const unsigned v_a = lds0 + kKeys * G::PK + (4 * hh + q4) * G::PV + 32 * g16 + 8 * pp;
+
+  v16f o[G::DB], lsum;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+#pragma unroll
+    for (int db = 0; db < G::DB; ++db) o[db][i] = 0.f;
+    lsum[i] = 0.f;
+  }
+  float m_i = -INFINITY;
+  const float c = p.scale_log2;
+  v8h ones;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) ones[i] = (_Float16)1.f;
+
+  for (int t = 0; t < ntiles; ++t) stage(t, t);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();                                    // the only barrier before the output staging
+  for (int t = 0; t < ntiles; ++t) {
+    const unsigned sbuf = (unsigned)t * G::SB;
+    v16f sc[2];
+    static_for<0, 2>([&](auto kbc) {
+      constexpr int kb = decltype(kbc)::value;
+      v8h kf[G::KS];
+      static_for<0, G::KS>([&](auto ksc) {
+        constexpr int ks = decltype(ksc)::value;
+        lds_read128_imm<kb * 32 * G::PK + ks * 32>(kf[ks], k_a + sbuf);
+      });
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+      for (int ks = 0; ks < G::KS; ++ks) asm volatile("" : "+v"(kf[ks]));
+      if constexpr (D % 16 != 0) kf[G::KS - 1] = hh ? zero8 : kf[G::KS - 1];   // d D .. KS * 16 - 1: zeros
+#pragma unroll
+      for (int i = 0; i < 16; ++i) sc[kb][i] = 0.f;
+#pragma unroll
+      for (int ks = 0; ks < G::KS; ++ks)
+        sc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[ks], qf[ks], sc[kb], 0, 0, 0);
+    });
+    if (t == ntiles - 1 && (p.tkv & (kKeys - 1)) != 0) {     // mask the absent keys
+      const int lim = p.tkv - t * kKeys - 4 * hh;
+#pragma unroll
+      for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          if (32 * kb + 8 * (r >> 2) + (r & 3) >= lim) sc[kb][r] = -INFINITY;
+    }
+    float mx = sc[0][0];
+#pragma unroll
+    for (int r = 1; r < 16; ++r) mx = fmaxf(mx, sc[0][r]);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) mx = fmaxf(mx, sc[1][r]);
+    mx = half_max(mx);
+    const float m_new = fmaxf(m_i, mx);
+    const bool grew = m_new > m_i;
+    const float mc = m_new * c;
+    v8h pf[2][2];
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        pf[kb][r >> 3][r & 7] = (_Float16)__builtin_amdgcn_exp2f(__builtin_fmaf(sc[kb][r], c, -mc));
+    if (__builtin_amdgcn_ballot_w64(grew)) {
+      const float alpha = __builtin_amdgcn_exp2f((m_i - m_new) * c);
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+#pragma unroll
+        for (int db = 0; db < G::DB; ++db) o[db][i] *= alpha;
+      }
+      lsum[0] *= alpha;
+    }
+    m_i = m_new;
+    // O^T += V^T P^T, 16 keys at a time (k-slot order of attn_pv_tile)
+    static_for<0, 4>([&](auto gc) {
+      constexpr int kb = decltype(gc)::value >> 1, u = decltype(gc)::value & 1;
+      constexpr int r0 = 32 * kb + 16 * u;
+      VFrag vf[G::DB];
+      static_for<0, G::DB>([&](auto dbc) {
+        constexpr int db = decltype(dbc)::value;
+        tr_read2_at<r0 * G::PV + 64 * db, (r0 + 8) * G::PV + 64 * db>(vf[db], v_a + sbuf);
+      });
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+      for (int db = 0; db < G::DB; ++db) asm volatile("" : "+v"(vf[db].h));
+#pragma unroll
+      for (int db = 0; db < G::DB; ++db)
+        o[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[db].h, pf[kb][u], o[db], 0, 0, 0);
+      lsum = __builtin_amdgcn_mfma_f32_32x32x16_f16(ones, pf[kb][u], lsum, 0, 0, 0);
+    });
+  }
+  __syncthreads();                                    // every wave is done with the K / V images
+
+  // ---- normalise, stage through LDS (wave-private rows of PO bytes), store whole rows ----
+  const float inv = 1.f / lsum[0];
+  char* Os = smem + wave * (32 * G::PO);
+#pragma unroll
+  for (int db = 0; db < G::DB; ++db)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      if (32 * db + 8 * g >= D) continue;              // (compile-time) columns past the head
+      v4h w;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) w[j] = (_Float16)(o[db][4 * g + j] * inv);
+      *reinterpret_cast<v4h*>(Os + l32 * G::PO + (32 * db + 8 * g + 4 * hh) * 2) = w;
+    }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  constexpr int NCH = 32 * G::DC;                     // 16-B chunks of the wave's 32 output rows
+#pragma unroll
+  for (int i = 0; i < (NCH + 63) / 64; ++i) {
+    const int id = lane + 64 * i, row = id / G::DC, ch = id - row * G::DC;
+    if (id >= NCH || q0 + row >= p.tq) continue;
+    const uint4 w = *reinterpret_cast<const uint4*>(Os + row * G::PO + ch * 16);
+    const long off = b * p.o_bs + (long)(q0 + row) * p.o_rs + head * D + ch * 8;
+    if constexpr (!QUANT) {
+      *reinterpret_cast<uint4*>(reinterpret_cast<__half*>(p.out) + off) = w;
+    } else {
+      const __half* hv = reinterpret_cast<const __half*>(&w);
+      float x[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) x[j] = __half2float(hv[j]);
+      *reinterpret_cast<uint2*>(reinterpret_cast<int8_t*>(p.out) + off) =
+          p.unfused ? quantize_pack8<true, A4>(x, s_inv, zp) : quantize_pack8<false, A4>(x, s_inv, zp);
+    }
+  }
+}
+
 template <int D, int WAVES>
 int launch_attn_hd(AttnParams& p, int batch, bool quant, bool a4, hipStream_t stream) {
   if ((long)p.qblocks * p.heads * batch > 0x7fffffffl) return MIXDQ_ERR_INVALID_ARG;
@@ -975,8 +1162,31 @@ int launch_attn_hd(AttnParams& p, int batch, bool quant, bool a4, hipStream_t st
 }
 
 template <int D>
+int launch_attn_hd_short(AttnParams& p, int batch, bool quant, bool a4, hipStream_t stream) {
+  p.qblocks = (p.tq + 127) / 128;
+  if ((long)p.qblocks * p.heads * batch > 0x7fffffffl) return MIXDQ_ERR_INVALID_ARG;
+  p.attn_blocks = p.qblocks * p.heads * batch;
+  p.pf_blocks = 0; p.n_pf = 0;
+  const int smem = AttnHd<D>::smem_short((p.tkv + kKeys - 1) / kKeys);   // one stage per 64 keys: 1 or 2
+  static bool seen[3][64] = {};
+#define MIXDQ_ATTN_HD_LAUNCH(Q, A, S)                                                                          \
+  do {                                                                                                         \
+    if (AttnHd<D>::smem_short(2) > 65536)                                                                      \
+      if (const int st = lds_opt_in(reinterpret_cast<const void*>(&attn_hd_short_kernel<D, Q, A>),            \
+                                    AttnHd<D>::smem_short(2), seen[S])) return st;                             \
+    hipLaunchKernelGGL((attn_hd_short_kernel<D, Q, A>), dim3(p.attn_blocks), dim3(256), smem, stream, p);      \
+  } while (0)
+  if (quant && a4) MIXDQ_ATTN_HD_LAUNCH(true, true, 2);
+  else if (quant) MIXDQ_ATTN_HD_LAUNCH(true, false, 1);
+  else MIXDQ_ATTN_HD_LAUNCH(false, false, 0);
+#undef MIXDQ_ATTN_HD_LAUNCH
+  return launch_status();
+}
+
+template <int D>
 int launch_attn_hd_form(AttnParams& p, int batch, int heads, int tq, int force, bool quant, bool a4,
                         hipStream_t stream) {
+  if (force == 1) return launch_attn_hd_short<D>(p, batch, quant, a4, stream);
   // 128-query workgroups when ONE image has at least half a chip of them (the head_dim 64 rule), else 64
   const bool big = force ? force == 4 : (long)((tq + 127) / 128) * heads >= kNumCU / 2;
   p.qblocks = big ? (tq + 127) / 128 : (tq + 63) / 64;
@@ -1060,9 +1270,15 @@ static int attention_f16_impl(const void* q, const void* k, const void* v, void*
   // gone: after the loop was pipelined it no longer won -- 16.9 vs 16.2 us, tools/bench_attn.py --
   // and, merging two partial softmaxes, it made a batch-1 result differ in its last bits from the
   // same image inside a batch.)
-  const int force = (flags >> 8) & 0xff;         // 4 / 2: waves per workgroup of the pipelined kernel; 1: the short-key kernel
-  if (hd) {                                       // one kernel, 4- or 2-wave workgroups; no short-key form
-    if (force != 0 && force != 2 && force != 4) return MIXDQ_ERR_SHAPE;
+  int force = (flags >> 8) & 0xff;               // 4 / 2: waves per workgroup of the pipelined kernel; 1: the short-key kernel
+  if (hd) {
+    // form 1: attn_hd_short_kernel, every key staged once (tkv <= 128: the 77-key cross-attention) -- the automatic
+    // choice there, from the key count alone (MIXDQ_ATTN_HD_SHORT=0 keeps forms 2 / 4 for A/B runs); forms 2 / 4:
+    // attn_hd_kernel in 2- or 4-wave workgroups.  All three give the same bits.
+    if (force != 0 && force != 1 && force != 2 && force != 4) return MIXDQ_ERR_SHAPE;
+    if (force == 1 && tkv > 2 * kKeys) return MIXDQ_ERR_SHAPE;
+    static const bool hd_short_on = [] { const char* e = getenv("MIXDQ_ATTN_HD_SHORT"); return !(e && e[0] == '0'); }();
+    if (force == 0 && hd_short_on && tkv <= 2 * kKeys) force = 1;
     if (head_dim == 40) return launch_attn_hd_form<40>(p, batch, heads, tq, force, quant, a4, stream);
     if (head_dim == 80) return launch_attn_hd_form<80>(p, batch, heads, tq, force, quant, a4, stream);
     return launch_attn_hd_form<160>(p, batch, heads, tq, force, quant, a4, stream);

@@ -52,6 +52,7 @@ _ACT_TAG = "_mixdq_silu_applied"     # on an FP16 tensor: its _version when HipG
 _SILU_PAIR = "_mixdq_silu_module"    # in a folding HipGroupNorm's __dict__: a weak reference to the SiLU it folds
 _OPS_TAG = "_mixdq_operands"        # on an FP16 tensor: (its _version, [(scale_inv, zero_point, bits, int8), ...])
 _CONSUMERS = "_mixdq_consumers"     # in a swapped producer's __dict__: the layers its parent hands its output to
+_DIRECT = "_mixdq_direct"           # in a HipGroupNorm's __dict__: its consumers read the norm itself, no SiLU between
 
 
 def _f16_cuda(x) -> bool:
@@ -126,7 +127,9 @@ class HipGroupNorm(nn.GroupNorm):
             silu = self._folds()
             # (the consumer reads silu(norm(x)): its operand can ride along only where the SiLU does)
             # (8-bit quantizers only: the GroupNorm launch refuses a 4-bit clamp)
-            cons = [c for c in _consumers(self, x.shape[1], x.device) if _abits(c) == 8][:1] if silu else []
+            # (a DIRECT consumer -- a Transformer2DModel's conv proj_in -- reads the norm itself)
+            rides = silu or (self.__dict__.get(_DIRECT, False) and not self.fuse_silu)
+            cons = [c for c in _consumers(self, x.shape[1], x.device) if _abits(c) == 8][:1] if rides else []
             qp = (cons[0].act_scales_inv, cons[0].act_zero_points) if cons else (None, None)
             q, y = _C.groupnorm_silu_quantize(x, self.num_groups, self.weight, self.bias, self.eps, *qp,
                                               silu=silu, want_f16=True)[:2]
@@ -485,6 +488,12 @@ OPERAND_PAIRS = {
 }
 
 
+# ... and parents whose GroupNorm output goes to the layer with NO activation between: the Transformer2DModel of a
+# network with conv projections (SD 1.5, use_linear_projection False: proj_in(norm(x)) on the image).  With linear
+# projections proj_in reads a reshaped view, another tensor object, and finds nothing attached.
+DIRECT_OPERAND_PAIRS = {"Transformer2DModel": (("norm", ("proj_in",)),)}
+
+
 def _submodule(root, path):
     for part in path.split("."):
         root = getattr(root, "_modules", {}).get(part)
@@ -549,6 +558,18 @@ def swap_glue_modules(unet: nn.Module, attention: bool = True, silu_pairs=None, 
             if cons:
                 prod.__dict__[_CONSUMERS] = cons       # (not registered as sub-modules: plain references)
                 n["operand_links"] += len(cons)
+        for prod_path, cons_paths in (DIRECT_OPERAND_PAIRS.get(type(parent).__name__, ())
+                                      if operand_pairs is None else ()):
+            prod = _submodule(parent, prod_path)
+            if type(prod) is not HipGroupNorm or _CONSUMERS in prod.__dict__ or prod.__dict__.get("fuse_silu"):
+                continue
+            # only a Conv2d-like consumer gets the norm's own output tensor (see DIRECT_OPERAND_PAIRS)
+            cons = tuple(c for c in (_submodule(parent, p) for p in cons_paths)
+                         if c is not None and hasattr(c, "in_channels"))
+            if cons:
+                prod.__dict__[_CONSUMERS] = cons
+                prod.__dict__[_DIRECT] = True
+                n["operand_links"] += len(cons)
     for mod in unet.modules():
         if isinstance(mod, _HipAttend) and not mod.__dict__.get("hand_off"):
             mod.__dict__["hand_off"] = True
@@ -563,6 +584,7 @@ def unswap_glue_modules(unet: nn.Module) -> None:
     """Restore the stock classes (and attention processors) swap_glue_modules replaced."""
     for mod in unet.modules():
         mod.__dict__.pop(_CONSUMERS, None)
+        mod.__dict__.pop(_DIRECT, None)
         mod.__dict__.pop("hand_off", None)
         mod.__dict__.pop(_BOS_BUFS, None)
         if isinstance(mod, _HipAttend) or isinstance(getattr(mod, "processor", None), HipAttnProcessor):

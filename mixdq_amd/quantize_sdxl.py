@@ -224,10 +224,13 @@ def hip_graph_opt(unet, args=None, warmup: int = 3):
 cuda_graph_opt = hip_graph_opt   # the reference's name
 
 
-def example_inputs(batch_size: int, sample_size: int, device, in_channels: int = 4, seed=None):
+def example_inputs(batch_size: int, sample_size: int, device, in_channels: int = 4, seed=None, cfg=None):
     """Synthetic UNet inputs of the reference's harness (quantize_sdxl.py:350-373):
     sample rand(B,4,L,L), encoder_hidden_states rand(B,77,2048), timestep 999.,
-    text_embeds rand(B,1280), time_ids [[S,S,0,0,S,S]] * B with S = 8 * L, all fp16."""
+    text_embeds rand(B,1280), time_ids [[S,S,0,0,S,S]] * B with S = 8 * L, all fp16.
+    `cfg`: the network's config where it is not SDXL's (mixdq_amd.unet.SD15_CONFIG: context [B, 77, 768] and, the
+    network having no addition embedding, added_cond_kwargs None)."""
+    cfg = cfg or {}
     g = None
     if seed is not None:
         g = torch.Generator(device="cpu").manual_seed(seed)
@@ -239,8 +242,8 @@ def example_inputs(batch_size: int, sample_size: int, device, in_channels: int =
     return dict(
         sample=rand(batch_size, in_channels, sample_size, sample_size),
         timestep=torch.tensor(999., device=device),
-        encoder_hidden_states=rand(batch_size, 77, 2048),
-        added_cond_kwargs=dict(
+        encoder_hidden_states=rand(batch_size, 77, cfg.get("cross_attention_dim", 2048)),
+        added_cond_kwargs=None if cfg.get("addition_embed_type", "text_time") is None else dict(
             time_ids=torch.tensor([[px, px, 0., 0., px, px]], dtype=torch.float16,
                                   device=device).repeat(batch_size, 1),
             text_embeds=rand(batch_size, 1280)),

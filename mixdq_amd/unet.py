@@ -400,6 +400,43 @@ SDXL_CONFIG = dict(
     norm_num_groups=32,
 )
 
+# The SD 1.5 UNet (the reference's third model: dreamshaper-7 under LCM-LoRA, configs/stable-diffusion/lcm_lora.yaml,
+# model_type 'sd'), diffusers' names for it.  What differs from SDXL besides the sizes: four levels with one
+# transformer layer each (none at the innermost), EIGHT heads at every level -- heads of 40 / 80 / 160 / 160 columns
+# (mid block: 160) -- no addition embedding, and 1x1 Conv2d proj_in / proj_out (use_linear_projection False).
+# 859 520 964 parameters; 282 quantizable layers = 184 Linear + 98 Conv2d.
+SD15_CONFIG = dict(
+    in_channels=4, out_channels=4,
+    block_out_channels=(320, 640, 1280, 1280),
+    layers_per_block=2,
+    transformer_layers_per_block=(1, 1, 1, 0),
+    mid_transformer_layers=1,
+    head_dim=None,
+    num_attention_heads=8,             # a head COUNT per level instead of a head width: width = channels / 8
+    cross_attention_dim=768,
+    time_embed_dim=1280,
+    addition_embed_type=None,          # no add_embedding; forward ignores added_cond_kwargs
+    addition_time_embed_dim=None,
+    projection_class_embeddings_input_dim=None,
+    use_linear_projection=False,       # Transformer2DModel.proj_in / proj_out are 1x1 convs
+    norm_num_groups=32,
+)
+
+
+def head_width(cfg, channels: int) -> int:
+    """Width of an attention head at a level of `channels` channels: cfg['head_dim'] (SDXL, the toy networks), or
+    channels / cfg['num_attention_heads'] where the network fixes the head COUNT instead (SD 1.5)."""
+    heads = cfg.get("num_attention_heads")
+    if heads:
+        if channels % heads:
+            raise ValueError(f"{channels} channels do not split into {heads} heads")
+        return channels // heads
+    return cfg["head_dim"]
+
+
+def _linear_proj(cfg) -> bool:
+    return bool(cfg.get("use_linear_projection", True))
+
 
 def sinusoidal_embedding(t: torch.Tensor, dim: int) -> torch.Tensor:
     """diffusers Timesteps(dim, flip_sin_to_cos=True, downscale_freq_shift=0)."""
@@ -848,14 +885,41 @@ class BasicTransformerBlock(nn.Module):
         return self.ff.forward_fused(ff, x, next_ln=next_ln)        # ... and the next block's norm1 feeds
 
 
+def _proj_rows(conv, feed, bhw, residual=None):
+    """A 1x1 Conv2d proj_in / proj_out of a Transformer2DModel on token rows: `feed` = (tensor, quantized?) as rows
+    [B, HW, C] -- the NHWC memory of the image -- returns rows [B, HW, N] (+ `residual`, rows too).  Over those rows
+    the 1x1 conv IS a Linear, and a W8A8 layer runs as one: the INT8 GEMM entry point on the [N, C] view of the
+    conv's KRSC weight, the residual in its epilogue (no conv path is involved).  Any other layer (FP16 network,
+    FP fallback, de-fused reference) is called as the module it is, on the image view of the same memory."""
+    t, quantized = feed
+    B, H, W = bhw
+    if (getattr(conv, "valid_for_acceleration", False) and conv.split == 0 and not conv.w_packed4
+            and (quantized or _fusable_f16(t)) and (quantized or not DEFUSE)):
+        from mixdq_amd.op.qlinear import qlinear
+        from mixdq_amd.nn.Conv2d import quant_op
+        x_int = t if quantized else quant_op(t, *_qp(conv))
+        w = conv.weight_int
+        w2 = w.permute(0, 2, 3, 1).reshape(w.shape[0], -1)              # [N, C]: a view of the KRSC storage
+        fold = residual is not None and residual.is_contiguous() and not DEFUSE
+        y = qlinear(x_int, w2, conv.weight_scales, conv.act_scales, conv.act_zero_points, conv.bias0, conv.scale,
+                    conv.bias0, conv.bias, _residual=residual if fold else None)
+        return y if residual is None or fold else y + residual
+    img = t.reshape(B, H, W, t.shape[-1]).permute(0, 3, 1, 2)            # [B, C, H, W], channels-last in memory
+    y = conv(img).permute(0, 2, 3, 1).reshape(B, H * W, -1)
+    return y if residual is None else y + residual
+
+
 class Transformer2DModel(nn.Module):
-    def __init__(self, dim, depth, cross_dim, head_dim, groups):
+    def __init__(self, dim, depth, cross_dim, head_dim, groups, linear_proj=True):
         super().__init__()
         self.norm = nn.GroupNorm(groups, dim, eps=1e-6)
-        self.proj_in = nn.Linear(dim, dim)
+        # diffusers' use_linear_projection: Linear on the token rows (SDXL), or a 1x1 Conv2d on the image (SD 1.5:
+        # weights [C, C, 1, 1]) -- the same arithmetic, applied before / after the image <-> tokens reshape
+        self.proj_in = nn.Linear(dim, dim) if linear_proj else nn.Conv2d(dim, dim, 1, 1, 0)
         self.transformer_blocks = nn.ModuleList(
             [BasicTransformerBlock(dim, cross_dim, head_dim) for _ in range(depth)])
-        self.proj_out = nn.Linear(dim, dim)
+        self.proj_out = nn.Linear(dim, dim) if linear_proj else nn.Conv2d(dim, dim, 1, 1, 0)
+        self.linear_proj = bool(linear_proj)
 
     fused = False
 
@@ -874,7 +938,9 @@ class Transformer2DModel(nn.Module):
                 # proj_in -> block 0's norm1, attn1.to_out.0 -> norm2, attn2.to_out.0 -> norm3,
                 # ff.net.2 -> the next block's norm1
                 first = (blocks[0].norm1, blocks[0].ln1_consumers(), owner)
-                if q and _accel(self.proj_in):
+                if not self.linear_proj:       # (a conv projection keeps its own launch: the chain starts behind it)
+                    h, feeds = _proj_rows(self.proj_in, (feed, q), (B, H, W)), None
+                elif q and _accel(self.proj_in):
                     h, feeds = _gemm_res_ln(self.proj_in, feed, None, first)
                 else:
                     h = _run(self.proj_in, (feed, q))
@@ -885,12 +951,23 @@ class Transformer2DModel(nn.Module):
                     out = blk.forward_fused(h, context, feeds1=feeds, next_ln=nl, owner=owner)
                     h, feeds = out if nl is not None else (out, None)
             else:
-                h = _run(self.proj_in, (feed, q))
+                h = _run(self.proj_in, (feed, q)) if self.linear_proj else _proj_rows(self.proj_in, (feed, q), (B, H, W))
                 for blk in blocks:
                     h = blk(h, context)
             res_rows = res.permute(0, 2, 3, 1).reshape(B, H * W, C)
-            h = _linear_res(self.proj_out, h, res_rows)             # proj_out(h) + res
+            if self.linear_proj:
+                h = _linear_res(self.proj_out, h, res_rows)         # proj_out(h) + res
+            else:
+                h = _proj_rows(self.proj_out, (h, False), (B, H, W), residual=res_rows)
             return h.reshape(B, H, W, C).permute(0, 3, 1, 2)
+        if not self.linear_proj:
+            # diffusers with use_linear_projection False: norm -> conv -> tokens; tokens -> conv -> + residual
+            h = self.proj_in(self.norm(x))
+            h = h.permute(0, 2, 3, 1).reshape(B, H * W, C)
+            for blk in self.transformer_blocks:
+                h = blk(h, context)
+            h = h.reshape(B, H, W, C).permute(0, 3, 1, 2)
+            return self.proj_out(h) + res
         h = self.norm(x).permute(0, 2, 3, 1).reshape(B, H * W, C)   # free when channels-last
         h = self.proj_in(h)
         for blk in self.transformer_blocks:
@@ -936,8 +1013,8 @@ class DownBlock(nn.Module):
              for i in range(n_layers)])
         if depth:
             self.attentions = nn.ModuleList(
-                [Transformer2DModel(cout, depth, cfg["cross_attention_dim"], cfg["head_dim"],
-                                    cfg["norm_num_groups"]) for _ in range(n_layers)])
+                [Transformer2DModel(cout, depth, cfg["cross_attention_dim"], head_width(cfg, cout),
+                                    cfg["norm_num_groups"], _linear_proj(cfg)) for _ in range(n_layers)])
         self.has_attn = bool(depth)
         if add_down:
             self.downsamplers = nn.ModuleList([Downsample2D(cout)])
@@ -960,8 +1037,8 @@ class MidBlock(nn.Module):
     def __init__(self, c, temb, depth, cfg):
         super().__init__()
         self.attentions = nn.ModuleList(
-            [Transformer2DModel(c, depth, cfg["cross_attention_dim"], cfg["head_dim"],
-                                cfg["norm_num_groups"])])
+            [Transformer2DModel(c, depth, cfg["cross_attention_dim"], head_width(cfg, c),
+                                cfg["norm_num_groups"], _linear_proj(cfg))])
         self.resnets = nn.ModuleList([ResnetBlock2D(c, c, temb, cfg["norm_num_groups"])
                                       for _ in range(2)])
 
@@ -982,8 +1059,8 @@ class UpBlock(nn.Module):
         self.resnets = nn.ModuleList(res)
         if depth:
             self.attentions = nn.ModuleList(
-                [Transformer2DModel(cout, depth, cfg["cross_attention_dim"], cfg["head_dim"],
-                                    cfg["norm_num_groups"]) for _ in skip_channels])
+                [Transformer2DModel(cout, depth, cfg["cross_attention_dim"], head_width(cfg, cout),
+                                    cfg["norm_num_groups"], _linear_proj(cfg)) for _ in skip_channels])
         self.has_attn = bool(depth)
         if add_up:
             self.upsamplers = nn.ModuleList([Upsample2D(cout)])
@@ -1001,7 +1078,8 @@ class UpBlock(nn.Module):
 
 class SDXLUNet(nn.Module):
     """forward(sample, timestep, encoder_hidden_states, added_cond_kwargs, return_dict=False)
-    -> (noise_pred,), the call shape of quantize_sdxl.py:375-385."""
+    -> (noise_pred,), the call shape of quantize_sdxl.py:375-385.  `cfg`: overrides of SDXL_CONFIG; SD15_CONFIG
+    makes it the SD 1.5 UNet (same classes, diffusers' names for that network)."""
 
     def __init__(self, cfg=None):
         super().__init__()
@@ -1011,7 +1089,8 @@ class SDXLUNet(nn.Module):
         temb = cfg["time_embed_dim"]
         self.conv_in = nn.Conv2d(cfg["in_channels"], boc[0], 3, 1, 1)
         self.time_embedding = TimestepEmbedding(boc[0], temb)
-        self.add_embedding = TimestepEmbedding(cfg["projection_class_embeddings_input_dim"], temb)
+        if cfg.get("addition_embed_type", "text_time") is not None:
+            self.add_embedding = TimestepEmbedding(cfg["projection_class_embeddings_input_dim"], temb)
         n = cfg["layers_per_block"]
         depths = cfg["transformer_layers_per_block"]
         self.down_blocks = nn.ModuleList()
@@ -1290,11 +1369,12 @@ class SDXLUNet(nn.Module):
             t = torch.tensor([t], dtype=torch.float32, device=sample.device)
         t = t.reshape(-1).expand(B)
         emb = self.time_embedding(sinusoidal_embedding(t, cfg["block_out_channels"][0]).to(dtype))
-        time_ids = added_cond_kwargs["time_ids"]
-        text_embeds = added_cond_kwargs["text_embeds"]
-        tid = sinusoidal_embedding(time_ids.flatten(), cfg["addition_time_embed_dim"])
-        add = torch.cat([text_embeds, tid.reshape(B, -1).to(dtype)], dim=-1)
-        emb = emb + self.add_embedding(add)
+        if cfg.get("addition_embed_type", "text_time") is not None:    # (else: added_cond_kwargs is ignored)
+            time_ids = added_cond_kwargs["time_ids"]
+            text_embeds = added_cond_kwargs["text_embeds"]
+            tid = sinusoidal_embedding(time_ids.flatten(), cfg["addition_time_embed_dim"])
+            add = torch.cat([text_embeds, tid.reshape(B, -1).to(dtype)], dim=-1)
+            emb = emb + self.add_embedding(add)
 
         use_pf = bool(self.fused and PREFETCH and sample.is_cuda and _fusable_f16(sample) and not DEFUSE)
         if not use_pf:
