@@ -71,7 +71,9 @@ enum mixdq_flags {
      k[8g+4+j] in the low nibble, two's complement; [N, K/2] bytes, conv [K,R,S,C/2]).  Needs
      K % 32 == 0 (conv: C % 32 == 0).  No reference counterpart: the reference's 4-bit layers
      fall back to FP16 (nn/Linear.py:31,133-134); results equal the W8 path run on the unpacked
-     values.  bias0 / scale are those of the unpacked integers. */
+     values.  bias0 / scale are those of the unpacked integers.  A packed 3x3 / stride 1 / pad 1 conv
+     in the LDS-halo kernel's range (C % 64 == 0; mixdq_conv_halo_select_flags != 0) runs on that
+     kernel's W4 instantiations, forced ids 90 .. 93 and MIXDQ_FLAG_UPSAMPLE2X included. */
   MIXDQ_FLAG_W4 = 2,
   /* mixdq_qconv2d_w8a8_table only: X is [N, H/2, W/2, C] and the conv runs on its nearest-neighbour
      2x upsampling (H, W stay the conv's input size) -- Upsample2D's conv(interpolate(x, 2.0)) without
@@ -490,8 +492,18 @@ int mixdq_igemm_select_id_geglu_w2(int64_t M, int N, int k_total);
  * INT8 conv on when no tile is forced -- 90: 8 x 16 output pixels x 80 channels per workgroup, 91:
  * 8 x 8 x 80, 92: 16 x 16 x 80 (64-byte channel chunks), 93: 16 x 16 x 160 (K % 160 == 0; the choice from
  * batch 8 on) -- or 0 when the implicit-GEMM family runs it (not 3x3 / stride 1 / pad 1, C % 64 != 0,
- * H or W % 8 != 0, packed-W4 weights).  Ids 90 .. 93 can be forced through bits 8..15 of `flags`. */
+ * H or W % 8 != 0).  Ids 90 .. 93 can be forced through bits 8..15 of `flags`.  This query answers for
+ * int8 weights; mixdq_conv_halo_select_flags takes the launch's flags. */
 int mixdq_conv_halo_select(int N, int H, int W, int C, int K, int R, int S, int stride, int pad);
+/* The same for a launch with these `flags`: MIXDQ_FLAG_W4 asks for the packed-W4 instantiations (same
+ * range and the same rule as int8 weights, except that K <= 16 output channels without 16 x 16 patches stay
+ * on the implicit-GEMM family -- measured; forced ids 90 .. 93 still take them),
+ * MIXDQ_FLAG_W2 answers 0 (no packed-W2 conv); the other bits are ignored.  Like the nine-argument query it
+ * answers 0 for every width when MIXDQ_HALO_CONV=0 is set in the environment, and for MIXDQ_FLAG_W4 also when
+ * MIXDQ_HALO_W4=0 is (the A/B switch that keeps only packed convs on the implicit-GEMM family): the answer is what
+ * an unforced launch of this process does, from the same switches, each read once per process. */
+int mixdq_conv_halo_select_flags(int N, int H, int W, int C, int K, int R, int S, int stride, int pad,
+                                 int flags);
 
 /* Introspection (tests): the table the GEMM + GEGLU epilogue of the large tiles looks GELU up in --
  * 2 x 0x4c00 uint16: f16 bits of gelu(g) for the FP16 gate g with bits (sign << 15) | magnitude,

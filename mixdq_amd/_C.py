@@ -738,12 +738,20 @@ def qlinear_geglu(input_int8, weight_int8, scale, bias0, bias, out_scale_inv, ou
 if hasattr(_lib, "mixdq_conv_halo_select"):      # (absent in older builds used for A/B runs)
     _lib.mixdq_conv_halo_select.argtypes = [_i32] * 9
     _lib.mixdq_conv_halo_select.restype = _i32
+if hasattr(_lib, "mixdq_conv_halo_select_flags"):
+    _lib.mixdq_conv_halo_select_flags.argtypes = [_i32] * 10
+    _lib.mixdq_conv_halo_select_flags.restype = _i32
 HALO_TILES = {90: (8, 16, 80), 91: (8, 8, 80), 92: (16, 16, 80), 93: (16, 16, 160)}   # csrc/iconv.hip: output pixels (rows, columns), channels
 
 
-def conv_halo_select(N, H, W, C, K, R, S, stride, padding) -> int:
+def conv_halo_select(N, H, W, C, K, R, S, stride, padding, w4=False) -> int:
     """Tile id (HALO_TILES key) of the LDS-resident-halo kernel an unforced INT8 conv of this shape
-    runs on, or 0 (the implicit-GEMM family)."""
+    runs on, or 0 (the implicit-GEMM family).  w4: for packed 4-bit weights (the kernel's W4
+    instantiations; 0 in a library without them, or with MIXDQ_HALO_W4=0)."""
+    if w4:
+        if not hasattr(_lib, "mixdq_conv_halo_select_flags"):
+            return 0
+        return int(_lib.mixdq_conv_halo_select_flags(N, H, W, C, K, R, S, stride, padding, FLAG_W4))
     if not hasattr(_lib, "mixdq_conv_halo_select"):
         return 0
     return int(_lib.mixdq_conv_halo_select(N, H, W, C, K, R, S, stride, padding))
@@ -757,11 +765,12 @@ def _conv_geometry(input_int8, weight_int8, stride, padding, dilation):
     return N, C, H, W, K, R, S, P, Q
 
 
-def conv_upsample2x_supported(x_shape, weight_shape, stride, padding) -> bool:
-    """qconv2d_w8_a8_ohalf(..., _upsample2x=True) takes this conv (the LDS-halo kernel's range)."""
+def conv_upsample2x_supported(x_shape, weight_shape, stride, padding, w4=False) -> bool:
+    """qconv2d_w8_a8_ohalf(..., _upsample2x=True) takes this conv (the LDS-halo kernel's range).
+    weight_shape: [K, C, R, S] of the unpacked weights; w4: they are stored packed."""
     N, C, H, W = x_shape
     K, _, R, S = weight_shape
-    return conv_halo_select(N, 2 * H, 2 * W, C, K, R, S, stride, padding) != 0
+    return conv_halo_select(N, 2 * H, 2 * W, C, K, R, S, stride, padding, w4) != 0
 
 
 def qconv2d_w8_a8_ohalf(input_int8, weight_int8, weight_scale, input_scale, input_zero_point,
@@ -829,8 +838,8 @@ def qconv2d_w8_a8_ohalf(input_int8, weight_int8, weight_scale, input_scale, inpu
     sc = _f32vec(scale)
     bs = None if bias is None else bias.contiguous()
     kind = "conv"
-    if RECORD is not None and _cfg in (0, 90, 91, 92, 93) and not _w4 and dilation == 1:
-        tile = _cfg or conv_halo_select(N, H, W, C, K, R, S, stride, padding)
+    if RECORD is not None and _cfg in (0, 90, 91, 92, 93) and dilation == 1:
+        tile = _cfg or conv_halo_select(N, H, W, C, K, R, S, stride, padding, _w4)
         kind = f"conv_halo{tile}" if tile else "conv"
     _record(kind, N * P * Q, K, R * S * C, C, _w4, qconv2d_w8_a8_ohalf,
             (input_int8, weight_int8, weight_scale, input_scale, input_zero_point, scale,

@@ -6,7 +6,7 @@ namespace mixdq {
 
 struct HaloConvArgs {
   const int8_t* X;        // [NI, H, W, C] int8 (NHWC)
-  const int8_t* Wt;       // [K, 3, 3, C] int8
+  const int8_t* Wt;       // [K, 3, 3, C] int8, or [K, 3, 3, C / 2] packed signed 4-bit (halo_conv_launch w4)
   const float* scale;     // [K]
   const __half* bias;     // [K] or null
   const float* table;     // [81][K] tap-rectangle sums (mixdq_conv_border_table)
@@ -22,9 +22,11 @@ struct HaloConvArgs {
 
 // Tile id the halo kernel would run this problem on (90: 8x16 pixels x 80 channels, 91: 8x8 x 80, 92: 16x16 x 80, 93: 16x16 x 160), or 0
 // when the problem is outside its range (then the implicit-GEMM family of csrc/igemm.hip runs it).
-int halo_conv_select(int NI, int H, int W, int C, int K, int R, int S, int stride, int pad);
+// w4: for packed 4-bit weights (MIXDQ_FLAG_W4) -- the same range (what a forced tile id is checked against: ask
+// with w4 = false) and the same rule but for one measured exception (csrc/iconv.hip).
+int halo_conv_select(int NI, int H, int W, int C, int K, int R, int S, int stride, int pad, bool w4 = false);
 
-// Launch; `tile` from halo_conv_select (or forced).  Returns a mixdq_status.
-int halo_conv_launch(const HaloConvArgs& a, int tile, hipStream_t stream);
+// Launch; `tile` from halo_conv_select (or forced); w4: Wt is packed.  Returns a mixdq_status.
+int halo_conv_launch(const HaloConvArgs& a, int tile, hipStream_t stream, bool w4 = false);
 
 }  // namespace mixdq

@@ -21,6 +21,15 @@
 //        counts stay uniform.
 //   Waves: 4 (pixels) x 2 k-split groups, v_mfma_i32_16x16x64_i8, weights as the A operand: a lane
 //        holds one pixel and 4 consecutive channels per register quad, as in igemm.hip.
+//
+// W4 (the second set of instantiations): the weights are PACKED signed 4-bit values in the layout of
+// igemm_kernel.h ("nibble-planar per 8": byte j of dword g holds k[8g+j] in its high nibble and k[8g+4+j]
+// in its low nibble), [K, 3, 3, C / 2].  The activation side is the same code; a weight row of a chunk is
+// CK / 2 bytes, a filter-row stage half the bytes (padded to whole 1-KiB pieces: every lane derives its
+// (tap, row, 16-byte slot) from its linear slot in the stage, the slots past the end read the zero page), a
+// fragment is one ds_read_b64 and 6 VALU (w & 0xF0F0F0F0, (w << 4) & 0xF0F0F0F0 per dword) giving 16 q in
+// natural k order, and the epilogue's table rows and scale are staged as table * 16 and scale / 16 -- exact
+// power-of-two factors that commute with every FP32 rounding behind them (igemm_kernel.h).
 #include <type_traits>
 
 #include "iconv.h"
@@ -47,7 +56,7 @@ __device__ __forceinline__ uint32_t add_f16x2_(uint32_t a, uint32_t b) {
 // one 64-byte MFMA k-step of a chunk; 4 waves x BM / 4 pixels), or 64 with eight waves x BM / 8 pixels.
 // WNG: wave groups over the BN channels (1: every wave computes all BN channels of its pixels; 2: a wave
 // computes BN / 2 channels of twice the pixels -- 9 fragment reads per 20 MFMAs instead of 7 per 10).
-template <int TH, int TW, int BN, int CK, int WNG = 1>
+template <int TH, int TW, int BN, int CK, int WNG = 1, bool W4 = false>
 struct HaloGeom {
   static constexpr int BM = TH * TW;                                  // output pixels per workgroup
   static constexpr int HWP = TW + 2, HP = (TH + 2) * HWP;             // halo row length, halo pixels
@@ -56,8 +65,10 @@ struct HaloGeom {
   static constexpr int PPP = 1024 / CK, LPP = CK / 16;                // pixels per 1-KiB DMA piece; lanes per pixel
   static constexpr int H_NI = ((HP + PPP - 1) / PPP + NWAVES - 1) / NWAVES;   // halo pieces per wave
   static constexpr int HALO_BYTES = H_NI * NWAVES * 1024;
-  static constexpr int W_TAP = BN * CK, W_STAGE = 3 * W_TAP;          // one tap tile; one filter row
-  static constexpr int W_PIECES = W_STAGE / 1024;
+  static constexpr int WROW = W4 ? CK / 2 : CK, WLPP = WROW / 16;     // bytes, 16-byte slots of a weight row
+  static constexpr int W_TAP = BN * WROW;                             // one tap tile
+  static constexpr int W_PIECES = (3 * W_TAP + 1023) / 1024;          // one filter row, in whole DMA pieces
+  static constexpr int W_STAGE = W_PIECES * 1024;
   static constexpr int W_LO = W_PIECES / NWAVES, W_REM = W_PIECES % NWAVES, W_NI = W_LO + (W_REM ? 1 : 0);
   static constexpr int HALO_OFF = 3 * W_STAGE;
   static constexpr int MAIN_BYTES = HALO_OFF + 2 * HALO_BYTES;
@@ -67,7 +78,8 @@ struct HaloGeom {
   static constexpr int PART_BYTES = (KSPLIT - 1) * WPX * TM * TN * 4 * 64 * 4;   // k-split partials
   static constexpr int SMEM = MAIN_BYTES + 9 * BN * 4 + BN * 6;       // + 9 border-class rows, scale, bias
   static_assert(CK == 64 || CK == 128, "one or two 64-byte MFMA k-steps per chunk");
-  static_assert(W_TAP % 1024 == 0 && WTN % 16 == 0 && WTM % 16 == 0, "whole DMA pieces / MFMA tiles");
+  static_assert((W4 || W_TAP % 1024 == 0) && W_TAP % 256 == 0 && WTN % 16 == 0 && WTM % 16 == 0,
+                "whole DMA pieces (int8) / LDS bank rows / MFMA tiles");
   static_assert(WNG == 1 || KSPLIT == 1, "channel wave groups only without the k-split");
   static_assert(BM * CS_STRIDE + PART_BYTES <= MAIN_BYTES, "epilogue staging overlays the main buffers");
   static_assert(SMEM <= 160 * 1024, "LDS is 160 KiB per CU");
@@ -86,11 +98,16 @@ struct HaloGeom {
     if (CK == 64) return ((row >> 2) & 1) << 1;
     return TW == 16 ? ((row >> 1) & 3) << 1 : (row >> 1) & 7;
   }
+  // packed weight rows (64 or 32 bytes; a fragment read is a ds_read_b64, served per 32-lane half = 16 rows x
+  // 2 k-quarters on banks (a / 4) % 64): XOR of the 16-byte slot with these bits spreads the 16 rows over the
+  // 256-byte bank row -- conflict-free for every tile, tap, fragment and k-split group
+  // (tests/test_halo_w4_host.py enumerates it)
+  __device__ static int wswz(int row) { return WROW == 64 ? (row >> 2) & 3 : (row >> 3) & 1; }
 };
 
-template <int TH, int TW, int BN, int CK, int WNG = 1>
+template <int TH, int TW, int BN, int CK, int WNG = 1, bool W4 = false>
 __global__ __launch_bounds__(512, 2) void conv3x3_halo_kernel(const HaloConvArgs p) {
-  using G = HaloGeom<TH, TW, BN, CK, WNG>;
+  using G = HaloGeom<TH, TW, BN, CK, WNG, W4>;
   constexpr int BM = G::BM, HWP = G::HWP, HP = G::HP, TM = G::TM, TN = G::TN;
   constexpr int CS_STRIDE = G::CS_STRIDE;
   MIXDQ_ARGS_NOW(p.X, p.Wt, p.scale, p.bias, p.table, p.zp, p.D, p.res, p.res_div, p.NI, p.H, p.W, p.C,
@@ -178,11 +195,23 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo_kernel(const HaloConvArgs
 #pragma unroll
   for (int j = 0; j < G::W_NI; ++j) {
     const int q = wid + 8 * j;
-    const int s = q / (BN / G::PPP), row = (q - s * (BN / G::PPP)) * G::PPP + lane / G::LPP;
-    const int c16 = ((lane % G::LPP) ^ G::swz(row)) << 4;
-    w_ok[j] = q < G::W_PIECES && n0 + row < p.K;
-    w_off[j] = w_ok[j] ? (uint32_t)(n0 + row) * (uint32_t)(9 * C) + (uint32_t)(s * C) + c16 : 0u;
-    w_c16[j] = c16;
+    if constexpr (W4) {
+      // packed rows: the lane's linear 16-byte slot of the stage -> (tap, row, slot); a piece holds 16 or 32
+      // rows and may straddle two tap tiles (80 x 32 bytes = 2.5 pieces); offsets in packed bytes
+      const int L = q * 64 + lane;
+      const int s = L / (BN * G::WLPP), rem = L - s * (BN * G::WLPP);
+      const int row = rem / G::WLPP;
+      const int c16 = ((rem % G::WLPP) ^ G::wswz(row)) << 4;
+      w_ok[j] = L < 3 * BN * G::WLPP && n0 + row < p.K;
+      w_off[j] = w_ok[j] ? (uint32_t)(n0 + row) * (uint32_t)(9 * (C >> 1)) + (uint32_t)(s * (C >> 1)) + c16 : 0u;
+      w_c16[j] = c16;
+    } else {
+      const int s = q / (BN / G::PPP), row = (q - s * (BN / G::PPP)) * G::PPP + lane / G::LPP;
+      const int c16 = ((lane % G::LPP) ^ G::swz(row)) << 4;
+      w_ok[j] = q < G::W_PIECES && n0 + row < p.K;
+      w_off[j] = w_ok[j] ? (uint32_t)(n0 + row) * (uint32_t)(9 * C) + (uint32_t)(s * C) + c16 : 0u;
+      w_c16[j] = c16;
+    }
   }
   auto stage_halo = [&](int chunk, int buf) {
     char* dst = smem + G::HALO_OFF + buf * G::HALO_BYTES;
@@ -196,13 +225,14 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo_kernel(const HaloConvArgs
   };
   auto stage_w = [&](int chunk, int r) {       // filter row r of a channel chunk -> stage r
     char* dst = smem + r * G::W_STAGE;
-    const int c0 = chunk * CK;
+    const int c0 = W4 ? chunk * (CK / 2) : chunk * CK;   // in bytes of a stored row (packed: C / 2 of them)
+    const int cend = W4 ? C >> 1 : C;
     const bool live = chunk < nch;
-    const int8_t* base = p.Wt + (r * 3) * C + c0;
+    const int8_t* base = p.Wt + (r * 3) * cend + c0;
 #pragma unroll
     for (int j = 0; j < G::W_NI; ++j) {
       if (j >= G::W_LO && wid >= G::W_REM) continue;     // wave-uniform: this wave has no such piece
-      const bool ok = live && w_ok[j] && c0 + w_c16[j] < C;
+      const bool ok = live && w_ok[j] && c0 + w_c16[j] < cend;
       dma16(ok ? (const void*)(base + w_off[j]) : (const void*)zero, dst + (wid + 8 * j) * 1024);
     }
   };
@@ -237,7 +267,10 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo_kernel(const HaloConvArgs
 #pragma unroll
   for (int tn = 0; tn < TN; ++tn) {
     const int row = wn * G::WTN + tn * 16 + lrow;
-    w_rd[tn] = row * CK + (((kg * 4 + lkq) ^ G::swz(row)) << 4);
+    if constexpr (W4)   // 8 packed bytes = this lane's 16 k: half (lkq & 1) of 16-byte slot kg * 2 + (lkq >> 1)
+      w_rd[tn] = row * G::WROW + (((kg * 2 + (lkq >> 1)) ^ G::wswz(row)) << 4) + (lkq & 1) * 8;
+    else
+      w_rd[tn] = row * CK + (((kg * 4 + lkq) ^ G::swz(row)) << 4);
   }
   v4i acc[TN][TM];
 #pragma unroll
@@ -268,8 +301,15 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo_kernel(const HaloConvArgs
 #pragma unroll
         for (int t = 0; t < TM; ++t) xf[t] = *reinterpret_cast<const v4i*>(Hs + x_rd[t][r * 3 + s]);
 #pragma unroll
-        for (int tn = 0; tn < TN; ++tn)
-          wf[tn] = *reinterpret_cast<const v4i*>(Ws + s * G::W_TAP + w_rd[tn]);
+        for (int tn = 0; tn < TN; ++tn) {
+          if constexpr (W4) {     // int8 values 16 q in natural k order (igemm_kernel.h)
+            const uint2 w = *reinterpret_cast<const uint2*>(Ws + s * G::W_TAP + w_rd[tn]);
+            wf[tn] = v4i{(int)(w.x & 0xF0F0F0F0u), (int)((w.x << 4) & 0xF0F0F0F0u),
+                         (int)(w.y & 0xF0F0F0F0u), (int)((w.y << 4) & 0xF0F0F0F0u)};
+          } else {
+            wf[tn] = *reinterpret_cast<const v4i*>(Ws + s * G::W_TAP + w_rd[tn]);
+          }
+        }
 #pragma unroll
         for (int tn = 0; tn < TN; ++tn)
 #pragma unroll
@@ -291,6 +331,10 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo_kernel(const HaloConvArgs
   __half* P_BS = reinterpret_cast<__half*>(P_SC + BN);
   if (tab_on) {
     const v4f zero4 = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (W4) {      // exact: the MFMA ran on 16 q
+      pre_tab = pre_tab * 16.0f;
+      if (pre_on) pre_sc = pre_sc * 0.0625f;
+    }
     *reinterpret_cast<v4f*>(P_TAB + tab_c * BN + tab_q * 4) = tab_in ? pre_tab : zero4;
     if (pre_on) {
       *reinterpret_cast<v4f*>(P_SC + tab_q * 4) = tab_in ? pre_sc : zero4;
@@ -430,16 +474,16 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo_kernel(const HaloConvArgs
   }
 }
 
-template <int TH, int TW, int BN, int CK, int WNG = 1>
+template <int TH, int TW, int BN, int CK, int WNG = 1, bool W4 = false>
 int launch_halo(const HaloConvArgs& a, hipStream_t stream) {
-  using G = HaloGeom<TH, TW, BN, CK, WNG>;
+  using G = HaloGeom<TH, TW, BN, CK, WNG, W4>;
   static bool seen[64] = {};
-  if (const int st = lds_opt_in(reinterpret_cast<const void*>(&conv3x3_halo_kernel<TH, TW, BN, CK, WNG>),
+  if (const int st = lds_opt_in(reinterpret_cast<const void*>(&conv3x3_halo_kernel<TH, TW, BN, CK, WNG, W4>),
                                 G::SMEM, seen))
     return st;
   const int64_t grid = (int64_t)a.NI * (a.H / TH) * (a.W / TW) * ((a.K + BN - 1) / BN);
   if (grid <= 0 || grid > 0x7fffffff) return MIXDQ_ERR_INVALID_ARG;
-  conv3x3_halo_kernel<TH, TW, BN, CK, WNG><<<dim3((unsigned)grid), 512, G::SMEM, stream>>>(a);
+  conv3x3_halo_kernel<TH, TW, BN, CK, WNG, W4><<<dim3((unsigned)grid), 512, G::SMEM, stream>>>(a);
   return launch_status();
 }
 
@@ -450,7 +494,11 @@ int launch_halo(const HaloConvArgs& a, hipStream_t stream) {
 // (65 KB per 128 x 80 outputs and 128-byte chunk against 113 KB for 8 x 16) as soon as that still
 // gives every CU a workgroup (128 x 128 x 320 at batch 1: 21.2 vs 28.8 us; every layer from batch 4
 // on); otherwise the patch that fills the chip: 8 x 16, or 8 x 8 for the 32 x 32 layers at batch 1.
-int halo_conv_select(int NI, int H, int W, int C, int K, int R, int S, int stride, int pad) {
+// Packed W4 weights (DESIGN.md 3.21 has the per-layer table): the same range and the same rule, except that a conv
+// of at most 16 output channels stays on the implicit-GEMM family unless it gets 16 x 16 patches -- the UNet's
+// conv_out (320 -> 4) at batch 1 is slower on the 8 x 8 patches than on the narrow implicit-GEMM W4 tile (at batch 8,
+// on tile 92, it is about twice as fast); every other 3x3 conv of the UNet is faster here at batch 1 and at batch 8.
+int halo_conv_select(int NI, int H, int W, int C, int K, int R, int S, int stride, int pad, bool w4) {
   if (R != 3 || S != 3 || stride != 1 || pad != 1 || NI <= 0) return 0;
   if (C % 64 != 0 || K % 4 != 0 || H % 8 != 0 || W % 8 != 0) return 0;
   // 32-bit per-lane offsets inside one image / the weight tensor
@@ -461,11 +509,21 @@ int halo_conv_select(int NI, int H, int W, int C, int K, int R, int S, int strid
   if (H % 16 == 0 && W % 16 == 0 && K % 160 == 0 && (int64_t)NI * (H / 16) * (W / 16) * (K / 160) >= kNumCU)
     return 93;
   if (H % 16 == 0 && W % 16 == 0 && (int64_t)NI * (H / 16) * (W / 16) * tiles_n >= kNumCU) return 92;
+  if (w4 && K <= 16) return 0;
   if (W % 16 == 0 && (int64_t)NI * (H / 8) * (W / 16) * tiles_n >= kNumCU) return 90;
   return 91;
 }
 
-int halo_conv_launch(const HaloConvArgs& a, int tile, hipStream_t stream) {
+int halo_conv_launch(const HaloConvArgs& a, int tile, hipStream_t stream, bool w4) {
+  if (w4) {
+    switch (tile) {
+      case 90: return launch_halo<8, 16, 80, 128, 1, true>(a, stream);
+      case 91: return launch_halo<8, 8, 80, 128, 1, true>(a, stream);
+      case 92: return launch_halo<16, 16, 80, 64, 1, true>(a, stream);
+      case 93: return launch_halo<16, 16, 160, 64, 2, true>(a, stream);
+      default: return MIXDQ_ERR_INVALID_ARG;
+    }
+  }
   switch (tile) {
     case 90: return launch_halo<8, 16, 80, 128>(a, stream);
     case 91: return launch_halo<8, 8, 80, 128>(a, stream);

@@ -675,6 +675,17 @@ extern "C" int mixdq_qlinear_w8a8(const int8_t* A, const int8_t* W, const float*
                                  nullptr, 1, flags, stream);
 }
 
+// The A/B switches of the halo path, each read once per process: the launch and mixdq_conv_halo_select_flags answer
+// from the same values.
+static bool halo_conv_switch() {
+  static const bool on = [] { const char* e = getenv("MIXDQ_HALO_CONV"); return !(e && e[0] == '0'); }();
+  return on;
+}
+static bool halo_w4_switch() {
+  static const bool on = [] { const char* e = getenv("MIXDQ_HALO_W4"); return !(e && e[0] == '0'); }();
+  return on;
+}
+
 extern "C" size_t mixdq_qconv2d_workspace_bytes(int K, int R, int S, int pad) {
   if (pad <= 0 || K <= 0 || R <= 0 || S <= 0) return 0;
   return (size_t)R * R * S * S * K * sizeof(float);
@@ -709,16 +720,20 @@ extern "C" int mixdq_qconv2d_w8a8_table(const int8_t* X, const int8_t* Wt, const
   if (P <= 0 || Q <= 0 || N == 0) return MIXDQ_OK;
   // 3x3 / stride 1 / pad 1 with the input halo resident in LDS (csrc/iconv.hip): the automatic choice
   // wherever it applies; tile ids 90 .. 93 force it, any other forced id keeps the implicit-GEMM family
-  // (MIXDQ_HALO_CONV=0: off, for A/B runs)
+  // (MIXDQ_HALO_CONV=0: off, for A/B runs).  Packed-W4 weights take the kernel's W4 instantiations
+  // (MIXDQ_HALO_W4=0: packed convs stay on the implicit-GEMM family, for A/B runs)
   {
-    static const bool halo_on = [] { const char* e = getenv("MIXDQ_HALO_CONV"); return !(e && e[0] == '0'); }();
+    const bool halo_on = halo_conv_switch(), halo_w4_on = halo_w4_switch();
+    const bool w4 = flags & MIXDQ_FLAG_W4;
     const int forced = (flags >> 8) & 0xff;
     const bool aligned = !(((uintptr_t)X | (uintptr_t)Wt | (uintptr_t)scale | (uintptr_t)table_or_null |
                             (uintptr_t)D | (uintptr_t)residual_f16_or_null) & 15) &&
                          !((uintptr_t)bias_f16_or_null & 7);
     int tile = 0;
-    if (!(flags & MIXDQ_FLAG_W4) && aligned && ((forced >= 90 && forced <= 93) || (forced == 0 && halo_on)))
+    if (aligned && forced >= 90 && forced <= 93)          // a forced id is checked against the RANGE (that of int8)
       tile = halo_conv_select(N, H, W, C, K, R, S, stride, pad);
+    else if (aligned && forced == 0 && halo_on && (!w4 || halo_w4_on))
+      tile = halo_conv_select(N, H, W, C, K, R, S, stride, pad, w4);
     if (forced >= 90 && forced <= 93) {
       if (tile == 0 || (forced != 91 && W % 16 != 0) || (forced >= 92 && H % 16 != 0)) return MIXDQ_ERR_SHAPE;
       tile = forced;
@@ -734,7 +749,7 @@ extern "C" int mixdq_qconv2d_w8a8_table(const int8_t* X, const int8_t* Wt, const
       if (a.res && a.res_div != 1 && a.res_div != (int64_t)H * W) return MIXDQ_ERR_INVALID_ARG;
       a.NI = N; a.H = H; a.W = W; a.C = C; a.K = K;
       a.unfused = (flags & MIXDQ_FLAG_UNFUSED) ? 1 : 0;
-      return halo_conv_launch(a, tile, (hipStream_t)stream);
+      return halo_conv_launch(a, tile, (hipStream_t)stream, w4);
     }
   }
   IgemmParams p{};
@@ -902,6 +917,14 @@ extern "C" int mixdq_conv_halo_select(int N, int H, int W, int C, int K, int R, 
   const char* e = getenv("MIXDQ_HALO_CONV");
   if (e && e[0] == '0') return 0;
   return halo_conv_select(N, H, W, C, K, R, S, stride, pad);
+}
+
+extern "C" int mixdq_conv_halo_select_flags(int N, int H, int W, int C, int K, int R, int S, int stride,
+                                            int pad, int flags) {
+  if (flags & MIXDQ_FLAG_W2) return 0;
+  const bool w4 = flags & MIXDQ_FLAG_W4;
+  if (!halo_conv_switch() || (w4 && !halo_w4_switch())) return 0;       // what an unforced launch does
+  return halo_conv_select(N, H, W, C, K, R, S, stride, pad, w4);
 }
 
 extern "C" int mixdq_igemm_select_id_w4(int64_t M, int N, int k_align, int k_total) {

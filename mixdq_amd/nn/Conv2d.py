@@ -215,10 +215,10 @@ class QuantizedConv2d(nn.Module):
         return self._conv(x_int, "", self.bias, residual, residual_per_image, upsample2x)
 
     def upsample2x_supported(self, x_shape) -> bool:
-        return bool(self.valid_for_acceleration and self.split == 0 and not self.w_packed4
+        return bool(self.valid_for_acceleration and self.split == 0
                     and _C.conv_upsample2x_supported(x_shape, (self.out_channels, self.in_channels)
                                                      + tuple(self.kernel_size), self.stride[0],
-                                                     self.padding[0]))
+                                                     self.padding[0], w4=self.w_packed4))
 
     def _conv(self, x_int, sfx, bias, residual=None, residual_per_image=False, upsample2x=False):
         return _C.qconv2d_w8_a8_ohalf(
