@@ -465,6 +465,33 @@ int mixdq_conv2d_f16(const void* X_f16, const void* Wt_f16, const void* bias_f16
                      int pad, const void* residual_f16_or_null, int64_t residual_row_div,
                      int flags, mixdq_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Sampler step: classifier-free guidance + scheduler update + the UNet's next input, and the step state kept on
+ * the device, so that a sampling loop is N replays of one captured graph with nothing from the host in between.
+ * No reference counterpart: the reference reaches the loop only through diffusers' pipeline call in its run()
+ * harness (quantize_sdxl.py:331-484); schedulers and guidance are diffusers' eager PyTorch ops there.
+ * Euler, Euler-ancestral, DDIM and LCM updates of an epsilon-predicting model are one affine map; with
+ * (a, b, c, s_next) = coef[*step] (coef: FP32 [n_steps][4], 16-byte aligned), per element i < n:
+ *   e      = f32(eps[i])                                                   rows_per_image == 1
+ *   e      = f32(eps[i]) + g * (f32(eps[row_stride + i]) - f32(eps[i]))    rows_per_image == 2
+ *   x[i]   = (a * x[i] + b * e) + c * noise[*step * noise_stride + i]      (noise == null: a * x[i] + b * e)
+ *   in[i]  = in[row_stride + i] (rows_per_image == 2) = f16_rn(x[i] * s_next)
+ * every operation FP32 round-to-nearest, never contracted (include/mixdq_math.h: mixdq_sampler_*).  x: the FP32
+ * latent state, updated in place; eps: the UNet's FP16 output -- unconditional rows first, the conditional rows
+ * row_stride elements behind them; in: the UNet's FP16 input buffer, same layout.  The kernel is elementwise over
+ * storage: x, noise, eps and in share ONE dense stride pattern (the Python layer: channels-last).  n need not be
+ * a multiple of 8.  Then, in a one-thread launch behind the step on the same stream (in-order execution is what
+ * keeps every workgroup of the step from seeing the moved index):
+ *   *timestep = t_table[*step + 1];  *step += 1             (t_table: FP32 [n_steps + 1])
+ * A call with *step outside [0, n_steps) reads and writes nothing.
+ * Errors: null pointers, n < 0, n_steps < 1, rows_per_image not 1 or 2, row_stride < n (rows_per_image == 2),
+ * noise_stride < n (with noise): MIXDQ_ERR_INVALID_ARG; x / eps / in / noise / coef not 16-byte aligned,
+ * row_stride % 8 != 0 (rows_per_image == 2), noise_stride % 4 != 0 (with noise): MIXDQ_ERR_ALIGNMENT. */
+int mixdq_sampler_step(float* x, const void* eps_f16, void* in_f16, const float* noise_or_null,
+                       int64_t noise_stride, const float* coef, const float* t_table, int n_steps,
+                       int* step, float* timestep, float guidance, int64_t n, int rows_per_image,
+                       int64_t row_stride, mixdq_stream_t stream);
+
 /* Which kernel instantiation mixdq_qlinear_w8a8 / mixdq_qconv2d_w8a8 will launch for a problem of
  * M rows x N output channels (k_align = K for Linear, C for Conv2d; k_total = K or R*S*C): the block tile BM x BN x BK
  * and LDS stage count of `igemm_kernel<BM,BN,BK,STAGES,CONV>`, or zeros for the small-alignment

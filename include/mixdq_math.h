@@ -98,4 +98,35 @@ MIXDQ_HD float mixdq_geluf(float x) {
   return 0.5f * x * (1.0f + mixdq_erff(x * 0.70710678118654752440f));
 }
 
+/* ---- sampler step (mixdq_sampler_step, csrc/sampler.hip): classifier-free guidance + the affine scheduler
+ * update.  Every operation is one IEEE binary32 round-to-nearest +, - or *, never contracted: on the device the
+ * _rn intrinsics (which the compiler may not fuse), on a host compiler plain operators under -ffp-contract=off.
+ *   e  = eps_u + g * (eps_c - eps_u)            three roundings: difference, product, sum
+ *   x' = (a*x + b*e) + c*n                      each product rounded, then the two sums; without noise a*x + b*e
+ *   in = f16_rn(x' * s_next)                    the product rounded to FP32 first, then to FP16 by the caller */
+#if defined(__HIP_DEVICE_COMPILE__)
+#define MIXDQ_MUL_RN(a, b) __fmul_rn((a), (b))
+#define MIXDQ_ADD_RN(a, b) __fadd_rn((a), (b))
+#define MIXDQ_SUB_RN(a, b) __fsub_rn((a), (b))
+#else
+#define MIXDQ_MUL_RN(a, b) ((a) * (b))
+#define MIXDQ_ADD_RN(a, b) ((a) + (b))
+#define MIXDQ_SUB_RN(a, b) ((a) - (b))
+#endif
+
+MIXDQ_HD float mixdq_sampler_guided_eps(float eps_u, float eps_c, float g) {
+  return MIXDQ_ADD_RN(eps_u, MIXDQ_MUL_RN(g, MIXDQ_SUB_RN(eps_c, eps_u)));
+}
+
+MIXDQ_HD float mixdq_sampler_update(float x, float e, float a, float b) {
+  return MIXDQ_ADD_RN(MIXDQ_MUL_RN(a, x), MIXDQ_MUL_RN(b, e));
+}
+
+MIXDQ_HD float mixdq_sampler_update_noise(float x, float e, float n, float a, float b, float c) {
+  return MIXDQ_ADD_RN(mixdq_sampler_update(x, e, a, b), MIXDQ_MUL_RN(c, n));
+}
+
+/* The FP32 value whose FP16 rounding is the UNet's next input. */
+MIXDQ_HD float mixdq_sampler_scaled_input(float x_next, float s_next) { return MIXDQ_MUL_RN(x_next, s_next); }
+
 #endif /* MIXDQ_MATH_H_ */

@@ -1312,3 +1312,46 @@ def attention_f16(q, k, v, heads, scale_inv=None, zero_point=None, softmax_scale
                 FLAGS | (int(_cfg) << 8) | _aflag(_abits), _stream())
     _status(code, "attention_f16")
     return out
+
+
+_lib.mixdq_sampler_step.argtypes = [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, ctypes.c_float, _i64, _i32,
+                                    _i64, _vp]
+_lib.mixdq_sampler_step.restype = _i32
+
+
+def sampler_step(x, eps, inp, coef, t_table, step, timestep, guidance=0.0, rows_per_image=1, noise=None, *,
+                 n=None, row_stride=None, noise_stride=None):
+    """One sampler step in place (mixdq_sampler_step): guidance over the two row blocks of `eps`, the affine
+    scheduler update of the FP32 state `x` with `coef[step]` = (a, b, c, s_next), the UNet's next FP16 input into
+    every row block of `inp`; then `timestep` <- `t_table[step + 1]` and `step` += 1, on the device.
+
+    x: fp32 state; eps / inp: fp16, `rows_per_image` blocks of `n` elements `row_stride` apart (unconditional block
+    first); noise: None, or fp32 [n_steps] blocks `noise_stride` apart; coef: fp32 [n_steps, 4]; t_table: fp32
+    [n_steps + 1]; step: int32 [1]; timestep: the fp32 0-dim tensor the UNet reads.  The kernel is elementwise over
+    STORAGE: x, eps, inp and noise must be dense and share one stride pattern (the caller's business: Sampler checks
+    it).  `n` defaults to x.numel(), the strides to n."""
+    for t_, name, dt in ((x, "x", torch.float32), (eps, "eps", torch.float16), (inp, "inp", torch.float16),
+                         (coef, "coef", torch.float32), (t_table, "t_table", torch.float32),
+                         (step, "step", torch.int32), (timestep, "timestep", torch.float32)) + (
+                             ((noise, "noise", torch.float32),) if noise is not None else ()):
+        _check(t_.is_cuda and t_.device == x.device and t_.dtype == dt, f"{name} should be a {dt} tensor on x's GPU")
+    _check(coef.dim() == 2 and coef.shape[1] == 4 and coef.is_contiguous() and t_table.is_contiguous(),
+           "coef should be a contiguous [n_steps, 4] table")
+    n_steps = coef.shape[0]
+    _check(t_table.numel() >= n_steps + 1, "t_table needs n_steps + 1 entries")
+    _check(step.numel() == 1 and timestep.numel() == 1, "step and timestep hold one value each")
+    n = x.numel() if n is None else int(n)
+    row_stride = n if row_stride is None else int(row_stride)
+    noise_stride = n if noise_stride is None else int(noise_stride)
+    _check(0 <= n <= x.numel(), "n exceeds the state")
+    if rows_per_image in (1, 2):                      # (anything else: the library's own error)
+        need = (rows_per_image - 1) * row_stride + n
+        _check(eps.numel() >= need and inp.numel() >= need, "eps / inp are smaller than rows_per_image row blocks")
+    if noise is not None:
+        _check(noise.numel() >= (n_steps - 1) * noise_stride + n, "noise is smaller than n_steps blocks")
+    with torch.cuda.device(x.device):
+        code = _lib.mixdq_sampler_step(x.data_ptr(), eps.data_ptr(), inp.data_ptr(), _ptr(noise), noise_stride,
+                                       coef.data_ptr(), t_table.data_ptr(), n_steps, step.data_ptr(),
+                                       timestep.data_ptr(), float(guidance), n, int(rows_per_image), row_stride,
+                                       _stream())
+    _status(code, "sampler_step")

@@ -1,0 +1,139 @@
+// Sampler step for gfx950: classifier-free guidance + the scheduler update + the UNet's next input, one launch,
+// and the device-side step state (step index, the timestep the UNet reads) in a one-thread launch behind it.
+// No reference counterpart: the reference reaches the sampling loop only through diffusers' pipeline call.
+//
+// Euler, Euler-ancestral, DDIM and LCM with an epsilon-predicting model are one affine map with per-step scalars:
+//   e  = eps_u + g * (eps_c - eps_u)      (rows_per_image == 2; == 1: e = eps_u)
+//   x' = (a*x + b*e) + c*n                (no noise pointer: a*x + b*e)
+//   in = f16_rn(x' * s_next)              written to every UNet row of the image
+// with (a, b, c, s_next) = coef[*step] -- arithmetic: include/mixdq_math.h, FP32 round-to-nearest, no contraction.
+//
+// HBM-bound and small (SDXL at 1024 px: 65 536 elements per image): elementwise over storage, 8 elements per lane
+// per pass -- 16-byte accesses on the FP16 tensors, two on the FP32 ones -- and a scalar tail for n % 8 elements.
+//
+// The step index is read by every workgroup of the step launch and advanced by the launch BEHIND it on the same
+// stream (sampler_advance_kernel, one thread): launches of one stream run in order, so no workgroup of the step
+// can read the index after it moved, without any in-launch ticket, fence or counter to re-initialise.
+#include "common.h"
+#include "../../include/mixdq_math.h"
+
+namespace mixdq {
+namespace {
+
+struct alignas(16) Half8 { uint32_t w[4]; };
+
+__device__ __forceinline__ float half_at(const Half8& h, int j) {
+  const uint32_t w = h.w[j >> 1];
+  __half_raw hr;
+  hr.x = (unsigned short)((j & 1) ? (w >> 16) : (w & 0xffffu));
+  return __half2float(__half(hr));
+}
+
+__device__ __forceinline__ uint32_t half_bits(float v) {
+  return (uint32_t)__half_raw(f32_to_f16_rn(v)).x;
+}
+
+template <int ROWS, bool NOISE>
+__device__ __forceinline__ float step_one(float x, float eu, float ec, float n, float g, float a, float b, float c) {
+  const float e = ROWS == 2 ? mixdq_sampler_guided_eps(eu, ec, g) : eu;
+  return NOISE ? mixdq_sampler_update_noise(x, e, n, a, b, c) : mixdq_sampler_update(x, e, a, b);
+}
+
+template <int ROWS, bool NOISE>
+__global__ __launch_bounds__(256) void sampler_step_kernel(float* __restrict__ x, const __half* __restrict__ eps,
+                                                           __half* __restrict__ in, const float* __restrict__ noise,
+                                                           int64_t noise_stride, const float* __restrict__ coef,
+                                                           const int* __restrict__ step_p, int n_steps, float g,
+                                                           int64_t n, int64_t row_stride) {
+  const int step = *step_p;
+  if (step < 0 || step >= n_steps) return;        // replayed past the table: nothing is read or written
+  const float4 k = *reinterpret_cast<const float4*>(coef + 4 * (int64_t)step);
+  const float a = k.x, b = k.y, c = k.z, s_next = k.w;
+  const float* nz = NOISE ? noise + (int64_t)step * noise_stride : nullptr;
+  const int64_t nvec = n >> 3;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += stride) {
+    const int64_t o = i << 3;
+    const float4 x0 = *reinterpret_cast<const float4*>(x + o), x1 = *reinterpret_cast<const float4*>(x + o + 4);
+    const Half8 eu = *reinterpret_cast<const Half8*>(eps + o);
+    Half8 ec = eu;
+    if (ROWS == 2) ec = *reinterpret_cast<const Half8*>(eps + row_stride + o);
+    float4 n0 = x0, n1 = x1;
+    if (NOISE) {
+      n0 = *reinterpret_cast<const float4*>(nz + o);
+      n1 = *reinterpret_cast<const float4*>(nz + o + 4);
+    }
+    const float xs[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
+    const float ns[8] = {n0.x, n0.y, n0.z, n0.w, n1.x, n1.y, n1.z, n1.w};
+    float y[8];
+    Half8 out;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) y[j] = step_one<ROWS, NOISE>(xs[j], half_at(eu, j), half_at(ec, j), ns[j], g, a, b, c);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      out.w[j] = half_bits(mixdq_sampler_scaled_input(y[2 * j], s_next)) |
+                 (half_bits(mixdq_sampler_scaled_input(y[2 * j + 1], s_next)) << 16);
+    *reinterpret_cast<float4*>(x + o) = make_float4(y[0], y[1], y[2], y[3]);
+    *reinterpret_cast<float4*>(x + o + 4) = make_float4(y[4], y[5], y[6], y[7]);
+    *reinterpret_cast<Half8*>(in + o) = out;
+    if (ROWS == 2) *reinterpret_cast<Half8*>(in + row_stride + o) = out;
+  }
+  // tail (n % 8 elements), by the first threads of block 0
+  const int64_t t = (nvec << 3) + threadIdx.x;
+  if (blockIdx.x == 0 && t < n) {
+    const float eu = __half2float(eps[t]);
+    const float ec = ROWS == 2 ? __half2float(eps[row_stride + t]) : eu;
+    const float y = step_one<ROWS, NOISE>(x[t], eu, ec, NOISE ? nz[t] : 0.0f, g, a, b, c);
+    const __half h = f32_to_f16_rn(mixdq_sampler_scaled_input(y, s_next));
+    x[t] = y;
+    in[t] = h;
+    if (ROWS == 2) in[row_stride + t] = h;
+  }
+}
+
+// Behind the step on the same stream: the timestep of the NEXT UNet forward, and the index moves on.
+__global__ void sampler_advance_kernel(const float* __restrict__ t_table, int n_steps, int* step_p, float* timestep) {
+  const int step = *step_p;
+  if (step < 0 || step >= n_steps) return;
+  *timestep = t_table[step + 1];
+  *step_p = step + 1;
+}
+
+}  // namespace
+}  // namespace mixdq
+
+using namespace mixdq;
+
+extern "C" int mixdq_sampler_step(float* x, const void* eps_f16, void* in_f16, const float* noise_or_null,
+                                  int64_t noise_stride, const float* coef, const float* t_table, int n_steps,
+                                  int* step, float* timestep, float guidance, int64_t n, int rows_per_image,
+                                  int64_t row_stride, mixdq_stream_t stream_) {
+  if (!x || !eps_f16 || !in_f16 || !coef || !t_table || !step || !timestep) return MIXDQ_ERR_INVALID_ARG;
+  if (n < 0 || n_steps < 1 || (rows_per_image != 1 && rows_per_image != 2)) return MIXDQ_ERR_INVALID_ARG;
+  if (rows_per_image == 2 && row_stride < n) return MIXDQ_ERR_INVALID_ARG;      // the two row blocks would overlap
+  if (noise_or_null && noise_stride < n) return MIXDQ_ERR_INVALID_ARG;
+  if ((uintptr_t)x % 16 || (uintptr_t)eps_f16 % 16 || (uintptr_t)in_f16 % 16 || (uintptr_t)coef % 16 ||
+      (uintptr_t)noise_or_null % 16 || (uintptr_t)t_table % 4 || (uintptr_t)step % 4 || (uintptr_t)timestep % 4)
+    return MIXDQ_ERR_ALIGNMENT;
+  if ((rows_per_image == 2 && row_stride % 8) || (noise_or_null && noise_stride % 4)) return MIXDQ_ERR_ALIGNMENT;
+  hipStream_t stream = (hipStream_t)stream_;
+  if (n > 0) {
+    int64_t blocks = ((n >> 3) + 255) / 256;
+    if (blocks > (int64_t)kNumCU * 8) blocks = (int64_t)kNumCU * 8;
+    if (blocks < 1) blocks = 1;
+    const __half* eps = (const __half*)eps_f16;
+    __half* in = (__half*)in_f16;
+#define S_LAUNCH(R, NZ)                                                                                    \
+  sampler_step_kernel<R, NZ><<<(int)blocks, 256, 0, stream>>>(x, eps, in, noise_or_null, noise_stride, coef, step, \
+                                                              n_steps, guidance, n, row_stride)
+    if (rows_per_image == 2) {
+      if (noise_or_null) S_LAUNCH(2, true); else S_LAUNCH(2, false);
+    } else {
+      if (noise_or_null) S_LAUNCH(1, true); else S_LAUNCH(1, false);
+    }
+#undef S_LAUNCH
+    if (hipGetLastError() != hipSuccess) return MIXDQ_ERR_LAUNCH;
+  }
+  sampler_advance_kernel<<<1, 1, 0, stream>>>(t_table, n_steps, step, timestep);
+  return launch_status();
+}

@@ -1,0 +1,213 @@
+"""The sampling loop around the UNet, on the device: embeddings and noise in, latents out.
+
+    Sampler(unet, kind, n_steps, guidance_scale=0.0, spacing=None).sample(noise, encoder_hidden_states, ...)
+
+Euler, Euler-ancestral and LCM updates of an epsilon-predicting model are one affine map per step,
+
+    x' = a * x + b * e + c * n,        UNet input of the next step = f16(x' * s_next),
+
+so a schedule is a table `coef[n_steps][4] = (a, b, c, s_next)` plus the timesteps; `schedule()` computes both in
+float64 with numpy (no diffusers import) and stores them as FP32.  One kernel (mixdq_sampler_step, csrc/sampler.hip)
+applies guidance and that map, writes the next UNet input and advances a step index and the UNet's timestep ON THE
+DEVICE; `Sampler` captures the UNet forward + that step once into a hipGraph and replays it n_steps times with
+nothing from the host in between.  The FP32 arithmetic, rounding by rounding, is include/mixdq_math.h; its numpy
+restatement is tests/sampler_ref.py.
+"""
+import numpy as np
+
+KINDS = ("euler_ancestral", "euler", "lcm")
+TRAIN_STEPS = 1000
+LCM_ORIGINAL_STEPS = 50
+_DEFAULT_SPACING = {"euler_ancestral": "trailing", "euler": "leading", "lcm": "lcm"}
+
+
+def alphas_cumprod() -> np.ndarray:
+    """Stable Diffusion's scaled-linear betas: cumprod(1 - linspace(sqrt(0.00085), sqrt(0.012), 1000) ** 2)."""
+    betas = np.linspace(0.00085 ** 0.5, 0.012 ** 0.5, TRAIN_STEPS, dtype=np.float64) ** 2
+    return np.cumprod(1.0 - betas)
+
+
+def timesteps(kind: str, n_steps: int, spacing=None) -> np.ndarray:
+    """The integer training timesteps a run of `n_steps` visits, first (noisiest) first."""
+    if kind not in KINDS:
+        raise ValueError(f"kind must be one of {KINDS}, not {kind!r}")
+    if not 1 <= n_steps <= TRAIN_STEPS:
+        raise ValueError("n_steps must be in [1, 1000]")
+    spacing = spacing or _DEFAULT_SPACING[kind]
+    if kind == "lcm":
+        if spacing != "lcm":
+            raise ValueError("lcm has its own spacing")
+        if n_steps > LCM_ORIGINAL_STEPS:
+            raise ValueError("lcm: at most 50 steps")
+        origin = (np.arange(1, LCM_ORIGINAL_STEPS + 1) * (TRAIN_STEPS // LCM_ORIGINAL_STEPS) - 1)[::-1]
+        idx = np.floor(np.linspace(0, LCM_ORIGINAL_STEPS, n_steps, endpoint=False)).astype(np.int64)
+        return origin[idx].astype(np.int64)
+    if spacing == "trailing":
+        return (np.round(TRAIN_STEPS - np.arange(n_steps) * (TRAIN_STEPS / n_steps)) - 1).astype(np.int64)
+    if spacing == "leading":
+        return ((np.arange(n_steps) * (TRAIN_STEPS // n_steps))[::-1] + 1).astype(np.int64)
+    raise ValueError(f"spacing must be 'trailing' or 'leading', not {spacing!r}")
+
+
+class Schedule:
+    """What one (kind, n_steps, spacing) needs: `timesteps` int64 [n]; `sigmas` float64 [n + 1] (euler kinds; ends in
+    0); `coef` FP32 [n, 4] = (a, b, c, s_next), computed in float64; `t_table` FP32 [n + 1] (the
+    timesteps, then one unused entry the last step's advance reads); `init_scale`: initial state = noise *
+    init_scale; `input_scale0`: first UNet input = f16(state * input_scale0)."""
+
+    def __init__(self, kind, n_steps, spacing=None):
+        self.kind, self.n_steps = kind, int(n_steps)
+        self.timesteps = ts = timesteps(kind, n_steps, spacing)
+        ac = alphas_cumprod()
+        coef = np.zeros((n_steps, 4), dtype=np.float64)
+        if kind == "lcm":
+            self.sigmas = None
+            for i, t in enumerate(ts):
+                last = i == n_steps - 1
+                c_skip = 0.25 / ((10.0 * t) ** 2 + 0.25)
+                c_out = 10.0 * t / np.sqrt((10.0 * t) ** 2 + 0.25)
+                sa, s1a = np.sqrt(ac[t]), np.sqrt(1.0 - ac[t])
+                sp = 1.0 if last else np.sqrt(ac[ts[i + 1]])
+                # x0 = (x - s1a e) / sa;  den = c_out x0 + c_skip x;  x' = sp den + sqrt(1 - ac_prev) n
+                coef[i] = (sp * (c_out / sa + c_skip), -sp * c_out * s1a / sa,
+                           0.0 if last else np.sqrt(1.0 - ac[ts[i + 1]]), 1.0)
+            self.init_scale, self.input_scale0 = 1.0, 1.0
+        else:
+            sig = np.concatenate([np.sqrt((1.0 - ac[ts]) / ac[ts]), [0.0]])
+            self.sigmas = sig
+            for i in range(n_steps):
+                s0, s1 = sig[i], sig[i + 1]
+                if kind == "euler_ancestral":
+                    up = np.sqrt(s1 ** 2 * (s0 ** 2 - s1 ** 2) / s0 ** 2)
+                    down = np.sqrt(s1 ** 2 - up ** 2)
+                    coef[i] = (1.0, down - s0, up, 1.0 / np.sqrt(s1 ** 2 + 1.0))
+                else:
+                    coef[i] = (1.0, s1 - s0, 0.0, 1.0 / np.sqrt(s1 ** 2 + 1.0))
+            self.init_scale = float(np.sqrt(sig[0] ** 2 + 1.0)) if kind == "euler_ancestral" else float(sig[0])
+            self.input_scale0 = float(1.0 / np.sqrt(sig[0] ** 2 + 1.0))
+        self.coef = coef.astype(np.float32)
+        self.t_table = np.concatenate([ts.astype(np.float64), [0.0]]).astype(np.float32)
+        self.uses_noise = bool((self.coef[:, 2] != 0).any())
+
+
+def schedule(kind, n_steps, spacing=None) -> Schedule:
+    return Schedule(kind, n_steps, spacing)
+
+
+class Sampler:
+    """`n_steps` of `kind` ('euler_ancestral': SDXL-Turbo, trailing spacing; 'euler': SDXL base, leading spacing with
+    offset 1, `spacing='trailing'` selectable; 'lcm': SD 1.5 LCM-LoRA) around `unet`, a mixdq_amd UNet on the GPU.
+
+    guidance_scale > 1: classifier-free guidance -- the UNet runs at 2B rows, `encoder_hidden_states` (and the
+    tensors of `added_cond_kwargs`) carry the B unconditional rows first, then the B conditional ones, as diffusers'
+    pipelines concatenate them; otherwise the UNet runs at B rows.
+
+    The first sample() captures ONE step -- the UNet forward, then mixdq_sampler_step -- into a hipGraph on static
+    buffers; every sample() copies its inputs in, resets the device step state and replays that graph n_steps
+    times: no host synchronisation, host write or eager kernel between the replays.  Inputs of another shape need
+    another Sampler."""
+
+    def __init__(self, unet, kind, n_steps, guidance_scale=0.0, spacing=None):
+        self.unet = unet
+        self.schedule = Schedule(kind, n_steps, spacing)
+        self.kind, self.n_steps = kind, int(n_steps)
+        self.guidance_scale = float(guidance_scale)
+        self.rows_per_image = 2 if self.guidance_scale > 1.0 else 1
+        self._graph = None
+
+    # ---- static buffers + capture ---------------------------------------------------------------------------
+    def _capture(self, noise, encoder_hidden_states, added_cond_kwargs):
+        import torch
+        from mixdq_amd import _C
+        from mixdq_amd.quantize_sdxl import _clone_args
+        sch, dev = self.schedule, noise.device
+        B, C, H, W = noise.shape
+        R = B * self.rows_per_image
+
+        def nhwc(*lead, dtype):       # [*lead, C, H, W] logical, channels-last in memory
+            nd = len(lead)
+            return torch.zeros(*lead, H, W, C, dtype=dtype, device=dev).permute(*range(nd), nd + 2, nd, nd + 1)
+        self._x = nhwc(B, dtype=torch.float32)
+        self._in = nhwc(R, dtype=torch.float16)
+        self._noise = nhwc(self.n_steps, B, dtype=torch.float32) if sch.uses_noise else None
+        self._coef = torch.from_numpy(sch.coef).to(dev)
+        self._t_table = torch.from_numpy(sch.t_table).to(dev)
+        self._t = torch.zeros((), dtype=torch.float32, device=dev)
+        self._step = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._init_scale = torch.tensor(sch.init_scale, dtype=torch.float32, device=dev)
+        self._input_scale0 = torch.tensor(sch.input_scale0, dtype=torch.float32, device=dev)
+        self._ehs, self._added = _clone_args((encoder_hidden_states, added_cond_kwargs))
+        self._key = self._shape_key(noise, encoder_hidden_states, added_cond_kwargs)
+        forward = getattr(self.unet.forward, "__wrapped__", self.unet.forward)   # (under hip_graph_opt: the eager one)
+        n = B * C * H * W
+
+        def one_step():
+            eps = forward(self._in, self._t, self._ehs, self._added)[0]
+            if (eps.dtype != torch.float16 or tuple(eps.shape) != tuple(self._in.shape)
+                    or any(a != b for a, b, d in zip(eps.stride(), self._in.stride(), eps.shape) if d > 1)):
+                raise RuntimeError("Sampler: the UNet's output is not an FP16 tensor of its input's shape in channels-"
+                                   f"last storage (shape {tuple(eps.shape)}, strides {eps.stride()}, {eps.dtype})")
+            _C.sampler_step(self._x, eps, self._in, self._coef, self._t_table, self._step, self._t,
+                            self.guidance_scale, self.rows_per_image, self._noise, n=n)
+
+        self._reset(noise, None)
+        side = torch.cuda.Stream(dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.no_grad(), torch.cuda.stream(side):
+            for _ in range(2):
+                self._step.zero_()
+                one_step()
+        torch.cuda.current_stream(dev).wait_stream(side)
+        self._step.zero_()
+        graph = torch.cuda.CUDAGraph()
+        with torch.no_grad(), torch.cuda.graph(graph):
+            one_step()
+        self._graph = graph
+
+    @staticmethod
+    def _shape_key(noise, ehs, added):
+        return (tuple(noise.shape), noise.device, tuple(ehs.shape), ehs.dtype,
+                None if added is None else tuple(sorted((k, tuple(v.shape), v.dtype) for k, v in added.items())))
+
+    def _reset(self, noise, step_noise):
+        """State of step 0: x = f32(noise) * init_scale, UNet input = f16(x * input_scale0) in every row block, the
+        step index 0, the timestep t_table[0].  Device ops in stream order: nothing here waits for the GPU."""
+        import torch
+        B = noise.shape[0]
+        torch.mul(noise.to(torch.float32), self._init_scale, out=self._x)
+        first = (self._x * self._input_scale0).to(torch.float16)
+        for r in range(self.rows_per_image):
+            self._in[r * B:(r + 1) * B].copy_(first)
+        if self._noise is not None and step_noise is not None:
+            self._noise.copy_(step_noise)
+        self._step.zero_()
+        self._t.copy_(self._t_table[0])
+
+    # ---- the loop -------------------------------------------------------------------------------------------
+    def sample(self, noise, encoder_hidden_states, added_cond_kwargs=None, step_noise=None):
+        """noise [B, C, H, W] (unit variance; FP32 or FP16), encoder_hidden_states [R, T, D] FP16 (R = B, or 2B
+        under guidance), added_cond_kwargs as the UNet takes them (R rows), step_noise [n_steps, B, C, H, W]: the
+        noise each stochastic step adds (required where the schedule has a non-zero c: euler_ancestral and lcm with
+        more than one step; there is no random number generator in the kernel).  Returns the FP32 latents."""
+        import torch
+        from mixdq_amd.quantize_sdxl import _copy_into
+        if not (torch.is_tensor(noise) and noise.is_cuda and noise.dim() == 4):
+            raise RuntimeError("Sampler.sample: noise should be a [B, C, H, W] GPU tensor")
+        R = noise.shape[0] * self.rows_per_image
+        if encoder_hidden_states.shape[0] != R:
+            raise RuntimeError(f"Sampler.sample: encoder_hidden_states should have {R} rows")
+        if self.schedule.uses_noise:
+            want = (self.n_steps,) + tuple(noise.shape)
+            if step_noise is None or tuple(step_noise.shape) != want:
+                raise RuntimeError(f"Sampler.sample: this schedule needs step_noise of shape {want}")
+        elif step_noise is not None:
+            raise RuntimeError("Sampler.sample: this schedule adds no noise: step_noise must be None")
+        if self._graph is None:
+            self._capture(noise, encoder_hidden_states, added_cond_kwargs)
+        elif self._shape_key(noise, encoder_hidden_states, added_cond_kwargs) != self._key:
+            raise RuntimeError("Sampler.sample: inputs differ in shape from those the step graph was captured for")
+        _copy_into((self._ehs, self._added), (encoder_hidden_states, added_cond_kwargs))
+        self._reset(noise, step_noise)
+        for _ in range(self.n_steps):
+            self._graph.replay()
+        return self._x.clone()
