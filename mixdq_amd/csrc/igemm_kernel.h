@@ -2041,7 +2041,9 @@ void igemm_kernel(MIXDQ_IGEMM_HEAD_PARAMS const IgemmParams p_in) {
         const float m2u = live[r] ? __uint_as_float((unsigned)rec[r][1]) : 0.f;
         const float mean = __fmul_rn(ln_row_tree(s1u, U), inv_c);
         const float e = __fsub_rn(__fmul_rn(s1u, inv_nu), mean);
-        const float t2 = ln_row_tree(__builtin_fmaf(__fmul_rn(e, n_u), e, m2u), U);
+        // (a lane without a unit adds exactly 0: the tree's first two levels run whatever U is, and with U < 4 --
+        //  N = 160, 80 -- such a lane's e is -mean, not 0)
+        const float t2 = ln_row_tree(live[r] ? __builtin_fmaf(__fmul_rn(e, n_u), e, m2u) : 0.f, U);
         const float rstd = 1.0f / sqrtf(__fadd_rn(__fmul_rn(t2, inv_c), p.ln_eps));
         if (u == 0) { ln_mr[2 * row] = mean; ln_mr[2 * row + 1] = rstd; }
       }

@@ -1,5 +1,6 @@
-"""Exact-result inputs for the FP16 attention core and the FP16 layer kernels (tests/test_attention_exact_gpu.py,
-tests/test_f16_exact_gpu.py run them on the GPU; tests/test_exact_inputs_host.py checks them on the CPU).
+"""Exact-result inputs for the FP16 attention core, the FP16 layer kernels and the norm producers
+(tests/test_attention_exact_gpu.py, tests/test_f16_exact_gpu.py, tests/test_norm_exact_gpu.py run them on the GPU;
+tests/test_exact_inputs_host.py checks them on the CPU).
 
 The technique: inputs for which the mathematically exact result is also the only result a correct kernel can
 produce, so that the comparison is equality of bits and needs no tolerance.  Every builder returns the inputs and the
@@ -25,6 +26,13 @@ FP16 layers
   linear() / conv2d() / gemm()   integer-valued activations in [-4, 4], weights in [-2, 2], bias a multiple of 1/8 in
                      [-4, 4]: |acc| < 2^20, so the FP32 accumulator and accumulator + bias are exact in any summation
                      order, and the result is fp16(acc + bias) [then fp16(f32(.) + f32(residual))] and nothing else.
+
+Norm producers (csrc/fused_norm.hip; the builders are at the end of this file)
+  gn_base() / gn_heavy()   integer data, one heavy element moved through the geometry's edges: the expected bits follow
+                     from the kernel's order-free finalize tail (gn_expected).
+  ln_heavy()         rows whose 16-column groups sum to zero (ln_expected_zero_mean), a heavy element moved through
+                     the group, unit and lane-wrap boundaries; constant rows (ln_expected_constant).
+  qedge_values()     values on the quantizers' ties and clamp ends.
 
 Plain numpy; imports without a GPU and without the built library.
 """
@@ -365,3 +373,223 @@ CONV = [  # N, C, H, W, K, ksize, stride, pad, bias: the shapes of tests/test_f1
     (3, 8, 7, 9, 12, 3, 1, 0, True),
 ]
 GEMM = [(77, 320, 640), (203, 1232, 136), (1, 5120, 8), (130, 16, 4)]   # M, K, N
+
+
+# ------------------------------------------------------------------------------------------ norm producers
+# GroupNorm: integer data (|x| <= 8, one heavy element of 64) -- every group's sum s and sum of squares q is an integer
+# below 2^24, hence an exact FP32 number in ANY summation order, and the output bits follow from the kernel's
+# order-free tail alone (csrc/fused_norm.hip gn_finalize_tail and the apply pass), restated here in numpy float32:
+#   mean = s / cnt;  var = max(fma(-mean, mean, q / cnt), 0);  rstd = 1 / sqrt(var + eps)
+#   a = rstd * gamma;  b = fma(-mean, a, beta);  y = f16(fma(x, a, b))
+# A dropped, doubled or mis-grouped element changes an integer, and with it the bits.
+HEAVY = 64.0
+GN_EPS = np.float32(1e-5)
+
+
+def fma32(a, b, c):
+    """Correctly rounded FP32 a * b + c (numpy has no fma): the product is exact in float64 (24 x 24 bits), the
+    float64 sum is rounded to odd with the exact error of the two-sum, and 53 >= 24 + 2 bits make the final rounding
+    to FP32 the single rounding of the exact value."""
+    a, b, c = (np.asarray(v, np.float32).astype(np.float64) for v in (a, b, c))
+    a, b, c = np.broadcast_arrays(a, b, c)
+    p = a * b
+    s = p + c
+    bb = s - p
+    err = (p - (s - bb)) + (c - bb)
+    bits = s.copy().view(np.int64)
+    fix = (err != 0) & ((bits & 1) == 0) & np.isfinite(s)
+    away = (err > 0) == (s > 0)                    # the exact value lies beyond s, away from zero
+    bits = np.where(fix, bits + np.where(away, 1, -1), bits)
+    return bits.view(np.float64).astype(np.float32)
+
+
+def gn_group_sums(x, G):
+    """Exact int64 (s, q) per (image, group) of integer-valued x [N, HW, C]."""
+    N, HW, C = x.shape
+    xi = x.astype(np.int64)
+    assert np.array_equal(xi.astype(np.float16), x), "not integer-valued"
+    v = xi.reshape(N, HW, G, C // G)
+    return v.sum(axis=(1, 3)), (v * v).sum(axis=(1, 3))
+
+
+def gn_expected(x, gamma, beta, G, eps=GN_EPS):
+    """The pre-activation FP16 bits of GroupNorm on integer-valued x [N, HW, C], from the closed formula."""
+    N, HW, C = x.shape
+    cg = C // G
+    s, q = gn_group_sums(x, G)
+    cnt = HW * cg
+    assert cnt < 2 ** 24 and np.abs(s).max() < 2 ** 24 and q.max() < 2 ** 24, "sums not exact in FP32"
+    cntf = np.float32(cnt)
+    mean = s.astype(np.float32) / cntf
+    var = np.maximum(fma32(-mean, mean, q.astype(np.float32) / cntf), np.float32(0))
+    rstd = np.float32(1) / np.sqrt(var + np.float32(eps), dtype=np.float32)
+    mean_c, rstd_c = np.repeat(mean, cg, axis=1), np.repeat(rstd, cg, axis=1)          # [N, C]
+    a = rstd_c * gamma.astype(np.float32)[None]
+    b = fma32(-mean_c, a, beta.astype(np.float32)[None])
+    y = fma32(x.astype(np.float32), a[:, None, :], b[:, None, :])
+    return y.astype(np.float16), dict(s=s, q=q, mean=mean, var=var, rstd=rstd)
+
+
+def _seeded_affine(seed, C):
+    gamma = (dd.normal_f16(seed, (C,), 0.3).astype(np.float32) + 1).astype(np.float16)
+    return gamma, dd.normal_f16(seed + 1, (C,), 0.2)
+
+
+@functools.lru_cache(maxsize=64)
+def gn_base(N, HW, C, G, seed=0):
+    """Integers in [-8, 8]; group 1 of the last image is constant (variance exactly 0) and, where there is more
+    than one image, image 0 is all zero."""
+    s0 = _seed(N, HW, C, G, seed, 91)
+    x = dd.int8(s0, (N, HW, C), -8, 9).astype(np.float16)
+    cg = C // G
+    if G > 1:
+        x[N - 1, :, cg:2 * cg] = 3.0
+    if N > 1:
+        x[0] = 0
+    gamma, beta = _seeded_affine(s0 + 1, C)
+    x.setflags(write=False)
+    return x, gamma, beta
+
+
+def gn_heavy_positions(geom, C1=None):
+    """{name: (pixel, channel)} of the single heavy element: first / last pixel of the image, of a chunk, the first
+    pixel of the last chunk, the last pixel lane of a block iteration; first / last channel of a group, both ends of
+    an octet that straddles two groups; with two sources the last channel of x and the first of x2.  `geom`: a
+    tests/norm_edges.py gn_launch() dict."""
+    HW, C, cg, PP, ppb, nchunk = (geom[k] for k in ("HW", "C", "cg", "PP", "ppb", "nchunk"))
+    G = C // cg
+    gm = min(G - 1, max(2, G // 2))                            # a middle group (not the constant one)
+    c0 = gm * cg
+    pos = {"first_pixel": (0, c0 + 1), "last_pixel": (HW - 1, c0 + 1)}
+    k = 1 if nchunk > 2 else 0                                 # a chunk that is neither first nor last where one exists
+    pos["chunk_first"] = (min(k * ppb, HW - 1), c0)
+    pos["chunk_last"] = (min((k + 1) * ppb, HW) - 1, c0)
+    pos["last_chunk_first"] = ((nchunk - 1) * ppb, c0 + cg - 1)
+    pos["last_pixel_lane"] = (min(k * ppb + PP, HW) - 1, c0 + cg - 1)
+    pos["group_first_channel"] = (HW // 2, c0)
+    pos["group_last_channel"] = (HW // 2, c0 + cg - 1)
+    for o in range(C // 8):
+        if (8 * o) // cg != (8 * o + 7) // cg and (8 * o) // cg >= 2:
+            pos["octet_leading_half"] = (HW // 2, 8 * o)
+            pos["octet_trailing_half"] = (HW // 2, 8 * o + 7)
+            pos["octet_boundary_below"] = (HW // 3, ((8 * o + 7) // cg) * cg - 1)
+            pos["octet_boundary_above"] = (HW // 3, ((8 * o + 7) // cg) * cg)
+            break
+    if C1 is not None and C1 != C:
+        pos["x_last_channel"] = (HW - 1, C1 - 1)
+        pos["x2_first_channel"] = (0, C1)
+    return pos
+
+
+def gn_heavy(N, HW, C, G, pixel, channel, seed=0):
+    """The base tensor with x[N - 1, pixel, channel] = 64, and the (image, group) whose sums that changes."""
+    x, gamma, beta = gn_base(N, HW, C, G, seed)
+    x = x.copy()
+    old = int(x[N - 1, pixel, channel])
+    x[N - 1, pixel, channel] = HEAVY
+    return x, gamma, beta, dict(image=N - 1, group=channel // (C // G), ds=int(HEAVY) - old,
+                                dq=int(HEAVY) ** 2 - old * old)
+
+
+# LayerNorm: rows of small integers in which every 16-column group sums to zero.  Every group mean, unit mean and the
+# row mean are exactly 0, every partial of the centred sums of squares is an exact integer, and the bits follow from
+#   var = f32(Q) * rn(1 / C);  rstd = 1 / sqrt(var + eps);  y = f16(fma(x * rstd, gamma, beta))
+def ln_zero_sum_rows(M, C, seed=0):
+    assert C % 16 == 0
+    half = dd.int8(_seed(M, C, seed, 92), (M, C // 16, 8), -8, 9).astype(np.int64)
+    g = np.concatenate([half, -half], axis=2)                                   # [M, C / 16, 16]: sums to zero
+    order = np.argsort(dd.u64(_seed(M, C, seed, 93), M * (C // 16) * 16).reshape(M, C // 16, 16), axis=2, kind="stable")
+    x = np.take_along_axis(g, order, axis=2).reshape(M, C)
+    assert (x.reshape(M, -1, 16).sum(axis=2) == 0).all()
+    return x.astype(np.float16)
+
+
+def ln_expected_zero_mean(x, gamma, beta, eps=GN_EPS):
+    """Bits of LayerNorm on rows whose 16-column groups all sum to zero (asserted)."""
+    M, C = x.shape
+    xi = x.astype(np.int64)
+    assert np.array_equal(xi.astype(np.float16), x) and (xi.reshape(M, -1, 16).sum(axis=2) == 0).all()
+    Q = (xi * xi).sum(axis=1)
+    assert Q.max() < 2 ** 24
+    inv_c = np.float32(1) / np.float32(C)
+    var = Q.astype(np.float32) * inv_c
+    rstd = np.float32(1) / np.sqrt(var + np.float32(eps), dtype=np.float32)
+    nrm = x.astype(np.float32) * rstd[:, None]
+    return fma32(nrm, gamma.astype(np.float32)[None], beta.astype(np.float32)[None]).astype(np.float16)
+
+
+def ln_expected_constant(c, C, gamma, beta, eps=GN_EPS):
+    """Bits of LayerNorm on a row of C copies of the small integer c: every sum is an exact integer and every unit
+    holds the same values, so the statistics are order-free; rn(1 / C) makes mean differ from c by a rounding unless C
+    is a power of two, and the formula carries that through."""
+    G = C // 16
+    U = 1
+    while U < 16 and G % (2 * U) == 0:
+        U *= 2
+    per = G // U
+    f = np.float32
+    inv_nu, inv_c = f(1) / f(16 * per), f(1) / f(C)
+    assert abs(C * c) < 2 ** 24
+    mean = f(C * c) * inv_c
+    mu = f(16 * per * c) * inv_nu
+    e = mu - mean
+    du = fma32(e * f(16 * per), e, f(0))                       # M2 of a constant unit is 0
+    var = f(U) * du * inv_c                                    # U equal values through the tree: an exact product
+    rstd = f(1) / np.sqrt(var + f(eps), dtype=np.float32)
+    nrm = (f(c) - mean) * rstd
+    return fma32(np.full(C, nrm, np.float32), gamma.astype(np.float32), beta.astype(np.float32)).astype(np.float16)
+
+
+def ln_heavy_columns(C):
+    """Columns the heavy element visits: first and last, both sides of every 16-column group boundary of one unit,
+    a unit boundary, and the lane-63 -> lane-0 chunk wrap (columns 504 .. 519) where the row is that long."""
+    G = C // 16
+    U = 1
+    while U < 16 and G % (2 * U) == 0:
+        U *= 2
+    per = G // U
+    u = U // 2                                                 # a middle unit
+    cols = {0, C - 1}
+    for k in range(per + 1):
+        b = 16 * (u * per + k)                                 # k = 0 and k = per: the unit's own boundaries
+        cols |= {b - 1, b}
+    if C >= 1024:
+        cols |= set(range(504, 520))
+    return sorted(c for c in cols if 0 <= c < C)
+
+
+@functools.lru_cache(maxsize=32)
+def ln_heavy(C, seed=0):
+    """Row 0: the zero-sum base row; row 1 + i: the base row with column ln_heavy_columns(C)[i] set to 64."""
+    cols = ln_heavy_columns(C)
+    base = ln_zero_sum_rows(1, C, seed)
+    x = np.repeat(base, 1 + len(cols), axis=0)
+    for i, c in enumerate(cols):
+        x[1 + i, c] = HEAVY
+    gamma, beta = _seeded_affine(_seed(C, seed, 94), C)
+    return x, gamma, beta, cols
+
+
+# Quantizer edges through the producers: FP16 values v = k / 8 in [-80, 80] -- with scale_inv 2 or 4 and zero points
+# on the quarter grid, v * scale_inv + zero_point lands exactly on integers, on k + 0.5 ties (both parities of k) and
+# beyond both clamp ends.
+QEDGE_LN = ((2.0, 0.0), (4.0, -3.0), (4.0, 100.5))            # one (scale_inv, zero_point) per LayerNorm slot
+QEDGE_GN, QEDGE_RAW = (2.0, 0.5), ((2.0, 0.0), (4.0, 27.5))
+
+
+def qedge_values(n, seed=0):
+    k = np.arange(-640, 641)
+    v = (k[dd.u64(_seed(n, seed, 95), n) % np.uint64(k.size)].astype(np.float64) / 8)
+    v[:k.size] = (k / 8)[:min(n, k.size)] if n >= k.size else v[:k.size]
+    return v.astype(np.float16)
+
+
+def qedge_facts(v, s_inv, zp):
+    """What a value set reaches under one quantizer: ties to both parities, both clamps, values beyond them."""
+    t = v.astype(np.float64) * s_inv + zp
+    tie = (t - np.floor(t)) == 0.5
+    inside = (t > -128) & (t < 127)
+    return dict(tie_even=bool((tie & inside & (np.floor(t) % 2 == 0)).any()),
+                tie_odd=bool((tie & inside & (np.floor(t) % 2 == 1)).any()),
+                at_low=bool((np.abs(t + 128) <= 0.5).any()), at_high=bool((np.abs(t - 127) <= 0.5).any()),
+                below=bool((t < -129).any()), above=bool((t > 128).any()))

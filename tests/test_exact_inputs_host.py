@@ -213,3 +213,105 @@ def test_gemm_expectations_equal_an_int64_evaluation(M, K, N):
     check_values(c, "a", "b")
     want = ei.f16_epilogue(c["a"].astype(np.int64) @ c["b"].astype(np.int64), None, None)
     assert np.array_equal(want.view(np.uint16), c["expected"].view(np.uint16))
+
+
+# ------------------------------------------------------------------------------------------ norm producers
+def test_fma32_is_the_correctly_rounded_fma():
+    from fractions import Fraction
+    a = dd_f32(1, 4000)
+    b = dd_f32(2, 4000)
+    c = (-(a.astype(np.float64) * b.astype(np.float64)) * (1 + dd_f32(3, 4000).astype(np.float64) * 1e-6)).astype(np.float32)
+    c[::3] = dd_f32(4, 4000)[::3]                           # cancelling and ordinary addends
+    r = ei.fma32(a, b, c)
+    for i in range(a.size):
+        exact = Fraction(float(a[i])) * Fraction(float(b[i])) + Fraction(float(c[i]))
+        d = abs(Fraction(float(r[i])) - exact)
+        for nb in (np.nextafter(r[i], np.float32(-np.inf)), np.nextafter(r[i], np.float32(np.inf))):
+            assert d <= abs(Fraction(float(nb)) - exact), i
+
+
+def dd_f32(seed, n):
+    from tests import detdata as dd
+    return dd.normal_f16(seed, (n,), 3.0).astype(np.float32) * np.float32(1.0009765)
+
+
+def _gn_exact_cases():
+    from tests.test_norm_exact_gpu import GN_EXACT
+    return GN_EXACT
+
+
+GN_EXACT_HOST = [c for c in _gn_exact_cases() if c[1] * c[2] <= 1 << 17]      # (the large ones: on the GPU only)
+
+
+@pytest.mark.parametrize("case", GN_EXACT_HOST, ids=[f"hw{c[1]}_c{c[2]}_g{c[3]}_{c[5]}" for c in GN_EXACT_HOST])
+def test_groupnorm_exact_inputs(oracle, case):
+    """The closed formula gives the oracle's bits (two restatements: one of the kernel's order, one order-free), lies
+    within the float64 bound, and every heavy position changes exactly one group's sums by the stated integers."""
+    from tests import norm_edges as ne
+    N, HW, Cc, G, silu, C1 = case
+    geom = ne.gn_launch(N, HW, Cc, G, silu)
+    x0, gamma, beta = ei.gn_base(N, HW, Cc, G)
+    assert np.abs(x0.astype(np.float64)).max() <= 8
+    s0, q0 = ei.gn_group_sums(x0, G)
+    pos = ei.gn_heavy_positions(geom, C1)
+    need = {"first_pixel", "last_pixel", "chunk_first", "chunk_last", "last_chunk_first", "last_pixel_lane",
+            "group_first_channel", "group_last_channel"}
+    if geom["cg"] % 8:
+        need |= {"octet_leading_half", "octet_trailing_half"}
+    if C1 is not None:
+        need |= {"x_last_channel", "x2_first_channel"}
+        assert pos["x_last_channel"][1] == C1 - 1 and pos["x2_first_channel"][1] == C1
+    assert need <= set(pos)
+    assert pos["first_pixel"][0] == 0 and pos["last_pixel"][0] == HW - 1
+    assert pos["last_chunk_first"][0] == (geom["nchunk"] - 1) * geom["ppb"]
+    assert pos["chunk_first"][0] % geom["ppb"] == 0 and (pos["chunk_last"][0] + 1) % geom["ppb"] in (0, HW % geom["ppb"])
+    if "octet_leading_half" in pos:
+        lo, hi = pos["octet_leading_half"][1], pos["octet_trailing_half"][1]
+        assert lo % 8 == 0 and hi == lo + 7 and lo // geom["cg"] + 1 == hi // geom["cg"]
+    for name, (p, ch) in [("base", (None, None))] + sorted(pos.items()):
+        if name == "base":
+            x = x0
+        else:
+            x, _, _, info = ei.gn_heavy(N, HW, Cc, G, p, ch)
+            s, q = ei.gn_group_sums(x, G)
+            assert (s - s0)[info["image"], info["group"]] == info["ds"] and np.count_nonzero(q - q0) == 1
+            assert (q - q0)[info["image"], info["group"]] == info["dq"] and info["group"] == ch // geom["cg"]
+        want, st = ei.gn_expected(x, gamma, beta, G)
+        _, h = oracle.groupnorm_silu_quantize(x, gamma, beta, 1e-5, G, False, 1.0, 0.0)
+        assert np.array_equal(want.view(np.uint16), h.view(np.uint16)), name
+        # (the constant group has variance 0 -- mean / sigma is infinite: its bits are pinned, the bound is not for it)
+        live = np.repeat(st["var"] > 0, Cc // G, axis=1)[:, None, :]
+        assert (ne.within_norm_bound(want, ne.groupnorm64(x, gamma, beta, 1e-5, G)) | ~live).all(), name
+    assert ei.gn_expected(x0, gamma, beta, G)[1]["var"][N - 1, 1] == 0           # the constant group
+
+
+@pytest.mark.parametrize("C", [16, 32, 48, 96, 160, 320, 512, 960, 1024, 1168, 1536, 1920, 2032, 2048])
+def test_layernorm_exact_inputs(oracle, C):
+    from tests import norm_edges as ne
+    x, gamma, beta, cols = ei.ln_heavy(C)
+    g = ne.ln_geom(1, C)
+    u = g["U"] // 2
+    need = {0, C - 1} | {16 * (u * g["per"] + k) + d for k in range(g["per"] + 1) for d in (-1, 0)}
+    if C >= 1024:
+        need |= set(range(504, 520))
+    assert {c for c in need if 0 <= c < C} <= set(cols)
+    assert g["U"] == 1 or any(c % (16 * g["per"]) == 0 and 0 < c < C for c in cols)      # a unit boundary
+    _, h = oracle.layernorm_quantize(x, gamma, beta, 1e-5, [])
+    assert np.array_equal(ei.ln_expected_zero_mean(x[:1], gamma, beta).view(np.uint16), h[:1].view(np.uint16))
+    assert ne.within_norm_bound(h, ne.layernorm64(x, gamma, beta, 1e-5)).all()
+    for c in (0, 3, 4, -7):
+        _, hc = oracle.layernorm_quantize(np.full((1, C), c, np.float16), gamma, beta, 1e-5, [])
+        assert np.array_equal(ei.ln_expected_constant(c, C, gamma, beta).view(np.uint16), hc[0].view(np.uint16)), c
+    assert np.array_equal(ei.ln_expected_constant(0, C, gamma, beta).view(np.uint16), beta.view(np.uint16))
+    if C & (C - 1) == 0:            # rn(1 / C) exact: a constant row gives exactly beta
+        assert np.array_equal(ei.ln_expected_constant(3, C, gamma, beta).view(np.uint16), beta.view(np.uint16))
+
+
+def test_quantizer_edge_values_reach_ties_and_both_clamps():
+    v = ei.qedge_values(2032)[0::2]
+    for qp in ei.QEDGE_LN:
+        assert all(ei.qedge_facts(v, *qp).values()), qp
+    x = ei.qedge_values(33 * 64, seed=3)
+    for qp in ei.QEDGE_RAW:
+        assert all(ei.qedge_facts(x, *qp).values()), qp
+    assert np.abs(ei.qedge_values(5000).astype(np.float64)).max() == 80
