@@ -217,6 +217,21 @@ int mixdq_qlinear_f16in_select_id(int64_t M, int N, int K, int w4);
  * `workspace`: device buffer of at least mixdq_qconv2d_workspace_bytes(K,R,S,pad) bytes
  *             (may be null when that is 0).
  * dilation must be 1 (MIXDQ_ERR_UNSUPPORTED otherwise); C % 4 == 0 and K % 4 == 0.
+ * Geometry: any R, S, stride and pad with pad < R and pad < S (MIXDQ_ERR_PADDING otherwise, nothing written:
+ * every window must hold an image row and column -- a border class is a non-empty tap rectangle, and the table
+ * rows of empty rectangles are never read).  mixdq_conv2d_f16 has no such limit (zero padding needs no class).
+ *
+ * Operand alignment, every entry point.  Operands are expected on 16-byte boundaries (FP16 bias vectors: 8).
+ * An operand off its boundary, but on its own element's natural alignment, is handled as follows:
+ *   mixdq_qlinear_w8a8[_rows], mixdq_qconv2d_w8a8[_table], mixdq_linear_f16, mixdq_conv2d_f16:
+ *       the one-output-per-thread generic kernel runs -- same bits, MIXDQ_OK.  (A conv in the LDS-halo kernel's
+ *       range falls through to it as well; a FORCED halo tile or MIXDQ_FLAG_UPSAMPLE2X then returns MIXDQ_ERR_SHAPE.)
+ *   the same entries with MIXDQ_FLAG_W4 / MIXDQ_FLAG_W2:     MIXDQ_ERR_W4_SHAPE / MIXDQ_ERR_W2_SHAPE
+ *   mixdq_qlinear_w8a8_geglu (output: 8 bytes):                MIXDQ_ERR_GEGLU_SHAPE
+ *   mixdq_qlinear_w8a8_grouped (A; W4 / W2: the packed code):  MIXDQ_ERR_ALIGNMENT
+ *   mixdq_qlinear_w8a8_attn, mixdq_qlinear_w8a8_ln, mixdq_attention_f16, mixdq_sampler_step:  MIXDQ_ERR_ALIGNMENT
+ *   mixdq_qlinear_f16in_w8a8:                                  MIXDQ_ERR_SHAPE (the caller issues the two launches)
+ * A refusing entry writes nothing.  tests/test_conv_geometry_gpu.py pins each line.
  */
 size_t mixdq_qconv2d_workspace_bytes(int K, int R, int S, int pad);
 

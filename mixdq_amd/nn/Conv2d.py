@@ -74,6 +74,13 @@ class QuantizedConv2d(nn.Module):
             cins = [in_channels] if split == 0 else [split, in_channels - split]
             if any(c % 32 != 0 for c in cins):       # packed pieces span 32 input channels
                 self.valid_for_acceleration = False
+        if self.valid_for_acceleration and padding[0] >= min(kernel_size):
+            # a window with no tap inside the image has no border class: the INT8 entries refuse the layer
+            # (MIXDQ_ERR_PADDING, include/mixdq_hip.h) -- decided here, not inside forward()
+            logging.warning(
+                f"Conv2d layer with kernel_size = {tuple(kernel_size)} and padding = {tuple(padding)} cannot use "
+                "quantized kernel (padding must be smaller than the kernel size). Falling back to FP kernels")
+            self.valid_for_acceleration = False
         if self.valid_for_acceleration and (in_channels % 4 != 0 or out_channels % 4 != 0):
             logging.warning(
                 f"Conv2d layer with in_channels = {in_channels} and out_channels = "

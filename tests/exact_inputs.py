@@ -347,10 +347,16 @@ def conv_accumulate(x, w, stride, pad, dtype=np.float64):
 
 @functools.lru_cache(maxsize=2)
 def conv2d(N, Cin, H, W, K, ks, stride, pad, bias=True, residual=None, seed=0):
-    """x [N, C, H, W], w [K, C, ks, ks] (NCHW order), residual None | "full" ([N, K, P, Q]) | "per_image" ([N, K])
-    -> expected [N, K, P, Q] fp16."""
-    s = _seed(N, Cin, H, W, K, ks, stride, pad, seed)
-    x, w = _ints16(s, (N, Cin, H, W), 4), _ints16(s + 1, (K, Cin, ks, ks), 2)
+    """x [N, C, H, W], w [K, C, R, S] (NCHW order), residual None | "full" ([N, K, P, Q]) | "per_image" ([N, K])
+    -> expected [N, K, P, Q] fp16.  `ks`: the square kernel size, or (R, S) (a square size given as an int keeps the
+    seed, and with it the data, it always had)."""
+    if isinstance(ks, tuple):
+        R, S = ks
+        s = _seed(N, Cin, H, W, K, R, S, stride, pad, seed, 78)
+    else:
+        R = S = ks
+        s = _seed(N, Cin, H, W, K, ks, stride, pad, seed)
+    x, w = _ints16(s, (N, Cin, H, W), 4), _ints16(s + 1, (K, Cin, R, S), 2)
     b = _eighths(s + 2, (K,)) if bias else None
     acc = conv_accumulate(x, w, stride, pad)
     res = None
