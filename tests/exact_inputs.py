@@ -1,6 +1,7 @@
-"""Exact-result inputs for the FP16 attention core, the FP16 layer kernels and the norm producers
-(tests/test_attention_exact_gpu.py, tests/test_f16_exact_gpu.py, tests/test_norm_exact_gpu.py run them on the GPU;
-tests/test_exact_inputs_host.py checks them on the CPU).
+"""Exact-result inputs for the FP16 attention core, the fused to_q + cross-attention launch, the FP16 layer kernels
+and the norm producers (tests/test_attention_exact_gpu.py, tests/test_qlinear_attention_exact_gpu.py,
+tests/test_f16_exact_gpu.py, tests/test_norm_exact_gpu.py run them on the GPU; tests/test_exact_inputs_host.py checks
+them on the CPU).
 
 The technique: inputs for which the mathematically exact result is also the only result a correct kernel can
 produce, so that the comparison is equality of bits and needs no tolerance.  Every builder returns the inputs and the
@@ -22,6 +23,12 @@ Attention
   small_integers()   q = 0, v small integers, tkv a power of two, tkv * max|v| < 2^24: out = fp16(sum / tkv) exactly.
   rescale()          score staircases, a late dominant key, equal large scores, |v| near the FP16 maximum: float64
                      softmax as the expected output (tolerance-held; they drive the running-maximum rescale).
+to_q + cross-attention (mixdq_qlinear_w8a8_attn: Q comes out of the INT8 GEMM, head width 64, at most 128 keys)
+  toq_operands()     int8 a [B, T, K], int8 w [N, K] in [-2, 1] (the same integers pack to W8, W4 and W2), scale 1,
+                     bias0 0, whose GEMM result IS the fp16 q of one of the builders above (asserted in int64):
+                     a one-hot row of `a` per (image, head) picks the sign code of the hot key -- or, for rescale(),
+                     the sign vector u -- out of w; for the q = 0 builders dense non-zero rows of `a` meet weight
+                     columns in cancelling pairs.
 FP16 layers
   linear() / conv2d() / gemm()   integer-valued activations in [-4, 4], weights in [-2, 2], bias a multiple of 1/8 in
                      [-4, 4]: |acc| < 2^20, so the FP32 accumulator and accumulator + bias are exact in any summation
@@ -228,10 +235,11 @@ RESCALE_KEY_COUNTS = (77, 300, 640)
 
 
 @functools.lru_cache(maxsize=4)
-def rescale(kind, D, tkv, tq=200, B=2, heads=2, seed=0):
+def rescale(kind, D, tkv, tq=200, B=2, heads=2, seed=0, q_noise=0.25):
     """q = alpha u + noise, k_j = beta_j u + noise with u a sign vector: the scaled log2 score of key j is about
     alpha beta_j sqrt(D) log2(e), chosen per kind (a staircase over the 64-key tiles, a late dominant key, one
-    large value for all).  Returns the float64 result as `expected` and the per-kind facts the host test checks."""
+    large value for all).  Returns the float64 result as `expected` and the per-kind facts the host test checks.
+    `q_noise`: the noise of q where the kind has any (0: q == alpha u exactly, the noise stays in k)."""
     assert kind in RESCALE_KINDS
     C = heads * D
     s0 = 5000 + seed + D + tkv + 97 * RESCALE_KINDS.index(kind)
@@ -262,7 +270,8 @@ def rescale(kind, D, tkv, tq=200, B=2, heads=2, seed=0):
         v = (mag * _signs(s0 + 4, (B, 1, C))).astype(np.float16)
     else:
         alpha = 2.0
-        q = (alpha * u + noise * dd.normal_f16(s0 + 1, (B, tq, C), 1.0).astype(np.float64)).astype(np.float16)
+        qn = q_noise if noise else 0.0
+        q = (alpha * u + qn * dd.normal_f16(s0 + 1, (B, tq, C), 1.0).astype(np.float64)).astype(np.float16)
         beta = level / (alpha * unit)
         k = (beta[None, :, None] * u + noise * dd.normal_f16(s0 + 2, (B, tkv, C), 1.0).astype(np.float64)
              ).astype(np.float16)
@@ -272,6 +281,90 @@ def rescale(kind, D, tkv, tq=200, B=2, heads=2, seed=0):
     tmax = np.stack([s[..., tile == t].max(axis=-1) for t in range(nt)], axis=-1)      # [B, h, tq, nt]
     facts = dict(tile_max=tmax, max_abs_score=float(np.abs(s).max()))
     return dict(q=q, k=k, v=v, heads=heads, expected=softmax_attention64(q, k, v, heads), facts=facts, scores=s)
+
+
+# ------------------------------------------------------------------------------------------ to_q + cross-attention
+# The fused launch (csrc/igemm_kernel.h, ATT) computes Q itself: 64 x 128 x 128 tiles of an INT8 GEMM, three stages,
+# the keys and values of a head pair staged by LDS-DMA ahead of the K-tiles.  The builders above prescribe a fp16 q;
+# here the GEMM's operands are built so that it produces that q exactly.
+#   K is cut into one block of 128 columns per (image, head): K = 128 B heads (1024: eight K-tiles at B = 2, heads = 4).
+#   one-hot: row (b, i) of `a` holds the amplitude at column 128 (b heads + h) + col[b, h][i] for every head h and 0
+#            elsewhere; w[n, block (b, h), j] is the sign the query must get at channel n (n inside head h) when it
+#            addresses column j, and 0 for n outside that head.  Columns no row addresses hold non-zero filler from
+#            {-2, -1, 1}: a mis-indexed K column gives a q that is no key.  acc = amplitude * sign, exactly.
+#   zero:    a[b, i, 2 j] == a[b, i, 2 j + 1] (random, non-zero), w[n, 2 j + 1] == -w[n, 2 j] in {-1, 1}: every
+#            accumulator is a sum of K / 2 cancelling pairs -- the GEMM multiplies, its result is 0.
+QATT_KEY_COUNTS = (1, 4, 5, 63, 64, 65, 77, 96, 97, 127, 128)     # both sides of the half-wave mask split, of the tile
+QATT_QUERY_COUNTS = (64, 192)                                     # whole 64-row tiles: one and three per image
+QATT_B, QATT_HEADS, QATT_BLOCK = 2, 4, 128
+QATT_RESCALE_KEY_COUNTS = (65, 77, 128)                           # two key tiles each
+QATT_RESCALE_COLUMNS = 96                                         # addressed columns per block of the rescale() form
+
+
+def _filler(seed, shape):
+    n = int(np.prod(shape))
+    return np.array([-2, -1, 1], np.int8)[((dd.u64(seed, n) >> np.uint64(35)) % np.uint64(3)).astype(np.int64)].reshape(shape)
+
+
+def _one_hot_operands(amp, col, sign, B, T, heads, D, seed):
+    """col [B, heads, T]: the addressed column of block (b, h) per query; sign [B, heads, D, ncol] in {-1, +1}: the
+    weights of the addressed columns.  Returns a [B, T, K], w [heads D, K]."""
+    ncol = sign.shape[-1]
+    assert ncol <= QATT_BLOCK and col.max() < ncol and col.min() >= 0 and set(np.unique(sign)) <= {-1, 1}
+    K = QATT_BLOCK * B * heads
+    a = np.zeros((B, T, K), np.int8)
+    w = np.zeros((heads * D, K), np.int8)
+    for b in range(B):
+        for h in range(heads):
+            c0 = QATT_BLOCK * (b * heads + h)
+            a[b, np.arange(T), c0 + col[b, h]] = amp
+            w[h * D:(h + 1) * D, c0:c0 + ncol] = sign[b, h]
+            if ncol < QATT_BLOCK:        # never addressed: non-zero at EVERY channel
+                w[:, c0 + ncol:c0 + QATT_BLOCK] = _filler(seed + 31 * (b * heads + h), (heads * D, QATT_BLOCK - ncol))
+    return a, w
+
+
+def _zero_operands(B, T, N, K, seed):
+    assert K % 2 == 0
+    half = dd.int8(seed, (B, T, K // 2), 1, 128) * (2 * dd.int8(seed + 1, (B, T, K // 2), 0, 2) - 1)   # 1 .. 127, signed
+    ws = (2 * dd.int8(seed + 2, (N, K // 2), 0, 2) - 1).astype(np.int8)
+    a = np.repeat(half.astype(np.int8), 2, axis=2)
+    w = np.stack([ws, -ws], axis=2).reshape(N, K)
+    assert (a != 0).all() and (w != 0).all()
+    return a, w
+
+
+@functools.lru_cache(maxsize=4)
+def toq_operands(family, tkv, tq=64, kind=None, B=QATT_B, heads=QATT_HEADS, seed=0):
+    """The operands of to_q for one attention case at head width 64: dict(a int8 [B, tq, K], w int8 [N, K] with values
+    in [-2, 1], scale, bias0 (float32 [N]: 1 and 0), q fp16 [B, tq, N] -- what the GEMM gives, bit for bit -- and
+    `case`, the attention builder's own dict (k, v, expected, ...)).
+    family: "selection" | "every_key_once" | "small_integers" | "rescale" (with `kind`, not "huge_values": its q is
+    no sign vector)."""
+    D = 64
+    N = heads * D
+    assert tq % 64 == 0 and 0 < tkv <= 2 * TILE
+    if family == "selection":
+        c = selection(D, tkv, tq, B, heads, seed)
+        ksign = np.sign(_heads(c["k"].astype(np.float64), heads)).astype(np.int8)          # [B, heads, tkv, D]
+        a, w = _one_hot_operands(int(AMPLITUDE[D]), c["hot"], ksign.transpose(0, 1, 3, 2), B, tq, heads, D, 6000 + seed + tkv)
+    elif family == "rescale":
+        assert kind in RESCALE_KINDS and kind != "huge_values"
+        c = rescale(kind, D, tkv, tq, B, heads, seed, q_noise=0.0)
+        u = np.sign(_heads(c["q"][:, :1].astype(np.float64), heads)).astype(np.int8)       # [B, heads, 1, D]
+        sign = np.repeat(u.transpose(0, 1, 3, 2), QATT_RESCALE_COLUMNS, axis=3)
+        col = np.broadcast_to((np.arange(tq) * 37 + 11) % QATT_RESCALE_COLUMNS, (B, heads, tq))
+        a, w = _one_hot_operands(2, col, sign, B, tq, heads, D, 6100 + seed + tkv)
+    else:
+        c = {"every_key_once": every_key_once, "small_integers": small_integers}[family](D, tkv, tq, B, heads, seed)
+        a, w = _zero_operands(B, tq, N, 512, 6200 + seed + tkv)
+    assert w.min() >= -2 and w.max() <= 1, "the weights must pack to W2"
+    assert (np.abs(a.astype(np.int64)).sum(axis=2) > 0).all(), "an all-zero activation row"
+    acc = a.reshape(B * tq, -1).astype(np.int64) @ w.astype(np.int64).T                      # exact
+    q = c["q"]
+    assert np.array_equal(acc.reshape(B, tq, N).astype(np.float64), q.astype(np.float64)), "the GEMM does not give q"
+    assert np.array_equal(acc.reshape(B, tq, N).astype(np.float16).view(np.uint16), q.view(np.uint16))
+    return dict(a=a, w=w, scale=np.ones(N, np.float32), bias0=np.zeros(N, np.float32), q=q, case=c)
 
 
 # ------------------------------------------------------------------------------------------ FP16 layers

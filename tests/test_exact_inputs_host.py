@@ -105,10 +105,15 @@ RESCALE = [(kind, D, tkv) for kind in ei.RESCALE_KINDS for D in ei.WIDTHS for tk
 
 @pytest.mark.parametrize("kind,D,tkv", RESCALE, ids=[f"{k}_d{D}_k{n}" for k, D, n in RESCALE])
 def test_rescale_cases(oracle, kind, D, tkv):
-    c = ei.rescale(kind, D, tkv)
+    check_rescale_case(oracle, ei.rescale(kind, D, tkv), kind)
+
+
+def check_rescale_case(oracle, c, kind, facts=True):
     _, ref64 = oracle.attention_f16(c["q"], c["k"], c["v"], c["heads"])
     scale = np.abs(c["v"].astype(np.float64)).max()
     assert np.abs(ref64 - c["expected"]).max() <= 1e-12 * scale
+    if not facts:
+        return
     tm = c["facts"]["tile_max"]                                  # [B, heads, tq, tiles], log2 units
     d = np.median(np.diff(tm, axis=-1), axis=(0, 1, 2))          # per tile boundary, the typical query
     if kind in ("rise4", "rise40", "fall4", "fall40"):
@@ -130,6 +135,175 @@ def test_rescale_key_counts_reach_the_short_form_the_ragged_mask_and_the_ring_wr
     assert any(n > 128 and n % 64 for n in ei.RESCALE_KEY_COUNTS)
     assert any(n % 64 == 0 and n // 64 > 4 for n in ei.RESCALE_KEY_COUNTS)
     assert ei.rescale("rise4", 64, 300)["q"].shape[0] >= 2                              # a batch: rows vs single runs
+
+
+# ------------------------------------------------------------------------------------------ to_q + cross-attention
+QATT = [(tkv, tq) for tkv in ei.QATT_KEY_COUNTS for tq in ei.QATT_QUERY_COUNTS]
+QATT_IDS = [f"k{tkv}_q{tq}" for tkv, tq in QATT]
+
+
+def attention_tolerance():
+    from tests.test_attention_gpu import ATOL, RTOL
+    return ATOL, RTOL
+
+
+def check_toq(oracle, o, what):
+    """oracle.qlinear on the operands, stored as W8 and unpacked from W4 and from W2, returns q bit for bit."""
+    import torch
+    from mixdq_amd.nn.utils import pack_w2, pack_w4, unpack_w2
+    a, w, q = o["a"], o["w"], o["q"]
+    B, T, K = a.shape
+    assert K % 128 == 0 and T % 64 == 0 and w.shape == (q.shape[-1], K) and w.shape[0] % 128 == 0
+    assert (o["scale"] == 1).all() and (o["bias0"] == 0).all()
+    wt = torch.from_numpy(w)
+    stored = {"W8": w, "W4": oracle.unpack_w4(pack_w4(wt).numpy()), "W2": unpack_w2(pack_w2(wt)).numpy()}
+    for name, wi in stored.items():
+        assert np.array_equal(wi, w), f"{what} {name}: the packed weights are other integers"
+        got, acc = oracle.qlinear(a, wi, o["bias0"], o["scale"], None, return_acc=True)
+        assert np.array_equal(got.view(np.uint16), q.view(np.uint16)), f"{what} {name}"
+        assert np.array_equal(acc.astype(np.float64), q.astype(np.float64)), f"{what} {name}: accumulators"
+
+
+def test_the_fused_launch_key_and_query_counts():
+    assert ei.QATT_KEY_COUNTS == (1, 4, 5, 63, 64, 65, 77, 96, 97, 127, 128)
+    assert ei.QATT_QUERY_COUNTS == (64, 192) and (ei.QATT_B, ei.QATT_HEADS) == (2, 4)
+    assert ei.QATT_BLOCK * ei.QATT_B * ei.QATT_HEADS == 1024                       # eight K-tiles of 128
+    assert set(ei.QATT_RESCALE_KEY_COUNTS) == {65, 77, 128} and all(n > 64 for n in ei.QATT_RESCALE_KEY_COUNTS)
+
+
+@pytest.mark.parametrize("tkv,tq", QATT, ids=QATT_IDS)
+def test_toq_selection_operands(oracle, tkv, tq):
+    """The GEMM gives the hot key (W8, W4, W2); selection()'s own preconditions hold at four heads and 64 / 192
+    queries (asserted inside the builder, restated from its stats); the oracle's attention on (q, k, v) is the hot
+    value row; a reference that swaps two value rows is rejected at exactly the queries that address them."""
+    o = ei.toq_operands("selection", tkv, tq)
+    c = o["case"]
+    a, w, hot, want, heads = o["a"], o["w"], c["hot"], c["expected"], c["heads"]
+    B, D = a.shape[0], 64
+    assert (B, heads, a.shape[2]) == (2, 4, 1024) and want.shape == (B, tq, heads * D)
+    check_toq(oracle, o, f"selection k{tkv} q{tq}")
+    st = c["stats"]
+    assert st["min_gap"] >= 26 and 0 < st["min_hot"] <= st["max_hot"] <= 1000 and st["max_rest_ulps"] <= 1 / 16
+    # the layout, restated: one 3 per (row, head block), at the hot key's column; sign codes below tkv, filler above
+    assert set(np.unique(a)) == {0, 3} and ((a != 0).sum(axis=2) == heads).all()
+    for b in range(B):
+        for h in range(heads):
+            c0 = 128 * (b * heads + h)
+            assert np.array_equal(np.argmax(a[b, :, c0:c0 + 128], axis=1), hot[b, h])
+            blk = w[:, c0:c0 + 128]
+            ks = np.sign(c["k"][b, :, h * D:(h + 1) * D].astype(np.float64)).T
+            assert np.array_equal(blk[h * D:(h + 1) * D, :tkv], ks)
+            outside = np.delete(blk[:, :tkv], np.s_[h * D:(h + 1) * D], axis=0)
+            assert (outside == 0).all() and (blk[:, tkv:] != 0).all() and set(np.unique(blk[:, tkv:])) <= {-2, -1, 1}
+            reached = set(int(x) for x in hot[b, h])
+            assert reached == set(range(tkv)) if tq >= tkv else required_keys(tkv) <= reached, (b, h)
+    ATOL, RTOL = attention_tolerance()
+    ref16, ref64 = oracle.attention_f16(o["q"], c["k"], c["v"], heads)
+    assert np.array_equal(ref16.view(np.uint16), want.view(np.uint16))
+    assert (np.abs(ref64 - want.astype(np.float64)) <= ATOL + RTOL * np.abs(ref64)).all()
+    assert (np.abs(ref64 - want.astype(np.float64)) <= ei.ulp16(want) / 8).all()
+    if tkv > 1:                      # the wrong variant: value rows j0 and j1 of (image 0, head 1) change places
+        j0, j1 = (0, tkv - 1) if tkv < 64 or tkv == 64 else (63, 64)
+        v2 = c["v"].copy()
+        v2[0, [j0, j1], D:2 * D] = c["v"][0, [j1, j0], D:2 * D]
+        wrong = ei.softmax_attention64(o["q"], c["k"], v2, heads).astype(np.float16)
+        differs = (wrong.view(np.uint16) != want.view(np.uint16)).any(axis=2)              # [B, tq]
+        assert np.array_equal(differs[0], np.isin(hot[0, 1], (j0, j1))) and differs[0].any() and not differs[1].any()
+        other = wrong.view(np.uint16)[..., np.r_[0:D, 2 * D:4 * D]] == want.view(np.uint16)[..., np.r_[0:D, 2 * D:4 * D]]
+        assert other.all()
+    right = ei.softmax_attention64(o["q"], c["k"], c["v"], heads).astype(np.float16)
+    assert np.array_equal(right.view(np.uint16), want.view(np.uint16))
+
+
+@pytest.mark.parametrize("tkv,tq", QATT, ids=QATT_IDS)
+def test_toq_zero_score_operands(oracle, tkv, tq):
+    """q = 0 out of a GEMM that multiplies: dense non-zero rows against weight columns in cancelling pairs.  The
+    oracle's attention gives 2048 / tkv; a reference that admits the clamped copy of the last key, or drops a key,
+    is rejected by more than the ulp the GPU test allows."""
+    ATOL, RTOL = attention_tolerance()
+    o = ei.toq_operands("every_key_once", tkv, tq)
+    c = o["case"]
+    check_toq(oracle, o, f"every_key_once k{tkv} q{tq}")
+    a, w = o["a"], o["w"]
+    assert (a != 0).all() and (w != 0).all() and (o["q"] == 0).all() and not np.signbit(o["q"]).any()
+    part = a[0, 0, :128].astype(np.int64) @ w[:, :128].astype(np.int64).T                    # one K-tile alone: exact 0 too,
+    assert (part == 0).all() and (a[0, 0, :127].astype(np.int64) @ w[:, :127].astype(np.int64).T != 0).any()   # but not a split pair
+    heads = c["heads"]
+    _, ref64 = oracle.attention_f16(o["q"], c["k"], c["v"], heads)
+    assert (np.abs(ref64 - c["expected"]) <= ATOL + RTOL * np.abs(ref64)).all()
+    assert np.abs(ref64 - c["expected"]).max() <= 1e-12 * ei.PROBE / tkv
+    assert required_keys(tkv) | {tkv - 1} <= set(int(x) for x in c["probes"].ravel())
+    last = c["probes"] == tkv - 1                                                            # [B, C]
+    assert last.any()
+    # wrong variant 1: the clamped re-read of the last key admitted past the mask (one more key, a copy of the last)
+    # (a single key: any number of copies of it give v -- there the selection family's distinct rows do the work)
+    k2, v2 = (np.concatenate([x, x[:, -1:]], axis=1) for x in (c["k"], c["v"]))
+    wrong = ei.softmax_attention64(o["q"], k2, v2, heads)
+    off = np.abs(wrong - c["expected"]) > c["ulp"]
+    assert off.all() or tkv == 1, "an admitted copy of the last key passes"
+    assert np.allclose(wrong[:, 0][last], 2 * ei.PROBE / (tkv + 1)) and np.allclose(wrong[:, 0][~last], ei.PROBE / (tkv + 1))
+    # wrong variant 2: key 0 dropped
+    if tkv > 1:
+        wrong = ei.softmax_attention64(o["q"], c["k"][:, 1:], c["v"][:, 1:], heads)
+        assert (np.abs(wrong - c["expected"]) > c["ulp"]).all()
+        assert (wrong[:, 0][c["probes"] == 0] == 0).all()
+    if c["exact"]:
+        o = ei.toq_operands("small_integers", tkv, tq)
+        s = o["case"]
+        check_toq(oracle, o, f"small_integers k{tkv} q{tq}")
+        _, ref64 = oracle.attention_f16(o["q"], s["k"], s["v"], heads)
+        assert np.abs(ref64 - s["mean"][:, None, :]).max() <= 1e-12 * max(1.0, np.abs(s["mean"]).max())
+        assert (np.abs(ref64 - s["expected"].astype(np.float64)) <= ATOL + RTOL * np.abs(ref64)).all()
+        vi = s["v"].astype(np.int64)
+        assert np.array_equal(s["expected"][:, 0], (vi.sum(axis=1) / tkv).astype(np.float16))
+        if tkv > 1:                  # two value rows exchanged between channels: another mean
+            v2 = s["v"].copy()
+            v2[:, 0] = s["v"][:, 0, ::-1]
+            wrong = ei.softmax_attention64(o["q"], s["k"], v2, heads).astype(np.float16)
+            assert (wrong.view(np.uint16) != s["expected"].view(np.uint16)).any()
+
+
+QATT_RESCALE = [(kind, tkv) for kind in ei.RESCALE_KINDS[:-1] for tkv in ei.QATT_RESCALE_KEY_COUNTS]
+
+
+@pytest.mark.parametrize("kind,tkv", QATT_RESCALE, ids=[f"{k}_k{n}" for k, n in QATT_RESCALE])
+def test_toq_rescale_operands(oracle, kind, tkv):
+    """q == 2 u exactly out of the GEMM (the noise stays in k); the facts of the kind hold as they do with noisy q."""
+    assert ei.RESCALE_KINDS[-1] == "huge_values"               # the one kind whose q is no sign vector: chain only
+    o = ei.toq_operands("rescale", tkv, 64, kind)
+    c = o["case"]
+    check_toq(oracle, o, f"rescale {kind} k{tkv}")
+    assert set(np.unique(o["q"].astype(np.float64))) == {-2.0, 2.0} and (o["q"] == o["q"][:, :1]).all()
+    assert c["facts"]["tile_max"].shape[-1] == 2 and c["heads"] == 4              # two key tiles
+    a, w = o["a"], o["w"]
+    assert set(np.unique(a)) == {0, 2} and ((a != 0).sum(axis=2) == 4).all()
+    assert (w.reshape(w.shape[0], -1, 128)[:, :, ei.QATT_RESCALE_COLUMNS:] != 0).all()
+    check_rescale_case(oracle, c, kind, facts=False)
+    # The facts, for two tiles of which the second holds 1, 13 or 64 keys.  The noise of k moves a score by
+    # sigma = alpha * 0.25 * log2(e) = 0.72 log2 units (q = 2 u has 64 entries of 2, the scale is 1 / 8); a tile's
+    # maximum lies up to ~3.5 sigma above its level (64 draws), a single key's score within 3.5 sigma of it.
+    sigma = 2 * 0.25 * ei.LOG2E
+    tm = c["facts"]["tile_max"]
+    d = np.median(tm[..., 1] - tm[..., 0])
+    if kind in ("rise4", "rise40", "fall4", "fall40"):
+        step = (40.0 if kind.endswith("40") else 4.0) * (1 if kind.startswith("rise") else -1)
+        assert abs(d - step) <= 3.5 * sigma and np.sign(d) == np.sign(step), d        # alpha = 2^-|d| at the second tile
+    elif kind == "late_dominant":
+        if tkv - 2 >= 64:            # the dominant key (tkv - 2) in the second tile, behind a maximum of 50 in the first
+            assert np.median(tm[..., 0]) >= 40 and d >= 40
+        else:                        # 65 keys: it is key 63, the last of the FIRST tile; the second tile's one key
+            assert np.median(tm[..., 0]) >= 90 and d <= -90      # underflows against it (P == 0, no rescale)
+    else:
+        sign = -1 if kind.endswith("negative") else 1
+        assert np.abs(c["scores"] - 60.0 * sign).max() <= 0.5
+
+
+def test_rescale_default_noise_is_unchanged():
+    """q_noise defaults to the 0.25 the kinds always had: the default call and the explicit one give the same bits."""
+    for kind in ("rise4", "equal_large"):
+        c, d = ei.rescale(kind, 64, 77), ei.rescale.__wrapped__(kind, 64, 77, q_noise=0.25)
+        assert all(np.array_equal(c[n].view(np.uint16), d[n].view(np.uint16)) for n in "qkv")
+    assert (np.abs(ei.rescale("rise4", 64, 77)["q"].astype(np.float64)) != 2).any()
 
 
 # ------------------------------------------------------------------------------------------ FP16 layers
