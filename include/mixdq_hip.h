@@ -79,7 +79,11 @@ enum mixdq_flags {
      2x upsampling (H, W stay the conv's input size) -- Upsample2D's conv(interpolate(x, 2.0)) without
      the upsampled tensor (quantizing commutes with nearest upsampling: the INT8 values are the same).
      3x3 / stride 1 / pad 1 shapes of the LDS-halo kernel only (mixdq_conv_halo_select != 0), else
-     MIXDQ_ERR_SHAPE.  No reference counterpart. */
+     MIXDQ_ERR_SHAPE.  No reference counterpart.
+     mixdq_conv2d_f16 takes the flag too (same contract: X is [N, H/2, W/2, C], H and W stay the conv's input size;
+     the gather of the MFMA tiles reads pixel (y >> 1, x >> 1) and tests (y, x) against H and W, so the result has
+     the bits of the conv on the materialised upsampling): 3x3 / stride 1 / pad 1, H and W even, C % 8 == 0,
+     K % 4 == 0 and 16-byte aligned operands (the MFMA tiles), else MIXDQ_ERR_SHAPE with nothing written. */
   MIXDQ_FLAG_UPSAMPLE2X = 4,
   /* mixdq_qlinear_f16in_w8a8 only: the FP16 operand's rows follow the output row map (see there). */
   MIXDQ_FLAG_A_ROWMAP = 8,
@@ -418,7 +422,12 @@ int mixdq_qlinear_w8a8_geglu(const int8_t* A, const int8_t* W_interleaved, const
                              int64_t M, int N, int K, const float* out_scale_inv,
                              const float* out_zero_point, int flags, mixdq_stream_t stream);
 
-/* FP16 attention core, head_dim D = 64, 40, 80 or 160 (MIXDQ_ERR_SHAPE otherwise; 40 / 80 / 160: SD 1.5's heads --
+/* FP16 attention core, head_dim D = 64, 40, 80, 160 or 512 (MIXDQ_ERR_SHAPE otherwise).
+ * D = 512 (the VAE decoder's single head; any `heads`): FP16 output only -- out_scale_inv != null is MIXDQ_ERR_SHAPE --
+ * one launch geometry (32 query rows per workgroup, D split over its four waves: csrc/attention.hip
+ * attn_512_kernel), so bits 8..15 of flags must be 0 (MIXDQ_ERR_SHAPE otherwise); any tq / tkv; a prefetch payload
+ * is ignored.
+ * 40 / 80 / 160: SD 1.5's heads --
  * forms 4 and 2 are one kernel, form 1 its short-key sibling for tkv <= 128, which is what a launch with so few keys
  * gets by default (MIXDQ_ATTN_HD_SHORT=0 in the environment: forms 4 / 2 there too, for A/B runs); all forms give the
  * same bits; a payload of mixdq_attention_f16_prefetch is ignored at these widths):
@@ -471,7 +480,8 @@ int mixdq_attention_f16_prefetch(const void* q_f16, const void* k_f16, const voi
  *   D[m,n] = f16( sum_k f32(A[m,k]) * f32(W[n,k]) + f32(bias[n]) )  [+ residual, as above]
  * A [M,K], W [N,K], D [M,N] row-major fp16; conv: X [N,H,W,C], Wt [K,R,S,C], D [N,P,Q,K].
  * K % 8 == 0 (conv: C % 8 == 0) and N % 4 == 0 run on MFMA tiles, anything else (conv_in: C = 4)
- * on a one-output-per-thread kernel.  flags: bits 8..15 force a tile configuration. */
+ * on a one-output-per-thread kernel.  flags: bits 8..15 force a tile configuration; mixdq_conv2d_f16 also takes
+ * MIXDQ_FLAG_UPSAMPLE2X (see the flag: the conv of Upsample2D without the upsampled tensor). */
 int mixdq_linear_f16(const void* A_f16, const void* W_f16, const void* bias_f16_or_null,
                      void* D_f16, int64_t M, int N, int K, const void* residual_f16_or_null,
                      int64_t residual_row_div, int flags, mixdq_stream_t stream);

@@ -976,10 +976,13 @@ def linear_f16(input, weight, bias=None, *, _residual=None, _cfg=0):
 
 
 def conv2d_f16(input, weight, bias=None, stride=1, padding=0, *, _residual=None,
-               _residual_per_image=False, _cfg=0):
+               _residual_per_image=False, _cfg=0, _upsample2x=False):
     """F.conv2d(input, weight, bias, stride, padding) for fp16 GPU tensors (square stride / padding,
     dilation 1, groups 1): input [N, C, H, W] and weight [K, C, R, S] are read in channels-last
-    memory (converted if they are not), the result is channels-last [N, K, P, Q]."""
+    memory (converted if they are not), the result is channels-last [N, K, P, Q].
+    `_upsample2x`: the conv runs on F.interpolate(input, scale_factor=2, mode="nearest") without that tensor being
+    made (MIXDQ_FLAG_UPSAMPLE2X: 3x3 / stride 1 / padding 1 on the MFMA tiles -- C % 8 == 0, K % 4 == 0 -- only;
+    anything else is refused); same bits as the conv on the materialised tensor."""
     _trace_w(weight)
     _check(input.is_cuda and input.dtype == torch.float16 and input.dim() == 4,
            "input should be a 4-D fp16 GPU tensor")
@@ -987,6 +990,10 @@ def conv2d_f16(input, weight, bias=None, stride=1, padding=0, *, _residual=None,
            "weight should be a 4-D fp16 tensor on the input's device")
     stride, padding = int(stride), int(padding)
     N, C, H, W, K, R, S, P, Q = _conv_geometry(input, weight, stride, padding, 1)
+    if _upsample2x:       # the conv runs on the nearest 2x upsampling of the stored input
+        H, W = 2 * H, 2 * W
+        P = (H + 2 * padding - (R - 1) - 1) // stride + 1
+        Q = (W + 2 * padding - (S - 1) - 1) // stride + 1
     _check(weight.size(1) == C, "input and weight channel counts should match")
     if bias is not None:
         _check(bias.dtype == torch.float16 and bias.numel() == K, "bias should be fp16 [K]")
@@ -1008,8 +1015,8 @@ def conv2d_f16(input, weight, bias=None, stride=1, padding=0, *, _residual=None,
     bs = None if bias is None else bias.contiguous()
     with torch.cuda.device(x.device):
         code = _lib.mixdq_conv2d_f16(x.data_ptr(), w.data_ptr(), _ptr(bs), D.data_ptr(), N, H, W, C,
-                                     K, R, S, stride, padding, res_ptr, res_div, int(_cfg) << 8,
-                                     _stream())
+                                     K, R, S, stride, padding, res_ptr, res_div,
+                                     (int(_cfg) << 8) | (FLAG_UPSAMPLE2X if _upsample2x else 0), _stream())
     _status(code, "conv2d_f16")
     return D
 
@@ -1044,8 +1051,16 @@ def groupnorm_supported(N, HW, C, G) -> bool:
     return _lib.mixdq_groupnorm_workspace_bytes(N, HW, C, G) > 0
 
 
+def groupnorm_workspace(N, HW, C, num_groups, device) -> torch.Tensor:
+    """A workspace for groupnorm_silu_quantize launches of this shape (`_workspace=`): owned by the caller, one
+    launch at a time per buffer."""
+    ws_bytes = _lib.mixdq_groupnorm_workspace_bytes(int(N), int(HW), int(C), int(num_groups))
+    _check(ws_bytes > 0, "groupnorm_silu_quantize: unsupported configuration")
+    return torch.empty(ws_bytes // 4, dtype=torch.float32, device=device)
+
+
 def groupnorm_silu_quantize(x, num_groups, weight, bias, eps, scale_inv=None, zero_point=None,
-                            silu=True, want_f16=False, x2=None, raw_qparams=None):
+                            silu=True, want_f16=False, x2=None, raw_qparams=None, *, _workspace=None):
     """x: fp16 [N, C, H, W] in channels-last memory (or [N, HW, C] contiguous).  Returns
     (int8 or None, fp16 or None) with x's shape and strides.
     x2 (same layout, same N / H / W): the GroupNorm of cat([x, x2], dim=channels) without making
@@ -1078,7 +1093,12 @@ def groupnorm_silu_quantize(x, num_groups, weight, bias, eps, scale_inv=None, ze
     _check(want_q or want_f16, "nothing to compute")
     ws_bytes = _lib.mixdq_groupnorm_workspace_bytes(N, HW, C, num_groups)
     _check(ws_bytes > 0, "groupnorm_silu_quantize: unsupported configuration")
-    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=x.device)
+    if _workspace is not None:
+        _check(_workspace.device == x.device and _workspace.numel() * _workspace.element_size() >= ws_bytes,
+               "groupnorm_silu_quantize: workspace too small (groupnorm_workspace)")
+        ws = _workspace
+    else:
+        ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=x.device)
     out_q = torch.empty(shape, dtype=torch.int8, device=x.device, **fmt) if want_q else None
     out_h = torch.empty(shape, dtype=torch.float16, device=x.device, **fmt) if want_f16 else None
     w, b = weight.contiguous(), bias.contiguous()
@@ -1250,8 +1270,9 @@ if hasattr(_lib, "mixdq_attention_f16_prefetch"):     # (absent in older builds 
 PREFETCH_MAX_RANGES = 16
 
 
-# head widths of mixdq_attention_f16 (64: the SDXL kernels; 40, 80, 160: SD 1.5's, csrc/attention.hip attn_hd_kernel)
-ATTENTION_HEAD_DIMS = (40, 64, 80, 160)
+# head widths of mixdq_attention_f16 (64: the SDXL kernels; 40, 80, 160: SD 1.5's, csrc/attention.hip attn_hd_kernel;
+# 512: the VAE decoder's single head, attn_512_kernel -- FP16 output only)
+ATTENTION_HEAD_DIMS = (40, 64, 80, 160, 512)
 
 
 def attention_f16(q, k, v, heads, scale_inv=None, zero_point=None, softmax_scale=None, _cfg=0, _prefetch=None,
@@ -1259,7 +1280,8 @@ def attention_f16(q, k, v, heads, scale_inv=None, zero_point=None, softmax_scale
     """FP16 attention core (the reference's get_attention_scores + bmm, quant_block.py:630-637).
 
     q [B, Tq, C], k/v [B, Tkv, C] fp16 with unit stride along C (column slices of a fused projection
-    are read in place); C = heads * D, head width D in ATTENTION_HEAD_DIMS (64: SDXL; 40, 80, 160: SD 1.5).
+    are read in place); C = heads * D, head width D in ATTENTION_HEAD_DIMS (64: SDXL; 40, 80, 160: SD 1.5; 512: the
+    VAE decoder -- FP16 output only: with `scale_inv` the library answers MIXDQ_ERR_SHAPE, as it does to `_cfg != 0`).
     `softmax_scale` defaults to D ** -0.5.  Returns fp16 [B, Tq, C], or — when `scale_inv`/`zero_point`
     (to_out.0's activation quantizer) are given — its int8 quantization.
     `_prefetch`: up to 16 GPU tensors (the weights of the layers behind this attention) that payload
@@ -1277,7 +1299,7 @@ def attention_f16(q, k, v, heads, scale_inv=None, zero_point=None, softmax_scale
     B, Tq, C = q.shape
     _check(k.shape == v.shape and k.shape[0] == B and k.shape[2] == C, "q/k/v shapes disagree")
     D = C // heads if heads > 0 else 0
-    _check(C == heads * D and D in ATTENTION_HEAD_DIMS, "head_dim must be 64, 40, 80 or 160")
+    _check(C == heads * D and D in ATTENTION_HEAD_DIMS, "head_dim must be 64, 40, 80, 160 or 512")
     quant = scale_inv is not None
     # (measurement only) recorded as ("attention", (B * heads * Tq, Tkv, D, D)): 4 * M * N * K FLOPs
     _record("attention", B * heads * Tq, k.shape[1], D, D, False, attention_f16,

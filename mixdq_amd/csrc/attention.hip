@@ -1,4 +1,4 @@
-// FP16 attention core for gfx950 (head_dim 64; 40, 80 and 160 in attn_hd_kernel below): O = softmax(Q K^T * scale) V,
+// FP16 attention core for gfx950 (head_dim 64; 40, 80 and 160 in attn_hd_kernel, 512 in attn_512_kernel below): O = softmax(Q K^T * scale) V,
 // flash-style.
 //
 // The reference keeps the attention matmuls in FP16 in both of its paths (SURVEY.md §0:
@@ -1193,6 +1193,233 @@ int launch_attn_hd_form(AttnParams& p, int batch, int heads, int tq, int force, 
   return big ? launch_attn_hd<D, 4>(p, batch, quant, a4, stream) : launch_attn_hd<D, 2>(p, batch, quant, a4, stream);
 }
 
+// ---- head width 512 (the VAE decoder's mid-block attention: one head over all H x W tokens) ---------------------
+// AttnHd<512> does not exist: a wave that owns 32 query rows x 512 columns of O^T needs 256 accumulator registers
+// next to 128 of Q fragments, and a 64-key K | V stage is 128 KB.  Here the FOUR waves of a workgroup share ONE
+// block of 32 query rows and split D: wave w holds columns 128 w .. 128 w + 127 of Q, K, V and O.  Per tile of 32
+// keys (K | V = 64 KB, two stages by LDS-DMA):
+//   partial S^T  wave w: K[:, its slice] Q^T[its slice], 8 k-steps of v_mfma_f32_32x32x16_f16 (FP32)
+//   S^T          the four partials meet in LDS (16 KB) and EVERY wave adds them in the fixed order
+//                ((p0 + p1) + p2) + p3: the four waves hold the same bits
+//   softmax      attn_hd_kernel's, run by each wave on those same bits: mask, row maximum, FP32 exponentials rounded
+//                to FP16, rescale
+//   O^T, sums    wave w: its four 32-column tiles of O^T += V^T[its slice] P^T, and the row sums from the rounded P
+// Register use: 64 (O^T) + 32 (Q) + 16 (sums) + the tile's transients.  LDS: 2 x 64 KB + 16 KB = 144 KB, one
+// workgroup per CU.  Images: 1024-B rows (a whole key), 16-B chunks XOR-swizzled by the SOURCE address of the DMA:
+//   K  chunk ^ (key & 15)          the 16 rows of a ds_read_b128 lane group -> 16 distinct bank quads
+//   V  chunk ^ 4 * (key & 3)       the four rows of a ds_read_b64_tr_b16 half-wave (64 B each) -> four disjoint ranges
+// ONE launch geometry (32 queries per workgroup, whatever the image or the batch): a batch row gets the bits it gets
+// alone.  FP16 output only.
+struct Attn512 {
+  static constexpr int D = 512, KEYS = 32, ROW = 2 * D;
+  static constexpr int TILE = KEYS * ROW;            // one K (or V) tile: 32 KB
+  static constexpr int SB = 2 * TILE;                // one stage: K image then V image
+  static constexpr int XOFF = 2 * SB;                // the partial-score exchange: [wave][4][64 lanes] x 16 B
+  static constexpr int XB = 4 * 4 * 64 * 16;
+  static constexpr int PO = 256 + 16;                // output staging row: a wave's 128 columns + padding
+  static constexpr int SMEM = XOFF + XB;
+  static_assert(SMEM <= 160 * 1024 && 4 * 32 * PO <= SB, "LDS is 160 KiB per CU; the output staging overlays stage 0");
+};
+
+template <int OFF>
+__device__ __forceinline__ void lds_write128f_imm(unsigned addr, const v4f& d) {
+  asm volatile("ds_write_b128 %0, %1 offset:%2" ::"v"(addr), "v"(d), "n"(OFF) : "memory");
+}
+template <int OFF>
+__device__ __forceinline__ void lds_read128f_imm(v4f& d, unsigned addr) {
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF) : "memory");
+}
+
+__global__ __launch_bounds__(256) void attn_512_kernel(const AttnParams p) {
+  using G = Attn512;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l32 = lane & 31, hh = lane >> 5;
+  const int blk = p.xcd_map ? attn_block_of(blockIdx.x, p.attn_blocks) : (int)blockIdx.x;
+  const int qb = blk % p.qblocks;
+  const int head = (blk / p.qblocks) % p.heads;
+  const int b = blk / (p.qblocks * p.heads);
+  const int q0 = qb * 32;                            // the four waves share these 32 query rows
+  const int ntiles = (p.tkv + G::KEYS - 1) / G::KEYS;
+  const int dcol = head * G::D + wave * 128;         // first column of this wave's slice
+
+  // Q^T fragments of the slice: lane's query row, d = 128 w + 16 ks + 8 h .. + 7
+  v8h qf[8];
+  {
+    const int qr = min(q0 + l32, p.tq - 1);
+    const __half* qrow = p.q + b * p.q_bs + (long)qr * p.q_rs + dcol + hh * 8;
+#pragma unroll
+    for (int ks = 0; ks < 8; ++ks) qf[ks] = *reinterpret_cast<const v8h*>(qrow + ks * 16);
+  }
+
+  // LDS-DMA staging: one wave-instruction fills one key row (64 chunks), lane -> slot; the slot holds chunk
+  // slot ^ swizzle(key), so the SOURCE address carries the permutation.  Waves 0, 1 stage K (16 keys each),
+  // waves 2, 3 stage V.  Keys past the end re-read the last key: finite data whose scores are masked to -inf.
+  const bool stage_v = wave >= 2;
+  const char* sbase = reinterpret_cast<const char*>((stage_v ? p.v + b * p.v_bs : p.k + b * p.k_bs) + head * G::D);
+  const unsigned srs = 2u * (unsigned)(stage_v ? p.v_rs : p.k_rs);
+  const int last_key = p.tkv - 1;
+  auto stage = [&](int buf, int t) {
+    char* dst = smem + buf * G::SB + wave * 16 * G::ROW;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int row = (wave & 1) * 16 + i;           // key row within the tile (wave-uniform)
+      const int sw = stage_v ? (row & 3) << 2 : row & 15;
+      const unsigned key = (unsigned)min(t * G::KEYS + row, last_key);
+      glds16(sbase + (key * srs + (unsigned)((lane ^ sw) * 16)), dst + i * G::ROW);
+    }
+  };
+
+  const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
+  const int q4 = (lane & 15) >> 2, pp = lane & 3, g16 = (lane >> 4) & 1;
+  unsigned k_a[8], v_a[4];
+#pragma unroll
+  for (int ks = 0; ks < 8; ++ks)                     // row l32, chunk 16 w + 2 ks + h
+    k_a[ks] = lds0 + l32 * G::ROW + ((16 * wave + ((2 * ks + hh) ^ (l32 & 15))) << 4);
+#pragma unroll
+  for (int db = 0; db < 4; ++db)                     // rows 4 h + q4 (+ 16 u, + 8), 64-B unit 4 w + db
+    v_a[db] = lds0 + G::TILE + (4 * hh + q4) * G::ROW + 256 * wave + 64 * (db ^ q4) + 32 * g16 + 8 * pp;
+  const unsigned x_w = lds0 + G::XOFF + wave * 4096 + lane * 16, x_r = lds0 + G::XOFF + lane * 16;
+
+  v16f o[4], lsum;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+#pragma unroll
+    for (int db = 0; db < 4; ++db) o[db][i] = 0.f;
+    lsum[i] = 0.f;
+  }
+  float m_i = -INFINITY;
+  const float c = p.scale_log2;
+  v8h ones;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) ones[i] = (_Float16)1.f;
+
+  stage(0, 0);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  for (int t = 0; t < ntiles; ++t) {
+    const unsigned sbuf = (unsigned)(t & 1) * G::SB;
+    if (t + 1 < ntiles) stage((t + 1) & 1, t + 1);   // its stage was last read in tile t - 1 (barrier since)
+    // ---- this wave's partial scores over its 128 columns ----
+    v16f sc;
+    {
+      v8h kf[8];
+#pragma unroll
+      for (int ks = 0; ks < 8; ++ks) lds_read128_imm<0>(kf[ks], k_a[ks] + sbuf);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+      for (int ks = 0; ks < 8; ++ks) asm volatile("" : "+v"(kf[ks]));
+#pragma unroll
+      for (int i = 0; i < 16; ++i) sc[i] = 0.f;
+#pragma unroll
+      for (int ks = 0; ks < 8; ++ks) sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[ks], qf[ks], sc, 0, 0, 0);
+    }
+    // ---- the four partials meet: every wave adds them in the order w = 0, 1, 2, 3 ----
+    // (the stores are inline asm, which the compiler's hazard pass does not see: an LDS instruction that reads the
+    // result of a 16-pass MFMA needs 19 idle states behind it)
+    asm volatile("s_nop 15\n\ts_nop 3" : "+v"(sc));
+    static_for<0, 4>([&](auto gc) {
+      constexpr int g = decltype(gc)::value;
+      lds_write128f_imm<g * 1024>(x_w, v4f{sc[4 * g], sc[4 * g + 1], sc[4 * g + 2], sc[4 * g + 3]});
+    });
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // (the DMA of tile t + 1 stays in flight)
+    {
+      v4f part[4][4];
+      static_for<0, 16>([&](auto ic) {
+        constexpr int w = decltype(ic)::value >> 2, g = decltype(ic)::value & 3;
+        lds_read128f_imm<w * 4096 + g * 1024>(part[w][g], x_r);
+      });
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+      for (int i = 0; i < 16; ++i) asm volatile("" : "+v"(part[i >> 2][i & 3]));
+#pragma unroll
+      for (int g = 0; g < 4; ++g)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          sc[4 * g + j] = __fadd_rn(__fadd_rn(__fadd_rn(part[0][g][j], part[1][g][j]), part[2][g][j]), part[3][g][j]);
+    }
+    if (t == ntiles - 1 && (p.tkv & (G::KEYS - 1)) != 0) {   // mask the absent keys
+      const int lim = p.tkv - t * G::KEYS - 4 * hh;
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        if (8 * (r >> 2) + (r & 3) >= lim) sc[r] = -INFINITY;
+    }
+    float mx = sc[0];
+#pragma unroll
+    for (int r = 1; r < 16; ++r) mx = fmaxf(mx, sc[r]);
+    mx = half_max(mx);
+    const float m_new = fmaxf(m_i, mx);
+    const bool grew = m_new > m_i;
+    const float mc = m_new * c;
+    v8h pf[2];
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+      pf[r >> 3][r & 7] = (_Float16)__builtin_amdgcn_exp2f(__builtin_fmaf(sc[r], c, -mc));
+    if (__builtin_amdgcn_ballot_w64(grew)) {
+      const float alpha = __builtin_amdgcn_exp2f((m_i - m_new) * c);
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+#pragma unroll
+        for (int db = 0; db < 4; ++db) o[db][i] *= alpha;
+      }
+      lsum[0] *= alpha;
+    }
+    m_i = m_new;
+    // ---- O^T += V^T P^T over this wave's 128 columns, 16 keys at a time (k-slot order of attn_pv_tile) ----
+    static_for<0, 2>([&](auto uc) {
+      constexpr int u = decltype(uc)::value;
+      VFrag vf[4];
+#pragma unroll
+      for (int db = 0; db < 4; ++db)
+        tr_read2_at<16 * u * G::ROW, (16 * u + 8) * G::ROW>(vf[db], v_a[db] + sbuf);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+      for (int db = 0; db < 4; ++db) asm volatile("" : "+v"(vf[db].h));
+#pragma unroll
+      for (int db = 0; db < 4; ++db)
+        o[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[db].h, pf[u], o[db], 0, 0, 0);
+      lsum = __builtin_amdgcn_mfma_f32_32x32x16_f16(ones, pf[u], lsum, 0, 0, 0);
+    });
+    // tile t + 1 has landed (every wave's pieces); every wave is done with tile t's stage and with the exchange
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+  }
+
+  // ---- normalise, stage through LDS (wave-private rows of PO bytes), store whole 16-B pieces ----
+  const float inv = 1.f / lsum[0];
+  char* Os = smem + wave * (32 * G::PO);
+#pragma unroll
+  for (int db = 0; db < 4; ++db)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      v4h w;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) w[j] = (_Float16)(o[db][4 * g + j] * inv);
+      *reinterpret_cast<v4h*>(Os + l32 * G::PO + (32 * db + 8 * g + 4 * hh) * 2) = w;
+    }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {                      // 32 rows x 16 chunks
+    const int id = lane + 64 * i, row = id >> 4, ch = id & 15;
+    if (q0 + row >= p.tq) continue;
+    const uint4 w = *reinterpret_cast<const uint4*>(Os + row * G::PO + ch * 16);
+    const long off = b * p.o_bs + (long)(q0 + row) * p.o_rs + dcol + ch * 8;
+    *reinterpret_cast<uint4*>(reinterpret_cast<__half*>(p.out) + off) = w;
+  }
+}
+
+int launch_attn_512(AttnParams& p, int batch, hipStream_t stream) {
+  p.qblocks = (p.tq + 31) / 32;
+  if ((long)p.qblocks * p.heads * batch > 0x7fffffffl) return MIXDQ_ERR_INVALID_ARG;
+  p.attn_blocks = p.qblocks * p.heads * batch;
+  p.pf_blocks = 0; p.n_pf = 0;                       // no payload workgroups at this width
+  static bool seen[64] = {};
+  if (const int st = lds_opt_in(reinterpret_cast<const void*>(&attn_512_kernel), Attn512::SMEM, seen)) return st;
+  hipLaunchKernelGGL(attn_512_kernel, dim3(p.attn_blocks), dim3(256), Attn512::SMEM, stream, p);
+  return launch_status();
+}
+
 }  // namespace
 }  // namespace mixdq
 
@@ -1212,7 +1439,9 @@ static int attention_f16_impl(const void* q, const void* k, const void* v, void*
   if (batch < 0 || heads <= 0 || tq < 0 || tkv <= 0) return MIXDQ_ERR_INVALID_ARG;
   if ((out_scale_inv == nullptr) != (out_zero_point == nullptr)) return MIXDQ_ERR_INVALID_ARG;
   const bool hd = head_dim == 40 || head_dim == 80 || head_dim == 160;   // attn_hd_kernel's widths
-  if (head_dim != kHeadDim && !hd) return MIXDQ_ERR_SHAPE;
+  const bool w512 = head_dim == Attn512::D;          // attn_512_kernel: the VAE decoder's head, FP16 output only
+  if (head_dim != kHeadDim && !hd && !w512) return MIXDQ_ERR_SHAPE;
+  if (w512 && out_scale_inv != nullptr) return MIXDQ_ERR_SHAPE;
   if (batch == 0 || tq == 0) return MIXDQ_OK;       // nothing to write (pointers may be null)
   if (!q || !k || !v || !out) return MIXDQ_ERR_INVALID_ARG;
   const bool quant = out_scale_inv != nullptr;
@@ -1243,7 +1472,7 @@ static int attention_f16_impl(const void* q, const void* k, const void* v, void*
   static const int xcd_on = [] { const char* e = getenv("MIXDQ_ATTN_XCD"); return !(e && e[0] == '0'); }();   // A/B runs
   p.xcd_map = xcd_on;
   for (int i = 0; i < 16; ++i) { p.pf_ptr[i] = nullptr; p.pf_bytes[i] = 0; }
-  for (int i = 0; i < (hd ? 0 : n_pf); ++i) {     // (no payload at the other widths: ignored)
+  for (int i = 0; i < (hd || w512 ? 0 : n_pf); ++i) {     // (no payload at the other widths: ignored)
     if (!pf_ptrs[i] || pf_bytes[i] < 16) continue;
     // the payload is a hint and must never fail a launch: a range that does not start on a 16-byte boundary
     // (a weight view at an odd offset) is rounded inward to the part that 16-byte loads can read
@@ -1271,6 +1500,7 @@ static int attention_f16_impl(const void* q, const void* k, const void* v, void*
   // and, merging two partial softmaxes, it made a batch-1 result differ in its last bits from the
   // same image inside a batch.)
   int force = (flags >> 8) & 0xff;               // 4 / 2: waves per workgroup of the pipelined kernel; 1: the short-key kernel
+  if (w512) return force == 0 ? launch_attn_512(p, batch, stream) : MIXDQ_ERR_SHAPE;   // one form
   if (hd) {
     // form 1: attn_hd_short_kernel, every key staged once (tkv <= 128: the 77-key cross-attention) -- the automatic
     // choice there, from the key count alone (MIXDQ_ATTN_HD_SHORT=0 keeps forms 2 / 4 for A/B runs); forms 2 / 4:

@@ -852,6 +852,15 @@ extern "C" int mixdq_conv2d_f16(const void* X_f16, const void* Wt_f16, const voi
   p.H = H; p.W = W; p.C = 2 * C; p.R = R; p.S = S; p.P = P; p.Q = Q; p.stride = stride; p.pad = pad;
   p.res = (const __half*)residual_f16_or_null;
   p.res_div = residual_row_div > 0 ? residual_row_div : 1;
+  if (flags & MIXDQ_FLAG_UPSAMPLE2X) {
+    // X is [N, H / 2, W / 2, C]; the MFMA tiles' gather reads pixel (y >> 1, x >> 1): 3x3 / stride 1 / pad 1 only,
+    // and only where dispatch_f16 takes the tiles (the one-output-per-thread fallback has no such gather)
+    const bool tiles = (2 * C) % 16 == 0 && K % 4 == 0 &&
+                       !(((uintptr_t)X_f16 | (uintptr_t)Wt_f16 | (uintptr_t)D_f16 | (uintptr_t)residual_f16_or_null) & 15) &&
+                       !((uintptr_t)bias_f16_or_null & 7);
+    if (R != 3 || S != 3 || stride != 1 || pad != 1 || (H & 1) || (W & 1) || !tiles) return MIXDQ_ERR_SHAPE;
+    p.ups = 1;
+  }
   return dispatch_f16<true>(p, (hipStream_t)stream, (flags >> 8) & 0xff);
 }
 

@@ -111,6 +111,10 @@ struct IgemmParams {
   int* ln_cnt;           // [0]: epoch (launches completed on this workspace), [1]: departures of the running one,
                          // [2]: sticky error word (the tag of a launch in which a record never arrived; 0 = none)
   int ln_local;          // 1: row blocks are laid out XCD by XCD and the records are first looked for in that L2
+  // CONV gather through a nearest 2x upsampling (mixdq_conv2d_f16 + MIXDQ_FLAG_UPSAMPLE2X): ups = 1: A is
+  // [N, H / 2, W / 2, C] and input pixel (y, x) of the H x W image is read from (y >> 1, x >> 1); the in-image
+  // test stays against H and W.  0 everywhere else (a shift by nothing).
+  int ups;
 };
 
 template <int BK>
@@ -678,7 +682,7 @@ void igemm_kernel(MIXDQ_IGEMM_HEAD_PARAMS const IgemmParams p_in) {
       const int64_t img = m / pq;
       const int rem = (int)(m - img * pq);
       const int pp = rem / p.Q, qq = rem - pp * p.Q;
-      a_base[j] = p.A + img * ((int64_t)p.H * p.W * p.C);
+      a_base[j] = p.A + img * ((int64_t)(p.H >> p.ups) * (p.W >> p.ups) * p.C);
       a_h0[j] = a_ok[j] ? pp * p.stride - p.pad : -(1 << 28);
       a_w0[j] = qq * p.stride - p.pad;
       const int kc = lc * 16;
@@ -761,7 +765,7 @@ void igemm_kernel(MIXDQ_IGEMM_HEAD_PARAMS const IgemmParams p_in) {
         const int hh = a_h0[j] + a_r[j], ww = a_w0[j] + a_s[j];
         const bool ok = (unsigned)hh < (unsigned)p.H && (unsigned)ww < (unsigned)p.W &&
                         a_r[j] < p.R;
-        src = ok ? (const void*)(a_base[j] + ((int64_t)(hh * p.W + ww) * p.C + a_c[j]))
+        src = ok ? (const void*)(a_base[j] + ((int64_t)((hh >> p.ups) * (p.W >> p.ups) + (ww >> p.ups)) * p.C + a_c[j]))
                  : (const void*)zero;
         a_c[j] += BK;
         while (a_c[j] >= p.C) {

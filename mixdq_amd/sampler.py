@@ -211,3 +211,9 @@ class Sampler:
         for _ in range(self.n_steps):
             self._graph.replay()
         return self._x.clone()
+
+    def sample_image(self, vae, noise, encoder_hidden_states, added_cond_kwargs=None, step_noise=None):
+        """sample(), then `vae.decode` (a mixdq_amd.vae.VAEDecoder, eager or under hip_graph_opt) of its latents on
+        the same stream: nothing waits for the GPU in between.  Returns (FP32 latents, FP16 image [B, 3, 8H, 8W])."""
+        latents = self.sample(noise, encoder_hidden_states, added_cond_kwargs, step_noise)
+        return latents, vae.decode(latents)

@@ -607,7 +607,8 @@ class Attention(nn.Module):
         out = self.to_out[0]
         C = q.shape[-1]
         D = C // self.heads
-        ok = (C == self.heads * D and D in _C.ATTENTION_HEAD_DIMS
+        from mixdq_amd.nn.glue import ATTENTION_HEAD_DIMS      # the UNets' widths (INT8 output; not the VAE's 512)
+        ok = (C == self.heads * D and D in ATTENTION_HEAD_DIMS
               and all(_fusable_f16(t) and t.dim() == 3 and t.stride(-1) == 1
                       and t.stride(0) % 8 == 0 and t.stride(1) % 8 == 0
                       and t.data_ptr() % 16 == 0 for t in (q, k, v)))

@@ -1,0 +1,95 @@
+"""Host tests of mixdq_amd.vae (no GPU): the decoder's parameter inventory against diffusers' AutoencoderKL, the state
+dict round trip, the padded conv_out and to_uint8."""
+import torch
+
+from mixdq_amd import vae as V
+
+SMALL = dict(V.VAE_SDXL_CONFIG, block_out_channels=(32, 64, 128, 512), layers_per_block=1, norm_num_groups=8)
+
+
+def _expected_names(block_out=(128, 256, 512, 512), layers=2):
+    """The issue's name list, expanded by hand: which ResNets carry a conv_shortcut follows from the channel plan."""
+    res = ("norm1", "conv1", "norm2", "conv2")
+    mods = ["post_quant_conv", "decoder.conv_in", "decoder.conv_norm_out", "decoder.conv_out"]
+    mods += [f"decoder.mid_block.resnets.{j}.{m}" for j in (0, 1) for m in res]
+    mods += [f"decoder.mid_block.attentions.0.{m}" for m in ("group_norm", "to_q", "to_k", "to_v", "to_out.0")]
+    rev = block_out[::-1]
+    for i in range(len(rev)):
+        cin = rev[max(i - 1, 0)]
+        for j in range(layers + 1):
+            mods += [f"decoder.up_blocks.{i}.resnets.{j}.{m}" for m in res]
+            if j == 0 and cin != rev[i]:
+                mods.append(f"decoder.up_blocks.{i}.resnets.{j}.conv_shortcut")
+        if i != len(rev) - 1:
+            mods.append(f"decoder.up_blocks.{i}.upsamplers.0.conv")
+    return {m + s for m in mods for s in (".weight", ".bias")}
+
+
+def test_sdxl_decoder_has_diffusers_parameter_counts_and_names():
+    vae = V.build_vae_decoder(V.VAE_SDXL_CONFIG)
+    counts = V.parameter_counts(vae)
+    assert counts["decoder"] == 49_490_179 and counts["post_quant_conv"] == 20
+    names = set(vae.state_dict().keys())
+    assert names == _expected_names() == set(V.state_dict_names())
+    # the two ResNets whose channel count changes, and only they, have a shortcut conv
+    assert {n for n in names if "conv_shortcut.weight" in n} == {
+        "decoder.up_blocks.2.resnets.0.conv_shortcut.weight", "decoder.up_blocks.3.resnets.0.conv_shortcut.weight"}
+    assert vae.state_dict()["decoder.mid_block.attentions.0.to_q.weight"].shape == (512, 512)
+    assert all(p.dtype == torch.float16 for p in vae.parameters())
+
+
+def test_configs():
+    assert V.VAE_SDXL_CONFIG["scaling_factor"] == 0.13025 and V.VAE_SD15_CONFIG["scaling_factor"] == 0.18215
+    for k in ("block_out_channels", "layers_per_block", "latent_channels", "norm_num_groups"):
+        assert V.VAE_SD15_CONFIG[k] == V.VAE_SDXL_CONFIG[k]
+    assert V.VAE_SDXL_CONFIG["block_out_channels"] == (128, 256, 512, 512)
+    assert (V.VAE_SDXL_CONFIG["layers_per_block"], V.VAE_SDXL_CONFIG["latent_channels"],
+            V.VAE_SDXL_CONFIG["norm_num_groups"]) == (2, 4, 32)
+    assert set(V.build_vae_decoder(SMALL).state_dict()) == _expected_names((32, 64, 128, 512), 1) == set(V.state_dict_names(SMALL))
+
+
+def test_load_state_dict_round_trips_and_drops_the_derived_weights():
+    a, b = V.build_vae_decoder(SMALL, seed=1), V.build_vae_decoder(SMALL, seed=2)
+    sd = a.state_dict()
+    assert not torch.equal(sd["decoder.conv_in.weight"], b.state_dict()["decoder.conv_in.weight"])
+    qkv_before = b._derived()["qkv"][0].clone()
+    missing, unexpected = b.load_state_dict(sd)
+    assert not missing and not unexpected
+    got = b.state_dict()
+    assert set(got) == set(sd) and all(torch.equal(got[k], sd[k]) for k in sd)
+    attn = b.decoder.mid_block.attentions[0]
+    w, bias = b._derived()["qkv"]
+    assert not torch.equal(w, qkv_before)
+    assert torch.equal(w, torch.cat([attn.to_q.weight, attn.to_k.weight, attn.to_v.weight])) and w.shape == (1536, 512)
+    assert torch.equal(bias, torch.cat([attn.to_q.bias, attn.to_k.bias, attn.to_v.bias]))
+    # z / scaling_factor is folded into post_quant_conv's 4 x 4 weight, in FP32
+    pw, pb = b._derived()["post_quant"]
+    assert torch.equal(pw, (b.post_quant_conv.weight.float() / 0.13025).half()) and torch.equal(pb, b.post_quant_conv.bias)
+
+
+def test_conv_out_is_padded_to_four_channels_and_sliced_back():
+    vae = V.build_vae_decoder(SMALL)
+    w4, b4 = vae.padded_conv_out()
+    w, b = vae.decoder.conv_out.weight, vae.decoder.conv_out.bias
+    assert tuple(w.shape) == (3, 32, 3, 3) and tuple(w4.shape) == (4, 32, 3, 3) and tuple(b4.shape) == (4,)
+    assert torch.equal(w4[:3], w) and torch.equal(b4[:3], b)
+    assert not w4[3].any() and not b4[3].any()
+    assert w4.is_contiguous(memory_format=torch.channels_last)
+    # the conv on the padded weight, cut to three channels, is the conv (FP32 on the CPU: the op itself is not at issue)
+    x = torch.randn(1, 32, 5, 6, generator=torch.Generator().manual_seed(3))
+    full = torch.nn.functional.conv2d(x, w4.float(), b4.float(), padding=1)
+    assert torch.equal(full[:, :3], torch.nn.functional.conv2d(x, w.float(), b.float(), padding=1))
+    assert not full[:, 3].any()
+
+
+def test_to_uint8_known_values():
+    x = torch.tensor([-3.0, -1.0, -0.5, 0.0, 0.5, 1.0, 2.0, 1.0 / 255, -1.0 + 4.0 / 255])
+    assert V.to_uint8(x).tolist() == [0, 0, 64, 128, 191, 255, 255, 128, 2]
+    assert V.to_uint8(x.half()).dtype == torch.uint8 and V.to_uint8(torch.zeros(2, 3, 4, 4)).shape == (2, 3, 4, 4)
+
+
+def test_decode_refuses_what_it_cannot_run():
+    import pytest
+    vae = V.build_vae_decoder(SMALL)
+    with pytest.raises(RuntimeError, match="GPU tensor"):
+        vae.decode(torch.zeros(1, 4, 8, 8))
