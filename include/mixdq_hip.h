@@ -97,6 +97,20 @@ enum mixdq_flags {
      the caller then quantizes and runs the GEMM).  Together with MIXDQ_FLAG_W4: MIXDQ_ERR_INVALID_ARG.
      No reference counterpart: the reference stores its 2-bit layers as 4-bit (TODO in its loader). */
   MIXDQ_FLAG_W2 = 16,
+  /* mixdq_attention_f16[_prefetch] only: a causal mask -- query row i attends to keys 0 .. i (a text encoder's
+     self-attention).  Head width 64, tq == tkv <= 128, FP16 output (out_scale_inv == null) and bits 8..15 of flags 0 or
+     1: the launch is the short-key kernel's (one geometry whatever the batch: a batch row has the bits of the
+     sequence alone); anything else answers MIXDQ_ERR_SHAPE with nothing written.  Same arithmetic, in the same
+     order, as the unmasked launch: a masked score is -inf before the row maximum is taken. */
+  MIXDQ_FLAG_CAUSAL = 32,
+  /* mixdq_linear_f16 only: an activation in the epilogue.  With h = f16(acc + bias) -- what the unflagged launch
+     stores -- the launch stores f16(act(f32(h))), what a stock FP16 Linear followed by the activation computes:
+       MIXDQ_FLAG_ACT_GELU        act = mixdq_geluf (erf form): the value of mixdq_gelu_table at h
+       MIXDQ_FLAG_ACT_QUICK_GELU  act = mixdq_quick_geluf: x / (1 + exp(-(1.702 x)))     (include/mixdq_math.h)
+     Both together, or either with a residual: MIXDQ_ERR_INVALID_ARG.  Every other entry point refuses them
+     (MIXDQ_ERR_UNSUPPORTED). */
+  MIXDQ_FLAG_ACT_GELU = 64,
+  MIXDQ_FLAG_ACT_QUICK_GELU = 128,
   /* bits 8..15: force a kernel configuration id (tuning / tests); 0 = automatic */
   /* A 4-bit activation quantizer in slot i (i = 0, 1, 2: the i-th quantizer of a launch; entry points with one
      quantizer use slot 0): the INT8 operand is the int8 quantizer with a narrower clamp,
@@ -112,6 +126,7 @@ enum mixdq_flags {
   MIXDQ_FLAG_A4_2 = 1 << 18
 };
 #define MIXDQ_FLAG_A4_ANY (MIXDQ_FLAG_A4_0 | MIXDQ_FLAG_A4_1 | MIXDQ_FLAG_A4_2)
+#define MIXDQ_FLAG_ACT_ANY (MIXDQ_FLAG_ACT_GELU | MIXDQ_FLAG_ACT_QUICK_GELU)
 
 const char* mixdq_status_string(int status);
 int mixdq_abi_version(void);
@@ -441,7 +456,8 @@ int mixdq_qlinear_w8a8_geglu(const int8_t* A, const int8_t* W_interleaved, const
  * out: fp16 rows (out_scale_inv == null), or — fused producer of to_out.0's INT8 operand — int8
  * rows q = sat8(rint(f16_out * scale_inv + zero_point)) (same arithmetic as mixdq_quantize_f16_i8).
  * flags: MIXDQ_FLAG_UNFUSED selects the unfused quantize variant; bits 8..15 force the workgroup
- * shape (4 = 128 query rows, 2 = 64; 1 = the short-key kernel, at every width: MIXDQ_ERR_SHAPE when tkv > 128). */
+ * shape (4 = 128 query rows, 2 = 64; 1 = the short-key kernel, at every width: MIXDQ_ERR_SHAPE when tkv > 128);
+ * MIXDQ_FLAG_CAUSAL: see the flag. */
 int mixdq_attention_f16(const void* q_f16, const void* k_f16, const void* v_f16, void* out,
                         int batch, int heads, int head_dim, int tq, int tkv,
                         int64_t q_batch_stride, int64_t q_row_stride,
@@ -481,7 +497,10 @@ int mixdq_attention_f16_prefetch(const void* q_f16, const void* k_f16, const voi
  * A [M,K], W [N,K], D [M,N] row-major fp16; conv: X [N,H,W,C], Wt [K,R,S,C], D [N,P,Q,K].
  * K % 8 == 0 (conv: C % 8 == 0) and N % 4 == 0 run on MFMA tiles, anything else (conv_in: C = 4)
  * on a one-output-per-thread kernel.  flags: bits 8..15 force a tile configuration; mixdq_conv2d_f16 also takes
- * MIXDQ_FLAG_UPSAMPLE2X (see the flag: the conv of Upsample2D without the upsampled tensor). */
+ * MIXDQ_FLAG_UPSAMPLE2X (see the flag: the conv of Upsample2D without the upsampled tensor), mixdq_linear_f16
+ * MIXDQ_FLAG_ACT_GELU / MIXDQ_FLAG_ACT_QUICK_GELU (see the flags: the activation of an MLP's first layer, applied to
+ * the rounded FP16 value where the tile is stored -- the same on every tile configuration and on the
+ * one-output-per-thread kernel). */
 int mixdq_linear_f16(const void* A_f16, const void* W_f16, const void* bias_f16_or_null,
                      void* D_f16, int64_t M, int N, int K, const void* residual_f16_or_null,
                      int64_t residual_row_div, int flags, mixdq_stream_t stream);
@@ -489,6 +508,16 @@ int mixdq_conv2d_f16(const void* X_f16, const void* Wt_f16, const void* bias_f16
                      void* D_f16, int N, int H, int W, int C, int K, int R, int S, int stride,
                      int pad, const void* residual_f16_or_null, int64_t residual_row_div,
                      int flags, mixdq_stream_t stream);
+
+/* Token + position embedding of a text encoder:
+ *   out[b, t, :] = f16_rn(f32(tok[ids[b, t]]) + f32(pos[t]))       ids int32 [B, T], tok fp16 [V, C], pos fp16 [>= T, C]
+ * An id outside [0, V) is CLAMPED into the range (ids < 0 read row 0, ids >= V row V - 1): the kernel cannot report
+ * an error, and a caller that wants to stay asynchronous cannot look at the ids.  C % 8 == 0 and 16-byte aligned
+ * tok / pos / out (16-byte vector loads and stores): MIXDQ_ERR_ALIGNMENT otherwise; null pointers, negative sizes,
+ * V < 1: MIXDQ_ERR_INVALID_ARG.  B * T == 0 writes nothing.  No reference counterpart (the reference reaches the
+ * text encoders through diffusers' pipeline). */
+int mixdq_embed_tokens_f16(const int32_t* ids, const void* tok_f16, const void* pos_f16, void* out_f16, int B, int T,
+                           int C, int V, mixdq_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Sampler step: classifier-free guidance + scheduler update + the UNet's next input, and the step state kept on

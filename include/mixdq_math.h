@@ -98,6 +98,10 @@ MIXDQ_HD float mixdq_geluf(float x) {
   return 0.5f * x * (1.0f + mixdq_erff(x * 0.70710678118654752440f));
 }
 
+/* quick-GELU (CLIP ViT-L's activation): x * sigmoid(1.702 x) as x / (1 + exp(-(1.702 x))) -- the product rounded,
+ * negated, one exp, the sum rounded, a correctly rounded division. */
+MIXDQ_HD float mixdq_quick_geluf(float x) { return x / (1.0f + mixdq_expf(-(1.702f * x))); }
+
 /* ---- sampler step (mixdq_sampler_step, csrc/sampler.hip): classifier-free guidance + the affine scheduler
  * update.  Every operation is one IEEE binary32 round-to-nearest +, - or *, never contracted: on the device the
  * _rn intrinsics (which the compiler may not fuse), on a host compiler plain operators under -ffp-contract=off.

@@ -134,6 +134,8 @@ IGEMM_WAVES = {1: (2, 2, 1, 32), 3: (2, 2, 1, 32), 4: (2, 2, 1, 32), 13: (4, 2, 
 FLAG_W4 = 2   # MIXDQ_FLAG_W4: the weight tensor holds packed signed 4-bit values
 FLAG_W2 = 16  # MIXDQ_FLAG_W2: the weight tensor holds packed signed 2-bit values ([N, K/4])
 FLAG_UPSAMPLE2X = 4   # MIXDQ_FLAG_UPSAMPLE2X: the conv input is read through a nearest 2x upsampling
+FLAG_CAUSAL = 32      # MIXDQ_FLAG_CAUSAL: attention_f16's causal mask (query row i attends to keys 0 .. i)
+FLAG_ACT = {None: 0, "gelu": 64, "quick_gelu": 128}   # MIXDQ_FLAG_ACT_GELU / _QUICK_GELU: linear_f16's epilogue activation
 # MIXDQ_FLAG_A4_<i>: quantizer slot i of a launch is a 4-bit one -- q clamped to [-128, -113] (Path A's [0, 15]
 # shifted by -128); the GEMMs read the operand unchanged
 FLAG_A4_0, FLAG_A4_1, FLAG_A4_2 = 1 << 16, 1 << 17, 1 << 18
@@ -949,10 +951,14 @@ _lib.mixdq_conv2d_f16.argtypes = [_vp] * 4 + [_i32] * 9 + [_vp, _i64, _i32, _vp]
 _lib.mixdq_conv2d_f16.restype = _i32
 
 
-def linear_f16(input, weight, bias=None, *, _residual=None, _cfg=0):
+def linear_f16(input, weight, bias=None, *, _residual=None, _cfg=0, _act=None):
     """F.linear(input, weight, bias) for fp16 GPU tensors: input [..., K], weight [N, K] -> [..., N],
     FP32 accumulation, bias added in FP32, one rounding to fp16; `_residual` (fp16, the output's
-    shape) is added after that rounding as a following torch half add would."""
+    shape) is added after that rounding as a following torch half add would.
+    `_act`: None, "gelu" (erf form) or "quick_gelu" (x * sigmoid(1.702 x)) -- the activation applied in the
+    epilogue to that rounded fp16 value, rounded to fp16 again: what the stock activation behind a stock FP16 Linear
+    computes (include/mixdq_math.h mixdq_geluf / mixdq_quick_geluf).  Not together with `_residual`."""
+    _check(_act in FLAG_ACT, f"_act should be None, 'gelu' or 'quick_gelu', got {_act!r}")
     _trace_w(weight)
     _check(input.is_cuda and input.dtype == torch.float16, "input should be an fp16 GPU tensor")
     _check(weight.dtype == torch.float16 and weight.device == input.device and weight.dim() == 2,
@@ -970,7 +976,7 @@ def linear_f16(input, weight, bias=None, *, _residual=None, _cfg=0):
     bs = None if bias is None else bias.contiguous()
     with torch.cuda.device(a.device):
         code = _lib.mixdq_linear_f16(a.data_ptr(), w.data_ptr(), _ptr(bs), D.data_ptr(), M, N, K,
-                                     _ptr(_residual), 1, int(_cfg) << 8, _stream())
+                                     _ptr(_residual), 1, (int(_cfg) << 8) | FLAG_ACT[_act], _stream())
     _status(code, "linear_f16")
     return D
 
@@ -1276,7 +1282,7 @@ ATTENTION_HEAD_DIMS = (40, 64, 80, 160, 512)
 
 
 def attention_f16(q, k, v, heads, scale_inv=None, zero_point=None, softmax_scale=None, _cfg=0, _prefetch=None,
-                  _abits=8):
+                  _abits=8, _causal=False):
     """FP16 attention core (the reference's get_attention_scores + bmm, quant_block.py:630-637).
 
     q [B, Tq, C], k/v [B, Tkv, C] fp16 with unit stride along C (column slices of a fused projection
@@ -1292,6 +1298,8 @@ def attention_f16(q, k, v, heads, scale_inv=None, zero_point=None, softmax_scale
     kernel (Tkv <= 128: every key of a head staged once), at every head width -- what `_cfg=0` picks for so few
     keys (MIXDQ_ATTN_SHORT=0 at width 64, MIXDQ_ATTN_HD_SHORT=0 at 40 / 80 / 160 keep the tiled kernel: A/B runs).
     `_cfg=1` with more keys is refused (MIXDQ_ERR_SHAPE).  Every form gives the same bits.
+    `_causal=True`: query row i attends to keys 0 .. i (MIXDQ_FLAG_CAUSAL: a text encoder's self-attention) -- head
+    width 64, Tq == Tkv <= 128, FP16 output, `_cfg` 0 or 1; anything else is refused (MIXDQ_ERR_SHAPE).
     """
     for t, n in ((q, "q"), (k, "k"), (v, "v")):
         _check(t.is_cuda and t.dtype == torch.float16 and t.dim() == 3 and t.stride(-1) == 1,
@@ -1304,7 +1312,8 @@ def attention_f16(q, k, v, heads, scale_inv=None, zero_point=None, softmax_scale
     # (measurement only) recorded as ("attention", (B * heads * Tq, Tkv, D, D)): 4 * M * N * K FLOPs
     _record("attention", B * heads * Tq, k.shape[1], D, D, False, attention_f16,
             (q, k, v, heads), dict(scale_inv=scale_inv, zero_point=zero_point,
-                                   softmax_scale=softmax_scale, _cfg=_cfg, _abits=_abits))     # (measured without the payload)
+                                   softmax_scale=softmax_scale, _cfg=_cfg, _abits=_abits,
+                                   _causal=_causal))     # (measured without the payload)
     out = torch.empty((B, Tq, C), dtype=torch.int8 if quant else torch.float16, device=q.device)
     sc = float(softmax_scale) if softmax_scale is not None else (0.125 if D == 64 else D ** -0.5)
     ctx = getattr(_TLS, "ctx", None)
@@ -1325,14 +1334,43 @@ def attention_f16(q, k, v, heads, scale_inv=None, zero_point=None, softmax_scale
                 q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, heads, D, Tq, k.shape[1],
                 q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1),
                 out.stride(0), out.stride(1), sc, _ptr(scale_inv), _ptr(zero_point), ptrs, sizes, len(pf),
-                FLAGS | (int(_cfg) << 8) | _aflag(_abits), _stream())
+                FLAGS | (int(_cfg) << 8) | _aflag(_abits) | (FLAG_CAUSAL if _causal else 0), _stream())
         else:
             code = _lib.mixdq_attention_f16(
                 q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, heads, D, Tq, k.shape[1],
                 q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1),
                 out.stride(0), out.stride(1), sc, _ptr(scale_inv), _ptr(zero_point),
-                FLAGS | (int(_cfg) << 8) | _aflag(_abits), _stream())
+                FLAGS | (int(_cfg) << 8) | _aflag(_abits) | (FLAG_CAUSAL if _causal else 0), _stream())
     _status(code, "attention_f16")
+    return out
+
+
+_lib.mixdq_embed_tokens_f16.argtypes = [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]
+_lib.mixdq_embed_tokens_f16.restype = _i32
+
+
+def embed_tokens_f16(ids, tok, pos):
+    """Token + position embedding of a text encoder (mixdq_embed_tokens_f16):
+    out[b, t, :] = fp16(fp32(tok[ids[b, t]]) + fp32(pos[t])).
+
+    ids: int32 [B, T] GPU tensor; tok: fp16 [V, C]; pos: fp16 [Tmax, C] with T <= Tmax; C % 8 == 0.  Returns fp16
+    [B, T, C].  An id outside [0, V) is clamped into the range (a negative id reads row 0, an id >= V row V - 1):
+    the kernel cannot report an error, and this layer does not read the ids back to check them -- that would wait
+    for the GPU and break a graph capture."""
+    _check(ids.is_cuda and ids.dtype == torch.int32 and ids.dim() == 2 and ids.is_contiguous(),
+           "ids should be a contiguous int32 [B, T] GPU tensor")
+    for t_, n in ((tok, "tok"), (pos, "pos")):
+        _check(t_.dtype == torch.float16 and t_.device == ids.device and t_.dim() == 2 and t_.is_contiguous(),
+               f"{n} should be a contiguous fp16 2-D tensor on the ids' device")
+    B, T = ids.shape
+    V, C = tok.shape
+    _check(pos.shape[1] == C and T <= pos.shape[0], "pos should be [Tmax, C] with T <= Tmax")
+    _check(V >= 1 and C % 8 == 0, "tok should be [V >= 1, C] with C % 8 == 0")
+    out = torch.empty((B, T, C), dtype=torch.float16, device=ids.device)
+    with torch.cuda.device(ids.device):
+        code = _lib.mixdq_embed_tokens_f16(ids.data_ptr(), tok.data_ptr(), pos.data_ptr(), out.data_ptr(), B, T, C, V,
+                                           _stream())
+    _status(code, "embed_tokens_f16")
     return out
 
 

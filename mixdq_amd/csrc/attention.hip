@@ -515,8 +515,15 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2, 2
 // tile by tile, unpipelined, exactly the sequence of the fused epilogue in igemm.hip -- in <= 128
 // registers: four workgroups per CU, 32 KB of LDS each.  Bit-identical to attn_fwd_kernel
 // (tests/test_attention_gpu.py).
-template <bool QUANT, bool A4 = false>
+// CAUSAL (MIXDQ_FLAG_CAUSAL: tq == tkv, FP16 output): beside the absent keys, a score whose key lies behind the
+// lane's query row becomes -inf before the row maximum is taken; everything else is the unmasked sequence.  Key 0
+// is admitted by every row, so tile 0 always leaves a finite maximum; a row below 64 masks all of tile 1, which
+// then contributes mx = -inf: m_new == m_i (not grown; alpha, if another lane makes the wave take that branch, is
+// exp2(0) = 1), every P is exp2(-inf) = 0, and o / lsum get +0 products added -- unchanged (an accumulator that
+// started at +0 is never -0).  A wave whose 32 rows are all below 64 therefore skips tile 1 with the same bits.
+template <bool QUANT, bool A4 = false, bool CAUSAL = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void attn_short_kernel(const AttnParams p) {
+  static_assert(!CAUSAL || !QUANT, "the causal launch stores FP16");
   MIXDQ_ARGS_NOW(p.q, p.k, p.v, p.out, p.q_bs, p.q_rs, p.k_bs, p.k_rs, p.v_bs, p.v_rs, p.o_bs, p.o_rs,
                  p.tq, p.tkv, p.heads, p.qblocks);
   MIXDQ_ARGS_NOW(p.scale_log2, p.s_inv, p.zp, p.unfused, p.xcd_map, p.attn_blocks);
@@ -584,6 +591,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
     if (t >= ntiles) break;
+    if constexpr (CAUSAL)
+      if (t * kKeys > q0 + 31) break;                // (wave-uniform) every row of the wave masks the whole tile
     v16f sc[2];
     {
       v8h kf[2][4];
@@ -609,6 +618,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 #pragma unroll
         for (int r = 0; r < 16; ++r)
           if (32 * kb + 8 * (r >> 2) + (r & 3) >= lim) sc[kb][r] = -INFINITY;
+    }
+    if constexpr (CAUSAL) {                          // key 64 t + 32 kb + 8 (r >> 2) + (r & 3) + 4 hh > row q0 + l32
+      const int lim = q0 + l32 - t * kKeys - 4 * hh;
+#pragma unroll
+      for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          if (32 * kb + 8 * (r >> 2) + (r & 3) > lim) sc[kb][r] = -INFINITY;
     }
     float mx = sc[0][0];
 #pragma unroll
@@ -690,12 +707,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   }
 }
 
-int launch_attn_short(AttnParams& p, int batch, bool quant, bool a4, hipStream_t stream) {
+int launch_attn_short(AttnParams& p, int batch, bool quant, bool a4, hipStream_t stream, bool causal = false) {
   if ((long)p.qblocks * p.heads * batch > 0x7fffffffl) return MIXDQ_ERR_INVALID_ARG;
   const int grid = p.qblocks * p.heads * batch;
   p.attn_blocks = grid;
   const int smem = 2 * kStageBytes;                  // two K | V tiles; the output staging overlays them
-  if (quant && a4) hipLaunchKernelGGL((attn_short_kernel<true, true>), dim3(grid), dim3(256), smem, stream, p);
+  if (causal) hipLaunchKernelGGL((attn_short_kernel<false, false, true>), dim3(grid), dim3(256), smem, stream, p);
+  else if (quant && a4) hipLaunchKernelGGL((attn_short_kernel<true, true>), dim3(grid), dim3(256), smem, stream, p);
   else if (quant) hipLaunchKernelGGL((attn_short_kernel<true>), dim3(grid), dim3(256), smem, stream, p);
   else hipLaunchKernelGGL((attn_short_kernel<false>), dim3(grid), dim3(256), smem, stream, p);
   return launch_status();
@@ -1442,6 +1460,13 @@ static int attention_f16_impl(const void* q, const void* k, const void* v, void*
   const bool w512 = head_dim == Attn512::D;          // attn_512_kernel: the VAE decoder's head, FP16 output only
   if (head_dim != kHeadDim && !hd && !w512) return MIXDQ_ERR_SHAPE;
   if (w512 && out_scale_inv != nullptr) return MIXDQ_ERR_SHAPE;
+  if (flags & MIXDQ_FLAG_ACT_ANY) return MIXDQ_ERR_UNSUPPORTED;   // mixdq_linear_f16's
+  const bool causal = (flags & MIXDQ_FLAG_CAUSAL) != 0;
+  if (causal) {                                      // the short-key kernel at width 64, FP16 output: nothing else
+    const int f = (flags >> 8) & 0xff;
+    if (head_dim != kHeadDim || tq != tkv || tkv > 2 * kKeys || out_scale_inv != nullptr || (f != 0 && f != 1))
+      return MIXDQ_ERR_SHAPE;
+  }
   if (batch == 0 || tq == 0) return MIXDQ_OK;       // nothing to write (pointers may be null)
   if (!q || !k || !v || !out) return MIXDQ_ERR_INVALID_ARG;
   const bool quant = out_scale_inv != nullptr;
@@ -1515,9 +1540,9 @@ static int attention_f16_impl(const void* q, const void* k, const void* v, void*
   }
   if (force == 1 && tkv > 2 * kKeys) return MIXDQ_ERR_SHAPE;
   static const bool short_on = [] { const char* e = getenv("MIXDQ_ATTN_SHORT"); return !(e && e[0] == '0'); }();   // A/B runs
-  if (force == 1 || (force == 0 && short_on && tkv <= 2 * kKeys)) {   // cross-attention: 77 keys
+  if (causal || force == 1 || (force == 0 && short_on && tkv <= 2 * kKeys)) {   // cross-attention: 77 keys; causal
     p.qblocks = (tq + 127) / 128;
-    return launch_attn_short(p, batch, quant, a4, stream);
+    return launch_attn_short(p, batch, quant, a4, stream, causal);
   }
   const long blocks128 = (long)((tq + 127) / 128) * heads;
   const bool big = force ? force == 4 : blocks128 >= kNumCU / 2;

@@ -814,6 +814,7 @@ extern "C" int mixdq_groupnorm_silu_quantize3(const void* x_nhwc, int C1, const 
                                               int64_t HW, int C, int G, int flags,
                                               mixdq_stream_t stream_) {
   if (flags & MIXDQ_FLAG_A4_ANY) return MIXDQ_ERR_UNSUPPORTED;   // 8-bit quantizers only (no 4-bit conv consumer)
+  if (flags & MIXDQ_FLAG_ACT_ANY) return MIXDQ_ERR_UNSUPPORTED;   // mixdq_linear_f16's epilogue activations
   GnRaw raw = {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};
   if (raw_q != nullptr) {
     for (int i = 0; i < 2; ++i) {
@@ -948,6 +949,7 @@ extern "C" int mixdq_layernorm_quantize(const void* x, const void* gamma, const 
                                         const float* const* scale_inv,
                                         const float* const* zero_point, int8_t* const* out_q,
                                         void* out_f16_or_null, int flags, mixdq_stream_t stream_) {
+  if (flags & MIXDQ_FLAG_ACT_ANY) return MIXDQ_ERR_UNSUPPORTED;   // mixdq_linear_f16's epilogue activations
   if (M < 0 || C <= 0 || n_out < 0 || n_out > 3) return MIXDQ_ERR_INVALID_ARG;
   if (C % 16 != 0 || C / 8 > 64 * kLnMaxChunks) return MIXDQ_ERR_SHAPE;   // (16-column groups: the statistics' order)
   if (M == 0) return MIXDQ_OK;
@@ -1014,6 +1016,7 @@ extern "C" int mixdq_layernorm_quantize(const void* x, const void* gamma, const 
 extern "C" int mixdq_geglu_quantize(const void* h, int64_t M, int D, const float* scale_inv,
                                     const float* zero_point, int8_t* out_q_or_null,
                                     void* out_f16_or_null, int flags, mixdq_stream_t stream_) {
+  if (flags & MIXDQ_FLAG_ACT_ANY) return MIXDQ_ERR_UNSUPPORTED;   // mixdq_linear_f16's epilogue activations
   if (M < 0 || D <= 0) return MIXDQ_ERR_INVALID_ARG;
   if (D % 8 != 0) return MIXDQ_ERR_SHAPE;
   if (M == 0) return MIXDQ_OK;

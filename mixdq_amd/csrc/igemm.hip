@@ -474,7 +474,8 @@ inline int select_cfg_f16(int64_t M, int N, int k_bytes) {
 
 // Small-alignment FP16 fallback (C % 8 != 0: conv_in has 4 input channels): one output per thread,
 // FP32 fmaf chain in (r, s, c) order, bias added in FP32, one rounding.
-template <bool CONV>
+// ACT: mixdq_linear_f16's epilogue activation (1: GELU, 2: quick-GELU), a compile-time parameter as on the tiles.
+template <bool CONV, int ACT = 0>
 __global__ __launch_bounds__(256) void f16_generic_kernel(const IgemmParams p) {
   const __half* A = reinterpret_cast<const __half*>(p.A);
   const __half* Wt = reinterpret_cast<const __half*>(p.Wt);
@@ -509,12 +510,29 @@ __global__ __launch_bounds__(256) void f16_generic_kernel(const IgemmParams p) {
     __half o = f32_to_f16_rn(acc);
     if (p.res != nullptr)
       o = f32_to_f16_rn(__fadd_rn(__half2float(o), __half2float(p.res[(m / p.res_div) * p.N + n])));
+    // the epilogue activation on the rounded value (igemm_kernel.h act_f16x2's arithmetic)
+    if constexpr (ACT == 1) o = f32_to_f16_rn(mixdq_geluf(__half2float(o)));
+    if constexpr (ACT == 2) o = f32_to_f16_rn(mixdq_quick_geluf(__half2float(o)));
     p.D[m * p.N + n] = o;
   }
 }
 
+// mixdq_linear_f16 with MIXDQ_FLAG_ACT_GELU / _QUICK_GELU: the ACT instantiations of the same tiles -- kernels of
+// their own beside the unflagged ones, which compile to what they compiled to before there was an activation.
+template <int ACT>
+int dispatch_f16_act(IgemmParams& p, hipStream_t stream, int cfg) {
+  switch (cfg) {
+#define X(ID, BM, BN, BK, ST, WM, WN, KS, MT) \
+  case ID: return launch_tile<BM, BN, BK, ST, WM, WN, false, 8, KS, MT, true, false, false, ACT>(p, stream);
+    MIXDQ_F16_CONFIGS(X)
+#undef X
+    default: return MIXDQ_ERR_INVALID_ARG;
+  }
+}
+
+// act: mixdq_linear_f16's epilogue activation (0: none, 1: GELU, 2: quick-GELU); never with CONV or a residual
 template <bool CONV>
-int dispatch_f16(IgemmParams& p, hipStream_t stream, int forced_cfg) {
+int dispatch_f16(IgemmParams& p, hipStream_t stream, int forced_cfg, int act = 0) {
   if (p.M <= 0 || p.N <= 0) return MIXDQ_OK;
   const int align_k = CONV ? p.C : p.Ktot;     // bytes
   const bool ptr_ok = ((uintptr_t)p.A % 16 == 0) && ((uintptr_t)p.Wt % 16 == 0) &&
@@ -523,10 +541,20 @@ int dispatch_f16(IgemmParams& p, hipStream_t stream, int forced_cfg) {
   if (align_k % 16 != 0 || p.N % 4 != 0 || !ptr_ok) {
     int64_t blocks = (p.M * p.N + 255) / 256;
     if (blocks > kNumCU * 16) blocks = kNumCU * 16;
-    f16_generic_kernel<CONV><<<(int)blocks, 256, 0, stream>>>(p);
+    if constexpr (!CONV) {
+      if (act == 1) f16_generic_kernel<false, 1><<<(int)blocks, 256, 0, stream>>>(p);
+      else if (act == 2) f16_generic_kernel<false, 2><<<(int)blocks, 256, 0, stream>>>(p);
+      else f16_generic_kernel<false><<<(int)blocks, 256, 0, stream>>>(p);
+    } else {
+      f16_generic_kernel<CONV><<<(int)blocks, 256, 0, stream>>>(p);
+    }
     return launch_status();
   }
   const int cfg = forced_cfg > 0 ? forced_cfg : select_cfg_f16(p.M, p.N, p.Ktot);
+  if constexpr (!CONV) {
+    if (act == 1) return dispatch_f16_act<1>(p, stream, cfg);
+    if (act == 2) return dispatch_f16_act<2>(p, stream, cfg);
+  }
   switch (cfg) {
 #define X(ID, BM, BN, BK, ST, WM, WN, KS, MT) \
   case ID: return launch_tile<BM, BN, BK, ST, WM, WN, CONV, 8, KS, MT, true>(p, stream);
@@ -547,6 +575,7 @@ extern "C" int mixdq_qlinear_w8a8_rows(const int8_t* A, const int8_t* W, const f
                                        int group_stride, int group_offset,
                                        const void* residual_f16_or_null, int64_t residual_row_div,
                                        int flags, mixdq_stream_t stream) {
+  if (flags & MIXDQ_FLAG_ACT_ANY) return MIXDQ_ERR_UNSUPPORTED;   // mixdq_linear_f16's epilogue activations
   if (M < 0 || N < 0 || K < 0) return MIXDQ_ERR_INVALID_ARG;
   if (M == 0 || N == 0) return MIXDQ_OK;
   if (!A || !W || !bias0 || !scale || !D_f16) return MIXDQ_ERR_INVALID_ARG;
@@ -571,6 +600,7 @@ extern "C" int mixdq_qlinear_w8a8_geglu(const int8_t* A, const int8_t* W, const 
                                         int8_t* out_i8, int64_t M, int N, int K,
                                         const float* out_scale_inv, const float* out_zero_point,
                                         int flags, mixdq_stream_t stream) {
+  if (flags & MIXDQ_FLAG_ACT_ANY) return MIXDQ_ERR_UNSUPPORTED;   // mixdq_linear_f16's epilogue activations
   // 8-bit output quantizer only (incl. the persistent tile): the caller runs the GEMM to FP16 and mixdq_geglu_quantize
   if (flags & MIXDQ_FLAG_A4_ANY) return MIXDQ_ERR_UNSUPPORTED;
   if (M < 0 || N < 0 || K < 0) return MIXDQ_ERR_INVALID_ARG;
@@ -600,6 +630,7 @@ extern "C" int mixdq_qlinear_w8a8_grouped(const int8_t* A, const mixdq_gemm_grou
                                           int ngroups, int64_t M, int max_N, int K, int group_rows,
                                           int group_stride, int group_offset, int flags,
                                           mixdq_stream_t stream) {
+  if (flags & MIXDQ_FLAG_ACT_ANY) return MIXDQ_ERR_UNSUPPORTED;   // mixdq_linear_f16's epilogue activations
   if (M < 0 || max_N < 0 || K < 0 || ngroups < 0) return MIXDQ_ERR_INVALID_ARG;
   if (M == 0 || max_N == 0 || ngroups == 0) return MIXDQ_OK;
   if (!A || !groups_device || ngroups > 65535) return MIXDQ_ERR_INVALID_ARG;
@@ -632,6 +663,7 @@ extern "C" int mixdq_qlinear_w8a8_attn(const int8_t* A, const int8_t* W, const f
                                        float softmax_scale, const float* out_scale_inv_or_null,
                                        const float* out_zero_point_or_null, int flags,
                                        mixdq_stream_t stream) {
+  if (flags & MIXDQ_FLAG_ACT_ANY) return MIXDQ_ERR_UNSUPPORTED;   // mixdq_linear_f16's epilogue activations
   if (M < 0 || N < 0 || K < 0 || rows_per_image <= 0 || tkv <= 0) return MIXDQ_ERR_INVALID_ARG;
   if (M == 0 || N == 0) return MIXDQ_OK;
   if (!A || !W || !bias0 || !scale || !k_f16 || !v_f16 || !out) return MIXDQ_ERR_INVALID_ARG;
@@ -671,6 +703,7 @@ extern "C" int mixdq_qlinear_w8a8_attn(const int8_t* A, const int8_t* W, const f
 extern "C" int mixdq_qlinear_w8a8(const int8_t* A, const int8_t* W, const float* bias0,
                                   const float* scale, const void* bias_f16_or_null, void* D_f16,
                                   int64_t M, int N, int K, int flags, mixdq_stream_t stream) {
+  if (flags & MIXDQ_FLAG_ACT_ANY) return MIXDQ_ERR_UNSUPPORTED;   // mixdq_linear_f16's epilogue activations
   return mixdq_qlinear_w8a8_rows(A, W, bias0, scale, bias_f16_or_null, D_f16, M, N, K, 0, 0, 0,
                                  nullptr, 1, flags, stream);
 }
@@ -708,6 +741,7 @@ extern "C" int mixdq_qconv2d_w8a8_table(const int8_t* X, const int8_t* Wt, const
                                         int stride, int pad, const void* residual_f16_or_null,
                                         int64_t residual_row_div, int flags,
                                         mixdq_stream_t stream) {
+  if (flags & MIXDQ_FLAG_ACT_ANY) return MIXDQ_ERR_UNSUPPORTED;   // mixdq_linear_f16's epilogue activations
   if (N < 0 || H <= 0 || W <= 0 || C <= 0 || K <= 0 || R <= 0 || S <= 0 || stride <= 0 || pad < 0)
     return MIXDQ_ERR_INVALID_ARG;
   if (!X || !Wt || !scale || !D) return MIXDQ_ERR_INVALID_ARG;
@@ -773,6 +807,7 @@ extern "C" int mixdq_qconv2d_w8a8(const int8_t* X, const int8_t* Wt, const float
                                   void* D, void* workspace, int N, int H, int W, int C, int K,
                                   int R, int S, int stride, int pad, int dilation, int flags,
                                   mixdq_stream_t stream) {
+  if (flags & MIXDQ_FLAG_ACT_ANY) return MIXDQ_ERR_UNSUPPORTED;   // mixdq_linear_f16's epilogue activations
   if (dilation != 1) return MIXDQ_ERR_UNSUPPORTED;
   const float* table = nullptr;
   if (pad > 0) {
@@ -823,6 +858,8 @@ extern "C" int mixdq_linear_f16(const void* A_f16, const void* W_f16, const void
   if (M == 0 || N == 0) return MIXDQ_OK;
   if (!A_f16 || !W_f16 || !D_f16) return MIXDQ_ERR_INVALID_ARG;
   if (flags & MIXDQ_FLAG_W2) return MIXDQ_ERR_UNSUPPORTED;   // FP16 weights
+  const int act = (flags & MIXDQ_FLAG_ACT_GELU ? 1 : 0) | (flags & MIXDQ_FLAG_ACT_QUICK_GELU ? 2 : 0);
+  if (act == 3 || (act != 0 && residual_f16_or_null != nullptr)) return MIXDQ_ERR_INVALID_ARG;
   if ((int64_t)K * 2 > 0x7fffffff) return MIXDQ_ERR_SHAPE;
   IgemmParams p{};
   p.A = (const int8_t*)A_f16; p.Wt = (const int8_t*)W_f16; p.bias = (const __half*)bias_f16_or_null;
@@ -831,13 +868,14 @@ extern "C" int mixdq_linear_f16(const void* A_f16, const void* W_f16, const void
   p.H = p.W = p.P = p.Q = 1; p.C = 2 * K; p.R = p.S = 1; p.stride = 1; p.pad = 0;
   p.res = (const __half*)residual_f16_or_null;
   p.res_div = residual_row_div > 0 ? residual_row_div : 1;
-  return dispatch_f16<false>(p, (hipStream_t)stream, (flags >> 8) & 0xff);
+  return dispatch_f16<false>(p, (hipStream_t)stream, (flags >> 8) & 0xff, act);
 }
 
 extern "C" int mixdq_conv2d_f16(const void* X_f16, const void* Wt_f16, const void* bias_f16_or_null,
                                 void* D_f16, int N, int H, int W, int C, int K, int R, int S,
                                 int stride, int pad, const void* residual_f16_or_null,
                                 int64_t residual_row_div, int flags, mixdq_stream_t stream) {
+  if (flags & MIXDQ_FLAG_ACT_ANY) return MIXDQ_ERR_UNSUPPORTED;   // mixdq_linear_f16's epilogue activations
   if (N < 0 || H <= 0 || W <= 0 || C <= 0 || K <= 0 || R <= 0 || S <= 0 || stride <= 0 || pad < 0)
     return MIXDQ_ERR_INVALID_ARG;
   if (!X_f16 || !Wt_f16 || !D_f16) return MIXDQ_ERR_INVALID_ARG;

@@ -117,6 +117,28 @@ struct IgemmParams {
   int ups;
 };
 
+// FP16 layers (mixdq_linear_f16, MIXDQ_FLAG_ACT_GELU / _QUICK_GELU): an activation applied to the ROUNDED FP16 value
+// where the tile's chunks are stored -- ACT 1: GELU (mixdq_geluf), 2: quick-GELU (mixdq_quick_geluf;
+// include/mixdq_math.h); never together with a residual.  ACT is a compile-time parameter of the kernels, so that a
+// launch without activation runs the code it ran before there was one.
+// f16(act(f32(h))) on the two halves of a dword:
+template <int ACT>
+__device__ __forceinline__ uint32_t act_f16x2(uint32_t w) {
+  static_assert(ACT == 1 || ACT == 2, "1: GELU, 2: quick-GELU");
+  uint32_t out = 0;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    __half_raw r;
+    r.x = (unsigned short)(j ? (w >> 16) : (w & 0xffffu));
+    const float h = __half2float(__half(r));
+    float a;
+    if constexpr (ACT == 1) a = mixdq_geluf(h);
+    else a = mixdq_quick_geluf(h);
+    out |= (uint32_t)__half_as_ushort(f32_to_f16_rn(a)) << (16 * j);
+  }
+  return out;
+}
+
 template <int BK>
 __device__ __forceinline__ int swz(int row) {
   // 256-B LDS bank row holds 4 (BK=64), 2 (BK=128) or 1 (BK=256) tile rows; XOR so that the 16 lanes of a
@@ -416,7 +438,7 @@ __device__ __forceinline__ void aq_wait4(v4i& a, v4i& b, v4i& c, v4i& d) {
 
 template <int BM, int BN, int BK, int STAGES, int WM, int WN, bool CONV, bool FAST, int WBITS,
           int KSPLIT = 1, int MT = 32, bool F16 = false, bool ATT = false, bool PHASED = false,
-          bool GROUPED = false, bool AQ = false, bool LNQ = false, bool ATT_A4 = false>
+          bool GROUPED = false, bool AQ = false, bool LNQ = false, bool ATT_A4 = false, int ACT = 0>
 __global__ __launch_bounds__(
     64 * WM * WN * KSPLIT,
     (ATT ? 2 : igemm_waves_per_simd<BM, BN, BK, STAGES, WM * WN * KSPLIT,
@@ -435,6 +457,8 @@ void igemm_kernel(MIXDQ_IGEMM_HEAD_PARAMS const IgemmParams p_in) {
   static_assert(!(CONV && FAST), "the fast staging path is for Linear");
   // ATT_A4: the attention output is to_out.0's operand for a 4-bit activation quantizer (MIXDQ_FLAG_A4_0)
   static_assert(!ATT_A4 || ATT, "the 4-bit output clamp belongs to the attention epilogue");
+  // ACT: the epilogue activation of mixdq_linear_f16 (1: GELU, 2: quick-GELU) -- instantiations of their own
+  static_assert(ACT == 0 || (F16 && !CONV && (ACT == 1 || ACT == 2)), "the epilogue activation belongs to the FP16 Linear");
   // AQ -- quantize-in-prologue (replaces the reference's quantize launch in front of every layer,
   // nn/Linear.py:162-176): the activation operand is read as FP16 into registers (16 bytes = 8 values per
   // lane and load), quantized there -- q = sat8(rint(fma(x, s_inv, zp))), the arithmetic of
@@ -1828,6 +1852,11 @@ void igemm_kernel(MIXDQ_IGEMM_HEAD_PARAMS const IgemmParams p_in) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) vw[e] = add_f16x2(vw[e], rw[e]);
     }
+    if constexpr (ACT != 0) {    // the epilogue activation: on the rounded value, one path for every tile configuration
+      uint32_t* vw = reinterpret_cast<uint32_t*>(&v);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) vw[e] = act_f16x2<ACT>(vw[e]);
+    }
     if constexpr (LNQ) {    // the FINAL value (residual added) back into the tile: the LayerNorm's input; the
       *reinterpret_cast<uint4*>(Cs + row * CS_STRIDE + cc * 16) = v;   // rows leave for D behind the records
       // ... and the 16-column group's statistics while the chunk is in registers: a chunk is half a group, its
@@ -2113,7 +2142,8 @@ inline int tile_map_gm() {
 }
 
 template <int BM, int BN, int BK, int STAGES, int WM, int WN, bool CONV, bool FAST, int WBITS, int KSPLIT,
-          int MT, bool F16 = false, bool PHASED = false, bool GROUPED = false, bool AQ = false, bool LNQ = false>
+          int MT, bool F16 = false, bool PHASED = false, bool GROUPED = false, bool AQ = false, bool LNQ = false,
+          int ACT = 0>
 int launch_kernel(IgemmParams& p, hipStream_t stream) {
   // (LNQ: the LDS request is padded past half a CU's LDS, so that no two workgroups share a CU: the tiles of a
   //  row block wait for each other, and the cross-CU hand-off form they use is the one-workgroup-per-CU one)
@@ -2126,7 +2156,7 @@ int launch_kernel(IgemmParams& p, hipStream_t stream) {
     static bool seen[64] = {};
     if (const int st = lds_opt_in(
             reinterpret_cast<const void*>(
-                &igemm_kernel<BM, BN, BK, STAGES, WM, WN, CONV, FAST, WBITS, KSPLIT, MT, F16, false, PHASED, GROUPED, AQ, LNQ>),
+                &igemm_kernel<BM, BN, BK, STAGES, WM, WN, CONV, FAST, WBITS, KSPLIT, MT, F16, false, PHASED, GROUPED, AQ, LNQ, false, ACT>),
             SMEM, seen))
       return st;
   }
@@ -2152,20 +2182,20 @@ int launch_kernel(IgemmParams& p, hipStream_t stream) {
       int n = 0, per_cu = 0;
       if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return MIXDQ_ERR_LAUNCH;
       if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
-              &per_cu, igemm_kernel<BM, BN, BK, STAGES, WM, WN, CONV, FAST, WBITS, KSPLIT, MT, F16, false, PHASED, GROUPED, AQ, LNQ>,
+              &per_cu, igemm_kernel<BM, BN, BK, STAGES, WM, WN, CONV, FAST, WBITS, KSPLIT, MT, F16, false, PHASED, GROUPED, AQ, LNQ, false, ACT>,
               64 * WM * WN * KSPLIT, SMEM) != hipSuccess)
         return MIXDQ_ERR_LAUNCH;
       cus[dev] = per_cu >= 1 ? n : -1;
     }
     if (cus[dev] < 0 || grid > cus[dev]) return MIXDQ_ERR_SHAPE;
   }
-  igemm_kernel<BM, BN, BK, STAGES, WM, WN, CONV, FAST, WBITS, KSPLIT, MT, F16, false, PHASED, GROUPED, AQ, LNQ>
+  igemm_kernel<BM, BN, BK, STAGES, WM, WN, CONV, FAST, WBITS, KSPLIT, MT, F16, false, PHASED, GROUPED, AQ, LNQ, false, ACT>
       <<<dim3((unsigned)grid, (unsigned)ny), 64 * WM * WN * KSPLIT, SMEM, stream>>>(MIXDQ_IGEMM_HEAD_ARGS(p) p);
   return launch_status();
 }
 
 template <int BM, int BN, int BK, int STAGES, int WM, int WN, bool CONV, int WBITS, int KSPLIT, int MT,
-          bool F16 = false, bool PHASED = false, bool GROUPED = false>
+          bool F16 = false, bool PHASED = false, bool GROUPED = false, int ACT = 0>
 int launch_tile(IgemmParams& p, hipStream_t stream) {
   if constexpr (!CONV) {
     const bool fits32 = (uint64_t)p.M * (uint64_t)p.Ktot < (1ull << 32) &&
@@ -2174,13 +2204,13 @@ int launch_tile(IgemmParams& p, hipStream_t stream) {
       if constexpr (PHASED && WBITS == 8 && !F16)
         return launch_kernel<BM, BN, BK, STAGES, WM, WN, false, true, 8, KSPLIT, MT, false, true>(p, stream);
       else if constexpr (!PHASED)
-        return launch_kernel<BM, BN, BK, STAGES, WM, WN, false, true, WBITS, KSPLIT, MT, F16, false, GROUPED>(p, stream);
+        return launch_kernel<BM, BN, BK, STAGES, WM, WN, false, true, WBITS, KSPLIT, MT, F16, false, GROUPED, false, false, ACT>(p, stream);
     }
   }
   if constexpr (PHASED)   // convs, packed weights, K tails: the same tile on the one-phase loop
     return launch_kernel<BM, BN, BK, STAGES, 4, 2, CONV, false, WBITS, 1, 32, F16>(p, stream);
   else
-    return launch_kernel<BM, BN, BK, STAGES, WM, WN, CONV, false, WBITS, KSPLIT, MT, F16, false, GROUPED>(p, stream);
+    return launch_kernel<BM, BN, BK, STAGES, WM, WN, CONV, false, WBITS, KSPLIT, MT, F16, false, GROUPED, false, false, ACT>(p, stream);
 }
 
 // AQ launches: the Linear fast path only -- whole K-tiles and 32-bit byte offsets into the FP16 operand

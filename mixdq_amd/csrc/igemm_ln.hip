@@ -71,6 +71,7 @@ extern "C" int mixdq_qlinear_w8a8_ln(const int8_t* A, const int8_t* W, const flo
                                      const float* const* scale_inv, const float* const* zero_point,
                                      int8_t* const* out_q, void* out_f16_or_null, void* workspace,
                                      int flags, mixdq_stream_t stream) {
+  if (flags & MIXDQ_FLAG_ACT_ANY) return MIXDQ_ERR_UNSUPPORTED;   // mixdq_linear_f16's epilogue activations
   // 8-bit quantizers only: with a 4-bit consumer the caller issues the GEMM and mixdq_layernorm_quantize
   if (flags & MIXDQ_FLAG_A4_ANY) return MIXDQ_ERR_UNSUPPORTED;
   if (M < 0 || N < 0 || K < 0 || n_out < 0 || n_out > 3) return MIXDQ_ERR_INVALID_ARG;

@@ -121,6 +121,33 @@ __global__ __launch_bounds__(256) void quantize_scalar_kernel(const __half* __re
   }
 }
 
+// Token + position embedding (mixdq_embed_tokens_f16): one 16-byte chunk of an output row per thread-step,
+// out = f16(f32(tok[id]) + f32(pos[t])) -- torch's half add.  An id outside [0, V) is clamped: the kernel has no
+// way to report it.
+__global__ __launch_bounds__(256) void embed_tokens_kernel(const int* __restrict__ ids, const uint4* __restrict__ tok,
+                                                           const uint4* __restrict__ pos, uint4* __restrict__ out,
+                                                           int64_t chunks, int T, int cpr, int V) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < chunks; i += stride) {
+    const int64_t row = i / cpr;
+    const int ch = (int)(i - row * cpr);
+    const int t = (int)(row % T);
+    const int id = min(max(ids[row], 0), V - 1);
+    const uint4 a = tok[(int64_t)id * cpr + ch], b = pos[(int64_t)t * cpr + ch];
+    const uint32_t aw[4] = {a.x, a.y, a.z, a.w}, bw[4] = {b.x, b.y, b.z, b.w};
+    uint32_t o[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const v2h ah = *reinterpret_cast<const v2h*>(&aw[e]), bh = *reinterpret_cast<const v2h*>(&bw[e]);
+      v2f r = __builtin_convertvector(ah, v2f) + __builtin_convertvector(bh, v2f);
+      asm("" : "+v"(r));
+      const v2h h = __builtin_convertvector(r, v2h);
+      o[e] = *reinterpret_cast<const uint32_t*>(&h);
+    }
+    out[i] = make_uint4(o[0], o[1], o[2], o[3]);
+  }
+}
+
 inline int grid_for(int64_t work_items) {
   int64_t blocks = (work_items + 255) / 256;
   const int64_t cap = (int64_t)kNumCU * 8;   // 2048 blocks, grid-stride the rest
@@ -138,6 +165,7 @@ extern "C" int mixdq_quantize_f16_i8(const void* x_f16, int8_t* out, const int64
                                      const int64_t* x_strides, const int64_t* out_strides,
                                      int ndim, const float* scale_inv, const float* zero_point,
                                      int flags, mixdq_stream_t stream_) {
+  if (flags & MIXDQ_FLAG_ACT_ANY) return MIXDQ_ERR_UNSUPPORTED;   // mixdq_linear_f16's epilogue activations
   if (ndim < 0 || ndim > 8 || !scale_inv || !zero_point) return MIXDQ_ERR_INVALID_ARG;
   hipStream_t stream = (hipStream_t)stream_;
   if (flags & (MIXDQ_FLAG_A4_1 | MIXDQ_FLAG_A4_2)) return MIXDQ_ERR_UNSUPPORTED;   // one quantizer: slot 0
@@ -203,5 +231,19 @@ extern "C" int mixdq_quantize_f16_i8(const void* x_f16, int8_t* out, const int64
     Q_LAUNCH(quantize_scalar_kernel, x, out, scale_inv, zero_point, a);
   }
 #undef Q_LAUNCH
+  return launch_status();
+}
+
+extern "C" int mixdq_embed_tokens_f16(const int32_t* ids, const void* tok_f16, const void* pos_f16, void* out_f16,
+                                      int B, int T, int C, int V, mixdq_stream_t stream_) {
+  if (B < 0 || T < 0 || C < 0 || V < 1) return MIXDQ_ERR_INVALID_ARG;
+  if (C % 8 != 0) return MIXDQ_ERR_ALIGNMENT;
+  const int64_t chunks = (int64_t)B * T * (C / 8);
+  if (chunks == 0) return MIXDQ_OK;
+  if (!ids || !tok_f16 || !pos_f16 || !out_f16) return MIXDQ_ERR_INVALID_ARG;
+  if (((uintptr_t)tok_f16 | (uintptr_t)pos_f16 | (uintptr_t)out_f16) & 15 || ((uintptr_t)ids & 3))
+    return MIXDQ_ERR_ALIGNMENT;
+  embed_tokens_kernel<<<grid_for(chunks), 256, 0, (hipStream_t)stream_>>>(
+      ids, (const uint4*)tok_f16, (const uint4*)pos_f16, (uint4*)out_f16, chunks, T, C / 8, V);
   return launch_status();
 }
