@@ -123,7 +123,16 @@ enum mixdq_flags {
      kernels cannot take a 4-bit activation and run such a layer in FP16 (nn/Linear.py:31,133-134). */
   MIXDQ_FLAG_A4_0 = 1 << 16,
   MIXDQ_FLAG_A4_1 = 1 << 17,
-  MIXDQ_FLAG_A4_2 = 1 << 18
+  MIXDQ_FLAG_A4_2 = 1 << 18,
+  /* mixdq_conv2d_f16 only: the `pad` rows and columns of zeros lie BELOW and RIGHT of the image only (F.pad(x, (0,
+     pad, 0, pad)) in front of an unpadded conv, without that tensor): P = (H + pad - R) / stride + 1, Q likewise,
+     and output pixel (p, q) reads its window from (p * stride, q * stride).  3x3 / stride 2 / pad 1 is the conv of
+     diffusers' Downsample2D as the VAE encoder uses it.  On the MFMA tiles and on the one-output-per-thread kernel,
+     with or without a residual or a forced tile id; same bits as the conv on the padded tensor.  Together with
+     MIXDQ_FLAG_UPSAMPLE2X, or pad >= R or pad >= S: MIXDQ_ERR_SHAPE, nothing written.  mixdq_qconv2d_w8a8[_table]
+     refuse it (MIXDQ_ERR_UNSUPPORTED: their zero-point border table is built for symmetric padding).  No reference
+     counterpart. */
+  MIXDQ_FLAG_PAD_AFTER = 1 << 19
 };
 #define MIXDQ_FLAG_A4_ANY (MIXDQ_FLAG_A4_0 | MIXDQ_FLAG_A4_1 | MIXDQ_FLAG_A4_2)
 #define MIXDQ_FLAG_ACT_ANY (MIXDQ_FLAG_ACT_GELU | MIXDQ_FLAG_ACT_QUICK_GELU)
@@ -497,7 +506,8 @@ int mixdq_attention_f16_prefetch(const void* q_f16, const void* k_f16, const voi
  * A [M,K], W [N,K], D [M,N] row-major fp16; conv: X [N,H,W,C], Wt [K,R,S,C], D [N,P,Q,K].
  * K % 8 == 0 (conv: C % 8 == 0) and N % 4 == 0 run on MFMA tiles, anything else (conv_in: C = 4)
  * on a one-output-per-thread kernel.  flags: bits 8..15 force a tile configuration; mixdq_conv2d_f16 also takes
- * MIXDQ_FLAG_UPSAMPLE2X (see the flag: the conv of Upsample2D without the upsampled tensor), mixdq_linear_f16
+ * MIXDQ_FLAG_UPSAMPLE2X (see the flag: the conv of Upsample2D without the upsampled tensor) and MIXDQ_FLAG_PAD_AFTER
+ * (see the flag: padding below and right only, the conv of Downsample2D), mixdq_linear_f16
  * MIXDQ_FLAG_ACT_GELU / MIXDQ_FLAG_ACT_QUICK_GELU (see the flags: the activation of an MLP's first layer, applied to
  * the rounded FP16 value where the tile is stored -- the same on every tile configuration and on the
  * one-output-per-thread kernel). */
@@ -518,6 +528,34 @@ int mixdq_conv2d_f16(const void* X_f16, const void* Wt_f16, const void* bias_f16
  * text encoders through diffusers' pipeline). */
 int mixdq_embed_tokens_f16(const int32_t* ids, const void* tok_f16, const void* pos_f16, void* out_f16, int B, int T,
                            int C, int V, mixdq_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * VAE encoder ends (csrc/vae.hip).  No reference counterpart (the reference reaches the VAE through diffusers'
+ * pipeline).
+ *
+ * mixdq_image_to_nhwc8_f16: the encoder's ingest.  img: [B, C, H, W] of uint8 (dtype 0), FP16 (1) or FP32 (2),
+ * element (b, c, y, x) at img + (b * sb + c * sc + y * sh + x * sw) ELEMENTS (NCHW and NHWC sources alike);
+ * out: FP16 [B, H, W, 8], one 16-byte store per pixel, channels C..7 zero.
+ *   uint8:  f16_rn(f32(u) * (2/255: 0x3C008081) - 1.0f)     two FP32 roundings, never contracted: u / 127.5 - 1
+ *   float:  f16_rn(f32(v))                                    no clamp
+ * Errors: null pointers, negative sizes, C outside 1..8, a dtype code outside 0..2: MIXDQ_ERR_INVALID_ARG; out not
+ * 16-byte aligned or img not aligned to its element: MIXDQ_ERR_ALIGNMENT.  B * H * W == 0 writes nothing (and looks at
+ * no pointer: an empty tensor has no storage).
+ *
+ * mixdq_vae_latent_sample: the posterior sample.  moments: FP16 [B, h, w, 2L] (channels 0..L-1 the mean, L..2L-1 the
+ * log-variance), noise: FP32 [B, h, w, L] or null, z: FP32 [B, h, w, L]; `pixels` = B * h * w.
+ *   z = (f32(mean) + exp(0.5 * clamp(f32(logvar), -30, 20)) * noise) * scaling_factor
+ *   noise == null:  z = f32(mean) * scaling_factor                  (the mode of the posterior)
+ * every operation one FP32 rounding, never contracted (include/mixdq_math.h: mixdq_vae_latent[_mode]).
+ * L % 4 == 0 and 16-byte aligned pointers: MIXDQ_ERR_ALIGNMENT otherwise; null moments / z, pixels < 0, L < 1:
+ * MIXDQ_ERR_INVALID_ARG.  pixels == 0 writes nothing. */
+#define MIXDQ_IMAGE_U8 0
+#define MIXDQ_IMAGE_F16 1
+#define MIXDQ_IMAGE_F32 2
+int mixdq_image_to_nhwc8_f16(const void* img, int dtype, int64_t sb, int64_t sc, int64_t sh, int64_t sw,
+                             void* out_f16, int B, int C, int H, int W, mixdq_stream_t stream);
+int mixdq_vae_latent_sample(const void* moments_f16, const float* noise_or_null, float* z, int64_t pixels, int L,
+                            float scaling_factor, mixdq_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Sampler step: classifier-free guidance + scheduler update + the UNet's next input, and the step state kept on

@@ -133,4 +133,21 @@ MIXDQ_HD float mixdq_sampler_update_noise(float x, float e, float n, float a, fl
 /* The FP32 value whose FP16 rounding is the UNet's next input. */
 MIXDQ_HD float mixdq_sampler_scaled_input(float x_next, float s_next) { return MIXDQ_MUL_RN(x_next, s_next); }
 
+/* ---- VAE encoder ends (csrc/vae.hip), same rule: one rounding per operation, never contracted.
+ * The posterior sample of an AutoencoderKL (DiagonalGaussianDistribution: logvar clamped to [-30, 20]), times the
+ * scaling factor:  z = (mean + exp(0.5 * logvar) * n) * sf;  without noise the mode, mean * sf. */
+MIXDQ_HD float mixdq_vae_latent(float mean, float logvar, float n, float sf) {
+  const float lv = __builtin_fminf(__builtin_fmaxf(logvar, -30.0f), 20.0f);
+  const float std = mixdq_expf(MIXDQ_MUL_RN(0.5f, lv));
+  return MIXDQ_MUL_RN(MIXDQ_ADD_RN(mean, MIXDQ_MUL_RN(std, n)), sf);
+}
+
+MIXDQ_HD float mixdq_vae_latent_mode(float mean, float sf) { return MIXDQ_MUL_RN(mean, sf); }
+
+/* A uint8 pixel as the FP32 value whose FP16 rounding the encoder reads: u * (2/255) - 1, the constant 2/255 rounded
+ * to FP32 (0x3C008081).  For all 256 values its FP16 rounding is that of u / 127.5 - 1 computed exactly. */
+MIXDQ_HD float mixdq_pixel_to_unit(uint32_t u) {
+  return MIXDQ_SUB_RN(MIXDQ_MUL_RN((float)u, mixdq_bits_to_float(0x3C008081u)), 1.0f);
+}
+
 #endif /* MIXDQ_MATH_H_ */

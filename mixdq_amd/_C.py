@@ -134,6 +134,7 @@ IGEMM_WAVES = {1: (2, 2, 1, 32), 3: (2, 2, 1, 32), 4: (2, 2, 1, 32), 13: (4, 2, 
 FLAG_W4 = 2   # MIXDQ_FLAG_W4: the weight tensor holds packed signed 4-bit values
 FLAG_W2 = 16  # MIXDQ_FLAG_W2: the weight tensor holds packed signed 2-bit values ([N, K/4])
 FLAG_UPSAMPLE2X = 4   # MIXDQ_FLAG_UPSAMPLE2X: the conv input is read through a nearest 2x upsampling
+FLAG_PAD_AFTER = 1 << 19   # MIXDQ_FLAG_PAD_AFTER: conv2d_f16's padding lies below and right of the image only
 FLAG_CAUSAL = 32      # MIXDQ_FLAG_CAUSAL: attention_f16's causal mask (query row i attends to keys 0 .. i)
 FLAG_ACT = {None: 0, "gelu": 64, "quick_gelu": 128}   # MIXDQ_FLAG_ACT_GELU / _QUICK_GELU: linear_f16's epilogue activation
 # MIXDQ_FLAG_A4_<i>: quantizer slot i of a launch is a 4-bit one -- q clamped to [-128, -113] (Path A's [0, 15]
@@ -982,13 +983,17 @@ def linear_f16(input, weight, bias=None, *, _residual=None, _cfg=0, _act=None):
 
 
 def conv2d_f16(input, weight, bias=None, stride=1, padding=0, *, _residual=None,
-               _residual_per_image=False, _cfg=0, _upsample2x=False):
+               _residual_per_image=False, _cfg=0, _upsample2x=False, _pad_after=False):
     """F.conv2d(input, weight, bias, stride, padding) for fp16 GPU tensors (square stride / padding,
     dilation 1, groups 1): input [N, C, H, W] and weight [K, C, R, S] are read in channels-last
     memory (converted if they are not), the result is channels-last [N, K, P, Q].
     `_upsample2x`: the conv runs on F.interpolate(input, scale_factor=2, mode="nearest") without that tensor being
     made (MIXDQ_FLAG_UPSAMPLE2X: 3x3 / stride 1 / padding 1 on the MFMA tiles -- C % 8 == 0, K % 4 == 0 -- only;
-    anything else is refused); same bits as the conv on the materialised tensor."""
+    anything else is refused); same bits as the conv on the materialised tensor.
+    `_pad_after`: the `padding` rows and columns of zeros lie below and right of the image only
+    (MIXDQ_FLAG_PAD_AFTER): F.conv2d(F.pad(input, (0, padding, 0, padding)), weight, bias, stride, 0) without the padded
+    tensor, same bits; 3x3 / stride 2 / padding 1 is the conv of diffusers' Downsample2D in a VAE encoder.  On the
+    MFMA tiles and the one-output-per-thread kernel alike; not together with `_upsample2x`."""
     _trace_w(weight)
     _check(input.is_cuda and input.dtype == torch.float16 and input.dim() == 4,
            "input should be a 4-D fp16 GPU tensor")
@@ -1000,6 +1005,9 @@ def conv2d_f16(input, weight, bias=None, stride=1, padding=0, *, _residual=None,
         H, W = 2 * H, 2 * W
         P = (H + 2 * padding - (R - 1) - 1) // stride + 1
         Q = (W + 2 * padding - (S - 1) - 1) // stride + 1
+    if _pad_after:        # zeros below and right only (with _upsample2x: the library refuses the pair)
+        P = max((H + padding - R) // stride + 1, 0)
+        Q = max((W + padding - S) // stride + 1, 0)
     _check(weight.size(1) == C, "input and weight channel counts should match")
     if bias is not None:
         _check(bias.dtype == torch.float16 and bias.numel() == K, "bias should be fp16 [K]")
@@ -1022,7 +1030,8 @@ def conv2d_f16(input, weight, bias=None, stride=1, padding=0, *, _residual=None,
     with torch.cuda.device(x.device):
         code = _lib.mixdq_conv2d_f16(x.data_ptr(), w.data_ptr(), _ptr(bs), D.data_ptr(), N, H, W, C,
                                      K, R, S, stride, padding, res_ptr, res_div,
-                                     (int(_cfg) << 8) | (FLAG_UPSAMPLE2X if _upsample2x else 0), _stream())
+                                     (int(_cfg) << 8) | (FLAG_UPSAMPLE2X if _upsample2x else 0)
+                                     | (FLAG_PAD_AFTER if _pad_after else 0), _stream())
     _status(code, "conv2d_f16")
     return D
 
@@ -1415,3 +1424,51 @@ def sampler_step(x, eps, inp, coef, t_table, step, timestep, guidance=0.0, rows_
                                        timestep.data_ptr(), float(guidance), n, int(rows_per_image), row_stride,
                                        _stream())
     _status(code, "sampler_step")
+
+
+
+_lib.mixdq_image_to_nhwc8_f16.argtypes = [_vp, _i32, _i64, _i64, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _vp]
+_lib.mixdq_image_to_nhwc8_f16.restype = _i32
+_lib.mixdq_vae_latent_sample.argtypes = [_vp, _vp, _vp, _i64, _i32, ctypes.c_float, _vp]
+_lib.mixdq_vae_latent_sample.restype = _i32
+IMAGE_DTYPES = {torch.uint8: 0, torch.float16: 1, torch.float32: 2}      # include/mixdq_hip.h MIXDQ_IMAGE_*
+
+
+def image_to_nhwc8_f16(image):
+    """The VAE encoder's ingest (mixdq_image_to_nhwc8_f16): image [B, C <= 8, H, W], uint8, fp16 or fp32, of ANY
+    strides (NCHW, channels-last, a slice: the kernel reads them) -> fp16 [B, 8, H, W] in channels-last storage,
+    channels C..7 zero.  uint8: f16(f32(u) * f32(2/255) - 1), which is f16(u / 127.5 - 1); floats: f16(v), no clamp."""
+    _check(torch.is_tensor(image) and image.is_cuda and image.dim() == 4 and image.dtype in IMAGE_DTYPES,
+           "image should be a 4-D uint8, fp16 or fp32 GPU tensor")
+    B, C, H, W = image.shape
+    _check(1 <= C <= 8, "image should have 1 to 8 channels")
+    out = torch.empty((B, H, W, 8), dtype=torch.float16, device=image.device)
+    sb, sc, sh, sw = image.stride()
+    with torch.cuda.device(image.device):
+        code = _lib.mixdq_image_to_nhwc8_f16(image.data_ptr(), IMAGE_DTYPES[image.dtype], sb, sc, sh, sw,
+                                             out.data_ptr(), B, C, H, W, _stream())
+    _status(code, "image_to_nhwc8_f16")
+    return out.permute(0, 3, 1, 2)
+
+
+def vae_latent_sample(moments, noise=None, scaling_factor=1.0):
+    """The posterior sample of an AutoencoderKL (mixdq_vae_latent_sample): moments fp16 [B, 2L, h, w] in
+    channels-last storage (channels 0..L-1 the mean, L..2L-1 the log-variance), noise fp32 [B, L, h, w]
+    channels-last or None -> fp32 [B, L, h, w] channels-last:
+    (mean + exp(0.5 * clamp(logvar, -30, 20)) * noise) * scaling_factor; without noise mean * scaling_factor (the
+    mode).  L % 4 == 0.  Arithmetic: include/mixdq_math.h mixdq_vae_latent."""
+    _check(torch.is_tensor(moments) and moments.is_cuda and moments.dtype == torch.float16 and moments.dim() == 4
+           and moments.shape[1] % 2 == 0 and moments.is_contiguous(memory_format=torch.channels_last),
+           "moments should be a channels-last fp16 [B, 2L, h, w] GPU tensor")
+    B, C2, h, w = moments.shape
+    L = C2 // 2
+    if noise is not None:
+        _check(torch.is_tensor(noise) and noise.device == moments.device and noise.dtype == torch.float32
+               and tuple(noise.shape) == (B, L, h, w) and noise.is_contiguous(memory_format=torch.channels_last),
+               "noise should be a channels-last fp32 [B, L, h, w] tensor on the moments' device")
+    z = torch.empty((B, h, w, L), dtype=torch.float32, device=moments.device)
+    with torch.cuda.device(moments.device):
+        code = _lib.mixdq_vae_latent_sample(moments.data_ptr(), _ptr(noise), z.data_ptr(), B * h * w, L,
+                                            float(scaling_factor), _stream())
+    _status(code, "vae_latent_sample")
+    return z.permute(0, 3, 1, 2)

@@ -742,6 +742,7 @@ extern "C" int mixdq_qconv2d_w8a8_table(const int8_t* X, const int8_t* Wt, const
                                         int64_t residual_row_div, int flags,
                                         mixdq_stream_t stream) {
   if (flags & MIXDQ_FLAG_ACT_ANY) return MIXDQ_ERR_UNSUPPORTED;   // mixdq_linear_f16's epilogue activations
+  if (flags & MIXDQ_FLAG_PAD_AFTER) return MIXDQ_ERR_UNSUPPORTED; // the border table's classes assume symmetric padding
   if (N < 0 || H <= 0 || W <= 0 || C <= 0 || K <= 0 || R <= 0 || S <= 0 || stride <= 0 || pad < 0)
     return MIXDQ_ERR_INVALID_ARG;
   if (!X || !Wt || !scale || !D) return MIXDQ_ERR_INVALID_ARG;
@@ -808,6 +809,7 @@ extern "C" int mixdq_qconv2d_w8a8(const int8_t* X, const int8_t* Wt, const float
                                   int R, int S, int stride, int pad, int dilation, int flags,
                                   mixdq_stream_t stream) {
   if (flags & MIXDQ_FLAG_ACT_ANY) return MIXDQ_ERR_UNSUPPORTED;   // mixdq_linear_f16's epilogue activations
+  if (flags & MIXDQ_FLAG_PAD_AFTER) return MIXDQ_ERR_UNSUPPORTED; // before the border table is written
   if (dilation != 1) return MIXDQ_ERR_UNSUPPORTED;
   const float* table = nullptr;
   if (pad > 0) {
@@ -880,9 +882,17 @@ extern "C" int mixdq_conv2d_f16(const void* X_f16, const void* Wt_f16, const voi
     return MIXDQ_ERR_INVALID_ARG;
   if (!X_f16 || !Wt_f16 || !D_f16) return MIXDQ_ERR_INVALID_ARG;
   if (flags & MIXDQ_FLAG_W2) return MIXDQ_ERR_UNSUPPORTED;   // FP16 weights
-  const int P = (H + 2 * pad - (R - 1) - 1) / stride + 1;
-  const int Q = (W + 2 * pad - (S - 1) - 1) / stride + 1;
+  // MIXDQ_FLAG_PAD_AFTER: the zeros lie below and right only.  Both kernels test every tap against the image
+  // ((unsigned)hh < H && (unsigned)ww < W) whatever the padding is, so the form is the window origin without the
+  // -pad shift (origin pad 0) and the output extent of a one-sided pad; nothing in a kernel changes.
+  const bool after = flags & MIXDQ_FLAG_PAD_AFTER;
+  if (after && ((flags & MIXDQ_FLAG_UPSAMPLE2X) || pad >= R || pad >= S)) return MIXDQ_ERR_SHAPE;
+  const int pads = after ? pad : 2 * pad;
+  if (H + pads < R || W + pads < S) return MIXDQ_OK;        // no window fits (and C's division would round up)
+  const int P = (H + pads - (R - 1) - 1) / stride + 1;
+  const int Q = (W + pads - (S - 1) - 1) / stride + 1;
   if (P <= 0 || Q <= 0 || N == 0) return MIXDQ_OK;
+  if (after) pad = 0;
   IgemmParams p{};
   p.A = (const int8_t*)X_f16; p.Wt = (const int8_t*)Wt_f16; p.bias = (const __half*)bias_f16_or_null;
   p.D = (__half*)D_f16;

@@ -12,6 +12,11 @@ applies guidance and that map, writes the next UNet input and advances a step in
 DEVICE; `Sampler` captures the UNet forward + that step once into a hipGraph and replays it n_steps times with
 nothing from the host in between.  The FP32 arithmetic, rounding by rounding, is include/mixdq_math.h; its numpy
 restatement is tests/sampler_ref.py.
+
+Image-to-image starts the same loop at a later step: `img2img_start(n_steps, strength)` is the first step index t0,
+`Schedule.start(t0)` the scalars that noise the encoded image to that step's level, and
+`sample(..., init_latents=z, strength=s)` sets the device step state to t0 and replays the SAME graph n_steps - t0
+times.  `Sampler.img2img` runs VAEEncoder.encode, that loop and VAEDecoder.decode on one stream.
 """
 import numpy as np
 
@@ -47,6 +52,21 @@ def timesteps(kind: str, n_steps: int, spacing=None) -> np.ndarray:
     if spacing == "leading":
         return ((np.arange(n_steps) * (TRAIN_STEPS // n_steps))[::-1] + 1).astype(np.int64)
     raise ValueError(f"spacing must be 'trailing' or 'leading', not {spacing!r}")
+
+
+def img2img_start(n_steps: int, strength: float) -> int:
+    """The index of the first step an image-to-image run of `strength` takes out of an `n_steps` schedule: diffusers'
+    `get_timesteps`, t_start = max(n_steps - min(int(n_steps * strength), n_steps), 0), the int() of the float
+    product as written there.  strength 1.0 is the whole schedule (the image only sets the mean of the start state)."""
+    n_steps = int(n_steps)
+    if not 0.0 < strength <= 1.0:
+        raise ValueError(f"strength must be in (0, 1], not {strength!r}")
+    if n_steps < 1:
+        raise ValueError("n_steps must be at least 1")
+    t0 = max(n_steps - min(int(n_steps * strength), n_steps), 0)
+    if t0 >= n_steps:
+        raise ValueError(f"strength {strength} leaves no step of {n_steps} (int(n_steps * strength) == 0)")
+    return t0
 
 
 class Schedule:
@@ -88,6 +108,18 @@ class Schedule:
         self.coef = coef.astype(np.float32)
         self.t_table = np.concatenate([ts.astype(np.float64), [0.0]]).astype(np.float32)
         self.uses_noise = bool((self.coef[:, 2] != 0).any())
+
+    def start(self, t0: int):
+        """(a0, c0, s0) in float64 for a run that starts at step `t0` from latents z: state = a0 * z + c0 * noise (the
+        schedulers' add_noise at timesteps[t0]), first UNet input = f16(state * s0) (their scale_model_input).
+        Euler kinds: (1, sigmas[t0], 1 / sqrt(sigmas[t0]^2 + 1)); lcm: (sqrt(ac), sqrt(1 - ac), 1) at timesteps[t0]."""
+        if not 0 <= t0 < self.n_steps:
+            raise ValueError(f"t0 must be in [0, {self.n_steps}), not {t0}")
+        if self.kind == "lcm":
+            ac = alphas_cumprod()[self.timesteps[t0]]
+            return float(np.sqrt(ac)), float(np.sqrt(1.0 - ac)), 1.0
+        sig = self.sigmas[t0]
+        return 1.0, float(sig), float(1.0 / np.sqrt(sig ** 2 + 1.0))
 
 
 def schedule(kind, n_steps, spacing=None) -> Schedule:
@@ -183,16 +215,52 @@ class Sampler:
         self._step.zero_()
         self._t.copy_(self._t_table[0])
 
+    def _reset_at(self, t0, init_latents, noise, step_noise):
+        """State of step t0 of an image-to-image run: x = fl32(fl32(a0 * z) + fl32(c0 * noise)) -- two products and one
+        sum, each a torch operation of its own so that none can fuse -- UNet input = f16(fl32(x * s0)) in every row
+        block, the step index t0, the timestep t_table[t0].  The scalars travel as launch arguments (rounded to FP32
+        there); like _reset, nothing here waits for the GPU."""
+        import torch
+        B = noise.shape[0]
+        a0, c0, s0 = self.schedule.start(t0)
+        az = torch.mul(init_latents.to(torch.float32), a0)
+        cn = torch.mul(noise.to(torch.float32), c0)
+        torch.add(az, cn, out=self._x)
+        first = torch.mul(self._x, s0).to(torch.float16)
+        for r in range(self.rows_per_image):
+            self._in[r * B:(r + 1) * B].copy_(first)
+        if self._noise is not None and step_noise is not None:
+            self._noise.copy_(step_noise)
+        self._step.fill_(t0)
+        self._t.copy_(self._t_table[t0])
+
     # ---- the loop -------------------------------------------------------------------------------------------
-    def sample(self, noise, encoder_hidden_states, added_cond_kwargs=None, step_noise=None):
+    def sample(self, noise, encoder_hidden_states, added_cond_kwargs=None, step_noise=None, *, init_latents=None,
+               strength=None):
         """noise [B, C, H, W] (unit variance; FP32 or FP16), encoder_hidden_states [R, T, D] FP16 (R = B, or 2B
         under guidance), added_cond_kwargs as the UNet takes them (R rows), step_noise [n_steps, B, C, H, W]: the
         noise each stochastic step adds (required where the schedule has a non-zero c: euler_ancestral and lcm with
-        more than one step; there is no random number generator in the kernel).  Returns the FP32 latents."""
+        more than one step; there is no random number generator in the kernel).  Returns the FP32 latents.
+
+        Image-to-image: `init_latents` (FP32 or FP16, noise's shape, multiplied by the VAE's scaling_factor: what
+        VAEEncoder.encode returns) together with `strength` in (0, 1].  The run starts at step t0 =
+        img2img_start(n_steps, strength) from init_latents noised to that step's level (Schedule.start) and replays
+        the same captured graph n_steps - t0 times; step_noise keeps its [n_steps, ...] shape, rows >= t0 are read.
+        A Sampler captured by either kind of call serves the other."""
         import torch
         from mixdq_amd.quantize_sdxl import _copy_into
         if not (torch.is_tensor(noise) and noise.is_cuda and noise.dim() == 4):
             raise RuntimeError("Sampler.sample: noise should be a [B, C, H, W] GPU tensor")
+        if (init_latents is None) != (strength is None):
+            raise RuntimeError("Sampler.sample: init_latents and strength go together (both, or neither)")
+        t0 = 0
+        if init_latents is not None:
+            if not (torch.is_tensor(init_latents) and init_latents.device == noise.device
+                    and tuple(init_latents.shape) == tuple(noise.shape)
+                    and init_latents.dtype in (torch.float32, torch.float16)):
+                raise RuntimeError("Sampler.sample: init_latents should be an FP32 or FP16 tensor of noise's shape "
+                                   f"{tuple(noise.shape)} on its device")
+            t0 = img2img_start(self.n_steps, strength)
         R = noise.shape[0] * self.rows_per_image
         if encoder_hidden_states.shape[0] != R:
             raise RuntimeError(f"Sampler.sample: encoder_hidden_states should have {R} rows")
@@ -207,8 +275,11 @@ class Sampler:
         elif self._shape_key(noise, encoder_hidden_states, added_cond_kwargs) != self._key:
             raise RuntimeError("Sampler.sample: inputs differ in shape from those the step graph was captured for")
         _copy_into((self._ehs, self._added), (encoder_hidden_states, added_cond_kwargs))
-        self._reset(noise, step_noise)
-        for _ in range(self.n_steps):
+        if init_latents is None:
+            self._reset(noise, step_noise)
+        else:
+            self._reset_at(t0, init_latents, noise, step_noise)
+        for _ in range(self.n_steps - t0):
             self._graph.replay()
         return self._x.clone()
 
@@ -217,3 +288,14 @@ class Sampler:
         the same stream: nothing waits for the GPU in between.  Returns (FP32 latents, FP16 image [B, 3, 8H, 8W])."""
         latents = self.sample(noise, encoder_hidden_states, added_cond_kwargs, step_noise)
         return latents, vae.decode(latents)
+
+    def img2img(self, enc, dec, image, noise, encoder_hidden_states, added_cond_kwargs=None, *, strength,
+                step_noise=None, latent_noise=None):
+        """Image to image on one stream: `enc.encode(image, latent_noise)` (a mixdq_amd.vae.VAEEncoder; latent_noise
+        None: the posterior's mode), sample(init_latents=that, strength=strength), then `dec.decode` (a VAEDecoder) --
+        either VAE eager or under hip_graph_opt, nothing waits for the GPU in between.  noise: [B, C, H/8, W/8], what
+        is added to the encoded image.  Returns (FP32 latents, FP16 image [B, 3, H, W])."""
+        z = enc.encode(image, latent_noise)
+        latents = self.sample(noise, encoder_hidden_states, added_cond_kwargs, step_noise, init_latents=z,
+                              strength=strength)
+        return latents, dec.decode(latents)

@@ -10,6 +10,16 @@ mixdq_groupnorm_silu_quantize with its FP16 output, mixdq_linear_f16 (one q|k|v 
 mixdq_attention_f16 at head width 512 reading the column slices.  The only torch operators of a decode are the dtype /
 layout conversion of the 4-channel input and views; `hip_graph_opt(vae)` captures it.
 
+The other half, image in, latents out (diffusers' AutoencoderKL.encode), is VAEEncoder:
+
+    enc = build_vae_encoder(VAE_SDXL_CONFIG).cuda()
+    latents = enc.encode(from_uint8(pixels), noise)          # [B, 3, H, W] uint8 / FP16 / FP32 -> FP32 [B, 4, H/8, W/8]
+
+Its launches are the decoder's, plus three forms of its own: mixdq_image_to_nhwc8_f16 (the ingest: any dtype and
+strides -> FP16 NHWC with 8 channels, so that conv_in runs on the MFMA tiles), mixdq_conv2d_f16 with
+MIXDQ_FLAG_PAD_AFTER (`Downsample2D`'s 3x3 / stride 2 conv over F.pad(x, (0, 1, 0, 1)) without the padded tensor) and
+mixdq_vae_latent_sample (the posterior sample times scaling_factor).  DESIGN.md section 3.25.
+
 This is a floating-point path with no counterpart in the reference (which reaches the VAE through diffusers'
 pipeline): it is held to tolerance against the same network built from stock torch modules (tests/vae_ref.py).
 DESIGN.md section 3.23.
@@ -119,43 +129,22 @@ class VaeDecoderNet(nn.Module):
         self.conv_out = nn.Conv2d(ch[0], cfg.get("out_channels", 3), 3, padding=1)
 
 
-class VAEDecoder(nn.Module):
-    """post_quant_conv + decoder of an AutoencoderKL, parameter names as diffusers'."""
+class _VaeHalf(nn.Module):
+    """What the two halves of the AutoencoderKL share: the config, the tensors derived from the weights (dropped by a
+    load or a move, rebuilt on the next run by the subclass's `_derive`) and the GroupNorm launch with its cached
+    workspaces.  The blocks above reach all three through the `vae` argument of their `run`."""
 
     def __init__(self, cfg=None):
         super().__init__()
         self.cfg = dict(VAE_SDXL_CONFIG if cfg is None else cfg)
-        lc = self.cfg["latent_channels"]
-        self.post_quant_conv = nn.Conv2d(lc, lc, 1)
-        self.decoder = VaeDecoderNet(self.cfg)
         self.scaling_factor = float(self.cfg["scaling_factor"])
         self._cache = None         # tensors derived from the weights (rebuilt after a load or a move)
         self._gn_ws = {}           # GroupNorm workspaces, one per (shape, device)
 
-    # ---- derived weights ------------------------------------------------------------------------------------
-    def padded_conv_out(self):
-        """conv_out's weight / bias padded with zero output channels to a multiple of four (3 -> 4), the width the MFMA
-        tiles take; decode() returns the first `out_channels` of that conv."""
-        w, b = self.decoder.conv_out.weight, self.decoder.conv_out.bias
-        k = w.shape[0]
-        k4 = (k + 3) // 4 * 4
-        w4 = torch.zeros((k4,) + tuple(w.shape[1:]), dtype=w.dtype, device=w.device)
-        b4 = torch.zeros(k4, dtype=b.dtype, device=b.device)
-        w4[:k], b4[:k] = w.detach(), b.detach()
-        return w4.contiguous(memory_format=torch.channels_last), b4
-
-    def scaled_post_quant_conv(self):
-        """post_quant_conv on z / scaling_factor == the conv with weight / scaling_factor on z (the division is done
-        once, in FP32, on the 4 x 4 weight; the bias is untouched)."""
-        w = self.post_quant_conv.weight.detach()
-        return ((w.float() / self.scaling_factor).to(w.dtype).contiguous(memory_format=torch.channels_last),
-                self.post_quant_conv.bias.detach())
-
     @torch.no_grad()
     def _derived(self):
         if self._cache is None:
-            self._cache = dict(qkv=tuple(t.detach() for t in self.decoder.mid_block.attentions[0].qkv()),
-                               conv_out=self.padded_conv_out(), post_quant=self.scaled_post_quant_conv())
+            self._cache = self._derive()
         return self._cache
 
     def refresh_derived_(self):
@@ -181,6 +170,39 @@ class VAEDecoder(nn.Module):
             ws = self._gn_ws[key] = _C.groupnorm_workspace(N, H * W, C, norm.num_groups, x.device)
         return _C.groupnorm_silu_quantize(x, norm.num_groups, norm.weight, norm.bias, norm.eps, silu=silu,
                                           want_f16=True, _workspace=ws)[1]
+
+
+class VAEDecoder(_VaeHalf):
+    """post_quant_conv + decoder of an AutoencoderKL, parameter names as diffusers'."""
+
+    def __init__(self, cfg=None):
+        super().__init__(cfg)
+        lc = self.cfg["latent_channels"]
+        self.post_quant_conv = nn.Conv2d(lc, lc, 1)
+        self.decoder = VaeDecoderNet(self.cfg)
+
+    # ---- derived weights ------------------------------------------------------------------------------------
+    def padded_conv_out(self):
+        """conv_out's weight / bias padded with zero output channels to a multiple of four (3 -> 4), the width the MFMA
+        tiles take; decode() returns the first `out_channels` of that conv."""
+        w, b = self.decoder.conv_out.weight, self.decoder.conv_out.bias
+        k = w.shape[0]
+        k4 = (k + 3) // 4 * 4
+        w4 = torch.zeros((k4,) + tuple(w.shape[1:]), dtype=w.dtype, device=w.device)
+        b4 = torch.zeros(k4, dtype=b.dtype, device=b.device)
+        w4[:k], b4[:k] = w.detach(), b.detach()
+        return w4.contiguous(memory_format=torch.channels_last), b4
+
+    def scaled_post_quant_conv(self):
+        """post_quant_conv on z / scaling_factor == the conv with weight / scaling_factor on z (the division is done
+        once, in FP32, on the 4 x 4 weight; the bias is untouched)."""
+        w = self.post_quant_conv.weight.detach()
+        return ((w.float() / self.scaling_factor).to(w.dtype).contiguous(memory_format=torch.channels_last),
+                self.post_quant_conv.bias.detach())
+
+    def _derive(self):
+        return dict(qkv=tuple(t.detach() for t in self.decoder.mid_block.attentions[0].qkv()),
+                    conv_out=self.padded_conv_out(), post_quant=self.scaled_post_quant_conv())
 
     # ---- forward --------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -210,9 +232,125 @@ class VAEDecoder(nn.Module):
         return self.forward(latents)
 
 
+class VaeDownsample(nn.Module):
+    def __init__(self, c):
+        super().__init__()
+        self.conv = nn.Conv2d(c, c, 3, stride=2, padding=0)      # over F.pad(x, (0, 1, 0, 1)): padded after, not before
+
+
+class VaeDownBlock(nn.Module):
+    def __init__(self, cin, cout, n_resnets, groups, add_down):
+        super().__init__()
+        self.resnets = nn.ModuleList([VaeResnetBlock(cin if i == 0 else cout, cout, groups) for i in range(n_resnets)])
+        if add_down:
+            self.downsamplers = nn.ModuleList([VaeDownsample(cout)])
+
+    def run(self, vae, x):
+        from mixdq_amd import _C
+        for r in self.resnets:
+            x = r.run(vae, x)
+        if hasattr(self, "downsamplers"):
+            conv = self.downsamplers[0].conv    # the zeros lie below and right only: no padded tensor
+            x = _C.conv2d_f16(x, conv.weight, conv.bias, 2, 1, _pad_after=True)
+        return x
+
+
+class VaeEncoderNet(nn.Module):
+    def __init__(self, cfg):
+        super().__init__()
+        ch, g = tuple(cfg["block_out_channels"]), cfg["norm_num_groups"]
+        self.conv_in = nn.Conv2d(cfg.get("in_channels", 3), ch[0], 3, padding=1)
+        self.down_blocks = nn.ModuleList([
+            VaeDownBlock(ch[max(i - 1, 0)], ch[i], cfg["layers_per_block"], g, i != len(ch) - 1)
+            for i in range(len(ch))])
+        self.mid_block = VaeMidBlock(ch[-1], g)
+        self.conv_norm_out = nn.GroupNorm(g, ch[-1], eps=GN_EPS)
+        self.conv_out = nn.Conv2d(ch[-1], 2 * cfg["latent_channels"], 3, padding=1)
+
+
+class VAEEncoder(_VaeHalf):
+    """encoder + quant_conv of an AutoencoderKL, parameter names as diffusers'."""
+
+    def __init__(self, cfg=None):
+        super().__init__(cfg)
+        lc = self.cfg["latent_channels"]
+        self.encoder = VaeEncoderNet(self.cfg)
+        self.quant_conv = nn.Conv2d(2 * lc, 2 * lc, 1)
+
+    # ---- derived weights ------------------------------------------------------------------------------------
+    def padded_conv_in(self):
+        """conv_in's weight padded with zero INPUT channels to eight (3 -> 8), the width at which the conv runs on the
+        MFMA tiles; the ingest kernel writes the image with eight channels, 3..7 zero."""
+        w = self.encoder.conv_in.weight.detach()
+        w8 = torch.zeros((w.shape[0], 8) + tuple(w.shape[2:]), dtype=w.dtype, device=w.device)
+        w8[:, :w.shape[1]] = w
+        return w8.contiguous(memory_format=torch.channels_last), self.encoder.conv_in.bias.detach()
+
+    def _derive(self):
+        return dict(qkv=tuple(t.detach() for t in self.encoder.mid_block.attentions[0].qkv()),
+                    conv_in=self.padded_conv_in())
+
+    # ---- forward --------------------------------------------------------------------------------------------
+    def _check_image(self, image, what):
+        cin = self.encoder.conv_in.in_channels
+        if not (torch.is_tensor(image) and image.is_cuda and image.dim() == 4 and image.shape[1] == cin
+                and image.dtype in (torch.uint8, torch.float16, torch.float32)
+                and image.shape[2] % 8 == 0 and image.shape[3] % 8 == 0):
+            raise RuntimeError("VAEEncoder.%s: image should be a [B, %d, H, W] uint8, FP16 or FP32 GPU tensor with H and "
+                               "W multiples of 8" % (what, cin))
+        if self.encoder.conv_in.weight.dtype != torch.float16:
+            raise RuntimeError("VAEEncoder.%s: the encoder runs in FP16 (build_vae_encoder / .half())" % what)
+
+    @torch.no_grad()
+    def _moments(self, image):
+        from mixdq_amd import _C
+        d, enc = self._derived(), self.encoder
+        x = _C.image_to_nhwc8_f16(image)                                  # any dtype and strides -> FP16, 8 channels
+        x = _C.conv2d_f16(x, *d["conv_in"], 1, 1)
+        for blk in enc.down_blocks:
+            x = blk.run(self, x)
+        x = enc.mid_block.run(self, x)
+        x = self._gn(enc.conv_norm_out, x, True)
+        x = _C.conv2d_f16(x, enc.conv_out.weight, enc.conv_out.bias, 1, 1)
+        return _C.conv2d_f16(x, self.quant_conv.weight, self.quant_conv.bias, 1, 0)
+
+    def moments(self, image):
+        """image -> FP16 [B, 2L, H/8, W/8] channels-last: the posterior's mean (channels 0..L-1) and log-variance, as
+        diffusers' `vae.quant_conv(vae.encoder(image))`."""
+        self._check_image(image, "moments")
+        return self._moments(image)
+
+    @torch.no_grad()
+    def forward(self, image, noise=None):
+        from mixdq_amd import _C
+        self._check_image(image, "encode")
+        if noise is not None:
+            want = (image.shape[0], self.cfg["latent_channels"], image.shape[2] // 8, image.shape[3] // 8)
+            if not (torch.is_tensor(noise) and noise.device == image.device and noise.dtype == torch.float32
+                    and tuple(noise.shape) == want):
+                raise RuntimeError("VAEEncoder.encode: noise should be an FP32 tensor of shape %s on the image's device"
+                                   % (want,))
+            noise = noise.contiguous(memory_format=torch.channels_last)
+        return _C.vae_latent_sample(self._moments(image), noise, self.scaling_factor)
+
+    def encode(self, image, noise=None):
+        """image [B, 3, H, W] (uint8: a pixel u is u / 127.5 - 1; FP16 / FP32: already in [-1, 1]; any strides; H and
+        W multiples of 8) -> FP32 [B, L, H/8, W/8] channels-last, already multiplied by scaling_factor: with `noise`
+        (FP32, the result's shape) diffusers' `vae.encode(x).latent_dist.sample() * scaling_factor`, without it
+        `.mode() * scaling_factor`.  What Sampler.sample(init_latents=...) takes."""
+        return self.forward(image, noise)
+
+
 def to_uint8(image):
     """(image / 2 + 0.5).clamp(0, 1) * 255, rounded: uint8, same shape."""
     return ((image.to(torch.float32) / 2 + 0.5).clamp(0, 1) * 255).round().to(torch.uint8)
+
+
+def from_uint8(pixels):
+    """The inverse of to_uint8: uint8 -> FP16 in [-1, 1], f16(f32(u) * f32(2 / 255) - 1) with each FP32 operation
+    rounded -- the ingest kernel's uint8 arithmetic (mixdq_image_to_nhwc8_f16) restated in torch.  For every u it is
+    f16(u / 127.5 - 1), diffusers' (u / 255) * 2 - 1 in FP32 rounded to FP16, and to_uint8 of it is u."""
+    return (pixels.to(torch.float32) * torch.tensor(2.0 / 255.0, dtype=torch.float32) - 1.0).to(torch.float16)
 
 
 def state_dict_names(cfg=None):
@@ -235,6 +373,25 @@ def state_dict_names(cfg=None):
     return [n + sfx for n in names for sfx in (".weight", ".bias")]
 
 
+def encoder_state_dict_names(cfg=None):
+    """The parameter names (diffusers') of the encoder half of an AutoencoderKL with this config, written out from
+    the layer list rather than read off the modules."""
+    cfg = VAE_SDXL_CONFIG if cfg is None else cfg
+    ch = tuple(cfg["block_out_channels"])
+    names = ["quant_conv", "encoder.conv_in"]
+    res = lambda p, short: [p + s for s in ("norm1", "conv1", "norm2", "conv2") + (("conv_shortcut",) if short else ())]
+    for i in range(len(ch)):
+        for j in range(cfg["layers_per_block"]):
+            names += res(f"encoder.down_blocks.{i}.resnets.{j}.", j == 0 and ch[max(i - 1, 0)] != ch[i])
+        if i != len(ch) - 1:
+            names.append(f"encoder.down_blocks.{i}.downsamplers.0.conv")
+    names += ["encoder.mid_block.attentions.0." + s for s in ("group_norm", "to_q", "to_k", "to_v", "to_out.0")]
+    for j in range(2):
+        names += res(f"encoder.mid_block.resnets.{j}.", False)
+    names += ["encoder.conv_norm_out", "encoder.conv_out"]
+    return [n + sfx for n in names for sfx in (".weight", ".bias")]
+
+
 def build_vae_decoder(cfg=None, seed: int = 42, device=None, dtype=torch.float16) -> VAEDecoder:
     """A decoder with synthetic weights (randn * 0.02 per conv / linear layer, as build_unet's), FP16, channels-last."""
     from mixdq_amd.unet import init_synthetic_weights
@@ -247,9 +404,23 @@ def build_vae_decoder(cfg=None, seed: int = 42, device=None, dtype=torch.float16
     return vae.eval()
 
 
+def build_vae_encoder(cfg=None, seed: int = 42, device=None, dtype=torch.float16) -> VAEEncoder:
+    """An encoder with synthetic weights (as build_vae_decoder's), FP16, channels-last."""
+    from mixdq_amd.unet import init_synthetic_weights
+    vae = VAEEncoder(cfg)
+    init_synthetic_weights(vae, seed)
+    vae = vae.to(dtype=dtype)
+    if device is not None:
+        vae = vae.to(device)
+    vae = vae.to(memory_format=torch.channels_last)
+    return vae.eval()
+
+
 def parameter_counts(vae) -> "OrderedDict[str, int]":
-    """Parameters under `decoder.` and under `post_quant_conv.`."""
-    out = OrderedDict(decoder=0, post_quant_conv=0)
+    """Parameters by top-level module: `decoder` and `post_quant_conv` (a VAEDecoder), `encoder` and `quant_conv` (a
+    VAEEncoder)."""
+    out = OrderedDict((k, 0) for k in (("encoder", "quant_conv") if isinstance(vae, VAEEncoder) else
+                                       ("decoder", "post_quant_conv")))
     for n, p in vae.named_parameters():
         out[n.split(".")[0]] += p.numel()
     return out
