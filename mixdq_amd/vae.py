@@ -130,15 +130,15 @@ class VaeDecoderNet(nn.Module):
 
 
 class _VaeHalf(nn.Module):
-    """What the two halves of the AutoencoderKL share: the config, the tensors derived from the weights (dropped by a
-    load or a move, rebuilt on the next run by the subclass's `_derive`) and the GroupNorm launch with its cached
-    workspaces.  The blocks above reach all three through the `vae` argument of their `run`."""
+    """What the two halves of the AutoencoderKL share: the config, the tensors derived from the weights (rewritten in
+    place by a load; dropped by a move and rebuilt on the next run by the subclass's `_derive`) and the GroupNorm launch
+    with its cached workspaces.  The blocks above reach all three through the `vae` argument of their `run`."""
 
     def __init__(self, cfg=None):
         super().__init__()
         self.cfg = dict(VAE_SDXL_CONFIG if cfg is None else cfg)
         self.scaling_factor = float(self.cfg["scaling_factor"])
-        self._cache = None         # tensors derived from the weights (rebuilt after a load or a move)
+        self._cache = None         # tensors derived from the weights (rewritten by a load, rebuilt after a move)
         self._gn_ws = {}           # GroupNorm workspaces, one per (shape, device)
 
     @torch.no_grad()
@@ -156,9 +156,24 @@ class _VaeHalf(nn.Module):
         self.refresh_derived_()
         return super()._apply(fn, recurse)
 
+    @torch.no_grad()
     def load_state_dict(self, *args, **kwargs):
+        """nn.Module.load_state_dict, then every derived tensor is rewritten IN PLACE, as the load rewrites the
+        parameters themselves: a graph captured from this half (hip_graph_opt) holds the addresses of both, and its
+        replays see the new weights.  The GroupNorm workspaces depend on shapes only and stay.  (A move or a dtype
+        change -- .to(), .half() -- gives every tensor a new address: capture after it, not before.)"""
         out = super().load_state_dict(*args, **kwargs)
-        self.refresh_derived_()
+        if self._cache is not None:
+            new = self._derive()
+            same = lambda t, n: (t.shape, t.dtype, t.device) == (n.shape, n.dtype, n.device)
+            if new.keys() != self._cache.keys() or not all(
+                    same(t, n) for k in new for t, n in zip(self._cache[k], new[k])):
+                self.refresh_derived_()           # (load_state_dict(assign=True) with other tensors: start over)
+            else:
+                for k in new:
+                    for t, n in zip(self._cache[k], new[k]):
+                        if t.data_ptr() != n.data_ptr():      # (a derived bias may BE the parameter: already loaded)
+                            t.copy_(n)
         return out
 
     def _gn(self, norm, x, silu):

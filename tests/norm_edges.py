@@ -20,6 +20,7 @@ SELF_FINALIZE_MAX = 64       # nchunk <= 64: the apply blocks finalize themselve
 TAB_MIN = 2 << 20            # MIXDQ_GN_SILU_TAB_MIN / the GEGLU table threshold: elements
 LN_MAX_CHUNKS = 4            # kLnMaxChunks
 ELEMENT_CAP = 4 << 20        # "about 4 Mi elements" per tensor
+VAE_EPS = (1e-6, 1e-5)       # mixdq_amd.vae.GN_EPS, and the UNet's
 
 
 def cdiv(a, b):
@@ -91,8 +92,8 @@ def gn_launch(N, HW, C, G, silu, tab_mode=-1, stats_unroll=0):
     return g
 
 
-def _gn(name, N, HW, C, G, silu, C1=None):
-    c = dict(name=name, N=N, HW=HW, C=C, G=G, silu=silu, C1=C if C1 is None else C1)
+def _gn(name, N, HW, C, G, silu, C1=None, eps=1e-5):
+    c = dict(name=name, N=N, HW=HW, C=C, G=G, silu=silu, C1=C if C1 is None else C1, eps=eps)
     c["geom"] = gn_launch(N, HW, C, G, silu)
     c["geom_tab"] = gn_launch(N, HW, C, G, silu, tab_mode=1)          # under MIXDQ_GN_SILU_TAB=1
     assert c["geom"] is not None, name
@@ -127,6 +128,15 @@ def gn_cases():
     out.append(_gn("c96_split24", 3, 43, 96, 8, False, C1=24))
     out.append(_gn("c320_split168", 1, 390, 320, 32, True, C1=168))
     out.append(_gn("c320_split160", 1, 7, 320, 32, False, C1=160))
+    # the VAE's widths (mixdq_amd.vae: 32 groups, eps 1e-6), SiLU and plain, at both eps.  C = 128: groups of 4 channels,
+    # every octet straddles two, 32 reducing threads of 256; HW = 16384 is 2 Mi elements (the table pass by the size
+    # rule) in 512 chunks.  C = 512 at HW = 8192 is the 4 Mi element cap, 512 chunks again.
+    for eps in VAE_EPS:
+        for silu in (True, False):
+            out.append(_gn("vae_c128_hw70", 1, 70, 128, 32, silu, eps=eps))
+            out.append(_gn("vae_c128_hw16384", 1, 16384, 128, 32, silu, eps=eps))
+            out.append(_gn("vae_c256_hw1040", 2, 1040, 256, 32, silu, eps=eps))      # 130 chunks: the finalize launch
+            out.append(_gn("vae_c512_hw8192", 1, 8192, 512, 32, silu, eps=eps))
     return out
 
 
@@ -134,7 +144,7 @@ GN_REFUSED = [(1, 16, 8200, 8), (1, 16, 2048, 512), (1, 16, 36, 6)]     # OC > 1
 
 
 def gn_id(c):
-    return f"{c['name']}_n{c['N']}_{'silu' if c['silu'] else 'plain'}"
+    return f"{c['name']}_n{c['N']}_{'silu' if c['silu'] else 'plain'}" + ("" if c["eps"] == 1e-5 else f"_eps{c['eps']:g}")
 
 
 def gn_inputs(c, seed=0):

@@ -98,6 +98,9 @@ CONV = [  # N, C, H, W, K, ksize, stride, pad, bias
     (1, 640, 16, 16, 320, 1, 1, 0, True),      # a 1x1 shortcut
     (2, 64, 13, 11, 72, 3, 2, 1, False),       # stride 2, odd sizes
     (1, 128, 5, 5, 64, 3, 1, 1, True), (3, 8, 7, 9, 12, 3, 1, 0, True),
+    # 1,179,648 outputs: more than the one-output-per-thread kernel's capped grid has threads (4096 x 256), so its
+    # grid-stride loop makes a second trip (the VAE decoder's conv_in at 128 x 128 latents: 8.4 M outputs)
+    (1, 4, 64, 72, 256, 3, 1, 1, True),
 ]
 
 

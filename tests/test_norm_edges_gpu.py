@@ -37,26 +37,26 @@ def bits(a):
 
 @pytest.mark.parametrize("case", GN, ids=[ne.gn_id(c) for c in GN])
 def test_groupnorm_edge(C, oracle, case):
-    N, HW, Cc, G, silu, C1 = (case[k] for k in ("N", "HW", "C", "G", "silu", "C1"))
+    N, HW, Cc, G, silu, C1, eps = (case[k] for k in ("N", "HW", "C", "G", "silu", "C1", "eps"))
     x, gamma, beta, (s_inv, zp) = ne.gn_inputs(case)
     xd, g, b, qp = t(x), t(gamma), t(beta), (scal(s_inv), scal(zp))
-    q, h = C.groupnorm_silu_quantize(xd, G, g, b, 1e-5, *qp, silu=silu, want_f16=True)
-    q_ref, h_ref = oracle.groupnorm_silu_quantize(x, gamma, beta, 1e-5, G, silu, s_inv, zp, C.FLAGS & 1)
+    q, h = C.groupnorm_silu_quantize(xd, G, g, b, eps, *qp, silu=silu, want_f16=True)
+    q_ref, h_ref = oracle.groupnorm_silu_quantize(x, gamma, beta, eps, G, silu, s_inv, zp, C.FLAGS & 1)
     assert np.array_equal(bits(h), bits(h_ref)), f"{(bits(h) != bits(h_ref)).sum()} fp16 values differ"
     assert np.array_equal(q.cpu().numpy(), q_ref)
     # the output-only variants agree with the combined call
-    q2, none = C.groupnorm_silu_quantize(xd, G, g, b, 1e-5, *qp, silu=silu)
+    q2, none = C.groupnorm_silu_quantize(xd, G, g, b, eps, *qp, silu=silu)
     assert none is None and torch.equal(q2, q)
-    none, h2 = C.groupnorm_silu_quantize(xd, G, g, b, 1e-5, silu=silu, want_f16=True)
+    none, h2 = C.groupnorm_silu_quantize(xd, G, g, b, eps, silu=silu, want_f16=True)
     assert none is None and torch.equal(h2, h)
     if C1 != Cc:                   # two sources read in place == the concatenated tensor
-        q3, h3 = C.groupnorm_silu_quantize(t(x[..., :C1]), G, g, b, 1e-5, *qp, silu=silu, want_f16=True,
+        q3, h3 = C.groupnorm_silu_quantize(t(x[..., :C1]), G, g, b, eps, *qp, silu=silu, want_f16=True,
                                            x2=t(x[..., C1:]))
         assert torch.equal(q3, q) and torch.equal(h3, h)
     # the definition in float64: the normalised value rounded once to FP16; SiLU of that value, rounded once more
-    _, pre = C.groupnorm_silu_quantize(xd, G, g, b, 1e-5, silu=False, want_f16=True)
+    _, pre = C.groupnorm_silu_quantize(xd, G, g, b, eps, silu=False, want_f16=True)
     pre = pre.cpu().numpy()
-    ok = ne.within_norm_bound(pre, ne.groupnorm64(x, gamma, beta, 1e-5, G))
+    ok = ne.within_norm_bound(pre, ne.groupnorm64(x, gamma, beta, eps, G))
     assert ok.all(), f"{(~ok).sum()} of {ok.size} pre-activations outside 1.001 ulp + 2e-6"
     if silu:
         ref = ne.silu64(pre.astype(np.float64)).astype(np.float16).astype(np.float64)

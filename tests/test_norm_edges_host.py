@@ -79,6 +79,29 @@ def test_groupnorm_cases_reach_the_apply_pass_forms():
                                       and c["N"] * c["HW"] * c["C"] >= ne.TAB_MIN) for c in GN)
 
 
+def test_groupnorm_cases_reach_the_vae_widths():
+    """mixdq_amd.vae's GroupNorms: 32 groups at C = 128, 256, 512, eps 1e-6 (and 1e-5), SiLU and plain."""
+    vae = [c for c in GN if c["name"].startswith("vae_")]
+    assert {c["eps"] for c in vae} == {1e-6, 1e-5} == set(ne.VAE_EPS) and all(c["eps"] == 1e-5 for c in GN if c not in vae)
+    assert all(c["G"] == 32 for c in vae) and {c["C"] for c in vae} == {128, 256, 512}
+    for eps in ne.VAE_EPS:
+        mine = [c for c in vae if c["eps"] == eps]
+        for C in (128, 256, 512):
+            assert {True, False} == {c["silu"] for c in mine if c["C"] == C}, (eps, C)
+        # groups of 4 channels under 32 groups: every octet straddles two groups, 32 reducing threads of 256
+        cg4 = [c for c in mine if c["geom"]["cg"] == 4 and c["G"] == 32]
+        assert cg4 and all(c["geom"]["threads"] == 256 and c["geom"]["OC"] == 16 for c in cg4)
+        assert {70, 16384} <= {c["HW"] for c in cg4}
+        # the table pass by the default size rule at cg == 4 (2 Mi elements), and 512 chunks
+        assert any(c["geom"]["table"] and c["N"] * c["HW"] * c["C"] == ne.TAB_MIN for c in cg4)
+        assert any(c["geom"]["nchunk"] == 512 for c in cg4)
+        assert any(not c["silu"] and c["geom"]["nchunk"] == 512 and not c["geom"]["table"] for c in cg4)
+        assert any(c["C"] == 512 and c["HW"] == 8192 and c["N"] * c["HW"] * c["C"] == ne.ELEMENT_CAP
+                   and c["geom"]["nchunk"] == 512 for c in mine)
+        assert any(c["C"] == 256 and c["geom"]["finalize"] == "launch" for c in mine)
+    assert len({ne.gn_id(c) for c in GN}) == len(GN)
+
+
 def test_groupnorm_two_source_splits():
     sp = [c for c in GN if c["C1"] != c["C"]]
     assert {"inside", "boundary"} == {c["split"] for c in sp}
@@ -113,8 +136,8 @@ def test_groupnorm_oracle_geometry_is_the_generators(oracle):
 @pytest.mark.parametrize("case", GN, ids=[ne.gn_id(c) for c in GN])
 def test_groupnorm_oracle_within_the_float64_bound(oracle, case):
     x, gamma, beta, (s_inv, zp) = ne.gn_inputs(case)
-    _, pre = oracle.groupnorm_silu_quantize(x, gamma, beta, 1e-5, case["G"], False, s_inv, zp)
-    ok = ne.within_norm_bound(pre, ne.groupnorm64(x, gamma, beta, 1e-5, case["G"]))
+    _, pre = oracle.groupnorm_silu_quantize(x, gamma, beta, case["eps"], case["G"], False, s_inv, zp)
+    ok = ne.within_norm_bound(pre, ne.groupnorm64(x, gamma, beta, case["eps"], case["G"]))
     assert ok.all(), f"{(~ok).sum()} of {ok.size} outside the bound"
 
 

@@ -243,6 +243,33 @@ def test_vae_graph_replay_equals_eager_bit_for_bit(small):
     assert torch.equal(bits(enc.encode(small["image"], small["noise"])), bits(small["latents"]))
 
 
+def test_vae_graph_replay_sees_a_later_load_state_dict(small):
+    """A captured encode holds the addresses of the parameters AND of the tensors derived from them (q|k|v, the
+    8-channel conv_in) and of the GroupNorm workspaces; load_state_dict rewrites the first two in place and keeps the
+    third, so a replay computes with the new weights."""
+    from mixdq_amd import vae as V
+    from mixdq_amd.quantize_sdxl import hip_graph_opt
+    image, noise = small["image"], small["noise"]
+    enc = V.build_vae_encoder(small["cfg"], seed=11, device=DEV)
+    donor = V.build_vae_encoder(small["cfg"], seed=12, device=DEV)
+    want = donor.encode(image, noise)
+    hip_graph_opt(enc)
+    before = enc.encode(image, noise).clone()
+    assert torch.equal(bits(before), bits(small["latents"]))
+    held = {k: list(v) for k, v in enc._derived().items()}          # (kept alive: their addresses cannot be handed out again)
+    ptrs = {k: [t.data_ptr() for t in v] for k, v in held.items()}
+    assert set(ptrs) == {"qkv", "conv_in"}
+    ws = {k: v.data_ptr() for k, v in enc._gn_ws.items()}
+    assert ws
+    enc.load_state_dict(donor.state_dict())
+    assert {k: [t.data_ptr() for t in v] for k, v in enc._derived().items()} == ptrs
+    assert {k: v.data_ptr() for k, v in enc._gn_ws.items()} == ws
+    after = enc.encode(image, noise)
+    assert len(enc.forward._cached) == 1                               # a replay, not a new capture
+    assert torch.equal(bits(after), bits(want))
+    assert not torch.equal(bits(after), bits(before))
+
+
 def test_encode_refuses_what_it_cannot_run(small):
     enc, image, noise = small["enc"], small["image"], small["noise"]
     for bad in (image[:, :2], image[:, :, :60], image.double(), image[0]):

@@ -60,8 +60,14 @@ def test_load_state_dict_round_trips_and_drops_the_derived_weights():
     sd = a.state_dict()
     assert not torch.equal(sd["encoder.conv_in.weight"], b.state_dict()["encoder.conv_in.weight"])
     qkv_before, conv_in_before = b._derived()["qkv"][0].clone(), b._derived()["conv_in"][0].clone()
+    ptrs = {k: [t.data_ptr() for t in v] for k, v in b._derived().items()}
+    assert set(ptrs) == {"qkv", "conv_in"}
+    b._gn_ws["kept"] = ws = object()                 # (the GroupNorm workspaces depend on shapes only: a load keeps them)
     missing, unexpected = b.load_state_dict(sd)
     assert not missing and not unexpected
+    # the derived tensors are rewritten at their addresses (a captured graph holds them), not dropped
+    assert b._cache is not None and {k: [t.data_ptr() for t in v] for k, v in b._cache.items()} == ptrs
+    assert b._gn_ws == {"kept": ws}
     got = b.state_dict()
     assert set(got) == set(sd) and all(torch.equal(got[k], sd[k]) for k in sd)
     attn = b.encoder.mid_block.attentions[0]
@@ -70,10 +76,18 @@ def test_load_state_dict_round_trips_and_drops_the_derived_weights():
     assert torch.equal(w, torch.cat([attn.to_q.weight, attn.to_k.weight, attn.to_v.weight])) and w.shape == (1536, 512)
     assert torch.equal(bias, torch.cat([attn.to_q.bias, attn.to_k.bias, attn.to_v.bias]))
     assert torch.equal(b._derived()["conv_in"][0][:, :3], a.encoder.conv_in.weight)
-    # a move drops them too; the decoder keeps the same handling from the shared base
+    assert not b._derived()["conv_in"][0][:, 3:].any() and torch.equal(b._derived()["conv_in"][1], a.encoder.conv_in.bias)
+    # a move or a dtype change does drop them, and the workspaces; the decoder keeps the same handling from the shared base
     b._derived()
     b.float()
+    assert b._cache is None and b._gn_ws == {}
+    b._derived()
+    b.half()
     assert b._cache is None
+    # load_state_dict(assign=True) puts other tensors in the parameters' place: with another dtype the cache starts over
+    b._derived()
+    b.load_state_dict({k: v.float() for k, v in sd.items()}, assign=True)
+    assert b._cache is None and b._derived()["conv_in"][0].dtype == torch.float32
     assert isinstance(b, V._VaeHalf) and isinstance(V.build_vae_decoder(SMALL), V._VaeHalf)
 
 

@@ -67,6 +67,32 @@ def test_vae_graph_replay_equals_eager_bit_for_bit(small):
     assert torch.equal(bits(vae.decode(small["latents"])), bits(small["image"]))
 
 
+def test_vae_graph_replay_sees_a_later_load_state_dict(small):
+    """A captured decode holds the addresses of the parameters AND of the tensors derived from them (q|k|v, the padded
+    conv_out, the scaled post_quant_conv) and of the GroupNorm workspaces; load_state_dict rewrites the first two in
+    place and keeps the third, so a replay computes with the new weights."""
+    from mixdq_amd import vae as V
+    from mixdq_amd.quantize_sdxl import hip_graph_opt
+    vae = V.build_vae_decoder(small["cfg"], seed=11, device=DEV)
+    donor = V.build_vae_decoder(small["cfg"], seed=12, device=DEV)
+    want = donor.decode(small["latents"])
+    hip_graph_opt(vae)
+    before = vae.decode(small["latents"]).clone()
+    assert torch.equal(bits(before), bits(small["image"]))
+    held = {k: list(v) for k, v in vae._derived().items()}          # (kept alive: their addresses cannot be handed out again)
+    ptrs = {k: [t.data_ptr() for t in v] for k, v in held.items()}
+    assert set(ptrs) == {"qkv", "conv_out", "post_quant"}
+    ws = {k: v.data_ptr() for k, v in vae._gn_ws.items()}
+    assert ws
+    vae.load_state_dict(donor.state_dict())
+    assert {k: [t.data_ptr() for t in v] for k, v in vae._derived().items()} == ptrs
+    assert {k: v.data_ptr() for k, v in vae._gn_ws.items()} == ws
+    after = vae.decode(small["latents"])
+    assert len(vae.forward._cached) == 1                               # a replay, not a new capture
+    assert torch.equal(bits(after), bits(want))
+    assert not torch.equal(bits(after), bits(before))
+
+
 def test_vae_batch_row_equals_the_image_alone(small):
     vae = small["vae"]
     for i in range(2):

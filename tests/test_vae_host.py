@@ -53,8 +53,14 @@ def test_load_state_dict_round_trips_and_drops_the_derived_weights():
     sd = a.state_dict()
     assert not torch.equal(sd["decoder.conv_in.weight"], b.state_dict()["decoder.conv_in.weight"])
     qkv_before = b._derived()["qkv"][0].clone()
+    ptrs = {k: [t.data_ptr() for t in v] for k, v in b._derived().items()}
+    assert set(ptrs) == {"qkv", "conv_out", "post_quant"}
+    b._gn_ws["kept"] = ws = object()                 # (the GroupNorm workspaces depend on shapes only: a load keeps them)
     missing, unexpected = b.load_state_dict(sd)
     assert not missing and not unexpected
+    # the derived tensors are rewritten at their addresses (a captured graph holds them), not dropped
+    assert b._cache is not None and {k: [t.data_ptr() for t in v] for k, v in b._cache.items()} == ptrs
+    assert b._gn_ws == {"kept": ws}
     got = b.state_dict()
     assert set(got) == set(sd) and all(torch.equal(got[k], sd[k]) for k in sd)
     attn = b.decoder.mid_block.attentions[0]
@@ -65,6 +71,22 @@ def test_load_state_dict_round_trips_and_drops_the_derived_weights():
     # z / scaling_factor is folded into post_quant_conv's 4 x 4 weight, in FP32
     pw, pb = b._derived()["post_quant"]
     assert torch.equal(pw, (b.post_quant_conv.weight.float() / 0.13025).half()) and torch.equal(pb, b.post_quant_conv.bias)
+    w4, b4 = b._derived()["conv_out"]
+    assert torch.equal(w4[:3], a.decoder.conv_out.weight) and not w4[3].any()
+    assert torch.equal(b4[:3], a.decoder.conv_out.bias) and not b4[3].any()
+    # a second load (back to b's first weights) is seen too: nothing was left aliasing a temporary
+    b.load_state_dict(V.build_vae_decoder(SMALL, seed=2).state_dict())
+    assert torch.equal(b._derived()["qkv"][0], qkv_before) and b._derived()["qkv"][0].data_ptr() == ptrs["qkv"][0]
+    # load_state_dict(assign=True) puts other tensors in the parameters' place: with another dtype the cache starts over
+    b.load_state_dict({k: v.float() for k, v in sd.items()}, assign=True)
+    assert b._cache is None and b._gn_ws == {} and b._derived()["qkv"][0].dtype == torch.float32
+    # a move or a dtype change drops the derived tensors and the workspaces
+    b._gn_ws["dropped"] = object()
+    b.half()
+    assert b._cache is None and b._gn_ws == {}
+    b._derived()
+    b.to("cpu", torch.float32)
+    assert b._cache is None
 
 
 def test_conv_out_is_padded_to_four_channels_and_sliced_back():
@@ -93,3 +115,26 @@ def test_decode_refuses_what_it_cannot_run():
     vae = V.build_vae_decoder(SMALL)
     with pytest.raises(RuntimeError, match="GPU tensor"):
         vae.decode(torch.zeros(1, 4, 8, 8))
+
+
+def test_the_conv_launch_enumeration_covers_the_networks_geometries():
+    """The list is derived; this names what it must contain (and that the modules built from the same config hold
+    exactly these weight shapes, so that a layer added to the network without the walk above shows)."""
+    from tests.vae_layers import LAUNCHES
+    got = set(LAUNCHES)
+    for cin, cout in ((128, 128), (128, 256), (256, 256), (256, 512), (512, 512), (512, 256), (256, 128)):
+        assert (cin, cout, 3, 1, None, False) in got, (cin, cout)
+    for c in (128, 256, 512):
+        assert (c, c, 3, 1, None, True) in got and (c, c, 3, 2, "pad_after", False) in got, c
+    assert {g[:2] for g in got if g[2] == 1 and g[0] > 8} == {(128, 256), (256, 512), (512, 256), (256, 128)}
+    assert {g[0] for g in got if g[4] == "upsample2x"} == {512, 256}
+    assert {(8, 128, 3, 1, None, False), (128, 4, 3, 1, None, False), (512, 8, 3, 1, None, False),
+            (8, 8, 1, 1, None, False), (4, 4, 1, 1, None, False), (4, 512, 3, 1, None, False)} <= got
+    assert all(residual is False or (cin == cout and k == 3 and flag is None) for cin, cout, k, _, flag, residual in got)
+    assert len(LAUNCHES) == len(got) == 25
+    # the weight shapes of the two modules, with the derived ones in place of the weights they stand for
+    dec, enc = V.build_vae_decoder(V.VAE_SDXL_CONFIG), V.build_vae_encoder(V.VAE_SDXL_CONFIG)
+    shapes = {tuple(p.shape) for m in (dec, enc) for n, p in m.named_parameters() if p.dim() == 4}
+    shapes -= {tuple(dec.decoder.conv_out.weight.shape), tuple(enc.encoder.conv_in.weight.shape)}
+    shapes |= {tuple(dec.padded_conv_out()[0].shape), tuple(enc.padded_conv_in()[0].shape)}
+    assert shapes == {(cout, cin, k, k) for cin, cout, k, _, _, _ in got}
