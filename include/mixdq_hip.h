@@ -607,6 +607,14 @@ int mixdq_igemm_select_id_geglu(int64_t M, int N, int k_total, int w4);
 /* ... and for the GEMM + GEGLU launch on packed-W2 weights; -1 = invalid (N % 32 or K % 64 != 0). */
 int mixdq_igemm_select_id_geglu_w2(int64_t M, int N, int k_total);
 
+/* Tile configurations this library was compiled with.  family: 0 INT8 GEMM/conv (all ids), 1 FP16,
+   2 grouped, 3 quantize-in-prologue (f16in), 5 LDS-halo conv.  (4, GEMM+LayerNorm, is not reported: ids 44, 45
+   and 56 are the cases of csrc/igemm_ln.hip.)  Returns the number of configurations of the family (negative:
+   unknown family).  With 0 <= index < that number and out != NULL, fills out[0..9]: families 0-3: id, BM, BN,
+   BK, STAGES, WM, WN, KSPLIT, MT, bits (1 four-phase loop, 2 takes packed W2, 4 takes GEMM+GEGLU); family 5:
+   id, TH, TW, BN, CK, WNG, 0... */
+int mixdq_tile_config(int family, int index, int* out);
+
 /* Tile id of the LDS-resident-halo kernel (csrc/iconv.hip) that mixdq_qconv2d_w8a8[_table] runs this
  * INT8 conv on when no tile is forced -- 90: 8 x 16 output pixels x 80 channels per workgroup, 91:
  * 8 x 8 x 80, 92: 16 x 16 x 80 (64-byte channel chunks), 93: 16 x 16 x 160 (K % 160 == 0; the choice from

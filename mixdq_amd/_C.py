@@ -105,31 +105,38 @@ def igemm_select(M: int, N: int, k_align: int, k_total: int = 0):
                                     ctypes.byref(bk), ctypes.byref(st)), "igemm_select")
     return bm.value, bn.value, bk.value, st.value
 
-# Kernel configurations of the INT8 GEMM / conv family (csrc/igemm.hip MIXDQ_IGEMM_CONFIGS):
-# id -> (BM, BN, BK, STAGES).  `_cfg=id` forces one (tuning and tests); 0 = automatic.
-IGEMM_CONFIGS = {1: (64, 64, 64, 2), 3: (128, 128, 64, 2), 4: (64, 64, 128, 3),
-                 13: (256, 128, 64, 3), 14: (256, 256, 64, 3), 15: (128, 256, 64, 3),
-                 18: (256, 128, 128, 2), 20: (256, 256, 128, 2), 25: (128, 320, 128, 2),
-                 27: (128, 320, 128, 2),   # the same tile on 16 waves of 16 x 160 (16x16x64 MFMAs)
-                 28: (128, 320, 128, 2),   # ... on 16 waves of 32 x 80 (7 fragment reads per 10 MFMAs instead of 11)
-                 35: (128, 128, 64, 3), 37: (64, 64, 128, 3), 41: (64, 128, 128, 3),
-                 # 16x16x64-MFMA tiles (exactly one workgroup per CU on the UNet's M = 1024 / 4096
-                 # layers; 45 / 56: deeper pipelines) and the 4- and 5-stage 128x320x64 tiles
-                 42: (64, 80, 128, 3), 43: (64, 240, 128, 3), 44: (128, 80, 128, 3),
-                 45: (64, 80, 128, 4), 46: (128, 320, 64, 4), 47: (128, 320, 64, 5), 56: (64, 80, 128, 6),
-                 # 256x256x128 on the four-phase loop (2 x 4 waves of 128x64, 16x16x64 MFMAs)
-                 70: (256, 256, 128, 2),
-                 # ... and its persistent form: one workgroup per CU walking its tiles (csrc/igemm_pp.h); what the
-                 # automatic choice takes instead of 70 where a CU has more than one tile
-                 71: (256, 256, 128, 2)}
+# The tile tables, as the LOADED library reports them (mixdq_tile_config), not a copy of the tables in csrc/.
+if not hasattr(_lib, "mixdq_tile_config"):
+    raise ImportError(f"{LIB_PATH} does not export mixdq_tile_config; mixdq_amd._C reads its tile tables from the "
+                      "library (rebuild with `python -m mixdq_amd.build --force`)")
+_lib.mixdq_tile_config.argtypes = [_i32, _i32, _vp]
+_lib.mixdq_tile_config.restype = _i32
 
+
+def tile_family(family):
+    """The rows (10 ints each) of one family of mixdq_tile_config."""
+    row = (ctypes.c_int * 10)()
+    rows = []
+    for i in range(_lib.mixdq_tile_config(family, 0, None)):
+        _lib.mixdq_tile_config(family, i, row)
+        rows.append(tuple(row))
+    return rows
+
+
+_TILES = tile_family(0)
+# Kernel configurations of the INT8 GEMM / conv family: id -> (BM, BN, BK, STAGES).  `_cfg=id` forces one (tuning
+# and tests); 0 = automatic.
+IGEMM_CONFIGS = {r[0]: r[1:5] for r in _TILES}
 # id -> (WM, WN, KSPLIT, MT): wave grid, k-split groups and MFMA shape of each configuration (the template
 # arguments that tell two configurations of one tile shape apart in a kernel trace)
-IGEMM_WAVES = {1: (2, 2, 1, 32), 3: (2, 2, 1, 32), 4: (2, 2, 1, 32), 13: (4, 2, 1, 32), 14: (4, 2, 1, 32),
-               15: (2, 4, 1, 32), 18: (4, 2, 1, 32), 20: (4, 2, 1, 32), 25: (4, 2, 1, 32), 27: (8, 2, 1, 16),
-               28: (4, 4, 1, 16), 35: (4, 2, 1, 32), 37: (2, 2, 2, 32), 41: (2, 4, 1, 32), 42: (4, 1, 2, 16),
-               43: (4, 1, 2, 16), 44: (4, 1, 2, 16), 45: (4, 1, 2, 16), 46: (4, 2, 1, 32), 47: (4, 2, 1, 32),
-               56: (4, 1, 2, 16), 70: (2, 4, 1, 16), 71: (2, 4, 1, 16)}
+IGEMM_WAVES = {r[0]: r[5:9] for r in _TILES}
+# configuration ids a packed-W2 launch cannot take (csrc/igemm.hip w2_tile_ok)
+W2_INADMISSIBLE = tuple(sorted(r[0] for r in _TILES if not r[9] & 2))
+F16_CONFIGS = tuple(sorted(r[0] for r in tile_family(1)))       # the FP16 layers' tiles (one accumulation order)
+GROUPED_CONFIGS = tuple(sorted(r[0] for r in tile_family(2)))   # the ids qlinear_grouped's _cfg takes
+F16IN_CONFIGS = tuple(sorted(r[0] for r in tile_family(3)))     # the quantize-in-prologue family's tiles
+# the LDS-halo conv's tiles: id -> output pixels (rows, columns), channels
+HALO_TILES = {r[0]: r[1:4] for r in tile_family(5)}
 
 FLAG_W4 = 2   # MIXDQ_FLAG_W4: the weight tensor holds packed signed 4-bit values
 FLAG_W2 = 16  # MIXDQ_FLAG_W2: the weight tensor holds packed signed 2-bit values ([N, K/4])
@@ -142,9 +149,6 @@ FLAG_ACT = {None: 0, "gelu": 64, "quick_gelu": 128}   # MIXDQ_FLAG_ACT_GELU / _Q
 FLAG_A4_0, FLAG_A4_1, FLAG_A4_2 = 1 << 16, 1 << 17, 1 << 18
 FLAG_A4 = (FLAG_A4_0, FLAG_A4_1, FLAG_A4_2)
 ACT_BITS = (8, 4)          # the activation widths the producers take
-# configuration ids a packed-W2 launch cannot take (the weight stage is not whole 1-KiB pieces; 27: see
-# csrc/igemm.hip w2_tile_ok)
-W2_INADMISSIBLE = (27, 42, 43, 44, 45, 56)
 
 
 def _wflag(w4, w2):
@@ -415,8 +419,6 @@ FLAG_A_ROWMAP = 8   # MIXDQ_FLAG_A_ROWMAP: the FP16 operand's rows follow the ou
 # (mixdq_qlinear_f16in_preferred: narrow layers -- the 1x1 shortcuts, K <= 640); "1": wherever supported.
 F16IN = os.environ.get("MIXDQ_F16IN", "auto").lower()
 F16IN = {"0": "0", "off": "0", "1": "1", "on": "1"}.get(F16IN, "auto")
-# Tile configurations the quantizing family is built for (csrc/igemm_aq.hip MIXDQ_AQ_CONFIGS)
-F16IN_CONFIGS = (4, 13, 27, 28, 35, 37, 41, 44, 45, 56)
 
 
 def _rows_view(x: torch.Tensor, K: int):
@@ -594,9 +596,6 @@ class GemmGroupTable:
         self.key = tuple(r[0] for r in rows) + tuple(r[4] for r in rows)
 
 
-GROUPED_CONFIGS = (4, 35, 37, 41, 56)   # csrc/igemm.hip MIXDQ_GROUPED_CONFIGS: the ids qlinear_grouped's _cfg takes
-
-
 def qlinear_grouped(input_int8, table: "GemmGroupTable", *, _row_map=None, _cfg=0):
     """`table.n` Linears on the same int8 input in one launch (mixdq_qlinear_w8a8_grouped); every
     member writes its own output tensor (the ones the table was built with)."""
@@ -744,7 +743,6 @@ if hasattr(_lib, "mixdq_conv_halo_select"):      # (absent in older builds used 
 if hasattr(_lib, "mixdq_conv_halo_select_flags"):
     _lib.mixdq_conv_halo_select_flags.argtypes = [_i32] * 10
     _lib.mixdq_conv_halo_select_flags.restype = _i32
-HALO_TILES = {90: (8, 16, 80), 91: (8, 8, 80), 92: (16, 16, 80), 93: (16, 16, 160)}   # csrc/iconv.hip: output pixels (rows, columns), channels
 
 
 def conv_halo_select(N, H, W, C, K, R, S, stride, padding, w4=False) -> int:
@@ -1034,9 +1032,6 @@ def conv2d_f16(input, weight, bias=None, stride=1, padding=0, *, _residual=None,
                                      | (FLAG_PAD_AFTER if _pad_after else 0), _stream())
     _status(code, "conv2d_f16")
     return D
-
-
-F16_CONFIGS = (4, 13, 20, 25, 35, 41)   # csrc/igemm.hip MIXDQ_F16_CONFIGS (one accumulation order)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -20,6 +20,15 @@ struct HaloConvArgs {
                           //    upsampling (Upsample2D: conv(interpolate(x))) without materialising it
 };
 
+// The halo kernel's tiles: X(id, TH, TW, BN, CK, WNG) -- output pixels (rows, columns), output channels, channel
+// chunk bytes, wave groups along the channels.  The only place they are written: halo_conv_launch's W8 and W4
+// switches are generated from it, and mixdq_tile_config (family 5) reports it.
+#define MIXDQ_HALO_TILES(X)   \
+  X(90, 8, 16, 80, 128, 1)    \
+  X(91, 8, 8, 80, 128, 1)     \
+  X(92, 16, 16, 80, 64, 1)    \
+  X(93, 16, 16, 160, 64, 2)
+
 // Tile id the halo kernel would run this problem on (90: 8x16 pixels x 80 channels, 91: 8x8 x 80, 92: 16x16 x 80, 93: 16x16 x 160), or 0
 // when the problem is outside its range (then the implicit-GEMM family of csrc/igemm.hip runs it).
 // w4: for packed 4-bit weights (MIXDQ_FLAG_W4) -- the same range (what a forced tile id is checked against: ask

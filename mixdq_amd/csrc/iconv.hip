@@ -517,18 +517,16 @@ int halo_conv_select(int NI, int H, int W, int C, int K, int R, int S, int strid
 int halo_conv_launch(const HaloConvArgs& a, int tile, hipStream_t stream, bool w4) {
   if (w4) {
     switch (tile) {
-      case 90: return launch_halo<8, 16, 80, 128, 1, true>(a, stream);
-      case 91: return launch_halo<8, 8, 80, 128, 1, true>(a, stream);
-      case 92: return launch_halo<16, 16, 80, 64, 1, true>(a, stream);
-      case 93: return launch_halo<16, 16, 160, 64, 2, true>(a, stream);
+#define X(ID, TH, TW, BN, CK, WNG) case ID: return launch_halo<TH, TW, BN, CK, WNG, true>(a, stream);
+      MIXDQ_HALO_TILES(X)
+#undef X
       default: return MIXDQ_ERR_INVALID_ARG;
     }
   }
   switch (tile) {
-    case 90: return launch_halo<8, 16, 80, 128>(a, stream);
-    case 91: return launch_halo<8, 8, 80, 128>(a, stream);
-    case 92: return launch_halo<16, 16, 80, 64>(a, stream);
-    case 93: return launch_halo<16, 16, 160, 64, 2>(a, stream);
+#define X(ID, TH, TW, BN, CK, WNG) case ID: return launch_halo<TH, TW, BN, CK, WNG>(a, stream);
+    MIXDQ_HALO_TILES(X)
+#undef X
     default: return MIXDQ_ERR_INVALID_ARG;
   }
 }

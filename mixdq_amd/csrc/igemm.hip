@@ -178,12 +178,18 @@ __global__ __launch_bounds__(256) void gemm_f16_kernel(const __half* __restrict_
 // (71: the persistent form of 70, csrc/igemm_pp.h -- one workgroup per CU walking its tiles; dispatch() runs it where
 //  the launch is in its range, and 70's kernel otherwise)
 
-struct TileCfg { int id, bm, bn, bk, stages, wm, wn, ksplit, mt; };
+struct TileCfg { int id, bm, bn, bk, stages, wm, wn, ksplit, mt; bool phased; };
 constexpr TileCfg kTileCfgs[] = {
-#define X(ID, BM, BN, BK, ST, WM, WN, KS, MT, PH) {ID, BM, BN, BK, ST, WM, WN, KS, MT},
+#define X(ID, BM, BN, BK, ST, WM, WN, KS, MT, PH) {ID, BM, BN, BK, ST, WM, WN, KS, MT, PH},
     MIXDQ_IGEMM_CONFIGS(X)
 #undef X
 };
+// the table's row of an id (id 0 and zeros for an id it does not have)
+constexpr TileCfg tile_cfg(int id) {
+  for (const TileCfg& c : kTileCfgs)
+    if (c.id == id) return c;
+  return TileCfg{};
+}
 
 // Automatic choice (tools/bench_gemm.py on MI355X): the largest tile that still fills the chip.
 // 8-wave 256-row tiles need ~2 blocks per CU of parallelism to pay; long-K problems take the
@@ -213,10 +219,14 @@ inline const std::vector<TuneEntry>& tune_overrides() {
 inline int tuned_cfg(int64_t M, int N, int Ktot, bool whole64) {
   for (const TuneEntry& t : tune_overrides()) {
     if (t.M != M || t.N != N || t.K != Ktot) continue;
-    for (const TileCfg& c : kTileCfgs)
-      if (c.id == t.cfg && (!whole64 || c.bn % 32 == 0)) return t.cfg;
+    if (const TileCfg c = tile_cfg(t.cfg); c.id != 0 && (!whole64 || c.bn % 32 == 0)) return t.cfg;
   }
   return 0;
+}
+
+// workgroups of a launch on tm x tn tiles
+inline int64_t tile_blocks(int64_t M, int N, int tm, int tn) {
+  return ((M + tm - 1) / tm) * (int64_t)((N + tn - 1) / tn);
 }
 
 // whole64: a GEMM+GEGLU launch (needs BN % 32 == 0: whole value|gate groups per tile; the name is
@@ -226,9 +236,7 @@ inline int tuned_cfg(int64_t M, int N, int Ktot, bool whole64) {
 inline int select_cfg(int64_t M, int N, int Ktot, bool whole64 = false, bool phased_ok = false,
                       bool tune = true) {
   if (tune) if (const int c = tuned_cfg(M, N, Ktot, whole64)) return c;
-  auto blocks = [&](int tm, int tn) {
-    return ((M + tm - 1) / tm) * (int64_t)((N + tn - 1) / tn);
-  };
+  auto blocks = [&](int tm, int tn) { return tile_blocks(M, N, tm, tn); };
   // exactly one (or two) 128x320 workgroups per CU: no tail round, the fewest L2->LDS bytes per MAC
   // among the tiles that still use every CU (M = 8192, N = 1280: 26.0 vs 28.2 us, K = 5120: 66 vs 78)
   const int64_t b320 = blocks(128, 320);
@@ -284,9 +292,7 @@ inline int select_cfg(int64_t M, int N, int Ktot, bool whole64 = false, bool pha
 // the k-split 64x64 tile vs 18.3 on 64x80; (1024, 10240, 1280) 26.7 on 128x128 vs 29.9 on 128x320).
 inline int select_cfg_w4(int64_t M, int N, int Ktot, bool whole64 = false) {
   if (const int c = tuned_cfg(M, N, Ktot, whole64)) return c;
-  auto blocks = [&](int tm, int tn) {
-    return ((M + tm - 1) / tm) * (int64_t)((N + tn - 1) / tn);
-  };
+  auto blocks = [&](int tm, int tn) { return tile_blocks(M, N, tm, tn); };
   // GEMM+GEGLU (its epilogue runs in registers on every tile, with the GELU table where the tile owns
   // its CU): the 128x320 tile at exactly one or two workgroups per CU, as for W8 ((1024, 10240, 1280):
   // 20.9 vs 25.9 us on 128x128, (4096, 5120, 640): 26.4 vs 30.0); 256x256 for the large launches
@@ -313,10 +319,9 @@ inline int select_cfg_w4(int64_t M, int N, int Ktot, bool whole64 = false) {
 // not tile 27 (128x320 on 8 x 2 waves of 16x16x64): its W2 instantiation needs 8-12 bytes of scratch where the
 // W8 and W4 ones need none, and the packed-weight rules never choose it (25 / 28 are the same tile shape).
 constexpr bool w2_tile_ok(int id, int bn, int bk) { return (bn * bk / 4) % 1024 == 0 && id != 27; }
-inline bool w2_cfg_ok(int id) {
-  for (const TileCfg& c : kTileCfgs)
-    if (c.id == id) return w2_tile_ok(c.id, c.bn, c.bk);
-  return false;
+constexpr bool w2_cfg_ok(int id) {
+  const TileCfg c = tile_cfg(id);
+  return c.id != 0 && w2_tile_ok(c.id, c.bn, c.bk);
 }
 
 // Tuned on the 2-bit Linear families of weight_4.00 at batch 1 and 8 (tools/bench_w2.py --sweep: every tile W2
@@ -330,9 +335,7 @@ inline bool w2_cfg_ok(int id) {
 // MIXDQ_IGEMM_TUNE applies (its admissible entries; an inadmissible one is mapped the same way).
 inline int select_cfg_w2(int64_t M, int N, int Ktot, bool whole64 = false) {
   if (const int c = tuned_cfg(M, N, Ktot, whole64)) if (w2_cfg_ok(c)) return c;
-  auto blocks = [&](int tm, int tn) {
-    return ((M + tm - 1) / tm) * (int64_t)((N + tn - 1) / tn);
-  };
+  auto blocks = [&](int tm, int tn) { return tile_blocks(M, N, tm, tn); };
   const int64_t b320 = blocks(128, 320);
   if (!whole64 && N % 320 == 0 && Ktot % 128 == 0 && Ktot >= 1024 && (b320 == kNumCU || b320 == 2 * kNumCU))
     return 28;
@@ -341,6 +344,35 @@ inline int select_cfg_w2(int64_t M, int N, int Ktot, bool whole64 = false) {
   const int c = select_cfg_w4(M, N, Ktot, whole64);
   if (w2_cfg_ok(c)) return c;
   return c == 44 ? 4 : c == 27 ? 25 : 41;
+}
+
+// A Linear launch on the fast staging path: whole 128-byte K-tiles and 32-bit operand offsets (what the four-phase
+// loop, ids 70 / 71, needs)
+inline bool fast_staging(int64_t M, int N, int k_total) {
+  return k_total % 128 == 0 && (uint64_t)M * (uint64_t)k_total < (1ull << 32) &&
+         (uint64_t)N * (uint64_t)k_total < (1ull << 32);
+}
+
+// The automatic choice, for the launch (dispatch) and for the queries (mixdq_igemm_select_id*, mixdq_igemm_select):
+// the id of MIXDQ_IGEMM_CONFIGS an unforced launch runs; 0: the one-output-per-thread kernel (W8 with
+// k_align % 16 != 0); -1: no kernel takes the problem.  k_align: what the rows are aligned to (K; a conv's C),
+// k_total: the GEMM's K (a conv's R * S * C); wbits: 8, or 4 / 2 for packed weights; geglu: the GEMM+GEGLU launch.
+// conv: the conv launch never takes the four-phase loop.  The queries pass conv = (k_align != k_total), so for a
+// 1x1 conv with C % 128 == 0 they may answer 70 / 71 where the launch (conv = true) runs the one-phase tile the
+// rule picks without them: kept as it was, for a change of its own to decide.
+inline int select_id(int64_t M, int N, int k_align, int k_total, int wbits, bool geglu, bool conv) {
+  if (M <= 0 || N <= 0 || N % (geglu ? 32 : 4) != 0) return -1;
+  if (wbits == 2) {
+    if (k_align % 64 != 0 || k_total % 64 != 0) return -1;
+    return select_cfg_w2(M, N, k_total, geglu);
+  }
+  if (wbits == 4) {
+    if (k_align % 32 != 0) return -1;
+    return select_cfg_w4(M, N, k_total, geglu);
+  }
+  if (k_align % (geglu ? 16 : 4) != 0) return -1;
+  if (k_align % 16 != 0) return 0;   // generic kernel
+  return select_cfg(M, N, k_total, geglu, !conv && fast_staging(M, N, k_total));
 }
 
 template <bool CONV, int WBITS>
@@ -367,17 +399,12 @@ int dispatch(IgemmParams& p, hipStream_t stream, int forced_cfg) {
     }
   }
   const bool whole64 = p.Dq != nullptr;
-  const bool phased_ok = !CONV && p.Ktot % 128 == 0 &&
-                         (uint64_t)p.M * (uint64_t)p.Ktot < (1ull << 32) &&
-                         (uint64_t)p.N * (uint64_t)p.Ktot < (1ull << 32);
-  const int cfg = forced_cfg > 0 ? forced_cfg
-                                 : (W2 ? select_cfg_w2(p.M, p.N, p.Ktot, whole64)
-                                       : W4 ? select_cfg_w4(p.M, p.N, p.Ktot, whole64)
-                                            : select_cfg(p.M, p.N, p.Ktot, whole64, phased_ok));
+  // (select_id's own gates are the ones passed above and in the GEGLU entry point: it answers a tile id here)
+  const int cfg = forced_cfg > 0 ? forced_cfg : select_id(p.M, p.N, align_k, p.Ktot, WBITS, whole64, CONV);
   // the four-phase 256 x 256 tile as ONE workgroup per CU walking its tiles (csrc/igemm_pp.h: the next tile's first
   // K-tile lands under the current tile's epilogue; same arithmetic, same bits) wherever a CU has more than one tile
   if constexpr (!CONV && WBITS == 8) {
-    if (cfg == 71 && phased_ok && pp_ok(p))
+    if (cfg == 71 && fast_staging(p.M, p.N, p.Ktot) && pp_ok(p))
       return whole64 ? launch_pp<true>(p, stream) : launch_pp<false>(p, stream);
   }
   switch (cfg) {
@@ -582,17 +609,15 @@ extern "C" int mixdq_qlinear_w8a8_rows(const int8_t* A, const int8_t* W, const f
   IgemmParams p{};
   p.A = A; p.Wt = W; p.bias0 = bias0; p.scale = scale; p.bias = (const __half*)bias_f16_or_null;
   p.table = nullptr; p.zp = nullptr; p.D = (__half*)D_f16;
-  p.M = M; p.N = N; p.Ktot = K;
-  p.H = p.W = p.P = p.Q = 1; p.C = K; p.R = p.S = 1; p.stride = 1; p.pad = 0;
+  linear_problem(p, M, N, K);
   p.grp_rows = group_rows; p.grp_stride = group_stride; p.grp_off = group_offset;
-  p.res = (const __half*)residual_f16_or_null;
-  p.res_div = residual_row_div > 0 ? residual_row_div : 1;
+  set_residual(p, residual_f16_or_null, residual_row_div);
   if (p.res && group_rows > 0) return MIXDQ_ERR_ROWMAP_RESIDUAL;   // residual rows follow m, not D_row
   p.unfused = (flags & MIXDQ_FLAG_UNFUSED) ? 1 : 0;
   if ((flags & MIXDQ_FLAG_W4) && (flags & MIXDQ_FLAG_W2)) return MIXDQ_ERR_INVALID_ARG;
-  if (flags & MIXDQ_FLAG_W2) return dispatch<false, 2>(p, (hipStream_t)stream, (flags >> 8) & 0xff);
-  if (flags & MIXDQ_FLAG_W4) return dispatch<false, 4>(p, (hipStream_t)stream, (flags >> 8) & 0xff);
-  return dispatch<false, 8>(p, (hipStream_t)stream, (flags >> 8) & 0xff);
+  return with_wbits(flags, [&](auto wb) {
+    return dispatch<false, decltype(wb)::value>(p, (hipStream_t)stream, forced_id(flags));
+  });
 }
 
 extern "C" int mixdq_qlinear_w8a8_geglu(const int8_t* A, const int8_t* W, const float* bias0,
@@ -617,13 +642,12 @@ extern "C" int mixdq_qlinear_w8a8_geglu(const int8_t* A, const int8_t* W, const 
   p.A = A; p.Wt = W; p.bias0 = bias0; p.scale = scale; p.bias = (const __half*)bias_f16_or_null;
   if (const int st = ensure_gelu_table((hipStream_t)stream)) return st;
   p.D = nullptr; p.Dq = out_i8; p.g_sinv = out_scale_inv; p.g_zp = out_zero_point;
-  p.M = M; p.N = N; p.Ktot = K;
-  p.H = p.W = p.P = p.Q = 1; p.C = K; p.R = p.S = 1; p.stride = 1; p.pad = 0;
+  linear_problem(p, M, N, K);
   p.res_div = 1;
   p.unfused = (flags & MIXDQ_FLAG_UNFUSED) ? 1 : 0;
-  if (flags & MIXDQ_FLAG_W2) return dispatch<false, 2>(p, (hipStream_t)stream, (flags >> 8) & 0xff);
-  if (flags & MIXDQ_FLAG_W4) return dispatch<false, 4>(p, (hipStream_t)stream, (flags >> 8) & 0xff);
-  return dispatch<false, 8>(p, (hipStream_t)stream, (flags >> 8) & 0xff);
+  return with_wbits(flags, [&](auto wb) {
+    return dispatch<false, decltype(wb)::value>(p, (hipStream_t)stream, forced_id(flags));
+  });
 }
 
 extern "C" int mixdq_qlinear_w8a8_grouped(const int8_t* A, const mixdq_gemm_group* groups_device,
@@ -641,18 +665,17 @@ extern "C" int mixdq_qlinear_w8a8_grouped(const int8_t* A, const mixdq_gemm_grou
     return w4 ? MIXDQ_ERR_W4_SHAPE : MIXDQ_ERR_ALIGNMENT;   // the LDS-DMA kernels only
   IgemmParams p{};
   p.A = A; p.groups = groups_device;
-  p.M = M; p.N = max_N; p.Ktot = K;
-  p.H = p.W = p.P = p.Q = 1; p.C = K; p.R = p.S = 1; p.stride = 1; p.pad = 0;
+  linear_problem(p, M, max_N, K);
   p.grp_rows = group_rows; p.grp_stride = group_stride; p.grp_off = group_offset;
   p.res_div = 1;
   p.unfused = (flags & MIXDQ_FLAG_UNFUSED) ? 1 : 0;
-  int cfg = (flags >> 8) & 0xff;
+  int cfg = forced_id(flags);
   // the members are independent problems: the tile only has to suit one of them, the grid
   // (x ngroups) fills the chip.  M <= 64: 64x64 k-split tiles, else 128x128 (8 waves).
   if (cfg == 0) cfg = M <= 64 ? 37 : 35;
-  return w2 ? dispatch_grouped<2>(p, ngroups, (hipStream_t)stream, cfg)
-       : w4 ? dispatch_grouped<4>(p, ngroups, (hipStream_t)stream, cfg)
-            : dispatch_grouped<8>(p, ngroups, (hipStream_t)stream, cfg);
+  return with_wbits(flags, [&](auto wb) {
+    return dispatch_grouped<decltype(wb)::value>(p, ngroups, (hipStream_t)stream, cfg);
+  });
 }
 
 extern "C" int mixdq_qlinear_w8a8_attn(const int8_t* A, const int8_t* W, const float* bias0,
@@ -682,8 +705,7 @@ extern "C" int mixdq_qlinear_w8a8_attn(const int8_t* A, const int8_t* W, const f
     return MIXDQ_ERR_ALIGNMENT;
   IgemmParams p{};
   p.A = A; p.Wt = W; p.bias0 = bias0; p.scale = scale;
-  p.M = M; p.N = N; p.Ktot = K;
-  p.H = p.W = p.P = p.Q = 1; p.C = K; p.R = p.S = 1; p.stride = 1; p.pad = 0;
+  linear_problem(p, M, N, K);
   p.res_div = 1;
   p.unfused = (flags & MIXDQ_FLAG_UNFUSED) ? 1 : 0;
   p.att_k = (const __half*)k_f16; p.att_v = (const __half*)v_f16;
@@ -694,10 +716,8 @@ extern "C" int mixdq_qlinear_w8a8_attn(const int8_t* A, const int8_t* W, const f
   p.att_out = out; p.att_sinv = out_scale_inv_or_null; p.att_zp = out_zero_point_or_null;
   if (flags & (MIXDQ_FLAG_A4_1 | MIXDQ_FLAG_A4_2)) return MIXDQ_ERR_UNSUPPORTED;   // one quantizer: slot 0
   if (out_scale_inv_or_null && (flags & MIXDQ_FLAG_A4_0))
-    return w2 ? launch_att<2, true>(p, (hipStream_t)stream)
-         : w4 ? launch_att<4, true>(p, (hipStream_t)stream) : launch_att<8, true>(p, (hipStream_t)stream);
-  return w2 ? launch_att<2>(p, (hipStream_t)stream)
-       : w4 ? launch_att<4>(p, (hipStream_t)stream) : launch_att<8>(p, (hipStream_t)stream);
+    return with_wbits(flags, [&](auto wb) { return launch_att<decltype(wb)::value, true>(p, (hipStream_t)stream); });
+  return with_wbits(flags, [&](auto wb) { return launch_att<decltype(wb)::value>(p, (hipStream_t)stream); });
 }
 
 extern "C" int mixdq_qlinear_w8a8(const int8_t* A, const int8_t* W, const float* bias0,
@@ -760,7 +780,7 @@ extern "C" int mixdq_qconv2d_w8a8_table(const int8_t* X, const int8_t* Wt, const
   {
     const bool halo_on = halo_conv_switch(), halo_w4_on = halo_w4_switch();
     const bool w4 = flags & MIXDQ_FLAG_W4;
-    const int forced = (flags >> 8) & 0xff;
+    const int forced = forced_id(flags);
     const bool aligned = !(((uintptr_t)X | (uintptr_t)Wt | (uintptr_t)scale | (uintptr_t)table_or_null |
                             (uintptr_t)D | (uintptr_t)residual_f16_or_null) & 15) &&
                          !((uintptr_t)bias_f16_or_null & 7);
@@ -795,11 +815,10 @@ extern "C" int mixdq_qconv2d_w8a8_table(const int8_t* X, const int8_t* Wt, const
   p.M = (int64_t)N * P * Q; p.N = K; p.Ktot = R * S * C;
   p.H = H; p.W = W; p.C = C; p.R = R; p.S = S; p.P = P; p.Q = Q; p.stride = stride; p.pad = pad;
   p.grp_rows = 0; p.grp_stride = 0; p.grp_off = 0;
-  p.res = (const __half*)residual_f16_or_null;
-  p.res_div = residual_row_div > 0 ? residual_row_div : 1;
+  set_residual(p, residual_f16_or_null, residual_row_div);
   p.unfused = (flags & MIXDQ_FLAG_UNFUSED) ? 1 : 0;
-  if (flags & MIXDQ_FLAG_W4) return dispatch<true, 4>(p, (hipStream_t)stream, (flags >> 8) & 0xff);
-  return dispatch<true, 8>(p, (hipStream_t)stream, (flags >> 8) & 0xff);
+  if (flags & MIXDQ_FLAG_W4) return dispatch<true, 4>(p, (hipStream_t)stream, forced_id(flags));
+  return dispatch<true, 8>(p, (hipStream_t)stream, forced_id(flags));
 }
 
 extern "C" int mixdq_qconv2d_w8a8(const int8_t* X, const int8_t* Wt, const float* scale,
@@ -866,11 +885,9 @@ extern "C" int mixdq_linear_f16(const void* A_f16, const void* W_f16, const void
   IgemmParams p{};
   p.A = (const int8_t*)A_f16; p.Wt = (const int8_t*)W_f16; p.bias = (const __half*)bias_f16_or_null;
   p.D = (__half*)D_f16;
-  p.M = M; p.N = N; p.Ktot = 2 * K;           // the kernel family counts K in bytes
-  p.H = p.W = p.P = p.Q = 1; p.C = 2 * K; p.R = p.S = 1; p.stride = 1; p.pad = 0;
-  p.res = (const __half*)residual_f16_or_null;
-  p.res_div = residual_row_div > 0 ? residual_row_div : 1;
-  return dispatch_f16<false>(p, (hipStream_t)stream, (flags >> 8) & 0xff, act);
+  linear_problem(p, M, N, 2 * K);             // the kernel family counts K in bytes
+  set_residual(p, residual_f16_or_null, residual_row_div);
+  return dispatch_f16<false>(p, (hipStream_t)stream, forced_id(flags), act);
 }
 
 extern "C" int mixdq_conv2d_f16(const void* X_f16, const void* Wt_f16, const void* bias_f16_or_null,
@@ -898,8 +915,7 @@ extern "C" int mixdq_conv2d_f16(const void* X_f16, const void* Wt_f16, const voi
   p.D = (__half*)D_f16;
   p.M = (int64_t)N * P * Q; p.N = K; p.Ktot = R * S * C * 2;
   p.H = H; p.W = W; p.C = 2 * C; p.R = R; p.S = S; p.P = P; p.Q = Q; p.stride = stride; p.pad = pad;
-  p.res = (const __half*)residual_f16_or_null;
-  p.res_div = residual_row_div > 0 ? residual_row_div : 1;
+  set_residual(p, residual_f16_or_null, residual_row_div);
   if (flags & MIXDQ_FLAG_UPSAMPLE2X) {
     // X is [N, H / 2, W / 2, C]; the MFMA tiles' gather reads pixel (y >> 1, x >> 1): 3x3 / stride 1 / pad 1 only,
     // and only where dispatch_f16 takes the tiles (the one-output-per-thread fallback has no such gather)
@@ -909,7 +925,7 @@ extern "C" int mixdq_conv2d_f16(const void* X_f16, const void* Wt_f16, const voi
     if (R != 3 || S != 3 || stride != 1 || pad != 1 || (H & 1) || (W & 1) || !tiles) return MIXDQ_ERR_SHAPE;
     p.ups = 1;
   }
-  return dispatch_f16<true>(p, (hipStream_t)stream, (flags >> 8) & 0xff);
+  return dispatch_f16<true>(p, (hipStream_t)stream, forced_id(flags));
 }
 
 extern "C" const char* mixdq_status_string(int status) {
@@ -957,16 +973,8 @@ extern "C" int mixdq_debug_stamps(void* buffer) {
 }
 #endif
 
-// a Linear problem (k_align == k_total: no taps) that takes the fast staging path
-static bool linear_fast(int64_t M, int N, int k_align, int k_total) {
-  return k_align == k_total && k_total % 128 == 0 &&
-         (uint64_t)M * (uint64_t)k_total < (1ull << 32) && (uint64_t)N * (uint64_t)k_total < (1ull << 32);
-}
-
 extern "C" int mixdq_igemm_select_id(int64_t M, int N, int k_align, int k_total) {
-  if (M <= 0 || N <= 0 || k_align % 4 != 0 || N % 4 != 0) return -1;
-  if (k_align % 16 != 0) return 0;   // generic kernel
-  return select_cfg(M, N, k_total, false, linear_fast(M, N, k_align, k_total));
+  return select_id(M, N, k_align, k_total, 8, false, k_align != k_total);
 }
 
 extern "C" int mixdq_conv_halo_select(int N, int H, int W, int C, int K, int R, int S, int stride,
@@ -985,33 +993,58 @@ extern "C" int mixdq_conv_halo_select_flags(int N, int H, int W, int C, int K, i
 }
 
 extern "C" int mixdq_igemm_select_id_w4(int64_t M, int N, int k_align, int k_total) {
-  if (M <= 0 || N <= 0 || k_align % 32 != 0 || N % 4 != 0) return -1;
-  return select_cfg_w4(M, N, k_total);
+  return select_id(M, N, k_align, k_total, 4, false, k_align != k_total);
 }
 
 extern "C" int mixdq_igemm_select_id_w2(int64_t M, int N, int k_align, int k_total) {
-  if (M <= 0 || N <= 0 || k_align % 64 != 0 || k_total % 64 != 0 || N % 4 != 0) return -1;
-  return select_cfg_w2(M, N, k_total);
+  return select_id(M, N, k_align, k_total, 2, false, k_align != k_total);
 }
 
 extern "C" int mixdq_igemm_select_id_geglu_w2(int64_t M, int N, int k_total) {
-  if (M <= 0 || N <= 0 || N % 32 != 0 || k_total % 64 != 0) return -1;
-  return select_cfg_w2(M, N, k_total, true);
+  return select_id(M, N, k_total, k_total, 2, true, false);
 }
 
 extern "C" int mixdq_igemm_select_id_geglu(int64_t M, int N, int k_total, int w4) {
-  if (M <= 0 || N <= 0 || N % 32 != 0 || k_total % (w4 ? 32 : 16) != 0) return -1;
-  return w4 ? select_cfg_w4(M, N, k_total, true)
-            : select_cfg(M, N, k_total, true, linear_fast(M, N, k_total, k_total));
+  return select_id(M, N, k_total, k_total, w4 ? 4 : 8, true, false);
+}
+
+// The tables this library was compiled with, for the bindings and the tests (include/mixdq_hip.h).
+extern "C" int mixdq_tile_config(int family, int index, int* out) {
+#define X(ID, ...) ID,
+  static constexpr int all[] = {MIXDQ_IGEMM_CONFIGS(X)}, f16[] = {MIXDQ_F16_CONFIGS(X)},
+                       grouped[] = {MIXDQ_GROUPED_CONFIGS(X)};
+#undef X
+#define X(...) {__VA_ARGS__},
+  static constexpr int halo[][6] = {MIXDQ_HALO_TILES(X)};
+#undef X
+  const int* ids = nullptr;
+  int n = -1;
+  switch (family) {
+    case 0: ids = all; n = (int)std::size(all); break;
+    case 1: ids = f16; n = (int)std::size(f16); break;
+    case 2: ids = grouped; n = (int)std::size(grouped); break;
+    case 3: n = aq_tile_ids(&ids); break;      // (that family's table is in its own translation unit)
+    case 5: n = (int)std::size(halo); break;
+  }
+  if (n < 0 || out == nullptr || index < 0 || index >= n) return n;
+  for (int i = 0; i < 10; ++i) out[i] = 0;
+  if (family == 5) {
+    for (int i = 0; i < 6; ++i) out[i] = halo[index][i];
+    return n;
+  }
+  const TileCfg c = tile_cfg(ids[index]);
+  const int row[10] = {c.id, c.bm, c.bn, c.bk, c.stages, c.wm, c.wn, c.ksplit, c.mt,
+                       (c.phased ? 1 : 0) | (w2_tile_ok(c.id, c.bn, c.bk) ? 2 : 0) | (geglu_tile_ok(c.bn, c.wn) ? 4 : 0)};
+  for (int i = 0; i < 10; ++i) out[i] = row[i];
+  return n;
 }
 
 extern "C" int mixdq_igemm_select(int64_t M, int N, int k_align, int k_total, int* bm, int* bn,
                                   int* bk, int* stages) {
   if (!bm || !bn || !bk || !stages || M <= 0 || N <= 0) return MIXDQ_ERR_INVALID_ARG;
-  if (k_align % 4 != 0 || N % 4 != 0) return MIXDQ_ERR_ALIGNMENT;
-  if (k_align % 16 != 0) { *bm = *bn = *bk = *stages = 0; return MIXDQ_OK; }   // generic kernel
-  const int cfg = select_cfg(M, N, k_total, false, linear_fast(M, N, k_align, k_total));
-  for (const TileCfg& c : kTileCfgs)
-    if (c.id == cfg) { *bm = c.bm; *bn = c.bn; *bk = c.bk; *stages = c.stages; }
+  const int cfg = select_id(M, N, k_align, k_total, 8, false, k_align != k_total);
+  if (cfg < 0) return MIXDQ_ERR_ALIGNMENT;
+  const TileCfg c = tile_cfg(cfg);             // (0, the generic kernel: zeros)
+  *bm = c.bm; *bn = c.bn; *bk = c.bk; *stages = c.stages;
   return MIXDQ_OK;
 }

@@ -4,6 +4,7 @@
 #pragma once
 #include <cstdio>
 #include <cstdlib>
+#include <iterator>
 #include <type_traits>
 #include <vector>
 
@@ -29,6 +30,10 @@
 #endif
 
 namespace mixdq {
+
+// the ids of the quantize-in-prologue family (csrc/igemm_aq.hip) and their number, for mixdq_tile_config
+int aq_tile_ids(const int** out);
+
 namespace {
 
 __device__ uint4 g_zero16;   // the zero page (device globals are zero-initialised)
@@ -116,6 +121,27 @@ struct IgemmParams {
   // test stays against H and W.  0 everywhere else (a shift by nothing).
   int ups;
 };
+
+// ---- what the entry points share
+// A Linear is the family's degenerate conv: a 1x1 image of K channels (K in bytes for the FP16 layers).
+inline void linear_problem(IgemmParams& p, int64_t M, int N, int K) {
+  p.M = M; p.N = N; p.Ktot = K;
+  p.H = p.W = p.P = p.Q = 1; p.C = K; p.R = p.S = 1; p.stride = 1; p.pad = 0;
+}
+inline void set_residual(IgemmParams& p, const void* residual_f16_or_null, int64_t row_div) {
+  p.res = (const __half*)residual_f16_or_null;
+  p.res_div = row_div > 0 ? row_div : 1;
+}
+// bits 8..15 of `flags`: a forced configuration id, 0 = the automatic choice
+constexpr int forced_id(int flags) { return (flags >> 8) & 0xff; }
+// f(std::integral_constant<int, WBITS>) for the weight width `flags` names (MIXDQ_FLAG_W2 / _W4, else 8): the one
+// place a run-time flag becomes the kernels' WBITS template argument
+template <class F>
+int with_wbits(int flags, F&& f) {
+  if (flags & MIXDQ_FLAG_W2) return f(std::integral_constant<int, 2>{});
+  if (flags & MIXDQ_FLAG_W4) return f(std::integral_constant<int, 4>{});
+  return f(std::integral_constant<int, 8>{});
+}
 
 // FP16 layers (mixdq_linear_f16, MIXDQ_FLAG_ACT_GELU / _QUICK_GELU): an activation applied to the ROUNDED FP16 value
 // where the tile's chunks are stored -- ACT 1: GELU (mixdq_geluf), 2: quick-GELU (mixdq_quick_geluf;
@@ -2141,6 +2167,9 @@ inline int tile_map_gm() {
   return gm;
 }
 
+// GEMM+GEGLU: whole 32-column value|gate groups per tile and per wave
+constexpr bool geglu_tile_ok(int bn, int wn) { return bn % 32 == 0 && (bn / wn) % 32 == 0; }
+
 template <int BM, int BN, int BK, int STAGES, int WM, int WN, bool CONV, bool FAST, int WBITS, int KSPLIT,
           int MT, bool F16 = false, bool PHASED = false, bool GROUPED = false, bool AQ = false, bool LNQ = false,
           int ACT = 0>
@@ -2150,7 +2179,7 @@ int launch_kernel(IgemmParams& p, hipStream_t stream) {
   constexpr int SMEM = LNQ && igemm_smem_bytes<BM, BN, BK, STAGES>() < 82 * 1024
                            ? 82 * 1024 : igemm_smem_bytes<BM, BN, BK, STAGES>();
   static_assert(SMEM <= 160 * 1024, "LDS is 160 KiB per CU");
-  if (p.Dq != nullptr && (BN % 32 != 0 || (BN / WN) % 32 != 0))        // whole value|gate groups per tile, per wave
+  if (p.Dq != nullptr && !geglu_tile_ok(BN, WN))                       // whole value|gate groups per tile, per wave
     return MIXDQ_ERR_GEGLU_SHAPE;
   if constexpr (SMEM > 64 * 1024) {   // opt in to > 64 KiB of dynamic LDS, once per instantiation and device
     static bool seen[64] = {};

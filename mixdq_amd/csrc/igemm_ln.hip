@@ -31,6 +31,7 @@ int select_ln(int64_t M, int N, int K) {
 constexpr size_t kLnCounterBytes = 4096;      // epoch, departures, sticky error word (three ints; a page of their own)
 
 }  // namespace
+
 }  // namespace mixdq
 
 using namespace mixdq;
@@ -80,7 +81,7 @@ extern "C" int mixdq_qlinear_w8a8_ln(const int8_t* A, const int8_t* W, const flo
       (n_out == 0 && !out_f16_or_null))
     return MIXDQ_ERR_INVALID_ARG;
   if (flags & (MIXDQ_FLAG_W4 | MIXDQ_FLAG_W2)) return MIXDQ_ERR_SHAPE;
-  int cfg = (flags >> 8) & 0xff;
+  int cfg = forced_id(flags);
   if (cfg == 0) cfg = mixdq_qlinear_ln_select_id(M, N, K);
   if (cfg <= 0) return MIXDQ_ERR_SHAPE;
   if ((((uintptr_t)A | (uintptr_t)W | (uintptr_t)D_f16 | (uintptr_t)scale | (uintptr_t)bias0 |
@@ -90,10 +91,8 @@ extern "C" int mixdq_qlinear_w8a8_ln(const int8_t* A, const int8_t* W, const flo
   IgemmParams p{};
   p.A = A; p.Wt = W; p.bias0 = bias0; p.scale = scale; p.bias = (const __half*)bias_f16_or_null;
   p.D = (__half*)D_f16;
-  p.M = M; p.N = N; p.Ktot = K;
-  p.H = p.W = p.P = p.Q = 1; p.C = K; p.R = p.S = 1; p.stride = 1; p.pad = 0;
-  p.res = (const __half*)residual_f16_or_null;
-  p.res_div = residual_row_div > 0 ? residual_row_div : 1;
+  linear_problem(p, M, N, K);
+  set_residual(p, residual_f16_or_null, residual_row_div);
   p.unfused = (flags & MIXDQ_FLAG_UNFUSED) ? 1 : 0;
   p.ln_gamma = (const __half*)gamma_f16; p.ln_beta = (const __half*)beta_f16; p.ln_eps = eps;
   p.ln_nq = n_out; p.ln_h = (__half*)out_f16_or_null;

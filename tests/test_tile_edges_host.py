@@ -1,8 +1,11 @@
 """The edge cases of tests/test_tile_edges_gpu.py cover every tile configuration (no GPU).  The required values
 are restated here from each configuration's (BM, BN, BK, STAGES), independently of the generator, so that a
 configuration added to the library -- or an edge dropped from the generator -- fails on the CPU."""
+import os
+
 import pytest
 
+from tests import conv_geometry as cg
 from tests import tile_edges as te
 
 
@@ -23,6 +26,15 @@ def test_generator_tables_are_the_bindings_tables():
     for table in (te.F16, te.AQ, te.GROUPED):            # the same ids name the same tiles
         for i, v in table.items():
             assert i in te.IGEMM and v[:4] == te.IGEMM[i][:4], i
+    # what the LOADED library reports (mixdq_tile_config) is what the source tree says: the build matches the tree
+    halo = te._xmacro(os.path.join(te.CSRC, "iconv.h"), "MIXDQ_HALO_TILES")
+    assert {i: v[:3] for i, v in halo.items()} == C.HALO_TILES
+    assert [r[:6] for r in C.tile_family(5)] == [(i, *v) for i, v in halo.items()]
+    assert C.tile_family(4) == []              # GEMM+LayerNorm: ids 44, 45, 56 are cases of igemm_ln.hip, not a table
+    for r in C.tile_family(0):             # ... and the admissibility rules restated in the generator
+        assert r[:9] == (r[0], *te.IGEMM[r[0]]), r
+        assert bool(r[9] & 2) == te.w2_admissible(r[0]) and bool(r[9] & 4) == te.geglu_admissible(r[0]), r
+        assert bool(r[9] & 1) == cg.IGEMM_GATHER[r[0]][6], r            # the four-phase loop
 
 
 @pytest.mark.parametrize("cfg", sorted(te.IGEMM))
