@@ -558,6 +558,40 @@ int mixdq_vae_latent_sample(const void* moments_f16, const float* noise_or_null,
                             float scaling_factor, mixdq_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Inpainting around the VAE (csrc/vae.hip).  No reference counterpart.  A mask value is SET (repaint) by
+ * diffusers' rule: uint8 u >= 128 (u / 255 >= 0.5), FP16 / FP32 v >= 0.5; NaN is not set.
+ *
+ * mixdq_mask_to_latent: an image-resolution mask as the latent-resolution mask the masked sampler step reads.
+ * mask: [B, H, W] of uint8 / FP16 / FP32 (the MIXDQ_IMAGE_* codes), element (b, y, x) at mask + (b * sb + y * sh +
+ * x * sw) ELEMENTS; out: FP32 [B, H/8, W/8] dense, every value exactly 0.0 or 1.0.
+ *   MIXDQ_MASK_NEAREST  out[b, i, j] = set(mask[b, 8i, 8j])      what F.interpolate(mask, size=(H/8, W/8)) in its
+ *                                                                default nearest mode picks: diffusers' pipeline
+ *   MIXDQ_MASK_ANY      out[b, i, j] = any pixel of rows 8i..8i+7, columns 8j..8j+7 set: a latent whose block
+ *                       touches the mask is repainted.  Rows are read with 8- / 16-byte loads where sw == 1 and the
+ *                       pointer, sh and sb keep every row start aligned, element by element otherwise.
+ * Errors: negative sizes, H % 8 or W % 8 nonzero, a dtype code outside 0..2, an unknown mode, null pointers:
+ * MIXDQ_ERR_INVALID_ARG; mask not aligned to its element or out to 4 bytes: MIXDQ_ERR_ALIGNMENT.  B * H * W == 0
+ * writes nothing (and looks at no pointer).
+ *
+ * mixdq_composite_u8: the decoded image pasted into the original under the mask, as pixels:
+ *   out[b, y, x, c] = set(mask[b, y, x]) ? mixdq_to_uint8(f32(decoded[b, c, y, x])) : original[b, c, y, x]     c < 3
+ * decoded: FP16, element (b, c, y, x) at decoded + (b * db + c * dc + y * dh + x * dw) elements (VAEDecoder.decode
+ * returns three channels of a four-channel channels-last tensor: strides say so); original: uint8, strides ob, oc,
+ * oh, ow likewise; mask: at image resolution, dtype code and strides mb, mh, mw as above; out: uint8 [B, H, W, 3]
+ * dense.  mixdq_to_uint8 (include/mixdq_math.h) is ((v / 2 + 0.5).clamp(0, 1) * 255).round(), half to even, NaN 0.
+ * Pixels outside the mask are the original's bytes.
+ * Errors: negative sizes, a mask dtype code outside 0..2, null pointers: MIXDQ_ERR_INVALID_ARG; decoded or mask not
+ * aligned to its element: MIXDQ_ERR_ALIGNMENT.  B * H * W == 0 writes nothing (and looks at no pointer). */
+#define MIXDQ_MASK_NEAREST 0
+#define MIXDQ_MASK_ANY 1
+int mixdq_mask_to_latent(const void* mask, int dtype, int64_t sb, int64_t sh, int64_t sw, float* out, int B, int H,
+                         int W, int mode, mixdq_stream_t stream);
+int mixdq_composite_u8(const void* decoded_f16, int64_t db, int64_t dc, int64_t dh, int64_t dw,
+                       const uint8_t* original, int64_t ob, int64_t oc, int64_t oh, int64_t ow, const void* mask,
+                       int mask_dtype, int64_t mb, int64_t mh, int64_t mw, uint8_t* out, int B, int H, int W,
+                       mixdq_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Sampler step: classifier-free guidance + scheduler update + the UNet's next input, and the step state kept on
  * the device, so that a sampling loop is N replays of one captured graph with nothing from the host in between.
  * No reference counterpart: the reference reaches the loop only through diffusers' pipeline call in its run()
@@ -583,6 +617,28 @@ int mixdq_sampler_step(float* x, const void* eps_f16, void* in_f16, const float*
                        int64_t noise_stride, const float* coef, const float* t_table, int n_steps,
                        int* step, float* timestep, float guidance, int64_t n, int rows_per_image,
                        int64_t row_stride, mixdq_stream_t stream);
+
+/* The same step for inpainting with a 4-channel UNet (diffusers' StableDiffusion[XL]InpaintPipeline when
+ * num_channels_unet == 4): after the update above, the region the mask keeps is overwritten with the image latents
+ * noised to the NEXT step's level.  With x' the value mixdq_sampler_step would store, (p, q) = blend[*step] (blend:
+ * FP32 [n_steps][2], 8-byte aligned: the scheduler's add_noise scalars at timestep *step + 1, the last row (1, 0))
+ * and m = mask[i / channels]:
+ *   k      = (p * z[i]) + (q * noise0[i])
+ *   x[i]   = ((1 - m) * k) + (m * x')                     m = 1 repaints, m = 0 keeps, values between blend
+ *   in[i]  = in[row_stride + i] (rows_per_image == 2) = f16_rn(x[i] * s_next)
+ * every operation FP32 round-to-nearest, never contracted (include/mixdq_math.h: mixdq_sampler_blend).  z: the image
+ * latents and noise0: the run's initial noise (diffusers re-uses it at every step), FP32, n elements each in x's
+ * stride pattern; mask: FP32, one value per latent pixel, [B, h, w] dense, n / channels entries -- element i of
+ * the channels-last storage belongs to entry i / channels.  Any channels >= 1 with n % channels == 0; n need not be
+ * a multiple of 8.  The advance launch behind it and the behaviour past the table are mixdq_sampler_step's.
+ * Errors: mixdq_sampler_step's, then null z / noise0 / mask / blend, channels < 1, n % channels != 0:
+ * MIXDQ_ERR_INVALID_ARG; z / noise0 not 16-byte, mask not 4-byte, blend not 8-byte aligned: MIXDQ_ERR_ALIGNMENT.
+ * A refused call launches nothing. */
+int mixdq_sampler_step_masked(float* x, const void* eps_f16, void* in_f16, const float* noise_or_null,
+                              int64_t noise_stride, const float* coef, const float* t_table, int n_steps,
+                              int* step, float* timestep, float guidance, int64_t n, int rows_per_image,
+                              int64_t row_stride, const float* z, const float* noise0, const float* mask,
+                              int channels, const float* blend, mixdq_stream_t stream);
 
 /* Which kernel instantiation mixdq_qlinear_w8a8 / mixdq_qconv2d_w8a8 will launch for a problem of
  * M rows x N output channels (k_align = K for Linear, C for Conv2d; k_total = K or R*S*C): the block tile BM x BN x BK

@@ -133,6 +133,29 @@ MIXDQ_HD float mixdq_sampler_update_noise(float x, float e, float n, float a, fl
 /* The FP32 value whose FP16 rounding is the UNet's next input. */
 MIXDQ_HD float mixdq_sampler_scaled_input(float x_next, float s_next) { return MIXDQ_MUL_RN(x_next, s_next); }
 
+/* ---- inpainting (mixdq_sampler_step_masked, csrc/sampler.hip), same rule.  After the scheduler update the region the
+ * mask keeps is overwritten with the image latents z noised to the NEXT step's level with the run's initial noise n0
+ * (diffusers' inpainting with a 4-channel UNet); m = 1 repaints, m = 0 keeps, values between blend:
+ *   k   = (p*z) + (q*n0)                        two products and a sum; (p, q) = blend[*step]
+ *   x'' = ((1 - m) * k) + (m * x')              one difference, two products and a sum
+ * For m == 0 the result is k and for m == 1 it is x' (finite operands; up to the sign of zero: -0 + +0 is +0). */
+MIXDQ_HD float mixdq_sampler_blend(float x_new, float z, float n0, float m, float p, float q) {
+  const float k = MIXDQ_ADD_RN(MIXDQ_MUL_RN(p, z), MIXDQ_MUL_RN(q, n0));
+  return MIXDQ_ADD_RN(MIXDQ_MUL_RN(MIXDQ_SUB_RN(1.0f, m), k), MIXDQ_MUL_RN(m, x_new));
+}
+
+/* ---- VAE decoder end (mixdq_composite_u8, csrc/vae.hip): one FP16 image value (given as its exact FP32 value) as
+ * the pixel vae.to_uint8 makes of it, ((f32(v) / 2 + 0.5).clamp(0, 1) * 255).round() with round-half-even:
+ * the halving is exact, then one sum, the clamp, one product, rintf -- each one FP32 operation.  -inf is 0, +inf
+ * 255.  NaN is 0: the torch expression carries the NaN to its conversion to uint8, which on the GPU goes through a
+ * 64-bit integer whose conversion from NaN is 0. */
+MIXDQ_HD uint8_t mixdq_to_uint8(float v) {
+  if (v != v) return 0;
+  float t = MIXDQ_ADD_RN(MIXDQ_MUL_RN(v, 0.5f), 0.5f);
+  t = __builtin_fminf(__builtin_fmaxf(t, 0.0f), 1.0f);
+  return (uint8_t)(int)__builtin_rintf(MIXDQ_MUL_RN(t, 255.0f));
+}
+
 /* ---- VAE encoder ends (csrc/vae.hip), same rule: one rounding per operation, never contracted.
  * The posterior sample of an AutoencoderKL (DiagonalGaussianDistribution: logvar clamped to [-30, 20]), times the
  * scaling factor:  z = (mean + exp(0.5 * logvar) * n) * sf;  without noise the mode, mean * sf. */

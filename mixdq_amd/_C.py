@@ -1421,6 +1421,56 @@ def sampler_step(x, eps, inp, coef, t_table, step, timestep, guidance=0.0, rows_
     _status(code, "sampler_step")
 
 
+_lib.mixdq_sampler_step_masked.argtypes = [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, ctypes.c_float, _i64,
+                                           _i32, _i64, _vp, _vp, _vp, _i32, _vp, _vp]
+_lib.mixdq_sampler_step_masked.restype = _i32
+
+
+def sampler_step_masked(x, eps, inp, coef, t_table, step, timestep, z, noise0, mask, blend, guidance=0.0,
+                        rows_per_image=1, noise=None, *, channels=4, n=None, row_stride=None, noise_stride=None):
+    """sampler_step for inpainting (mixdq_sampler_step_masked): the same guidance and update, then the region the
+    mask keeps is overwritten with the image latents at the next step's noise level,
+    x = (1 - m) * (p * z + q * noise0) + m * x', (p, q) = blend[step], and the UNet's next input is taken from that.
+
+    z, noise0: fp32, `n` elements in x's stride pattern; mask: fp32, one value per latent pixel ([B, h, w] dense,
+    n / channels entries; 1 repaints, 0 keeps): element i of the channels-last storage belongs to entry
+    i // channels; blend: fp32 [n_steps, 2] (Schedule.blend).  Everything else as sampler_step."""
+    for t_, name, dt in ((x, "x", torch.float32), (eps, "eps", torch.float16), (inp, "inp", torch.float16),
+                         (coef, "coef", torch.float32), (t_table, "t_table", torch.float32),
+                         (step, "step", torch.int32), (timestep, "timestep", torch.float32),
+                         (z, "z", torch.float32), (noise0, "noise0", torch.float32), (mask, "mask", torch.float32),
+                         (blend, "blend", torch.float32)) + (
+                             ((noise, "noise", torch.float32),) if noise is not None else ()):
+        _check(torch.is_tensor(t_) and t_.is_cuda and t_.device == x.device and t_.dtype == dt,
+               f"{name} should be a {dt} tensor on x's GPU")
+    _check(coef.dim() == 2 and coef.shape[1] == 4 and coef.is_contiguous() and t_table.is_contiguous(),
+           "coef should be a contiguous [n_steps, 4] table")
+    n_steps = coef.shape[0]
+    _check(tuple(blend.shape) == (n_steps, 2) and blend.is_contiguous(), "blend should be a contiguous [n_steps, 2] table")
+    _check(t_table.numel() >= n_steps + 1, "t_table needs n_steps + 1 entries")
+    _check(step.numel() == 1 and timestep.numel() == 1, "step and timestep hold one value each")
+    n = x.numel() if n is None else int(n)
+    row_stride = n if row_stride is None else int(row_stride)
+    noise_stride = n if noise_stride is None else int(noise_stride)
+    channels = int(channels)
+    _check(0 <= n <= x.numel(), "n exceeds the state")
+    _check(z.numel() >= n and noise0.numel() >= n, "z / noise0 are smaller than the state")
+    if channels >= 1 and n % channels == 0:           # (anything else: the library's own error)
+        _check(mask.is_contiguous() and mask.numel() >= n // channels, "mask should be dense with n / channels entries")
+    if rows_per_image in (1, 2):
+        need = (rows_per_image - 1) * row_stride + n
+        _check(eps.numel() >= need and inp.numel() >= need, "eps / inp are smaller than rows_per_image row blocks")
+    if noise is not None:
+        _check(noise.numel() >= (n_steps - 1) * noise_stride + n, "noise is smaller than n_steps blocks")
+    with torch.cuda.device(x.device):
+        code = _lib.mixdq_sampler_step_masked(x.data_ptr(), eps.data_ptr(), inp.data_ptr(), _ptr(noise), noise_stride,
+                                              coef.data_ptr(), t_table.data_ptr(), n_steps, step.data_ptr(),
+                                              timestep.data_ptr(), float(guidance), n, int(rows_per_image), row_stride,
+                                              z.data_ptr(), noise0.data_ptr(), mask.data_ptr(), channels,
+                                              blend.data_ptr(), _stream())
+    _status(code, "sampler_step_masked")
+
+
 
 _lib.mixdq_image_to_nhwc8_f16.argtypes = [_vp, _i32, _i64, _i64, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _vp]
 _lib.mixdq_image_to_nhwc8_f16.restype = _i32
@@ -1467,3 +1517,59 @@ def vae_latent_sample(moments, noise=None, scaling_factor=1.0):
                                             float(scaling_factor), _stream())
     _status(code, "vae_latent_sample")
     return z.permute(0, 3, 1, 2)
+
+
+_lib.mixdq_mask_to_latent.argtypes = [_vp, _i32, _i64, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _vp]
+_lib.mixdq_mask_to_latent.restype = _i32
+_lib.mixdq_composite_u8.argtypes = ([_vp] + [_i64] * 4) * 2 + [_vp, _i32] + [_i64] * 3 + [_vp, _i32, _i32, _i32, _vp]
+_lib.mixdq_composite_u8.restype = _i32
+MASK_MODES = {"nearest": 0, "any": 1}                                     # include/mixdq_hip.h MIXDQ_MASK_*
+
+
+def _mask3(mask, what):
+    """An image-resolution mask [B, H, W] or [B, 1, H, W] as (B, H, W, element strides)."""
+    _check(torch.is_tensor(mask) and mask.is_cuda and mask.dtype in IMAGE_DTYPES
+           and (mask.dim() == 3 or (mask.dim() == 4 and mask.shape[1] == 1)),
+           f"{what}: mask should be a [B, H, W] or [B, 1, H, W] uint8, fp16 or fp32 GPU tensor")
+    st = mask.stride()
+    return mask.shape[0], mask.shape[-2], mask.shape[-1], (st[0], st[-2], st[-1])
+
+
+def mask_to_latent(mask, mode="nearest"):
+    """An image-resolution inpainting mask as the latent-resolution one Sampler.sample(mask=) takes
+    (mixdq_mask_to_latent): mask [B, H, W] or [B, 1, H, W], uint8 (set: u >= 128), fp16 or fp32 (set: v >= 0.5; NaN is
+    not set), of ANY strides, H and W multiples of 8 -> fp32 [B, H/8, W/8] of 0.0 / 1.0.  mode 'nearest': pixel
+    (8i, 8j), what F.interpolate(mask, size=(H/8, W/8)) picks and so diffusers' pipeline; 'any': 1 where any pixel of
+    the 8x8 block is set (a latent whose block touches the mask is repainted)."""
+    _check(mode in MASK_MODES, f"mask_to_latent: mode should be one of {tuple(MASK_MODES)}")
+    B, H, W, (sb, sh, sw) = _mask3(mask, "mask_to_latent")
+    _check(H % 8 == 0 and W % 8 == 0, "mask_to_latent: H and W should be multiples of 8")
+    out = torch.empty((B, H // 8, W // 8), dtype=torch.float32, device=mask.device)
+    with torch.cuda.device(mask.device):
+        code = _lib.mixdq_mask_to_latent(mask.data_ptr(), IMAGE_DTYPES[mask.dtype], sb, sh, sw, out.data_ptr(), B, H, W,
+                                         MASK_MODES[mode], _stream())
+    _status(code, "mask_to_latent")
+    return out
+
+
+def composite_u8(decoded, original, mask):
+    """The decoded image pasted into the original under the mask, as pixels (mixdq_composite_u8): decoded fp16
+    [B, 3, H, W] (any strides: what VAEDecoder.decode returns), original uint8 [B, 3, H, W] (any strides), mask
+    [B, H, W] or [B, 1, H, W] at image resolution (uint8 / fp16 / fp32, set as in mask_to_latent) -> uint8
+    [B, 3, H, W] in channels-last storage: to_uint8(decoded) where the mask is set, the original's bytes elsewhere."""
+    _check(torch.is_tensor(decoded) and decoded.is_cuda and decoded.dtype == torch.float16 and decoded.dim() == 4
+           and decoded.shape[1] == 3, "composite_u8: decoded should be an fp16 [B, 3, H, W] GPU tensor")
+    _check(torch.is_tensor(original) and original.device == decoded.device and original.dtype == torch.uint8
+           and tuple(original.shape) == tuple(decoded.shape),
+           "composite_u8: original should be a uint8 tensor of decoded's shape on its device")
+    B, _, H, W = decoded.shape
+    mB, mH, mW, mst = _mask3(mask, "composite_u8")
+    _check(mask.device == decoded.device and (mB, mH, mW) == (B, H, W),
+           "composite_u8: mask should have decoded's batch, height and width and be on its device")
+    out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=decoded.device)
+    with torch.cuda.device(decoded.device):
+        code = _lib.mixdq_composite_u8(decoded.data_ptr(), *decoded.stride(), original.data_ptr(), *original.stride(),
+                                       mask.data_ptr(), IMAGE_DTYPES[mask.dtype], *mst, out.data_ptr(), B, H, W,
+                                       _stream())
+    _status(code, "composite_u8")
+    return out.permute(0, 3, 1, 2)

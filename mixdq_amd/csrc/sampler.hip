@@ -11,6 +11,11 @@
 // HBM-bound and small (SDXL at 1024 px: 65 536 elements per image): elementwise over storage, 8 elements per lane
 // per pass -- 16-byte accesses on the FP16 tensors, two on the FP32 ones -- and a scalar tail for n % 8 elements.
 //
+// mixdq_sampler_step_masked (inpainting) is the same step with one more map behind the update, in a sibling kernel:
+//   k   = p*z + q*n0,   x'' = (1 - m)*k + m*x'     (p, q) = blend[*step], m = mask[i / channels]
+// three more FP32 reads per element (z, n0 as 16-byte loads; the mask one value per latent pixel), x'' stored to x
+// and in = f16_rn(x'' * s_next).  The four plain instantiations are untouched by it.
+//
 // The step index is read by every workgroup of the step launch and advanced by the launch BEHIND it on the same
 // stream (sampler_advance_kernel, one thread): launches of one stream run in order, so no workgroup of the step
 // can read the index after it moved, without any in-launch ticket, fence or counter to re-initialise.
@@ -91,12 +96,110 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(float* __restrict__ x
   }
 }
 
+// The masked step: sampler_step_kernel's body, then mixdq_sampler_blend.  Element i of the (channels-last) storage
+// belongs to mask entry i / channels.  C4: channels == 4, an 8-element pass covers exactly two latent pixels; otherwise
+// the quotient and remainder of the pass's first element are divided out once and carried along.
+template <int ROWS, bool NOISE, bool C4>
+__global__ __launch_bounds__(256) void sampler_step_masked_kernel(
+    float* __restrict__ x, const __half* __restrict__ eps, __half* __restrict__ in, const float* __restrict__ noise,
+    int64_t noise_stride, const float* __restrict__ coef, const int* __restrict__ step_p, int n_steps, float g, int64_t n,
+    int64_t row_stride, const float* __restrict__ z, const float* __restrict__ noise0, const float* __restrict__ mask,
+    int channels, const float* __restrict__ blend) {
+  const int step = *step_p;
+  if (step < 0 || step >= n_steps) return;        // replayed past the table: nothing is read or written
+  const float4 k = *reinterpret_cast<const float4*>(coef + 4 * (int64_t)step);
+  const float a = k.x, b = k.y, c = k.z, s_next = k.w;
+  const float2 pq = *reinterpret_cast<const float2*>(blend + 2 * (int64_t)step);
+  const float* nz = NOISE ? noise + (int64_t)step * noise_stride : nullptr;
+  const int64_t nvec = n >> 3;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += stride) {
+    const int64_t o = i << 3;
+    const float4 x0 = *reinterpret_cast<const float4*>(x + o), x1 = *reinterpret_cast<const float4*>(x + o + 4);
+    const float4 z0 = *reinterpret_cast<const float4*>(z + o), z1 = *reinterpret_cast<const float4*>(z + o + 4);
+    const float4 i0 = *reinterpret_cast<const float4*>(noise0 + o), i1 = *reinterpret_cast<const float4*>(noise0 + o + 4);
+    const Half8 eu = *reinterpret_cast<const Half8*>(eps + o);
+    Half8 ec = eu;
+    if (ROWS == 2) ec = *reinterpret_cast<const Half8*>(eps + row_stride + o);
+    float4 n0 = x0, n1 = x1;
+    if (NOISE) {
+      n0 = *reinterpret_cast<const float4*>(nz + o);
+      n1 = *reinterpret_cast<const float4*>(nz + o + 4);
+    }
+    float ms[8];
+    if (C4) {
+      const float m0 = mask[2 * i], m1 = mask[2 * i + 1];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) ms[j] = j < 4 ? m0 : m1;
+    } else {
+      int64_t q = o / channels;                    // o + j < n and n % channels == 0: q stays below n / channels
+      int r = (int)(o - q * channels);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        ms[j] = mask[q];
+        if (++r == channels) { r = 0; ++q; }
+      }
+    }
+    const float xs[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
+    const float ns[8] = {n0.x, n0.y, n0.z, n0.w, n1.x, n1.y, n1.z, n1.w};
+    const float zs[8] = {z0.x, z0.y, z0.z, z0.w, z1.x, z1.y, z1.z, z1.w};
+    const float is[8] = {i0.x, i0.y, i0.z, i0.w, i1.x, i1.y, i1.z, i1.w};
+    float y[8];
+    Half8 out;
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      y[j] = mixdq_sampler_blend(step_one<ROWS, NOISE>(xs[j], half_at(eu, j), half_at(ec, j), ns[j], g, a, b, c), zs[j],
+                                 is[j], ms[j], pq.x, pq.y);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      out.w[j] = half_bits(mixdq_sampler_scaled_input(y[2 * j], s_next)) |
+                 (half_bits(mixdq_sampler_scaled_input(y[2 * j + 1], s_next)) << 16);
+    *reinterpret_cast<float4*>(x + o) = make_float4(y[0], y[1], y[2], y[3]);
+    *reinterpret_cast<float4*>(x + o + 4) = make_float4(y[4], y[5], y[6], y[7]);
+    *reinterpret_cast<Half8*>(in + o) = out;
+    if (ROWS == 2) *reinterpret_cast<Half8*>(in + row_stride + o) = out;
+  }
+  // tail (n % 8 elements), by the first threads of block 0
+  const int64_t t = (nvec << 3) + threadIdx.x;
+  if (blockIdx.x == 0 && t < n) {
+    const float eu = __half2float(eps[t]);
+    const float ec = ROWS == 2 ? __half2float(eps[row_stride + t]) : eu;
+    const float y = mixdq_sampler_blend(step_one<ROWS, NOISE>(x[t], eu, ec, NOISE ? nz[t] : 0.0f, g, a, b, c), z[t],
+                                        noise0[t], mask[t / channels], pq.x, pq.y);
+    const __half h = f32_to_f16_rn(mixdq_sampler_scaled_input(y, s_next));
+    x[t] = y;
+    in[t] = h;
+    if (ROWS == 2) in[row_stride + t] = h;
+  }
+}
+
 // Behind the step on the same stream: the timestep of the NEXT UNet forward, and the index moves on.
 __global__ void sampler_advance_kernel(const float* __restrict__ t_table, int n_steps, int* step_p, float* timestep) {
   const int step = *step_p;
   if (step < 0 || step >= n_steps) return;
   *timestep = t_table[step + 1];
   *step_p = step + 1;
+}
+
+// The argument checks of both entry points, in mixdq_sampler_step's order.
+int check_step_args(const float* x, const void* eps_f16, const void* in_f16, const float* noise_or_null,
+                    int64_t noise_stride, const float* coef, const float* t_table, int n_steps, const int* step,
+                    const float* timestep, int64_t n, int rows_per_image, int64_t row_stride) {
+  if (!x || !eps_f16 || !in_f16 || !coef || !t_table || !step || !timestep) return MIXDQ_ERR_INVALID_ARG;
+  if (n < 0 || n_steps < 1 || (rows_per_image != 1 && rows_per_image != 2)) return MIXDQ_ERR_INVALID_ARG;
+  if (rows_per_image == 2 && row_stride < n) return MIXDQ_ERR_INVALID_ARG;      // the two row blocks would overlap
+  if (noise_or_null && noise_stride < n) return MIXDQ_ERR_INVALID_ARG;
+  if ((uintptr_t)x % 16 || (uintptr_t)eps_f16 % 16 || (uintptr_t)in_f16 % 16 || (uintptr_t)coef % 16 ||
+      (uintptr_t)noise_or_null % 16 || (uintptr_t)t_table % 4 || (uintptr_t)step % 4 || (uintptr_t)timestep % 4)
+    return MIXDQ_ERR_ALIGNMENT;
+  if ((rows_per_image == 2 && row_stride % 8) || (noise_or_null && noise_stride % 4)) return MIXDQ_ERR_ALIGNMENT;
+  return MIXDQ_OK;
+}
+
+int step_blocks(int64_t n) {
+  int64_t blocks = ((n >> 3) + 255) / 256;
+  if (blocks > (int64_t)kNumCU * 8) blocks = (int64_t)kNumCU * 8;
+  return blocks < 1 ? 1 : (int)blocks;
 }
 
 }  // namespace
@@ -108,30 +211,58 @@ extern "C" int mixdq_sampler_step(float* x, const void* eps_f16, void* in_f16, c
                                   int64_t noise_stride, const float* coef, const float* t_table, int n_steps,
                                   int* step, float* timestep, float guidance, int64_t n, int rows_per_image,
                                   int64_t row_stride, mixdq_stream_t stream_) {
-  if (!x || !eps_f16 || !in_f16 || !coef || !t_table || !step || !timestep) return MIXDQ_ERR_INVALID_ARG;
-  if (n < 0 || n_steps < 1 || (rows_per_image != 1 && rows_per_image != 2)) return MIXDQ_ERR_INVALID_ARG;
-  if (rows_per_image == 2 && row_stride < n) return MIXDQ_ERR_INVALID_ARG;      // the two row blocks would overlap
-  if (noise_or_null && noise_stride < n) return MIXDQ_ERR_INVALID_ARG;
-  if ((uintptr_t)x % 16 || (uintptr_t)eps_f16 % 16 || (uintptr_t)in_f16 % 16 || (uintptr_t)coef % 16 ||
-      (uintptr_t)noise_or_null % 16 || (uintptr_t)t_table % 4 || (uintptr_t)step % 4 || (uintptr_t)timestep % 4)
-    return MIXDQ_ERR_ALIGNMENT;
-  if ((rows_per_image == 2 && row_stride % 8) || (noise_or_null && noise_stride % 4)) return MIXDQ_ERR_ALIGNMENT;
+  const int bad = check_step_args(x, eps_f16, in_f16, noise_or_null, noise_stride, coef, t_table, n_steps, step, timestep,
+                                  n, rows_per_image, row_stride);
+  if (bad != MIXDQ_OK) return bad;
   hipStream_t stream = (hipStream_t)stream_;
   if (n > 0) {
-    int64_t blocks = ((n >> 3) + 255) / 256;
-    if (blocks > (int64_t)kNumCU * 8) blocks = (int64_t)kNumCU * 8;
-    if (blocks < 1) blocks = 1;
+    const int blocks = step_blocks(n);
     const __half* eps = (const __half*)eps_f16;
     __half* in = (__half*)in_f16;
-#define S_LAUNCH(R, NZ)                                                                                    \
-  sampler_step_kernel<R, NZ><<<(int)blocks, 256, 0, stream>>>(x, eps, in, noise_or_null, noise_stride, coef, step, \
-                                                              n_steps, guidance, n, row_stride)
+#define S_LAUNCH(R, NZ)                                                                               \
+  sampler_step_kernel<R, NZ><<<blocks, 256, 0, stream>>>(x, eps, in, noise_or_null, noise_stride, coef, step, \
+                                                         n_steps, guidance, n, row_stride)
     if (rows_per_image == 2) {
       if (noise_or_null) S_LAUNCH(2, true); else S_LAUNCH(2, false);
     } else {
       if (noise_or_null) S_LAUNCH(1, true); else S_LAUNCH(1, false);
     }
 #undef S_LAUNCH
+    if (hipGetLastError() != hipSuccess) return MIXDQ_ERR_LAUNCH;
+  }
+  sampler_advance_kernel<<<1, 1, 0, stream>>>(t_table, n_steps, step, timestep);
+  return launch_status();
+}
+
+extern "C" int mixdq_sampler_step_masked(float* x, const void* eps_f16, void* in_f16, const float* noise_or_null,
+                                         int64_t noise_stride, const float* coef, const float* t_table, int n_steps,
+                                         int* step, float* timestep, float guidance, int64_t n, int rows_per_image,
+                                         int64_t row_stride, const float* z, const float* noise0, const float* mask,
+                                         int channels, const float* blend, mixdq_stream_t stream_) {
+  const int bad = check_step_args(x, eps_f16, in_f16, noise_or_null, noise_stride, coef, t_table, n_steps, step, timestep,
+                                  n, rows_per_image, row_stride);
+  if (bad != MIXDQ_OK) return bad;
+  if (!z || !noise0 || !mask || !blend || channels < 1 || n % channels) return MIXDQ_ERR_INVALID_ARG;
+  if ((uintptr_t)z % 16 || (uintptr_t)noise0 % 16 || (uintptr_t)mask % 4 || (uintptr_t)blend % 8)
+    return MIXDQ_ERR_ALIGNMENT;
+  hipStream_t stream = (hipStream_t)stream_;
+  if (n > 0) {
+    const int blocks = step_blocks(n);
+    const __half* eps = (const __half*)eps_f16;
+    __half* in = (__half*)in_f16;
+#define M_LAUNCH(R, NZ, C4)                                                                                          \
+  sampler_step_masked_kernel<R, NZ, C4><<<blocks, 256, 0, stream>>>(x, eps, in, noise_or_null, noise_stride, coef, step, \
+                                                                    n_steps, guidance, n, row_stride, z, noise0, mask,   \
+                                                                    channels, blend)
+#define M_LAUNCH_C(R, NZ) \
+  do { if (channels == 4) M_LAUNCH(R, NZ, true); else M_LAUNCH(R, NZ, false); } while (0)
+    if (rows_per_image == 2) {
+      if (noise_or_null) M_LAUNCH_C(2, true); else M_LAUNCH_C(2, false);
+    } else {
+      if (noise_or_null) M_LAUNCH_C(1, true); else M_LAUNCH_C(1, false);
+    }
+#undef M_LAUNCH_C
+#undef M_LAUNCH
     if (hipGetLastError() != hipSuccess) return MIXDQ_ERR_LAUNCH;
   }
   sampler_advance_kernel<<<1, 1, 0, stream>>>(t_table, n_steps, step, timestep);

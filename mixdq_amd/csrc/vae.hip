@@ -5,6 +5,13 @@
 //                              channels C..7 zero: the 8-channel form conv_in takes on the MFMA tiles (2C % 16 == 0)
 //   mixdq_vae_latent_sample    FP16 moments [B, h, w, 2L] (+ FP32 noise [B, h, w, L]) -> FP32 z [B, h, w, L]
 //
+// and the two launches inpainting adds around the VAE:
+//
+//   mixdq_mask_to_latent       image-resolution mask [B, H, W] uint8 / FP16 / FP32 at any element strides -> FP32
+//                              [B, H/8, W/8] of 0.0 / 1.0: pixel (8i, 8j) (NEAREST) or any pixel of the 8x8 block (ANY)
+//   mixdq_composite_u8         out = mask ? to_uint8(decoded) : original, uint8 [B, H, W, 3]: the pixels outside the
+//                              mask come back bit-identical (the VAE round trip does not reproduce an image)
+//
 // Arithmetic: include/mixdq_math.h (mixdq_pixel_to_unit, mixdq_vae_latent[_mode]), FP32 round-to-nearest, never
 // contracted.  Both are HBM-bound and grid-stride, one pixel (one group of four latent channels) per lane per trip;
 // every load of a trip is requested before the first value is used, and each lane writes one 16-byte store.
@@ -89,6 +96,83 @@ __global__ __launch_bounds__(256) void vae_latent_kernel(const __half* __restric
   }
 }
 
+// ---- inpainting: the mask's binarisation (diffusers': uint8 u / 255 >= 0.5, floats v >= 0.5; NaN compares false)
+__device__ __forceinline__ bool mask_set(uint8_t u) { return u >= 128; }
+__device__ __forceinline__ bool mask_set(__half h) { return __half2float(h) >= 0.5f; }
+__device__ __forceinline__ bool mask_set(float f) { return f >= 0.5f; }
+
+// eight consecutive elements of one mask row in the widest loads their size allows (the launcher checked alignment)
+__device__ __forceinline__ void load_row8(const uint8_t* p, uint8_t (&v)[8]) {
+  const uint2 w = *reinterpret_cast<const uint2*>(p);
+  memcpy(v, &w, 8);
+}
+__device__ __forceinline__ void load_row8(const __half* p, __half (&v)[8]) {
+  const uint4 w = *reinterpret_cast<const uint4*>(p);
+  memcpy(v, &w, 16);
+}
+__device__ __forceinline__ void load_row8(const float* p, float (&v)[8]) {
+  const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
+  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+}
+
+// One lane = one latent pixel.  ANY reads its 8x8 block: WIDE one row per (pair of) vector load(s), otherwise element
+// by element at the caller's strides.
+template <typename T, bool ANY, bool WIDE>
+__global__ __launch_bounds__(256) void mask_to_latent_kernel(const T* __restrict__ mask, int64_t sb, int64_t sh,
+                                                             int64_t sw, float* __restrict__ out, int64_t pixels, int h,
+                                                             int w) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < pixels; i += stride) {
+    const int64_t row = i / w;
+    const int x = (int)(i - row * w);
+    const int64_t b = row / h;
+    const int y = (int)(row - b * h);
+    const T* px = mask + (b * sb + (int64_t)(8 * y) * sh + (int64_t)(8 * x) * sw);
+    bool set = false;
+    if constexpr (!ANY) {
+      set = mask_set(*px);
+    } else if constexpr (WIDE) {
+#pragma unroll
+      for (int r = 0; r < 8; ++r) {
+        T v[8];
+        load_row8(px + r * sh, v);
+#pragma unroll
+        for (int c = 0; c < 8; ++c) set |= mask_set(v[c]);
+      }
+    } else {
+      for (int r = 0; r < 8; ++r)
+#pragma unroll
+        for (int c = 0; c < 8; ++c) set |= mask_set(px[r * sh + c * sw]);
+    }
+    out[i] = set ? 1.0f : 0.0f;
+  }
+}
+
+// One lane = one pixel: three decoded FP16 values, the mask value, three original bytes, three bytes out.
+template <typename T>
+__global__ __launch_bounds__(256) void composite_u8_kernel(const __half* __restrict__ dec, int64_t db, int64_t dc,
+                                                           int64_t dh, int64_t dw, const uint8_t* __restrict__ orig,
+                                                           int64_t ob, int64_t oc, int64_t oh, int64_t ow,
+                                                           const T* __restrict__ mask, int64_t mb, int64_t mh, int64_t mw,
+                                                           uint8_t* __restrict__ out, int64_t pixels, int H, int W) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < pixels; i += stride) {
+    const int64_t row = i / W;
+    const int x = (int)(i - row * W);
+    const int64_t b = row / H;
+    const int y = (int)(row - b * H);
+    const __half* d = dec + (b * db + y * dh + x * dw);
+    const uint8_t* o = orig + (b * ob + y * oh + x * ow);
+    const bool set = mask_set(mask[b * mb + y * mh + x * mw]);
+    const __half d0 = d[0], d1 = d[dc], d2 = d[2 * dc];
+    const uint8_t o0 = o[0], o1 = o[oc], o2 = o[2 * oc];
+    uint8_t* q = out + i * 3;
+    q[0] = set ? mixdq_to_uint8(__half2float(d0)) : o0;
+    q[1] = set ? mixdq_to_uint8(__half2float(d1)) : o1;
+    q[2] = set ? mixdq_to_uint8(__half2float(d2)) : o2;
+  }
+}
+
 int grid_for(int64_t items) {
   int64_t blocks = (items + 255) / 256;
   if (blocks > (int64_t)kNumCU * 8) blocks = (int64_t)kNumCU * 8;
@@ -140,5 +224,68 @@ extern "C" int mixdq_vae_latent_sample(const void* moments_f16, const float* noi
     if (L == 4) V_LAUNCH(false, true); else V_LAUNCH(false, false);
   }
 #undef V_LAUNCH
+  return launch_status();
+}
+
+namespace {
+int image_elem_size(int dtype) {
+  return dtype == MIXDQ_IMAGE_U8 ? 1 : dtype == MIXDQ_IMAGE_F16 ? 2 : dtype == MIXDQ_IMAGE_F32 ? 4 : 0;
+}
+
+template <typename T>
+void launch_mask_to_latent(const void* mask, int64_t sb, int64_t sh, int64_t sw, float* out, int64_t pixels, int h, int w,
+                           int mode, hipStream_t stream) {
+  const T* m = (const T*)mask;
+  const int blocks = grid_for(pixels);
+  // a row of 8 elements as one 8-byte (uint8) or 16-byte load(s): every row start must be aligned to that
+  const int64_t align = sizeof(T) == 1 ? 8 : 16;
+  const bool wide = sw == 1 && (uintptr_t)mask % align == 0 && (sh * (int64_t)sizeof(T)) % align == 0 &&
+                    (sb * (int64_t)sizeof(T)) % align == 0;
+  if (mode == MIXDQ_MASK_NEAREST)
+    mask_to_latent_kernel<T, false, false><<<blocks, 256, 0, stream>>>(m, sb, sh, sw, out, pixels, h, w);
+  else if (wide)
+    mask_to_latent_kernel<T, true, true><<<blocks, 256, 0, stream>>>(m, sb, sh, sw, out, pixels, h, w);
+  else
+    mask_to_latent_kernel<T, true, false><<<blocks, 256, 0, stream>>>(m, sb, sh, sw, out, pixels, h, w);
+}
+}  // namespace
+
+extern "C" int mixdq_mask_to_latent(const void* mask, int dtype, int64_t sb, int64_t sh, int64_t sw, float* out, int B,
+                                    int H, int W, int mode, mixdq_stream_t stream_) {
+  const int elem = image_elem_size(dtype);
+  if (B < 0 || H < 0 || W < 0 || H % 8 || W % 8 || !elem) return MIXDQ_ERR_INVALID_ARG;
+  if (mode != MIXDQ_MASK_NEAREST && mode != MIXDQ_MASK_ANY) return MIXDQ_ERR_INVALID_ARG;
+  if ((int64_t)B * H * W == 0) return MIXDQ_OK;     // (an empty tensor has no storage: before the pointer checks)
+  if (!mask || !out) return MIXDQ_ERR_INVALID_ARG;
+  if ((uintptr_t)out % 4 || (uintptr_t)mask % elem) return MIXDQ_ERR_ALIGNMENT;
+  hipStream_t stream = (hipStream_t)stream_;
+  const int h = H / 8, w = W / 8;
+  const int64_t pixels = (int64_t)B * h * w;
+  if (dtype == MIXDQ_IMAGE_U8) launch_mask_to_latent<uint8_t>(mask, sb, sh, sw, out, pixels, h, w, mode, stream);
+  else if (dtype == MIXDQ_IMAGE_F16) launch_mask_to_latent<__half>(mask, sb, sh, sw, out, pixels, h, w, mode, stream);
+  else launch_mask_to_latent<float>(mask, sb, sh, sw, out, pixels, h, w, mode, stream);
+  return launch_status();
+}
+
+extern "C" int mixdq_composite_u8(const void* decoded_f16, int64_t db, int64_t dc, int64_t dh, int64_t dw,
+                                  const uint8_t* original, int64_t ob, int64_t oc, int64_t oh, int64_t ow,
+                                  const void* mask, int mask_dtype, int64_t mb, int64_t mh, int64_t mw, uint8_t* out,
+                                  int B, int H, int W, mixdq_stream_t stream_) {
+  const int elem = image_elem_size(mask_dtype);
+  if (B < 0 || H < 0 || W < 0 || !elem) return MIXDQ_ERR_INVALID_ARG;
+  const int64_t pixels = (int64_t)B * H * W;
+  if (pixels == 0) return MIXDQ_OK;                 // (an empty tensor has no storage: before the pointer checks)
+  if (!decoded_f16 || !original || !mask || !out) return MIXDQ_ERR_INVALID_ARG;
+  if ((uintptr_t)decoded_f16 % 2 || (uintptr_t)mask % elem) return MIXDQ_ERR_ALIGNMENT;
+  hipStream_t stream = (hipStream_t)stream_;
+  const __half* d = (const __half*)decoded_f16;
+  const int blocks = grid_for(pixels);
+#define C_LAUNCH(T) \
+  composite_u8_kernel<T><<<blocks, 256, 0, stream>>>(d, db, dc, dh, dw, original, ob, oc, oh, ow, (const T*)mask, mb, mh, \
+                                                     mw, out, pixels, H, W)
+  if (mask_dtype == MIXDQ_IMAGE_U8) C_LAUNCH(uint8_t);
+  else if (mask_dtype == MIXDQ_IMAGE_F16) C_LAUNCH(__half);
+  else C_LAUNCH(float);
+#undef C_LAUNCH
   return launch_status();
 }

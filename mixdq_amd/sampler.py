@@ -17,6 +17,13 @@ Image-to-image starts the same loop at a later step: `img2img_start(n_steps, str
 `Schedule.start(t0)` the scalars that noise the encoded image to that step's level, and
 `sample(..., init_latents=z, strength=s)` sets the device step state to t0 and replays the SAME graph n_steps - t0
 times.  `Sampler.img2img` runs VAEEncoder.encode, that loop and VAEDecoder.decode on one stream.
+
+Inpainting (a 4-channel UNet, diffusers' StableDiffusion[XL]InpaintPipeline with num_channels_unet == 4) is the same
+loop with one more map per step: after the update, the region the mask keeps is overwritten with the image latents
+noised to the NEXT step's level, x = (1 - m) * (p * z + q * noise) + m * x', (p, q) = `Schedule.blend[step]`
+(mixdq_sampler_step_masked).  `sample(..., init_latents=z, mask=m)` replays a second captured graph -- the UNet forward
+plus that step -- on the same static buffers; `Sampler.inpaint` runs encode, mixdq_mask_to_latent, that loop, decode
+and, on request, the uint8 composite with the original image on one stream.
 """
 import numpy as np
 
@@ -73,7 +80,9 @@ class Schedule:
     """What one (kind, n_steps, spacing) needs: `timesteps` int64 [n]; `sigmas` float64 [n + 1] (euler kinds; ends in
     0); `coef` FP32 [n, 4] = (a, b, c, s_next), computed in float64; `t_table` FP32 [n + 1] (the
     timesteps, then one unused entry the last step's advance reads); `init_scale`: initial state = noise *
-    init_scale; `input_scale0`: first UNet input = f16(state * input_scale0)."""
+    init_scale; `input_scale0`: first UNet input = f16(state * input_scale0); `blend` FP32 [n, 2] = (p, q), computed in
+    float64: what the masked step noises the kept region with after step i -- row i < n - 1 the schedulers' add_noise
+    at timesteps[i + 1] (`start(i + 1)[:2]`), the last row (1, 0): the kept region ends as the clean image latents."""
 
     def __init__(self, kind, n_steps, spacing=None):
         self.kind, self.n_steps = kind, int(n_steps)
@@ -108,6 +117,8 @@ class Schedule:
         self.coef = coef.astype(np.float32)
         self.t_table = np.concatenate([ts.astype(np.float64), [0.0]]).astype(np.float32)
         self.uses_noise = bool((self.coef[:, 2] != 0).any())
+        self.blend = np.array([self.start(i + 1)[:2] for i in range(self.n_steps - 1)] + [(1.0, 0.0)],
+                              dtype=np.float64).astype(np.float32)
 
     def start(self, t0: int):
         """(a0, c0, s0) in float64 for a run that starts at step `t0` from latents z: state = a0 * z + c0 * noise (the
@@ -137,7 +148,10 @@ class Sampler:
     The first sample() captures ONE step -- the UNet forward, then mixdq_sampler_step -- into a hipGraph on static
     buffers; every sample() copies its inputs in, resets the device step state and replays that graph n_steps
     times: no host synchronisation, host write or eager kernel between the replays.  Inputs of another shape need
-    another Sampler."""
+    another Sampler.  The first sample(mask=...) captures a SECOND graph on the same buffers -- the UNet forward, then
+    mixdq_sampler_step_masked -- which shares the first one's memory pool (neither keeps a tensor alive between
+    replays, and they never run concurrently); the plain graph is not touched, and one Sampler serves text-to-image,
+    image-to-image and masked calls in any order."""
 
     def __init__(self, unet, kind, n_steps, guidance_scale=0.0, spacing=None):
         self.unet = unet
@@ -146,11 +160,12 @@ class Sampler:
         self.guidance_scale = float(guidance_scale)
         self.rows_per_image = 2 if self.guidance_scale > 1.0 else 1
         self._graph = None
+        self._graph_masked = None
+        self._key = None
 
     # ---- static buffers + capture ---------------------------------------------------------------------------
-    def _capture(self, noise, encoder_hidden_states, added_cond_kwargs):
+    def _setup(self, noise, encoder_hidden_states, added_cond_kwargs):
         import torch
-        from mixdq_amd import _C
         from mixdq_amd.quantize_sdxl import _clone_args
         sch, dev = self.schedule, noise.device
         B, C, H, W = noise.shape
@@ -159,6 +174,7 @@ class Sampler:
         def nhwc(*lead, dtype):       # [*lead, C, H, W] logical, channels-last in memory
             nd = len(lead)
             return torch.zeros(*lead, H, W, C, dtype=dtype, device=dev).permute(*range(nd), nd + 2, nd, nd + 1)
+        self._nhwc = nhwc
         self._x = nhwc(B, dtype=torch.float32)
         self._in = nhwc(R, dtype=torch.float16)
         self._noise = nhwc(self.n_steps, B, dtype=torch.float32) if sch.uses_noise else None
@@ -170,8 +186,21 @@ class Sampler:
         self._input_scale0 = torch.tensor(sch.input_scale0, dtype=torch.float32, device=dev)
         self._ehs, self._added = _clone_args((encoder_hidden_states, added_cond_kwargs))
         self._key = self._shape_key(noise, encoder_hidden_states, added_cond_kwargs)
+
+    def _capture(self, noise, masked=False):
+        """Capture one step -- the UNet forward, then mixdq_sampler_step (masked: mixdq_sampler_step_masked, reading the
+        static z / noise0 / mask buffers made here) -- on the static buffers and return the graph."""
+        import torch
+        from mixdq_amd import _C
+        dev = noise.device
+        B, C, H, W = noise.shape
         forward = getattr(self.unet.forward, "__wrapped__", self.unet.forward)   # (under hip_graph_opt: the eager one)
         n = B * C * H * W
+        if masked:
+            self._z = self._nhwc(B, dtype=torch.float32)
+            self._noise0 = self._nhwc(B, dtype=torch.float32)
+            self._mask = torch.zeros(B, H, W, dtype=torch.float32, device=dev)
+            self._blend = torch.from_numpy(self.schedule.blend).to(dev)
 
         def one_step():
             eps = forward(self._in, self._t, self._ehs, self._added)[0]
@@ -179,8 +208,13 @@ class Sampler:
                     or any(a != b for a, b, d in zip(eps.stride(), self._in.stride(), eps.shape) if d > 1)):
                 raise RuntimeError("Sampler: the UNet's output is not an FP16 tensor of its input's shape in channels-"
                                    f"last storage (shape {tuple(eps.shape)}, strides {eps.stride()}, {eps.dtype})")
-            _C.sampler_step(self._x, eps, self._in, self._coef, self._t_table, self._step, self._t,
-                            self.guidance_scale, self.rows_per_image, self._noise, n=n)
+            if masked:
+                _C.sampler_step_masked(self._x, eps, self._in, self._coef, self._t_table, self._step, self._t, self._z,
+                                       self._noise0, self._mask, self._blend, self.guidance_scale, self.rows_per_image,
+                                       self._noise, channels=C, n=n)
+            else:
+                _C.sampler_step(self._x, eps, self._in, self._coef, self._t_table, self._step, self._t,
+                                self.guidance_scale, self.rows_per_image, self._noise, n=n)
 
         self._reset(noise, None)
         side = torch.cuda.Stream(dev)
@@ -192,9 +226,11 @@ class Sampler:
         torch.cuda.current_stream(dev).wait_stream(side)
         self._step.zero_()
         graph = torch.cuda.CUDAGraph()
-        with torch.no_grad(), torch.cuda.graph(graph):
+        other = self._graph if masked else self._graph_masked
+        pool = {} if other is None else {"pool": other.pool()}
+        with torch.no_grad(), torch.cuda.graph(graph, **pool):
             one_step()
-        self._graph = graph
+        return graph
 
     @staticmethod
     def _shape_key(noise, ehs, added):
@@ -236,7 +272,7 @@ class Sampler:
 
     # ---- the loop -------------------------------------------------------------------------------------------
     def sample(self, noise, encoder_hidden_states, added_cond_kwargs=None, step_noise=None, *, init_latents=None,
-               strength=None):
+               strength=None, mask=None):
         """noise [B, C, H, W] (unit variance; FP32 or FP16), encoder_hidden_states [R, T, D] FP16 (R = B, or 2B
         under guidance), added_cond_kwargs as the UNet takes them (R rows), step_noise [n_steps, B, C, H, W]: the
         noise each stochastic step adds (required where the schedule has a non-zero c: euler_ancestral and lcm with
@@ -246,13 +282,29 @@ class Sampler:
         VAEEncoder.encode returns) together with `strength` in (0, 1].  The run starts at step t0 =
         img2img_start(n_steps, strength) from init_latents noised to that step's level (Schedule.start) and replays
         the same captured graph n_steps - t0 times; step_noise keeps its [n_steps, ...] shape, rows >= t0 are read.
-        A Sampler captured by either kind of call serves the other."""
+        A Sampler captured by either kind of call serves the other.
+
+        Inpainting: `mask` (FP32 [B, h, w] or [B, 1, h, w] on noise's device, values in [0, 1]: 1 repaints, 0 keeps
+        -- what _C.mask_to_latent returns, or a soft mask of the caller's) together with `init_latents`.  After every
+        step the kept region is overwritten with init_latents noised with `noise` to the next step's level
+        (Schedule.blend; after the last step: init_latents themselves), on the second captured graph.  `strength`
+        None then means the whole schedule from pure noise, exactly as a text-to-image call starts (diffusers'
+        is_strength_max); otherwise the start is image-to-image's.  The mask does not touch the start state."""
         import torch
         from mixdq_amd.quantize_sdxl import _copy_into
         if not (torch.is_tensor(noise) and noise.is_cuda and noise.dim() == 4):
             raise RuntimeError("Sampler.sample: noise should be a [B, C, H, W] GPU tensor")
-        if (init_latents is None) != (strength is None):
-            raise RuntimeError("Sampler.sample: init_latents and strength go together (both, or neither)")
+        if mask is None:
+            if (init_latents is None) != (strength is None):
+                raise RuntimeError("Sampler.sample: init_latents and strength go together (both, or neither)")
+        else:
+            if init_latents is None:
+                raise RuntimeError("Sampler.sample: mask requires init_latents (the image whose unmasked region is kept)")
+            B, _, H, W = noise.shape
+            if not (torch.is_tensor(mask) and mask.device == noise.device and mask.dtype == torch.float32
+                    and tuple(mask.shape) in ((B, H, W), (B, 1, H, W))):
+                raise RuntimeError(f"Sampler.sample: mask should be an FP32 tensor of shape {(B, H, W)} or "
+                                   f"{(B, 1, H, W)} on noise's device")
         t0 = 0
         if init_latents is not None:
             if not (torch.is_tensor(init_latents) and init_latents.device == noise.device
@@ -260,7 +312,8 @@ class Sampler:
                     and init_latents.dtype in (torch.float32, torch.float16)):
                 raise RuntimeError("Sampler.sample: init_latents should be an FP32 or FP16 tensor of noise's shape "
                                    f"{tuple(noise.shape)} on its device")
-            t0 = img2img_start(self.n_steps, strength)
+            if strength is not None:
+                t0 = img2img_start(self.n_steps, strength)
         R = noise.shape[0] * self.rows_per_image
         if encoder_hidden_states.shape[0] != R:
             raise RuntimeError(f"Sampler.sample: encoder_hidden_states should have {R} rows")
@@ -270,17 +323,28 @@ class Sampler:
                 raise RuntimeError(f"Sampler.sample: this schedule needs step_noise of shape {want}")
         elif step_noise is not None:
             raise RuntimeError("Sampler.sample: this schedule adds no noise: step_noise must be None")
-        if self._graph is None:
-            self._capture(noise, encoder_hidden_states, added_cond_kwargs)
+        if self._key is None:
+            self._setup(noise, encoder_hidden_states, added_cond_kwargs)
         elif self._shape_key(noise, encoder_hidden_states, added_cond_kwargs) != self._key:
             raise RuntimeError("Sampler.sample: inputs differ in shape from those the step graph was captured for")
+        if mask is None:
+            if self._graph is None:
+                self._graph = self._capture(noise)
+            graph = self._graph
+        else:
+            if self._graph_masked is None:
+                self._graph_masked = self._capture(noise, masked=True)
+            graph = self._graph_masked
+            self._z.copy_(init_latents)             # (an FP16 tensor widens exactly)
+            self._noise0.copy_(noise)
+            self._mask.copy_(mask.reshape(self._mask.shape))
         _copy_into((self._ehs, self._added), (encoder_hidden_states, added_cond_kwargs))
-        if init_latents is None:
+        if init_latents is None or strength is None:
             self._reset(noise, step_noise)
         else:
             self._reset_at(t0, init_latents, noise, step_noise)
         for _ in range(self.n_steps - t0):
-            self._graph.replay()
+            graph.replay()
         return self._x.clone()
 
     def sample_image(self, vae, noise, encoder_hidden_states, added_cond_kwargs=None, step_noise=None):
@@ -299,3 +363,22 @@ class Sampler:
         latents = self.sample(noise, encoder_hidden_states, added_cond_kwargs, step_noise, init_latents=z,
                               strength=strength)
         return latents, dec.decode(latents)
+
+    def inpaint(self, enc, dec, image, mask, noise, encoder_hidden_states, added_cond_kwargs=None, *, strength=None,
+                step_noise=None, latent_noise=None, mask_mode="nearest", composite=False):
+        """Inpainting on one stream: `enc.encode(image, latent_noise)`, `_C.mask_to_latent(mask, mask_mode)` (mask at
+        image resolution, [B, H, W] or [B, 1, H, W], uint8 / FP16 / FP32: set where repainted; 'nearest' is
+        diffusers' downscaling, 'any' repaints every latent whose 8x8 block touches the mask),
+        sample(init_latents=that, strength=strength, mask=that), `dec.decode` -- nothing waits for the GPU in between.
+        strength None: the whole schedule from pure noise.  Returns (FP32 latents, FP16 image [B, 3, H, W]); with
+        composite=True `image` must be uint8 and the second result is uint8: the decoded pixels where the mask is
+        set, the input's own bytes elsewhere (vae.composite_uint8)."""
+        import torch
+        from mixdq_amd import _C
+        if composite and not (torch.is_tensor(image) and image.dtype == torch.uint8):
+            raise RuntimeError("Sampler.inpaint: composite=True pastes into the input pixels: image should be uint8")
+        z = enc.encode(image, latent_noise)
+        latents = self.sample(noise, encoder_hidden_states, added_cond_kwargs, step_noise, init_latents=z,
+                              strength=strength, mask=_C.mask_to_latent(mask, mask_mode))
+        decoded = dec.decode(latents)
+        return latents, (_C.composite_u8(decoded, image, mask) if composite else decoded)

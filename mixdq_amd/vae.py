@@ -361,6 +361,15 @@ def to_uint8(image):
     return ((image.to(torch.float32) / 2 + 0.5).clamp(0, 1) * 255).round().to(torch.uint8)
 
 
+def composite_uint8(decoded, original, mask):
+    """Inpainting's last step, one launch (mixdq_composite_u8): to_uint8(decoded) where `mask` (image resolution,
+    [B, H, W] or [B, 1, H, W]; uint8 >= 128 or float >= 0.5 is set) is set, `original`'s bytes elsewhere -- every pixel
+    outside the mask comes back bit-identical, which the VAE round trip alone does not give.  decoded: FP16
+    [B, 3, H, W] as VAEDecoder.decode returns it; original: uint8, same shape, any strides.  uint8, channels-last."""
+    from mixdq_amd import _C
+    return _C.composite_u8(decoded, original, mask)
+
+
 def from_uint8(pixels):
     """The inverse of to_uint8: uint8 -> FP16 in [-1, 1], f16(f32(u) * f32(2 / 255) - 1) with each FP32 operation
     rounded -- the ingest kernel's uint8 arithmetic (mixdq_image_to_nhwc8_f16) restated in torch.  For every u it is
