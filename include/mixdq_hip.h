@@ -159,6 +159,21 @@ int mixdq_quantize_f16_i8(const void* x_f16, int8_t* out,
                           const int64_t* out_strides, int ndim,
                           const float* scale_inv, const float* zero_point,
                           int flags, mixdq_stream_t stream);
+/* What mixdq_quantize_f16_i8 would launch for these sizes, strides and pointers: the answer of the host function
+ * the launch itself calls (dimensions sorted by x stride, size-1 dimensions dropped, mergeable neighbours
+ * collapsed; more than four left: MIXDQ_ERR_SHAPE).  No GPU needed; x_f16 / out are looked at for their alignment
+ * only (16 / 8 bytes) and never dereferenced.  Returns the status the launch would return before launching; with
+ * MIXDQ_OK the outputs (each may be null) hold
+ *   *route            0 dense (linear on both sides, 8 elements a lane-step), 1 rows (inner run contiguous on both
+ *                     sides, a multiple of 8, outer strides multiples of 8, aligned), 2 scalar (one element a
+ *                     lane-step); -1: no element, nothing is launched
+ *   *rank             dimensions left after the collapse (1..4; 0 with route -1)
+ *   collapsed_sizes4  their sizes, slowest first, right-aligned in four entries (leading entries 1)
+ *   *blocks           blocks of 256 lanes in the grid (at most 8 per CU; the kernels grid-stride beyond). */
+int mixdq_quantize_f16_i8_route(const int64_t* sizes, const int64_t* x_strides,
+                                const int64_t* out_strides, int ndim,
+                                const void* x_f16, const void* out,
+                                int* route, int* rank, int64_t* collapsed_sizes4, int* blocks);
 
 /* ---------------------------------------------------------------------------------------------
  * a2. INT8 x INT8 -> INT32 GEMM with FP32 epilogue -> FP16.

@@ -318,6 +318,26 @@ def _quantize(input, scale_inv, zero_point, abits=8):
     return out
 
 
+if not hasattr(_lib, "mixdq_quantize_f16_i8_route"):
+    raise ImportError(f"{LIB_PATH} does not export mixdq_quantize_f16_i8_route (rebuild with "
+                      "`python -m mixdq_amd.build --force`)")
+_lib.mixdq_quantize_f16_i8_route.argtypes = [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]
+_lib.mixdq_quantize_f16_i8_route.restype = _i32
+QUANTIZE_ROUTES = {-1: "none", 0: "dense", 1: "rows", 2: "scalar"}
+
+
+def quantize_route(sizes, x_strides, out_strides, x_ptr: int, out_ptr: int):
+    """What mixdq_quantize_f16_i8 launches for this call, asked of the library (no GPU needed; the pointers are
+    looked at for alignment only): (status, route name, collapsed rank, the four collapsed sizes, blocks)."""
+    nd = len(sizes)
+    route, rank, blocks = ctypes.c_int(-1), ctypes.c_int(0), ctypes.c_int(0)
+    sz4 = (ctypes.c_int64 * 4)()
+    code = _lib.mixdq_quantize_f16_i8_route(_i64arr(list(sizes) or [1]), _i64arr(list(x_strides) or [1]),
+                                            _i64arr(list(out_strides) or [1]), nd or 1, x_ptr, out_ptr,
+                                            ctypes.byref(route), ctypes.byref(rank), sz4, ctypes.byref(blocks))
+    return int(code), QUANTIZE_ROUTES[route.value], rank.value, tuple(sz4), blocks.value
+
+
 def quantize_per_tensor_to_int8(input, scale_inv, zero_point, *, _abits=8):
     """Quantize to int 8 per tensor with scale and zero point.  `_abits=4`: a 4-bit activation quantizer
     (MIXDQ_FLAG_A4_0): the same INT8 operand clamped to [-128, -113]."""

@@ -156,21 +156,20 @@ inline int grid_for(int64_t work_items) {
   return (int)blocks;
 }
 
-}  // namespace
-}  // namespace mixdq
+// What one mixdq_quantize_f16_i8 call launches: the planner's answer (mixdq_quantize_f16_i8_route reports it).
+enum { kRouteNone = -1, kRouteDense = 0, kRouteRows = 1, kRouteScalar = 2 };
+struct QuantizePlan {
+  int route;            // kRouteNone: no element, nothing is launched
+  int rank;             // dimensions left after the sort and the collapse (m; 0 with kRouteNone)
+  int blocks;           // grid of the launch (256 lanes a block)
+  int64_t numel;
+  StridedArgs a;        // the collapsed dimensions, right-aligned (dense: size[3] = numel)
+};
 
-using namespace mixdq;
-
-extern "C" int mixdq_quantize_f16_i8(const void* x_f16, int8_t* out, const int64_t* sizes,
-                                     const int64_t* x_strides, const int64_t* out_strides,
-                                     int ndim, const float* scale_inv, const float* zero_point,
-                                     int flags, mixdq_stream_t stream_) {
-  if (flags & MIXDQ_FLAG_ACT_ANY) return MIXDQ_ERR_UNSUPPORTED;   // mixdq_linear_f16's epilogue activations
-  if (ndim < 0 || ndim > 8 || !scale_inv || !zero_point) return MIXDQ_ERR_INVALID_ARG;
-  hipStream_t stream = (hipStream_t)stream_;
-  if (flags & (MIXDQ_FLAG_A4_1 | MIXDQ_FLAG_A4_2)) return MIXDQ_ERR_UNSUPPORTED;   // one quantizer: slot 0
-  const bool unfused = flags & MIXDQ_FLAG_UNFUSED, a4 = flags & MIXDQ_FLAG_A4_0;
-  // ---- sort dims by x stride (descending), drop size-1 dims, collapse mergeable neighbours ----
+// Sort the dimensions by x stride (descending), drop size-1 dimensions, collapse mergeable neighbours, and choose
+// the kernel and its grid.  Host arithmetic only: x and out are looked at for their alignment, never dereferenced.
+inline int plan_quantize(const int64_t* sizes, const int64_t* x_strides, const int64_t* out_strides, int ndim,
+                         const void* x, const void* out, QuantizePlan* p) {
   int64_t sz[8], xs[8], os[8];
   int n = 0;
   int64_t numel = 1;
@@ -181,8 +180,10 @@ extern "C" int mixdq_quantize_f16_i8(const void* x_f16, int8_t* out, const int64
       sz[n] = sizes[d]; xs[n] = x_strides[d]; os[n] = out_strides[d]; ++n;
     }
   }
-  if (numel == 0) return MIXDQ_OK;
-  if (!x_f16 || !out) return MIXDQ_ERR_INVALID_ARG;
+  p->route = kRouteNone; p->rank = 0; p->blocks = 0; p->numel = numel;
+  for (int i = 0; i < 4; ++i) { p->a.size[i] = 1; p->a.xs[i] = 0; p->a.os[i] = 0; }
+  if (numel == 0) { p->a.size[3] = 0; return MIXDQ_OK; }
+  if (!x || !out) return MIXDQ_ERR_INVALID_ARG;
   for (int i = 1; i < n; ++i)   // insertion sort, stable
     for (int j = i; j > 0 && xs[j - 1] < xs[j]; --j) {
       int64_t t;
@@ -200,11 +201,44 @@ extern "C" int mixdq_quantize_f16_i8(const void* x_f16, int8_t* out, const int64
   }
   if (m == 0) { sz[0] = 1; xs[0] = 1; os[0] = 1; m = 1; }
   if (m > 4) return MIXDQ_ERR_SHAPE;
-  const __half* x = (const __half*)x_f16;
+  StridedArgs& a = p->a;
+  for (int i = 0; i < m; ++i) {
+    a.size[4 - m + i] = sz[i]; a.xs[4 - m + i] = xs[i]; a.os[4 - m + i] = os[i];
+  }
+  p->rank = m;
   const bool aligned = ((uintptr_t)x % 16 == 0) && ((uintptr_t)out % 8 == 0);
-
   if (m == 1 && xs[0] == 1 && os[0] == 1 && aligned) {
-    int grid = grid_for((numel >> 3) + 1);
+    p->route = kRouteDense;
+    p->blocks = grid_for((numel >> 3) + 1);
+    return MIXDQ_OK;
+  }
+  bool rows_ok = aligned && a.xs[3] == 1 && a.os[3] == 1 && a.size[3] % 8 == 0;
+  for (int i = 0; i < 3 && rows_ok; ++i)
+    if (a.size[i] > 1 && (a.xs[i] % 8 != 0 || a.os[i] % 8 != 0)) rows_ok = false;
+  p->route = rows_ok ? kRouteRows : kRouteScalar;
+  p->blocks = grid_for(rows_ok ? numel >> 3 : numel);
+  return MIXDQ_OK;
+}
+
+}  // namespace
+}  // namespace mixdq
+
+using namespace mixdq;
+
+extern "C" int mixdq_quantize_f16_i8(const void* x_f16, int8_t* out, const int64_t* sizes,
+                                     const int64_t* x_strides, const int64_t* out_strides,
+                                     int ndim, const float* scale_inv, const float* zero_point,
+                                     int flags, mixdq_stream_t stream_) {
+  if (flags & MIXDQ_FLAG_ACT_ANY) return MIXDQ_ERR_UNSUPPORTED;   // mixdq_linear_f16's epilogue activations
+  if (ndim < 0 || ndim > 8 || !scale_inv || !zero_point) return MIXDQ_ERR_INVALID_ARG;
+  hipStream_t stream = (hipStream_t)stream_;
+  if (flags & (MIXDQ_FLAG_A4_1 | MIXDQ_FLAG_A4_2)) return MIXDQ_ERR_UNSUPPORTED;   // one quantizer: slot 0
+  const bool unfused = flags & MIXDQ_FLAG_UNFUSED, a4 = flags & MIXDQ_FLAG_A4_0;
+  QuantizePlan p;
+  const int status = plan_quantize(sizes, x_strides, out_strides, ndim, x_f16, out, &p);
+  if (status != MIXDQ_OK || p.route == kRouteNone) return status;
+  const __half* x = (const __half*)x_f16;
+  const int grid = p.blocks;
 #define Q_LAUNCH(K, ...)                                                              \
   do {                                                                                \
     if (a4) { if (unfused) K<true, true><<<grid, 256, 0, stream>>>(__VA_ARGS__);     \
@@ -212,26 +246,27 @@ extern "C" int mixdq_quantize_f16_i8(const void* x_f16, int8_t* out, const int64
     else if (unfused) K<true><<<grid, 256, 0, stream>>>(__VA_ARGS__);                 \
     else K<false><<<grid, 256, 0, stream>>>(__VA_ARGS__);                             \
   } while (0)
-    Q_LAUNCH(quantize_dense_kernel, x, out, scale_inv, zero_point, numel);
-    return launch_status();
-  }
-  StridedArgs a;
-  for (int i = 0; i < 4; ++i) { a.size[i] = 1; a.xs[i] = 0; a.os[i] = 0; }
-  for (int i = 0; i < m; ++i) {
-    a.size[4 - m + i] = sz[i]; a.xs[4 - m + i] = xs[i]; a.os[4 - m + i] = os[i];
-  }
-  bool rows_ok = aligned && a.xs[3] == 1 && a.os[3] == 1 && a.size[3] % 8 == 0;
-  for (int i = 0; i < 3 && rows_ok; ++i)
-    if (a.size[i] > 1 && (a.xs[i] % 8 != 0 || a.os[i] % 8 != 0)) rows_ok = false;
-  if (rows_ok) {
-    int grid = grid_for(numel >> 3);
-    Q_LAUNCH(quantize_rows_kernel, x, out, scale_inv, zero_point, a);
-  } else {
-    int grid = grid_for(numel);
-    Q_LAUNCH(quantize_scalar_kernel, x, out, scale_inv, zero_point, a);
-  }
+  if (p.route == kRouteDense) Q_LAUNCH(quantize_dense_kernel, x, out, scale_inv, zero_point, p.numel);
+  else if (p.route == kRouteRows) Q_LAUNCH(quantize_rows_kernel, x, out, scale_inv, zero_point, p.a);
+  else Q_LAUNCH(quantize_scalar_kernel, x, out, scale_inv, zero_point, p.a);
 #undef Q_LAUNCH
   return launch_status();
+}
+
+extern "C" int mixdq_quantize_f16_i8_route(const int64_t* sizes, const int64_t* x_strides,
+                                           const int64_t* out_strides, int ndim, const void* x_f16,
+                                           const void* out, int* route, int* rank,
+                                           int64_t* collapsed_sizes4, int* blocks) {
+  if (ndim < 0 || ndim > 8) return MIXDQ_ERR_INVALID_ARG;
+  QuantizePlan p;
+  const int status = plan_quantize(sizes, x_strides, out_strides, ndim, x_f16, out, &p);
+  if (status != MIXDQ_OK) return status;
+  if (route) *route = p.route;
+  if (rank) *rank = p.rank;
+  if (blocks) *blocks = p.blocks;
+  if (collapsed_sizes4)
+    for (int i = 0; i < 4; ++i) collapsed_sizes4[i] = p.a.size[i];
+  return MIXDQ_OK;
 }
 
 extern "C" int mixdq_embed_tokens_f16(const int32_t* ids, const void* tok_f16, const void* pos_f16, void* out_f16,

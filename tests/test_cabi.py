@@ -22,7 +22,7 @@ def declared_symbols():
 
 def test_header_declares_the_operator_entry_points():
     syms = declared_symbols()
-    for required in ("mixdq_quantize_f16_i8", "mixdq_qlinear_w8a8", "mixdq_qlinear_w8a8_rows",
+    for required in ("mixdq_quantize_f16_i8", "mixdq_quantize_f16_i8_route", "mixdq_qlinear_w8a8", "mixdq_qlinear_w8a8_rows",
                      "mixdq_qconv2d_w8a8", "mixdq_qconv2d_w8a8_table", "mixdq_conv_border_table",
                      "mixdq_conv_zero_point_propagate", "mixdq_qconv2d_workspace_bytes",
                      "mixdq_gemm_f16", "mixdq_status_string", "mixdq_abi_version",
