@@ -655,6 +655,39 @@ int mixdq_sampler_step_masked(float* x, const void* eps_f16, void* in_f16, const
                               int64_t row_stride, const float* z, const float* noise0, const float* mask,
                               int channels, const float* blend, mixdq_stream_t stream);
 
+/* The step of a two-step multistep solver, DPM-Solver++ 2M (diffusers' DPMSolverMultistepScheduler, epsilon
+ * prediction, solver_order 2, midpoint): the one update rule here that is not an affine map of (x, eps, noise), because
+ * a second-order step also needs the previous step's data prediction.  hist: FP32, n elements in x's stride pattern,
+ * 16-byte aligned, a buffer of its own (it may not overlap x) -- that previous prediction; coef8: FP32 [n_steps][8],
+ * 16-byte aligned, row i = (u, v, A, B1, B2, D2, s_next, 0); first: a device int32 holding the index of the first step
+ * of this run (0, or an image-to-image run's start).  With e the guided epsilon as above, per element i < n:
+ *   x0      = (u * x[i]) + (v * e)                                          the data prediction
+ *   second  = *step > *first && D2 != 0                                     the same for every element of the launch
+ *   x[i]    = second ? ((A * x[i]) + (B2 * x0)) + (D2 * hist[i]) : (A * x[i]) + (B1 * x0)
+ *   hist[i] = x0                                                            on EVERY step, first-order ones included
+ *   in[i]   = in[row_stride + i] (rows_per_image == 2) = f16_rn(x[i] * s_next)
+ * every operation FP32 round-to-nearest, never contracted (include/mixdq_math.h: mixdq_sampler_x0,
+ * mixdq_sampler_update_2m, mixdq_sampler_update).  On a first-order step hist is not read: before the first step of a
+ * run it may hold anything, NaN included, and nothing has to clear it between runs.  These kinds add no noise: there
+ * is no noise operand.  The advance launch behind the step and the behaviour past the table (nothing read or written,
+ * hist included) are mixdq_sampler_step's.
+ * Errors: mixdq_sampler_step's (coef8 in coef's place), then null hist / first, hist overlapping x:
+ * MIXDQ_ERR_INVALID_ARG; hist / coef8 not 16-byte, first not 4-byte aligned: MIXDQ_ERR_ALIGNMENT. */
+int mixdq_sampler_step_2m(float* x, const void* eps_f16, void* in_f16, float* hist, const float* coef8,
+                          const float* t_table, int n_steps, int* step, const int* first, float* timestep,
+                          float guidance, int64_t n, int rows_per_image, int64_t row_stride, mixdq_stream_t stream);
+
+/* mixdq_sampler_step_2m for inpainting: with x' the value it would store, x[i] = mixdq_sampler_step_masked's blend of
+ * x' with (p, q) = blend[*step] and m = mask[i / channels], and in[i] is taken from that.  hist[i] is x0 as above,
+ * NOT blended: the solver's history is the model's prediction (diffusers' pipeline overwrites the latents after
+ * scheduler.step and leaves the scheduler's model_outputs alone).  z, noise0, mask, channels, blend and their errors
+ * as in mixdq_sampler_step_masked, after mixdq_sampler_step_2m's. */
+int mixdq_sampler_step_2m_masked(float* x, const void* eps_f16, void* in_f16, float* hist, const float* coef8,
+                                 const float* t_table, int n_steps, int* step, const int* first, float* timestep,
+                                 float guidance, int64_t n, int rows_per_image, int64_t row_stride, const float* z,
+                                 const float* noise0, const float* mask, int channels, const float* blend,
+                                 mixdq_stream_t stream);
+
 /* Which kernel instantiation mixdq_qlinear_w8a8 / mixdq_qconv2d_w8a8 will launch for a problem of
  * M rows x N output channels (k_align = K for Linear, C for Conv2d; k_total = K or R*S*C): the block tile BM x BN x BK
  * and LDS stage count of `igemm_kernel<BM,BN,BK,STAGES,CONV>`, or zeros for the small-alignment

@@ -144,6 +144,19 @@ MIXDQ_HD float mixdq_sampler_blend(float x_new, float z, float n0, float m, floa
   return MIXDQ_ADD_RN(MIXDQ_MUL_RN(MIXDQ_SUB_RN(1.0f, m), k), MIXDQ_MUL_RN(m, x_new));
 }
 
+/* ---- multistep sampler step (mixdq_sampler_step_2m, csrc/sampler.hip), same rule.  DPM-Solver++ 2M works on the
+ * data prediction x0 and keeps the previous step's one as its history h:
+ *   x0 = (u*x) + (v*e)                          two products and a sum; e the guided epsilon
+ *   x' = ((A*x) + (B*x0)) + (D*h)               second-order step: each product rounded, then the two sums
+ * The first-order step is mixdq_sampler_update(x, x0, A, B1): h is not an operand of it. */
+MIXDQ_HD float mixdq_sampler_x0(float x, float e, float u, float v) {
+  return MIXDQ_ADD_RN(MIXDQ_MUL_RN(u, x), MIXDQ_MUL_RN(v, e));
+}
+
+MIXDQ_HD float mixdq_sampler_update_2m(float x, float x0, float h, float A, float B, float D) {
+  return MIXDQ_ADD_RN(MIXDQ_ADD_RN(MIXDQ_MUL_RN(A, x), MIXDQ_MUL_RN(B, x0)), MIXDQ_MUL_RN(D, h));
+}
+
 /* ---- VAE decoder end (mixdq_composite_u8, csrc/vae.hip): one FP16 image value (given as its exact FP32 value) as
  * the pixel vae.to_uint8 makes of it, ((f32(v) / 2 + 0.5).clamp(0, 1) * 255).round() with round-half-even:
  * the halving is exact, then one sum, the clamp, one product, rintf -- each one FP32 operation.  -inf is 0, +inf

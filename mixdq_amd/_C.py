@@ -1491,6 +1491,81 @@ def sampler_step_masked(x, eps, inp, coef, t_table, step, timestep, z, noise0, m
     _status(code, "sampler_step_masked")
 
 
+_lib.mixdq_sampler_step_2m.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, ctypes.c_float, _i64, _i32,
+                                       _i64, _vp]
+_lib.mixdq_sampler_step_2m.restype = _i32
+_lib.mixdq_sampler_step_2m_masked.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, ctypes.c_float, _i64,
+                                              _i32, _i64, _vp, _vp, _vp, _i32, _vp, _vp]
+_lib.mixdq_sampler_step_2m_masked.restype = _i32
+
+
+def _check_step_2m(x, eps, inp, hist, coef8, t_table, step, first, timestep, extra, n, row_stride, rows_per_image):
+    """The checks the two multistep bindings share; returns (n_steps, n, row_stride)."""
+    for t_, name, dt in ((x, "x", torch.float32), (eps, "eps", torch.float16), (inp, "inp", torch.float16),
+                         (hist, "hist", torch.float32), (coef8, "coef8", torch.float32),
+                         (t_table, "t_table", torch.float32), (step, "step", torch.int32),
+                         (first, "first", torch.int32), (timestep, "timestep", torch.float32)) + extra:
+        _check(torch.is_tensor(t_) and t_.is_cuda and t_.device == x.device and t_.dtype == dt,
+               f"{name} should be a {dt} tensor on x's GPU")
+    _check(coef8.dim() == 2 and coef8.shape[1] == 8 and coef8.is_contiguous() and t_table.is_contiguous(),
+           "coef8 should be a contiguous [n_steps, 8] table")
+    n_steps = coef8.shape[0]
+    _check(t_table.numel() >= n_steps + 1, "t_table needs n_steps + 1 entries")
+    _check(step.numel() == 1 and first.numel() == 1 and timestep.numel() == 1,
+           "step, first and timestep hold one value each")
+    n = x.numel() if n is None else int(n)
+    row_stride = n if row_stride is None else int(row_stride)
+    _check(0 <= n <= x.numel(), "n exceeds the state")
+    _check(hist.numel() >= n, "hist is smaller than the state")
+    if rows_per_image in (1, 2):                      # (anything else: the library's own error)
+        need = (rows_per_image - 1) * row_stride + n
+        _check(eps.numel() >= need and inp.numel() >= need, "eps / inp are smaller than rows_per_image row blocks")
+    return n_steps, n, row_stride
+
+
+def sampler_step_2m(x, eps, inp, hist, coef8, t_table, step, first, timestep, guidance=0.0, rows_per_image=1, *,
+                    n=None, row_stride=None):
+    """One DPM-Solver++ 2M step in place (mixdq_sampler_step_2m): guidance as sampler_step, the data prediction
+    x0 = u * x + v * e, a second-order update of `x` from x0 and `hist` (the previous step's x0) when `step` > `first`
+    and the row's D2 != 0, a first-order one otherwise (hist is not read then); `hist` <- x0 on every step; the UNet's
+    next FP16 input into every row block of `inp`; then `timestep` and `step` advance as in sampler_step.
+
+    hist: fp32, `n` elements in x's stride pattern, not x itself; coef8: fp32 [n_steps, 8] (Schedule.coef of
+    'dpmpp_2m'): (u, v, A, B1, B2, D2, s_next, 0); first: int32 [1], the index of the run's first step.  Everything
+    else as sampler_step; there is no noise operand."""
+    n_steps, n, row_stride = _check_step_2m(x, eps, inp, hist, coef8, t_table, step, first, timestep, (), n, row_stride,
+                                            rows_per_image)
+    with torch.cuda.device(x.device):
+        code = _lib.mixdq_sampler_step_2m(x.data_ptr(), eps.data_ptr(), inp.data_ptr(), hist.data_ptr(),
+                                          coef8.data_ptr(), t_table.data_ptr(), n_steps, step.data_ptr(),
+                                          first.data_ptr(), timestep.data_ptr(), float(guidance), n,
+                                          int(rows_per_image), row_stride, _stream())
+    _status(code, "sampler_step_2m")
+
+
+def sampler_step_2m_masked(x, eps, inp, hist, coef8, t_table, step, first, timestep, z, noise0, mask, blend,
+                           guidance=0.0, rows_per_image=1, *, channels=4, n=None, row_stride=None):
+    """sampler_step_2m for inpainting (mixdq_sampler_step_2m_masked): the same step, then sampler_step_masked's blend
+    of the new state with the image latents at the next step's noise level.  `hist` is the unblended x0.  z, noise0,
+    mask, blend and channels as in sampler_step_masked."""
+    extra = ((z, "z", torch.float32), (noise0, "noise0", torch.float32), (mask, "mask", torch.float32),
+             (blend, "blend", torch.float32))
+    n_steps, n, row_stride = _check_step_2m(x, eps, inp, hist, coef8, t_table, step, first, timestep, extra, n,
+                                            row_stride, rows_per_image)
+    _check(tuple(blend.shape) == (n_steps, 2) and blend.is_contiguous(), "blend should be a contiguous [n_steps, 2] table")
+    channels = int(channels)
+    _check(z.numel() >= n and noise0.numel() >= n, "z / noise0 are smaller than the state")
+    if channels >= 1 and n % channels == 0:           # (anything else: the library's own error)
+        _check(mask.is_contiguous() and mask.numel() >= n // channels, "mask should be dense with n / channels entries")
+    with torch.cuda.device(x.device):
+        code = _lib.mixdq_sampler_step_2m_masked(x.data_ptr(), eps.data_ptr(), inp.data_ptr(), hist.data_ptr(),
+                                                 coef8.data_ptr(), t_table.data_ptr(), n_steps, step.data_ptr(),
+                                                 first.data_ptr(), timestep.data_ptr(), float(guidance), n,
+                                                 int(rows_per_image), row_stride, z.data_ptr(), noise0.data_ptr(),
+                                                 mask.data_ptr(), channels, blend.data_ptr(), _stream())
+    _status(code, "sampler_step_2m_masked")
+
+
 
 _lib.mixdq_image_to_nhwc8_f16.argtypes = [_vp, _i32, _i64, _i64, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _vp]
 _lib.mixdq_image_to_nhwc8_f16.restype = _i32

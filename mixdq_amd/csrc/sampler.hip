@@ -16,6 +16,11 @@
 // three more FP32 reads per element (z, n0 as 16-byte loads; the mask one value per latent pixel), x'' stored to x
 // and in = f16_rn(x'' * s_next).  The four plain instantiations are untouched by it.
 //
+// mixdq_sampler_step_2m[_masked] (DPM-Solver++ 2M) is NOT one affine map of (x, eps, noise): a second-order step also
+// reads the previous step's data prediction.  That one value per element is the only state a multistep solver adds; it
+// lives in a caller-owned FP32 buffer `hist` that a third kernel (sampler_step_2m_kernel, below the two others, which
+// it does not touch) reads and rewrites, with the index of the run's first step in a device int beside the step index.
+//
 // The step index is read by every workgroup of the step launch and advanced by the launch BEHIND it on the same
 // stream (sampler_advance_kernel, one thread): launches of one stream run in order, so no workgroup of the step
 // can read the index after it moved, without any in-launch ticket, fence or counter to re-initialise.
@@ -173,6 +178,111 @@ __global__ __launch_bounds__(256) void sampler_step_masked_kernel(
   }
 }
 
+// The multistep step (DPM-Solver++ 2M, mixdq_sampler_step_2m[_masked]): the data prediction x0 = u*x + v*e, then a
+// first- or second-order update of x from x0 and the PREVIOUS step's x0, which lives in `hist` (FP32, x's layout) and is
+// replaced by this step's on every launch.  (u, v, A, B1, B2, D2, s_next, 0) = coef8[*step].  Which order a step takes
+// depends on the table and on two device scalars only -- the first executed step of a run (*step == *first) and a row
+// with D2 == 0 are first-order -- so the choice is uniform over the launch and `hist` is not read at all on a
+// first-order step: it may hold anything there.  One more FP32 read (second-order steps) and write per element than the
+// plain step; these kinds add no noise.  MASKED: 0 none, 1 the blend with channels == 4, 2 with any channel count;
+// the blend touches x and the UNet input, never `hist`.
+template <int ROWS>
+__device__ __forceinline__ float step_2m_one(float x, float eu, float ec, float h, float g, float u, float v, float A,
+                                             float B, float D, bool second, float* x0_out) {
+  const float e = ROWS == 2 ? mixdq_sampler_guided_eps(eu, ec, g) : eu;
+  const float x0 = mixdq_sampler_x0(x, e, u, v);
+  *x0_out = x0;
+  return second ? mixdq_sampler_update_2m(x, x0, h, A, B, D) : mixdq_sampler_update(x, x0, A, B);
+}
+
+template <int ROWS, int MASKED>
+__global__ __launch_bounds__(256) void sampler_step_2m_kernel(
+    float* __restrict__ x, const __half* __restrict__ eps, __half* __restrict__ in, float* __restrict__ hist,
+    const float* __restrict__ coef8, const int* __restrict__ step_p, const int* __restrict__ first_p, int n_steps, float g,
+    int64_t n, int64_t row_stride, const float* __restrict__ z, const float* __restrict__ noise0,
+    const float* __restrict__ mask, int channels, const float* __restrict__ blend) {
+  const int step = *step_p;
+  if (step < 0 || step >= n_steps) return;        // replayed past the table: nothing is read or written
+  const float4 k0 = *reinterpret_cast<const float4*>(coef8 + 8 * (int64_t)step);
+  const float4 k1 = *reinterpret_cast<const float4*>(coef8 + 8 * (int64_t)step + 4);
+  const float u = k0.x, v = k0.y, A = k0.z, D = k1.y, s_next = k1.z;
+  const bool second = step > *first_p && D != 0.0f;
+  const float B = second ? k1.x : k0.w;
+  float2 pq = make_float2(1.0f, 0.0f);
+  if (MASKED) pq = *reinterpret_cast<const float2*>(blend + 2 * (int64_t)step);
+  const int64_t nvec = n >> 3;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += stride) {
+    const int64_t o = i << 3;
+    const float4 x0 = *reinterpret_cast<const float4*>(x + o), x1 = *reinterpret_cast<const float4*>(x + o + 4);
+    const Half8 eu = *reinterpret_cast<const Half8*>(eps + o);
+    Half8 ec = eu;
+    if (ROWS == 2) ec = *reinterpret_cast<const Half8*>(eps + row_stride + o);
+    float4 h0 = x0, h1 = x1;
+    if (second) {
+      h0 = *reinterpret_cast<const float4*>(hist + o);
+      h1 = *reinterpret_cast<const float4*>(hist + o + 4);
+    }
+    float4 z0 = x0, z1 = x1, i0 = x0, i1 = x1;
+    float ms[8];
+    if (MASKED) {
+      z0 = *reinterpret_cast<const float4*>(z + o);
+      z1 = *reinterpret_cast<const float4*>(z + o + 4);
+      i0 = *reinterpret_cast<const float4*>(noise0 + o);
+      i1 = *reinterpret_cast<const float4*>(noise0 + o + 4);
+      if (MASKED == 1) {
+        const float m0 = mask[2 * i], m1 = mask[2 * i + 1];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) ms[j] = j < 4 ? m0 : m1;
+      } else {
+        int64_t q = o / channels;                  // o + j < n and n % channels == 0: q stays below n / channels
+        int r = (int)(o - q * channels);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          ms[j] = mask[q];
+          if (++r == channels) { r = 0; ++q; }
+        }
+      }
+    }
+    const float xs[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
+    const float hs[8] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
+    const float zs[8] = {z0.x, z0.y, z0.z, z0.w, z1.x, z1.y, z1.z, z1.w};
+    const float is[8] = {i0.x, i0.y, i0.z, i0.w, i1.x, i1.y, i1.z, i1.w};
+    float y[8], p0[8];
+    Half8 out;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      y[j] = step_2m_one<ROWS>(xs[j], half_at(eu, j), half_at(ec, j), hs[j], g, u, v, A, B, D, second, &p0[j]);
+      if (MASKED) y[j] = mixdq_sampler_blend(y[j], zs[j], is[j], ms[j], pq.x, pq.y);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      out.w[j] = half_bits(mixdq_sampler_scaled_input(y[2 * j], s_next)) |
+                 (half_bits(mixdq_sampler_scaled_input(y[2 * j + 1], s_next)) << 16);
+    *reinterpret_cast<float4*>(hist + o) = make_float4(p0[0], p0[1], p0[2], p0[3]);
+    *reinterpret_cast<float4*>(hist + o + 4) = make_float4(p0[4], p0[5], p0[6], p0[7]);
+    *reinterpret_cast<float4*>(x + o) = make_float4(y[0], y[1], y[2], y[3]);
+    *reinterpret_cast<float4*>(x + o + 4) = make_float4(y[4], y[5], y[6], y[7]);
+    *reinterpret_cast<Half8*>(in + o) = out;
+    if (ROWS == 2) *reinterpret_cast<Half8*>(in + row_stride + o) = out;
+  }
+  // tail (n % 8 elements), by the first threads of block 0
+  const int64_t t = (nvec << 3) + threadIdx.x;
+  if (blockIdx.x == 0 && t < n) {
+    const float eu = __half2float(eps[t]);
+    const float ec = ROWS == 2 ? __half2float(eps[row_stride + t]) : eu;
+    const float xt = x[t];
+    float p0;
+    float y = step_2m_one<ROWS>(xt, eu, ec, second ? hist[t] : xt, g, u, v, A, B, D, second, &p0);
+    if (MASKED) y = mixdq_sampler_blend(y, z[t], noise0[t], mask[t / channels], pq.x, pq.y);
+    const __half h = f32_to_f16_rn(mixdq_sampler_scaled_input(y, s_next));
+    hist[t] = p0;
+    x[t] = y;
+    in[t] = h;
+    if (ROWS == 2) in[row_stride + t] = h;
+  }
+}
+
 // Behind the step on the same stream: the timestep of the NEXT UNet forward, and the index moves on.
 __global__ void sampler_advance_kernel(const float* __restrict__ t_table, int n_steps, int* step_p, float* timestep) {
   const int step = *step_p;
@@ -263,6 +373,76 @@ extern "C" int mixdq_sampler_step_masked(float* x, const void* eps_f16, void* in
     }
 #undef M_LAUNCH_C
 #undef M_LAUNCH
+    if (hipGetLastError() != hipSuccess) return MIXDQ_ERR_LAUNCH;
+  }
+  sampler_advance_kernel<<<1, 1, 0, stream>>>(t_table, n_steps, step, timestep);
+  return launch_status();
+}
+
+namespace mixdq {
+namespace {
+
+// What the two multistep entry points check beyond check_step_args (which sees coef8 as its table).
+int check_2m_args(const float* x, const float* hist, const float* coef8, const int* first, int64_t n) {
+  if (!hist || !coef8 || !first) return MIXDQ_ERR_INVALID_ARG;
+  if (hist < x + n && x < hist + n) return MIXDQ_ERR_INVALID_ARG;                // the history is a buffer of its own
+  if ((uintptr_t)hist % 16 || (uintptr_t)coef8 % 16 || (uintptr_t)first % 4) return MIXDQ_ERR_ALIGNMENT;
+  return MIXDQ_OK;
+}
+
+}  // namespace
+}  // namespace mixdq
+
+extern "C" int mixdq_sampler_step_2m(float* x, const void* eps_f16, void* in_f16, float* hist, const float* coef8,
+                                     const float* t_table, int n_steps, int* step, const int* first, float* timestep,
+                                     float guidance, int64_t n, int rows_per_image, int64_t row_stride,
+                                     mixdq_stream_t stream_) {
+  int bad = check_step_args(x, eps_f16, in_f16, nullptr, 0, coef8, t_table, n_steps, step, timestep, n, rows_per_image,
+                            row_stride);
+  if (bad == MIXDQ_OK) bad = check_2m_args(x, hist, coef8, first, n);
+  if (bad != MIXDQ_OK) return bad;
+  hipStream_t stream = (hipStream_t)stream_;
+  if (n > 0) {
+    const int blocks = step_blocks(n);
+    const __half* eps = (const __half*)eps_f16;
+    __half* in = (__half*)in_f16;
+#define S2_LAUNCH(R)                                                                                                  \
+  sampler_step_2m_kernel<R, 0><<<blocks, 256, 0, stream>>>(x, eps, in, hist, coef8, step, first, n_steps, guidance, n, \
+                                                           row_stride, nullptr, nullptr, nullptr, 1, nullptr)
+    if (rows_per_image == 2) S2_LAUNCH(2); else S2_LAUNCH(1);
+#undef S2_LAUNCH
+    if (hipGetLastError() != hipSuccess) return MIXDQ_ERR_LAUNCH;
+  }
+  sampler_advance_kernel<<<1, 1, 0, stream>>>(t_table, n_steps, step, timestep);
+  return launch_status();
+}
+
+extern "C" int mixdq_sampler_step_2m_masked(float* x, const void* eps_f16, void* in_f16, float* hist, const float* coef8,
+                                            const float* t_table, int n_steps, int* step, const int* first,
+                                            float* timestep, float guidance, int64_t n, int rows_per_image,
+                                            int64_t row_stride, const float* z, const float* noise0, const float* mask,
+                                            int channels, const float* blend, mixdq_stream_t stream_) {
+  int bad = check_step_args(x, eps_f16, in_f16, nullptr, 0, coef8, t_table, n_steps, step, timestep, n, rows_per_image,
+                            row_stride);
+  if (bad == MIXDQ_OK) bad = check_2m_args(x, hist, coef8, first, n);
+  if (bad != MIXDQ_OK) return bad;
+  if (!z || !noise0 || !mask || !blend || channels < 1 || n % channels) return MIXDQ_ERR_INVALID_ARG;
+  if ((uintptr_t)z % 16 || (uintptr_t)noise0 % 16 || (uintptr_t)mask % 4 || (uintptr_t)blend % 8)
+    return MIXDQ_ERR_ALIGNMENT;
+  hipStream_t stream = (hipStream_t)stream_;
+  if (n > 0) {
+    const int blocks = step_blocks(n);
+    const __half* eps = (const __half*)eps_f16;
+    __half* in = (__half*)in_f16;
+#define M2_LAUNCH(R, M)                                                                                               \
+  sampler_step_2m_kernel<R, M><<<blocks, 256, 0, stream>>>(x, eps, in, hist, coef8, step, first, n_steps, guidance, n, \
+                                                           row_stride, z, noise0, mask, channels, blend)
+    if (rows_per_image == 2) {
+      if (channels == 4) M2_LAUNCH(2, 1); else M2_LAUNCH(2, 2);
+    } else {
+      if (channels == 4) M2_LAUNCH(1, 1); else M2_LAUNCH(1, 2);
+    }
+#undef M2_LAUNCH
     if (hipGetLastError() != hipSuccess) return MIXDQ_ERR_LAUNCH;
   }
   sampler_advance_kernel<<<1, 1, 0, stream>>>(t_table, n_steps, step, timestep);

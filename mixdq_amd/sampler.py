@@ -24,13 +24,24 @@ noised to the NEXT step's level, x = (1 - m) * (p * z + q * noise) + m * x', (p,
 (mixdq_sampler_step_masked).  `sample(..., init_latents=z, mask=m)` replays a second captured graph -- the UNet forward
 plus that step -- on the same static buffers; `Sampler.inpaint` runs encode, mixdq_mask_to_latent, that loop, decode
 and, on request, the uint8 composite with the original image on one stream.
+
+'ddim' is one more such table.  'dpmpp_2m' (DPM-Solver++ 2M, diffusers' DPMSolverMultistepScheduler, optionally with
+Karras sigmas) is not an affine map of (x, e, n): from its second step on it also reads the previous step's data
+prediction x0 = u * x + v * e.  Its table is `multistep_table`, [n_steps][8] = (u, v, A, B1, B2, D2, s_next, 0); the
+Sampler keeps that one extra tensor (`_hist`) and the index of the run's first step (`_first`) on the device beside the
+step index, and the captured graphs record mixdq_sampler_step_2m[_masked] instead.  The step at `_first` and the last
+one are first-order, so a run never reads what an earlier run left in `_hist`.
 """
 import numpy as np
 
-KINDS = ("euler_ancestral", "euler", "lcm")
+KINDS = ("euler_ancestral", "euler", "lcm")          # the kinds of the first device-side loop (sigma-space or LCM start)
+VP_KINDS = ("ddim", "dpmpp_2m")                      # state kept in VP space: init_scale = input_scale0 = s_next = 1
+ALL_KINDS = KINDS + VP_KINDS
 TRAIN_STEPS = 1000
 LCM_ORIGINAL_STEPS = 50
-_DEFAULT_SPACING = {"euler_ancestral": "trailing", "euler": "leading", "lcm": "lcm"}
+KARRAS_RHO = 7.0
+_DEFAULT_SPACING = {"euler_ancestral": "trailing", "euler": "leading", "lcm": "lcm", "ddim": "leading",
+                    "dpmpp_2m": "leading"}
 
 
 def alphas_cumprod() -> np.ndarray:
@@ -39,12 +50,35 @@ def alphas_cumprod() -> np.ndarray:
     return np.cumprod(1.0 - betas)
 
 
-def timesteps(kind: str, n_steps: int, spacing=None) -> np.ndarray:
-    """The integer training timesteps a run of `n_steps` visits, first (noisiest) first."""
-    if kind not in KINDS:
-        raise ValueError(f"kind must be one of {KINDS}, not {kind!r}")
+def train_sigmas() -> np.ndarray:
+    """sqrt((1 - ac) / ac) at the 1000 training timesteps, rising."""
+    ac = alphas_cumprod()
+    return np.sqrt((1.0 - ac) / ac)
+
+
+def karras_sigmas(n_steps: int) -> np.ndarray:
+    """Karras et al.'s rho = 7 ramp of `n_steps` sigmas between the training schedule's largest and smallest one
+    (diffusers' use_karras_sigmas), falling, without the final 0."""
+    sig = train_sigmas()
+    lo, hi = sig[0] ** (1.0 / KARRAS_RHO), sig[-1] ** (1.0 / KARRAS_RHO)
+    return (hi + np.linspace(0.0, 1.0, n_steps) * (lo - hi)) ** KARRAS_RHO
+
+
+def timesteps(kind: str, n_steps: int, spacing=None, karras=False) -> np.ndarray:
+    """The integer training timesteps a run of `n_steps` visits, first (noisiest) first.  karras ('dpmpp_2m' only):
+    the timesteps at which the training schedule has the Karras ladder's sigmas, round(interp(log sigma, log
+    sigma_train, 0..999)) -- the ladder takes the place of a spacing."""
+    if kind not in ALL_KINDS:
+        raise ValueError(f"kind must be one of {ALL_KINDS}, not {kind!r}")
     if not 1 <= n_steps <= TRAIN_STEPS:
         raise ValueError("n_steps must be in [1, 1000]")
+    if karras:
+        if kind != "dpmpp_2m":
+            raise ValueError("karras sigmas are for 'dpmpp_2m' only")
+        if spacing is not None:
+            raise ValueError("karras sigmas take the place of a spacing: leave spacing None")
+        t = np.interp(np.log(karras_sigmas(n_steps)), np.log(train_sigmas()), np.arange(TRAIN_STEPS, dtype=np.float64))
+        return np.round(t).astype(np.int64)
     spacing = spacing or _DEFAULT_SPACING[kind]
     if kind == "lcm":
         if spacing != "lcm":
@@ -76,20 +110,74 @@ def img2img_start(n_steps: int, strength: float) -> int:
     return t0
 
 
+def multistep_table(sigmas) -> np.ndarray:
+    """The float64 [n, 8] table of DPM-Solver++ 2M (epsilon prediction, midpoint) for a falling ladder of n + 1 sigmas
+    that ends in 0: row i = (u, v, A, B1, B2, D2, s_next, 0).  With alpha = 1 / sqrt(sigma^2 + 1), sigma_hat = sigma *
+    alpha (the VP state is x = alpha * x0 + sigma_hat * eps), lambda = -log sigma, h = lambda_{i+1} - lambda_i,
+    E = -alpha_{i+1} * expm1(-h) and r = (lambda_i - lambda_{i-1}) / h:
+        x0 = u * x + v * eps                     u = 1 / alpha_i, v = -sigma_i
+        first order:   x' = A * x + B1 * x0      A = sigma_hat_{i+1} / sigma_hat_i, B1 = E
+        second order:  x' = A * x + B2 * x0 + D2 * x0_prev      B2 = E * (1 + 1 / (2 r)), D2 = -E / (2 r)
+    Row 0 has no predecessor and the last row steps to sigma 0, where lambda is infinite: both are first-order (B2 =
+    B1, D2 = 0), the last one (A, B1) = (0, 1) -- x' = x0.  s_next is 1: a VP state is the UNet's input as it is."""
+    sig = np.asarray(sigmas, dtype=np.float64)
+    n = len(sig) - 1
+    if n < 1 or sig[-1] != 0.0 or not (sig[:-1] > 0).all() or not (np.diff(sig) < 0).all():
+        raise ValueError("sigmas must fall strictly from positive values to a final 0")
+    alpha = 1.0 / np.sqrt(sig ** 2 + 1.0)
+    hat = sig * alpha
+    lam = -np.log(sig[:-1])
+    tab = np.zeros((n, 8), dtype=np.float64)
+    for i in range(n):
+        tab[i, 0], tab[i, 1], tab[i, 6] = 1.0 / alpha[i], -sig[i], 1.0
+        if i == n - 1:
+            tab[i, 2:6] = (0.0, 1.0, 1.0, 0.0)
+            continue
+        h = lam[i + 1] - lam[i]
+        E = -alpha[i + 1] * np.expm1(-h)
+        tab[i, 2:6] = (hat[i + 1] / hat[i], E, E, 0.0)
+        if i > 0:
+            r = (lam[i] - lam[i - 1]) / h
+            tab[i, 4:6] = (E * (1.0 + 1.0 / (2.0 * r)), -E / (2.0 * r))
+    return tab
+
+
 class Schedule:
     """What one (kind, n_steps, spacing) needs: `timesteps` int64 [n]; `sigmas` float64 [n + 1] (euler kinds; ends in
     0); `coef` FP32 [n, 4] = (a, b, c, s_next), computed in float64; `t_table` FP32 [n + 1] (the
     timesteps, then one unused entry the last step's advance reads); `init_scale`: initial state = noise *
     init_scale; `input_scale0`: first UNet input = f16(state * input_scale0); `blend` FP32 [n, 2] = (p, q), computed in
     float64: what the masked step noises the kept region with after step i -- row i < n - 1 the schedulers' add_noise
-    at timesteps[i + 1] (`start(i + 1)[:2]`), the last row (1, 0): the kept region ends as the clean image latents."""
+    at timesteps[i + 1] (`start(i + 1)[:2]`), the last row (1, 0): the kept region ends as the clean image latents.
 
-    def __init__(self, kind, n_steps, spacing=None):
+    'ddim' (diffusers' DDIMScheduler as Stable Diffusion configures it: eta 0, set_alpha_to_one False) is one more
+    [n, 4] table.  'dpmpp_2m' (`karras`: the rho = 7 sigma ladder in place of a spacing) is the one kind of `order` 2:
+    `coef` is FP32 [n, 8], `multistep_table(sigmas)` rounded, for mixdq_sampler_step_2m; `sigmas` float64 [n + 1]."""
+
+    def __init__(self, kind, n_steps, spacing=None, karras=False):
         self.kind, self.n_steps = kind, int(n_steps)
-        self.timesteps = ts = timesteps(kind, n_steps, spacing)
+        self.timesteps = ts = timesteps(kind, n_steps, spacing, karras)
+        self.order = 2 if kind == "dpmpp_2m" else 1
         ac = alphas_cumprod()
         coef = np.zeros((n_steps, 4), dtype=np.float64)
-        if kind == "lcm":
+        if kind == "dpmpp_2m":
+            self.sigmas = np.concatenate([karras_sigmas(n_steps) if karras else np.sqrt((1.0 - ac[ts]) / ac[ts]), [0.0]])
+            coef = multistep_table(self.sigmas)
+            self.init_scale, self.input_scale0 = 1.0, 1.0
+        elif kind == "ddim":
+            self.sigmas = None
+            spacing = spacing or _DEFAULT_SPACING[kind]
+            for i, t in enumerate(ts):
+                if spacing == "leading":
+                    prev = t - TRAIN_STEPS // n_steps
+                else:
+                    prev = ts[i + 1] if i + 1 < n_steps else -1
+                ac_prev = ac[prev] if prev >= 0 else ac[0]          # set_alpha_to_one False: the final alpha is ac[0]
+                sa, s1a, sp = np.sqrt(ac[t]), np.sqrt(1.0 - ac[t]), np.sqrt(ac_prev)
+                # x0 = (x - s1a e) / sa;  x' = sp x0 + sqrt(1 - ac_prev) e
+                coef[i] = (sp / sa, np.sqrt(1.0 - ac_prev) - sp * s1a / sa, 0.0, 1.0)
+            self.init_scale, self.input_scale0 = 1.0, 1.0
+        elif kind == "lcm":
             self.sigmas = None
             for i, t in enumerate(ts):
                 last = i == n_steps - 1
@@ -116,30 +204,36 @@ class Schedule:
             self.input_scale0 = float(1.0 / np.sqrt(sig[0] ** 2 + 1.0))
         self.coef = coef.astype(np.float32)
         self.t_table = np.concatenate([ts.astype(np.float64), [0.0]]).astype(np.float32)
-        self.uses_noise = bool((self.coef[:, 2] != 0).any())
+        self.uses_noise = self.order == 1 and bool((self.coef[:, 2] != 0).any())
         self.blend = np.array([self.start(i + 1)[:2] for i in range(self.n_steps - 1)] + [(1.0, 0.0)],
                               dtype=np.float64).astype(np.float32)
 
     def start(self, t0: int):
         """(a0, c0, s0) in float64 for a run that starts at step `t0` from latents z: state = a0 * z + c0 * noise (the
         schedulers' add_noise at timesteps[t0]), first UNet input = f16(state * s0) (their scale_model_input).
-        Euler kinds: (1, sigmas[t0], 1 / sqrt(sigmas[t0]^2 + 1)); lcm: (sqrt(ac), sqrt(1 - ac), 1) at timesteps[t0]."""
+        Euler kinds: (1, sigmas[t0], 1 / sqrt(sigmas[t0]^2 + 1)); lcm and ddim: (sqrt(ac), sqrt(1 - ac), 1) at
+        timesteps[t0]; dpmpp_2m: the same two in terms of its own sigma, (alpha, sigma * alpha, 1) at sigmas[t0]."""
         if not 0 <= t0 < self.n_steps:
             raise ValueError(f"t0 must be in [0, {self.n_steps}), not {t0}")
-        if self.kind == "lcm":
+        if self.kind in ("lcm", "ddim"):
             ac = alphas_cumprod()[self.timesteps[t0]]
             return float(np.sqrt(ac)), float(np.sqrt(1.0 - ac)), 1.0
         sig = self.sigmas[t0]
+        if self.kind == "dpmpp_2m":
+            alpha = 1.0 / np.sqrt(sig ** 2 + 1.0)
+            return float(alpha), float(sig * alpha), 1.0
         return 1.0, float(sig), float(1.0 / np.sqrt(sig ** 2 + 1.0))
 
 
-def schedule(kind, n_steps, spacing=None) -> Schedule:
-    return Schedule(kind, n_steps, spacing)
+def schedule(kind, n_steps, spacing=None, karras=False) -> Schedule:
+    return Schedule(kind, n_steps, spacing, karras)
 
 
 class Sampler:
     """`n_steps` of `kind` ('euler_ancestral': SDXL-Turbo, trailing spacing; 'euler': SDXL base, leading spacing with
-    offset 1, `spacing='trailing'` selectable; 'lcm': SD 1.5 LCM-LoRA) around `unet`, a mixdq_amd UNet on the GPU.
+    offset 1, `spacing='trailing'` selectable; 'lcm': SD 1.5 LCM-LoRA; 'ddim' and 'dpmpp_2m': the non-distilled
+    checkpoints, leading spacing with offset 1, 'trailing' selectable, `karras=True`: 'dpmpp_2m' on the Karras sigma
+    ladder) around `unet`, a mixdq_amd UNet on the GPU.
 
     guidance_scale > 1: classifier-free guidance -- the UNet runs at 2B rows, `encoder_hidden_states` (and the
     tensors of `added_cond_kwargs`) carry the B unconditional rows first, then the B conditional ones, as diffusers'
@@ -153,9 +247,9 @@ class Sampler:
     replays, and they never run concurrently); the plain graph is not touched, and one Sampler serves text-to-image,
     image-to-image and masked calls in any order."""
 
-    def __init__(self, unet, kind, n_steps, guidance_scale=0.0, spacing=None):
+    def __init__(self, unet, kind, n_steps, guidance_scale=0.0, spacing=None, karras=False):
         self.unet = unet
-        self.schedule = Schedule(kind, n_steps, spacing)
+        self.schedule = Schedule(kind, n_steps, spacing, karras)
         self.kind, self.n_steps = kind, int(n_steps)
         self.guidance_scale = float(guidance_scale)
         self.rows_per_image = 2 if self.guidance_scale > 1.0 else 1
@@ -182,6 +276,9 @@ class Sampler:
         self._t_table = torch.from_numpy(sch.t_table).to(dev)
         self._t = torch.zeros((), dtype=torch.float32, device=dev)
         self._step = torch.zeros(1, dtype=torch.int32, device=dev)
+        if sch.order == 2:            # the multistep state: the previous step's x0, and where this run started
+            self._hist = nhwc(B, dtype=torch.float32)
+            self._first = torch.zeros(1, dtype=torch.int32, device=dev)
         self._init_scale = torch.tensor(sch.init_scale, dtype=torch.float32, device=dev)
         self._input_scale0 = torch.tensor(sch.input_scale0, dtype=torch.float32, device=dev)
         self._ehs, self._added = _clone_args((encoder_hidden_states, added_cond_kwargs))
@@ -208,7 +305,14 @@ class Sampler:
                     or any(a != b for a, b, d in zip(eps.stride(), self._in.stride(), eps.shape) if d > 1)):
                 raise RuntimeError("Sampler: the UNet's output is not an FP16 tensor of its input's shape in channels-"
                                    f"last storage (shape {tuple(eps.shape)}, strides {eps.stride()}, {eps.dtype})")
-            if masked:
+            if self.schedule.order == 2 and masked:
+                _C.sampler_step_2m_masked(self._x, eps, self._in, self._hist, self._coef, self._t_table, self._step,
+                                          self._first, self._t, self._z, self._noise0, self._mask, self._blend,
+                                          self.guidance_scale, self.rows_per_image, channels=C, n=n)
+            elif self.schedule.order == 2:
+                _C.sampler_step_2m(self._x, eps, self._in, self._hist, self._coef, self._t_table, self._step,
+                                   self._first, self._t, self.guidance_scale, self.rows_per_image, n=n)
+            elif masked:
                 _C.sampler_step_masked(self._x, eps, self._in, self._coef, self._t_table, self._step, self._t, self._z,
                                        self._noise0, self._mask, self._blend, self.guidance_scale, self.rows_per_image,
                                        self._noise, channels=C, n=n)
@@ -249,6 +353,8 @@ class Sampler:
         if self._noise is not None and step_noise is not None:
             self._noise.copy_(step_noise)
         self._step.zero_()
+        if self.schedule.order == 2:
+            self._first.zero_()
         self._t.copy_(self._t_table[0])
 
     def _reset_at(self, t0, init_latents, noise, step_noise):
@@ -268,6 +374,8 @@ class Sampler:
         if self._noise is not None and step_noise is not None:
             self._noise.copy_(step_noise)
         self._step.fill_(t0)
+        if self.schedule.order == 2:  # the run's first step is first-order: the history of an earlier run is not read
+            self._first.fill_(t0)
         self._t.copy_(self._t_table[t0])
 
     # ---- the loop -------------------------------------------------------------------------------------------
