@@ -688,6 +688,48 @@ int mixdq_sampler_step_2m_masked(float* x, const void* eps_f16, void* in_f16, fl
                                  const float* noise0, const float* mask, int channels, const float* blend,
                                  mixdq_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Gaussian noise made on the device: Philox4x32-10, a counter-based generator, and Box-Muller on 24-bit uniforms
+ * (include/mixdq_math.h: mixdq_philox4x32_10, mixdq_rng_*; integers and FP32 with every rounding explicit, so the
+ * values can be restated bit for bit on a host).  No reference counterpart (the reference takes torch's generator
+ * through diffusers).  Image b of a batch has a 64-bit seed seeds[b] (device memory, 8-byte aligned, read as unsigned);
+ * element e of that image, counted in storage (NHWC) order, is output lane e & 3 of the call with
+ *   key (lo32(seed), hi32(seed)),  counter (lo32(e >> 2), hi32(e >> 2), step, stream)
+ * stream: what the noise is for (below); step: the absolute index of the sampler step that consumes it (stream 1), 0
+ * for the others.  An image's noise depends on its seed and size only -- not on its batch position, the batch size,
+ * the launch geometry or where a run starts in the schedule.  |z| <= sqrt(48 ln 2) ~ 5.77. */
+#define MIXDQ_RNG_STREAM_START 0   /* start noise; the img2img / inpainting noise */
+#define MIXDQ_RNG_STREAM_STEP 1    /* what a stochastic sampler step adds */
+#define MIXDQ_RNG_STREAM_VAE 2     /* the VAE posterior's noise */
+
+/* out[b * n_image + e] for b < B, e < n_image, dense.  Any n_image >= 1; out 16-byte aligned when n_image % 4 == 0
+ * (16-byte stores), 4-byte otherwise.  The seeds are read by the kernel: a captured graph serves every seed.
+ * Errors: null out / seeds, B < 0, n_image < 1: MIXDQ_ERR_INVALID_ARG; out or seeds misaligned: MIXDQ_ERR_ALIGNMENT.
+ * B == 0 writes nothing. */
+int mixdq_randn_f32(float* out, int B, int64_t n_image, const uint64_t* seeds_device, uint32_t stream, uint32_t step,
+                    mixdq_stream_t hip_stream);
+
+/* Introspection (tests): the map from raw words to normals alone -- z[4 q .. 4 q + 3] = mixdq_rng_normals4(r[4 q ..
+ * 4 q + 3]) for q < n_quads; r and z 16-byte aligned device memory. */
+int mixdq_rng_normals_from_bits(const uint32_t* r, float* z, int64_t n_quads, mixdq_stream_t stream);
+
+/* mixdq_sampler_step / mixdq_sampler_step_masked with the noise of stochastic steps computed in registers instead of
+ * read from a buffer: n[i] = the normal of (seeds[i / n_image], element i % n_image, step *step, stream
+ * MIXDQ_RNG_STREAM_STEP), the values mixdq_randn_f32(.., MIXDQ_RNG_STREAM_STEP, *step) writes -- then exactly the
+ * sibling's arithmetic with that n.  seeds (n / n_image entries) and n_image take the place of noise and
+ * noise_stride; everything else is the sibling's, in its order.  n_image % 8 == 0: an 8-element pass lies inside one
+ * image and takes two Philox calls; other n_image: one call per element.
+ * Errors: the sibling's, then null seeds, n_image < 1, n % n_image != 0: MIXDQ_ERR_INVALID_ARG; seeds not 8-byte
+ * aligned: MIXDQ_ERR_ALIGNMENT. */
+int mixdq_sampler_step_rng(float* x, const void* eps_f16, void* in_f16, const uint64_t* seeds, int64_t n_image,
+                           const float* coef, const float* t_table, int n_steps, int* step, float* timestep,
+                           float guidance, int64_t n, int rows_per_image, int64_t row_stride, mixdq_stream_t stream);
+int mixdq_sampler_step_masked_rng(float* x, const void* eps_f16, void* in_f16, const uint64_t* seeds, int64_t n_image,
+                                  const float* coef, const float* t_table, int n_steps, int* step, float* timestep,
+                                  float guidance, int64_t n, int rows_per_image, int64_t row_stride, const float* z,
+                                  const float* noise0, const float* mask, int channels, const float* blend,
+                                  mixdq_stream_t stream);
+
 /* Which kernel instantiation mixdq_qlinear_w8a8 / mixdq_qconv2d_w8a8 will launch for a problem of
  * M rows x N output channels (k_align = K for Linear, C for Conv2d; k_total = K or R*S*C): the block tile BM x BN x BK
  * and LDS stage count of `igemm_kernel<BM,BN,BK,STAGES,CONV>`, or zeros for the small-alignment

@@ -186,4 +186,129 @@ MIXDQ_HD float mixdq_pixel_to_unit(uint32_t u) {
   return MIXDQ_SUB_RN(MIXDQ_MUL_RN((float)u, mixdq_bits_to_float(0x3C008081u)), 1.0f);
 }
 
+/* ---- Gaussian noise (mixdq_randn_f32, mixdq_sampler_step[_masked]_rng, csrc/sampler.hip), same rule: integers, and
+ * FP32 with every rounding explicit.  A counter-based generator: nothing is kept between calls, any element can be
+ * computed alone, and the value of an element depends on (seed, element, step, stream) only.
+ *
+ * Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11; the Random123 constants):
+ * ten rounds of  (c0, c1, c2, c3) <- (hi(M1*c2) ^ c1 ^ k0, lo(M1*c2), hi(M0*c0) ^ c3 ^ k1, lo(M0*c0)),  the key
+ * bumped by (W0, W1) between rounds. */
+#define MIXDQ_PHILOX_M0 0xD2511F53u
+#define MIXDQ_PHILOX_M1 0xCD9E8D57u
+#define MIXDQ_PHILOX_W0 0x9E3779B9u
+#define MIXDQ_PHILOX_W1 0xBB67AE85u
+
+MIXDQ_HD void mixdq_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {
+  uint32_t c0 = ctr[0], c1 = ctr[1], c2 = ctr[2], c3 = ctr[3], k0 = key[0], k1 = key[1];
+  for (int r = 0; r < 10; ++r) {
+    const uint64_t p0 = (uint64_t)MIXDQ_PHILOX_M0 * c0, p1 = (uint64_t)MIXDQ_PHILOX_M1 * c2;
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+    c0 = n0; c1 = (uint32_t)p1; c2 = n2; c3 = (uint32_t)p0;
+    k0 += MIXDQ_PHILOX_W0; k1 += MIXDQ_PHILOX_W1;
+  }
+  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+/* The correctly rounded square root: the compiler's own under -fno-fast-math (on the device clang expands it to the
+ * correctly rounded sequence; HIP's __fsqrt_rn is, without OCML_BASIC_ROUNDED_OPERATIONS, the 1-ulp native one). */
+#define MIXDQ_SQRT_RN(a) __builtin_sqrtf(a)
+
+/* log(k * 2^-24) for k = 1 .. 2^24, max error 0.851 ulp over all 2^24 arguments (measured against float64; 0 at
+ * k = 2^24 exactly, never positive).  k is exact as a float; its exponent is split off in integers so that the
+ * mantissa m lies in [2/3, 4/3), then log1p(m - 1) by a degree-11 polynomial in two interleaved chains and
+ * e * ln 2 added with one fma.  Minimax coefficients as published by N. Juffa for single-precision logf. */
+MIXDQ_HD float mixdq_rng_log_u24(uint32_t k) {
+  const float x = (float)k;
+  uint32_t bits;
+  memcpy(&bits, &x, 4);
+  const uint32_t e = (bits - 0x3F2AAAABu) & 0xFF800000u;
+  float m = mixdq_bits_to_float(bits - e);
+  const float i = (float)(((int32_t)e >> 23) - 24);
+  m = m - 1.0f;
+  const float s = m * m;
+  float r = -0.130310059f, t = 0.140869141f;
+  r = __builtin_fmaf(r, s, -0.121483512f);
+  t = __builtin_fmaf(t, s, 0.139814854f);
+  r = __builtin_fmaf(r, s, -0.166846126f);
+  t = __builtin_fmaf(t, s, 0.200120345f);
+  r = __builtin_fmaf(r, s, -0.249996200f);
+  r = __builtin_fmaf(t, m, r);
+  r = __builtin_fmaf(r, m, 0.333331972f);
+  r = __builtin_fmaf(r, m, -0.5f);
+  r = __builtin_fmaf(r, s, m);
+  return __builtin_fmaf(i, 0.693147182f, r);
+}
+
+/* sin and cos of 2 pi j 2^-24 for j = 0 .. 2^24 - 1, each max error 1.015 ulp over all 2^24 arguments (measured against
+ * float64; exact zeros where the functions have them).  The reduction is in integers and exact: the top three bits are
+ * the octant, the low 21 (in odd octants their complement to 2^21) the place inside it, x = r * 2^-21 in [0, 1], angle
+ * x * pi/4.  sin(x pi/4) = x * (pi/4 + y * S(y)) and cos(x pi/4) = 1 + y * C(y) with y = x * x, S and C of degree 2
+ * and 3 (Chebyshev-node fits, 3.4e-9 and 2.7e-10 relative before rounding); pi/4 enters as an FP32 high part and a
+ * correction so that the leading term is rounded once. */
+MIXDQ_HD void mixdq_rng_sincos_u24(uint32_t j, float* sn, float* cs) {
+  const uint32_t octant = j >> 21;
+  uint32_t r = j & 0x1FFFFFu;
+  if (octant & 1u) r = 0x200000u - r;
+  const float x = (float)r * 4.76837158203125e-07f;            /* 2^-21: exact */
+  const float y = x * x;
+  float q = __builtin_fmaf(-3.595429006963968e-05f, y, 0.0024900068528950214f);
+  q = __builtin_fmaf(q, y, -0.08074543625116348f);
+  const float w = __builtin_fmaf(q, y, -2.4276526e-08f);
+  const float xw = x * w;
+  const float s = __builtin_fmaf(x, mixdq_bits_to_float(0x3F490FDBu), xw);
+  float p = __builtin_fmaf(3.541952764862799e-06f, y, -0.00032596138771623373f);
+  p = __builtin_fmaf(p, y, 0.01585433818399906f);
+  p = __builtin_fmaf(p, y, -0.3084251284599304f);
+  const float c = __builtin_fmaf(p, y, 1.0f);
+  const int swap = ((octant + 1u) >> 1) & 1u;                  /* octants 1, 2, 5, 6 */
+  float so = swap ? c : s, co = swap ? s : c;
+  if (octant >= 4u) so = -so;
+  if (((octant + 2u) >> 2) & 1u) co = -co;                     /* octants 2 .. 5 */
+  *sn = so;
+  *cs = co;
+}
+
+/* Two 32-bit words to two standard normals (Box-Muller on 24-bit uniforms): u1 = ((ra >> 8) + 1) 2^-24 in (0, 1],
+ * u2 = (rb >> 8) 2^-24 in [0, 1), rad = sqrt(-2 log u1) (the doubling exact, the root correctly rounded), z0 = rad *
+ * cos(2 pi u2), z1 = rad * sin(2 pi u2).  |z| <= sqrt(48 ln 2) ~ 5.77: the distribution has no longer tail. */
+MIXDQ_HD void mixdq_rng_box_muller(uint32_t ra, uint32_t rb, float* z0, float* z1) {
+  const float rad = MIXDQ_SQRT_RN(MIXDQ_MUL_RN(-2.0f, mixdq_rng_log_u24((ra >> 8) + 1u)));
+  float sn, cs;
+  mixdq_rng_sincos_u24(rb >> 8, &sn, &cs);
+  *z0 = MIXDQ_MUL_RN(rad, cs);
+  *z1 = MIXDQ_MUL_RN(rad, sn);
+}
+
+/* The four outputs of one Philox call as four normals: (r0, r1) -> (z0, z1), (r2, r3) -> (z2, z3). */
+MIXDQ_HD void mixdq_rng_normals4(const uint32_t r[4], float z[4]) {
+  mixdq_rng_box_muller(r[0], r[1], &z[0], &z[1]);
+  mixdq_rng_box_muller(r[2], r[3], &z[2], &z[3]);
+}
+
+/* Which call produces which element.  Image b of a batch has a 64-bit seed; element e of that image, counted in
+ * storage (NHWC) order, is lane e & 3 of the call with key (lo32(seed), hi32(seed)) and counter (lo32(e >> 2),
+ * hi32(e >> 2), step, stream) -- stream: what the noise is for (MIXDQ_RNG_STREAM_*, mixdq_hip.h), step: the absolute
+ * index of the sampler step that consumes it (0 for the other streams).  mixdq_rng_quad: elements 4 * quad .. + 3. */
+MIXDQ_HD void mixdq_rng_bits(uint64_t seed, uint64_t quad, uint32_t step, uint32_t stream, uint32_t r[4]) {
+  const uint32_t ctr[4] = {(uint32_t)quad, (uint32_t)(quad >> 32), step, stream};
+  const uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+  mixdq_philox4x32_10(ctr, key, r);
+}
+
+MIXDQ_HD void mixdq_rng_quad(uint64_t seed, uint64_t quad, uint32_t step, uint32_t stream, float z[4]) {
+  uint32_t r[4];
+  mixdq_rng_bits(seed, quad, step, stream, r);
+  mixdq_rng_normals4(r, z);
+}
+
+/* One element alone: the same call, the Box-Muller pair of its lane only -- the same bits as mixdq_rng_quad's. */
+MIXDQ_HD float mixdq_rng_normal_at(uint64_t seed, uint64_t e, uint32_t step, uint32_t stream) {
+  uint32_t r[4];
+  float z0, z1;
+  mixdq_rng_bits(seed, e >> 2, step, stream, r);
+  if (e & 2u) mixdq_rng_box_muller(r[2], r[3], &z0, &z1);
+  else mixdq_rng_box_muller(r[0], r[1], &z0, &z1);
+  return (e & 1u) ? z1 : z0;
+}
+
 #endif /* MIXDQ_MATH_H_ */

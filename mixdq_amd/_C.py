@@ -1401,10 +1401,69 @@ def embed_tokens_f16(ids, tok, pos):
 _lib.mixdq_sampler_step.argtypes = [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, ctypes.c_float, _i64, _i32,
                                     _i64, _vp]
 _lib.mixdq_sampler_step.restype = _i32
+_lib.mixdq_sampler_step_rng.argtypes = _lib.mixdq_sampler_step.argtypes
+_lib.mixdq_sampler_step_rng.restype = _i32
+_lib.mixdq_randn_f32.argtypes = [_vp, _i32, _i64, _vp, ctypes.c_uint32, ctypes.c_uint32, _vp]
+_lib.mixdq_randn_f32.restype = _i32
+_lib.mixdq_rng_normals_from_bits.argtypes = [_vp, _vp, _i64, _vp]
+_lib.mixdq_rng_normals_from_bits.restype = _i32
+RNG_STREAM_START, RNG_STREAM_STEP, RNG_STREAM_VAE = 0, 1, 2               # include/mixdq_hip.h MIXDQ_RNG_STREAM_*
+
+
+def _check_seeds(seeds, B, what):
+    _check(torch.is_tensor(seeds) and seeds.dtype == torch.int64 and seeds.dim() == 1 and seeds.shape[0] == B
+           and seeds.is_contiguous(), f"{what}: seeds should be a contiguous int64 tensor of shape [{B}]")
+
+
+def _check_step_seeds(seeds, noise, n, n_image, numel, what):
+    """The checks of a step binding's `seeds=` / `n_image=`; returns (n, n_image).  They come first and look at no
+    device, so that a wrong call is refused the same way wherever it is made."""
+    _check(noise is None, f"{what}: noise and seeds exclude each other (with seeds the step makes its own noise)")
+    n = int(numel if n is None else n)
+    n_image = n if n_image is None else int(n_image)
+    _check(n_image >= 1 and n % n_image == 0, f"{what}: n = {n} is not a multiple of n_image = {n_image}")
+    _check_seeds(seeds, n // n_image, what)
+    return n, n_image
+
+
+def randn(shape, seeds, stream=0, step=0, out=None):
+    """Standard normals made on the device (mixdq_randn_f32): fp32 [B, C, H, W] in channels-last storage.  seeds: int64
+    GPU tensor [B], one per image, its bits read as unsigned.  Element e = (h * W + w) * C + c of image b is lane e & 3
+    of Philox4x32-10 with key seeds[b] and counter (e >> 2, step, stream) through Box-Muller (include/mixdq_math.h):
+    an image's values depend on its seed and shape only.  stream: RNG_STREAM_START (0), _STEP (1, with `step` the index
+    of the sampler step that adds it), _VAE (2).  out: a dense channels-last fp32 tensor of that shape to fill."""
+    _check(len(shape) == 4 and all(int(d) >= 1 for d in shape[1:]) and int(shape[0]) >= 0,
+           "randn: shape should be (B, C, H, W)")
+    B, C, H, W = (int(d) for d in shape)
+    _check_seeds(seeds, B, "randn")
+    _check(seeds.is_cuda, "randn: seeds should be on the GPU")
+    _check(0 <= int(stream) < 2 ** 32 and 0 <= int(step) < 2 ** 32, "randn: stream and step are unsigned 32-bit values")
+    if out is None:
+        out = torch.empty((B, H, W, C), dtype=torch.float32, device=seeds.device).permute(0, 3, 1, 2)
+    else:
+        _check(torch.is_tensor(out) and out.dtype == torch.float32 and out.device == seeds.device
+               and tuple(out.shape) == (B, C, H, W) and out.permute(0, 2, 3, 1).is_contiguous(),
+               "randn: out should be a dense channels-last fp32 tensor of the shape on the seeds' device")
+    with torch.cuda.device(seeds.device):
+        code = _lib.mixdq_randn_f32(out.data_ptr(), B, C * H * W, seeds.data_ptr(), int(stream), int(step), _stream())
+    _status(code, "randn")
+    return out
+
+
+def rng_normals_from_bits(r):
+    """Test hook (mixdq_rng_normals_from_bits): int32 GPU tensor [n, 4] -- the raw 32-bit words, their bits read as
+    unsigned -- -> fp32 [n, 4]."""
+    _check(torch.is_tensor(r) and r.is_cuda and r.dtype == torch.int32 and r.dim() == 2 and r.shape[1] == 4
+           and r.is_contiguous(), "rng_normals_from_bits: r should be a contiguous int32 [n, 4] GPU tensor")
+    z = torch.empty(r.shape, dtype=torch.float32, device=r.device)
+    with torch.cuda.device(r.device):
+        code = _lib.mixdq_rng_normals_from_bits(r.data_ptr(), z.data_ptr(), r.shape[0], _stream())
+    _status(code, "rng_normals_from_bits")
+    return z
 
 
 def sampler_step(x, eps, inp, coef, t_table, step, timestep, guidance=0.0, rows_per_image=1, noise=None, *,
-                 n=None, row_stride=None, noise_stride=None):
+                 n=None, row_stride=None, noise_stride=None, seeds=None, n_image=None):
     """One sampler step in place (mixdq_sampler_step): guidance over the two row blocks of `eps`, the affine
     scheduler update of the FP32 state `x` with `coef[step]` = (a, b, c, s_next), the UNet's next FP16 input into
     every row block of `inp`; then `timestep` <- `t_table[step + 1]` and `step` += 1, on the device.
@@ -1413,11 +1472,18 @@ def sampler_step(x, eps, inp, coef, t_table, step, timestep, guidance=0.0, rows_
     first); noise: None, or fp32 [n_steps] blocks `noise_stride` apart; coef: fp32 [n_steps, 4]; t_table: fp32
     [n_steps + 1]; step: int32 [1]; timestep: the fp32 0-dim tensor the UNet reads.  The kernel is elementwise over
     STORAGE: x, eps, inp and noise must be dense and share one stride pattern (the caller's business: Sampler checks
-    it).  `n` defaults to x.numel(), the strides to n."""
+    it).  `n` defaults to x.numel(), the strides to n.
+
+    seeds (int64 [n / n_image] on x's GPU, read as unsigned; `noise` must then be None): the step computes its noise in
+    registers (mixdq_sampler_step_rng) -- the values randn(.., seeds, stream=RNG_STREAM_STEP, step=<step>) holds for
+    images of `n_image` elements (default: n, one image)."""
+    if seeds is not None:
+        n, n_image = _check_step_seeds(seeds, noise, n, n_image, x.numel(), "sampler_step")
     for t_, name, dt in ((x, "x", torch.float32), (eps, "eps", torch.float16), (inp, "inp", torch.float16),
                          (coef, "coef", torch.float32), (t_table, "t_table", torch.float32),
                          (step, "step", torch.int32), (timestep, "timestep", torch.float32)) + (
-                             ((noise, "noise", torch.float32),) if noise is not None else ()):
+                             ((noise, "noise", torch.float32),) if noise is not None else ()) + (
+                             ((seeds, "seeds", torch.int64),) if seeds is not None else ()):
         _check(t_.is_cuda and t_.device == x.device and t_.dtype == dt, f"{name} should be a {dt} tensor on x's GPU")
     _check(coef.dim() == 2 and coef.shape[1] == 4 and coef.is_contiguous() and t_table.is_contiguous(),
            "coef should be a contiguous [n_steps, 4] table")
@@ -1433,6 +1499,14 @@ def sampler_step(x, eps, inp, coef, t_table, step, timestep, guidance=0.0, rows_
         _check(eps.numel() >= need and inp.numel() >= need, "eps / inp are smaller than rows_per_image row blocks")
     if noise is not None:
         _check(noise.numel() >= (n_steps - 1) * noise_stride + n, "noise is smaller than n_steps blocks")
+    if seeds is not None:
+        with torch.cuda.device(x.device):
+            code = _lib.mixdq_sampler_step_rng(x.data_ptr(), eps.data_ptr(), inp.data_ptr(), seeds.data_ptr(), n_image,
+                                               coef.data_ptr(), t_table.data_ptr(), n_steps, step.data_ptr(),
+                                               timestep.data_ptr(), float(guidance), n, int(rows_per_image), row_stride,
+                                               _stream())
+        _status(code, "sampler_step")
+        return
     with torch.cuda.device(x.device):
         code = _lib.mixdq_sampler_step(x.data_ptr(), eps.data_ptr(), inp.data_ptr(), _ptr(noise), noise_stride,
                                        coef.data_ptr(), t_table.data_ptr(), n_steps, step.data_ptr(),
@@ -1444,23 +1518,30 @@ def sampler_step(x, eps, inp, coef, t_table, step, timestep, guidance=0.0, rows_
 _lib.mixdq_sampler_step_masked.argtypes = [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, ctypes.c_float, _i64,
                                            _i32, _i64, _vp, _vp, _vp, _i32, _vp, _vp]
 _lib.mixdq_sampler_step_masked.restype = _i32
+_lib.mixdq_sampler_step_masked_rng.argtypes = _lib.mixdq_sampler_step_masked.argtypes
+_lib.mixdq_sampler_step_masked_rng.restype = _i32
 
 
 def sampler_step_masked(x, eps, inp, coef, t_table, step, timestep, z, noise0, mask, blend, guidance=0.0,
-                        rows_per_image=1, noise=None, *, channels=4, n=None, row_stride=None, noise_stride=None):
+                        rows_per_image=1, noise=None, *, channels=4, n=None, row_stride=None, noise_stride=None,
+                        seeds=None, n_image=None):
     """sampler_step for inpainting (mixdq_sampler_step_masked): the same guidance and update, then the region the
     mask keeps is overwritten with the image latents at the next step's noise level,
     x = (1 - m) * (p * z + q * noise0) + m * x', (p, q) = blend[step], and the UNet's next input is taken from that.
 
     z, noise0: fp32, `n` elements in x's stride pattern; mask: fp32, one value per latent pixel ([B, h, w] dense,
     n / channels entries; 1 repaints, 0 keeps): element i of the channels-last storage belongs to entry
-    i // channels; blend: fp32 [n_steps, 2] (Schedule.blend).  Everything else as sampler_step."""
+    i // channels; blend: fp32 [n_steps, 2] (Schedule.blend).  Everything else as sampler_step, `seeds` / `n_image`
+    (mixdq_sampler_step_masked_rng) included."""
+    if seeds is not None:
+        n, n_image = _check_step_seeds(seeds, noise, n, n_image, x.numel(), "sampler_step_masked")
     for t_, name, dt in ((x, "x", torch.float32), (eps, "eps", torch.float16), (inp, "inp", torch.float16),
                          (coef, "coef", torch.float32), (t_table, "t_table", torch.float32),
                          (step, "step", torch.int32), (timestep, "timestep", torch.float32),
                          (z, "z", torch.float32), (noise0, "noise0", torch.float32), (mask, "mask", torch.float32),
                          (blend, "blend", torch.float32)) + (
-                             ((noise, "noise", torch.float32),) if noise is not None else ()):
+                             ((noise, "noise", torch.float32),) if noise is not None else ()) + (
+                             ((seeds, "seeds", torch.int64),) if seeds is not None else ()):
         _check(torch.is_tensor(t_) and t_.is_cuda and t_.device == x.device and t_.dtype == dt,
                f"{name} should be a {dt} tensor on x's GPU")
     _check(coef.dim() == 2 and coef.shape[1] == 4 and coef.is_contiguous() and t_table.is_contiguous(),
@@ -1482,6 +1563,15 @@ def sampler_step_masked(x, eps, inp, coef, t_table, step, timestep, z, noise0, m
         _check(eps.numel() >= need and inp.numel() >= need, "eps / inp are smaller than rows_per_image row blocks")
     if noise is not None:
         _check(noise.numel() >= (n_steps - 1) * noise_stride + n, "noise is smaller than n_steps blocks")
+    if seeds is not None:
+        with torch.cuda.device(x.device):
+            code = _lib.mixdq_sampler_step_masked_rng(x.data_ptr(), eps.data_ptr(), inp.data_ptr(), seeds.data_ptr(),
+                                                      n_image, coef.data_ptr(), t_table.data_ptr(), n_steps,
+                                                      step.data_ptr(), timestep.data_ptr(), float(guidance), n,
+                                                      int(rows_per_image), row_stride, z.data_ptr(), noise0.data_ptr(),
+                                                      mask.data_ptr(), channels, blend.data_ptr(), _stream())
+        _status(code, "sampler_step_masked")
+        return
     with torch.cuda.device(x.device):
         code = _lib.mixdq_sampler_step_masked(x.data_ptr(), eps.data_ptr(), inp.data_ptr(), _ptr(noise), noise_stride,
                                               coef.data_ptr(), t_table.data_ptr(), n_steps, step.data_ptr(),

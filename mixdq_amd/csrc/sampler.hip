@@ -21,6 +21,12 @@
 // lives in a caller-owned FP32 buffer `hist` that a third kernel (sampler_step_2m_kernel, below the two others, which
 // it does not touch) reads and rewrites, with the index of the run's first step in a device int beside the step index.
 //
+// mixdq_sampler_step[_masked]_rng are the first two kernels in a third noise mode: n is not loaded but computed in
+// registers -- Philox4x32-10 keyed by the image's seed, counter (element / 4, *step, stream 1), then Box-Muller
+// (include/mixdq_math.h: mixdq_rng_*) -- so a stochastic schedule needs no [n_steps, ...] noise buffer and a captured
+// graph serves every seed (the seeds are read from device memory).  mixdq_randn_f32 fills a buffer by the same rule
+// (the start noise, the VAE posterior's), mixdq_rng_normals_from_bits is the words-to-normals map alone, for tests.
+//
 // The step index is read by every workgroup of the step launch and advanced by the launch BEHIND it on the same
 // stream (sampler_advance_kernel, one thread): launches of one stream run in order, so no workgroup of the step
 // can read the index after it moved, without any in-launch ticket, fence or counter to re-initialise.
@@ -43,23 +49,93 @@ __device__ __forceinline__ uint32_t half_bits(float v) {
   return (uint32_t)__half_raw(f32_to_f16_rn(v)).x;
 }
 
-template <int ROWS, bool NOISE>
+// NOISE, the step kernels' noise mode: 0 none, 1 read from a buffer, 2 and 3 computed in registers (mixdq_rng_*,
+// include/mixdq_math.h) from (seeds[image], element in the image, *step) on stream MIXDQ_RNG_STREAM_STEP.  An 8-element
+// pass starting at storage element o: 2 (n_image % 8 == 0) -- it lies inside one image and is two whole Philox calls;
+// 3 -- any n_image: one call per element, the image index carried along.  Roughly 300 vector operations per 8 elements
+// in mode 2 against a 32-byte load in mode 1.
+template <bool WHOLE>
+__device__ __forceinline__ void rng_noise8(const uint64_t* __restrict__ seeds, int64_t n_image, int64_t o, uint32_t step,
+                                           float ns[8]) {
+  int64_t b = o / n_image;
+  int64_t e = o - b * n_image;
+  if (WHOLE) {
+    const uint64_t seed = seeds[b];
+    mixdq_rng_quad(seed, (uint64_t)e >> 2, step, MIXDQ_RNG_STREAM_STEP, ns);
+    mixdq_rng_quad(seed, ((uint64_t)e >> 2) + 1, step, MIXDQ_RNG_STREAM_STEP, ns + 4);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {                  // o + j < n and n % n_image == 0: b stays below n / n_image
+      ns[j] = mixdq_rng_normal_at(seeds[b], (uint64_t)e, step, MIXDQ_RNG_STREAM_STEP);
+      if (++e == n_image) { e = 0; ++b; }
+    }
+  }
+}
+
+template <int NOISE>
+__device__ __forceinline__ float tail_noise(const float* __restrict__ nz, const uint64_t* __restrict__ seeds,
+                                            int64_t n_image, int64_t t, uint32_t step) {
+  if (NOISE == 0) return 0.0f;
+  if (NOISE == 1) return nz[t];
+  const int64_t b = t / n_image;
+  return mixdq_rng_normal_at(seeds[b], (uint64_t)(t - b * n_image), step, MIXDQ_RNG_STREAM_STEP);
+}
+
+// mixdq_randn_f32: one Philox call -- four normals -- per lane per pass, grid-stride over the B * ceil(n_image / 4) calls.
+// VEC (n_image % 4 == 0): every call's four elements are one aligned 16-byte store; otherwise the last call of an image
+// is partly used and the stores are scalar.
+template <bool VEC>
+__global__ __launch_bounds__(256) void randn_kernel(float* __restrict__ out, int64_t n_image, int64_t quads_per_image,
+                                                    int64_t total_quads, const uint64_t* __restrict__ seeds,
+                                                    uint32_t rstream, uint32_t step) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < total_quads; q += stride) {
+    const int64_t b = q / quads_per_image;         // q < B * quads_per_image: b < B
+    const int64_t qi = q - b * quads_per_image;
+    float z[4];
+    mixdq_rng_quad(seeds[b], (uint64_t)qi, step, rstream, z);
+    float* p = out + b * n_image + 4 * qi;
+    if (VEC) {
+      *reinterpret_cast<float4*>(p) = make_float4(z[0], z[1], z[2], z[3]);
+    } else {
+      const int64_t left = n_image - 4 * qi;       // >= 1
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (j < left) p[j] = z[j];
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void normals_from_bits_kernel(const uint32_t* __restrict__ r, float* __restrict__ z,
+                                                                int64_t n_quads) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n_quads; q += stride) {
+    const uint4 w = *reinterpret_cast<const uint4*>(r + 4 * q);
+    const uint32_t rr[4] = {w.x, w.y, w.z, w.w};
+    float zz[4];
+    mixdq_rng_normals4(rr, zz);
+    *reinterpret_cast<float4*>(z + 4 * q) = make_float4(zz[0], zz[1], zz[2], zz[3]);
+  }
+}
+
+template <int ROWS, int NOISE>
 __device__ __forceinline__ float step_one(float x, float eu, float ec, float n, float g, float a, float b, float c) {
   const float e = ROWS == 2 ? mixdq_sampler_guided_eps(eu, ec, g) : eu;
   return NOISE ? mixdq_sampler_update_noise(x, e, n, a, b, c) : mixdq_sampler_update(x, e, a, b);
 }
 
-template <int ROWS, bool NOISE>
+template <int ROWS, int NOISE>
 __global__ __launch_bounds__(256) void sampler_step_kernel(float* __restrict__ x, const __half* __restrict__ eps,
                                                            __half* __restrict__ in, const float* __restrict__ noise,
                                                            int64_t noise_stride, const float* __restrict__ coef,
                                                            const int* __restrict__ step_p, int n_steps, float g,
-                                                           int64_t n, int64_t row_stride) {
+                                                           int64_t n, int64_t row_stride,
+                                                           const uint64_t* __restrict__ seeds, int64_t n_image) {
   const int step = *step_p;
   if (step < 0 || step >= n_steps) return;        // replayed past the table: nothing is read or written
   const float4 k = *reinterpret_cast<const float4*>(coef + 4 * (int64_t)step);
   const float a = k.x, b = k.y, c = k.z, s_next = k.w;
-  const float* nz = NOISE ? noise + (int64_t)step * noise_stride : nullptr;
+  const float* nz = NOISE == 1 ? noise + (int64_t)step * noise_stride : nullptr;
   const int64_t nvec = n >> 3;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += stride) {
@@ -69,12 +145,13 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(float* __restrict__ x
     Half8 ec = eu;
     if (ROWS == 2) ec = *reinterpret_cast<const Half8*>(eps + row_stride + o);
     float4 n0 = x0, n1 = x1;
-    if (NOISE) {
+    if (NOISE == 1) {
       n0 = *reinterpret_cast<const float4*>(nz + o);
       n1 = *reinterpret_cast<const float4*>(nz + o + 4);
     }
     const float xs[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-    const float ns[8] = {n0.x, n0.y, n0.z, n0.w, n1.x, n1.y, n1.z, n1.w};
+    float ns[8] = {n0.x, n0.y, n0.z, n0.w, n1.x, n1.y, n1.z, n1.w};
+    if (NOISE >= 2) rng_noise8<NOISE == 2>(seeds, n_image, o, (uint32_t)step, ns);
     float y[8];
     Half8 out;
 #pragma unroll
@@ -93,7 +170,7 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(float* __restrict__ x
   if (blockIdx.x == 0 && t < n) {
     const float eu = __half2float(eps[t]);
     const float ec = ROWS == 2 ? __half2float(eps[row_stride + t]) : eu;
-    const float y = step_one<ROWS, NOISE>(x[t], eu, ec, NOISE ? nz[t] : 0.0f, g, a, b, c);
+    const float y = step_one<ROWS, NOISE>(x[t], eu, ec, tail_noise<NOISE>(nz, seeds, n_image, t, (uint32_t)step), g, a, b, c);
     const __half h = f32_to_f16_rn(mixdq_sampler_scaled_input(y, s_next));
     x[t] = y;
     in[t] = h;
@@ -104,18 +181,18 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(float* __restrict__ x
 // The masked step: sampler_step_kernel's body, then mixdq_sampler_blend.  Element i of the (channels-last) storage
 // belongs to mask entry i / channels.  C4: channels == 4, an 8-element pass covers exactly two latent pixels; otherwise
 // the quotient and remainder of the pass's first element are divided out once and carried along.
-template <int ROWS, bool NOISE, bool C4>
+template <int ROWS, int NOISE, bool C4>
 __global__ __launch_bounds__(256) void sampler_step_masked_kernel(
     float* __restrict__ x, const __half* __restrict__ eps, __half* __restrict__ in, const float* __restrict__ noise,
     int64_t noise_stride, const float* __restrict__ coef, const int* __restrict__ step_p, int n_steps, float g, int64_t n,
     int64_t row_stride, const float* __restrict__ z, const float* __restrict__ noise0, const float* __restrict__ mask,
-    int channels, const float* __restrict__ blend) {
+    int channels, const float* __restrict__ blend, const uint64_t* __restrict__ seeds, int64_t n_image) {
   const int step = *step_p;
   if (step < 0 || step >= n_steps) return;        // replayed past the table: nothing is read or written
   const float4 k = *reinterpret_cast<const float4*>(coef + 4 * (int64_t)step);
   const float a = k.x, b = k.y, c = k.z, s_next = k.w;
   const float2 pq = *reinterpret_cast<const float2*>(blend + 2 * (int64_t)step);
-  const float* nz = NOISE ? noise + (int64_t)step * noise_stride : nullptr;
+  const float* nz = NOISE == 1 ? noise + (int64_t)step * noise_stride : nullptr;
   const int64_t nvec = n >> 3;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += stride) {
@@ -127,7 +204,7 @@ __global__ __launch_bounds__(256) void sampler_step_masked_kernel(
     Half8 ec = eu;
     if (ROWS == 2) ec = *reinterpret_cast<const Half8*>(eps + row_stride + o);
     float4 n0 = x0, n1 = x1;
-    if (NOISE) {
+    if (NOISE == 1) {
       n0 = *reinterpret_cast<const float4*>(nz + o);
       n1 = *reinterpret_cast<const float4*>(nz + o + 4);
     }
@@ -146,7 +223,8 @@ __global__ __launch_bounds__(256) void sampler_step_masked_kernel(
       }
     }
     const float xs[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-    const float ns[8] = {n0.x, n0.y, n0.z, n0.w, n1.x, n1.y, n1.z, n1.w};
+    float ns[8] = {n0.x, n0.y, n0.z, n0.w, n1.x, n1.y, n1.z, n1.w};
+    if (NOISE >= 2) rng_noise8<NOISE == 2>(seeds, n_image, o, (uint32_t)step, ns);
     const float zs[8] = {z0.x, z0.y, z0.z, z0.w, z1.x, z1.y, z1.z, z1.w};
     const float is[8] = {i0.x, i0.y, i0.z, i0.w, i1.x, i1.y, i1.z, i1.w};
     float y[8];
@@ -169,7 +247,7 @@ __global__ __launch_bounds__(256) void sampler_step_masked_kernel(
   if (blockIdx.x == 0 && t < n) {
     const float eu = __half2float(eps[t]);
     const float ec = ROWS == 2 ? __half2float(eps[row_stride + t]) : eu;
-    const float y = mixdq_sampler_blend(step_one<ROWS, NOISE>(x[t], eu, ec, NOISE ? nz[t] : 0.0f, g, a, b, c), z[t],
+    const float y = mixdq_sampler_blend(step_one<ROWS, NOISE>(x[t], eu, ec, tail_noise<NOISE>(nz, seeds, n_image, t, (uint32_t)step), g, a, b, c), z[t],
                                         noise0[t], mask[t / channels], pq.x, pq.y);
     const __half h = f32_to_f16_rn(mixdq_sampler_scaled_input(y, s_next));
     x[t] = y;
@@ -331,11 +409,11 @@ extern "C" int mixdq_sampler_step(float* x, const void* eps_f16, void* in_f16, c
     __half* in = (__half*)in_f16;
 #define S_LAUNCH(R, NZ)                                                                               \
   sampler_step_kernel<R, NZ><<<blocks, 256, 0, stream>>>(x, eps, in, noise_or_null, noise_stride, coef, step, \
-                                                         n_steps, guidance, n, row_stride)
+                                                         n_steps, guidance, n, row_stride, nullptr, 0)
     if (rows_per_image == 2) {
-      if (noise_or_null) S_LAUNCH(2, true); else S_LAUNCH(2, false);
+      if (noise_or_null) S_LAUNCH(2, 1); else S_LAUNCH(2, 0);
     } else {
-      if (noise_or_null) S_LAUNCH(1, true); else S_LAUNCH(1, false);
+      if (noise_or_null) S_LAUNCH(1, 1); else S_LAUNCH(1, 0);
     }
 #undef S_LAUNCH
     if (hipGetLastError() != hipSuccess) return MIXDQ_ERR_LAUNCH;
@@ -363,16 +441,122 @@ extern "C" int mixdq_sampler_step_masked(float* x, const void* eps_f16, void* in
 #define M_LAUNCH(R, NZ, C4)                                                                                          \
   sampler_step_masked_kernel<R, NZ, C4><<<blocks, 256, 0, stream>>>(x, eps, in, noise_or_null, noise_stride, coef, step, \
                                                                     n_steps, guidance, n, row_stride, z, noise0, mask,   \
-                                                                    channels, blend)
+                                                                    channels, blend, nullptr, 0)
 #define M_LAUNCH_C(R, NZ) \
   do { if (channels == 4) M_LAUNCH(R, NZ, true); else M_LAUNCH(R, NZ, false); } while (0)
     if (rows_per_image == 2) {
-      if (noise_or_null) M_LAUNCH_C(2, true); else M_LAUNCH_C(2, false);
+      if (noise_or_null) M_LAUNCH_C(2, 1); else M_LAUNCH_C(2, 0);
     } else {
-      if (noise_or_null) M_LAUNCH_C(1, true); else M_LAUNCH_C(1, false);
+      if (noise_or_null) M_LAUNCH_C(1, 1); else M_LAUNCH_C(1, 0);
     }
 #undef M_LAUNCH_C
 #undef M_LAUNCH
+    if (hipGetLastError() != hipSuccess) return MIXDQ_ERR_LAUNCH;
+  }
+  sampler_advance_kernel<<<1, 1, 0, stream>>>(t_table, n_steps, step, timestep);
+  return launch_status();
+}
+
+// ---- noise made on the device ------------------------------------------------------------------------------------------
+namespace mixdq {
+namespace {
+
+int quad_blocks(int64_t quads) {
+  int64_t blocks = (quads + 255) / 256;
+  if (blocks > (int64_t)kNumCU * 8) blocks = (int64_t)kNumCU * 8;
+  return blocks < 1 ? 1 : (int)blocks;
+}
+
+// What the two _rng entry points check beyond check_step_args.
+int check_rng_args(const uint64_t* seeds, int64_t n_image, int64_t n) {
+  if (!seeds || n_image < 1 || n % n_image) return MIXDQ_ERR_INVALID_ARG;
+  if ((uintptr_t)seeds % 8) return MIXDQ_ERR_ALIGNMENT;
+  return MIXDQ_OK;
+}
+
+}  // namespace
+}  // namespace mixdq
+
+extern "C" int mixdq_randn_f32(float* out, int B, int64_t n_image, const uint64_t* seeds_device, uint32_t rstream,
+                               uint32_t step, mixdq_stream_t stream_) {
+  if (!out || !seeds_device || B < 0 || n_image < 1) return MIXDQ_ERR_INVALID_ARG;
+  const bool vec = n_image % 4 == 0;
+  if ((uintptr_t)out % (vec ? 16 : 4) || (uintptr_t)seeds_device % 8) return MIXDQ_ERR_ALIGNMENT;
+  if (B == 0) return MIXDQ_OK;
+  hipStream_t stream = (hipStream_t)stream_;
+  const int64_t qpi = (n_image + 3) / 4, total = qpi * B;
+  const int blocks = quad_blocks(total);
+  if (vec) randn_kernel<true><<<blocks, 256, 0, stream>>>(out, n_image, qpi, total, seeds_device, rstream, step);
+  else randn_kernel<false><<<blocks, 256, 0, stream>>>(out, n_image, qpi, total, seeds_device, rstream, step);
+  return launch_status();
+}
+
+extern "C" int mixdq_rng_normals_from_bits(const uint32_t* r, float* z, int64_t n_quads, mixdq_stream_t stream_) {
+  if (!r || !z || n_quads < 0) return MIXDQ_ERR_INVALID_ARG;
+  if ((uintptr_t)r % 16 || (uintptr_t)z % 16) return MIXDQ_ERR_ALIGNMENT;
+  if (n_quads == 0) return MIXDQ_OK;
+  normals_from_bits_kernel<<<quad_blocks(n_quads), 256, 0, (hipStream_t)stream_>>>(r, z, n_quads);
+  return launch_status();
+}
+
+extern "C" int mixdq_sampler_step_rng(float* x, const void* eps_f16, void* in_f16, const uint64_t* seeds,
+                                      int64_t n_image, const float* coef, const float* t_table, int n_steps, int* step,
+                                      float* timestep, float guidance, int64_t n, int rows_per_image, int64_t row_stride,
+                                      mixdq_stream_t stream_) {
+  int bad = check_step_args(x, eps_f16, in_f16, nullptr, 0, coef, t_table, n_steps, step, timestep, n, rows_per_image,
+                            row_stride);
+  if (bad == MIXDQ_OK) bad = check_rng_args(seeds, n_image, n);
+  if (bad != MIXDQ_OK) return bad;
+  hipStream_t stream = (hipStream_t)stream_;
+  if (n > 0) {
+    const int blocks = step_blocks(n);
+    const __half* eps = (const __half*)eps_f16;
+    __half* in = (__half*)in_f16;
+#define R_LAUNCH(R, NZ)                                                                                             \
+  sampler_step_kernel<R, NZ><<<blocks, 256, 0, stream>>>(x, eps, in, nullptr, 0, coef, step, n_steps, guidance, n, \
+                                                         row_stride, seeds, n_image)
+    if (rows_per_image == 2) {
+      if (n_image % 8 == 0) R_LAUNCH(2, 2); else R_LAUNCH(2, 3);
+    } else {
+      if (n_image % 8 == 0) R_LAUNCH(1, 2); else R_LAUNCH(1, 3);
+    }
+#undef R_LAUNCH
+    if (hipGetLastError() != hipSuccess) return MIXDQ_ERR_LAUNCH;
+  }
+  sampler_advance_kernel<<<1, 1, 0, stream>>>(t_table, n_steps, step, timestep);
+  return launch_status();
+}
+
+extern "C" int mixdq_sampler_step_masked_rng(float* x, const void* eps_f16, void* in_f16, const uint64_t* seeds,
+                                             int64_t n_image, const float* coef, const float* t_table, int n_steps,
+                                             int* step, float* timestep, float guidance, int64_t n, int rows_per_image,
+                                             int64_t row_stride, const float* z, const float* noise0, const float* mask,
+                                             int channels, const float* blend, mixdq_stream_t stream_) {
+  int bad = check_step_args(x, eps_f16, in_f16, nullptr, 0, coef, t_table, n_steps, step, timestep, n, rows_per_image,
+                            row_stride);
+  if (bad == MIXDQ_OK) bad = check_rng_args(seeds, n_image, n);
+  if (bad != MIXDQ_OK) return bad;
+  if (!z || !noise0 || !mask || !blend || channels < 1 || n % channels) return MIXDQ_ERR_INVALID_ARG;
+  if ((uintptr_t)z % 16 || (uintptr_t)noise0 % 16 || (uintptr_t)mask % 4 || (uintptr_t)blend % 8)
+    return MIXDQ_ERR_ALIGNMENT;
+  hipStream_t stream = (hipStream_t)stream_;
+  if (n > 0) {
+    const int blocks = step_blocks(n);
+    const __half* eps = (const __half*)eps_f16;
+    __half* in = (__half*)in_f16;
+#define MR_LAUNCH(R, NZ, C4)                                                                                          \
+  sampler_step_masked_kernel<R, NZ, C4><<<blocks, 256, 0, stream>>>(x, eps, in, nullptr, 0, coef, step, n_steps,      \
+                                                                    guidance, n, row_stride, z, noise0, mask, channels, \
+                                                                    blend, seeds, n_image)
+#define MR_LAUNCH_C(R, NZ) \
+  do { if (channels == 4) MR_LAUNCH(R, NZ, true); else MR_LAUNCH(R, NZ, false); } while (0)
+    if (rows_per_image == 2) {
+      if (n_image % 8 == 0) MR_LAUNCH_C(2, 2); else MR_LAUNCH_C(2, 3);
+    } else {
+      if (n_image % 8 == 0) MR_LAUNCH_C(1, 2); else MR_LAUNCH_C(1, 3);
+    }
+#undef MR_LAUNCH_C
+#undef MR_LAUNCH
     if (hipGetLastError() != hipSuccess) return MIXDQ_ERR_LAUNCH;
   }
   sampler_advance_kernel<<<1, 1, 0, stream>>>(t_table, n_steps, step, timestep);

@@ -31,6 +31,11 @@ prediction x0 = u * x + v * e.  Its table is `multistep_table`, [n_steps][8] = (
 Sampler keeps that one extra tensor (`_hist`) and the index of the run's first step (`_first`) on the device beside the
 step index, and the captured graphs record mixdq_sampler_step_2m[_masked] instead.  The step at `_first` and the last
 one are first-order, so a run never reads what an earlier run left in `_hist`.
+
+`sample(..., seed=)` makes the noise on the device instead of taking it: Philox4x32-10 keyed by a 64-bit seed per image,
+counter (element / 4, step, stream), Box-Muller on 24-bit uniforms (include/mixdq_math.h; numpy restatement:
+tests/rng_ref.py).  The start noise is one mixdq_randn_f32 launch; the noise of stochastic steps is computed inside
+mixdq_sampler_step[_masked]_rng, recorded in graphs of their own that read a static seed buffer.
 """
 import numpy as np
 
@@ -229,6 +234,27 @@ def schedule(kind, n_steps, spacing=None, karras=False) -> Schedule:
     return Schedule(kind, n_steps, spacing, karras)
 
 
+def seed_tensor(seed, B, device):
+    """`seed` as the int64 [B] tensor on `device` whose bits, read as unsigned, are the per-image seeds: a Python int in
+    [0, 2^64) -- image b takes (seed + b) mod 2^64; a sequence of B such ints; or an int64 [B] tensor on `device`, taken
+    as it is (no host involvement)."""
+    import torch
+    if torch.is_tensor(seed):
+        if not (seed.dtype == torch.int64 and tuple(seed.shape) == (B,) and seed.device == torch.device(device)):
+            raise RuntimeError(f"seed: a tensor should be int64 of shape [{B}] on {device}")
+        return seed
+    if isinstance(seed, int) and not isinstance(seed, bool):
+        vals = [seed + b for b in range(B)]
+        if not 0 <= seed < 2 ** 64:
+            raise RuntimeError("seed: an int should be in [0, 2^64)")
+    else:
+        vals = list(seed)
+        if len(vals) != B or not all(isinstance(v, int) and 0 <= v < 2 ** 64 for v in vals):
+            raise RuntimeError(f"seed: a sequence should hold {B} ints in [0, 2^64)")
+    vals = [v % 2 ** 64 for v in vals]
+    return torch.tensor([v - 2 ** 64 if v >= 2 ** 63 else v for v in vals], dtype=torch.int64).to(device)
+
+
 class Sampler:
     """`n_steps` of `kind` ('euler_ancestral': SDXL-Turbo, trailing spacing; 'euler': SDXL base, leading spacing with
     offset 1, `spacing='trailing'` selectable; 'lcm': SD 1.5 LCM-LoRA; 'ddim' and 'dpmpp_2m': the non-distilled
@@ -245,7 +271,13 @@ class Sampler:
     another Sampler.  The first sample(mask=...) captures a SECOND graph on the same buffers -- the UNet forward, then
     mixdq_sampler_step_masked -- which shares the first one's memory pool (neither keeps a tensor alive between
     replays, and they never run concurrently); the plain graph is not touched, and one Sampler serves text-to-image,
-    image-to-image and masked calls in any order."""
+    image-to-image and masked calls in any order.
+
+    sample(seed=...) makes the noise on the device (mixdq_randn_f32; the counter layout: include/mixdq_math.h).  Where
+    the schedule adds noise per step, the first seeded call captures one more graph -- the UNet forward, then
+    mixdq_sampler_step[_masked]_rng, which computes that noise in registers from a static seed buffer -- on the same
+    static buffers and in the same memory pool; calls with and without `seed` alternate in any order, every seed
+    replays the same graph, and the [n_steps, ...] noise buffer exists only once a call without `seed` was made."""
 
     def __init__(self, unet, kind, n_steps, guidance_scale=0.0, spacing=None, karras=False):
         self.unet = unet
@@ -255,6 +287,10 @@ class Sampler:
         self.rows_per_image = 2 if self.guidance_scale > 1.0 else 1
         self._graph = None
         self._graph_masked = None
+        self._graph_rng = None
+        self._graph_masked_rng = None
+        self._seeds = None
+        self._start = None
         self._key = None
 
     # ---- static buffers + capture ---------------------------------------------------------------------------
@@ -271,7 +307,7 @@ class Sampler:
         self._nhwc = nhwc
         self._x = nhwc(B, dtype=torch.float32)
         self._in = nhwc(R, dtype=torch.float16)
-        self._noise = nhwc(self.n_steps, B, dtype=torch.float32) if sch.uses_noise else None
+        self._noise = None            # the [n_steps, ...] step noise: made by the first capture that reads it
         self._coef = torch.from_numpy(sch.coef).to(dev)
         self._t_table = torch.from_numpy(sch.t_table).to(dev)
         self._t = torch.zeros((), dtype=torch.float32, device=dev)
@@ -284,16 +320,21 @@ class Sampler:
         self._ehs, self._added = _clone_args((encoder_hidden_states, added_cond_kwargs))
         self._key = self._shape_key(noise, encoder_hidden_states, added_cond_kwargs)
 
-    def _capture(self, noise, masked=False):
+    def _capture(self, noise, masked=False, rng=False):
         """Capture one step -- the UNet forward, then mixdq_sampler_step (masked: mixdq_sampler_step_masked, reading the
-        static z / noise0 / mask buffers made here) -- on the static buffers and return the graph."""
+        static z / noise0 / mask buffers made here; rng: the _rng entry points, reading the static seeds in place of
+        the step-noise buffer) -- on the static buffers and return the graph."""
         import torch
         from mixdq_amd import _C
         dev = noise.device
         B, C, H, W = noise.shape
         forward = getattr(self.unet.forward, "__wrapped__", self.unet.forward)   # (under hip_graph_opt: the eager one)
         n = B * C * H * W
-        if masked:
+        if self.schedule.uses_noise and not rng and self._noise is None:
+            self._noise = self._nhwc(self.n_steps, B, dtype=torch.float32)
+        rng_args = dict(seeds=self._seeds, n_image=C * H * W) if rng else {}
+        step_noise = None if rng else self._noise
+        if masked and not hasattr(self, "_z"):
             self._z = self._nhwc(B, dtype=torch.float32)
             self._noise0 = self._nhwc(B, dtype=torch.float32)
             self._mask = torch.zeros(B, H, W, dtype=torch.float32, device=dev)
@@ -315,10 +356,10 @@ class Sampler:
             elif masked:
                 _C.sampler_step_masked(self._x, eps, self._in, self._coef, self._t_table, self._step, self._t, self._z,
                                        self._noise0, self._mask, self._blend, self.guidance_scale, self.rows_per_image,
-                                       self._noise, channels=C, n=n)
+                                       step_noise, channels=C, n=n, **rng_args)
             else:
                 _C.sampler_step(self._x, eps, self._in, self._coef, self._t_table, self._step, self._t,
-                                self.guidance_scale, self.rows_per_image, self._noise, n=n)
+                                self.guidance_scale, self.rows_per_image, step_noise, n=n, **rng_args)
 
         self._reset(noise, None)
         side = torch.cuda.Stream(dev)
@@ -330,8 +371,9 @@ class Sampler:
         torch.cuda.current_stream(dev).wait_stream(side)
         self._step.zero_()
         graph = torch.cuda.CUDAGraph()
-        other = self._graph if masked else self._graph_masked
-        pool = {} if other is None else {"pool": other.pool()}
+        graphs = (self._graph, self._graph_masked, self._graph_rng, self._graph_masked_rng)
+        others = [g for g in graphs if g is not None]
+        pool = {"pool": others[0].pool()} if others else {}
         with torch.no_grad(), torch.cuda.graph(graph, **pool):
             one_step()
         return graph
@@ -380,11 +422,19 @@ class Sampler:
 
     # ---- the loop -------------------------------------------------------------------------------------------
     def sample(self, noise, encoder_hidden_states, added_cond_kwargs=None, step_noise=None, *, init_latents=None,
-               strength=None, mask=None):
+               strength=None, mask=None, seed=None):
         """noise [B, C, H, W] (unit variance; FP32 or FP16), encoder_hidden_states [R, T, D] FP16 (R = B, or 2B
         under guidance), added_cond_kwargs as the UNet takes them (R rows), step_noise [n_steps, B, C, H, W]: the
         noise each stochastic step adds (required where the schedule has a non-zero c: euler_ancestral and lcm with
-        more than one step; there is no random number generator in the kernel).  Returns the FP32 latents.
+        more than one step) -- unless `seed` is given.  Returns the FP32 latents.
+
+        `seed`: a Python int in [0, 2^64) (image b uses (seed + b) mod 2^64), a sequence of B ints, or an int64 GPU
+        tensor [B] (taken without host involvement).  The noise is then made on the device by Philox4x32-10 and
+        Box-Muller (mixdq_randn_f32; |z| <= 5.77): `noise` may be a shape (B, C, H, W) -- the start noise is stream 0
+        of the seeds, on encoder_hidden_states' device -- and step_noise must be None: the steps compute their noise
+        (stream 1, counter word = the absolute step index) in registers.  With `seed` and a noise TENSOR only the step
+        noise comes from the seed.  Image b's noise depends on its seed and shape only: not on B, its batch position or
+        the start step -- and it is not torch's or diffusers' noise for that seed.
 
         Image-to-image: `init_latents` (FP32 or FP16, noise's shape, multiplied by the VAE's scaling_factor: what
         VAEEncoder.encode returns) together with `strength` in (0, 1].  The run starts at step t0 =
@@ -400,6 +450,27 @@ class Sampler:
         is_strength_max); otherwise the start is image-to-image's.  The mask does not touch the start state."""
         import torch
         from mixdq_amd.quantize_sdxl import _copy_into
+        seeds = None
+        if seed is not None:
+            from mixdq_amd import _C
+            if step_noise is not None:
+                raise RuntimeError("Sampler.sample: with seed the steps make their own noise: step_noise must be None")
+            shape = tuple(noise.shape) if torch.is_tensor(noise) else tuple(int(d) for d in noise)
+            if len(shape) != 4:
+                raise RuntimeError("Sampler.sample: noise should be a [B, C, H, W] GPU tensor or, with seed, that "
+                                   "shape")
+            dev = encoder_hidden_states.device
+            seeds = seed_tensor(seed, shape[0], dev)
+            if self._seeds is None:
+                self._seeds = torch.zeros(shape[0], dtype=torch.int64, device=dev)
+            if tuple(self._seeds.shape) != (shape[0],) or self._seeds.device != dev:
+                raise RuntimeError("Sampler.sample: inputs differ in shape from those the step graph was captured for")
+            self._seeds.copy_(seeds)
+            if not torch.is_tensor(noise):
+                if self._start is None or tuple(self._start.shape) != shape:
+                    B, C, H, W = shape
+                    self._start = torch.empty((B, H, W, C), dtype=torch.float32, device=dev).permute(0, 3, 1, 2)
+                noise = _C.randn(shape, self._seeds, _C.RNG_STREAM_START, 0, out=self._start)
         if not (torch.is_tensor(noise) and noise.is_cuda and noise.dim() == 4):
             raise RuntimeError("Sampler.sample: noise should be a [B, C, H, W] GPU tensor")
         if mask is None:
@@ -425,9 +496,10 @@ class Sampler:
         R = noise.shape[0] * self.rows_per_image
         if encoder_hidden_states.shape[0] != R:
             raise RuntimeError(f"Sampler.sample: encoder_hidden_states should have {R} rows")
-        if self.schedule.uses_noise:
+        rng = seeds is not None and self.schedule.uses_noise
+        if self.schedule.uses_noise:                # (rng: the steps make it, and step_noise is None)
             want = (self.n_steps,) + tuple(noise.shape)
-            if step_noise is None or tuple(step_noise.shape) != want:
+            if not rng and (step_noise is None or tuple(step_noise.shape) != want):
                 raise RuntimeError(f"Sampler.sample: this schedule needs step_noise of shape {want}")
         elif step_noise is not None:
             raise RuntimeError("Sampler.sample: this schedule adds no noise: step_noise must be None")
@@ -435,14 +507,11 @@ class Sampler:
             self._setup(noise, encoder_hidden_states, added_cond_kwargs)
         elif self._shape_key(noise, encoder_hidden_states, added_cond_kwargs) != self._key:
             raise RuntimeError("Sampler.sample: inputs differ in shape from those the step graph was captured for")
-        if mask is None:
-            if self._graph is None:
-                self._graph = self._capture(noise)
-            graph = self._graph
-        else:
-            if self._graph_masked is None:
-                self._graph_masked = self._capture(noise, masked=True)
-            graph = self._graph_masked
+        name = "_graph" + ("_masked" if mask is not None else "") + ("_rng" if rng else "")
+        if getattr(self, name) is None:
+            setattr(self, name, self._capture(noise, masked=mask is not None, rng=rng))
+        graph = getattr(self, name)
+        if mask is not None:
             self._z.copy_(init_latents)             # (an FP16 tensor widens exactly)
             self._noise0.copy_(noise)
             self._mask.copy_(mask.reshape(self._mask.shape))
@@ -455,38 +524,53 @@ class Sampler:
             graph.replay()
         return self._x.clone()
 
-    def sample_image(self, vae, noise, encoder_hidden_states, added_cond_kwargs=None, step_noise=None):
+    def sample_image(self, vae, noise, encoder_hidden_states, added_cond_kwargs=None, step_noise=None, *, seed=None):
         """sample(), then `vae.decode` (a mixdq_amd.vae.VAEDecoder, eager or under hip_graph_opt) of its latents on
-        the same stream: nothing waits for the GPU in between.  Returns (FP32 latents, FP16 image [B, 3, 8H, 8W])."""
-        latents = self.sample(noise, encoder_hidden_states, added_cond_kwargs, step_noise)
+        the same stream: nothing waits for the GPU in between.  Returns (FP32 latents, FP16 image [B, 3, 8H, 8W]).
+        `seed` as in sample(): with it `noise` may be the latent shape, and seed -> image is this one call."""
+        latents = self.sample(noise, encoder_hidden_states, added_cond_kwargs, step_noise, seed=seed)
         return latents, vae.decode(latents)
 
+    def _latent_noise(self, latent_noise, latent_seed, noise, encoder_hidden_states):
+        """The VAE posterior's noise of img2img / inpaint: `latent_noise` as given; with `latent_seed` (as sample()'s
+        seed) stream 2 of those seeds at the latent shape; neither: None, the posterior's mode."""
+        import torch
+        from mixdq_amd import _C
+        if latent_seed is None:
+            return latent_noise
+        if latent_noise is not None:
+            raise RuntimeError("Sampler: latent_noise and latent_seed exclude each other")
+        shape = tuple(noise.shape) if torch.is_tensor(noise) else tuple(int(d) for d in noise)
+        return _C.randn(shape, seed_tensor(latent_seed, shape[0], encoder_hidden_states.device), _C.RNG_STREAM_VAE, 0)
+
     def img2img(self, enc, dec, image, noise, encoder_hidden_states, added_cond_kwargs=None, *, strength,
-                step_noise=None, latent_noise=None):
+                step_noise=None, latent_noise=None, seed=None, latent_seed=None):
         """Image to image on one stream: `enc.encode(image, latent_noise)` (a mixdq_amd.vae.VAEEncoder; latent_noise
         None: the posterior's mode), sample(init_latents=that, strength=strength), then `dec.decode` (a VAEDecoder) --
         either VAE eager or under hip_graph_opt, nothing waits for the GPU in between.  noise: [B, C, H/8, W/8], what
-        is added to the encoded image.  Returns (FP32 latents, FP16 image [B, 3, H, W])."""
-        z = enc.encode(image, latent_noise)
+        is added to the encoded image.  Returns (FP32 latents, FP16 image [B, 3, H, W]).  `seed` as in sample() (noise
+        may then be the latent shape); it does not touch the posterior, which stays the mode unless `latent_noise` or
+        `latent_seed` (stream 2 of those seeds) is given."""
+        z = enc.encode(image, self._latent_noise(latent_noise, latent_seed, noise, encoder_hidden_states))
         latents = self.sample(noise, encoder_hidden_states, added_cond_kwargs, step_noise, init_latents=z,
-                              strength=strength)
+                              strength=strength, seed=seed)
         return latents, dec.decode(latents)
 
     def inpaint(self, enc, dec, image, mask, noise, encoder_hidden_states, added_cond_kwargs=None, *, strength=None,
-                step_noise=None, latent_noise=None, mask_mode="nearest", composite=False):
+                step_noise=None, latent_noise=None, mask_mode="nearest", composite=False, seed=None, latent_seed=None):
         """Inpainting on one stream: `enc.encode(image, latent_noise)`, `_C.mask_to_latent(mask, mask_mode)` (mask at
         image resolution, [B, H, W] or [B, 1, H, W], uint8 / FP16 / FP32: set where repainted; 'nearest' is
         diffusers' downscaling, 'any' repaints every latent whose 8x8 block touches the mask),
         sample(init_latents=that, strength=strength, mask=that), `dec.decode` -- nothing waits for the GPU in between.
         strength None: the whole schedule from pure noise.  Returns (FP32 latents, FP16 image [B, 3, H, W]); with
         composite=True `image` must be uint8 and the second result is uint8: the decoded pixels where the mask is
-        set, the input's own bytes elsewhere (vae.composite_uint8)."""
+        set, the input's own bytes elsewhere (vae.composite_uint8).  `seed` / `latent_seed` as in img2img."""
         import torch
         from mixdq_amd import _C
         if composite and not (torch.is_tensor(image) and image.dtype == torch.uint8):
             raise RuntimeError("Sampler.inpaint: composite=True pastes into the input pixels: image should be uint8")
-        z = enc.encode(image, latent_noise)
+        z = enc.encode(image, self._latent_noise(latent_noise, latent_seed, noise, encoder_hidden_states))
         latents = self.sample(noise, encoder_hidden_states, added_cond_kwargs, step_noise, init_latents=z,
-                              strength=strength, mask=_C.mask_to_latent(mask, mask_mode))
+                              strength=strength, mask=_C.mask_to_latent(mask, mask_mode), seed=seed)
         decoded = dec.decode(latents)
         return latents, (_C.composite_u8(decoded, image, mask) if composite else decoded)
