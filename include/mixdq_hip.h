@@ -607,6 +607,67 @@ int mixdq_composite_u8(const void* decoded_f16, int64_t db, int64_t dc, int64_t 
                        mixdq_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Separable resampling (csrc/image.hip): resize, mask blur and the crop workflow's paste are one filter kernel over
+ * host-made tables.  No reference counterpart.  Arithmetic: include/mixdq_math.h (mixdq_resample_tap, mixdq_round_u8,
+ * mixdq_blend_u8, mixdq_to_uint8): the horizontal chain of every source row first, then the vertical chain, FP32 fused
+ * multiply-adds in tap order, zero weights skipped.
+ *
+ * Tables (device memory): xs int32 [Bt, Wd], wx float [Bt, Wd, Tx], ys int32 [Bt, Hd], wy float [Bt, Hd, Ty]; Bt is 1
+ * (one table for the batch) or B (one per image); 1 <= Tx, Ty <= 256.  Tap i of output column x reads source column
+ * min(max(xs[x] + i, 0), Ws - 1) with weight wx[x][i], rows likewise: a bad table gives wrong pixels, never an access
+ * out of bounds.
+ *
+ * mixdq_resample: src [B, C, Hs, Ws] of uint8 / FP16 / FP32 (MIXDQ_IMAGE_*), element (b, c, y, x) at src + (b * sb +
+ * c * sc + y * sh + x * sw) ELEMENTS, C in 1..4; dst dense [B, Hd, Wd, C].
+ *   src_mode  MIXDQ_RESAMPLE_SRC_VALUE  an element enters as (float)u (uint8) or as its value (FP16 / FP32)
+ *             MIXDQ_RESAMPLE_SRC_MASK   as 255.0f where it is set (u >= 128, v >= 0.5; NaN is not), 0.0f elsewhere
+ *   dst_kind  MIXDQ_RESAMPLE_DST_U8       uint8, mixdq_round_u8(acc)
+ *             MIXDQ_RESAMPLE_DST_U8_UNIT  uint8, mixdq_to_uint8(acc): a source in [-1, 1] (a decoded image) as pixels
+ *             MIXDQ_RESAMPLE_DST_F32      float, the accumulator itself
+ * Errors: negative sizes, C outside 1..4, Tx / Ty outside 1..256, Bt neither 1 nor B, an unknown dtype, src_mode or
+ * dst_kind, an output without a source (Hs * Ws == 0), null pointers: MIXDQ_ERR_INVALID_ARG; src not aligned to its
+ * element, a table or an F32 dst not to 4 bytes: MIXDQ_ERR_ALIGNMENT.  B * Hd * Wd == 0 writes nothing (and looks at
+ * no pointer).
+ *
+ * mixdq_resample_paste_u8: the way back of the crop workflow in one launch.  decoded: FP16 [B, 3, Hm, Wm] at element
+ * strides db, dc, dh, dw; out: uint8 [B, H, W, 3] dense, holding the original, updated IN PLACE; win: int32 [B, 4] =
+ * (x0, y0, x1, y1), image b's half-open window in out; tables as above with Wd = Wt, Hd = Ht (the largest window of
+ * the batch) indexed by the window-relative coordinate, the source extents being Wm and Hm.  For every pixel (x, y)
+ * of image b with x0 <= x < min(x1, x0 + Wt, W), rows likewise, and every c < 3:
+ *   out[b, y, x, c] = mixdq_blend_u8(m, mixdq_to_uint8(acc), out[b, y, x, c])
+ * mask [B, H, W] at element strides mb, mh, mw:
+ *   MIXDQ_PASTE_MASK_BINARY  any MIXDQ_IMAGE_* dtype, m = set ? 255 : 0
+ *   MIXDQ_PASTE_MASK_SOFT    uint8 only, m = the byte
+ * Nothing outside a window (or outside the image, whatever win says) is written; inside, a byte with m = 0 is written
+ * back unchanged; each byte is read and written by the same lane.
+ * Errors: as above, and SOFT with a mask that is not uint8: MIXDQ_ERR_INVALID_ARG; decoded or mask not aligned to its
+ * element, win or a table not to 4 bytes: MIXDQ_ERR_ALIGNMENT.  B * Ht * Wt == 0 or B * H * W == 0 writes nothing.
+ *
+ * mixdq_mask_bbox: mask [B, H, W] (MIXDQ_IMAGE_*, strides sb, sh, sw) -> out int32 [B, 4] = (x0, y0, x1, y1), the
+ * half-open bounding box of the set pixels, (0, 0, 0, 0) where none is set.  One workgroup per image; not a hot path
+ * (it runs once, in front of a host read-back).  Errors: negative sizes, an unknown dtype, null pointers:
+ * MIXDQ_ERR_INVALID_ARG; mask not aligned to its element, out not to 4 bytes: MIXDQ_ERR_ALIGNMENT.  B * H * W == 0
+ * writes nothing. */
+#define MIXDQ_RESAMPLE_SRC_VALUE 0
+#define MIXDQ_RESAMPLE_SRC_MASK 1
+#define MIXDQ_RESAMPLE_DST_U8 0
+#define MIXDQ_RESAMPLE_DST_U8_UNIT 1
+#define MIXDQ_RESAMPLE_DST_F32 2
+#define MIXDQ_PASTE_MASK_BINARY 0
+#define MIXDQ_PASTE_MASK_SOFT 1
+#define MIXDQ_RESAMPLE_MAX_TAPS 256
+int mixdq_resample(const void* src, int dtype, int64_t sb, int64_t sc, int64_t sh, int64_t sw, int src_mode, void* dst,
+                   int dst_kind, const int32_t* xs, const float* wx, int Tx, const int32_t* ys, const float* wy, int Ty,
+                   int Bt, int B, int C, int Hs, int Ws, int Hd, int Wd, mixdq_stream_t stream);
+int mixdq_resample_paste_u8(const void* decoded_f16, int64_t db, int64_t dc, int64_t dh, int64_t dw, int Hm, int Wm,
+                            uint8_t* out, const void* mask, int mask_dtype, int64_t mb, int64_t mh, int64_t mw,
+                            int mask_mode, const int32_t* win, const int32_t* xs, const float* wx, int Tx,
+                            const int32_t* ys, const float* wy, int Ty, int Bt, int Ht, int Wt, int B, int H, int W,
+                            mixdq_stream_t stream);
+int mixdq_mask_bbox(const void* mask, int dtype, int64_t sb, int64_t sh, int64_t sw, int32_t* out, int B, int H, int W,
+                    mixdq_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Sampler step: classifier-free guidance + scheduler update + the UNet's next input, and the step state kept on
  * the device, so that a sampling loop is N replays of one captured graph with nothing from the host in between.
  * No reference counterpart: the reference reaches the loop only through diffusers' pipeline call in its run()

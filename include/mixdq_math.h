@@ -311,4 +311,31 @@ MIXDQ_HD float mixdq_rng_normal_at(uint64_t seed, uint64_t e, uint32_t step, uin
   return (e & 1u) ? z1 : z0;
 }
 
+/* ---- separable resampling (mixdq_resample, mixdq_resample_paste_u8, csrc/image.hip).  One output value is two
+ * chains of explicit fused multiply-adds over host-made FP32 weight tables, each starting at +0: for every source row
+ * of its vertical window the horizontal chain over taps i = 0 .. Tx-1 in order (an FP32 value, never rounded to 8
+ * bits), then the vertical chain of those values over j = 0 .. Ty-1 in order.  A tap whose weight is zero (either
+ * sign) is SKIPPED, not multiplied: the zero padding of a shorter table row never meets a NaN or inf of a float
+ * source.  Source elements enter as (float)u for uint8 (pixel scale 0 .. 255), as their value for FP16 / FP32, and in
+ * MASK mode as 255.0f where the element is set by mixdq_mask_to_latent's rule and 0.0f elsewhere. */
+MIXDQ_HD float mixdq_resample_tap(float acc, float w, float v) {
+  return (w == 0.0f) ? acc : __builtin_fmaf(w, v, acc);
+}
+
+/* An accumulator on the pixel scale as a byte: NaN and everything <= 0 is 0, everything >= 255 is 255, between them
+ * rintf (half to even). */
+MIXDQ_HD uint8_t mixdq_round_u8(float a) {
+  if (a != a) return 0;
+  if (a <= 0.0f) return 0;
+  if (a >= 255.0f) return 255;
+  return (uint8_t)(int)__builtin_rintf(a);
+}
+
+/* The feathered paste, in integers: (m*d + (255-m)*o + 127) / 255 -- the nearest integer to the exact quotient
+ * (255 is odd: the remainder is never half of it, no tie exists).  m = 0 gives o, m = 255 gives d. */
+MIXDQ_HD uint8_t mixdq_blend_u8(uint8_t m, uint8_t d, uint8_t o) {
+  const uint32_t s = (uint32_t)m * d + (uint32_t)(255u - m) * o + 127u;
+  return (uint8_t)(s / 255u);
+}
+
 #endif /* MIXDQ_MATH_H_ */

@@ -1758,3 +1758,101 @@ def composite_u8(decoded, original, mask):
                                        _stream())
     _status(code, "composite_u8")
     return out.permute(0, 3, 1, 2)
+
+
+_lib.mixdq_resample.argtypes = ([_vp, _i32] + [_i64] * 4 + [_i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32]
+                                + [_i32] * 7 + [_vp])
+_lib.mixdq_resample.restype = _i32
+_lib.mixdq_resample_paste_u8.argtypes = ([_vp] + [_i64] * 4 + [_i32, _i32, _vp, _vp, _i32] + [_i64] * 3
+                                         + [_i32, _vp, _vp, _vp, _i32, _vp, _vp, _i32] + [_i32] * 6 + [_vp])
+_lib.mixdq_resample_paste_u8.restype = _i32
+_lib.mixdq_mask_bbox.argtypes = [_vp, _i32, _i64, _i64, _i64, _vp, _i32, _i32, _i32, _vp]
+_lib.mixdq_mask_bbox.restype = _i32
+RESAMPLE_DST = {"u8": (0, torch.uint8), "u8_unit": (1, torch.uint8), "f32": (2, torch.float32)}   # MIXDQ_RESAMPLE_DST_*
+RESAMPLE_MAX_TAPS = 256                                                   # MIXDQ_RESAMPLE_MAX_TAPS
+
+
+def _tables(xs, wx, ys, wy, B, Hd, Wd, dev, what):
+    """The four device tables of a resampling launch as (Bt, Tx, Ty): xs int32 [Bt, Wd], wx fp32 [Bt, Wd, Tx], ys int32
+    [Bt, Hd], wy fp32 [Bt, Hd, Ty], dense, Bt 1 or B."""
+    for tab, dt, nd in ((xs, torch.int32, 2), (wx, torch.float32, 3), (ys, torch.int32, 2), (wy, torch.float32, 3)):
+        _check(torch.is_tensor(tab) and tab.device == dev and tab.dtype == dt and tab.dim() == nd
+               and tab.is_contiguous(), f"{what}: tables should be dense int32 [Bt, n] / fp32 [Bt, n, T] tensors on "
+               "the source's device")
+    Bt = xs.shape[0]
+    _check(Bt in (1, B) and wx.shape[0] == Bt and ys.shape[0] == Bt and wy.shape[0] == Bt,
+           f"{what}: tables should have one leading entry, or one per image")
+    _check(xs.shape[1] == Wd and wx.shape[1] == Wd and ys.shape[1] == Hd and wy.shape[1] == Hd,
+           f"{what}: tables should have one row per output column / row")
+    return Bt, wx.shape[2], wy.shape[2]
+
+
+def resample(src, xs, wx, ys, wy, out="u8", mask=False):
+    """The separable filter (mixdq_resample): src [B, C <= 4, Hs, Ws] uint8 / fp16 / fp32 of ANY strides, tables as
+    mixdq_amd.image.resample_table / gaussian_table make them (xs int32 [Bt, Wd], wx fp32 [Bt, Wd, Tx], ys int32
+    [Bt, Hd], wy fp32 [Bt, Hd, Ty]; Bt 1 or B) -> [B, C, Hd, Wd] in channels-last storage: 'u8' (mixdq_round_u8),
+    'u8_unit' (mixdq_to_uint8: a source in [-1, 1]) or 'f32' (the accumulator).  mask=True: an element enters as 255
+    where it is set (mask_to_latent's rule) and 0 elsewhere.  Arithmetic: include/mixdq_math.h mixdq_resample_tap."""
+    _check(torch.is_tensor(src) and src.is_cuda and src.dim() == 4 and src.dtype in IMAGE_DTYPES,
+           "resample: src should be a 4-D uint8, fp16 or fp32 GPU tensor")
+    _check(out in RESAMPLE_DST, f"resample: out should be one of {tuple(RESAMPLE_DST)}")
+    B, C, Hs, Ws = src.shape
+    _check(1 <= C <= 4, "resample: src should have 1 to 4 channels")
+    _check(torch.is_tensor(xs) and torch.is_tensor(ys) and xs.dim() == 2 and ys.dim() == 2, "resample: xs / ys should "
+           "be 2-D tensors")
+    Hd, Wd = ys.shape[1], xs.shape[1]
+    Bt, Tx, Ty = _tables(xs, wx, ys, wy, B, Hd, Wd, src.device, "resample")
+    kind, dt = RESAMPLE_DST[out]
+    dst = torch.empty((B, Hd, Wd, C), dtype=dt, device=src.device)
+    sb, sc, sh, sw = src.stride()
+    with torch.cuda.device(src.device):
+        code = _lib.mixdq_resample(src.data_ptr(), IMAGE_DTYPES[src.dtype], sb, sc, sh, sw, 1 if mask else 0,
+                                   dst.data_ptr(), kind, xs.data_ptr(), wx.data_ptr(), Tx, ys.data_ptr(), wy.data_ptr(),
+                                   Ty, Bt, B, C, Hs, Ws, Hd, Wd, _stream())
+    _status(code, "resample")
+    return dst.permute(0, 3, 1, 2)
+
+
+def resample_paste_u8(decoded, out, mask, win, xs, wx, ys, wy, soft=False):
+    """The crop workflow's way back, one launch, IN PLACE (mixdq_resample_paste_u8): decoded fp16 [B, 3, Hm, Wm] (any
+    strides) is resized into window win[b] = (x0, y0, x1, y1) (int32 [B, 4] on the device) of `out`, uint8
+    [B, 3, H, W] in channels-last storage holding the original, as mixdq_blend_u8(m, to_uint8(resized), out); mask
+    [B, H, W] or [B, 1, H, W] of any strides: soft=True its uint8 bytes are m, otherwise m = 255 where it is set.
+    Tables (window-relative, [Bt, Wt] / [Bt, Ht] with Wt, Ht the largest window) as in resample.  Returns `out`."""
+    _check(torch.is_tensor(decoded) and decoded.is_cuda and decoded.dtype == torch.float16 and decoded.dim() == 4
+           and decoded.shape[1] == 3, "resample_paste_u8: decoded should be an fp16 [B, 3, Hm, Wm] GPU tensor")
+    B, _, Hm, Wm = decoded.shape
+    _check(torch.is_tensor(out) and out.device == decoded.device and out.dtype == torch.uint8 and out.dim() == 4
+           and out.shape[0] == B and out.shape[1] == 3 and out.permute(0, 2, 3, 1).is_contiguous(),
+           "resample_paste_u8: out should be a uint8 [B, 3, H, W] tensor in channels-last storage on decoded's device")
+    H, W = out.shape[2], out.shape[3]
+    mB, mH, mW, mst = _mask3(mask, "resample_paste_u8")
+    _check(mask.device == decoded.device and (mB, mH, mW) == (B, H, W),
+           "resample_paste_u8: mask should have out's batch, height and width and be on its device")
+    _check(not soft or mask.dtype == torch.uint8, "resample_paste_u8: a soft mask should be uint8")
+    _check(torch.is_tensor(win) and win.device == decoded.device and win.dtype == torch.int32
+           and tuple(win.shape) == (B, 4) and win.is_contiguous(), "resample_paste_u8: win should be an int32 [B, 4] "
+           "tensor on decoded's device")
+    _check(torch.is_tensor(xs) and torch.is_tensor(ys) and xs.dim() == 2 and ys.dim() == 2, "resample_paste_u8: xs / ys "
+           "should be 2-D tensors")
+    Ht, Wt = ys.shape[1], xs.shape[1]
+    Bt, Tx, Ty = _tables(xs, wx, ys, wy, B, Ht, Wt, decoded.device, "resample_paste_u8")
+    with torch.cuda.device(decoded.device):
+        code = _lib.mixdq_resample_paste_u8(decoded.data_ptr(), *decoded.stride(), Hm, Wm, out.data_ptr(),
+                                            mask.data_ptr(), IMAGE_DTYPES[mask.dtype], *mst, 1 if soft else 0,
+                                            win.data_ptr(), xs.data_ptr(), wx.data_ptr(), Tx, ys.data_ptr(),
+                                            wy.data_ptr(), Ty, Bt, Ht, Wt, B, H, W, _stream())
+    _status(code, "resample_paste_u8")
+    return out
+
+
+def mask_bbox(mask):
+    """The bounding boxes of a mask's set pixels (mixdq_mask_bbox): mask [B, H, W] or [B, 1, H, W], uint8 / fp16 / fp32
+    of any strides -> int32 [B, 4] = (x0, y0, x1, y1) on the device, half-open, (0, 0, 0, 0) where nothing is set."""
+    B, H, W, (sb, sh, sw) = _mask3(mask, "mask_bbox")
+    out = torch.zeros((B, 4), dtype=torch.int32, device=mask.device)
+    with torch.cuda.device(mask.device):
+        code = _lib.mixdq_mask_bbox(mask.data_ptr(), IMAGE_DTYPES[mask.dtype], sb, sh, sw, out.data_ptr(), B, H, W,
+                                    _stream())
+    _status(code, "mask_bbox")
+    return out

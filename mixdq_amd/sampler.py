@@ -557,20 +557,78 @@ class Sampler:
         return latents, dec.decode(latents)
 
     def inpaint(self, enc, dec, image, mask, noise, encoder_hidden_states, added_cond_kwargs=None, *, strength=None,
-                step_noise=None, latent_noise=None, mask_mode="nearest", composite=False, seed=None, latent_seed=None):
+                step_noise=None, latent_noise=None, mask_mode="nearest", composite=False, seed=None, latent_seed=None,
+                crop=None, crop_pad=32, mask_blur=0.0, resample="lanczos3"):
         """Inpainting on one stream: `enc.encode(image, latent_noise)`, `_C.mask_to_latent(mask, mask_mode)` (mask at
         image resolution, [B, H, W] or [B, 1, H, W], uint8 / FP16 / FP32: set where repainted; 'nearest' is
         diffusers' downscaling, 'any' repaints every latent whose 8x8 block touches the mask),
         sample(init_latents=that, strength=strength, mask=that), `dec.decode` -- nothing waits for the GPU in between.
         strength None: the whole schedule from pure noise.  Returns (FP32 latents, FP16 image [B, 3, H, W]); with
         composite=True `image` must be uint8 and the second result is uint8: the decoded pixels where the mask is
-        set, the input's own bytes elsewhere (vae.composite_uint8).  `seed` / `latent_seed` as in img2img."""
+        set, the input's own bytes elsewhere (vae.composite_uint8).  `seed` / `latent_seed` as in img2img.
+
+        `crop` ("only the masked region"): 'auto' (per image: image.mask_bbox -- the one host read-back -- grown by
+        `crop_pad` and brought to the model's aspect by image.crop_region), one integer (x0, y0, x1, y1) or B of them.
+        `image` is then uint8 of ANY height and width, `mask` has its size, composite must be True, and `noise` (or
+        its shape, with seed) fixes the model size as 8 x its extent.  The window is resized to the model size
+        (`resample`: 'bilinear' / 'bicubic' / 'lanczos3'; the mask: bilinear of its binarisation), inpainted there,
+        and the decode is resized back and pasted into the window of the untouched original (image.paste) under the
+        mask -- blurred by `mask_blur` pixels (image.blur_mask) where that is > 0.  Returns (FP32 latents, uint8
+        [B, 3, H, W] at the ORIGINAL size); every pixel outside the window, and every pixel whose paste weight is 0,
+        is the input's own byte.  After the tables are uploaded (cached by sizes, boxes and filter) nothing comes from
+        the host."""
         import torch
         from mixdq_amd import _C
         if composite and not (torch.is_tensor(image) and image.dtype == torch.uint8):
             raise RuntimeError("Sampler.inpaint: composite=True pastes into the input pixels: image should be uint8")
+        if crop is not None:
+            return self._inpaint_crop(enc, dec, image, mask, noise, encoder_hidden_states, added_cond_kwargs,
+                                      strength=strength, step_noise=step_noise, latent_noise=latent_noise,
+                                      mask_mode=mask_mode, composite=composite, seed=seed, latent_seed=latent_seed,
+                                      crop=crop, crop_pad=crop_pad, mask_blur=mask_blur, resample=resample)
         z = enc.encode(image, self._latent_noise(latent_noise, latent_seed, noise, encoder_hidden_states))
         latents = self.sample(noise, encoder_hidden_states, added_cond_kwargs, step_noise, init_latents=z,
                               strength=strength, mask=_C.mask_to_latent(mask, mask_mode), seed=seed)
         decoded = dec.decode(latents)
         return latents, (_C.composite_u8(decoded, image, mask) if composite else decoded)
+
+    def _inpaint_crop(self, enc, dec, image, mask, noise, encoder_hidden_states, added_cond_kwargs, *, strength,
+                      step_noise, latent_noise, mask_mode, composite, seed, latent_seed, crop, crop_pad, mask_blur,
+                      resample):
+        """inpaint(crop=...): resize the window to the model size, inpaint there, paste the decode back."""
+        import torch
+        from mixdq_amd import _C
+        from mixdq_amd import image as I
+        if not (torch.is_tensor(image) and image.dtype == torch.uint8 and image.dim() == 4 and image.shape[1] == 3):
+            raise RuntimeError("Sampler.inpaint: crop pastes into the input pixels: image should be uint8 [B, 3, H, W]")
+        if not composite:
+            raise RuntimeError("Sampler.inpaint: crop returns the pasted pixels: composite should be True")
+        if resample not in I.FILTERS:
+            raise RuntimeError(f"Sampler.inpaint: resample should be one of {tuple(I.FILTERS)}")
+        mask_blur = float(mask_blur)
+        if not mask_blur >= 0.0:
+            raise RuntimeError("Sampler.inpaint: mask_blur should be >= 0")
+        shape = tuple(noise.shape) if torch.is_tensor(noise) else tuple(int(d) for d in noise)
+        if len(shape) != 4:
+            raise RuntimeError("Sampler.inpaint: noise should be a [B, C, h, w] GPU tensor or, with seed, that shape")
+        B, H, W = image.shape[0], image.shape[2], image.shape[3]
+        model_hw = (8 * shape[2], 8 * shape[3])
+        if not (torch.is_tensor(mask) and mask.dim() in (3, 4) and mask.shape[0] == B
+                and tuple(mask.shape[-2:]) == (H, W)):
+            raise RuntimeError("Sampler.inpaint: with crop the mask should have the image's batch, height and width")
+        if isinstance(crop, str):
+            if crop != "auto":
+                raise RuntimeError("Sampler.inpaint: crop should be 'auto', one (x0, y0, x1, y1) or one per image")
+            boxes = tuple(I.crop_region(bb, (H, W), model_hw, crop_pad) for bb in I.mask_bbox(mask))
+        else:
+            boxes = I._boxes(crop, B, H, W, "Sampler.inpaint", integer=True)
+        mask3 = mask if mask.dim() == 3 else mask[:, 0]
+        small = I.resize(image, model_hw, boxes, resample)
+        small_mask = I.resize(mask3[:, None], model_hw, boxes, "bilinear", mask=True)[:, 0]
+        z = enc.encode(small, self._latent_noise(latent_noise, latent_seed, noise, encoder_hidden_states))
+        latents = self.sample(noise, encoder_hidden_states, added_cond_kwargs, step_noise, init_latents=z,
+                              strength=strength, mask=_C.mask_to_latent(small_mask, mask_mode), seed=seed)
+        decoded = dec.decode(latents)
+        soft = mask_blur > 0.0
+        return latents, I.paste(decoded, image, I.blur_mask(mask3, mask_blur) if soft else mask3, boxes, resample,
+                                soft=soft)
