@@ -563,7 +563,27 @@ int mixdq_embed_tokens_f16(const int32_t* ids, const void* tok_f16, const void* 
  *   noise == null:  z = f32(mean) * scaling_factor                  (the mode of the posterior)
  * every operation one FP32 rounding, never contracted (include/mixdq_math.h: mixdq_vae_latent[_mode]).
  * L % 4 == 0 and 16-byte aligned pointers: MIXDQ_ERR_ALIGNMENT otherwise; null moments / z, pixels < 0, L < 1:
- * MIXDQ_ERR_INVALID_ARG.  pixels == 0 writes nothing. */
+ * MIXDQ_ERR_INVALID_ARG.  pixels == 0 writes nothing.
+ *
+ * mixdq_image_to_nhwc8_f16_masked: the same ingest with the masked pixels blanked, for the 9-channel inpainting
+ * checkpoints' "masked image".  mask: [B, H, W] at image resolution, dtype code and element strides mb, mh, mw as
+ * mixdq_composite_u8 takes them, SET by the rule below (uint8 u >= 128, floats v >= 0.5, NaN not set):
+ *   out[b, y, x, c] = set(mask[b, y, x]) ? +0.0 : ingest(img[b, c, y, x])      c < C;   channels C..7 zero
+ * with `ingest` the arithmetic above, unchanged; one 16-byte store per pixel.  It is diffusers'
+ * init_image * (mask < 0.5) in model space: a blanked pixel is mid-grey (0.0), not black (-1.0).  It differs from that
+ * product only where the product is not +0.0 under a set mask: diffusers leaves -0.0 for a negative source and NaN
+ * for a non-finite one, this kernel stores +0.0.  An all-clear mask gives mixdq_image_to_nhwc8_f16's bits.
+ * Errors: as mixdq_image_to_nhwc8_f16, and a mask dtype code outside 0..2 or a null mask: MIXDQ_ERR_INVALID_ARG; mask
+ * not aligned to its element: MIXDQ_ERR_ALIGNMENT.  B * H * W == 0 writes nothing (and looks at no pointer).
+ *
+ * mixdq_inpaint_cond_f16: the conditioning channels of a 9-channel inpainting UNet in the padded 8-channel form
+ * SDXLUNet.cond_term takes.  mask_lat: FP32 [B, h, w] dense (mixdq_mask_to_latent's output, or a soft mask: the values
+ * pass through), zl: FP32 [B, h, w, L] dense (mixdq_vae_latent_sample's output for the blanked image), out: FP16
+ * [B, h, w, 8]; `pixels` = B * h * w.
+ *   out[p, 0] = f16_rn(mask_lat[p]);   out[p, 1 + l] = f16_rn(zl[p, l]), l < L;   out[p, L + 1 .. 7] = +0.0
+ * One 16-byte store per latent pixel.  1 <= L <= 7.
+ * Errors: pixels < 0, L outside 1..7, null pointers: MIXDQ_ERR_INVALID_ARG; out not 16-byte aligned, mask_lat or zl
+ * not 4-byte aligned: MIXDQ_ERR_ALIGNMENT.  pixels == 0 writes nothing (and looks at no pointer). */
 #define MIXDQ_IMAGE_U8 0
 #define MIXDQ_IMAGE_F16 1
 #define MIXDQ_IMAGE_F32 2
@@ -571,6 +591,11 @@ int mixdq_image_to_nhwc8_f16(const void* img, int dtype, int64_t sb, int64_t sc,
                              void* out_f16, int B, int C, int H, int W, mixdq_stream_t stream);
 int mixdq_vae_latent_sample(const void* moments_f16, const float* noise_or_null, float* z, int64_t pixels, int L,
                             float scaling_factor, mixdq_stream_t stream);
+int mixdq_image_to_nhwc8_f16_masked(const void* img, int dtype, int64_t sb, int64_t sc, int64_t sh, int64_t sw,
+                                    const void* mask, int mask_dtype, int64_t mb, int64_t mh, int64_t mw,
+                                    void* out_f16, int B, int C, int H, int W, mixdq_stream_t stream);
+int mixdq_inpaint_cond_f16(const float* mask_lat, const float* zl, void* out_f16, int64_t pixels, int L,
+                           mixdq_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Inpainting around the VAE (csrc/vae.hip).  No reference counterpart.  A mask value is SET (repaint) by
@@ -647,7 +672,18 @@ int mixdq_composite_u8(const void* decoded_f16, int64_t db, int64_t dc, int64_t 
  * half-open bounding box of the set pixels, (0, 0, 0, 0) where none is set.  One workgroup per image; not a hot path
  * (it runs once, in front of a host read-back).  Errors: negative sizes, an unknown dtype, null pointers:
  * MIXDQ_ERR_INVALID_ARG; mask not aligned to its element, out not to 4 bytes: MIXDQ_ERR_ALIGNMENT.  B * H * W == 0
- * writes nothing. */
+ * writes nothing.
+ *
+ * mixdq_mask_dilate_u8: a mask grown by `radius` pixels (front ends' "grow mask by").  mask [B, H, W] (MIXDQ_IMAGE_*,
+ * element strides sb, sh, sw) -> out uint8 [B, H, W] dense:
+ *   out[b, y, x] = 255 where any pixel of rows max(y - r, 0) .. min(y + r, H - 1), columns max(x - r, 0) ..
+ *                  min(x + r, W - 1) of image b is set (u >= 128, v >= 0.5; NaN is not), 0 elsewhere
+ * -- the square window of PIL's ImageFilter.MaxFilter(2r + 1) on the binarised mask, exact; a window never reaches
+ * into another image of the batch.  0 <= radius <= 255; radius 0 is the binarisation, a radius beyond the image is
+ * legal.  Two launches: rows (mask -> scratch), then columns (scratch -> out); scratch: uint8 [B, H, W] of the
+ * caller's, overwritten, distinct from out.  Not a hot path (once per call, in front of the whole pipeline).
+ * Errors: negative sizes, an unknown dtype, radius outside 0..255, null pointers: MIXDQ_ERR_INVALID_ARG; mask not
+ * aligned to its element: MIXDQ_ERR_ALIGNMENT.  B * H * W == 0 writes nothing (and looks at no pointer). */
 #define MIXDQ_RESAMPLE_SRC_VALUE 0
 #define MIXDQ_RESAMPLE_SRC_MASK 1
 #define MIXDQ_RESAMPLE_DST_U8 0
@@ -666,6 +702,8 @@ int mixdq_resample_paste_u8(const void* decoded_f16, int64_t db, int64_t dc, int
                             mixdq_stream_t stream);
 int mixdq_mask_bbox(const void* mask, int dtype, int64_t sb, int64_t sh, int64_t sw, int32_t* out, int B, int H, int W,
                     mixdq_stream_t stream);
+int mixdq_mask_dilate_u8(const void* mask, int dtype, int64_t sb, int64_t sh, int64_t sw, uint8_t* scratch,
+                         uint8_t* out, int B, int H, int W, int radius, mixdq_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Sampler step: classifier-free guidance + scheduler update + the UNet's next input, and the step state kept on
@@ -762,6 +800,7 @@ int mixdq_sampler_step_2m_masked(float* x, const void* eps_f16, void* in_f16, fl
 #define MIXDQ_RNG_STREAM_START 0   /* start noise; the img2img / inpainting noise */
 #define MIXDQ_RNG_STREAM_STEP 1    /* what a stochastic sampler step adds */
 #define MIXDQ_RNG_STREAM_VAE 2     /* the VAE posterior's noise */
+#define MIXDQ_RNG_STREAM_COND 3    /* the posterior's noise of the blanked image a 9-channel inpainting UNet reads */
 
 /* out[b * n_image + e] for b < B, e < n_image, dense.  Any n_image >= 1; out 16-byte aligned when n_image % 4 == 0
  * (16-byte stores), 4-byte otherwise.  The seeds are read by the kernel: a captured graph serves every seed.

@@ -1408,6 +1408,7 @@ _lib.mixdq_randn_f32.restype = _i32
 _lib.mixdq_rng_normals_from_bits.argtypes = [_vp, _vp, _i64, _vp]
 _lib.mixdq_rng_normals_from_bits.restype = _i32
 RNG_STREAM_START, RNG_STREAM_STEP, RNG_STREAM_VAE = 0, 1, 2               # include/mixdq_hip.h MIXDQ_RNG_STREAM_*
+RNG_STREAM_COND = 3                                                       # ... the blanked image's posterior (9-channel UNets)
 
 
 def _check_seeds(seeds, B, what):
@@ -1431,7 +1432,7 @@ def randn(shape, seeds, stream=0, step=0, out=None):
     GPU tensor [B], one per image, its bits read as unsigned.  Element e = (h * W + w) * C + c of image b is lane e & 3
     of Philox4x32-10 with key seeds[b] and counter (e >> 2, step, stream) through Box-Muller (include/mixdq_math.h):
     an image's values depend on its seed and shape only.  stream: RNG_STREAM_START (0), _STEP (1, with `step` the index
-    of the sampler step that adds it), _VAE (2).  out: a dense channels-last fp32 tensor of that shape to fill."""
+    of the sampler step that adds it), _VAE (2), _COND (3).  out: a dense channels-last fp32 tensor of that shape to fill."""
     _check(len(shape) == 4 and all(int(d) >= 1 for d in shape[1:]) and int(shape[0]) >= 0,
            "randn: shape should be (B, C, H, W)")
     B, C, H, W = (int(d) for d in shape)
@@ -1661,22 +1662,39 @@ _lib.mixdq_image_to_nhwc8_f16.argtypes = [_vp, _i32, _i64, _i64, _i64, _i64, _vp
 _lib.mixdq_image_to_nhwc8_f16.restype = _i32
 _lib.mixdq_vae_latent_sample.argtypes = [_vp, _vp, _vp, _i64, _i32, ctypes.c_float, _vp]
 _lib.mixdq_vae_latent_sample.restype = _i32
+_lib.mixdq_image_to_nhwc8_f16_masked.argtypes = ([_vp, _i32] + [_i64] * 4 + [_vp, _i32] + [_i64] * 3
+                                                 + [_vp, _i32, _i32, _i32, _i32, _vp])
+_lib.mixdq_image_to_nhwc8_f16_masked.restype = _i32
+_lib.mixdq_inpaint_cond_f16.argtypes = [_vp, _vp, _vp, _i64, _i32, _vp]
+_lib.mixdq_inpaint_cond_f16.restype = _i32
 IMAGE_DTYPES = {torch.uint8: 0, torch.float16: 1, torch.float32: 2}      # include/mixdq_hip.h MIXDQ_IMAGE_*
 
 
-def image_to_nhwc8_f16(image):
+def image_to_nhwc8_f16(image, mask=None):
     """The VAE encoder's ingest (mixdq_image_to_nhwc8_f16): image [B, C <= 8, H, W], uint8, fp16 or fp32, of ANY
     strides (NCHW, channels-last, a slice: the kernel reads them) -> fp16 [B, 8, H, W] in channels-last storage,
-    channels C..7 zero.  uint8: f16(f32(u) * f32(2/255) - 1), which is f16(u / 127.5 - 1); floats: f16(v), no clamp."""
+    channels C..7 zero.  uint8: f16(f32(u) * f32(2/255) - 1), which is f16(u / 127.5 - 1); floats: f16(v), no clamp.
+    `mask` ([B, H, W] or [B, 1, H, W] at the image's size, uint8 / fp16 / fp32 of any strides, set as in
+    mask_to_latent): the pixels under it are stored as +0.0 in every channel (mixdq_image_to_nhwc8_f16_masked) --
+    diffusers' init_image * (mask < 0.5), the "masked image" a 9-channel inpainting UNet is conditioned on."""
     _check(torch.is_tensor(image) and image.is_cuda and image.dim() == 4 and image.dtype in IMAGE_DTYPES,
            "image should be a 4-D uint8, fp16 or fp32 GPU tensor")
     B, C, H, W = image.shape
     _check(1 <= C <= 8, "image should have 1 to 8 channels")
+    if mask is not None:
+        mB, mH, mW, mst = _mask3(mask, "image_to_nhwc8_f16")
+        _check(mask.device == image.device and (mB, mH, mW) == (B, H, W),
+               "image_to_nhwc8_f16: mask should have the image's batch, height and width and be on its device")
     out = torch.empty((B, H, W, 8), dtype=torch.float16, device=image.device)
     sb, sc, sh, sw = image.stride()
     with torch.cuda.device(image.device):
-        code = _lib.mixdq_image_to_nhwc8_f16(image.data_ptr(), IMAGE_DTYPES[image.dtype], sb, sc, sh, sw,
-                                             out.data_ptr(), B, C, H, W, _stream())
+        if mask is None:
+            code = _lib.mixdq_image_to_nhwc8_f16(image.data_ptr(), IMAGE_DTYPES[image.dtype], sb, sc, sh, sw,
+                                                 out.data_ptr(), B, C, H, W, _stream())
+        else:
+            code = _lib.mixdq_image_to_nhwc8_f16_masked(image.data_ptr(), IMAGE_DTYPES[image.dtype], sb, sc, sh, sw,
+                                                        mask.data_ptr(), IMAGE_DTYPES[mask.dtype], *mst,
+                                                        out.data_ptr(), B, C, H, W, _stream())
     _status(code, "image_to_nhwc8_f16")
     return out.permute(0, 3, 1, 2)
 
@@ -1735,6 +1753,27 @@ def mask_to_latent(mask, mode="nearest"):
                                          MASK_MODES[mode], _stream())
     _status(code, "mask_to_latent")
     return out
+
+
+def inpaint_cond(mask_lat, zl):
+    """The conditioning channels of a 9-channel inpainting UNet (mixdq_inpaint_cond_f16): mask_lat fp32 [B, h, w] or
+    [B, 1, h, w] dense (what mask_to_latent returns, or a soft mask: the values pass through), zl fp32 [B, L, h, w] in
+    channels-last storage (what VAEEncoder.encode returns for the blanked image), 1 <= L <= 7 -> fp16 [B, 8, h, w] in
+    channels-last storage: channel 0 f16(mask), channels 1..L f16(zl), the rest zero.  What Sampler.sample(cond=) and
+    SDXLUNet.cond_term take."""
+    _check(torch.is_tensor(zl) and zl.is_cuda and zl.dtype == torch.float32 and zl.dim() == 4
+           and zl.permute(0, 2, 3, 1).is_contiguous(),
+           "inpaint_cond: zl should be a channels-last fp32 [B, L, h, w] GPU tensor")
+    B, L, h, w = zl.shape
+    _check(1 <= L <= 7, "inpaint_cond: zl should have 1 to 7 channels")
+    _check(torch.is_tensor(mask_lat) and mask_lat.device == zl.device and mask_lat.dtype == torch.float32
+           and tuple(mask_lat.shape) in ((B, h, w), (B, 1, h, w)) and mask_lat.is_contiguous(),
+           f"inpaint_cond: mask_lat should be a dense fp32 tensor of shape {(B, h, w)} or {(B, 1, h, w)} on zl's device")
+    out = torch.empty((B, h, w, 8), dtype=torch.float16, device=zl.device)
+    with torch.cuda.device(zl.device):
+        code = _lib.mixdq_inpaint_cond_f16(mask_lat.data_ptr(), zl.data_ptr(), out.data_ptr(), B * h * w, L, _stream())
+    _status(code, "inpaint_cond")
+    return out.permute(0, 3, 1, 2)
 
 
 def composite_u8(decoded, original, mask):
@@ -1855,4 +1894,27 @@ def mask_bbox(mask):
         code = _lib.mixdq_mask_bbox(mask.data_ptr(), IMAGE_DTYPES[mask.dtype], sb, sh, sw, out.data_ptr(), B, H, W,
                                     _stream())
     _status(code, "mask_bbox")
+    return out
+
+
+_lib.mixdq_mask_dilate_u8.argtypes = [_vp, _i32, _i64, _i64, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _vp]
+_lib.mixdq_mask_dilate_u8.restype = _i32
+MASK_DILATE_MAX_RADIUS = 255
+
+
+def mask_dilate(mask, radius):
+    """A mask grown by `radius` pixels (mixdq_mask_dilate_u8): mask [B, H, W] or [B, 1, H, W], uint8 / fp16 / fp32 of
+    any strides -> dense uint8 of the same shape, 255 where any set pixel (mask_to_latent's rule) lies within `radius`
+    rows and columns -- a square window, PIL's ImageFilter.MaxFilter(2 * radius + 1) of the binarised mask -- and 0
+    elsewhere; windows are clipped at the image border and never reach another image of the batch.  0 <= radius <=
+    255; 0 binarises; a radius larger than the image is legal."""
+    B, H, W, (sb, sh, sw) = _mask3(mask, "mask_dilate")
+    _check(isinstance(radius, int) and not isinstance(radius, bool) and 0 <= radius <= MASK_DILATE_MAX_RADIUS,
+           "mask_dilate: radius should be an int in [0, 255]")
+    out = torch.empty(tuple(mask.shape), dtype=torch.uint8, device=mask.device)
+    scratch = torch.empty((B, H, W), dtype=torch.uint8, device=mask.device)
+    with torch.cuda.device(mask.device):
+        code = _lib.mixdq_mask_dilate_u8(mask.data_ptr(), IMAGE_DTYPES[mask.dtype], sb, sh, sw, scratch.data_ptr(),
+                                         out.data_ptr(), B, H, W, radius, _stream())
+    _status(code, "mask_dilate")
     return out

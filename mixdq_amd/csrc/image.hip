@@ -6,6 +6,7 @@
 //   mixdq_resample_paste_u8   FP16 decode [B, 3, Hm, Wm] -> resized into a per-image window of the full-size uint8
 //                             original, blended in place under a binary or soft mask
 //   mixdq_mask_bbox           the bounding box of a mask's set pixels, one workgroup per image
+//   mixdq_mask_dilate_u8      a mask grown by r pixels (a (2r + 1)^2 square maximum of its binarisation), rows then columns
 //
 // Arithmetic: include/mixdq_math.h (mixdq_resample_tap: explicit FMAs in tap order, zero weights skipped; the
 // horizontal chain of each source row first, then the vertical chain of those FP32 values).
@@ -219,6 +220,44 @@ __global__ __launch_bounds__(kBoxLanes) void mask_bbox_kernel(const T* __restric
   }
 }
 
+// Mask growth, the rows: one lane = one pixel; tmp = 255 where any pixel of columns x - r .. x + r of its own row is set.
+// The window is clipped to the row, so nothing is read outside the image; neighbouring lanes read neighbouring bytes.
+template <typename T>
+__global__ __launch_bounds__(256) void mask_dilate_rows_kernel(const T* __restrict__ mask, int64_t sb, int64_t sh,
+                                                               int64_t sw, uint8_t* __restrict__ tmp, int64_t pixels, int H,
+                                                               int W, int r) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < pixels; i += stride) {
+    const int64_t row = i / W;
+    const int x = (int)(i - row * W);
+    const int64_t b = row / H;
+    const int y = (int)(row - b * H);
+    const T* __restrict__ p = mask + (b * sb + (int64_t)y * sh);
+    const int x0 = max(x - r, 0), x1 = min(x + r, W - 1);
+    bool set = false;
+    for (int k = x0; k <= x1; ++k) set |= px_set(p[(int64_t)k * sw]);
+    tmp[i] = set ? 255 : 0;
+  }
+}
+
+// ... and the columns: out = 255 where any tmp of rows y - r .. y + r of the same image and column is non-zero.  The
+// window is clipped to the image's own rows: it never reaches the neighbouring image of the batch.
+__global__ __launch_bounds__(256) void mask_dilate_cols_kernel(const uint8_t* __restrict__ tmp, uint8_t* __restrict__ out,
+                                                               int64_t pixels, int H, int W, int r) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < pixels; i += stride) {
+    const int64_t row = i / W;
+    const int x = (int)(i - row * W);
+    const int64_t b = row / H;
+    const int y = (int)(row - b * H);
+    const uint8_t* __restrict__ p = tmp + (b * H * (int64_t)W + x);
+    const int y0 = max(y - r, 0), y1 = min(y + r, H - 1);
+    uint32_t any = 0;
+    for (int k = y0; k <= y1; ++k) any |= p[(int64_t)k * W];
+    out[i] = any ? 255 : 0;
+  }
+}
+
 int elem_size(int dtype) {
   return dtype == MIXDQ_IMAGE_U8 ? 1 : dtype == MIXDQ_IMAGE_F16 ? 2 : dtype == MIXDQ_IMAGE_F32 ? 4 : 0;
 }
@@ -307,5 +346,28 @@ extern "C" int mixdq_mask_bbox(const void* mask, int dtype, int64_t sb, int64_t 
   if (dtype == MIXDQ_IMAGE_U8) mask_bbox_kernel<uint8_t><<<B, kBoxLanes, 0, stream>>>((const uint8_t*)mask, sb, sh, sw, out, H, W);
   else if (dtype == MIXDQ_IMAGE_F16) mask_bbox_kernel<__half><<<B, kBoxLanes, 0, stream>>>((const __half*)mask, sb, sh, sw, out, H, W);
   else mask_bbox_kernel<float><<<B, kBoxLanes, 0, stream>>>((const float*)mask, sb, sh, sw, out, H, W);
+  return launch_status();
+}
+
+extern "C" int mixdq_mask_dilate_u8(const void* mask, int dtype, int64_t sb, int64_t sh, int64_t sw, uint8_t* scratch,
+                                    uint8_t* out, int B, int H, int W, int radius, mixdq_stream_t stream_) {
+  const int elem = elem_size(dtype);
+  if (B < 0 || H < 0 || W < 0 || !elem || radius < 0 || radius > 255) return MIXDQ_ERR_INVALID_ARG;
+  const int64_t pixels = (int64_t)B * H * W;
+  if (pixels == 0) return MIXDQ_OK;                  // (an empty tensor has no storage: before the pointer checks)
+  if (!mask || !scratch || !out || scratch == out) return MIXDQ_ERR_INVALID_ARG;
+  if ((uintptr_t)mask % elem) return MIXDQ_ERR_ALIGNMENT;
+  hipStream_t stream = (hipStream_t)stream_;
+  int64_t blocks64 = (pixels + 255) / 256;
+  if (blocks64 > (int64_t)kNumCU * 32) blocks64 = (int64_t)kNumCU * 32;
+  const int blocks = (int)blocks64;
+  if (dtype == MIXDQ_IMAGE_U8)
+    mask_dilate_rows_kernel<uint8_t><<<blocks, 256, 0, stream>>>((const uint8_t*)mask, sb, sh, sw, scratch, pixels, H, W, radius);
+  else if (dtype == MIXDQ_IMAGE_F16)
+    mask_dilate_rows_kernel<__half><<<blocks, 256, 0, stream>>>((const __half*)mask, sb, sh, sw, scratch, pixels, H, W, radius);
+  else
+    mask_dilate_rows_kernel<float><<<blocks, 256, 0, stream>>>((const float*)mask, sb, sh, sw, scratch, pixels, H, W, radius);
+  if (launch_status() != MIXDQ_OK) return MIXDQ_ERR_LAUNCH;
+  mask_dilate_cols_kernel<<<blocks, 256, 0, stream>>>(scratch, out, pixels, H, W, radius);
   return launch_status();
 }

@@ -12,6 +12,12 @@
 //   mixdq_composite_u8         out = mask ? to_uint8(decoded) : original, uint8 [B, H, W, 3]: the pixels outside the
 //                              mask come back bit-identical (the VAE round trip does not reproduce an image)
 //
+// and the two the 9-channel inpainting checkpoints add (their UNet reads the mask and the blanked image's latents):
+//
+//   mixdq_image_to_nhwc8_f16_masked   the ingest with every pixel under the mask stored as +0.0 (mid-grey)
+//   mixdq_inpaint_cond_f16            FP32 latent mask [B, h, w] + FP32 latents [B, h, w, L <= 7] -> FP16 [B, h, w, 8]
+//                                     (mask | latents | zeros): the padded form SDXLUNet.cond_term takes
+//
 // Arithmetic: include/mixdq_math.h (mixdq_pixel_to_unit, mixdq_vae_latent[_mode]), FP32 round-to-nearest, never
 // contracted.  Both are HBM-bound and grid-stride, one pixel (one group of four latent channels) per lane per trip;
 // every load of a trip is requested before the first value is used, and each lane writes one 16-byte store.
@@ -145,6 +151,65 @@ __global__ __launch_bounds__(256) void mask_to_latent_kernel(const T* __restrict
         for (int c = 0; c < 8; ++c) set |= mask_set(px[r * sh + c * sw]);
     }
     out[i] = set ? 1.0f : 0.0f;
+  }
+}
+
+// The ingest with the masked pixels blanked: image_to_nhwc8_kernel's loads and arithmetic, plus the pixel's mask value;
+// a set pixel stores sixteen zero bytes (+0.0 in every channel), whatever its source holds.
+template <typename T, typename M>
+__global__ __launch_bounds__(256) void image_to_nhwc8_masked_kernel(const T* __restrict__ img, int64_t sb, int64_t sc,
+                                                                    int64_t sh, int64_t sw, const M* __restrict__ mask,
+                                                                    int64_t mb, int64_t mh, int64_t mw,
+                                                                    Half8* __restrict__ out, int64_t pixels, int C, int H,
+                                                                    int W) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < pixels; i += stride) {
+    const int64_t row = i / W;
+    const int x = (int)(i - row * W);
+    const int64_t b = row / H;
+    const int y = (int)(row - b * H);
+    const T* px = img + (b * sb + y * sh + x * sw);
+    const M mv = mask[b * mb + y * mh + x * mw];
+    T v[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) v[c] = c < C ? px[c * sc] : T(0);     // channels >= C are never read
+    const bool set = mask_set(mv);
+    uint32_t h[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) h[c] = (c < C && !set) ? half_bits(ingest_value(v[c])) : 0u;
+    Half8 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o.w[j] = h[2 * j] | (h[2 * j + 1] << 16);
+    out[i] = o;
+  }
+}
+
+// One lane = one latent pixel: its mask value and its L latent values, as FP16 in one 16-byte row (mask | z | zeros).
+// L4: the pixel's four latents are one 16-byte load (the launcher checked alignment).
+template <bool L4>
+__global__ __launch_bounds__(256) void inpaint_cond_kernel(const float* __restrict__ mask_lat,
+                                                           const float* __restrict__ zl, Half8* __restrict__ out,
+                                                           int64_t pixels, int L) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < pixels; i += stride) {
+    float v[8];
+    v[0] = mask_lat[i];
+    if constexpr (L4) {
+      const float4 z = *reinterpret_cast<const float4*>(zl + i * 4);
+      v[1] = z.x; v[2] = z.y; v[3] = z.z; v[4] = z.w;
+      v[5] = v[6] = v[7] = 0.0f;
+    } else {
+      const float* z = zl + i * (int64_t)L;
+#pragma unroll
+      for (int c = 1; c < 8; ++c) v[c] = c <= L ? z[c - 1] : 0.0f;    // latents >= L are never read
+    }
+    uint32_t h[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) h[c] = c <= L ? half_bits(v[c]) : 0u;
+    Half8 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o.w[j] = h[2 * j] | (h[2 * j + 1] << 16);
+    out[i] = o;
   }
 }
 
@@ -287,5 +352,58 @@ extern "C" int mixdq_composite_u8(const void* decoded_f16, int64_t db, int64_t d
   else if (mask_dtype == MIXDQ_IMAGE_F16) C_LAUNCH(__half);
   else C_LAUNCH(float);
 #undef C_LAUNCH
+  return launch_status();
+}
+
+namespace {
+template <typename T>
+void launch_ingest_masked(const void* img, int64_t sb, int64_t sc, int64_t sh, int64_t sw, const void* mask,
+                          int mask_dtype, int64_t mb, int64_t mh, int64_t mw, Half8* out, int64_t pixels, int C, int H,
+                          int W, hipStream_t stream) {
+  const int blocks = grid_for(pixels);
+#define I_LAUNCH(M) \
+  image_to_nhwc8_masked_kernel<T, M><<<blocks, 256, 0, stream>>>((const T*)img, sb, sc, sh, sw, (const M*)mask, mb, mh, \
+                                                                 mw, out, pixels, C, H, W)
+  if (mask_dtype == MIXDQ_IMAGE_U8) I_LAUNCH(uint8_t);
+  else if (mask_dtype == MIXDQ_IMAGE_F16) I_LAUNCH(__half);
+  else I_LAUNCH(float);
+#undef I_LAUNCH
+}
+}  // namespace
+
+extern "C" int mixdq_image_to_nhwc8_f16_masked(const void* img, int dtype, int64_t sb, int64_t sc, int64_t sh,
+                                               int64_t sw, const void* mask, int mask_dtype, int64_t mb, int64_t mh,
+                                               int64_t mw, void* out_f16, int B, int C, int H, int W,
+                                               mixdq_stream_t stream_) {
+  const int elem = image_elem_size(dtype), melem = image_elem_size(mask_dtype);
+  if (B < 0 || H < 0 || W < 0 || C < 1 || C > 8 || !elem || !melem) return MIXDQ_ERR_INVALID_ARG;
+  const int64_t pixels = (int64_t)B * H * W;
+  if (pixels == 0) return MIXDQ_OK;                 // (an empty tensor has no storage: before the pointer checks)
+  if (!img || !mask || !out_f16) return MIXDQ_ERR_INVALID_ARG;
+  if ((uintptr_t)out_f16 % 16 || (uintptr_t)img % elem || (uintptr_t)mask % melem) return MIXDQ_ERR_ALIGNMENT;
+  hipStream_t stream = (hipStream_t)stream_;
+  Half8* out = (Half8*)out_f16;
+  if (dtype == MIXDQ_IMAGE_U8)
+    launch_ingest_masked<uint8_t>(img, sb, sc, sh, sw, mask, mask_dtype, mb, mh, mw, out, pixels, C, H, W, stream);
+  else if (dtype == MIXDQ_IMAGE_F16)
+    launch_ingest_masked<__half>(img, sb, sc, sh, sw, mask, mask_dtype, mb, mh, mw, out, pixels, C, H, W, stream);
+  else
+    launch_ingest_masked<float>(img, sb, sc, sh, sw, mask, mask_dtype, mb, mh, mw, out, pixels, C, H, W, stream);
+  return launch_status();
+}
+
+extern "C" int mixdq_inpaint_cond_f16(const float* mask_lat, const float* zl, void* out_f16, int64_t pixels, int L,
+                                      mixdq_stream_t stream_) {
+  if (pixels < 0 || L < 1 || L > 7) return MIXDQ_ERR_INVALID_ARG;
+  if (pixels == 0) return MIXDQ_OK;                 // (an empty tensor has no storage: before the pointer checks)
+  if (!mask_lat || !zl || !out_f16) return MIXDQ_ERR_INVALID_ARG;
+  if ((uintptr_t)out_f16 % 16 || (uintptr_t)mask_lat % 4 || (uintptr_t)zl % 4) return MIXDQ_ERR_ALIGNMENT;
+  hipStream_t stream = (hipStream_t)stream_;
+  Half8* out = (Half8*)out_f16;
+  const int blocks = grid_for(pixels);
+  if (L == 4 && (uintptr_t)zl % 16 == 0)
+    inpaint_cond_kernel<true><<<blocks, 256, 0, stream>>>(mask_lat, zl, out, pixels, L);
+  else
+    inpaint_cond_kernel<false><<<blocks, 256, 0, stream>>>(mask_lat, zl, out, pixels, L);
   return launch_status();
 }

@@ -36,6 +36,17 @@ one are first-order, so a run never reads what an earlier run left in `_hist`.
 counter (element / 4, step, stream), Box-Muller on 24-bit uniforms (include/mixdq_math.h; numpy restatement:
 tests/rng_ref.py).  The start noise is one mixdq_randn_f32 launch; the noise of stochastic steps is computed inside
 mixdq_sampler_step[_masked]_rng, recorded in graphs of their own that read a static seed buffer.
+
+The inpainting CHECKPOINTS (a 9-channel UNet: unet.cond_channels == 5, diffusers' pipeline with num_channels_unet == 9)
+read cat([scaled latents, latent mask, latents of the image with the masked pixels blanked]).  The five conditioning
+channels are constant over a run, and a conv is linear in its input channels: `sample(..., cond=c)` computes conv_in's
+share of them once per call (unet.cond_term, outside the graph) into one static [R, C0, h, w] buffer, and every captured
+step runs the 4-channel conv_in with that buffer as the residual of its epilogue.  The step kernels, the [R, 4, h, w]
+input buffer and the four graphs stay as they are; `cond` is orthogonal to init_latents / strength / mask / seed.
+`Sampler.inpaint` builds `cond` (VAEEncoder.encode(image, noise, mask=), mixdq_mask_to_latent, mixdq_inpaint_cond_f16),
+and runs such a UNet without the blend; `Sampler.inpaint_ext` is inpaint with three more keywords (`inpaint` calls it
+with their defaults): `blend=True` keeps the blend as well, `mask_grow` > 0 grows the mask first
+(mixdq_mask_dilate_u8), `cond_latent_noise` is the blanked image's posterior noise.  DESIGN.md section 3.30.
 """
 import numpy as np
 
@@ -292,6 +303,7 @@ class Sampler:
         self._seeds = None
         self._start = None
         self._key = None
+        self._cond_term = None        # the static [R, C0, h, w] conv_in term of a UNet with conditioning channels
 
     # ---- static buffers + capture ---------------------------------------------------------------------------
     def _setup(self, noise, encoder_hidden_states, added_cond_kwargs):
@@ -340,8 +352,10 @@ class Sampler:
             self._mask = torch.zeros(B, H, W, dtype=torch.float32, device=dev)
             self._blend = torch.from_numpy(self.schedule.blend).to(dev)
 
+        cond_kw = {} if self._cond_term is None else {"cond_term": self._cond_term}
+
         def one_step():
-            eps = forward(self._in, self._t, self._ehs, self._added)[0]
+            eps = forward(self._in, self._t, self._ehs, self._added, **cond_kw)[0]
             if (eps.dtype != torch.float16 or tuple(eps.shape) != tuple(self._in.shape)
                     or any(a != b for a, b, d in zip(eps.stride(), self._in.stride(), eps.shape) if d > 1)):
                 raise RuntimeError("Sampler: the UNet's output is not an FP16 tensor of its input's shape in channels-"
@@ -421,8 +435,38 @@ class Sampler:
         self._t.copy_(self._t_table[t0])
 
     # ---- the loop -------------------------------------------------------------------------------------------
+    def _set_cond(self, cond, noise):
+        """sample(cond=): checked, turned into conv_in's constant term by unet.cond_term (which also re-derives the
+        split weights in place after a reload) and copied into the static buffer every captured step reads -- device
+        work in stream order, nothing read back."""
+        import torch
+        cc = int(getattr(self.unet, "cond_channels", 0))
+        if cc <= 0:
+            if cond is not None:
+                raise RuntimeError("Sampler.sample: cond given, but the UNet has no conditioning channels")
+            return
+        B, _, H, W = noise.shape
+        R = B * self.rows_per_image
+        if cond is None:
+            raise RuntimeError(f"Sampler.sample: this UNet has {cc} conditioning channels: cond is required "
+                               "(_C.inpaint_cond of the latent mask and the masked image's latents)")
+        if not (torch.is_tensor(cond) and cond.device == noise.device and cond.dtype == torch.float16
+                and cond.dim() == 4 and cond.shape[0] in (B, R) and cond.shape[1] in (cc, 8)
+                and tuple(cond.shape[2:]) == (H, W)):
+            raise RuntimeError(f"Sampler.sample: cond should be an FP16 tensor of shape [{B} or {R}, {cc} or 8, {H}, "
+                               f"{W}] on noise's device")
+        term = self.unet.cond_term(cond)
+        if self._cond_term is None:
+            self._cond_term = torch.zeros((R, H, W, term.shape[1]), dtype=torch.float16,
+                                          device=noise.device).permute(0, 3, 1, 2)
+        if term.shape[0] == R:
+            self._cond_term.copy_(term)
+        else:                                       # B rows: the same conditioning in every row block (guidance)
+            for r in range(self.rows_per_image):
+                self._cond_term[r * B:(r + 1) * B].copy_(term)
+
     def sample(self, noise, encoder_hidden_states, added_cond_kwargs=None, step_noise=None, *, init_latents=None,
-               strength=None, mask=None, seed=None):
+               strength=None, mask=None, seed=None, cond=None):
         """noise [B, C, H, W] (unit variance; FP32 or FP16), encoder_hidden_states [R, T, D] FP16 (R = B, or 2B
         under guidance), added_cond_kwargs as the UNet takes them (R rows), step_noise [n_steps, B, C, H, W]: the
         noise each stochastic step adds (required where the schedule has a non-zero c: euler_ancestral and lcm with
@@ -447,7 +491,15 @@ class Sampler:
         step the kept region is overwritten with init_latents noised with `noise` to the next step's level
         (Schedule.blend; after the last step: init_latents themselves), on the second captured graph.  `strength`
         None then means the whole schedule from pure noise, exactly as a text-to-image call starts (diffusers'
-        is_strength_max); otherwise the start is image-to-image's.  The mask does not touch the start state."""
+        is_strength_max); otherwise the start is image-to-image's.  The mask does not touch the start state.
+
+        `cond` (required exactly when unet.cond_channels > 0: the 9-channel inpainting checkpoints): FP16 [B or R, Cc
+        or 8, h, w] on noise's device -- the latent-resolution mask, then the latents of the image with the masked
+        pixels blanked, as _C.inpaint_cond writes them; B rows serve every row block (classifier-free guidance reads the
+        same mask and image in both).  It is constant over the run, so its share of conv_in is computed ONCE here
+        (unet.cond_term, outside the graph) into a static buffer that every captured step adds in its conv_in epilogue:
+        no concatenated 9-channel input exists, the graphs are the four above, and calls with different `cond` replay
+        the same graph objects.  Orthogonal to init_latents / strength / mask / seed."""
         import torch
         from mixdq_amd.quantize_sdxl import _copy_into
         seeds = None
@@ -507,6 +559,7 @@ class Sampler:
             self._setup(noise, encoder_hidden_states, added_cond_kwargs)
         elif self._shape_key(noise, encoder_hidden_states, added_cond_kwargs) != self._key:
             raise RuntimeError("Sampler.sample: inputs differ in shape from those the step graph was captured for")
+        self._set_cond(cond, noise)
         name = "_graph" + ("_masked" if mask is not None else "") + ("_rng" if rng else "")
         if getattr(self, name) is None:
             setattr(self, name, self._capture(noise, masked=mask is not None, rng=rng))
@@ -524,36 +577,40 @@ class Sampler:
             graph.replay()
         return self._x.clone()
 
-    def sample_image(self, vae, noise, encoder_hidden_states, added_cond_kwargs=None, step_noise=None, *, seed=None):
+    def sample_image(self, vae, noise, encoder_hidden_states, added_cond_kwargs=None, step_noise=None, *, seed=None,
+                     cond=None):
         """sample(), then `vae.decode` (a mixdq_amd.vae.VAEDecoder, eager or under hip_graph_opt) of its latents on
         the same stream: nothing waits for the GPU in between.  Returns (FP32 latents, FP16 image [B, 3, 8H, 8W]).
-        `seed` as in sample(): with it `noise` may be the latent shape, and seed -> image is this one call."""
-        latents = self.sample(noise, encoder_hidden_states, added_cond_kwargs, step_noise, seed=seed)
+        `seed` and `cond` as in sample(): with seed `noise` may be the latent shape, and seed -> image is this one
+        call."""
+        latents = self.sample(noise, encoder_hidden_states, added_cond_kwargs, step_noise, seed=seed, cond=cond)
         return latents, vae.decode(latents)
 
-    def _latent_noise(self, latent_noise, latent_seed, noise, encoder_hidden_states):
+    def _latent_noise(self, latent_noise, latent_seed, noise, encoder_hidden_states, stream=None):
         """The VAE posterior's noise of img2img / inpaint: `latent_noise` as given; with `latent_seed` (as sample()'s
-        seed) stream 2 of those seeds at the latent shape; neither: None, the posterior's mode."""
+        seed) stream 2 of those seeds at the latent shape (`stream`: another one -- 3 for the blanked image of a
+        9-channel inpainting run); neither: None, the posterior's mode."""
         import torch
         from mixdq_amd import _C
-        if latent_seed is None:
+        if latent_noise is not None or latent_seed is None:
+            if latent_noise is not None and latent_seed is not None and stream is None:
+                raise RuntimeError("Sampler: latent_noise and latent_seed exclude each other")
             return latent_noise
-        if latent_noise is not None:
-            raise RuntimeError("Sampler: latent_noise and latent_seed exclude each other")
         shape = tuple(noise.shape) if torch.is_tensor(noise) else tuple(int(d) for d in noise)
-        return _C.randn(shape, seed_tensor(latent_seed, shape[0], encoder_hidden_states.device), _C.RNG_STREAM_VAE, 0)
+        return _C.randn(shape, seed_tensor(latent_seed, shape[0], encoder_hidden_states.device),
+                        _C.RNG_STREAM_VAE if stream is None else stream, 0)
 
     def img2img(self, enc, dec, image, noise, encoder_hidden_states, added_cond_kwargs=None, *, strength,
-                step_noise=None, latent_noise=None, seed=None, latent_seed=None):
+                step_noise=None, latent_noise=None, seed=None, latent_seed=None, cond=None):
         """Image to image on one stream: `enc.encode(image, latent_noise)` (a mixdq_amd.vae.VAEEncoder; latent_noise
         None: the posterior's mode), sample(init_latents=that, strength=strength), then `dec.decode` (a VAEDecoder) --
         either VAE eager or under hip_graph_opt, nothing waits for the GPU in between.  noise: [B, C, H/8, W/8], what
         is added to the encoded image.  Returns (FP32 latents, FP16 image [B, 3, H, W]).  `seed` as in sample() (noise
         may then be the latent shape); it does not touch the posterior, which stays the mode unless `latent_noise` or
-        `latent_seed` (stream 2 of those seeds) is given."""
+        `latent_seed` (stream 2 of those seeds) is given.  `cond` as in sample()."""
         z = enc.encode(image, self._latent_noise(latent_noise, latent_seed, noise, encoder_hidden_states))
         latents = self.sample(noise, encoder_hidden_states, added_cond_kwargs, step_noise, init_latents=z,
-                              strength=strength, seed=seed)
+                              strength=strength, seed=seed, cond=cond)
         return latents, dec.decode(latents)
 
     def inpaint(self, enc, dec, image, mask, noise, encoder_hidden_states, added_cond_kwargs=None, *, strength=None,
@@ -576,28 +633,82 @@ class Sampler:
         mask -- blurred by `mask_blur` pixels (image.blur_mask) where that is > 0.  Returns (FP32 latents, uint8
         [B, 3, H, W] at the ORIGINAL size); every pixel outside the window, and every pixel whose paste weight is 0,
         is the input's own byte.  After the tables are uploaded (cached by sizes, boxes and filter) nothing comes from
-        the host."""
+        the host.
+
+        This is inpaint_ext() with its three further keywords at their defaults (blend=None, mask_grow=0,
+        cond_latent_noise=None): on a 4-channel UNet what it always was; on a 9-channel inpainting UNet diffusers' loop
+        without the blend, the conditioning built from `image` and `mask`."""
+        return self.inpaint_ext(enc, dec, image, mask, noise, encoder_hidden_states, added_cond_kwargs,
+                                strength=strength, step_noise=step_noise, latent_noise=latent_noise, mask_mode=mask_mode,
+                                composite=composite, seed=seed, latent_seed=latent_seed, crop=crop, crop_pad=crop_pad,
+                                mask_blur=mask_blur, resample=resample)
+
+    def inpaint_ext(self, enc, dec, image, mask, noise, encoder_hidden_states, added_cond_kwargs=None, *, strength=None,
+                    step_noise=None, latent_noise=None, mask_mode="nearest", composite=False, seed=None,
+                    latent_seed=None, crop=None, crop_pad=32, mask_blur=0.0, resample="lanczos3", blend=None,
+                    mask_grow=0, cond_latent_noise=None):
+        """inpaint() -- same arguments, same results -- with the keywords the inpainting checkpoints and mask growth add.
+
+        `mask_grow` > 0: the mask is replaced by `_C.mask_dilate(mask, mask_grow)` -- grown by that many pixels, a
+        square window -- for EVERYTHING in the call: the bounding box of crop='auto', the model-size mask, the blanked
+        image, the blur, the composite / paste.  (Front ends' "grow mask by"; any UNet.)
+
+        A UNet with conditioning channels (unet.cond_channels == 1 + the VAE's latent channels: the 9-channel
+        inpainting checkpoints) is also given `cond = _C.inpaint_cond(latent mask, enc.encode(image, cond_noise,
+        mask=mask))`: the mask and the latents of the image with the masked pixels blanked; cond_noise is
+        `cond_latent_noise`, else stream 3 of `latent_seed`, else None (the posterior's mode).  `blend`: whether the
+        kept region is also overwritten after every step (the masked graph).  None means True for a 4-channel UNet
+        (blend=False is refused there: nothing else would keep the image) and False for a 9-channel one, diffusers'
+        behaviour: a plain loop or, with `strength`, an image-to-image one -- with strength None the init image is not
+        even encoded.  blend=True on a 9-channel UNet runs the masked graph as well.  On the crop path the blanked
+        encode reads the resized window and the resized mask."""
         import torch
         from mixdq_amd import _C
         if composite and not (torch.is_tensor(image) and image.dtype == torch.uint8):
             raise RuntimeError("Sampler.inpaint: composite=True pastes into the input pixels: image should be uint8")
+        cc = int(getattr(self.unet, "cond_channels", 0))
+        if blend is None:
+            blend = cc == 0
+        if not blend and cc == 0:
+            raise RuntimeError("Sampler.inpaint: blend=False leaves the image to the UNet's conditioning channels, and "
+                               "this UNet has none")
+        if cc > 0 and cc != 1 + int(enc.cfg["latent_channels"]):
+            raise RuntimeError(f"Sampler.inpaint: the UNet's {cc} conditioning channels are not a mask and the VAE's "
+                               f"{enc.cfg['latent_channels']} latent channels")
+        if not (isinstance(mask_grow, int) and not isinstance(mask_grow, bool) and 0 <= mask_grow <= 255):
+            raise RuntimeError("Sampler.inpaint: mask_grow should be an int in [0, 255]")
+        if mask_grow > 0:
+            mask = _C.mask_dilate(mask, mask_grow)
+        kw = dict(strength=strength, step_noise=step_noise, latent_noise=latent_noise, mask_mode=mask_mode, seed=seed,
+                  latent_seed=latent_seed, blend=bool(blend), cond_latent_noise=cond_latent_noise)
         if crop is not None:
             return self._inpaint_crop(enc, dec, image, mask, noise, encoder_hidden_states, added_cond_kwargs,
-                                      strength=strength, step_noise=step_noise, latent_noise=latent_noise,
-                                      mask_mode=mask_mode, composite=composite, seed=seed, latent_seed=latent_seed,
-                                      crop=crop, crop_pad=crop_pad, mask_blur=mask_blur, resample=resample)
-        z = enc.encode(image, self._latent_noise(latent_noise, latent_seed, noise, encoder_hidden_states))
-        latents = self.sample(noise, encoder_hidden_states, added_cond_kwargs, step_noise, init_latents=z,
-                              strength=strength, mask=_C.mask_to_latent(mask, mask_mode), seed=seed)
+                                      composite=composite, crop=crop, crop_pad=crop_pad, mask_blur=mask_blur,
+                                      resample=resample, **kw)
+        latents = self._inpaint_latents(enc, image, mask, noise, encoder_hidden_states, added_cond_kwargs, **kw)
         decoded = dec.decode(latents)
         return latents, (_C.composite_u8(decoded, image, mask) if composite else decoded)
 
-    def _inpaint_crop(self, enc, dec, image, mask, noise, encoder_hidden_states, added_cond_kwargs, *, strength,
-                      step_noise, latent_noise, mask_mode, composite, seed, latent_seed, crop, crop_pad, mask_blur,
-                      resample):
+    def _inpaint_latents(self, enc, image, mask, noise, encoder_hidden_states, added_cond_kwargs, *, strength,
+                         step_noise, latent_noise, mask_mode, seed, latent_seed, blend, cond_latent_noise):
+        """The model-size part of inpaint(): the encodes, the latent mask, the conditioning, the loop."""
+        from mixdq_amd import _C
+        m = _C.mask_to_latent(mask, mask_mode)
+        cond = None
+        if int(getattr(self.unet, "cond_channels", 0)) > 0:
+            cond_noise = self._latent_noise(cond_latent_noise, latent_seed, noise, encoder_hidden_states,
+                                            stream=_C.RNG_STREAM_COND)
+            cond = _C.inpaint_cond(m, enc.encode(image, cond_noise, mask=mask))
+        z = None
+        if blend or strength is not None:           # (a plain 9-channel run never reads the init image's latents)
+            z = enc.encode(image, self._latent_noise(latent_noise, latent_seed, noise, encoder_hidden_states))
+        return self.sample(noise, encoder_hidden_states, added_cond_kwargs, step_noise, init_latents=z,
+                           strength=strength, mask=m if blend else None, seed=seed, cond=cond)
+
+    def _inpaint_crop(self, enc, dec, image, mask, noise, encoder_hidden_states, added_cond_kwargs, *, composite, crop,
+                      crop_pad, mask_blur, resample, **kw):
         """inpaint(crop=...): resize the window to the model size, inpaint there, paste the decode back."""
         import torch
-        from mixdq_amd import _C
         from mixdq_amd import image as I
         if not (torch.is_tensor(image) and image.dtype == torch.uint8 and image.dim() == 4 and image.shape[1] == 3):
             raise RuntimeError("Sampler.inpaint: crop pastes into the input pixels: image should be uint8 [B, 3, H, W]")
@@ -625,9 +736,7 @@ class Sampler:
         mask3 = mask if mask.dim() == 3 else mask[:, 0]
         small = I.resize(image, model_hw, boxes, resample)
         small_mask = I.resize(mask3[:, None], model_hw, boxes, "bilinear", mask=True)[:, 0]
-        z = enc.encode(small, self._latent_noise(latent_noise, latent_seed, noise, encoder_hidden_states))
-        latents = self.sample(noise, encoder_hidden_states, added_cond_kwargs, step_noise, init_latents=z,
-                              strength=strength, mask=_C.mask_to_latent(small_mask, mask_mode), seed=seed)
+        latents = self._inpaint_latents(enc, small, small_mask, noise, encoder_hidden_states, added_cond_kwargs, **kw)
         decoded = dec.decode(latents)
         soft = mask_blur > 0.0
         return latents, I.paste(decoded, image, I.blur_mask(mask3, mask_blur) if soft else mask3, boxes, resample,

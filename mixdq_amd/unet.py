@@ -422,6 +422,12 @@ SD15_CONFIG = dict(
     norm_num_groups=32,
 )
 
+# The inpainting checkpoints (stable-diffusion-xl-1.0-inpainting-0.1, stable-diffusion-inpainting): the same networks
+# with a 9-channel conv_in, whose input is cat([scaled latents (4), latent-resolution mask (1), latents of the image
+# with the masked pixels blanked (4)]).  The five conditioning channels are constant over a run: SDXLUNet.cond_term.
+SDXL_INPAINT_CONFIG = dict(SDXL_CONFIG, in_channels=9)
+SD15_INPAINT_CONFIG = dict(SD15_CONFIG, in_channels=9)
+
 
 def head_width(cfg, channels: int) -> int:
     """Width of an attention head at a level of `channels` channels: cfg['head_dim'] (SDXL, the toy networks), or
@@ -1089,6 +1095,8 @@ class SDXLUNet(nn.Module):
         boc = cfg["block_out_channels"]
         temb = cfg["time_embed_dim"]
         self.conv_in = nn.Conv2d(cfg["in_channels"], boc[0], 3, 1, 1)
+        # input channels beyond the latents': 0, or the 5 (mask + masked-image latents) of an inpainting checkpoint
+        self.cond_channels = cfg["in_channels"] - cfg["out_channels"]
         self.time_embedding = TimestepEmbedding(boc[0], temb)
         if cfg.get("addition_embed_type", "text_time") is not None:
             self.add_embedding = TimestepEmbedding(cfg["projection_class_embeddings_input_dim"], temb)
@@ -1360,9 +1368,114 @@ class SDXLUNet(nn.Module):
             self.prepare_fused_()
         return self
 
+    # ---- the split conv_in of an inpainting checkpoint (cond_channels > 0) ---------------
+    # conv_in(cat([x, c])) = conv(x; W[:, :4]) + conv(c; W[:, 4:]) + bias, and c -- the mask and the masked image's
+    # latents -- is the same at every step of a run: the second term (with the bias) is computed once per run by
+    # cond_term(), and a step's conv_in is the 4-channel conv with that term as the residual of its epilogue.
+    def _conv_in_weight(self):
+        w = getattr(self.conv_in, "weight", None)
+        if w is None or getattr(self.conv_in, "valid_for_acceleration", False):
+            raise RuntimeError("SDXLUNet: the split conv_in needs conv_in as a floating-point layer (a 9-channel "
+                               "conv_in always is one: QuantizedConv2d falls back where in_channels % 4 != 0)")
+        return w
+
+    @torch.no_grad()
+    def _conv_in_split(self, refresh: bool):
+        """(Wx8, Wc8): conv_in.weight[:, :out_channels] and [:, out_channels:], each zero-padded to 8 input channels,
+        KRSC in memory.  Cached; with `refresh` they are re-derived IN PLACE (same storage: a captured graph keeps
+        reading them) when the weight tensor or its `_version` changed.  Without it the cache is only read."""
+        c = self.__dict__.get("_cin_split")
+        if not refresh:
+            if c is None:
+                raise RuntimeError("SDXLUNet.forward: cond_term= should be what this UNet's cond_term() returned")
+            return c["wx"], c["wc"]
+        w = self._conv_in_weight()
+        if c is not None and c["w"] is w and c["version"] == w._version:
+            return c["wx"], c["wc"]
+        co = self.cfg["out_channels"]
+        shape = (w.shape[0], 8) + tuple(w.shape[2:])
+        if c is None or c["wx"].shape != shape or c["wx"].dtype != w.dtype or c["wx"].device != w.device:
+            new = lambda: torch.zeros(shape, dtype=w.dtype, device=w.device).contiguous(  # noqa: E731
+                memory_format=torch.channels_last)
+            c = self.__dict__["_cin_split"] = dict(wx=new(), wc=new())
+        c["wx"][:, :co] = w[:, :co]
+        c["wc"][:, :self.cond_channels] = w[:, co:]
+        c["w"], c["version"] = w, w._version
+        return c["wx"], c["wc"]
+
+    @staticmethod
+    def _pad8(x):
+        """x [N, C <= 8, h, w] with zero channels up to 8, channels-last."""
+        if x.shape[1] == 8:
+            return x.contiguous(memory_format=torch.channels_last)
+        xp = torch.zeros((x.shape[0], 8, x.shape[2], x.shape[3]), dtype=x.dtype, device=x.device
+                         ).contiguous(memory_format=torch.channels_last)
+        xp[:, :x.shape[1]] = x
+        return xp
+
+    @torch.no_grad()
+    def cond_term(self, cond):
+        """The part of conv_in's output that the conditioning channels contribute, bias included: cond [N, Cc, h, w]
+        (Cc = cond_channels: for an inpainting checkpoint the latent-resolution mask, then the latents of the image
+        with the masked pixels blanked) or the padded 8-channel form _C.inpaint_cond writes, in conv_in's dtype (FP16
+        on the GPU) -> T = conv2d_f16(cond8, Wc8, bias=conv_in.bias, 1, 1), channels-last [N, C0, h, w].  The padding
+        columns of Wc8 are zero, so what the padding channels of an 8-channel `cond` hold is irrelevant as long as it
+        is finite.  Pass it as forward(sample4, ..., cond_term=T) at every step of the run.  The split weights are
+        re-derived here, in place, when conv_in.weight was replaced or written since: call it after a reload, outside
+        a captured graph (Sampler.sample does, at every call)."""
+        if self.cond_channels <= 0:
+            raise RuntimeError("SDXLUNet.cond_term: this UNet has no conditioning channels (in_channels == "
+                               "out_channels)")
+        if self.cond_channels > 8:
+            raise RuntimeError("SDXLUNet.cond_term: at most 8 conditioning channels")
+        w = self._conv_in_weight()
+        if not (torch.is_tensor(cond) and cond.dim() == 4 and cond.shape[1] in (self.cond_channels, 8)
+                and cond.dtype == w.dtype and cond.device == w.device):
+            raise RuntimeError(f"SDXLUNet.cond_term: cond should be a [N, {self.cond_channels} or 8, h, w] {w.dtype} "
+                               f"tensor on {w.device}")
+        _, wc = self._conv_in_split(refresh=True)
+        c8 = self._pad8(cond)
+        bias = self.conv_in.bias
+        if c8.is_cuda and c8.dtype == torch.float16:
+            from mixdq_amd import _C
+            return _C.conv2d_f16(c8, wc, bias, 1, 1)
+        return F.conv2d(c8, wc, bias, 1, 1).contiguous(memory_format=torch.channels_last)
+
+    def _conv_in_with_term(self, x, term):
+        """conv_in of a step: conv(x8; Wx8) with `term` as the residual -- f16(f32(f16(sum)) + f32(T)), a torch half
+        add of the two rounded tensors."""
+        wx, _ = self._conv_in_split(refresh=False)
+        x8 = self._pad8(x)
+        if x8.is_cuda and x8.dtype == torch.float16:
+            from mixdq_amd import _C
+            return _C.conv2d_f16(x8, wx, None, 1, 1, _residual=term)
+        return F.conv2d(x8, wx, None, 1, 1) + term
+
+    def _check_cond_term(self, sample, cond_term):
+        co, cc = self.cfg["out_channels"], self.cond_channels
+        if cond_term is None:
+            if cc > 0 and sample.shape[1] == co:
+                raise RuntimeError(f"SDXLUNet.forward: this UNet has {cc} conditioning channels: a {co}-channel sample "
+                                   f"needs cond_term= (unet.cond_term(cond)), or pass all {co + cc} channels")
+            return
+        if cc <= 0:
+            raise RuntimeError("SDXLUNet.forward: cond_term given, but this UNet has no conditioning channels")
+        if sample.dim() != 4 or sample.shape[1] != co:
+            raise RuntimeError(f"SDXLUNet.forward: with cond_term the sample should have {co} channels")
+        want = (sample.shape[0], self.conv_in.out_channels, sample.shape[2], sample.shape[3])
+        if not (torch.is_tensor(cond_term) and tuple(cond_term.shape) == want and cond_term.dtype == sample.dtype
+                and cond_term.device == sample.device
+                and cond_term.is_contiguous(memory_format=torch.channels_last)):
+            raise RuntimeError(f"SDXLUNet.forward: cond_term should be a channels-last {sample.dtype} tensor of shape "
+                               f"{want} (one row per sample row) on the sample's device")
+
     def forward(self, sample, timestep, encoder_hidden_states, added_cond_kwargs=None,
-                return_dict=False):
+                return_dict=False, cond_term=None):
+        """`cond_term` (UNets with cond_channels > 0): what cond_term(cond) returned, one row per row of `sample`,
+        which then has out_channels channels -- conv_in runs split, without a concatenated input.  Without it such a
+        UNet takes all in_channels channels in `sample` (the drop-in form)."""
         cfg = self.cfg
+        self._check_cond_term(sample, cond_term)
         B = sample.shape[0]
         dtype = sample.dtype
         t = timestep
@@ -1379,7 +1492,7 @@ class SDXLUNet(nn.Module):
 
         use_pf = bool(self.fused and PREFETCH and sample.is_cuda and _fusable_f16(sample) and not DEFUSE)
         if not use_pf:
-            return self._forward_body(sample, emb, encoder_hidden_states)
+            return self._forward_body(sample, emb, encoder_hidden_states, cond_term)
         # Trace this forward's weight order and replay the plan of the last forward ON THIS DEVICE: the state
         # is this call's own PrefetchContext (thread-local while it runs), the plans are kept per device in
         # the instance and hold weak references -- a plan made for another device, or for weights that have
@@ -1394,7 +1507,7 @@ class SDXLUNet(nn.Module):
         ctx = _C.PrefetchContext(sample.device, plan["lists"] if plan else None)
         try:
             with ctx:
-                return self._forward_body(sample, emb, encoder_hidden_states)
+                return self._forward_body(sample, emb, encoder_hidden_states, cond_term)
         finally:
             if ctx._outer is None:                               # (an inner, inactive context traced nothing)
                 sig = _trace_signature(ctx.trace)
@@ -1407,18 +1520,19 @@ class SDXLUNet(nn.Module):
 
     def _apply(self, fn, recurse=True):          # .to() / .cuda() / .half(): the weights move, the plans go
         self.__dict__.pop("_pf_plans", None)
+        self.__dict__.pop("_cin_split", None)    # (... and the split conv_in weights: cond_term() makes them anew)
         return super()._apply(fn, recurse)
 
     def load_state_dict(self, *args, **kwargs):
         self.__dict__.pop("_pf_plans", None)
         return super().load_state_dict(*args, **kwargs)
 
-    def _forward_body(self, sample, emb, encoder_hidden_states):
+    def _forward_body(self, sample, emb, encoder_hidden_states, cond_term=None):
         if self.fused and _fusable_f16(sample) and not DEFUSE:
             self._project_temb_ahead(emb)
             self._project_context_ahead(encoder_hidden_states)
         x = sample.contiguous(memory_format=torch.channels_last)
-        x = self.conv_in(x)
+        x = self.conv_in(x) if cond_term is None else self._conv_in_with_term(x, cond_term)
         skips = [x]
         for blk in self.down_blocks:
             x, outs = blk(x, emb, encoder_hidden_states)

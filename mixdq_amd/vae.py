@@ -16,7 +16,9 @@ The other half, image in, latents out (diffusers' AutoencoderKL.encode), is VAEE
     latents = enc.encode(from_uint8(pixels), noise)          # [B, 3, H, W] uint8 / FP16 / FP32 -> FP32 [B, 4, H/8, W/8]
 
 Its launches are the decoder's, plus three forms of its own: mixdq_image_to_nhwc8_f16 (the ingest: any dtype and
-strides -> FP16 NHWC with 8 channels, so that conv_in runs on the MFMA tiles), mixdq_conv2d_f16 with
+strides -> FP16 NHWC with 8 channels, so that conv_in runs on the MFMA tiles; `encode(image, noise, mask=m)` takes
+mixdq_image_to_nhwc8_f16_masked instead, which stores the pixels under the mask as 0.0: the blanked image whose latents
+the 9-channel inpainting checkpoints read), mixdq_conv2d_f16 with
 MIXDQ_FLAG_PAD_AFTER (`Downsample2D`'s 3x3 / stride 2 conv over F.pad(x, (0, 1, 0, 1)) without the padded tensor) and
 mixdq_vae_latent_sample (the posterior sample times scaling_factor).  DESIGN.md section 3.25.
 
@@ -317,10 +319,10 @@ class VAEEncoder(_VaeHalf):
             raise RuntimeError("VAEEncoder.%s: the encoder runs in FP16 (build_vae_encoder / .half())" % what)
 
     @torch.no_grad()
-    def _moments(self, image):
+    def _moments(self, image, mask=None):
         from mixdq_amd import _C
         d, enc = self._derived(), self.encoder
-        x = _C.image_to_nhwc8_f16(image)                                  # any dtype and strides -> FP16, 8 channels
+        x = _C.image_to_nhwc8_f16(image, mask)                            # any dtype and strides -> FP16, 8 channels
         x = _C.conv2d_f16(x, *d["conv_in"], 1, 1)
         for blk in enc.down_blocks:
             x = blk.run(self, x)
@@ -336,9 +338,15 @@ class VAEEncoder(_VaeHalf):
         return self._moments(image)
 
     @torch.no_grad()
-    def forward(self, image, noise=None):
+    def forward(self, image, noise=None, mask=None):
         from mixdq_amd import _C
         self._check_image(image, "encode")
+        if mask is not None and not (torch.is_tensor(mask) and mask.device == image.device
+                                     and mask.dtype in (torch.uint8, torch.float16, torch.float32)
+                                     and tuple(mask.shape) in ((image.shape[0],) + tuple(image.shape[2:]),
+                                                               (image.shape[0], 1) + tuple(image.shape[2:]))):
+            raise RuntimeError("VAEEncoder.encode: mask should be a [B, H, W] or [B, 1, H, W] uint8, FP16 or FP32 "
+                               "tensor of the image's size on its device")
         if noise is not None:
             want = (image.shape[0], self.cfg["latent_channels"], image.shape[2] // 8, image.shape[3] // 8)
             if not (torch.is_tensor(noise) and noise.device == image.device and noise.dtype == torch.float32
@@ -346,14 +354,21 @@ class VAEEncoder(_VaeHalf):
                 raise RuntimeError("VAEEncoder.encode: noise should be an FP32 tensor of shape %s on the image's device"
                                    % (want,))
             noise = noise.contiguous(memory_format=torch.channels_last)
-        return _C.vae_latent_sample(self._moments(image), noise, self.scaling_factor)
+        return _C.vae_latent_sample(self._moments(image, mask), noise, self.scaling_factor)
 
-    def encode(self, image, noise=None):
+    def encode(self, image, noise=None, mask=None):
         """image [B, 3, H, W] (uint8: a pixel u is u / 127.5 - 1; FP16 / FP32: already in [-1, 1]; any strides; H and
         W multiples of 8) -> FP32 [B, L, H/8, W/8] channels-last, already multiplied by scaling_factor: with `noise`
         (FP32, the result's shape) diffusers' `vae.encode(x).latent_dist.sample() * scaling_factor`, without it
-        `.mode() * scaling_factor`.  What Sampler.sample(init_latents=...) takes."""
-        return self.forward(image, noise)
+        `.mode() * scaling_factor`.  What Sampler.sample(init_latents=...) takes.
+
+        `mask` ([B, H, W] or [B, 1, H, W] at the image's size; uint8 >= 128 or float >= 0.5 is set; any strides): the
+        pixels under it enter the encoder as 0.0 -- mid-grey -- in every channel (mixdq_image_to_nhwc8_f16_masked in
+        place of the plain ingest, nothing else differs): diffusers' `init_image * (mask < 0.5)`, the masked image whose
+        latents a 9-channel inpainting UNet is conditioned on (_C.inpaint_cond)."""
+        if mask is None:
+            return self.forward(image, noise)
+        return self.forward(image, noise, mask)
 
 
 def to_uint8(image):
