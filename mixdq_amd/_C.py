@@ -1398,11 +1398,18 @@ def embed_tokens_f16(ids, tok, pos):
     return out
 
 
-_lib.mixdq_sampler_step.argtypes = [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, ctypes.c_float, _i64, _i32,
-                                    _i64, _vp]
-_lib.mixdq_sampler_step.restype = _i32
-_lib.mixdq_sampler_step_rng.argtypes = _lib.mixdq_sampler_step.argtypes
-_lib.mixdq_sampler_step_rng.restype = _i32
+# The six step entry points: x, eps, in, then what the kind adds around the table, then the part they all share.
+# order 1: noise, noise_stride (_rng: seeds, n_image), coef, t_table, n_steps, step
+_STEP_ORDER1 = [_vp] * 3 + [_vp, _i64, _vp, _vp, _i32, _vp]
+# 2M: hist, coef8, t_table, n_steps, step, first
+_STEP_2M = [_vp] * 3 + [_vp, _vp, _vp, _i32, _vp, _vp]
+_STEP_SHARED = [_vp, ctypes.c_float, _i64, _i32, _i64]      # timestep, guidance, n, rows_per_image, row_stride
+_STEP_MASKED = [_vp, _vp, _vp, _i32, _vp]                   # z, noise0, mask, channels, blend
+for _name, _head, _tail in (("", _STEP_ORDER1, []), ("_masked", _STEP_ORDER1, _STEP_MASKED),
+                            ("_rng", _STEP_ORDER1, []), ("_masked_rng", _STEP_ORDER1, _STEP_MASKED),
+                            ("_2m", _STEP_2M, []), ("_2m_masked", _STEP_2M, _STEP_MASKED)):
+    getattr(_lib, "mixdq_sampler_step" + _name).argtypes = _head + _STEP_SHARED + _tail + [_vp]
+    getattr(_lib, "mixdq_sampler_step" + _name).restype = _i32
 _lib.mixdq_randn_f32.argtypes = [_vp, _i32, _i64, _vp, ctypes.c_uint32, ctypes.c_uint32, _vp]
 _lib.mixdq_randn_f32.restype = _i32
 _lib.mixdq_rng_normals_from_bits.argtypes = [_vp, _vp, _i64, _vp]
@@ -1463,6 +1470,75 @@ def rng_normals_from_bits(r):
     return z
 
 
+def _sampler_step(what, x, eps, inp, table, width, t_table, step, timestep, guidance, rows_per_image, n, row_stride, *,
+                  hist=None, first=None, masked=None, channels=4, noise=None, noise_stride=None, seeds=None,
+                  n_image=None):
+    """The checks and the call of the four step bindings.  `what`: the binding's name; `table`: coef (width 4) or, for
+    the multistep kinds, coef8 (width 8), which come with `hist` and `first`; masked: None or (z, noise0, mask, blend);
+    noise / seeds: at most one of them, width 4 only."""
+    if seeds is not None:
+        n, n_image = _check_step_seeds(seeds, noise, n, n_image, x.numel(), what)
+    f32, f16, i32 = torch.float32, torch.float16, torch.int32
+    two_m = width == 8
+    tname = "coef8" if two_m else "coef"
+    operands = [(x, "x", f32), (eps, "eps", f16), (inp, "inp", f16)] + [(hist, "hist", f32)] * two_m + [
+        (table, tname, f32), (t_table, "t_table", f32), (step, "step", i32)] + [(first, "first", i32)] * two_m + [
+        (timestep, "timestep", f32)]
+    if masked is not None:
+        z, noise0, mask, blend = masked
+        operands += [(z, "z", f32), (noise0, "noise0", f32), (mask, "mask", f32), (blend, "blend", f32)]
+    if noise is not None:
+        operands.append((noise, "noise", f32))
+    if seeds is not None:
+        operands.append((seeds, "seeds", torch.int64))
+    for t_, name, dt in operands:
+        _check(torch.is_tensor(t_) and t_.is_cuda and t_.device == x.device and t_.dtype == dt,
+               f"{name} should be a {dt} tensor on x's GPU")
+    _check(table.dim() == 2 and table.shape[1] == width and table.is_contiguous() and t_table.is_contiguous(),
+           f"{tname} should be a contiguous [n_steps, {width}] table")
+    n_steps = table.shape[0]
+    if masked is not None:
+        _check(tuple(blend.shape) == (n_steps, 2) and blend.is_contiguous(),
+               "blend should be a contiguous [n_steps, 2] table")
+    _check(t_table.numel() >= n_steps + 1, "t_table needs n_steps + 1 entries")
+    if two_m:
+        _check(step.numel() == 1 and first.numel() == 1 and timestep.numel() == 1,
+               "step, first and timestep hold one value each")
+    else:
+        _check(step.numel() == 1 and timestep.numel() == 1, "step and timestep hold one value each")
+    n = x.numel() if n is None else int(n)
+    row_stride = n if row_stride is None else int(row_stride)
+    noise_stride = n if noise_stride is None else int(noise_stride)
+    _check(0 <= n <= x.numel(), "n exceeds the state")
+    if two_m:
+        _check(hist.numel() >= n, "hist is smaller than the state")
+    if masked is not None:
+        channels = int(channels)
+        _check(z.numel() >= n and noise0.numel() >= n, "z / noise0 are smaller than the state")
+        if channels >= 1 and n % channels == 0:       # (anything else: the library's own error)
+            _check(mask.is_contiguous() and mask.numel() >= n // channels,
+                   "mask should be dense with n / channels entries")
+    if rows_per_image in (1, 2):                      # (anything else: the library's own error)
+        need = (rows_per_image - 1) * row_stride + n
+        _check(eps.numel() >= need and inp.numel() >= need, "eps / inp are smaller than rows_per_image row blocks")
+    if noise is not None:
+        _check(noise.numel() >= (n_steps - 1) * noise_stride + n, "noise is smaller than n_steps blocks")
+    args = [x.data_ptr(), eps.data_ptr(), inp.data_ptr()]
+    if two_m:
+        args += [hist.data_ptr(), table.data_ptr(), t_table.data_ptr(), n_steps, step.data_ptr(), first.data_ptr()]
+    else:
+        args += [seeds.data_ptr(), n_image] if seeds is not None else [_ptr(noise), noise_stride]
+        args += [table.data_ptr(), t_table.data_ptr(), n_steps, step.data_ptr()]
+    args += [timestep.data_ptr(), float(guidance), n, int(rows_per_image), row_stride]
+    if masked is not None:
+        args += [z.data_ptr(), noise0.data_ptr(), mask.data_ptr(), channels, blend.data_ptr()]
+    entry = "mixdq_sampler_step" + ("_2m" if two_m else "") + ("_masked" if masked is not None else "") + (
+        "_rng" if seeds is not None else "")
+    with torch.cuda.device(x.device):
+        code = getattr(_lib, entry)(*args, _stream())
+    _status(code, what)
+
+
 def sampler_step(x, eps, inp, coef, t_table, step, timestep, guidance=0.0, rows_per_image=1, noise=None, *,
                  n=None, row_stride=None, noise_stride=None, seeds=None, n_image=None):
     """One sampler step in place (mixdq_sampler_step): guidance over the two row blocks of `eps`, the affine
@@ -1478,49 +1554,8 @@ def sampler_step(x, eps, inp, coef, t_table, step, timestep, guidance=0.0, rows_
     seeds (int64 [n / n_image] on x's GPU, read as unsigned; `noise` must then be None): the step computes its noise in
     registers (mixdq_sampler_step_rng) -- the values randn(.., seeds, stream=RNG_STREAM_STEP, step=<step>) holds for
     images of `n_image` elements (default: n, one image)."""
-    if seeds is not None:
-        n, n_image = _check_step_seeds(seeds, noise, n, n_image, x.numel(), "sampler_step")
-    for t_, name, dt in ((x, "x", torch.float32), (eps, "eps", torch.float16), (inp, "inp", torch.float16),
-                         (coef, "coef", torch.float32), (t_table, "t_table", torch.float32),
-                         (step, "step", torch.int32), (timestep, "timestep", torch.float32)) + (
-                             ((noise, "noise", torch.float32),) if noise is not None else ()) + (
-                             ((seeds, "seeds", torch.int64),) if seeds is not None else ()):
-        _check(t_.is_cuda and t_.device == x.device and t_.dtype == dt, f"{name} should be a {dt} tensor on x's GPU")
-    _check(coef.dim() == 2 and coef.shape[1] == 4 and coef.is_contiguous() and t_table.is_contiguous(),
-           "coef should be a contiguous [n_steps, 4] table")
-    n_steps = coef.shape[0]
-    _check(t_table.numel() >= n_steps + 1, "t_table needs n_steps + 1 entries")
-    _check(step.numel() == 1 and timestep.numel() == 1, "step and timestep hold one value each")
-    n = x.numel() if n is None else int(n)
-    row_stride = n if row_stride is None else int(row_stride)
-    noise_stride = n if noise_stride is None else int(noise_stride)
-    _check(0 <= n <= x.numel(), "n exceeds the state")
-    if rows_per_image in (1, 2):                      # (anything else: the library's own error)
-        need = (rows_per_image - 1) * row_stride + n
-        _check(eps.numel() >= need and inp.numel() >= need, "eps / inp are smaller than rows_per_image row blocks")
-    if noise is not None:
-        _check(noise.numel() >= (n_steps - 1) * noise_stride + n, "noise is smaller than n_steps blocks")
-    if seeds is not None:
-        with torch.cuda.device(x.device):
-            code = _lib.mixdq_sampler_step_rng(x.data_ptr(), eps.data_ptr(), inp.data_ptr(), seeds.data_ptr(), n_image,
-                                               coef.data_ptr(), t_table.data_ptr(), n_steps, step.data_ptr(),
-                                               timestep.data_ptr(), float(guidance), n, int(rows_per_image), row_stride,
-                                               _stream())
-        _status(code, "sampler_step")
-        return
-    with torch.cuda.device(x.device):
-        code = _lib.mixdq_sampler_step(x.data_ptr(), eps.data_ptr(), inp.data_ptr(), _ptr(noise), noise_stride,
-                                       coef.data_ptr(), t_table.data_ptr(), n_steps, step.data_ptr(),
-                                       timestep.data_ptr(), float(guidance), n, int(rows_per_image), row_stride,
-                                       _stream())
-    _status(code, "sampler_step")
-
-
-_lib.mixdq_sampler_step_masked.argtypes = [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, ctypes.c_float, _i64,
-                                           _i32, _i64, _vp, _vp, _vp, _i32, _vp, _vp]
-_lib.mixdq_sampler_step_masked.restype = _i32
-_lib.mixdq_sampler_step_masked_rng.argtypes = _lib.mixdq_sampler_step_masked.argtypes
-_lib.mixdq_sampler_step_masked_rng.restype = _i32
+    _sampler_step("sampler_step", x, eps, inp, coef, 4, t_table, step, timestep, guidance, rows_per_image, n, row_stride,
+                  noise=noise, noise_stride=noise_stride, seeds=seeds, n_image=n_image)
 
 
 def sampler_step_masked(x, eps, inp, coef, t_table, step, timestep, z, noise0, mask, blend, guidance=0.0,
@@ -1534,84 +1569,9 @@ def sampler_step_masked(x, eps, inp, coef, t_table, step, timestep, z, noise0, m
     n / channels entries; 1 repaints, 0 keeps): element i of the channels-last storage belongs to entry
     i // channels; blend: fp32 [n_steps, 2] (Schedule.blend).  Everything else as sampler_step, `seeds` / `n_image`
     (mixdq_sampler_step_masked_rng) included."""
-    if seeds is not None:
-        n, n_image = _check_step_seeds(seeds, noise, n, n_image, x.numel(), "sampler_step_masked")
-    for t_, name, dt in ((x, "x", torch.float32), (eps, "eps", torch.float16), (inp, "inp", torch.float16),
-                         (coef, "coef", torch.float32), (t_table, "t_table", torch.float32),
-                         (step, "step", torch.int32), (timestep, "timestep", torch.float32),
-                         (z, "z", torch.float32), (noise0, "noise0", torch.float32), (mask, "mask", torch.float32),
-                         (blend, "blend", torch.float32)) + (
-                             ((noise, "noise", torch.float32),) if noise is not None else ()) + (
-                             ((seeds, "seeds", torch.int64),) if seeds is not None else ()):
-        _check(torch.is_tensor(t_) and t_.is_cuda and t_.device == x.device and t_.dtype == dt,
-               f"{name} should be a {dt} tensor on x's GPU")
-    _check(coef.dim() == 2 and coef.shape[1] == 4 and coef.is_contiguous() and t_table.is_contiguous(),
-           "coef should be a contiguous [n_steps, 4] table")
-    n_steps = coef.shape[0]
-    _check(tuple(blend.shape) == (n_steps, 2) and blend.is_contiguous(), "blend should be a contiguous [n_steps, 2] table")
-    _check(t_table.numel() >= n_steps + 1, "t_table needs n_steps + 1 entries")
-    _check(step.numel() == 1 and timestep.numel() == 1, "step and timestep hold one value each")
-    n = x.numel() if n is None else int(n)
-    row_stride = n if row_stride is None else int(row_stride)
-    noise_stride = n if noise_stride is None else int(noise_stride)
-    channels = int(channels)
-    _check(0 <= n <= x.numel(), "n exceeds the state")
-    _check(z.numel() >= n and noise0.numel() >= n, "z / noise0 are smaller than the state")
-    if channels >= 1 and n % channels == 0:           # (anything else: the library's own error)
-        _check(mask.is_contiguous() and mask.numel() >= n // channels, "mask should be dense with n / channels entries")
-    if rows_per_image in (1, 2):
-        need = (rows_per_image - 1) * row_stride + n
-        _check(eps.numel() >= need and inp.numel() >= need, "eps / inp are smaller than rows_per_image row blocks")
-    if noise is not None:
-        _check(noise.numel() >= (n_steps - 1) * noise_stride + n, "noise is smaller than n_steps blocks")
-    if seeds is not None:
-        with torch.cuda.device(x.device):
-            code = _lib.mixdq_sampler_step_masked_rng(x.data_ptr(), eps.data_ptr(), inp.data_ptr(), seeds.data_ptr(),
-                                                      n_image, coef.data_ptr(), t_table.data_ptr(), n_steps,
-                                                      step.data_ptr(), timestep.data_ptr(), float(guidance), n,
-                                                      int(rows_per_image), row_stride, z.data_ptr(), noise0.data_ptr(),
-                                                      mask.data_ptr(), channels, blend.data_ptr(), _stream())
-        _status(code, "sampler_step_masked")
-        return
-    with torch.cuda.device(x.device):
-        code = _lib.mixdq_sampler_step_masked(x.data_ptr(), eps.data_ptr(), inp.data_ptr(), _ptr(noise), noise_stride,
-                                              coef.data_ptr(), t_table.data_ptr(), n_steps, step.data_ptr(),
-                                              timestep.data_ptr(), float(guidance), n, int(rows_per_image), row_stride,
-                                              z.data_ptr(), noise0.data_ptr(), mask.data_ptr(), channels,
-                                              blend.data_ptr(), _stream())
-    _status(code, "sampler_step_masked")
-
-
-_lib.mixdq_sampler_step_2m.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, ctypes.c_float, _i64, _i32,
-                                       _i64, _vp]
-_lib.mixdq_sampler_step_2m.restype = _i32
-_lib.mixdq_sampler_step_2m_masked.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, ctypes.c_float, _i64,
-                                              _i32, _i64, _vp, _vp, _vp, _i32, _vp, _vp]
-_lib.mixdq_sampler_step_2m_masked.restype = _i32
-
-
-def _check_step_2m(x, eps, inp, hist, coef8, t_table, step, first, timestep, extra, n, row_stride, rows_per_image):
-    """The checks the two multistep bindings share; returns (n_steps, n, row_stride)."""
-    for t_, name, dt in ((x, "x", torch.float32), (eps, "eps", torch.float16), (inp, "inp", torch.float16),
-                         (hist, "hist", torch.float32), (coef8, "coef8", torch.float32),
-                         (t_table, "t_table", torch.float32), (step, "step", torch.int32),
-                         (first, "first", torch.int32), (timestep, "timestep", torch.float32)) + extra:
-        _check(torch.is_tensor(t_) and t_.is_cuda and t_.device == x.device and t_.dtype == dt,
-               f"{name} should be a {dt} tensor on x's GPU")
-    _check(coef8.dim() == 2 and coef8.shape[1] == 8 and coef8.is_contiguous() and t_table.is_contiguous(),
-           "coef8 should be a contiguous [n_steps, 8] table")
-    n_steps = coef8.shape[0]
-    _check(t_table.numel() >= n_steps + 1, "t_table needs n_steps + 1 entries")
-    _check(step.numel() == 1 and first.numel() == 1 and timestep.numel() == 1,
-           "step, first and timestep hold one value each")
-    n = x.numel() if n is None else int(n)
-    row_stride = n if row_stride is None else int(row_stride)
-    _check(0 <= n <= x.numel(), "n exceeds the state")
-    _check(hist.numel() >= n, "hist is smaller than the state")
-    if rows_per_image in (1, 2):                      # (anything else: the library's own error)
-        need = (rows_per_image - 1) * row_stride + n
-        _check(eps.numel() >= need and inp.numel() >= need, "eps / inp are smaller than rows_per_image row blocks")
-    return n_steps, n, row_stride
+    _sampler_step("sampler_step_masked", x, eps, inp, coef, 4, t_table, step, timestep, guidance, rows_per_image, n,
+                  row_stride, masked=(z, noise0, mask, blend), channels=channels, noise=noise,
+                  noise_stride=noise_stride, seeds=seeds, n_image=n_image)
 
 
 def sampler_step_2m(x, eps, inp, hist, coef8, t_table, step, first, timestep, guidance=0.0, rows_per_image=1, *,
@@ -1624,14 +1584,8 @@ def sampler_step_2m(x, eps, inp, hist, coef8, t_table, step, first, timestep, gu
     hist: fp32, `n` elements in x's stride pattern, not x itself; coef8: fp32 [n_steps, 8] (Schedule.coef of
     'dpmpp_2m'): (u, v, A, B1, B2, D2, s_next, 0); first: int32 [1], the index of the run's first step.  Everything
     else as sampler_step; there is no noise operand."""
-    n_steps, n, row_stride = _check_step_2m(x, eps, inp, hist, coef8, t_table, step, first, timestep, (), n, row_stride,
-                                            rows_per_image)
-    with torch.cuda.device(x.device):
-        code = _lib.mixdq_sampler_step_2m(x.data_ptr(), eps.data_ptr(), inp.data_ptr(), hist.data_ptr(),
-                                          coef8.data_ptr(), t_table.data_ptr(), n_steps, step.data_ptr(),
-                                          first.data_ptr(), timestep.data_ptr(), float(guidance), n,
-                                          int(rows_per_image), row_stride, _stream())
-    _status(code, "sampler_step_2m")
+    _sampler_step("sampler_step_2m", x, eps, inp, coef8, 8, t_table, step, timestep, guidance, rows_per_image, n,
+                  row_stride, hist=hist, first=first)
 
 
 def sampler_step_2m_masked(x, eps, inp, hist, coef8, t_table, step, first, timestep, z, noise0, mask, blend,
@@ -1639,23 +1593,8 @@ def sampler_step_2m_masked(x, eps, inp, hist, coef8, t_table, step, first, times
     """sampler_step_2m for inpainting (mixdq_sampler_step_2m_masked): the same step, then sampler_step_masked's blend
     of the new state with the image latents at the next step's noise level.  `hist` is the unblended x0.  z, noise0,
     mask, blend and channels as in sampler_step_masked."""
-    extra = ((z, "z", torch.float32), (noise0, "noise0", torch.float32), (mask, "mask", torch.float32),
-             (blend, "blend", torch.float32))
-    n_steps, n, row_stride = _check_step_2m(x, eps, inp, hist, coef8, t_table, step, first, timestep, extra, n,
-                                            row_stride, rows_per_image)
-    _check(tuple(blend.shape) == (n_steps, 2) and blend.is_contiguous(), "blend should be a contiguous [n_steps, 2] table")
-    channels = int(channels)
-    _check(z.numel() >= n and noise0.numel() >= n, "z / noise0 are smaller than the state")
-    if channels >= 1 and n % channels == 0:           # (anything else: the library's own error)
-        _check(mask.is_contiguous() and mask.numel() >= n // channels, "mask should be dense with n / channels entries")
-    with torch.cuda.device(x.device):
-        code = _lib.mixdq_sampler_step_2m_masked(x.data_ptr(), eps.data_ptr(), inp.data_ptr(), hist.data_ptr(),
-                                                 coef8.data_ptr(), t_table.data_ptr(), n_steps, step.data_ptr(),
-                                                 first.data_ptr(), timestep.data_ptr(), float(guidance), n,
-                                                 int(rows_per_image), row_stride, z.data_ptr(), noise0.data_ptr(),
-                                                 mask.data_ptr(), channels, blend.data_ptr(), _stream())
-    _status(code, "sampler_step_2m_masked")
-
+    _sampler_step("sampler_step_2m_masked", x, eps, inp, coef8, 8, t_table, step, timestep, guidance, rows_per_image, n,
+                  row_stride, hist=hist, first=first, masked=(z, noise0, mask, blend), channels=channels)
 
 
 _lib.mixdq_image_to_nhwc8_f16.argtypes = [_vp, _i32, _i64, _i64, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _vp]

@@ -2,34 +2,40 @@
 // and the device-side step state (step index, the timestep the UNet reads) in a one-thread launch behind it.
 // No reference counterpart: the reference reaches the sampling loop only through diffusers' pipeline call.
 //
-// Euler, Euler-ancestral, DDIM and LCM with an epsilon-predicting model are one affine map with per-step scalars:
-//   e  = eps_u + g * (eps_c - eps_u)      (rows_per_image == 2; == 1: e = eps_u)
-//   x' = (a*x + b*e) + c*n                (no noise pointer: a*x + b*e)
-//   in = f16_rn(x' * s_next)              written to every UNet row of the image
-// with (a, b, c, s_next) = coef[*step] -- arithmetic: include/mixdq_math.h, FP32 round-to-nearest, no contraction.
+// Every step is ONE kernel template, sampler_step_kernel<ROWS, ORDER, NOISE, MASK>, and one per-element function
+// (step_one) built from include/mixdq_math.h -- FP32 round-to-nearest, no contraction:
+//   e   = eps_u + g * (eps_c - eps_u)                     ROWS 2 (rows_per_image; 1: e = eps_u)
+//   x'  = (a*x + b*e) + c*n                               ORDER 1; NOISE 0: a*x + b*e;  (a, b, c, s_next) = coef[*step]
+//   x0  = u*x + v*e,  x' = A*x + B*x0 [+ D*hist]          ORDER 2; (u, v, A, B1, B2, D2, s_next, 0) = coef8[*step]
+//   x'' = (1 - m)*(p*z + q*n0) + m*x'                     MASK 1, 2; (p, q) = blend[*step], m = mask[i / channels]
+//   in  = f16_rn(x'' * s_next)                            written to every UNet row of the image; x'' stored to x
+// A mode's operands are read only by the instantiations of that mode; the six mixdq_sampler_step* entry points fill
+// one operand set (StepArgs), check it (check_step) and launch (launch_step), which picks the instantiation.
 //
-// HBM-bound and small (SDXL at 1024 px: 65 536 elements per image): elementwise over storage, 8 elements per lane
-// per pass -- 16-byte accesses on the FP16 tensors, two on the FP32 ones -- and a scalar tail for n % 8 elements.
+// ORDER 1 -- Euler, Euler-ancestral, DDIM and LCM with an epsilon-predicting model -- is one affine map with per-step
+// scalars.  ORDER 2 (DPM-Solver++ 2M, mixdq_sampler_step_2m[_masked]) is NOT an affine map of (x, eps, noise): a
+// second-order step also reads the previous step's data prediction.  That one value per element is the only state a
+// multistep solver adds; it lives in a caller-owned FP32 buffer `hist`, read on second-order steps and rewritten on
+// every step, with the index of the run's first step in a device int beside the step index.  These kinds add no noise:
+// ORDER 2 exists with NOISE 0 only.
 //
-// mixdq_sampler_step_masked (inpainting) is the same step with one more map behind the update, in a sibling kernel:
-//   k   = p*z + q*n0,   x'' = (1 - m)*k + m*x'     (p, q) = blend[*step], m = mask[i / channels]
-// three more FP32 reads per element (z, n0 as 16-byte loads; the mask one value per latent pixel), x'' stored to x
-// and in = f16_rn(x'' * s_next).  The four plain instantiations are untouched by it.
-//
-// mixdq_sampler_step_2m[_masked] (DPM-Solver++ 2M) is NOT one affine map of (x, eps, noise): a second-order step also
-// reads the previous step's data prediction.  That one value per element is the only state a multistep solver adds; it
-// lives in a caller-owned FP32 buffer `hist` that a third kernel (sampler_step_2m_kernel, below the two others, which
-// it does not touch) reads and rewrites, with the index of the run's first step in a device int beside the step index.
-//
-// mixdq_sampler_step[_masked]_rng are the first two kernels in a third noise mode: n is not loaded but computed in
-// registers -- Philox4x32-10 keyed by the image's seed, counter (element / 4, *step, stream 1), then Box-Muller
+// NOISE: 0 none; 1 read from a buffer; 2 and 3 (mixdq_sampler_step[_masked]_rng) computed in registers --
+// Philox4x32-10 keyed by the image's seed, counter (element / 4, *step, stream 1), then Box-Muller
 // (include/mixdq_math.h: mixdq_rng_*) -- so a stochastic schedule needs no [n_steps, ...] noise buffer and a captured
 // graph serves every seed (the seeds are read from device memory).  mixdq_randn_f32 fills a buffer by the same rule
 // (the start noise, the VAE posterior's), mixdq_rng_normals_from_bits is the words-to-normals map alone, for tests.
 //
+// MASK (inpainting, the *_masked entry points): 0 none; 1 channels == 4; 2 any channel count.  Three more FP32 reads
+// per element (z, n0 as 16-byte loads; the mask one value per latent pixel); the blend touches x and the UNet input,
+// never `hist`.
+//
+// HBM-bound and small (SDXL at 1024 px: 65 536 elements per image): elementwise over storage, 8 elements per lane
+// per pass -- 16-byte accesses on the FP16 tensors, two on the FP32 ones -- and a scalar tail for n % 8 elements.
+//
 // The step index is read by every workgroup of the step launch and advanced by the launch BEHIND it on the same
 // stream (sampler_advance_kernel, one thread): launches of one stream run in order, so no workgroup of the step
 // can read the index after it moved, without any in-launch ticket, fence or counter to re-initialise.
+#include <type_traits>
 #include "common.h"
 #include "../../include/mixdq_math.h"
 
@@ -49,7 +55,17 @@ __device__ __forceinline__ uint32_t half_bits(float v) {
   return (uint32_t)__half_raw(f32_to_f16_rn(v)).x;
 }
 
-// NOISE, the step kernels' noise mode: 0 none, 1 read from a buffer, 2 and 3 computed in registers (mixdq_rng_*,
+__device__ __forceinline__ void load8(const float* __restrict__ p, float v[8]) {
+  const float4 lo = *reinterpret_cast<const float4*>(p), hi = *reinterpret_cast<const float4*>(p + 4);
+  v[0] = lo.x, v[1] = lo.y, v[2] = lo.z, v[3] = lo.w, v[4] = hi.x, v[5] = hi.y, v[6] = hi.z, v[7] = hi.w;
+}
+
+__device__ __forceinline__ void store8(float* __restrict__ p, const float v[8]) {
+  *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+  *reinterpret_cast<float4*>(p + 4) = make_float4(v[4], v[5], v[6], v[7]);
+}
+
+// NOISE, the step kernel's noise mode: 0 none, 1 read from a buffer, 2 and 3 computed in registers (mixdq_rng_*,
 // include/mixdq_math.h) from (seeds[image], element in the image, *step) on stream MIXDQ_RNG_STREAM_STEP.  An 8-element
 // pass starting at storage element o: 2 (n_image % 8 == 0) -- it lies inside one image and is two whole Philox calls;
 // 3 -- any n_image: one call per element, the image index carried along.  Roughly 300 vector operations per 8 elements
@@ -79,6 +95,34 @@ __device__ __forceinline__ float tail_noise(const float* __restrict__ nz, const 
   if (NOISE == 1) return nz[t];
   const int64_t b = t / n_image;
   return mixdq_rng_normal_at(seeds[b], (uint64_t)(t - b * n_image), step, MIXDQ_RNG_STREAM_STEP);
+}
+
+// The noise of the 8-element pass at storage element o; NOISE 0 leaves ns alone.
+template <int NOISE>
+__device__ __forceinline__ void noise8(const float* __restrict__ nz, const uint64_t* __restrict__ seeds, int64_t n_image,
+                                       int64_t o, uint32_t step, float ns[8]) {
+  if constexpr (NOISE == 1) load8(nz + o, ns);
+  if constexpr (NOISE >= 2) rng_noise8<NOISE == 2>(seeds, n_image, o, step, ns);
+}
+
+// The mask values of the 8-element pass at storage element o (o % 8 == 0): element i of the (channels-last) storage
+// belongs to mask entry i / channels.  MASK 1: channels == 4, the pass covers exactly two latent pixels; MASK 2: the
+// quotient and remainder of the pass's first element are divided out once and carried along.
+template <int MASK>
+__device__ __forceinline__ void mask8(const float* __restrict__ mask, int channels, int64_t o, float ms[8]) {
+  if constexpr (MASK == 1) {
+    const float m0 = mask[o >> 2], m1 = mask[(o >> 2) + 1];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) ms[j] = j < 4 ? m0 : m1;
+  } else {
+    int64_t q = o / channels;                      // o + j < n and n % channels == 0: q stays below n / channels
+    int r = (int)(o - q * channels);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      ms[j] = mask[q];
+      if (++r == channels) { r = 0; ++q; }
+    }
+  }
 }
 
 // mixdq_randn_f32: one Philox call -- four normals -- per lane per pass, grid-stride over the B * ceil(n_image / 4) calls.
@@ -118,229 +162,94 @@ __global__ __launch_bounds__(256) void normals_from_bits_kernel(const uint32_t* 
   }
 }
 
-template <int ROWS, int NOISE>
-__device__ __forceinline__ float step_one(float x, float eu, float ec, float n, float g, float a, float b, float c) {
-  const float e = ROWS == 2 ? mixdq_sampler_guided_eps(eu, ec, g) : eu;
-  return NOISE ? mixdq_sampler_update_noise(x, e, n, a, b, c) : mixdq_sampler_update(x, e, a, b);
+// The scalars of one launch: the guidance scale and row *step of the tables.  ORDER 1: (a, b, c, s_next) = coef[*step].
+// ORDER 2: a = A, d = D2 and b = B2 on a second-order step, B1 on a first-order one.  Which order a step takes depends
+// on the table and on two device scalars only -- the first executed step of a run (*step == *first) and a row with
+// D2 == 0 are first-order -- so `second` is uniform over the launch.  MASK: (p, q) = blend[*step].
+struct StepRow {
+  float g, a, b, c, u, v, d, s_next, p, q;
+  bool second;
+};
+
+// One element: guidance, the update, the blend.  n, h and (z, n0, m) are operands of NOISE != 0, of a second-order
+// step and of MASK != 0 only; ORDER 2 hands the data prediction (the next step's h, unblended) back in *x0_out.
+template <int ROWS, int ORDER, int NOISE, int MASK>
+__device__ __forceinline__ float step_one(const StepRow& k, float x, float eu, float ec, float n, float h, float z,
+                                          float n0, float m, float* x0_out) {
+  const float e = ROWS == 2 ? mixdq_sampler_guided_eps(eu, ec, k.g) : eu;
+  float y;
+  if constexpr (ORDER == 1) {
+    y = NOISE ? mixdq_sampler_update_noise(x, e, n, k.a, k.b, k.c) : mixdq_sampler_update(x, e, k.a, k.b);
+  } else {
+    const float x0 = mixdq_sampler_x0(x, e, k.u, k.v);
+    *x0_out = x0;
+    // both computed, one selected: a branch per element would cut the 8-element pass into blocks (more registers)
+    const float y1 = mixdq_sampler_update(x, x0, k.a, k.b), y2 = mixdq_sampler_update_2m(x, x0, h, k.a, k.b, k.d);
+    y = k.second ? y2 : y1;
+  }
+  return MASK ? mixdq_sampler_blend(y, z, n0, m, k.p, k.q) : y;
 }
 
-template <int ROWS, int NOISE>
-__global__ __launch_bounds__(256) void sampler_step_kernel(float* __restrict__ x, const __half* __restrict__ eps,
-                                                           __half* __restrict__ in, const float* __restrict__ noise,
-                                                           int64_t noise_stride, const float* __restrict__ coef,
-                                                           const int* __restrict__ step_p, int n_steps, float g,
-                                                           int64_t n, int64_t row_stride,
-                                                           const uint64_t* __restrict__ seeds, int64_t n_image) {
-  const int step = *step_p;
-  if (step < 0 || step >= n_steps) return;        // replayed past the table: nothing is read or written
-  const float4 k = *reinterpret_cast<const float4*>(coef + 4 * (int64_t)step);
-  const float a = k.x, b = k.y, c = k.z, s_next = k.w;
-  const float* nz = NOISE == 1 ? noise + (int64_t)step * noise_stride : nullptr;
-  const int64_t nvec = n >> 3;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += stride) {
-    const int64_t o = i << 3;
-    const float4 x0 = *reinterpret_cast<const float4*>(x + o), x1 = *reinterpret_cast<const float4*>(x + o + 4);
-    const Half8 eu = *reinterpret_cast<const Half8*>(eps + o);
-    Half8 ec = eu;
-    if (ROWS == 2) ec = *reinterpret_cast<const Half8*>(eps + row_stride + o);
-    float4 n0 = x0, n1 = x1;
-    if (NOISE == 1) {
-      n0 = *reinterpret_cast<const float4*>(nz + o);
-      n1 = *reinterpret_cast<const float4*>(nz + o + 4);
-    }
-    const float xs[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-    float ns[8] = {n0.x, n0.y, n0.z, n0.w, n1.x, n1.y, n1.z, n1.w};
-    if (NOISE >= 2) rng_noise8<NOISE == 2>(seeds, n_image, o, (uint32_t)step, ns);
-    float y[8];
-    Half8 out;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) y[j] = step_one<ROWS, NOISE>(xs[j], half_at(eu, j), half_at(ec, j), ns[j], g, a, b, c);
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      out.w[j] = half_bits(mixdq_sampler_scaled_input(y[2 * j], s_next)) |
-                 (half_bits(mixdq_sampler_scaled_input(y[2 * j + 1], s_next)) << 16);
-    *reinterpret_cast<float4*>(x + o) = make_float4(y[0], y[1], y[2], y[3]);
-    *reinterpret_cast<float4*>(x + o + 4) = make_float4(y[4], y[5], y[6], y[7]);
-    *reinterpret_cast<Half8*>(in + o) = out;
-    if (ROWS == 2) *reinterpret_cast<Half8*>(in + row_stride + o) = out;
-  }
-  // tail (n % 8 elements), by the first threads of block 0
-  const int64_t t = (nvec << 3) + threadIdx.x;
-  if (blockIdx.x == 0 && t < n) {
-    const float eu = __half2float(eps[t]);
-    const float ec = ROWS == 2 ? __half2float(eps[row_stride + t]) : eu;
-    const float y = step_one<ROWS, NOISE>(x[t], eu, ec, tail_noise<NOISE>(nz, seeds, n_image, t, (uint32_t)step), g, a, b, c);
-    const __half h = f32_to_f16_rn(mixdq_sampler_scaled_input(y, s_next));
-    x[t] = y;
-    in[t] = h;
-    if (ROWS == 2) in[row_stride + t] = h;
-  }
-}
-
-// The masked step: sampler_step_kernel's body, then mixdq_sampler_blend.  Element i of the (channels-last) storage
-// belongs to mask entry i / channels.  C4: channels == 4, an 8-element pass covers exactly two latent pixels; otherwise
-// the quotient and remainder of the pass's first element are divided out once and carried along.
-template <int ROWS, int NOISE, bool C4>
-__global__ __launch_bounds__(256) void sampler_step_masked_kernel(
-    float* __restrict__ x, const __half* __restrict__ eps, __half* __restrict__ in, const float* __restrict__ noise,
-    int64_t noise_stride, const float* __restrict__ coef, const int* __restrict__ step_p, int n_steps, float g, int64_t n,
-    int64_t row_stride, const float* __restrict__ z, const float* __restrict__ noise0, const float* __restrict__ mask,
-    int channels, const float* __restrict__ blend, const uint64_t* __restrict__ seeds, int64_t n_image) {
-  const int step = *step_p;
-  if (step < 0 || step >= n_steps) return;        // replayed past the table: nothing is read or written
-  const float4 k = *reinterpret_cast<const float4*>(coef + 4 * (int64_t)step);
-  const float a = k.x, b = k.y, c = k.z, s_next = k.w;
-  const float2 pq = *reinterpret_cast<const float2*>(blend + 2 * (int64_t)step);
-  const float* nz = NOISE == 1 ? noise + (int64_t)step * noise_stride : nullptr;
-  const int64_t nvec = n >> 3;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += stride) {
-    const int64_t o = i << 3;
-    const float4 x0 = *reinterpret_cast<const float4*>(x + o), x1 = *reinterpret_cast<const float4*>(x + o + 4);
-    const float4 z0 = *reinterpret_cast<const float4*>(z + o), z1 = *reinterpret_cast<const float4*>(z + o + 4);
-    const float4 i0 = *reinterpret_cast<const float4*>(noise0 + o), i1 = *reinterpret_cast<const float4*>(noise0 + o + 4);
-    const Half8 eu = *reinterpret_cast<const Half8*>(eps + o);
-    Half8 ec = eu;
-    if (ROWS == 2) ec = *reinterpret_cast<const Half8*>(eps + row_stride + o);
-    float4 n0 = x0, n1 = x1;
-    if (NOISE == 1) {
-      n0 = *reinterpret_cast<const float4*>(nz + o);
-      n1 = *reinterpret_cast<const float4*>(nz + o + 4);
-    }
-    float ms[8];
-    if (C4) {
-      const float m0 = mask[2 * i], m1 = mask[2 * i + 1];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) ms[j] = j < 4 ? m0 : m1;
-    } else {
-      int64_t q = o / channels;                    // o + j < n and n % channels == 0: q stays below n / channels
-      int r = (int)(o - q * channels);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        ms[j] = mask[q];
-        if (++r == channels) { r = 0; ++q; }
-      }
-    }
-    const float xs[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-    float ns[8] = {n0.x, n0.y, n0.z, n0.w, n1.x, n1.y, n1.z, n1.w};
-    if (NOISE >= 2) rng_noise8<NOISE == 2>(seeds, n_image, o, (uint32_t)step, ns);
-    const float zs[8] = {z0.x, z0.y, z0.z, z0.w, z1.x, z1.y, z1.z, z1.w};
-    const float is[8] = {i0.x, i0.y, i0.z, i0.w, i1.x, i1.y, i1.z, i1.w};
-    float y[8];
-    Half8 out;
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      y[j] = mixdq_sampler_blend(step_one<ROWS, NOISE>(xs[j], half_at(eu, j), half_at(ec, j), ns[j], g, a, b, c), zs[j],
-                                 is[j], ms[j], pq.x, pq.y);
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      out.w[j] = half_bits(mixdq_sampler_scaled_input(y[2 * j], s_next)) |
-                 (half_bits(mixdq_sampler_scaled_input(y[2 * j + 1], s_next)) << 16);
-    *reinterpret_cast<float4*>(x + o) = make_float4(y[0], y[1], y[2], y[3]);
-    *reinterpret_cast<float4*>(x + o + 4) = make_float4(y[4], y[5], y[6], y[7]);
-    *reinterpret_cast<Half8*>(in + o) = out;
-    if (ROWS == 2) *reinterpret_cast<Half8*>(in + row_stride + o) = out;
-  }
-  // tail (n % 8 elements), by the first threads of block 0
-  const int64_t t = (nvec << 3) + threadIdx.x;
-  if (blockIdx.x == 0 && t < n) {
-    const float eu = __half2float(eps[t]);
-    const float ec = ROWS == 2 ? __half2float(eps[row_stride + t]) : eu;
-    const float y = mixdq_sampler_blend(step_one<ROWS, NOISE>(x[t], eu, ec, tail_noise<NOISE>(nz, seeds, n_image, t, (uint32_t)step), g, a, b, c), z[t],
-                                        noise0[t], mask[t / channels], pq.x, pq.y);
-    const __half h = f32_to_f16_rn(mixdq_sampler_scaled_input(y, s_next));
-    x[t] = y;
-    in[t] = h;
-    if (ROWS == 2) in[row_stride + t] = h;
-  }
-}
-
-// The multistep step (DPM-Solver++ 2M, mixdq_sampler_step_2m[_masked]): the data prediction x0 = u*x + v*e, then a
-// first- or second-order update of x from x0 and the PREVIOUS step's x0, which lives in `hist` (FP32, x's layout) and is
-// replaced by this step's on every launch.  (u, v, A, B1, B2, D2, s_next, 0) = coef8[*step].  Which order a step takes
-// depends on the table and on two device scalars only -- the first executed step of a run (*step == *first) and a row
-// with D2 == 0 are first-order -- so the choice is uniform over the launch and `hist` is not read at all on a
-// first-order step: it may hold anything there.  One more FP32 read (second-order steps) and write per element than the
-// plain step; these kinds add no noise.  MASKED: 0 none, 1 the blend with channels == 4, 2 with any channel count;
-// the blend touches x and the UNet input, never `hist`.
-template <int ROWS>
-__device__ __forceinline__ float step_2m_one(float x, float eu, float ec, float h, float g, float u, float v, float A,
-                                             float B, float D, bool second, float* x0_out) {
-  const float e = ROWS == 2 ? mixdq_sampler_guided_eps(eu, ec, g) : eu;
-  const float x0 = mixdq_sampler_x0(x, e, u, v);
-  *x0_out = x0;
-  return second ? mixdq_sampler_update_2m(x, x0, h, A, B, D) : mixdq_sampler_update(x, x0, A, B);
-}
-
-template <int ROWS, int MASKED>
-__global__ __launch_bounds__(256) void sampler_step_2m_kernel(
-    float* __restrict__ x, const __half* __restrict__ eps, __half* __restrict__ in, float* __restrict__ hist,
-    const float* __restrict__ coef8, const int* __restrict__ step_p, const int* __restrict__ first_p, int n_steps, float g,
-    int64_t n, int64_t row_stride, const float* __restrict__ z, const float* __restrict__ noise0,
+// `table` is coef (ORDER 1) or coef8 (ORDER 2).  (noise, noise_stride): NOISE 1; (seeds, n_image): NOISE 2, 3;
+// (hist, first_p): ORDER 2, and `hist` is not read at all on a first-order step: it may hold anything there;
+// (z, noise0, mask, channels, blend): MASK 1, 2.  The other instantiations never touch them (they are passed null).
+template <int ROWS, int ORDER, int NOISE, int MASK>
+__global__ __launch_bounds__(256) void sampler_step_kernel(
+    float* __restrict__ x, const __half* __restrict__ eps, __half* __restrict__ in, const float* __restrict__ table,
+    const int* __restrict__ step_p, int n_steps, float g, int64_t n, int64_t row_stride, const float* __restrict__ noise,
+    int64_t noise_stride, const uint64_t* __restrict__ seeds, int64_t n_image, float* __restrict__ hist,
+    const int* __restrict__ first_p, const float* __restrict__ z, const float* __restrict__ noise0,
     const float* __restrict__ mask, int channels, const float* __restrict__ blend) {
+  static_assert(ORDER == 1 || (ORDER == 2 && NOISE == 0), "the multistep kinds add no noise");
   const int step = *step_p;
   if (step < 0 || step >= n_steps) return;        // replayed past the table: nothing is read or written
-  const float4 k0 = *reinterpret_cast<const float4*>(coef8 + 8 * (int64_t)step);
-  const float4 k1 = *reinterpret_cast<const float4*>(coef8 + 8 * (int64_t)step + 4);
-  const float u = k0.x, v = k0.y, A = k0.z, D = k1.y, s_next = k1.z;
-  const bool second = step > *first_p && D != 0.0f;
-  const float B = second ? k1.x : k0.w;
-  float2 pq = make_float2(1.0f, 0.0f);
-  if (MASKED) pq = *reinterpret_cast<const float2*>(blend + 2 * (int64_t)step);
+  StepRow k = {};
+  k.g = g;
+  if constexpr (ORDER == 1) {
+    const float4 r = *reinterpret_cast<const float4*>(table + 4 * (int64_t)step);
+    k.a = r.x, k.b = r.y, k.c = r.z, k.s_next = r.w;
+  } else {
+    const float4 r0 = *reinterpret_cast<const float4*>(table + 8 * (int64_t)step);
+    const float4 r1 = *reinterpret_cast<const float4*>(table + 8 * (int64_t)step + 4);
+    k.u = r0.x, k.v = r0.y, k.a = r0.z, k.d = r1.y, k.s_next = r1.z;
+    k.second = step > *first_p && k.d != 0.0f;
+    k.b = k.second ? r1.x : r0.w;
+  }
+  if constexpr (MASK != 0) {
+    const float2 pq = *reinterpret_cast<const float2*>(blend + 2 * (int64_t)step);
+    k.p = pq.x, k.q = pq.y;
+  }
+  const float* nz = NOISE == 1 ? noise + (int64_t)step * noise_stride : nullptr;
   const int64_t nvec = n >> 3;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += stride) {
     const int64_t o = i << 3;
-    const float4 x0 = *reinterpret_cast<const float4*>(x + o), x1 = *reinterpret_cast<const float4*>(x + o + 4);
+    float xs[8], ns[8] = {}, hs[8] = {}, zs[8] = {}, is[8] = {}, ms[8] = {};
+    load8(x + o, xs);
     const Half8 eu = *reinterpret_cast<const Half8*>(eps + o);
     Half8 ec = eu;
     if (ROWS == 2) ec = *reinterpret_cast<const Half8*>(eps + row_stride + o);
-    float4 h0 = x0, h1 = x1;
-    if (second) {
-      h0 = *reinterpret_cast<const float4*>(hist + o);
-      h1 = *reinterpret_cast<const float4*>(hist + o + 4);
+    noise8<NOISE>(nz, seeds, n_image, o, (uint32_t)step, ns);
+    if constexpr (ORDER == 2) {
+      if (k.second) load8(hist + o, hs);
     }
-    float4 z0 = x0, z1 = x1, i0 = x0, i1 = x1;
-    float ms[8];
-    if (MASKED) {
-      z0 = *reinterpret_cast<const float4*>(z + o);
-      z1 = *reinterpret_cast<const float4*>(z + o + 4);
-      i0 = *reinterpret_cast<const float4*>(noise0 + o);
-      i1 = *reinterpret_cast<const float4*>(noise0 + o + 4);
-      if (MASKED == 1) {
-        const float m0 = mask[2 * i], m1 = mask[2 * i + 1];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) ms[j] = j < 4 ? m0 : m1;
-      } else {
-        int64_t q = o / channels;                  // o + j < n and n % channels == 0: q stays below n / channels
-        int r = (int)(o - q * channels);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          ms[j] = mask[q];
-          if (++r == channels) { r = 0; ++q; }
-        }
-      }
+    if constexpr (MASK != 0) {
+      load8(z + o, zs);
+      load8(noise0 + o, is);
+      mask8<MASK>(mask, channels, o, ms);
     }
-    const float xs[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-    const float hs[8] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
-    const float zs[8] = {z0.x, z0.y, z0.z, z0.w, z1.x, z1.y, z1.z, z1.w};
-    const float is[8] = {i0.x, i0.y, i0.z, i0.w, i1.x, i1.y, i1.z, i1.w};
     float y[8], p0[8];
     Half8 out;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      y[j] = step_2m_one<ROWS>(xs[j], half_at(eu, j), half_at(ec, j), hs[j], g, u, v, A, B, D, second, &p0[j]);
-      if (MASKED) y[j] = mixdq_sampler_blend(y[j], zs[j], is[j], ms[j], pq.x, pq.y);
-    }
+    for (int j = 0; j < 8; ++j)
+      y[j] = step_one<ROWS, ORDER, NOISE, MASK>(k, xs[j], half_at(eu, j), half_at(ec, j), ns[j], hs[j], zs[j], is[j],
+                                                ms[j], &p0[j]);
 #pragma unroll
     for (int j = 0; j < 4; ++j)
-      out.w[j] = half_bits(mixdq_sampler_scaled_input(y[2 * j], s_next)) |
-                 (half_bits(mixdq_sampler_scaled_input(y[2 * j + 1], s_next)) << 16);
-    *reinterpret_cast<float4*>(hist + o) = make_float4(p0[0], p0[1], p0[2], p0[3]);
-    *reinterpret_cast<float4*>(hist + o + 4) = make_float4(p0[4], p0[5], p0[6], p0[7]);
-    *reinterpret_cast<float4*>(x + o) = make_float4(y[0], y[1], y[2], y[3]);
-    *reinterpret_cast<float4*>(x + o + 4) = make_float4(y[4], y[5], y[6], y[7]);
+      out.w[j] = half_bits(mixdq_sampler_scaled_input(y[2 * j], k.s_next)) |
+                 (half_bits(mixdq_sampler_scaled_input(y[2 * j + 1], k.s_next)) << 16);
+    if constexpr (ORDER == 2) store8(hist + o, p0);
+    store8(x + o, y);
     *reinterpret_cast<Half8*>(in + o) = out;
     if (ROWS == 2) *reinterpret_cast<Half8*>(in + row_stride + o) = out;
   }
@@ -349,12 +258,15 @@ __global__ __launch_bounds__(256) void sampler_step_2m_kernel(
   if (blockIdx.x == 0 && t < n) {
     const float eu = __half2float(eps[t]);
     const float ec = ROWS == 2 ? __half2float(eps[row_stride + t]) : eu;
-    const float xt = x[t];
-    float p0;
-    float y = step_2m_one<ROWS>(xt, eu, ec, second ? hist[t] : xt, g, u, v, A, B, D, second, &p0);
-    if (MASKED) y = mixdq_sampler_blend(y, z[t], noise0[t], mask[t / channels], pq.x, pq.y);
-    const __half h = f32_to_f16_rn(mixdq_sampler_scaled_input(y, s_next));
-    hist[t] = p0;
+    float hv = 0.0f, zv = 0.0f, iv = 0.0f, mv = 0.0f, p0;
+    if constexpr (ORDER == 2) {
+      if (k.second) hv = hist[t];
+    }
+    if constexpr (MASK != 0) zv = z[t], iv = noise0[t], mv = mask[t / channels];
+    const float y = step_one<ROWS, ORDER, NOISE, MASK>(
+        k, x[t], eu, ec, tail_noise<NOISE>(nz, seeds, n_image, t, (uint32_t)step), hv, zv, iv, mv, &p0);
+    const __half h = f32_to_f16_rn(mixdq_sampler_scaled_input(y, k.s_next));
+    if constexpr (ORDER == 2) hist[t] = p0;
     x[t] = y;
     in[t] = h;
     if (ROWS == 2) in[row_stride + t] = h;
@@ -369,25 +281,102 @@ __global__ void sampler_advance_kernel(const float* __restrict__ t_table, int n_
   *step_p = step + 1;
 }
 
-// The argument checks of both entry points, in mixdq_sampler_step's order.
-int check_step_args(const float* x, const void* eps_f16, const void* in_f16, const float* noise_or_null,
-                    int64_t noise_stride, const float* coef, const float* t_table, int n_steps, const int* step,
-                    const float* timestep, int64_t n, int rows_per_image, int64_t row_stride) {
-  if (!x || !eps_f16 || !in_f16 || !coef || !t_table || !step || !timestep) return MIXDQ_ERR_INVALID_ARG;
-  if (n < 0 || n_steps < 1 || (rows_per_image != 1 && rows_per_image != 2)) return MIXDQ_ERR_INVALID_ARG;
-  if (rows_per_image == 2 && row_stride < n) return MIXDQ_ERR_INVALID_ARG;      // the two row blocks would overlap
-  if (noise_or_null && noise_stride < n) return MIXDQ_ERR_INVALID_ARG;
-  if ((uintptr_t)x % 16 || (uintptr_t)eps_f16 % 16 || (uintptr_t)in_f16 % 16 || (uintptr_t)coef % 16 ||
-      (uintptr_t)noise_or_null % 16 || (uintptr_t)t_table % 4 || (uintptr_t)step % 4 || (uintptr_t)timestep % 4)
+// The operand set of one step.  The first block is every entry point's (`table`: coef, or coef8 where multistep);
+// an entry point sets `rng` / `multistep` / `masked` and the operands of that mode, which are checked and read only then.
+struct StepArgs {
+  float* x;
+  const void *eps_f16;
+  void* in_f16;
+  const float *table, *t_table;
+  int n_steps;
+  int* step;
+  float* timestep;
+  float guidance;
+  int64_t n;
+  int rows_per_image;
+  int64_t row_stride;
+  const float* noise = nullptr;                    // the plain entry points' noise_or_null
+  int64_t noise_stride = 0;
+  bool rng = false, multistep = false, masked = false;
+  const uint64_t* seeds = nullptr;
+  int64_t n_image = 0;
+  float* hist = nullptr;
+  const int* first = nullptr;
+  const float *z = nullptr, *noise0 = nullptr, *mask = nullptr, *blend = nullptr;
+  int channels = 1;
+
+  void set_masked(const float* z_, const float* noise0_, const float* mask_, int channels_, const float* blend_) {
+    masked = true, z = z_, noise0 = noise0_, mask = mask_, channels = channels_, blend = blend_;
+  }
+};
+
+// The argument checks of every entry point, in one order: the base operands, then those of rng, multistep, masked.
+int check_step(const StepArgs& a) {
+  if (!a.x || !a.eps_f16 || !a.in_f16 || !a.table || !a.t_table || !a.step || !a.timestep) return MIXDQ_ERR_INVALID_ARG;
+  if (a.n < 0 || a.n_steps < 1 || (a.rows_per_image != 1 && a.rows_per_image != 2)) return MIXDQ_ERR_INVALID_ARG;
+  if (a.rows_per_image == 2 && a.row_stride < a.n) return MIXDQ_ERR_INVALID_ARG;  // the two row blocks would overlap
+  if (a.noise && a.noise_stride < a.n) return MIXDQ_ERR_INVALID_ARG;
+  if ((uintptr_t)a.x % 16 || (uintptr_t)a.eps_f16 % 16 || (uintptr_t)a.in_f16 % 16 || (uintptr_t)a.table % 16 ||
+      (uintptr_t)a.noise % 16 || (uintptr_t)a.t_table % 4 || (uintptr_t)a.step % 4 || (uintptr_t)a.timestep % 4)
     return MIXDQ_ERR_ALIGNMENT;
-  if ((rows_per_image == 2 && row_stride % 8) || (noise_or_null && noise_stride % 4)) return MIXDQ_ERR_ALIGNMENT;
+  if ((a.rows_per_image == 2 && a.row_stride % 8) || (a.noise && a.noise_stride % 4)) return MIXDQ_ERR_ALIGNMENT;
+  if (a.rng) {
+    if (!a.seeds || a.n_image < 1 || a.n % a.n_image) return MIXDQ_ERR_INVALID_ARG;
+    if ((uintptr_t)a.seeds % 8) return MIXDQ_ERR_ALIGNMENT;
+  }
+  if (a.multistep) {
+    if (!a.hist || !a.first) return MIXDQ_ERR_INVALID_ARG;
+    if (a.hist < a.x + a.n && a.x < a.hist + a.n) return MIXDQ_ERR_INVALID_ARG;  // the history is a buffer of its own
+    if ((uintptr_t)a.hist % 16 || (uintptr_t)a.first % 4) return MIXDQ_ERR_ALIGNMENT;
+  }
+  if (a.masked) {
+    if (!a.z || !a.noise0 || !a.mask || !a.blend || a.channels < 1 || a.n % a.channels) return MIXDQ_ERR_INVALID_ARG;
+    if ((uintptr_t)a.z % 16 || (uintptr_t)a.noise0 % 16 || (uintptr_t)a.mask % 4 || (uintptr_t)a.blend % 8)
+      return MIXDQ_ERR_ALIGNMENT;
+  }
   return MIXDQ_OK;
 }
 
-int step_blocks(int64_t n) {
-  int64_t blocks = ((n >> 3) + 255) / 256;
+// Blocks of 256 lanes for `items` grid-stride items (8-element passes of a step, Philox calls of a fill).
+int grid_blocks(int64_t items) {
+  int64_t blocks = (items + 255) / 256;
   if (blocks > (int64_t)kNumCU * 8) blocks = (int64_t)kNumCU * 8;
   return blocks < 1 ? 1 : (int)blocks;
+}
+
+// f(std::integral_constant<int, V>) for the V among Vs that equals v: a runtime mode becomes a template argument.
+template <int... Vs, class F>
+void with_constant(int v, F&& f) {
+  ((v == Vs ? (void)f(std::integral_constant<int, Vs>{}) : (void)0), ...);
+}
+
+// Check, launch the instantiation the operand set asks for, then the advance.  n == 0 launches the advance alone.
+int launch_step(const StepArgs& a, mixdq_stream_t stream_) {
+  const int bad = check_step(a);
+  if (bad != MIXDQ_OK) return bad;
+  hipStream_t stream = (hipStream_t)stream_;
+  if (a.n > 0) {
+    const int noise = a.rng ? (a.n_image % 8 == 0 ? 2 : 3) : (a.noise ? 1 : 0);
+    const int mask = a.masked ? (a.channels == 4 ? 1 : 2) : 0;
+    with_constant<1, 2>(a.rows_per_image, [&](auto rows) {
+      with_constant<1, 2>(a.multistep ? 2 : 1, [&](auto order) {
+        with_constant<0, 1, 2, 3>(noise, [&](auto nz) {
+          with_constant<0, 1, 2>(mask, [&](auto m) {
+            constexpr int ROWS = decltype(rows)::value, ORDER = decltype(order)::value;
+            constexpr int NOISE = decltype(nz)::value, MASK = decltype(m)::value;
+            if constexpr (ORDER == 1 || NOISE == 0)
+              sampler_step_kernel<ROWS, ORDER, NOISE, MASK><<<grid_blocks(a.n >> 3), 256, 0, stream>>>(
+                  a.x, (const __half*)a.eps_f16, (__half*)a.in_f16, a.table, a.step, a.n_steps, a.guidance, a.n,
+                  a.row_stride, a.noise, a.noise_stride, a.seeds, a.n_image, a.hist, a.first, a.z, a.noise0, a.mask,
+                  a.channels, a.blend);
+          });
+        });
+      });
+    });
+    if (hipGetLastError() != hipSuccess) return MIXDQ_ERR_LAUNCH;
+  }
+  sampler_advance_kernel<<<1, 1, 0, stream>>>(a.t_table, a.n_steps, a.step, a.timestep);
+  return launch_status();
 }
 
 }  // namespace
@@ -399,27 +388,9 @@ extern "C" int mixdq_sampler_step(float* x, const void* eps_f16, void* in_f16, c
                                   int64_t noise_stride, const float* coef, const float* t_table, int n_steps,
                                   int* step, float* timestep, float guidance, int64_t n, int rows_per_image,
                                   int64_t row_stride, mixdq_stream_t stream_) {
-  const int bad = check_step_args(x, eps_f16, in_f16, noise_or_null, noise_stride, coef, t_table, n_steps, step, timestep,
-                                  n, rows_per_image, row_stride);
-  if (bad != MIXDQ_OK) return bad;
-  hipStream_t stream = (hipStream_t)stream_;
-  if (n > 0) {
-    const int blocks = step_blocks(n);
-    const __half* eps = (const __half*)eps_f16;
-    __half* in = (__half*)in_f16;
-#define S_LAUNCH(R, NZ)                                                                               \
-  sampler_step_kernel<R, NZ><<<blocks, 256, 0, stream>>>(x, eps, in, noise_or_null, noise_stride, coef, step, \
-                                                         n_steps, guidance, n, row_stride, nullptr, 0)
-    if (rows_per_image == 2) {
-      if (noise_or_null) S_LAUNCH(2, 1); else S_LAUNCH(2, 0);
-    } else {
-      if (noise_or_null) S_LAUNCH(1, 1); else S_LAUNCH(1, 0);
-    }
-#undef S_LAUNCH
-    if (hipGetLastError() != hipSuccess) return MIXDQ_ERR_LAUNCH;
-  }
-  sampler_advance_kernel<<<1, 1, 0, stream>>>(t_table, n_steps, step, timestep);
-  return launch_status();
+  StepArgs a = {x, eps_f16, in_f16, coef, t_table, n_steps, step, timestep, guidance, n, rows_per_image, row_stride};
+  a.noise = noise_or_null, a.noise_stride = noise_stride;
+  return launch_step(a, stream_);
 }
 
 extern "C" int mixdq_sampler_step_masked(float* x, const void* eps_f16, void* in_f16, const float* noise_or_null,
@@ -427,56 +398,13 @@ extern "C" int mixdq_sampler_step_masked(float* x, const void* eps_f16, void* in
                                          int* step, float* timestep, float guidance, int64_t n, int rows_per_image,
                                          int64_t row_stride, const float* z, const float* noise0, const float* mask,
                                          int channels, const float* blend, mixdq_stream_t stream_) {
-  const int bad = check_step_args(x, eps_f16, in_f16, noise_or_null, noise_stride, coef, t_table, n_steps, step, timestep,
-                                  n, rows_per_image, row_stride);
-  if (bad != MIXDQ_OK) return bad;
-  if (!z || !noise0 || !mask || !blend || channels < 1 || n % channels) return MIXDQ_ERR_INVALID_ARG;
-  if ((uintptr_t)z % 16 || (uintptr_t)noise0 % 16 || (uintptr_t)mask % 4 || (uintptr_t)blend % 8)
-    return MIXDQ_ERR_ALIGNMENT;
-  hipStream_t stream = (hipStream_t)stream_;
-  if (n > 0) {
-    const int blocks = step_blocks(n);
-    const __half* eps = (const __half*)eps_f16;
-    __half* in = (__half*)in_f16;
-#define M_LAUNCH(R, NZ, C4)                                                                                          \
-  sampler_step_masked_kernel<R, NZ, C4><<<blocks, 256, 0, stream>>>(x, eps, in, noise_or_null, noise_stride, coef, step, \
-                                                                    n_steps, guidance, n, row_stride, z, noise0, mask,   \
-                                                                    channels, blend, nullptr, 0)
-#define M_LAUNCH_C(R, NZ) \
-  do { if (channels == 4) M_LAUNCH(R, NZ, true); else M_LAUNCH(R, NZ, false); } while (0)
-    if (rows_per_image == 2) {
-      if (noise_or_null) M_LAUNCH_C(2, 1); else M_LAUNCH_C(2, 0);
-    } else {
-      if (noise_or_null) M_LAUNCH_C(1, 1); else M_LAUNCH_C(1, 0);
-    }
-#undef M_LAUNCH_C
-#undef M_LAUNCH
-    if (hipGetLastError() != hipSuccess) return MIXDQ_ERR_LAUNCH;
-  }
-  sampler_advance_kernel<<<1, 1, 0, stream>>>(t_table, n_steps, step, timestep);
-  return launch_status();
+  StepArgs a = {x, eps_f16, in_f16, coef, t_table, n_steps, step, timestep, guidance, n, rows_per_image, row_stride};
+  a.noise = noise_or_null, a.noise_stride = noise_stride;
+  a.set_masked(z, noise0, mask, channels, blend);
+  return launch_step(a, stream_);
 }
 
 // ---- noise made on the device ------------------------------------------------------------------------------------------
-namespace mixdq {
-namespace {
-
-int quad_blocks(int64_t quads) {
-  int64_t blocks = (quads + 255) / 256;
-  if (blocks > (int64_t)kNumCU * 8) blocks = (int64_t)kNumCU * 8;
-  return blocks < 1 ? 1 : (int)blocks;
-}
-
-// What the two _rng entry points check beyond check_step_args.
-int check_rng_args(const uint64_t* seeds, int64_t n_image, int64_t n) {
-  if (!seeds || n_image < 1 || n % n_image) return MIXDQ_ERR_INVALID_ARG;
-  if ((uintptr_t)seeds % 8) return MIXDQ_ERR_ALIGNMENT;
-  return MIXDQ_OK;
-}
-
-}  // namespace
-}  // namespace mixdq
-
 extern "C" int mixdq_randn_f32(float* out, int B, int64_t n_image, const uint64_t* seeds_device, uint32_t rstream,
                                uint32_t step, mixdq_stream_t stream_) {
   if (!out || !seeds_device || B < 0 || n_image < 1) return MIXDQ_ERR_INVALID_ARG;
@@ -485,7 +413,7 @@ extern "C" int mixdq_randn_f32(float* out, int B, int64_t n_image, const uint64_
   if (B == 0) return MIXDQ_OK;
   hipStream_t stream = (hipStream_t)stream_;
   const int64_t qpi = (n_image + 3) / 4, total = qpi * B;
-  const int blocks = quad_blocks(total);
+  const int blocks = grid_blocks(total);
   if (vec) randn_kernel<true><<<blocks, 256, 0, stream>>>(out, n_image, qpi, total, seeds_device, rstream, step);
   else randn_kernel<false><<<blocks, 256, 0, stream>>>(out, n_image, qpi, total, seeds_device, rstream, step);
   return launch_status();
@@ -495,7 +423,7 @@ extern "C" int mixdq_rng_normals_from_bits(const uint32_t* r, float* z, int64_t 
   if (!r || !z || n_quads < 0) return MIXDQ_ERR_INVALID_ARG;
   if ((uintptr_t)r % 16 || (uintptr_t)z % 16) return MIXDQ_ERR_ALIGNMENT;
   if (n_quads == 0) return MIXDQ_OK;
-  normals_from_bits_kernel<<<quad_blocks(n_quads), 256, 0, (hipStream_t)stream_>>>(r, z, n_quads);
+  normals_from_bits_kernel<<<grid_blocks(n_quads), 256, 0, (hipStream_t)stream_>>>(r, z, n_quads);
   return launch_status();
 }
 
@@ -503,28 +431,9 @@ extern "C" int mixdq_sampler_step_rng(float* x, const void* eps_f16, void* in_f1
                                       int64_t n_image, const float* coef, const float* t_table, int n_steps, int* step,
                                       float* timestep, float guidance, int64_t n, int rows_per_image, int64_t row_stride,
                                       mixdq_stream_t stream_) {
-  int bad = check_step_args(x, eps_f16, in_f16, nullptr, 0, coef, t_table, n_steps, step, timestep, n, rows_per_image,
-                            row_stride);
-  if (bad == MIXDQ_OK) bad = check_rng_args(seeds, n_image, n);
-  if (bad != MIXDQ_OK) return bad;
-  hipStream_t stream = (hipStream_t)stream_;
-  if (n > 0) {
-    const int blocks = step_blocks(n);
-    const __half* eps = (const __half*)eps_f16;
-    __half* in = (__half*)in_f16;
-#define R_LAUNCH(R, NZ)                                                                                             \
-  sampler_step_kernel<R, NZ><<<blocks, 256, 0, stream>>>(x, eps, in, nullptr, 0, coef, step, n_steps, guidance, n, \
-                                                         row_stride, seeds, n_image)
-    if (rows_per_image == 2) {
-      if (n_image % 8 == 0) R_LAUNCH(2, 2); else R_LAUNCH(2, 3);
-    } else {
-      if (n_image % 8 == 0) R_LAUNCH(1, 2); else R_LAUNCH(1, 3);
-    }
-#undef R_LAUNCH
-    if (hipGetLastError() != hipSuccess) return MIXDQ_ERR_LAUNCH;
-  }
-  sampler_advance_kernel<<<1, 1, 0, stream>>>(t_table, n_steps, step, timestep);
-  return launch_status();
+  StepArgs a = {x, eps_f16, in_f16, coef, t_table, n_steps, step, timestep, guidance, n, rows_per_image, row_stride};
+  a.rng = true, a.seeds = seeds, a.n_image = n_image;
+  return launch_step(a, stream_);
 }
 
 extern "C" int mixdq_sampler_step_masked_rng(float* x, const void* eps_f16, void* in_f16, const uint64_t* seeds,
@@ -532,73 +441,20 @@ extern "C" int mixdq_sampler_step_masked_rng(float* x, const void* eps_f16, void
                                              int* step, float* timestep, float guidance, int64_t n, int rows_per_image,
                                              int64_t row_stride, const float* z, const float* noise0, const float* mask,
                                              int channels, const float* blend, mixdq_stream_t stream_) {
-  int bad = check_step_args(x, eps_f16, in_f16, nullptr, 0, coef, t_table, n_steps, step, timestep, n, rows_per_image,
-                            row_stride);
-  if (bad == MIXDQ_OK) bad = check_rng_args(seeds, n_image, n);
-  if (bad != MIXDQ_OK) return bad;
-  if (!z || !noise0 || !mask || !blend || channels < 1 || n % channels) return MIXDQ_ERR_INVALID_ARG;
-  if ((uintptr_t)z % 16 || (uintptr_t)noise0 % 16 || (uintptr_t)mask % 4 || (uintptr_t)blend % 8)
-    return MIXDQ_ERR_ALIGNMENT;
-  hipStream_t stream = (hipStream_t)stream_;
-  if (n > 0) {
-    const int blocks = step_blocks(n);
-    const __half* eps = (const __half*)eps_f16;
-    __half* in = (__half*)in_f16;
-#define MR_LAUNCH(R, NZ, C4)                                                                                          \
-  sampler_step_masked_kernel<R, NZ, C4><<<blocks, 256, 0, stream>>>(x, eps, in, nullptr, 0, coef, step, n_steps,      \
-                                                                    guidance, n, row_stride, z, noise0, mask, channels, \
-                                                                    blend, seeds, n_image)
-#define MR_LAUNCH_C(R, NZ) \
-  do { if (channels == 4) MR_LAUNCH(R, NZ, true); else MR_LAUNCH(R, NZ, false); } while (0)
-    if (rows_per_image == 2) {
-      if (n_image % 8 == 0) MR_LAUNCH_C(2, 2); else MR_LAUNCH_C(2, 3);
-    } else {
-      if (n_image % 8 == 0) MR_LAUNCH_C(1, 2); else MR_LAUNCH_C(1, 3);
-    }
-#undef MR_LAUNCH_C
-#undef MR_LAUNCH
-    if (hipGetLastError() != hipSuccess) return MIXDQ_ERR_LAUNCH;
-  }
-  sampler_advance_kernel<<<1, 1, 0, stream>>>(t_table, n_steps, step, timestep);
-  return launch_status();
+  StepArgs a = {x, eps_f16, in_f16, coef, t_table, n_steps, step, timestep, guidance, n, rows_per_image, row_stride};
+  a.rng = true, a.seeds = seeds, a.n_image = n_image;
+  a.set_masked(z, noise0, mask, channels, blend);
+  return launch_step(a, stream_);
 }
 
-namespace mixdq {
-namespace {
-
-// What the two multistep entry points check beyond check_step_args (which sees coef8 as its table).
-int check_2m_args(const float* x, const float* hist, const float* coef8, const int* first, int64_t n) {
-  if (!hist || !coef8 || !first) return MIXDQ_ERR_INVALID_ARG;
-  if (hist < x + n && x < hist + n) return MIXDQ_ERR_INVALID_ARG;                // the history is a buffer of its own
-  if ((uintptr_t)hist % 16 || (uintptr_t)coef8 % 16 || (uintptr_t)first % 4) return MIXDQ_ERR_ALIGNMENT;
-  return MIXDQ_OK;
-}
-
-}  // namespace
-}  // namespace mixdq
-
+// ---- the multistep kinds: `hist` and `first` beside the base operands, coef8 as the table -----------------------------
 extern "C" int mixdq_sampler_step_2m(float* x, const void* eps_f16, void* in_f16, float* hist, const float* coef8,
                                      const float* t_table, int n_steps, int* step, const int* first, float* timestep,
                                      float guidance, int64_t n, int rows_per_image, int64_t row_stride,
                                      mixdq_stream_t stream_) {
-  int bad = check_step_args(x, eps_f16, in_f16, nullptr, 0, coef8, t_table, n_steps, step, timestep, n, rows_per_image,
-                            row_stride);
-  if (bad == MIXDQ_OK) bad = check_2m_args(x, hist, coef8, first, n);
-  if (bad != MIXDQ_OK) return bad;
-  hipStream_t stream = (hipStream_t)stream_;
-  if (n > 0) {
-    const int blocks = step_blocks(n);
-    const __half* eps = (const __half*)eps_f16;
-    __half* in = (__half*)in_f16;
-#define S2_LAUNCH(R)                                                                                                  \
-  sampler_step_2m_kernel<R, 0><<<blocks, 256, 0, stream>>>(x, eps, in, hist, coef8, step, first, n_steps, guidance, n, \
-                                                           row_stride, nullptr, nullptr, nullptr, 1, nullptr)
-    if (rows_per_image == 2) S2_LAUNCH(2); else S2_LAUNCH(1);
-#undef S2_LAUNCH
-    if (hipGetLastError() != hipSuccess) return MIXDQ_ERR_LAUNCH;
-  }
-  sampler_advance_kernel<<<1, 1, 0, stream>>>(t_table, n_steps, step, timestep);
-  return launch_status();
+  StepArgs a = {x, eps_f16, in_f16, coef8, t_table, n_steps, step, timestep, guidance, n, rows_per_image, row_stride};
+  a.multistep = true, a.hist = hist, a.first = first;
+  return launch_step(a, stream_);
 }
 
 extern "C" int mixdq_sampler_step_2m_masked(float* x, const void* eps_f16, void* in_f16, float* hist, const float* coef8,
@@ -606,29 +462,8 @@ extern "C" int mixdq_sampler_step_2m_masked(float* x, const void* eps_f16, void*
                                             float* timestep, float guidance, int64_t n, int rows_per_image,
                                             int64_t row_stride, const float* z, const float* noise0, const float* mask,
                                             int channels, const float* blend, mixdq_stream_t stream_) {
-  int bad = check_step_args(x, eps_f16, in_f16, nullptr, 0, coef8, t_table, n_steps, step, timestep, n, rows_per_image,
-                            row_stride);
-  if (bad == MIXDQ_OK) bad = check_2m_args(x, hist, coef8, first, n);
-  if (bad != MIXDQ_OK) return bad;
-  if (!z || !noise0 || !mask || !blend || channels < 1 || n % channels) return MIXDQ_ERR_INVALID_ARG;
-  if ((uintptr_t)z % 16 || (uintptr_t)noise0 % 16 || (uintptr_t)mask % 4 || (uintptr_t)blend % 8)
-    return MIXDQ_ERR_ALIGNMENT;
-  hipStream_t stream = (hipStream_t)stream_;
-  if (n > 0) {
-    const int blocks = step_blocks(n);
-    const __half* eps = (const __half*)eps_f16;
-    __half* in = (__half*)in_f16;
-#define M2_LAUNCH(R, M)                                                                                               \
-  sampler_step_2m_kernel<R, M><<<blocks, 256, 0, stream>>>(x, eps, in, hist, coef8, step, first, n_steps, guidance, n, \
-                                                           row_stride, z, noise0, mask, channels, blend)
-    if (rows_per_image == 2) {
-      if (channels == 4) M2_LAUNCH(2, 1); else M2_LAUNCH(2, 2);
-    } else {
-      if (channels == 4) M2_LAUNCH(1, 1); else M2_LAUNCH(1, 2);
-    }
-#undef M2_LAUNCH
-    if (hipGetLastError() != hipSuccess) return MIXDQ_ERR_LAUNCH;
-  }
-  sampler_advance_kernel<<<1, 1, 0, stream>>>(t_table, n_steps, step, timestep);
-  return launch_status();
+  StepArgs a = {x, eps_f16, in_f16, coef8, t_table, n_steps, step, timestep, guidance, n, rows_per_image, row_stride};
+  a.multistep = true, a.hist = hist, a.first = first;
+  a.set_masked(z, noise0, mask, channels, blend);
+  return launch_step(a, stream_);
 }

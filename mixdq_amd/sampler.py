@@ -344,13 +344,24 @@ class Sampler:
         n = B * C * H * W
         if self.schedule.uses_noise and not rng and self._noise is None:
             self._noise = self._nhwc(self.n_steps, B, dtype=torch.float32)
-        rng_args = dict(seeds=self._seeds, n_image=C * H * W) if rng else {}
-        step_noise = None if rng else self._noise
         if masked and not hasattr(self, "_z"):
             self._z = self._nhwc(B, dtype=torch.float32)
             self._noise0 = self._nhwc(B, dtype=torch.float32)
             self._mask = torch.zeros(B, H, W, dtype=torch.float32, device=dev)
             self._blend = torch.from_numpy(self.schedule.blend).to(dev)
+        # the binding and its operands behind (x, eps): chosen once, here, not inside one_step
+        blend = (self._z, self._noise0, self._mask, self._blend) if masked else ()
+        kw = dict(channels=C, n=n) if masked else dict(n=n)
+        if self.schedule.order == 2:
+            step_fn = _C.sampler_step_2m_masked if masked else _C.sampler_step_2m
+            tail = (self._in, self._hist, self._coef, self._t_table, self._step, self._first, self._t, *blend,
+                    self.guidance_scale, self.rows_per_image)
+        else:
+            step_fn = _C.sampler_step_masked if masked else _C.sampler_step
+            tail = (self._in, self._coef, self._t_table, self._step, self._t, *blend, self.guidance_scale,
+                    self.rows_per_image, None if rng else self._noise)
+            if rng:
+                kw.update(seeds=self._seeds, n_image=C * H * W)
 
         cond_kw = {} if self._cond_term is None else {"cond_term": self._cond_term}
 
@@ -360,20 +371,7 @@ class Sampler:
                     or any(a != b for a, b, d in zip(eps.stride(), self._in.stride(), eps.shape) if d > 1)):
                 raise RuntimeError("Sampler: the UNet's output is not an FP16 tensor of its input's shape in channels-"
                                    f"last storage (shape {tuple(eps.shape)}, strides {eps.stride()}, {eps.dtype})")
-            if self.schedule.order == 2 and masked:
-                _C.sampler_step_2m_masked(self._x, eps, self._in, self._hist, self._coef, self._t_table, self._step,
-                                          self._first, self._t, self._z, self._noise0, self._mask, self._blend,
-                                          self.guidance_scale, self.rows_per_image, channels=C, n=n)
-            elif self.schedule.order == 2:
-                _C.sampler_step_2m(self._x, eps, self._in, self._hist, self._coef, self._t_table, self._step,
-                                   self._first, self._t, self.guidance_scale, self.rows_per_image, n=n)
-            elif masked:
-                _C.sampler_step_masked(self._x, eps, self._in, self._coef, self._t_table, self._step, self._t, self._z,
-                                       self._noise0, self._mask, self._blend, self.guidance_scale, self.rows_per_image,
-                                       step_noise, channels=C, n=n, **rng_args)
-            else:
-                _C.sampler_step(self._x, eps, self._in, self._coef, self._t_table, self._step, self._t,
-                                self.guidance_scale, self.rows_per_image, step_noise, n=n, **rng_args)
+            step_fn(self._x, eps, *tail, **kw)
 
         self._reset(noise, None)
         side = torch.cuda.Stream(dev)
@@ -401,30 +399,13 @@ class Sampler:
         """State of step 0: x = f32(noise) * init_scale, UNet input = f16(x * input_scale0) in every row block, the
         step index 0, the timestep t_table[0].  Device ops in stream order: nothing here waits for the GPU."""
         import torch
-        B = noise.shape[0]
         torch.mul(noise.to(torch.float32), self._init_scale, out=self._x)
-        first = (self._x * self._input_scale0).to(torch.float16)
-        for r in range(self.rows_per_image):
-            self._in[r * B:(r + 1) * B].copy_(first)
-        if self._noise is not None and step_noise is not None:
-            self._noise.copy_(step_noise)
-        self._step.zero_()
-        if self.schedule.order == 2:
-            self._first.zero_()
-        self._t.copy_(self._t_table[0])
+        self._start_at(0, (self._x * self._input_scale0).to(torch.float16), step_noise)
 
-    def _reset_at(self, t0, init_latents, noise, step_noise):
-        """State of step t0 of an image-to-image run: x = fl32(fl32(a0 * z) + fl32(c0 * noise)) -- two products and one
-        sum, each a torch operation of its own so that none can fuse -- UNet input = f16(fl32(x * s0)) in every row
-        block, the step index t0, the timestep t_table[t0].  The scalars travel as launch arguments (rounded to FP32
-        there); like _reset, nothing here waits for the GPU."""
-        import torch
-        B = noise.shape[0]
-        a0, c0, s0 = self.schedule.start(t0)
-        az = torch.mul(init_latents.to(torch.float32), a0)
-        cn = torch.mul(noise.to(torch.float32), c0)
-        torch.add(az, cn, out=self._x)
-        first = torch.mul(self._x, s0).to(torch.float16)
+    def _start_at(self, t0, first, step_noise):
+        """What _reset and _reset_at share: the first UNet input into every row block, the step noise, and the device
+        step state at t0."""
+        B = first.shape[0]
         for r in range(self.rows_per_image):
             self._in[r * B:(r + 1) * B].copy_(first)
         if self._noise is not None and step_noise is not None:
@@ -433,6 +414,18 @@ class Sampler:
         if self.schedule.order == 2:  # the run's first step is first-order: the history of an earlier run is not read
             self._first.fill_(t0)
         self._t.copy_(self._t_table[t0])
+
+    def _reset_at(self, t0, init_latents, noise, step_noise):
+        """State of step t0 of an image-to-image run: x = fl32(fl32(a0 * z) + fl32(c0 * noise)) -- two products and one
+        sum, each a torch operation of its own so that none can fuse -- UNet input = f16(fl32(x * s0)) in every row
+        block, the step index t0, the timestep t_table[t0].  The scalars travel as launch arguments (rounded to FP32
+        there); like _reset, nothing here waits for the GPU."""
+        import torch
+        a0, c0, s0 = self.schedule.start(t0)
+        az = torch.mul(init_latents.to(torch.float32), a0)
+        cn = torch.mul(noise.to(torch.float32), c0)
+        torch.add(az, cn, out=self._x)
+        self._start_at(t0, torch.mul(self._x, s0).to(torch.float16), step_noise)
 
     # ---- the loop -------------------------------------------------------------------------------------------
     def _set_cond(self, cond, noise):

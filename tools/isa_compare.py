@@ -16,7 +16,7 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FILES = ["quantize", "fused_norm", "attention", "igemm", "igemm_aq", "igemm_ln", "iconv"]
+FILES = ["quantize", "fused_norm", "attention", "igemm", "igemm_aq", "igemm_ln", "iconv", "sampler"]
 
 
 def assemble(tree, out):
