@@ -21,6 +21,7 @@ import torch.nn.functional as F
 from torch.ao.quantization import QConfig
 
 from mixdq_amd import _C
+from mixdq_amd.derived import after_load, derive, holder_of, refresh
 from mixdq_amd.nn.glue import tagged_operand
 from mixdq_amd.nn.utils import create_qparams_from_dtype, pack_w4, unpack_w4
 from mixdq_amd.op.quant import quantize_per_tensor_vectorized
@@ -40,8 +41,23 @@ def _w8a8_ok(w, a, w4_kernel=False) -> bool:
         and torch.all(w.zero_points == 0.0).item())
 
 
-def _refresh_after_load(mod, _incompatible_keys):
-    mod.refresh_derived_()
+def _border_table_of(old, wsum):
+    """Builder of the zero-point border table: into the stored table where it still fits."""
+    fits = old is not None and old[0].device == wsum.device and old[0].shape[1] == wsum.shape[0]
+    return (_C.conv_border_table(wsum, out=old[0] if fits else None),)
+
+
+def pad_in8(w):
+    """w [K, C, R, S] with zero input channels up to the next multiple of 8 (a 16-byte multiple of FP16: the width the
+    MFMA tiles take; zeros add nothing), KRSC in memory."""
+    wp = torch.zeros((w.shape[0], w.shape[1] + -w.shape[1] % 8) + tuple(w.shape[2:]), dtype=w.dtype,
+                     device=w.device).contiguous(memory_format=torch.channels_last)
+    wp[:, :w.shape[1]] = w
+    return wp
+
+
+def _padded_weight(_old, w):
+    return (pad_in8(w),)
 
 
 class QuantizedConv2d(nn.Module):
@@ -91,7 +107,7 @@ class QuantizedConv2d(nn.Module):
             self._register_qparams("", w_qparams, a_qparams, device)
             if split != 0:
                 self._register_qparams("_0", w_qparams_0, a_qparams_0, device)
-            self.register_load_state_dict_post_hook(_refresh_after_load)
+        self.register_load_state_dict_post_hook(after_load)   # (FP fallback layers too: their padded weight)
 
     def _register_qparams(self, sfx, w, a, device):
         self.register_buffer("weight_scales" + sfx, w.scales.to(device).float())
@@ -190,28 +206,15 @@ class QuantizedConv2d(nn.Module):
                 + F.conv2d(x[:, self.split:], deq("_0"), None, *args))
 
     def _border_table(self, sfx):
-        """Cached tap-rectangle sums for padded convs.  Derived from the weights only, so it is
-        built once -- and rebuilt IN PLACE (same address: captured graphs keep reading it) when
-        weight_sum_by_input_channels is replaced or updated in place (load_state_dict, broadcast)."""
+        """Tap-rectangle sums for padded convs, derived from weight_sum_by_input_channels."""
         if self.padding[0] == 0:
             return None
         wsum = getattr(self, "weight_sum_by_input_channels" + sfx)
-        cache = self.__dict__.setdefault("_tables", {})
-        e = cache.get(sfx)
-        if e is not None and e[0] is wsum and e[1] == wsum._version:
-            return e[2]
-        out = None
-        if e is not None and e[2].device == wsum.device and e[2].shape[1] == wsum.shape[0]:
-            out = e[2]
-        table = _C.conv_border_table(wsum, out=out)
-        cache[sfx] = (wsum, wsum._version, table)
-        return table
+        return derive(holder_of(self), ("table", sfx), (wsum,), _border_table_of)[0]
 
     def refresh_derived_(self):
         """Re-derive cached state from the buffers after they were written in place."""
-        if self.valid_for_acceleration and self.padding[0] > 0 and self.scale.is_cuda:
-            for sfx in ("", "_0") if self.split else ("",):
-                self._border_table(sfx)
+        refresh(self.__dict__.get("_derived_tensors"))
 
     def forward_quantized(self, x_int, residual=None, residual_per_image=False, upsample2x=False):
         """The conv half of forward() for an input already quantized with this layer's activation
@@ -253,20 +256,14 @@ class QuantizedConv2d(nn.Module):
                 w = self.weight = w.contiguous(memory_format=torch.channels_last)
             if self.in_channels % 8:
                 # conv_in (4 input channels): zero-pad the channels to a 16-byte multiple so the
-                # layer runs on the MFMA tiles (the padded weight is cached; zeros add nothing)
+                # layer runs on the MFMA tiles (the padded weight is a derived tensor)
                 cp = -self.in_channels % 8
-                wp = self.__dict__.get("_w_padded")
-                if wp is None or wp[0] is not w or wp[1] != w._version:
-                    wpad = torch.zeros((w.shape[0], w.shape[1] + cp, w.shape[2], w.shape[3]),
-                                       dtype=w.dtype, device=w.device
-                                       ).contiguous(memory_format=torch.channels_last)
-                    wpad[:, :w.shape[1]] = w
-                    wp = self.__dict__["_w_padded"] = (w, w._version, wpad)
+                wp = derive(holder_of(self), "w_padded", (w,), _padded_weight)[0]
                 xp = torch.zeros((x.shape[0], x.shape[1] + cp, x.shape[2], x.shape[3]),
                                  dtype=x.dtype, device=x.device
                                  ).contiguous(memory_format=torch.channels_last)
                 xp[:, :x.shape[1]] = x
-                x, w = xp, wp[2]
+                x, w = xp, wp
             if residual is not None and not residual_per_image and not residual.is_contiguous(
                     memory_format=torch.channels_last):
                 return _C.conv2d_f16(x, w, self.bias, self.stride[0], self.padding[0]) + residual

@@ -195,7 +195,7 @@ class _HipGEGLU:
         return v * F.gelu(g)
 
 
-_BOS_BUFS = "_mixdq_bos_out"          # in a BOS layer's __dict__: {(B, T, device): [buffer, bos row tensor, its version]}
+_BOS_BUFS = "_mixdq_bos_out"          # in a BOS layer's __dict__: {(B, T, device): [buffer, holder of its row-0 record]}
 # A kept buffer is never freed while its layer lives (a captured graph may hold its address), so their NUMBER is
 # bounded instead: a layer that has handed out this many (batch, tokens, device) shapes serves further shapes the
 # reference's way (allocate + copy row 0 per call).  197 KB per image at 77 x 1280: 16 shapes of <= 64 images stay
@@ -203,13 +203,32 @@ _BOS_BUFS = "_mixdq_bos_out"          # in a BOS layer's __dict__: {(B, T, devic
 BOS_BUFFERS_MAX = int(__import__("os").environ.get("MIXDQ_BOS_BUFFERS_MAX", "16"))
 
 
+def _fill_row0(old, *rows):
+    """Builder of a kept buffer's BOS row: written where it is (broadcast over the batch)."""
+    old[0].copy_(rows[0] if len(rows) == 1 else torch.cat(rows, dim=-1))
+    return old
+
+
+def kept_bos_buffer(bufs: dict, key, width, rows, limit=None):
+    """The kept FP16 [B, T, width] buffer of bufs[key = (B, T, device)] -- made on first use, never dropped -- whose
+    row 0 is the derived tensor of the BOS `rows` (side by side); None where `bufs` already keeps `limit` buffers."""
+    from mixdq_amd.derived import derive
+    slot = bufs.get(key)
+    if slot is None:
+        if limit is not None and len(bufs) >= limit:
+            return None
+        slot = bufs[key] = [torch.empty((key[0], key[1], width), dtype=torch.float16, device=key[2]), {}]
+    derive(slot[1], "row0", rows, _fill_row0, into=(slot[0][:, :1, :],))
+    return slot[0]
+
+
 def _project_context(layer, ctx):
     """`layer(ctx)` for the key / value projection of a swapped attention.  A BOS layer (token 0 of the text context
     is a precomputed FP16 row, nn/Linear.py) writes into a buffer the layer keeps per (batch, tokens, device), whose
     row 0 was filled once -- the reference's `out[:, :1] = bos_pre_computed` copy per call (140 launches per step)
     disappears.  Safe HERE because the swapped attention consumes k / v before it returns; every buffer ever handed
-    out stays alive with the layer (a captured hipGraph holds its address), and row 0 is re-filled in place when
-    the BOS row changes (load_state_dict: the buffer's in-place version).  A hooked layer gets the plain call: a
+    out stays alive with the layer (a captured hipGraph holds its address), and row 0 is a derived tensor of the BOS
+    row.  A hooked layer gets the plain call: a
     hook may keep its output, which the next forward would overwrite in a kept buffer."""
     if _hooked(layer) or not _is_bos_layer(layer, ctx):
         return layer(ctx)
@@ -219,20 +238,8 @@ def _project_context(layer, ctx):
 def _bos_buffer(layer, ctx):
     """The kept [B, T, N] output buffer of a BOS layer for this (batch, tokens, device), row 0 filled; None when the
     layer already keeps BOS_BUFFERS_MAX of them.  One forward at a time per module, as with a captured graph."""
-    bufs = layer.__dict__.setdefault(_BOS_BUFS, {})
-    key = (ctx.shape[0], ctx.shape[1], ctx.device)
-    row = layer.bos_pre_computed
-    e = bufs.get(key)
-    if e is None:
-        if len(bufs) >= BOS_BUFFERS_MAX:
-            return None
-        e = bufs[key] = [torch.empty((ctx.shape[0], ctx.shape[1], layer.out_features), dtype=torch.float16,
-                                     device=ctx.device), None, -1]
-    if e[1] is not row or e[2] != row._version:
-        with torch.no_grad():
-            e[0][:, :1, :] = row
-        e[1], e[2] = row, row._version
-    return e[0]
+    return kept_bos_buffer(layer.__dict__.setdefault(_BOS_BUFS, {}), (ctx.shape[0], ctx.shape[1], ctx.device),
+                           layer.out_features, (layer.bos_pre_computed,), BOS_BUFFERS_MAX)
 
 
 def _is_bos_layer(layer, ctx) -> bool:

@@ -23,6 +23,8 @@ from collections import OrderedDict, namedtuple
 import torch
 import torch.nn as nn
 
+from mixdq_amd.derived import DerivedWeights
+
 CLIP_L_CONFIG = dict(hidden_size=768, num_hidden_layers=12, num_attention_heads=12, intermediate_size=3072,
                      hidden_act="quick_gelu", projection_dim=None, vocab_size=49408, max_position_embeddings=77,
                      layer_norm_eps=1e-5)
@@ -42,6 +44,10 @@ class ClipEmbeddings(nn.Module):
         self.position_embedding = nn.Embedding(cfg["max_position_embeddings"], cfg["hidden_size"])
 
 
+def _cat_qkv(_old, wq, bq, wk, bk, wv, bv):
+    return torch.cat([wq, wk, wv]).contiguous(), torch.cat([bq, bk, bv]).contiguous()
+
+
 class ClipAttention(nn.Module):
     def __init__(self, c):
         super().__init__()
@@ -50,8 +56,10 @@ class ClipAttention(nn.Module):
 
     def qkv(self):
         """q_proj | k_proj | v_proj as ONE [3C, C] projection."""
-        return (torch.cat([self.q_proj.weight, self.k_proj.weight, self.v_proj.weight]).contiguous(),
-                torch.cat([self.q_proj.bias, self.k_proj.bias, self.v_proj.bias]).contiguous())
+        return _cat_qkv(None, *self.qkv_sources())
+
+    def qkv_sources(self):
+        return tuple(p for m in (self.q_proj, self.k_proj, self.v_proj) for p in (m.weight, m.bias))
 
 
 class ClipMLP(nn.Module):
@@ -94,7 +102,7 @@ class ClipTextTransformer(nn.Module):
         self.final_layer_norm = nn.LayerNorm(cfg["hidden_size"], eps=cfg["layer_norm_eps"])
 
 
-class TextEncoder(nn.Module):
+class TextEncoder(DerivedWeights, nn.Module):
     """A CLIPTextModel (projection_dim None) or CLIPTextModelWithProjection, parameter names as transformers'."""
 
     def __init__(self, cfg=None):
@@ -109,40 +117,11 @@ class TextEncoder(nn.Module):
         self.text_model = ClipTextTransformer(self.cfg)
         if self.cfg.get("projection_dim"):
             self.text_projection = nn.Linear(c, self.cfg["projection_dim"], bias=False)
-        self._cache = None         # tensors derived from the weights (rebuilt after a load or a move)
+        self._init_derived()
 
-    # ---- derived weights ------------------------------------------------------------------------------------
-    @torch.no_grad()
-    def _derived(self):
-        if self._cache is None:
-            self._cache = dict(qkv=[tuple(t.detach() for t in layer.self_attn.qkv())
-                                    for layer in self.text_model.encoder.layers])
-        return self._cache
-
-    def refresh_derived_(self):
-        self._cache = None
-        return self
-
-    def _apply(self, fn, recurse=True):          # .to() / .cuda() / .half(): the weights move, the derived ones go
-        self.refresh_derived_()
-        return super()._apply(fn, recurse)
-
-    @torch.no_grad()
-    def load_state_dict(self, *args, **kwargs):
-        """nn.Module.load_state_dict, then the derived q|k|v tensors are rewritten IN PLACE, as the load rewrites the
-        parameters themselves: a graph captured from this encoder (hip_graph_opt) holds the addresses of both, and its
-        replays see the new weights.  (A move or a dtype change -- .to(), .half() -- gives every tensor a new address:
-        capture after it, not before.)"""
-        out = super().load_state_dict(*args, **kwargs)
-        if self._cache is not None:
-            for layer, (w, b) in zip(self.text_model.encoder.layers, self._cache["qkv"]):
-                nw, nb = layer.self_attn.qkv()
-                if (nw.shape, nw.dtype, nw.device, nb.dtype, nb.device) != (w.shape, w.dtype, w.device, b.dtype, b.device):
-                    self.refresh_derived_()       # (load_state_dict(assign=True) with other tensors: start over)
-                    break
-                w.copy_(nw)
-                b.copy_(nb)
-        return out
+    def _derive(self):
+        """The derived weights (lifecycle: DerivedWeights): layer index -> its q|k|v projection."""
+        return {i: (layer.self_attn.qkv_sources(), _cat_qkv) for i, layer in enumerate(self.text_model.encoder.layers)}
 
     @staticmethod
     def _ln(norm, x):
@@ -168,12 +147,12 @@ class TextEncoder(nn.Module):
             raise RuntimeError("TextEncoder.forward: the encoder runs in FP16 (build_text_encoder / .half())")
         B, C = ids.shape[0], self.cfg["hidden_size"]
         ids32 = ids.to(torch.int32).contiguous()
-        qkv = self._derived()["qkv"]
+        qkv = self._derived()
         x = _C.embed_tokens_f16(ids32, tm.embeddings.token_embedding.weight, tm.embeddings.position_embedding.weight)
         penultimate = x
-        for layer, w in zip(tm.encoder.layers, qkv):
+        for i, layer in enumerate(tm.encoder.layers):
             penultimate = x
-            x = layer.run(self, x, w)
+            x = layer.run(self, x, qkv[i])
         last = self._ln(tm.final_layer_norm, x)
         eos = ids32.argmax(-1)                                           # the EOS token has the largest id
         pooled = last.gather(1, eos.view(B, 1, 1).expand(B, 1, C)).view(B, C)

@@ -17,6 +17,7 @@ Weights are synthetic (no network, no checkpoints): randn * 0.02, seeded per lay
 """
 from __future__ import annotations
 
+import functools
 import math
 import weakref
 from collections import OrderedDict
@@ -24,6 +25,8 @@ from collections import OrderedDict
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+
+from mixdq_amd import derived
 
 # ---------------------------------------------------------------------------------------------
 # Fused forward.  With `unet.fused = True` (set_fused) the glue that
@@ -88,26 +91,15 @@ def _fusable_f16(x) -> bool:
     return x.is_cuda and x.dtype == torch.float16
 
 
-# ---------------------------------------------------------------------------------------------
-# Derived state of the fused graph (packed GEMM operands, quantizer groupings) is cached on the
-# modules.  Two rules keep the caches honest:
-#   * a cached DECISION (do these layers share one activation quantizer?) is valid only for the
-#     very tensors it was taken on, at their current in-place `_version` -- module swaps
-#     (quantize_unet after an FP16 run), `.to()` and load_state_dict / broadcast all invalidate it;
-#   * cached DATA never goes stale because it is not a copy: the row-concatenated tensors of a
-#     packed GEMM become the storage and the layers' own buffers become views of them, so in-place
-#     updates reach the packed launch -- and every captured graph -- by construction.
-# ---------------------------------------------------------------------------------------------
+# (What is cached on the modules and when it is stale: DESIGN.md "Derived tensors".)
 def _quantizer_groups(holder: dict, key, layers):
     """Group id per layer: equal activation quantizers -- qparams and width (8 / 4 bits) -- <=> equal id.  One
     device->host copy (a sync: only ever taken in the eager warm-up that precedes graph capture), memoised in
-    `holder[key]` against the identity and in-place version of the qparam tensors and the layers' widths."""
+    `holder[key]` with the derived tensors' freshness test: the qparam tensors, their versions, the widths."""
     src = [t for m in layers for t in (m.act_scales_inv, m.act_zero_points)]
-    bits = [_abits(m) for m in layers]
-    ver = tuple(t._version for t in src) + tuple(bits)
+    bits = tuple(_abits(m) for m in layers)
     e = holder.get(key)
-    if (e is not None and len(e[0]) == len(src) and all(a is b for a, b in zip(e[0], src))
-            and e[1] == ver):
+    if derived.fresh(e, src, bits):
         return e[2]
     ids = []
     if layers:
@@ -115,8 +107,14 @@ def _quantizer_groups(holder: dict, key, layers):
         seen = {}
         for i in range(len(layers)):
             ids.append(seen.setdefault((vals[2 * i], vals[2 * i + 1], bits[i]), len(seen)))
-    holder[key] = (src, ver, ids)
+    holder[key] = derived.record(src, bits, ids)
     return ids
+
+
+def _split_pad8(co, _old, w):
+    """Builder of the split conv_in weights: w[:, :co] and w[:, co:], each padded to 8 input channels."""
+    from mixdq_amd.nn.Conv2d import pad_in8
+    return pad_in8(w[:, :co]), pad_in8(w[:, co:])
 
 
 def _memo(mod) -> dict:
@@ -204,10 +202,6 @@ def _pack_valid(pack, layers) -> bool:
                 return False
             off += t.shape[0]
     return True
-
-
-def _refresh_after_load(mod, _incompatible_keys):
-    mod.refresh_derived_()
 
 
 def _gn_feed(norm: nn.GroupNorm, x, consumer, silu: bool, x2=None, raw_for=None):
@@ -1122,7 +1116,7 @@ class SDXLUNet(nn.Module):
         self.conv_norm_out = nn.GroupNorm(cfg["norm_num_groups"], boc[0], eps=1e-5)
         self.conv_act = nn.SiLU()          # (diffusers' name)
         self.conv_out = nn.Conv2d(boc[0], cfg["out_channels"], 3, 1, 1)
-        self.register_load_state_dict_post_hook(_refresh_after_load)
+        self.register_load_state_dict_post_hook(derived.after_load)
 
     fused = False
 
@@ -1146,6 +1140,7 @@ class SDXLUNet(nn.Module):
         shared by every layer whose activation quantizer is identical.  (Round 1 ran these on a
         side stream; measured, a second long-lived branch in the hipGraph costs more than the
         kernels it hides: 14.96 -> 14.36 ms with both side branches removed.)"""
+        from mixdq_amd.nn.glue import kept_bos_buffer
         blocks = [m for m in self.modules() if isinstance(m, BasicTransformerBlock)]
         if not blocks or not context.is_cuda:
             return
@@ -1176,18 +1171,9 @@ class SDXLUNet(nn.Module):
                 pack = self._kv_pack(blk, context)
             if pack is not None:        # to_k | to_v as ONE GEMM against [2C, K] (cf. _qkv_fused)
                 # persistent [B, T, 2C] buffer PER SHAPE (a captured graph keeps raw pointers into
-                # it: a buffer is never dropped while its pack lives), BOS row written once -- it is
-                # a constant -- and rewritten in place if the BOS tensors changed
-                bos_key = (lk.bos_pre_computed.data_ptr(), lk.bos_pre_computed._version,
-                           lv.bos_pre_computed.data_ptr(), lv.bos_pre_computed._version)
-                slot = pack.setdefault("outs", {}).get((B, T, context.device))
-                if slot is None:
-                    slot = pack["outs"][(B, T, context.device)] = [None, torch.empty(
-                        (B, T, 2 * pack["C"]), dtype=torch.float16, device=context.device)]
-                if slot[0] != bos_key:
-                    slot[1][:, :1, :] = torch.cat([lk.bos_pre_computed, lv.bos_pre_computed], dim=-1)
-                    slot[0] = bos_key
-                o = slot[1]
+                # it: a buffer is never dropped while its pack lives), BOS row derived from the two BOS tensors
+                o = kept_bos_buffer(pack.setdefault("outs", {}), (B, T, context.device), 2 * pack["C"],
+                                    (lk.bos_pre_computed, lv.bos_pre_computed))
                 blk._kv = (o[..., :pack["C"]], o[..., pack["C"]:], None)
                 grouped.setdefault((gid[id(lk)], lk.in_features, pack["wbits"]), []).append(
                     (lk, pack, o))
@@ -1198,16 +1184,9 @@ class SDXLUNet(nn.Module):
                     outs.append(layer(context))
                     continue
                 # persistent K / V buffer per layer and shape (never dropped: see above)
-                bos_key = (layer.bos_pre_computed.data_ptr(), layer.bos_pre_computed._version)
-                bufs = layer.__dict__.setdefault("_kv_buf", {})
-                slot = bufs.get((B, T, context.device))
-                if slot is None:
-                    slot = bufs[(B, T, context.device)] = [None, torch.empty(
-                        (B, T, layer.out_features), dtype=torch.float16, device=context.device)]
-                if slot[0] != bos_key:
-                    slot[1][:, :1, :] = layer.bos_pre_computed
-                    slot[0] = bos_key
-                outs.append(layer.forward_bos_quantized(ctx_int8(layer), B, T, out=slot[1]))
+                buf = kept_bos_buffer(layer.__dict__.setdefault("_kv_buf", {}), (B, T, context.device),
+                                      layer.out_features, (layer.bos_pre_computed,))
+                outs.append(layer.forward_bos_quantized(ctx_int8(layer), B, T, out=buf))
             blk._kv = (outs[0], outs[1], None)
         from mixdq_amd import _C
         from mixdq_amd.op.qlinear import qlinear
@@ -1290,29 +1269,16 @@ class SDXLUNet(nn.Module):
             _C.qlinear_grouped(x_int, table)
 
     def refresh_derived_(self):
-        """After buffers were written IN PLACE (load_state_dict, shard.broadcast_module_state):
-        re-derive, at their existing addresses, the cached tensors that are computed from buffers
-        rather than views of them -- the conv border tables and the BOS row of the persistent
-        K / V buffers -- so that captured graphs see the new values too.  (Packed GEMM operands
-        are views and need nothing.)"""
-        with torch.no_grad():
-            for m in self.modules():
-                if m is not self and hasattr(m, "refresh_derived_"):
-                    m.refresh_derived_()
-                bufs = m.__dict__.get("_kv_buf")
-                if bufs and torch.is_tensor(getattr(m, "bos_pre_computed", None)):
-                    for slot in bufs.values():
-                        slot[1][:, :1, :] = m.bos_pre_computed.to(slot[1].device)
-                        slot[0] = None          # re-keyed on the next forward
-                pack = m.__dict__.get("_kvpack")
-                if pack is not None and pack.get("outs"):
-                    lk, lv = (r() for r in pack["layers"])
-                    if lk is None or lv is None:
-                        continue
-                    for slot in pack["outs"].values():
-                        slot[1][:, :1, :] = torch.cat(
-                            [lk.bos_pre_computed, lv.bos_pre_computed], dim=-1).to(slot[1].device)
-                        slot[0] = None
+        """After buffers were written IN PLACE (load_state_dict, shard.broadcast_module_state): every derived
+        tensor of this network follows at its address, so that captured graphs see the new values too."""
+        for m in self.modules():
+            if m is not self and hasattr(m, "refresh_derived_"):
+                m.refresh_derived_()
+            d = m.__dict__
+            kept = (d.get("_kv_buf"), d.get("_mixdq_bos_out"), (d.get("_kvpack") or {}).get("outs"))
+            for slot in [s for bufs in kept if bufs for s in bufs.values()]:
+                derived.refresh(slot[1])           # (the BOS row of a kept K / V buffer)
+        derived.refresh(self.__dict__.get("_derived_tensors"))
         return self
 
     def prepare_fused_(self):
@@ -1379,29 +1345,17 @@ class SDXLUNet(nn.Module):
                                "conv_in always is one: QuantizedConv2d falls back where in_channels % 4 != 0)")
         return w
 
-    @torch.no_grad()
     def _conv_in_split(self, refresh: bool):
         """(Wx8, Wc8): conv_in.weight[:, :out_channels] and [:, out_channels:], each zero-padded to 8 input channels,
-        KRSC in memory.  Cached; with `refresh` they are re-derived IN PLACE (same storage: a captured graph keeps
-        reading them) when the weight tensor or its `_version` changed.  Without it the cache is only read."""
-        c = self.__dict__.get("_cin_split")
-        if not refresh:
-            if c is None:
-                raise RuntimeError("SDXLUNet.forward: cond_term= should be what this UNet's cond_term() returned")
-            return c["wx"], c["wc"]
-        w = self._conv_in_weight()
-        if c is not None and c["w"] is w and c["version"] == w._version:
-            return c["wx"], c["wc"]
-        co = self.cfg["out_channels"]
-        shape = (w.shape[0], 8) + tuple(w.shape[2:])
-        if c is None or c["wx"].shape != shape or c["wx"].dtype != w.dtype or c["wx"].device != w.device:
-            new = lambda: torch.zeros(shape, dtype=w.dtype, device=w.device).contiguous(  # noqa: E731
-                memory_format=torch.channels_last)
-            c = self.__dict__["_cin_split"] = dict(wx=new(), wc=new())
-        c["wx"][:, :co] = w[:, :co]
-        c["wc"][:, :self.cond_channels] = w[:, co:]
-        c["w"], c["version"] = w, w._version
-        return c["wx"], c["wc"]
+        KRSC in memory: derived from conv_in.weight with `refresh`; without it (inside a captured step) only read."""
+        if refresh:
+            return derived.derive(derived.holder_of(self), "cin_split", (self._conv_in_weight(),),
+                                  functools.partial(_split_pad8, self.cfg["out_channels"]),
+                                  extra=self.cfg["out_channels"])
+        out = derived.stored(self.__dict__.get("_derived_tensors"), "cin_split")
+        if out is None:
+            raise RuntimeError("SDXLUNet.forward: cond_term= should be what this UNet's cond_term() returned")
+        return out
 
     @staticmethod
     def _pad8(x):
@@ -1520,7 +1474,7 @@ class SDXLUNet(nn.Module):
 
     def _apply(self, fn, recurse=True):          # .to() / .cuda() / .half(): the weights move, the plans go
         self.__dict__.pop("_pf_plans", None)
-        self.__dict__.pop("_cin_split", None)    # (... and the split conv_in weights: cond_term() makes them anew)
+        derived.drop(self.__dict__.get("_derived_tensors"))   # (... and the split conv_in weights: cond_term() makes them anew)
         return super()._apply(fn, recurse)
 
     def load_state_dict(self, *args, **kwargs):

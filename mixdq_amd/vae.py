@@ -26,10 +26,13 @@ This is a floating-point path with no counterpart in the reference (which reache
 pipeline): it is held to tolerance against the same network built from stock torch modules (tests/vae_ref.py).
 DESIGN.md section 3.23.
 """
+import functools
 from collections import OrderedDict
 
 import torch
 import torch.nn as nn
+
+from mixdq_amd.derived import DerivedWeights
 
 VAE_SDXL_CONFIG = dict(block_out_channels=(128, 256, 512, 512), layers_per_block=2, latent_channels=4,
                        out_channels=3, norm_num_groups=32, scaling_factor=0.13025)
@@ -56,6 +59,29 @@ class VaeResnetBlock(nn.Module):
         return _C.conv2d_f16(h, self.conv2.weight, self.conv2.bias, 1, 1, _residual=x)
 
 
+def _cat_qkv(_old, wq, bq, wk, bk, wv, bv):
+    return torch.cat([wq, wk, wv]).contiguous(), torch.cat([bq, bk, bv]).contiguous()
+
+
+def _pad_out4(_old, w, b):
+    k = w.shape[0]
+    k4 = (k + 3) // 4 * 4
+    w4 = torch.zeros((k4,) + tuple(w.shape[1:]), dtype=w.dtype, device=w.device)
+    b4 = torch.zeros(k4, dtype=b.dtype, device=b.device)
+    w4[:k], b4[:k] = w.detach(), b.detach()
+    return w4.contiguous(memory_format=torch.channels_last), b4
+
+
+def _scaled(factor, _old, w, b):
+    w = w.detach()
+    return (w.float() / factor).to(w.dtype).contiguous(memory_format=torch.channels_last), b.detach()
+
+
+def _pad_in8(_old, w, b):
+    from mixdq_amd.nn.Conv2d import pad_in8
+    return pad_in8(w.detach()), b.detach()
+
+
 class VaeAttention(nn.Module):
     """diffusers' Attention as the VAE's mid block uses it: one head as wide as the block, a residual connection."""
 
@@ -67,8 +93,10 @@ class VaeAttention(nn.Module):
 
     def qkv(self):
         """to_q | to_k | to_v as ONE [3C, C] projection."""
-        return (torch.cat([self.to_q.weight, self.to_k.weight, self.to_v.weight]).contiguous(),
-                torch.cat([self.to_q.bias, self.to_k.bias, self.to_v.bias]).contiguous())
+        return _cat_qkv(None, *self.qkv_sources())
+
+    def qkv_sources(self):
+        return tuple(p for m in (self.to_q, self.to_k, self.to_v) for p in (m.weight, m.bias))
 
     def run(self, vae, x):
         from mixdq_amd import _C
@@ -131,52 +159,22 @@ class VaeDecoderNet(nn.Module):
         self.conv_out = nn.Conv2d(ch[0], cfg.get("out_channels", 3), 3, padding=1)
 
 
-class _VaeHalf(nn.Module):
-    """What the two halves of the AutoencoderKL share: the config, the tensors derived from the weights (rewritten in
-    place by a load; dropped by a move and rebuilt on the next run by the subclass's `_derive`) and the GroupNorm launch
-    with its cached workspaces.  The blocks above reach all three through the `vae` argument of their `run`."""
+class _VaeHalf(DerivedWeights, nn.Module):
+    """What the two halves of the AutoencoderKL share: the config, the tensors derived from the weights (the
+    subclass's `_derive` declares them; lifecycle: DerivedWeights) and the GroupNorm launch with its cached workspaces,
+    which depend on shapes only: a load keeps them, a move or a load that changed the weights' metadata drops them.
+    The blocks above reach all three through the `vae` argument of their `run`."""
 
     def __init__(self, cfg=None):
         super().__init__()
         self.cfg = dict(VAE_SDXL_CONFIG if cfg is None else cfg)
         self.scaling_factor = float(self.cfg["scaling_factor"])
-        self._cache = None         # tensors derived from the weights (rewritten by a load, rebuilt after a move)
         self._gn_ws = {}           # GroupNorm workspaces, one per (shape, device)
+        self._init_derived()
 
-    @torch.no_grad()
-    def _derived(self):
-        if self._cache is None:
-            self._cache = self._derive()
-        return self._cache
-
-    def refresh_derived_(self):
-        self._cache = None
+    def _drop_derived(self):
+        super()._drop_derived()
         self._gn_ws = {}
-        return self
-
-    def _apply(self, fn, recurse=True):          # .to() / .cuda() / .half(): the weights move, the derived ones go
-        self.refresh_derived_()
-        return super()._apply(fn, recurse)
-
-    @torch.no_grad()
-    def load_state_dict(self, *args, **kwargs):
-        """nn.Module.load_state_dict, then every derived tensor is rewritten IN PLACE, as the load rewrites the
-        parameters themselves: a graph captured from this half (hip_graph_opt) holds the addresses of both, and its
-        replays see the new weights.  The GroupNorm workspaces depend on shapes only and stay.  (A move or a dtype
-        change -- .to(), .half() -- gives every tensor a new address: capture after it, not before.)"""
-        out = super().load_state_dict(*args, **kwargs)
-        if self._cache is not None:
-            new = self._derive()
-            same = lambda t, n: (t.shape, t.dtype, t.device) == (n.shape, n.dtype, n.device)
-            if new.keys() != self._cache.keys() or not all(
-                    same(t, n) for k in new for t, n in zip(self._cache[k], new[k])):
-                self.refresh_derived_()           # (load_state_dict(assign=True) with other tensors: start over)
-            else:
-                for k in new:
-                    for t, n in zip(self._cache[k], new[k]):
-                        if t.data_ptr() != n.data_ptr():      # (a derived bias may BE the parameter: already loaded)
-                            t.copy_(n)
-        return out
 
     def _gn(self, norm, x, silu):
         from mixdq_amd import _C
@@ -202,24 +200,18 @@ class VAEDecoder(_VaeHalf):
     def padded_conv_out(self):
         """conv_out's weight / bias padded with zero output channels to a multiple of four (3 -> 4), the width the MFMA
         tiles take; decode() returns the first `out_channels` of that conv."""
-        w, b = self.decoder.conv_out.weight, self.decoder.conv_out.bias
-        k = w.shape[0]
-        k4 = (k + 3) // 4 * 4
-        w4 = torch.zeros((k4,) + tuple(w.shape[1:]), dtype=w.dtype, device=w.device)
-        b4 = torch.zeros(k4, dtype=b.dtype, device=b.device)
-        w4[:k], b4[:k] = w.detach(), b.detach()
-        return w4.contiguous(memory_format=torch.channels_last), b4
+        return _pad_out4(None, self.decoder.conv_out.weight, self.decoder.conv_out.bias)
 
     def scaled_post_quant_conv(self):
         """post_quant_conv on z / scaling_factor == the conv with weight / scaling_factor on z (the division is done
         once, in FP32, on the 4 x 4 weight; the bias is untouched)."""
-        w = self.post_quant_conv.weight.detach()
-        return ((w.float() / self.scaling_factor).to(w.dtype).contiguous(memory_format=torch.channels_last),
-                self.post_quant_conv.bias.detach())
+        return _scaled(self.scaling_factor, None, self.post_quant_conv.weight, self.post_quant_conv.bias)
 
     def _derive(self):
-        return dict(qkv=tuple(t.detach() for t in self.decoder.mid_block.attentions[0].qkv()),
-                    conv_out=self.padded_conv_out(), post_quant=self.scaled_post_quant_conv())
+        conv_out, pq = self.decoder.conv_out, self.post_quant_conv
+        return dict(qkv=(self.decoder.mid_block.attentions[0].qkv_sources(), _cat_qkv),
+                    conv_out=((conv_out.weight, conv_out.bias), _pad_out4),
+                    post_quant=((pq.weight, pq.bias), functools.partial(_scaled, self.scaling_factor)))
 
     # ---- forward --------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -298,14 +290,12 @@ class VAEEncoder(_VaeHalf):
     def padded_conv_in(self):
         """conv_in's weight padded with zero INPUT channels to eight (3 -> 8), the width at which the conv runs on the
         MFMA tiles; the ingest kernel writes the image with eight channels, 3..7 zero."""
-        w = self.encoder.conv_in.weight.detach()
-        w8 = torch.zeros((w.shape[0], 8) + tuple(w.shape[2:]), dtype=w.dtype, device=w.device)
-        w8[:, :w.shape[1]] = w
-        return w8.contiguous(memory_format=torch.channels_last), self.encoder.conv_in.bias.detach()
+        return _pad_in8(None, self.encoder.conv_in.weight, self.encoder.conv_in.bias)
 
     def _derive(self):
-        return dict(qkv=tuple(t.detach() for t in self.encoder.mid_block.attentions[0].qkv()),
-                    conv_in=self.padded_conv_in())
+        conv_in = self.encoder.conv_in
+        return dict(qkv=(self.encoder.mid_block.attentions[0].qkv_sources(), _cat_qkv),
+                    conv_in=((conv_in.weight, conv_in.bias), _pad_in8))
 
     # ---- forward --------------------------------------------------------------------------------------------
     def _check_image(self, image, what):

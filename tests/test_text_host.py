@@ -103,34 +103,34 @@ def test_state_dict_round_trip_and_synthetic_weights():
 def test_derived_qkv_cache_is_rebuilt_after_a_load_and_a_move():
     a, b = T.build_text_encoder(SMALL, seed=1), T.build_text_encoder(SMALL, seed=2)
     d0 = a._derived()
-    assert a._derived() is d0                                         # cached
-    w, bias = d0["qkv"][1]
+    assert all(a._derived()[i] is d0[i] for i in d0) and len(d0) == len(a.text_model.encoder.layers)   # cached
+    w, bias = d0[1]
     att = a.text_model.encoder.layers[1].self_attn
     assert tuple(w.shape) == (384, 128) and tuple(bias.shape) == (384,)
     assert torch.equal(w[:128], att.q_proj.weight) and torch.equal(w[128:256], att.k_proj.weight)
     assert torch.equal(w[256:], att.v_proj.weight) and torch.equal(bias[128:256], att.k_proj.bias)
     # a load rewrites the derived tensors where they are (a captured graph holds their addresses) ...
-    ptrs = [(w.data_ptr(), bias.data_ptr()) for w, bias in d0["qkv"]]
+    ptrs = [(w.data_ptr(), bias.data_ptr()) for w, bias in d0.values()]
     a.load_state_dict(b.state_dict())
     d1 = a._derived()
-    assert [(w.data_ptr(), bias.data_ptr()) for w, bias in d1["qkv"]] == ptrs
-    for layer, (w, bias) in zip(b.text_model.encoder.layers, d1["qkv"]):
+    assert [(w.data_ptr(), bias.data_ptr()) for w, bias in d1.values()] == ptrs
+    for layer, (w, bias) in zip(b.text_model.encoder.layers, d1.values()):
         bw, bb = layer.self_attn.qkv()
         assert torch.equal(w, bw) and torch.equal(bias, bb)
-    assert not torch.equal(d1["qkv"][1][0][:128], T.build_text_encoder(SMALL, seed=1).text_model.encoder.layers[1]
+    assert not torch.equal(d1[1][0][:128], T.build_text_encoder(SMALL, seed=1).text_model.encoder.layers[1]
                            .self_attn.q_proj.weight)
     # ... also before the cache exists, and through assign=True, which swaps the parameters themselves
     c = T.build_text_encoder(SMALL, seed=3)
     c.load_state_dict(b.state_dict())
-    assert torch.equal(c._derived()["qkv"][2][0], d1["qkv"][2][0])
+    assert torch.equal(c._derived()[2][0], d1[2][0])
     c.load_state_dict(T.build_text_encoder(SMALL, seed=1).state_dict(), assign=True)
-    assert torch.equal(c._derived()["qkv"][1][0][:128], T.build_text_encoder(SMALL, seed=1).text_model.encoder
+    assert torch.equal(c._derived()[1][0][:128], T.build_text_encoder(SMALL, seed=1).text_model.encoder
                        .layers[1].self_attn.q_proj.weight)
     # a move or a dtype change drops them: every tensor has a new address anyway
     a.to(torch.float32)
     d2 = a._derived()
-    assert d2 is not d1 and d2["qkv"][0][0].dtype == torch.float32
-    assert torch.equal(d2["qkv"][1][0][:128], a.text_model.encoder.layers[1].self_attn.q_proj.weight)
+    assert d2[0] is not d1[0] and d2[0][0].dtype == torch.float32
+    assert torch.equal(d2[1][0][:128], a.text_model.encoder.layers[1].self_attn.q_proj.weight)
 
 
 def test_forward_refusals_without_a_gpu():

@@ -4,6 +4,8 @@ import numpy as np
 import pytest
 import torch
 
+from mixdq_amd import derived
+
 from mixdq_amd import vae as V
 from tests import vae_enc_ref as ER
 
@@ -66,7 +68,7 @@ def test_load_state_dict_round_trips_and_drops_the_derived_weights():
     missing, unexpected = b.load_state_dict(sd)
     assert not missing and not unexpected
     # the derived tensors are rewritten at their addresses (a captured graph holds them), not dropped
-    assert b._cache is not None and {k: [t.data_ptr() for t in v] for k, v in b._cache.items()} == ptrs
+    assert {k: [t.data_ptr() for t in derived.stored(derived.holder_of(b), k)] for k in derived.holder_of(b)} == ptrs
     assert b._gn_ws == {"kept": ws}
     got = b.state_dict()
     assert set(got) == set(sd) and all(torch.equal(got[k], sd[k]) for k in sd)
@@ -80,14 +82,14 @@ def test_load_state_dict_round_trips_and_drops_the_derived_weights():
     # a move or a dtype change does drop them, and the workspaces; the decoder keeps the same handling from the shared base
     b._derived()
     b.float()
-    assert b._cache is None and b._gn_ws == {}
+    assert not derived.holder_of(b) and b._gn_ws == {}
     b._derived()
     b.half()
-    assert b._cache is None
+    assert not derived.holder_of(b)
     # load_state_dict(assign=True) puts other tensors in the parameters' place: with another dtype the cache starts over
     b._derived()
     b.load_state_dict({k: v.float() for k, v in sd.items()}, assign=True)
-    assert b._cache is None and b._derived()["conv_in"][0].dtype == torch.float32
+    assert not derived.holder_of(b) and b._derived()["conv_in"][0].dtype == torch.float32
     assert isinstance(b, V._VaeHalf) and isinstance(V.build_vae_decoder(SMALL), V._VaeHalf)
 
 

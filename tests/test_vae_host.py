@@ -2,6 +2,8 @@
 dict round trip, the padded conv_out and to_uint8."""
 import torch
 
+from mixdq_amd import derived
+
 from mixdq_amd import vae as V
 
 SMALL = dict(V.VAE_SDXL_CONFIG, block_out_channels=(32, 64, 128, 512), layers_per_block=1, norm_num_groups=8)
@@ -59,7 +61,7 @@ def test_load_state_dict_round_trips_and_drops_the_derived_weights():
     missing, unexpected = b.load_state_dict(sd)
     assert not missing and not unexpected
     # the derived tensors are rewritten at their addresses (a captured graph holds them), not dropped
-    assert b._cache is not None and {k: [t.data_ptr() for t in v] for k, v in b._cache.items()} == ptrs
+    assert {k: [t.data_ptr() for t in derived.stored(derived.holder_of(b), k)] for k in derived.holder_of(b)} == ptrs
     assert b._gn_ws == {"kept": ws}
     got = b.state_dict()
     assert set(got) == set(sd) and all(torch.equal(got[k], sd[k]) for k in sd)
@@ -79,14 +81,14 @@ def test_load_state_dict_round_trips_and_drops_the_derived_weights():
     assert torch.equal(b._derived()["qkv"][0], qkv_before) and b._derived()["qkv"][0].data_ptr() == ptrs["qkv"][0]
     # load_state_dict(assign=True) puts other tensors in the parameters' place: with another dtype the cache starts over
     b.load_state_dict({k: v.float() for k, v in sd.items()}, assign=True)
-    assert b._cache is None and b._gn_ws == {} and b._derived()["qkv"][0].dtype == torch.float32
+    assert not derived.holder_of(b) and b._gn_ws == {} and b._derived()["qkv"][0].dtype == torch.float32
     # a move or a dtype change drops the derived tensors and the workspaces
     b._gn_ws["dropped"] = object()
     b.half()
-    assert b._cache is None and b._gn_ws == {}
+    assert not derived.holder_of(b) and b._gn_ws == {}
     b._derived()
     b.to("cpu", torch.float32)
-    assert b._cache is None
+    assert not derived.holder_of(b)
 
 
 def test_conv_out_is_padded_to_four_channels_and_sliced_back():

@@ -38,7 +38,8 @@ for k, v in by.most_common(12):
 print("sum of distinct storages MB", sum(by.values()) / 2**20)
 extra = 0
 for m in unet.modules():
-    for key in ("_tables", "_kv_buf", "_kvpack", "_qkv", "_w_padded"):
+    # (_derived_tensors: the holder of mixdq_amd/derived.py -- border tables, padded weights, the split conv_in)
+    for key in ("_derived_tensors", "_kv_buf", "_mixdq_bos_out", "_kvpack", "_qkv"):
         v = m.__dict__.get(key)
         if v is None:
             continue
