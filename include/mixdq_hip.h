@@ -583,7 +583,20 @@ int mixdq_embed_tokens_f16(const int32_t* ids, const void* tok_f16, const void* 
  *   out[p, 0] = f16_rn(mask_lat[p]);   out[p, 1 + l] = f16_rn(zl[p, l]), l < L;   out[p, L + 1 .. 7] = +0.0
  * One 16-byte store per latent pixel.  1 <= L <= 7.
  * Errors: pixels < 0, L outside 1..7, null pointers: MIXDQ_ERR_INVALID_ARG; out not 16-byte aligned, mask_lat or zl
- * not 4-byte aligned: MIXDQ_ERR_ALIGNMENT.  pixels == 0 writes nothing (and looks at no pointer). */
+ * not 4-byte aligned: MIXDQ_ERR_ALIGNMENT.  pixels == 0 writes nothing (and looks at no pointer).
+ *
+ * mixdq_ip2p_cond_f16: the conditioning channels of an 8-channel InstructPix2Pix UNet in the same padded form, one row
+ * block per UNet row block (mixdq_sampler_step3's order: text + image, image only, neither).  moments: FP16
+ * [B, h, w, 2L] dense (the VAE encoder's output in memory: L means, then L log-variances, which are not read), out:
+ * FP16 [rows * B, h, w, 8], rows 1 or 3; pixels_per_image = h * w.  With p a pixel of image b:
+ *   out[r * B + b, p, l] = f16_rn(f32(mean[b, p, l]) * scale)      l < L, r < min(rows, 2)
+ *   every other channel, and the whole third block                 +0.0
+ * one FP32 rounding (include/mixdq_math.h: mixdq_vae_latent_mode), then the FP16 one: scale 1.0f returns the mean's own
+ * bits -- latent_dist.mode() unscaled, what both diffusers pipelines feed; CosXL-Edit multiplies by scaling_factor.  One
+ * 16-byte store per output pixel.  1 <= L <= 8.
+ * Errors: B < 0, pixels_per_image < 0, L outside 1..8, rows not 1 or 3, null pointers: MIXDQ_ERR_INVALID_ARG; out not
+ * 16-byte, moments not 2-byte aligned: MIXDQ_ERR_ALIGNMENT.  B * pixels_per_image == 0 writes nothing (and looks at no
+ * pointer). */
 #define MIXDQ_IMAGE_U8 0
 #define MIXDQ_IMAGE_F16 1
 #define MIXDQ_IMAGE_F32 2
@@ -596,6 +609,8 @@ int mixdq_image_to_nhwc8_f16_masked(const void* img, int dtype, int64_t sb, int6
                                     void* out_f16, int B, int C, int H, int W, mixdq_stream_t stream);
 int mixdq_inpaint_cond_f16(const float* mask_lat, const float* zl, void* out_f16, int64_t pixels, int L,
                            mixdq_stream_t stream);
+int mixdq_ip2p_cond_f16(const void* moments_f16, void* out_f16, int B, int64_t pixels_per_image, int L, int rows,
+                        float scale, mixdq_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Inpainting around the VAE (csrc/vae.hip).  No reference counterpart.  A mask value is SET (repaint) by
@@ -829,6 +844,31 @@ int mixdq_sampler_step_masked_rng(float* x, const void* eps_f16, void* in_f16, c
                                   float guidance, int64_t n, int rows_per_image, int64_t row_stride, const float* z,
                                   const float* noise0, const float* mask, int channels, const float* blend,
                                   mixdq_stream_t stream);
+
+/* The step with THREE UNet rows per image and two guidance scales: InstructPix2Pix (diffusers'
+ * StableDiffusion[XL]InstructPix2PixPipeline).  eps and in hold three row blocks row_stride elements apart, in those
+ * pipelines' order -- NOT the two-row convention, where the unconditional block comes first:
+ *   block 0: text + image (e_t)      block 1: image only (e_i)      block 2: neither (e_u)
+ *   e     = (e_u + g * (e_t - e_i)) + gi * (e_i - e_u)              g = guidance, gi = image_guidance
+ *   in[i] = in[row_stride + i] = in[2 * row_stride + i] = f16_rn(x[i] * s_next)
+ * six roundings, FP32 round-to-nearest, never contracted (include/mixdq_math.h: mixdq_sampler_guided_eps3); everything
+ * behind the guided epsilon -- update, history, blend, scaled input, the advance launch, the behaviour past the table --
+ * is the sibling's of the same mode.  This ONE entry point takes the whole operand set flat; the operands of a mode
+ * are null when the mode is off:
+ *   table, table_width       coef and 4, or coef8 and 8 (DPM-Solver++ 2M: then hist and first, and no noise)
+ *   noise_or_null / noise_stride, seeds_or_null / n_image       at most one of the two, width 4 only
+ *   hist_or_null / first_or_null                                both with width 8, neither with width 4
+ *   z / noise0 / mask / blend (+ channels)                      all four (the masked step) or none
+ * Errors, before any launch: table_width not 4 or 8, width 8 with noise or seeds, noise and seeds together, width 8
+ * without hist / first (or width 4 with one): MIXDQ_ERR_INVALID_ARG; then the siblings' checks in their order, with
+ * row_stride >= n and row_stride % 8 == 0 as for two rows.  The six entry points above keep refusing
+ * rows_per_image == 3. */
+int mixdq_sampler_step3(float* x, const void* eps_f16, void* in_f16, const float* table, int table_width,
+                        const float* t_table, int n_steps, int* step, float* timestep, float guidance,
+                        float image_guidance, int64_t n, int64_t row_stride, const float* noise_or_null,
+                        int64_t noise_stride, const uint64_t* seeds_or_null, int64_t n_image, float* hist_or_null,
+                        const int* first_or_null, const float* z, const float* noise0, const float* mask, int channels,
+                        const float* blend, mixdq_stream_t stream);
 
 /* Which kernel instantiation mixdq_qlinear_w8a8 / mixdq_qconv2d_w8a8 will launch for a problem of
  * M rows x N output channels (k_align = K for Linear, C for Conv2d; k_total = K or R*S*C): the block tile BM x BN x BK

@@ -122,6 +122,15 @@ MIXDQ_HD float mixdq_sampler_guided_eps(float eps_u, float eps_c, float g) {
   return MIXDQ_ADD_RN(eps_u, MIXDQ_MUL_RN(g, MIXDQ_SUB_RN(eps_c, eps_u)));
 }
 
+/* InstructPix2Pix (mixdq_sampler_step3): three UNet rows per image -- e_t with text and image, e_i with the image only,
+ * e_u with neither -- and two scales, diffusers' expression in its own left-to-right order:
+ *   e = (e_u + g * (e_t - e_i)) + gi * (e_i - e_u)      six roundings: two differences, two products, two sums
+ * With e_i == e_u the second product is +-0 and e is the two-row guidance of (e_u, e_t), as a value. */
+MIXDQ_HD float mixdq_sampler_guided_eps3(float e_t, float e_i, float e_u, float g, float gi) {
+  return MIXDQ_ADD_RN(MIXDQ_ADD_RN(e_u, MIXDQ_MUL_RN(g, MIXDQ_SUB_RN(e_t, e_i))),
+                      MIXDQ_MUL_RN(gi, MIXDQ_SUB_RN(e_i, e_u)));
+}
+
 MIXDQ_HD float mixdq_sampler_update(float x, float e, float a, float b) {
   return MIXDQ_ADD_RN(MIXDQ_MUL_RN(a, x), MIXDQ_MUL_RN(b, e));
 }

@@ -1410,6 +1410,11 @@ for _name, _head, _tail in (("", _STEP_ORDER1, []), ("_masked", _STEP_ORDER1, _S
                             ("_2m", _STEP_2M, []), ("_2m_masked", _STEP_2M, _STEP_MASKED)):
     getattr(_lib, "mixdq_sampler_step" + _name).argtypes = _head + _STEP_SHARED + _tail + [_vp]
     getattr(_lib, "mixdq_sampler_step" + _name).restype = _i32
+# the three-row step: x, eps, in, table, width, t_table, n_steps, step, timestep, guidance, image_guidance, n, row_stride,
+# noise, noise_stride, seeds, n_image, hist, first, then the masked operands
+_lib.mixdq_sampler_step3.argtypes = ([_vp] * 4 + [_i32, _vp, _i32, _vp, _vp, ctypes.c_float, ctypes.c_float, _i64, _i64]
+                                     + [_vp, _i64, _vp, _i64, _vp, _vp] + _STEP_MASKED + [_vp])
+_lib.mixdq_sampler_step3.restype = _i32
 _lib.mixdq_randn_f32.argtypes = [_vp, _i32, _i64, _vp, ctypes.c_uint32, ctypes.c_uint32, _vp]
 _lib.mixdq_randn_f32.restype = _i32
 _lib.mixdq_rng_normals_from_bits.argtypes = [_vp, _vp, _i64, _vp]
@@ -1472,10 +1477,11 @@ def rng_normals_from_bits(r):
 
 def _sampler_step(what, x, eps, inp, table, width, t_table, step, timestep, guidance, rows_per_image, n, row_stride, *,
                   hist=None, first=None, masked=None, channels=4, noise=None, noise_stride=None, seeds=None,
-                  n_image=None):
-    """The checks and the call of the four step bindings.  `what`: the binding's name; `table`: coef (width 4) or, for
+                  n_image=None, image_guidance=None):
+    """The checks and the call of the five step bindings.  `what`: the binding's name; `table`: coef (width 4) or, for
     the multistep kinds, coef8 (width 8), which come with `hist` and `first`; masked: None or (z, noise0, mask, blend);
-    noise / seeds: at most one of them, width 4 only."""
+    noise / seeds: at most one of them, width 4 only; image_guidance: None, or the second scale of the three-row step
+    (mixdq_sampler_step3, rows_per_image == 3)."""
     if seeds is not None:
         n, n_image = _check_step_seeds(seeds, noise, n, n_image, x.numel(), what)
     f32, f16, i32 = torch.float32, torch.float16, torch.int32
@@ -1518,11 +1524,21 @@ def _sampler_step(what, x, eps, inp, table, width, t_table, step, timestep, guid
         if channels >= 1 and n % channels == 0:       # (anything else: the library's own error)
             _check(mask.is_contiguous() and mask.numel() >= n // channels,
                    "mask should be dense with n / channels entries")
-    if rows_per_image in (1, 2):                      # (anything else: the library's own error)
+    if rows_per_image in (1, 2) or image_guidance is not None:   # (anything else: the library's own error)
         need = (rows_per_image - 1) * row_stride + n
         _check(eps.numel() >= need and inp.numel() >= need, "eps / inp are smaller than rows_per_image row blocks")
     if noise is not None:
         _check(noise.numel() >= (n_steps - 1) * noise_stride + n, "noise is smaller than n_steps blocks")
+    if image_guidance is not None:
+        args = [x.data_ptr(), eps.data_ptr(), inp.data_ptr(), table.data_ptr(), width, t_table.data_ptr(), n_steps,
+                step.data_ptr(), timestep.data_ptr(), float(guidance), float(image_guidance), n, row_stride,
+                _ptr(noise), noise_stride, _ptr(seeds), 0 if seeds is None else n_image, _ptr(hist), _ptr(first)]
+        args += [t_.data_ptr() for t_ in masked[:3]] + [channels, masked[3].data_ptr()] if masked is not None else [
+            None, None, None, 1, None]
+        with torch.cuda.device(x.device):
+            code = _lib.mixdq_sampler_step3(*args, _stream())
+        _status(code, what)
+        return
     args = [x.data_ptr(), eps.data_ptr(), inp.data_ptr()]
     if two_m:
         args += [hist.data_ptr(), table.data_ptr(), t_table.data_ptr(), n_steps, step.data_ptr(), first.data_ptr()]
@@ -1597,6 +1613,33 @@ def sampler_step_2m_masked(x, eps, inp, hist, coef8, t_table, step, first, times
                   row_stride, hist=hist, first=first, masked=(z, noise0, mask, blend), channels=channels)
 
 
+def sampler_step3(x, eps, inp, table, t_table, step, timestep, guidance, image_guidance, *, noise=None, seeds=None,
+                  n_image=None, hist=None, first=None, z=None, noise0=None, mask=None, blend=None, channels=4, n=None,
+                  row_stride=None, noise_stride=None):
+    """One sampler step with THREE UNet rows per image and two guidance scales (mixdq_sampler_step3; InstructPix2Pix).
+    eps / inp: fp16, three blocks of `n` elements `row_stride` apart in diffusers' InstructPix2Pix order -- block 0 text +
+    image (e_t), block 1 image only (e_i), block 2 neither (e_u); NOT the two-row convention, whose unconditional block
+    comes first.  e = (e_u + guidance * (e_t - e_i)) + image_guidance * (e_i - e_u), then the sibling's step:
+
+    table: coef fp32 [n_steps, 4] (sampler_step / sampler_step_masked, with `noise` or `seeds` / `n_image` as there), or
+    coef8 fp32 [n_steps, 8] together with `hist` and `first` (sampler_step_2m[_masked]; no noise).  z, noise0, mask and
+    blend (all four, with `channels`) add sampler_step_masked's blend.  The next FP16 input goes to all three blocks of
+    `inp`; `timestep` and `step` advance as in sampler_step."""
+    width = table.shape[1] if torch.is_tensor(table) and table.dim() == 2 else 4
+    _check(width in (4, 8), "sampler_step3: table should be coef [n_steps, 4] or coef8 [n_steps, 8]")
+    if width == 8:
+        _check(noise is None and seeds is None, "sampler_step3: the multistep kinds add no noise")
+        _check(hist is not None and first is not None, "sampler_step3: coef8 comes with hist and first")
+    else:
+        _check(hist is None and first is None, "sampler_step3: hist and first come with coef8")
+    some = [t_ is not None for t_ in (z, noise0, mask, blend)]
+    _check(all(some) or not any(some), "sampler_step3: z, noise0, mask and blend go together")
+    _sampler_step("sampler_step3", x, eps, inp, table, width, t_table, step, timestep, guidance, 3, n, row_stride,
+                  hist=hist, first=first, masked=(z, noise0, mask, blend) if all(some) else None, channels=channels,
+                  noise=noise, noise_stride=noise_stride, seeds=seeds, n_image=n_image,
+                  image_guidance=image_guidance)
+
+
 _lib.mixdq_image_to_nhwc8_f16.argtypes = [_vp, _i32, _i64, _i64, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _vp]
 _lib.mixdq_image_to_nhwc8_f16.restype = _i32
 _lib.mixdq_vae_latent_sample.argtypes = [_vp, _vp, _vp, _i64, _i32, ctypes.c_float, _vp]
@@ -1606,6 +1649,8 @@ _lib.mixdq_image_to_nhwc8_f16_masked.argtypes = ([_vp, _i32] + [_i64] * 4 + [_vp
 _lib.mixdq_image_to_nhwc8_f16_masked.restype = _i32
 _lib.mixdq_inpaint_cond_f16.argtypes = [_vp, _vp, _vp, _i64, _i32, _vp]
 _lib.mixdq_inpaint_cond_f16.restype = _i32
+_lib.mixdq_ip2p_cond_f16.argtypes = [_vp, _vp, _i32, _i64, _i32, _i32, ctypes.c_float, _vp]
+_lib.mixdq_ip2p_cond_f16.restype = _i32
 IMAGE_DTYPES = {torch.uint8: 0, torch.float16: 1, torch.float32: 2}      # include/mixdq_hip.h MIXDQ_IMAGE_*
 
 
@@ -1712,6 +1757,28 @@ def inpaint_cond(mask_lat, zl):
     with torch.cuda.device(zl.device):
         code = _lib.mixdq_inpaint_cond_f16(mask_lat.data_ptr(), zl.data_ptr(), out.data_ptr(), B * h * w, L, _stream())
     _status(code, "inpaint_cond")
+    return out.permute(0, 3, 1, 2)
+
+
+def ip2p_cond(moments, rows=3, scale=1.0):
+    """The conditioning channels of an 8-channel InstructPix2Pix UNet (mixdq_ip2p_cond_f16): moments fp16 [B, 2L, h, w] in
+    channels-last storage (what VAEEncoder.moments returns), 1 <= L <= 8 -> fp16 [rows * B, 8, h, w] in channels-last
+    storage, rows 1 or 3.  Row blocks in sampler_step3's order -- text + image, image only, neither: the first
+    min(rows, 2) blocks hold f16(f32(mean) * scale) in channels 0..L-1 and +0.0 behind them, the third block is all +0.0.
+    scale 1.0 returns the mean's own bits (latent_dist.mode(), unscaled: diffusers' InstructPix2Pix pipelines).  What
+    Sampler.sample(cond=) and SDXLUNet.cond_term take."""
+    _check(torch.is_tensor(moments) and moments.is_cuda and moments.dtype == torch.float16 and moments.dim() == 4
+           and moments.shape[1] % 2 == 0 and moments.permute(0, 2, 3, 1).is_contiguous(),
+           "ip2p_cond: moments should be a channels-last fp16 [B, 2L, h, w] GPU tensor")
+    B, C2, h, w = moments.shape
+    L = C2 // 2
+    _check(1 <= L <= 8, "ip2p_cond: moments should hold 1 to 8 latent channels")
+    _check(rows in (1, 3), "ip2p_cond: rows should be 1 or 3 (a two-row run cannot say which block is unconditioned)")
+    out = torch.empty((rows * B, h, w, 8), dtype=torch.float16, device=moments.device)
+    with torch.cuda.device(moments.device):
+        code = _lib.mixdq_ip2p_cond_f16(moments.data_ptr(), out.data_ptr(), B, h * w, L, int(rows), float(scale),
+                                        _stream())
+    _status(code, "ip2p_cond")
     return out.permute(0, 3, 1, 2)
 
 

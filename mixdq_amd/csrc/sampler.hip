@@ -5,12 +5,16 @@
 // Every step is ONE kernel template, sampler_step_kernel<ROWS, ORDER, NOISE, MASK>, and one per-element function
 // (step_one) built from include/mixdq_math.h -- FP32 round-to-nearest, no contraction:
 //   e   = eps_u + g * (eps_c - eps_u)                     ROWS 2 (rows_per_image; 1: e = eps_u)
+//   e   = (e_u + g * (e_t - e_i)) + gi * (e_i - e_u)      ROWS 3 (InstructPix2Pix: row blocks e_t, e_i, e_u in that order)
 //   x'  = (a*x + b*e) + c*n                               ORDER 1; NOISE 0: a*x + b*e;  (a, b, c, s_next) = coef[*step]
 //   x0  = u*x + v*e,  x' = A*x + B*x0 [+ D*hist]          ORDER 2; (u, v, A, B1, B2, D2, s_next, 0) = coef8[*step]
 //   x'' = (1 - m)*(p*z + q*n0) + m*x'                     MASK 1, 2; (p, q) = blend[*step], m = mask[i / channels]
 //   in  = f16_rn(x'' * s_next)                            written to every UNet row of the image; x'' stored to x
 // A mode's operands are read only by the instantiations of that mode; the six mixdq_sampler_step* entry points fill
 // one operand set (StepArgs), check it (check_step) and launch (launch_step), which picks the instantiation.
+// mixdq_sampler_step3 is the one entry point of ROWS 3: it takes the whole operand set flat, a mode's operands null
+// where the mode is off.  The two-row blocks are (unconditional, conditional); the three-row blocks follow diffusers'
+// InstructPix2Pix pipelines: block 0 text + image, block 1 image only, block 2 neither.
 //
 // ORDER 1 -- Euler, Euler-ancestral, DDIM and LCM with an epsilon-predicting model -- is one affine map with per-step
 // scalars.  ORDER 2 (DPM-Solver++ 2M, mixdq_sampler_step_2m[_masked]) is NOT an affine map of (x, eps, noise): a
@@ -162,21 +166,24 @@ __global__ __launch_bounds__(256) void normals_from_bits_kernel(const uint32_t* 
   }
 }
 
-// The scalars of one launch: the guidance scale and row *step of the tables.  ORDER 1: (a, b, c, s_next) = coef[*step].
+// The scalars of one launch: the guidance scale (ROWS 3: and the image guidance scale gi) and row *step of the tables.  ORDER 1: (a, b, c, s_next) = coef[*step].
 // ORDER 2: a = A, d = D2 and b = B2 on a second-order step, B1 on a first-order one.  Which order a step takes depends
 // on the table and on two device scalars only -- the first executed step of a run (*step == *first) and a row with
 // D2 == 0 are first-order -- so `second` is uniform over the launch.  MASK: (p, q) = blend[*step].
 struct StepRow {
-  float g, a, b, c, u, v, d, s_next, p, q;
+  float g, gi, a, b, c, u, v, d, s_next, p, q;
   bool second;
 };
 
-// One element: guidance, the update, the blend.  n, h and (z, n0, m) are operands of NOISE != 0, of a second-order
+// One element: guidance, the update, the blend.  (e0, e1, e2) are the element's values in the row blocks -- ROWS 1: e0;
+// ROWS 2: (eps_u, eps_c); ROWS 3: (e_t, e_i, e_u).  n, h and (z, n0, m) are operands of NOISE != 0, of a second-order
 // step and of MASK != 0 only; ORDER 2 hands the data prediction (the next step's h, unblended) back in *x0_out.
 template <int ROWS, int ORDER, int NOISE, int MASK>
-__device__ __forceinline__ float step_one(const StepRow& k, float x, float eu, float ec, float n, float h, float z,
-                                          float n0, float m, float* x0_out) {
-  const float e = ROWS == 2 ? mixdq_sampler_guided_eps(eu, ec, k.g) : eu;
+__device__ __forceinline__ float step_one(const StepRow& k, float x, float e0, float e1, float e2, float n, float h,
+                                          float z, float n0, float m, float* x0_out) {
+  const float e = ROWS == 3   ? mixdq_sampler_guided_eps3(e0, e1, e2, k.g, k.gi)
+                  : ROWS == 2 ? mixdq_sampler_guided_eps(e0, e1, k.g)
+                              : e0;
   float y;
   if constexpr (ORDER == 1) {
     y = NOISE ? mixdq_sampler_update_noise(x, e, n, k.a, k.b, k.c) : mixdq_sampler_update(x, e, k.a, k.b);
@@ -196,7 +203,8 @@ __device__ __forceinline__ float step_one(const StepRow& k, float x, float eu, f
 template <int ROWS, int ORDER, int NOISE, int MASK>
 __global__ __launch_bounds__(256) void sampler_step_kernel(
     float* __restrict__ x, const __half* __restrict__ eps, __half* __restrict__ in, const float* __restrict__ table,
-    const int* __restrict__ step_p, int n_steps, float g, int64_t n, int64_t row_stride, const float* __restrict__ noise,
+    const int* __restrict__ step_p, int n_steps, float g, float gi, int64_t n, int64_t row_stride,
+    const float* __restrict__ noise,
     int64_t noise_stride, const uint64_t* __restrict__ seeds, int64_t n_image, float* __restrict__ hist,
     const int* __restrict__ first_p, const float* __restrict__ z, const float* __restrict__ noise0,
     const float* __restrict__ mask, int channels, const float* __restrict__ blend) {
@@ -204,7 +212,7 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(
   const int step = *step_p;
   if (step < 0 || step >= n_steps) return;        // replayed past the table: nothing is read or written
   StepRow k = {};
-  k.g = g;
+  k.g = g, k.gi = gi;
   if constexpr (ORDER == 1) {
     const float4 r = *reinterpret_cast<const float4*>(table + 4 * (int64_t)step);
     k.a = r.x, k.b = r.y, k.c = r.z, k.s_next = r.w;
@@ -226,9 +234,10 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(
     const int64_t o = i << 3;
     float xs[8], ns[8] = {}, hs[8] = {}, zs[8] = {}, is[8] = {}, ms[8] = {};
     load8(x + o, xs);
-    const Half8 eu = *reinterpret_cast<const Half8*>(eps + o);
-    Half8 ec = eu;
-    if (ROWS == 2) ec = *reinterpret_cast<const Half8*>(eps + row_stride + o);
+    const Half8 e0 = *reinterpret_cast<const Half8*>(eps + o);
+    Half8 e1 = e0, e2 = e0;
+    if (ROWS >= 2) e1 = *reinterpret_cast<const Half8*>(eps + row_stride + o);
+    if (ROWS == 3) e2 = *reinterpret_cast<const Half8*>(eps + 2 * row_stride + o);
     noise8<NOISE>(nz, seeds, n_image, o, (uint32_t)step, ns);
     if constexpr (ORDER == 2) {
       if (k.second) load8(hist + o, hs);
@@ -242,8 +251,8 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(
     Half8 out;
 #pragma unroll
     for (int j = 0; j < 8; ++j)
-      y[j] = step_one<ROWS, ORDER, NOISE, MASK>(k, xs[j], half_at(eu, j), half_at(ec, j), ns[j], hs[j], zs[j], is[j],
-                                                ms[j], &p0[j]);
+      y[j] = step_one<ROWS, ORDER, NOISE, MASK>(k, xs[j], half_at(e0, j), half_at(e1, j), half_at(e2, j), ns[j], hs[j],
+                                                zs[j], is[j], ms[j], &p0[j]);
 #pragma unroll
     for (int j = 0; j < 4; ++j)
       out.w[j] = half_bits(mixdq_sampler_scaled_input(y[2 * j], k.s_next)) |
@@ -251,25 +260,28 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(
     if constexpr (ORDER == 2) store8(hist + o, p0);
     store8(x + o, y);
     *reinterpret_cast<Half8*>(in + o) = out;
-    if (ROWS == 2) *reinterpret_cast<Half8*>(in + row_stride + o) = out;
+    if (ROWS >= 2) *reinterpret_cast<Half8*>(in + row_stride + o) = out;
+    if (ROWS == 3) *reinterpret_cast<Half8*>(in + 2 * row_stride + o) = out;
   }
   // tail (n % 8 elements), by the first threads of block 0
   const int64_t t = (nvec << 3) + threadIdx.x;
   if (blockIdx.x == 0 && t < n) {
-    const float eu = __half2float(eps[t]);
-    const float ec = ROWS == 2 ? __half2float(eps[row_stride + t]) : eu;
+    const float e0 = __half2float(eps[t]);
+    const float e1 = ROWS >= 2 ? __half2float(eps[row_stride + t]) : e0;
+    const float e2 = ROWS == 3 ? __half2float(eps[2 * row_stride + t]) : e0;
     float hv = 0.0f, zv = 0.0f, iv = 0.0f, mv = 0.0f, p0;
     if constexpr (ORDER == 2) {
       if (k.second) hv = hist[t];
     }
     if constexpr (MASK != 0) zv = z[t], iv = noise0[t], mv = mask[t / channels];
     const float y = step_one<ROWS, ORDER, NOISE, MASK>(
-        k, x[t], eu, ec, tail_noise<NOISE>(nz, seeds, n_image, t, (uint32_t)step), hv, zv, iv, mv, &p0);
+        k, x[t], e0, e1, e2, tail_noise<NOISE>(nz, seeds, n_image, t, (uint32_t)step), hv, zv, iv, mv, &p0);
     const __half h = f32_to_f16_rn(mixdq_sampler_scaled_input(y, k.s_next));
     if constexpr (ORDER == 2) hist[t] = p0;
     x[t] = y;
     in[t] = h;
-    if (ROWS == 2) in[row_stride + t] = h;
+    if (ROWS >= 2) in[row_stride + t] = h;
+    if (ROWS == 3) in[2 * row_stride + t] = h;
   }
 }
 
@@ -295,6 +307,8 @@ struct StepArgs {
   int64_t n;
   int rows_per_image;
   int64_t row_stride;
+  float image_guidance = 0.0f;                     // rows_per_image == 3
+  bool three = false;                              // mixdq_sampler_step3: the only entry point that takes three rows
   const float* noise = nullptr;                    // the plain entry points' noise_or_null
   int64_t noise_stride = 0;
   bool rng = false, multistep = false, masked = false;
@@ -313,13 +327,14 @@ struct StepArgs {
 // The argument checks of every entry point, in one order: the base operands, then those of rng, multistep, masked.
 int check_step(const StepArgs& a) {
   if (!a.x || !a.eps_f16 || !a.in_f16 || !a.table || !a.t_table || !a.step || !a.timestep) return MIXDQ_ERR_INVALID_ARG;
-  if (a.n < 0 || a.n_steps < 1 || (a.rows_per_image != 1 && a.rows_per_image != 2)) return MIXDQ_ERR_INVALID_ARG;
-  if (a.rows_per_image == 2 && a.row_stride < a.n) return MIXDQ_ERR_INVALID_ARG;  // the two row blocks would overlap
+  if (a.n < 0 || a.n_steps < 1 || (a.three ? a.rows_per_image != 3 : a.rows_per_image != 1 && a.rows_per_image != 2))
+    return MIXDQ_ERR_INVALID_ARG;
+  if (a.rows_per_image >= 2 && a.row_stride < a.n) return MIXDQ_ERR_INVALID_ARG;  // the row blocks would overlap
   if (a.noise && a.noise_stride < a.n) return MIXDQ_ERR_INVALID_ARG;
   if ((uintptr_t)a.x % 16 || (uintptr_t)a.eps_f16 % 16 || (uintptr_t)a.in_f16 % 16 || (uintptr_t)a.table % 16 ||
       (uintptr_t)a.noise % 16 || (uintptr_t)a.t_table % 4 || (uintptr_t)a.step % 4 || (uintptr_t)a.timestep % 4)
     return MIXDQ_ERR_ALIGNMENT;
-  if ((a.rows_per_image == 2 && a.row_stride % 8) || (a.noise && a.noise_stride % 4)) return MIXDQ_ERR_ALIGNMENT;
+  if ((a.rows_per_image >= 2 && a.row_stride % 8) || (a.noise && a.noise_stride % 4)) return MIXDQ_ERR_ALIGNMENT;
   if (a.rng) {
     if (!a.seeds || a.n_image < 1 || a.n % a.n_image) return MIXDQ_ERR_INVALID_ARG;
     if ((uintptr_t)a.seeds % 8) return MIXDQ_ERR_ALIGNMENT;
@@ -358,7 +373,7 @@ int launch_step(const StepArgs& a, mixdq_stream_t stream_) {
   if (a.n > 0) {
     const int noise = a.rng ? (a.n_image % 8 == 0 ? 2 : 3) : (a.noise ? 1 : 0);
     const int mask = a.masked ? (a.channels == 4 ? 1 : 2) : 0;
-    with_constant<1, 2>(a.rows_per_image, [&](auto rows) {
+    with_constant<1, 2, 3>(a.rows_per_image, [&](auto rows) {
       with_constant<1, 2>(a.multistep ? 2 : 1, [&](auto order) {
         with_constant<0, 1, 2, 3>(noise, [&](auto nz) {
           with_constant<0, 1, 2>(mask, [&](auto m) {
@@ -366,9 +381,9 @@ int launch_step(const StepArgs& a, mixdq_stream_t stream_) {
             constexpr int NOISE = decltype(nz)::value, MASK = decltype(m)::value;
             if constexpr (ORDER == 1 || NOISE == 0)
               sampler_step_kernel<ROWS, ORDER, NOISE, MASK><<<grid_blocks(a.n >> 3), 256, 0, stream>>>(
-                  a.x, (const __half*)a.eps_f16, (__half*)a.in_f16, a.table, a.step, a.n_steps, a.guidance, a.n,
-                  a.row_stride, a.noise, a.noise_stride, a.seeds, a.n_image, a.hist, a.first, a.z, a.noise0, a.mask,
-                  a.channels, a.blend);
+                  a.x, (const __half*)a.eps_f16, (__half*)a.in_f16, a.table, a.step, a.n_steps, a.guidance,
+                  a.image_guidance, a.n, a.row_stride, a.noise, a.noise_stride, a.seeds, a.n_image, a.hist, a.first, a.z,
+                  a.noise0, a.mask, a.channels, a.blend);
           });
         });
       });
@@ -465,5 +480,25 @@ extern "C" int mixdq_sampler_step_2m_masked(float* x, const void* eps_f16, void*
   StepArgs a = {x, eps_f16, in_f16, coef8, t_table, n_steps, step, timestep, guidance, n, rows_per_image, row_stride};
   a.multistep = true, a.hist = hist, a.first = first;
   a.set_masked(z, noise0, mask, channels, blend);
+  return launch_step(a, stream_);
+}
+
+// ---- three rows per image (InstructPix2Pix): the whole operand set flat, a mode's operands null where it is off --------
+extern "C" int mixdq_sampler_step3(float* x, const void* eps_f16, void* in_f16, const float* table, int table_width,
+                                   const float* t_table, int n_steps, int* step, float* timestep, float guidance,
+                                   float image_guidance, int64_t n, int64_t row_stride, const float* noise_or_null,
+                                   int64_t noise_stride, const uint64_t* seeds_or_null, int64_t n_image,
+                                   float* hist_or_null, const int* first_or_null, const float* z, const float* noise0,
+                                   const float* mask, int channels, const float* blend, mixdq_stream_t stream_) {
+  StepArgs a = {x, eps_f16, in_f16, table, t_table, n_steps, step, timestep, guidance, n, 3, row_stride};
+  a.three = true, a.image_guidance = image_guidance;
+  const bool two_m = table_width == 8, stochastic = noise_or_null || seeds_or_null;
+  if (table_width != 4 && !two_m) return MIXDQ_ERR_INVALID_ARG;
+  if ((two_m && stochastic) || (noise_or_null && seeds_or_null)) return MIXDQ_ERR_INVALID_ARG;
+  if (two_m != (hist_or_null || first_or_null)) return MIXDQ_ERR_INVALID_ARG;   // (one of the pair: check_step's null check)
+  a.noise = noise_or_null, a.noise_stride = noise_stride;
+  if (seeds_or_null) a.rng = true, a.seeds = seeds_or_null, a.n_image = n_image;
+  if (two_m) a.multistep = true, a.hist = hist_or_null, a.first = first_or_null;
+  if (z || noise0 || mask || blend) a.set_masked(z, noise0, mask, channels, blend);
   return launch_step(a, stream_);
 }

@@ -18,6 +18,11 @@
 //   mixdq_inpaint_cond_f16            FP32 latent mask [B, h, w] + FP32 latents [B, h, w, L <= 7] -> FP16 [B, h, w, 8]
 //                                     (mask | latents | zeros): the padded form SDXLUNet.cond_term takes
 //
+// and the one InstructPix2Pix adds (its 8-channel UNet reads the unscaled image latents, zero in the unconditional rows):
+//
+//   mixdq_ip2p_cond_f16               FP16 moments [B, h, w, 2L] -> FP16 [rows * B, h, w, 8], rows 1 or 3: f16(mean *
+//                                     scale) | zeros in the first two row blocks, the third block all +0.0
+//
 // Arithmetic: include/mixdq_math.h (mixdq_pixel_to_unit, mixdq_vae_latent[_mode]), FP32 round-to-nearest, never
 // contracted.  Both are HBM-bound and grid-stride, one pixel (one group of four latent channels) per lane per trip;
 // every load of a trip is requested before the first value is used, and each lane writes one 16-byte store.
@@ -213,6 +218,38 @@ __global__ __launch_bounds__(256) void inpaint_cond_kernel(const float* __restri
   }
 }
 
+// One lane = one latent pixel of one image: the L means of its moments, scaled, as FP16 in one 16-byte row (mean | zeros),
+// stored to the first min(ROWS, 2) row blocks of `out`; the third block (ROWS == 3) gets sixteen zero bytes.  Blocks are
+// `total` = B * pixels_per_image rows apart.  L4: the pixel's four means are one 8-byte load (the launcher checked
+// alignment).
+template <int ROWS, bool L4>
+__global__ __launch_bounds__(256) void ip2p_cond_kernel(const __half* __restrict__ moments, Half8* __restrict__ out,
+                                                        int64_t total, int L, float scale) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+    uint32_t h[8];
+    if constexpr (L4) {
+      const Half4 m = *reinterpret_cast<const Half4*>(moments + i * 8);
+#pragma unroll
+      for (int c = 0; c < 8; ++c)
+        h[c] = c < 4 ? half_bits(mixdq_vae_latent_mode(half_of(m.w[c >> 1], c & 1), scale)) : 0u;
+    } else {
+      const __half* m = moments + i * (2 * (int64_t)L);
+#pragma unroll
+      for (int c = 0; c < 8; ++c)                                    // the log-variances and channels >= L are never read
+        h[c] = c < L ? half_bits(mixdq_vae_latent_mode(__half2float(m[c]), scale)) : 0u;
+    }
+    Half8 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o.w[j] = h[2 * j] | (h[2 * j + 1] << 16);
+    out[i] = o;
+    if constexpr (ROWS == 3) {
+      out[total + i] = o;
+      out[2 * total + i] = Half8{{0u, 0u, 0u, 0u}};
+    }
+  }
+}
+
 // One lane = one pixel: three decoded FP16 values, the mask value, three original bytes, three bytes out.
 template <typename T>
 __global__ __launch_bounds__(256) void composite_u8_kernel(const __half* __restrict__ dec, int64_t db, int64_t dc,
@@ -405,5 +442,24 @@ extern "C" int mixdq_inpaint_cond_f16(const float* mask_lat, const float* zl, vo
     inpaint_cond_kernel<true><<<blocks, 256, 0, stream>>>(mask_lat, zl, out, pixels, L);
   else
     inpaint_cond_kernel<false><<<blocks, 256, 0, stream>>>(mask_lat, zl, out, pixels, L);
+  return launch_status();
+}
+
+extern "C" int mixdq_ip2p_cond_f16(const void* moments_f16, void* out_f16, int B, int64_t pixels_per_image, int L,
+                                   int rows, float scale, mixdq_stream_t stream_) {
+  if (B < 0 || pixels_per_image < 0 || L < 1 || L > 8 || (rows != 1 && rows != 3)) return MIXDQ_ERR_INVALID_ARG;
+  const int64_t total = (int64_t)B * pixels_per_image;
+  if (total == 0) return MIXDQ_OK;                  // (an empty tensor has no storage: before the pointer checks)
+  if (!moments_f16 || !out_f16) return MIXDQ_ERR_INVALID_ARG;
+  if ((uintptr_t)out_f16 % 16 || (uintptr_t)moments_f16 % 2) return MIXDQ_ERR_ALIGNMENT;
+  hipStream_t stream = (hipStream_t)stream_;
+  const __half* m = (const __half*)moments_f16;
+  Half8* out = (Half8*)out_f16;
+  const int blocks = grid_for(total);
+  const bool l4 = L == 4 && (uintptr_t)moments_f16 % 8 == 0;
+#define P_LAUNCH(R, V) ip2p_cond_kernel<R, V><<<blocks, 256, 0, stream>>>(m, out, total, L, scale)
+  if (rows == 3) { if (l4) P_LAUNCH(3, true); else P_LAUNCH(3, false); }
+  else { if (l4) P_LAUNCH(1, true); else P_LAUNCH(1, false); }
+#undef P_LAUNCH
   return launch_status();
 }

@@ -47,6 +47,15 @@ input buffer and the four graphs stay as they are; `cond` is orthogonal to init_
 and runs such a UNet without the blend; `Sampler.inpaint_ext` is inpaint with three more keywords (`inpaint` calls it
 with their defaults): `blend=True` keeps the blend as well, `mask_grow` > 0 grows the mask first
 (mixdq_mask_dilate_u8), `cond_latent_noise` is the blanked image's posterior noise.  DESIGN.md section 3.30.
+
+InstructPix2Pix (an 8-channel UNet: unet.cond_channels == 4; diffusers' StableDiffusion[XL]InstructPix2PixPipeline) is a
+different loop, not just another checkpoint: `Sampler(..., image_guidance_scale=s_I)` runs THREE UNet rows per image --
+row blocks in those pipelines' order: text + image, image only, neither -- and every captured graph records
+mixdq_sampler_step3, whose guidance is e = e_u + s_T (e_t - e_i) + s_I (e_i - e_u).  The conditioning differs between
+the row blocks: the UNSCALED image latents (the posterior's mode) in the first two, zero in the third
+(mixdq_ip2p_cond_f16).  `Sampler.instruct` runs VAEEncoder.moments, that launch, the loop from pure noise and
+VAEDecoder.decode on one stream.  Everything else -- kinds, masks, seeds, the four graphs, the static buffers -- is
+unchanged: 3B rows is simply a batch.  DESIGN.md section 3.32.
 """
 import numpy as np
 
@@ -288,14 +297,23 @@ class Sampler:
     the schedule adds noise per step, the first seeded call captures one more graph -- the UNet forward, then
     mixdq_sampler_step[_masked]_rng, which computes that noise in registers from a static seed buffer -- on the same
     static buffers and in the same memory pool; calls with and without `seed` alternate in any order, every seed
-    replays the same graph, and the [n_steps, ...] noise buffer exists only once a call without `seed` was made."""
+    replays the same graph, and the [n_steps, ...] noise buffer exists only once a call without `seed` was made.
 
-    def __init__(self, unet, kind, n_steps, guidance_scale=0.0, spacing=None, karras=False):
+    image_guidance_scale (a number; None: everything above): InstructPix2Pix.  The UNet runs at 3B rows whatever the
+    two scales are, and `encoder_hidden_states` (and the tensors of `added_cond_kwargs`) carry them in diffusers'
+    InstructPix2Pix order, cat([prompt, negative, negative]): B rows with text + image, B with the image only, B with
+    neither -- NOT the two-row order, where the unconditional rows come first.  `cond` follows the same blocks
+    (_C.ip2p_cond).  Every captured graph then records mixdq_sampler_step3 with both scales:
+    e = e_u + guidance_scale * (e_t - e_i) + image_guidance_scale * (e_i - e_u)."""
+
+    def __init__(self, unet, kind, n_steps, guidance_scale=0.0, spacing=None, karras=False, *,
+                 image_guidance_scale=None):
         self.unet = unet
         self.schedule = Schedule(kind, n_steps, spacing, karras)
         self.kind, self.n_steps = kind, int(n_steps)
         self.guidance_scale = float(guidance_scale)
-        self.rows_per_image = 2 if self.guidance_scale > 1.0 else 1
+        self.image_guidance_scale = None if image_guidance_scale is None else float(image_guidance_scale)
+        self.rows_per_image = 3 if image_guidance_scale is not None else 2 if self.guidance_scale > 1.0 else 1
         self._graph = None
         self._graph_masked = None
         self._graph_rng = None
@@ -335,7 +353,8 @@ class Sampler:
     def _capture(self, noise, masked=False, rng=False):
         """Capture one step -- the UNet forward, then mixdq_sampler_step (masked: mixdq_sampler_step_masked, reading the
         static z / noise0 / mask buffers made here; rng: the _rng entry points, reading the static seeds in place of
-        the step-noise buffer) -- on the static buffers and return the graph."""
+        the step-noise buffer; three rows per image: mixdq_sampler_step3 with the same operands) -- on the static
+        buffers and return the graph."""
         import torch
         from mixdq_amd import _C
         dev = noise.device
@@ -352,7 +371,19 @@ class Sampler:
         # the binding and its operands behind (x, eps): chosen once, here, not inside one_step
         blend = (self._z, self._noise0, self._mask, self._blend) if masked else ()
         kw = dict(channels=C, n=n) if masked else dict(n=n)
-        if self.schedule.order == 2:
+        if self.rows_per_image == 3:  # one binding for every mode: the operands of a mode that is off stay None
+            step_fn = _C.sampler_step3
+            tail = (self._in, self._coef, self._t_table, self._step, self._t, self.guidance_scale,
+                    self.image_guidance_scale)
+            if masked:
+                kw.update(z=self._z, noise0=self._noise0, mask=self._mask, blend=self._blend)
+            if self.schedule.order == 2:
+                kw.update(hist=self._hist, first=self._first)
+            elif rng:
+                kw.update(seeds=self._seeds, n_image=C * H * W)
+            else:
+                kw.update(noise=self._noise)
+        elif self.schedule.order == 2:
             step_fn = _C.sampler_step_2m_masked if masked else _C.sampler_step_2m
             tail = (self._in, self._hist, self._coef, self._t_table, self._step, self._first, self._t, *blend,
                     self.guidance_scale, self.rows_per_image)
@@ -442,7 +473,8 @@ class Sampler:
         R = B * self.rows_per_image
         if cond is None:
             raise RuntimeError(f"Sampler.sample: this UNet has {cc} conditioning channels: cond is required "
-                               "(_C.inpaint_cond of the latent mask and the masked image's latents)")
+                               "(_C.inpaint_cond of the latent mask and the masked image's latents; _C.ip2p_cond of "
+                               "the image's moments for InstructPix2Pix)")
         if not (torch.is_tensor(cond) and cond.device == noise.device and cond.dtype == torch.float16
                 and cond.dim() == 4 and cond.shape[0] in (B, R) and cond.shape[1] in (cc, 8)
                 and tuple(cond.shape[2:]) == (H, W)):
@@ -460,8 +492,8 @@ class Sampler:
 
     def sample(self, noise, encoder_hidden_states, added_cond_kwargs=None, step_noise=None, *, init_latents=None,
                strength=None, mask=None, seed=None, cond=None):
-        """noise [B, C, H, W] (unit variance; FP32 or FP16), encoder_hidden_states [R, T, D] FP16 (R = B, or 2B
-        under guidance), added_cond_kwargs as the UNet takes them (R rows), step_noise [n_steps, B, C, H, W]: the
+        """noise [B, C, H, W] (unit variance; FP32 or FP16), encoder_hidden_states [R, T, D] FP16 (R = B, 2B
+        under guidance, or 3B with image_guidance_scale), added_cond_kwargs as the UNet takes them (R rows), step_noise [n_steps, B, C, H, W]: the
         noise each stochastic step adds (required where the schedule has a non-zero c: euler_ancestral and lcm with
         more than one step) -- unless `seed` is given.  Returns the FP32 latents.
 
@@ -492,7 +524,9 @@ class Sampler:
         same mask and image in both).  It is constant over the run, so its share of conv_in is computed ONCE here
         (unet.cond_term, outside the graph) into a static buffer that every captured step adds in its conv_in epilogue:
         no concatenated 9-channel input exists, the graphs are the four above, and calls with different `cond` replay
-        the same graph objects.  Orthogonal to init_latents / strength / mask / seed."""
+        the same graph objects.  Orthogonal to init_latents / strength / mask / seed.  An 8-channel InstructPix2Pix
+        UNet takes the image latents here: _C.ip2p_cond(enc.moments(image), rows=3) -- R rows, zero in the third block
+        (Sampler.instruct builds it)."""
         import torch
         from mixdq_amd.quantize_sdxl import _copy_into
         seeds = None
@@ -604,6 +638,30 @@ class Sampler:
         z = enc.encode(image, self._latent_noise(latent_noise, latent_seed, noise, encoder_hidden_states))
         latents = self.sample(noise, encoder_hidden_states, added_cond_kwargs, step_noise, init_latents=z,
                               strength=strength, seed=seed, cond=cond)
+        return latents, dec.decode(latents)
+
+    def instruct(self, enc, dec, image, noise, encoder_hidden_states, added_cond_kwargs=None, *, step_noise=None,
+                 seed=None, cond_scale=1.0):
+        """InstructPix2Pix on one stream: `enc.moments(image)` (a mixdq_amd.vae.VAEEncoder), `_C.ip2p_cond(moments,
+        rows=self.rows_per_image, scale=cond_scale)`, sample(noise, ..., cond=that) and `dec.decode` (a VAEDecoder) --
+        nothing waits for the GPU in between.  The run starts from PURE noise: the image enters only through `cond`, the
+        posterior's mode UNSCALED (cond_scale 1.0: diffusers' pipelines; CosXL-Edit: the VAE's scaling_factor) in the
+        text + image and image-only row blocks and zero in the unconditional one.  noise: [B, C, H/8, W/8], or with
+        `seed` that shape; encoder_hidden_states / added_cond_kwargs: 3B rows, cat([prompt, negative, negative]).
+        Returns (FP32 latents, FP16 image [B, 3, H, W]), as img2img.  A Sampler without image_guidance_scale and
+        guidance (rows_per_image == 1) runs the image-conditioned row alone; rows_per_image == 2 is refused: a two-row
+        run cannot say which block is unconditioned."""
+        from mixdq_amd import _C
+        cc = int(getattr(self.unet, "cond_channels", 0))
+        if cc <= 0 or cc != int(enc.cfg["latent_channels"]):
+            raise RuntimeError(f"Sampler.instruct: the UNet's {cc} conditioning channels are not the VAE's "
+                               f"{enc.cfg['latent_channels']} latent channels (an InstructPix2Pix UNet has 2 x latent "
+                               "input channels)")
+        if self.rows_per_image == 2:
+            raise RuntimeError("Sampler.instruct: a two-row run cannot say which block is unconditioned: construct the "
+                               "Sampler with image_guidance_scale= (three rows per image)")
+        cond = _C.ip2p_cond(enc.moments(image), rows=self.rows_per_image, scale=cond_scale)
+        latents = self.sample(noise, encoder_hidden_states, added_cond_kwargs, step_noise, seed=seed, cond=cond)
         return latents, dec.decode(latents)
 
     def inpaint(self, enc, dec, image, mask, noise, encoder_hidden_states, added_cond_kwargs=None, *, strength=None,

@@ -422,6 +422,15 @@ SD15_CONFIG = dict(
 SDXL_INPAINT_CONFIG = dict(SDXL_CONFIG, in_channels=9)
 SD15_INPAINT_CONFIG = dict(SD15_CONFIG, in_channels=9)
 
+# InstructPix2Pix (timbrooks/instruct-pix2pix; diffusers' StableDiffusion[XL]InstructPix2PixPipeline): the same networks
+# with an 8-channel conv_in, whose input is cat([scaled latents (4), UNSCALED latents of the image to edit (4)]).  The
+# four conditioning channels are constant over a run (and zero in the unconditional rows): SDXLUNet.cond_term, fed by
+# _C.ip2p_cond.  An 8-channel conv_in COULD be quantized (in_channels % 4 == 0), but the split conv_in needs it as a
+# floating-point layer and refuses a quantized one: leave 'conv_in' out of the activation bit-width config of these
+# UNets (it then falls back to FP16, as a 9-channel one does by itself).  859 532 484 / 2 567 475 204 parameters.
+SD15_IP2P_CONFIG = dict(SD15_CONFIG, in_channels=8)
+SDXL_IP2P_CONFIG = dict(SDXL_CONFIG, in_channels=8)
+
 
 def head_width(cfg, channels: int) -> int:
     """Width of an attention head at a level of `channels` channels: cfg['head_dim'] (SDXL, the toy networks), or
