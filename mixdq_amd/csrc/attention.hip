@@ -24,8 +24,6 @@
 // Softmax in FP32 with base-2 exponentials (v_exp_f32), P rounded to FP16 for the second MFMA, row
 // sums accumulated in FP32 from that rounded P (a third MFMA with a ones operand); O staged through LDS and stored as whole 128-B rows.
 #include "common.h"
-#include <cstdlib>
-#include <type_traits>
 #include "attn_core.h"
 
 namespace mixdq {
@@ -712,10 +710,15 @@ int launch_attn_short(AttnParams& p, int batch, bool quant, bool a4, hipStream_t
   const int grid = p.qblocks * p.heads * batch;
   p.attn_blocks = grid;
   const int smem = 2 * kStageBytes;                  // two K | V tiles; the output staging overlays them
-  if (causal) hipLaunchKernelGGL((attn_short_kernel<false, false, true>), dim3(grid), dim3(256), smem, stream, p);
-  else if (quant && a4) hipLaunchKernelGGL((attn_short_kernel<true, true>), dim3(grid), dim3(256), smem, stream, p);
-  else if (quant) hipLaunchKernelGGL((attn_short_kernel<true>), dim3(grid), dim3(256), smem, stream, p);
-  else hipLaunchKernelGGL((attn_short_kernel<false>), dim3(grid), dim3(256), smem, stream, p);
+  with_bool(causal, [&](auto c) {
+    with_bool(quant && !causal, [&](auto q) {          // (the causal form writes FP16: the entry point refuses the rest)
+      with_bool(quant && !causal && a4, [&](auto a) {
+        constexpr bool C = decltype(c)::value, Q = decltype(q)::value, A4 = decltype(a)::value;
+        if constexpr ((Q || !A4) && !(C && Q))
+          hipLaunchKernelGGL((attn_short_kernel<Q, A4, C>), dim3(grid), dim3(256), smem, stream, p);
+      });
+    });
+  });
   return launch_status();
 }
 
@@ -734,12 +737,15 @@ int launch_attn(AttnParams& p, int batch, bool quant, bool a4, hipStream_t strea
   const int smem = attn_smem_bytes(WAVES, STAGES);
   const dim3 g(grid), b(WAVES * 64);
   const bool ragged = (p.tkv & (kKeys - 1)) != 0;   // whole key tiles: no masking code at all
-#define MIXDQ_ATTN_LAUNCH(Q, R, A4) \
-  hipLaunchKernelGGL((attn_fwd_kernel<WAVES, STAGES, Q, R, A4>), g, b, smem, stream, p)
-  if (quant && a4) { if (ragged) MIXDQ_ATTN_LAUNCH(true, true, true); else MIXDQ_ATTN_LAUNCH(true, false, true); }
-  else if (quant)  { if (ragged) MIXDQ_ATTN_LAUNCH(true, true, false); else MIXDQ_ATTN_LAUNCH(true, false, false); }
-  else             { if (ragged) MIXDQ_ATTN_LAUNCH(false, true, false); else MIXDQ_ATTN_LAUNCH(false, false, false); }
-#undef MIXDQ_ATTN_LAUNCH
+  with_bool(quant, [&](auto q) {
+    with_bool(ragged, [&](auto r) {
+      with_bool(quant && a4, [&](auto a) {
+        constexpr bool Q = decltype(q)::value, R = decltype(r)::value, A4 = decltype(a)::value;
+        if constexpr (Q || !A4)                          // A4 is a form of the output quantizer
+          hipLaunchKernelGGL((attn_fwd_kernel<WAVES, STAGES, Q, R, A4>), g, b, smem, stream, p);
+      });
+    });
+  });
   return launch_status();
 }
 
@@ -1164,19 +1170,18 @@ int launch_attn_hd(AttnParams& p, int batch, bool quant, bool a4, hipStream_t st
   p.attn_blocks = p.qblocks * p.heads * batch;
   p.pf_blocks = 0; p.n_pf = 0;                       // no payload workgroups at these widths
   constexpr int smem = AttnHd<D>::smem(WAVES);
-  static bool seen[3][64] = {};
-#define MIXDQ_ATTN_HD_LAUNCH(Q, A, S)                                                                          \
-  do {                                                                                                         \
-    if (smem > 65536)                                                                                          \
-      if (const int st = lds_opt_in(reinterpret_cast<const void*>(&attn_hd_kernel<D, WAVES, Q, A>), smem,     \
-                                    seen[S])) return st;                                                       \
-    hipLaunchKernelGGL((attn_hd_kernel<D, WAVES, Q, A>), dim3(p.attn_blocks), dim3(WAVES * 64), smem, stream, p); \
-  } while (0)
-  if (quant && a4) MIXDQ_ATTN_HD_LAUNCH(true, true, 2);
-  else if (quant) MIXDQ_ATTN_HD_LAUNCH(true, false, 1);
-  else MIXDQ_ATTN_HD_LAUNCH(false, false, 0);
-#undef MIXDQ_ATTN_HD_LAUNCH
-  return launch_status();
+  int status = MIXDQ_OK;
+  with_bool(quant, [&](auto q) {
+    with_bool(quant && a4, [&](auto a) {
+      constexpr bool Q = decltype(q)::value, A4 = decltype(a)::value;
+      if constexpr (Q || !A4) {
+        if constexpr (smem > 65536) status = lds_opt_in<&attn_hd_kernel<D, WAVES, Q, A4>>(smem);
+        if (status != MIXDQ_OK) return;
+        hipLaunchKernelGGL((attn_hd_kernel<D, WAVES, Q, A4>), dim3(p.attn_blocks), dim3(WAVES * 64), smem, stream, p);
+      }
+    });
+  });
+  return status != MIXDQ_OK ? status : launch_status();
 }
 
 template <int D>
@@ -1186,19 +1191,19 @@ int launch_attn_hd_short(AttnParams& p, int batch, bool quant, bool a4, hipStrea
   p.attn_blocks = p.qblocks * p.heads * batch;
   p.pf_blocks = 0; p.n_pf = 0;
   const int smem = AttnHd<D>::smem_short((p.tkv + kKeys - 1) / kKeys);   // one stage per 64 keys: 1 or 2
-  static bool seen[3][64] = {};
-#define MIXDQ_ATTN_HD_LAUNCH(Q, A, S)                                                                          \
-  do {                                                                                                         \
-    if (AttnHd<D>::smem_short(2) > 65536)                                                                      \
-      if (const int st = lds_opt_in(reinterpret_cast<const void*>(&attn_hd_short_kernel<D, Q, A>),            \
-                                    AttnHd<D>::smem_short(2), seen[S])) return st;                             \
-    hipLaunchKernelGGL((attn_hd_short_kernel<D, Q, A>), dim3(p.attn_blocks), dim3(256), smem, stream, p);      \
-  } while (0)
-  if (quant && a4) MIXDQ_ATTN_HD_LAUNCH(true, true, 2);
-  else if (quant) MIXDQ_ATTN_HD_LAUNCH(true, false, 1);
-  else MIXDQ_ATTN_HD_LAUNCH(false, false, 0);
-#undef MIXDQ_ATTN_HD_LAUNCH
-  return launch_status();
+  int status = MIXDQ_OK;
+  with_bool(quant, [&](auto q) {
+    with_bool(quant && a4, [&](auto a) {
+      constexpr bool Q = decltype(q)::value, A4 = decltype(a)::value;
+      if constexpr (Q || !A4) {
+        if constexpr (AttnHd<D>::smem_short(2) > 65536)   // (opted in for two stages, whatever this launch stages)
+          status = lds_opt_in<&attn_hd_short_kernel<D, Q, A4>>(AttnHd<D>::smem_short(2));
+        if (status != MIXDQ_OK) return;
+        hipLaunchKernelGGL((attn_hd_short_kernel<D, Q, A4>), dim3(p.attn_blocks), dim3(256), smem, stream, p);
+      }
+    });
+  });
+  return status != MIXDQ_OK ? status : launch_status();
 }
 
 template <int D>
@@ -1432,8 +1437,7 @@ int launch_attn_512(AttnParams& p, int batch, hipStream_t stream) {
   if ((long)p.qblocks * p.heads * batch > 0x7fffffffl) return MIXDQ_ERR_INVALID_ARG;
   p.attn_blocks = p.qblocks * p.heads * batch;
   p.pf_blocks = 0; p.n_pf = 0;                       // no payload workgroups at this width
-  static bool seen[64] = {};
-  if (const int st = lds_opt_in(reinterpret_cast<const void*>(&attn_512_kernel), Attn512::SMEM, seen)) return st;
+  if (const int st = lds_opt_in<&attn_512_kernel>(Attn512::SMEM)) return st;
   hipLaunchKernelGGL(attn_512_kernel, dim3(p.attn_blocks), dim3(256), Attn512::SMEM, stream, p);
   return launch_status();
 }
@@ -1494,7 +1498,7 @@ static int attention_f16_impl(const void* q, const void* k, const void* v, void*
   p.s_inv = out_scale_inv; p.zp = out_zero_point;
   p.unfused = (flags & MIXDQ_FLAG_UNFUSED) ? 1 : 0;
   p.attn_blocks = 0; p.pf_blocks = 0; p.n_pf = 0; p.pf_nt = 0; p.pf_delay = 0;
-  static const int xcd_on = [] { const char* e = getenv("MIXDQ_ATTN_XCD"); return !(e && e[0] == '0'); }();   // A/B runs
+  static const int xcd_on = env_flag("MIXDQ_ATTN_XCD", true);   // A/B runs
   p.xcd_map = xcd_on;
   for (int i = 0; i < 16; ++i) { p.pf_ptr[i] = nullptr; p.pf_bytes[i] = 0; }
   for (int i = 0; i < (hd || w512 ? 0 : n_pf); ++i) {     // (no payload at the other widths: ignored)
@@ -1508,9 +1512,9 @@ static int attention_f16_impl(const void* q, const void* k, const void* v, void*
     p.pf_bytes[p.n_pf++] = pf_bytes[i] - cut;
   }
   if (p.n_pf) {   // one payload workgroup per CU by default (MIXDQ_PREFETCH_BLOCKS / MIXDQ_PREFETCH_NT: A/B runs)
-    static const int blocks = [] { const char* e = getenv("MIXDQ_PREFETCH_BLOCKS"); return e ? atoi(e) : kNumCU; }();
-    static const int nt = [] { const char* e = getenv("MIXDQ_PREFETCH_NT"); return e ? atoi(e) : 0; }();
-    static const int delay = [] { const char* e = getenv("MIXDQ_PREFETCH_DELAY"); return e ? atoi(e) : 0; }();
+    static const int blocks = env_int("MIXDQ_PREFETCH_BLOCKS", kNumCU);
+    static const int nt = env_int("MIXDQ_PREFETCH_NT", 0);
+    static const int delay = env_int("MIXDQ_PREFETCH_DELAY", 0);
     p.pf_blocks = blocks > 0 ? blocks : 0;
     p.pf_nt = nt;
     p.pf_delay = delay >= 0 && delay <= 16 ? delay : 0;
@@ -1532,14 +1536,16 @@ static int attention_f16_impl(const void* q, const void* k, const void* v, void*
     // attn_hd_kernel in 2- or 4-wave workgroups.  All three give the same bits.
     if (force != 0 && force != 1 && force != 2 && force != 4) return MIXDQ_ERR_SHAPE;
     if (force == 1 && tkv > 2 * kKeys) return MIXDQ_ERR_SHAPE;
-    static const bool hd_short_on = [] { const char* e = getenv("MIXDQ_ATTN_HD_SHORT"); return !(e && e[0] == '0'); }();
+    static const bool hd_short_on = env_flag("MIXDQ_ATTN_HD_SHORT", true);
     if (force == 0 && hd_short_on && tkv <= 2 * kKeys) force = 1;
-    if (head_dim == 40) return launch_attn_hd_form<40>(p, batch, heads, tq, force, quant, a4, stream);
-    if (head_dim == 80) return launch_attn_hd_form<80>(p, batch, heads, tq, force, quant, a4, stream);
-    return launch_attn_hd_form<160>(p, batch, heads, tq, force, quant, a4, stream);
+    int status = MIXDQ_ERR_SHAPE;
+    with_constant<40, 80, 160>(head_dim, [&](auto d) {
+      status = launch_attn_hd_form<decltype(d)::value>(p, batch, heads, tq, force, quant, a4, stream);
+    });
+    return status;
   }
   if (force == 1 && tkv > 2 * kKeys) return MIXDQ_ERR_SHAPE;
-  static const bool short_on = [] { const char* e = getenv("MIXDQ_ATTN_SHORT"); return !(e && e[0] == '0'); }();   // A/B runs
+  static const bool short_on = env_flag("MIXDQ_ATTN_SHORT", true);   // A/B runs
   if (causal || force == 1 || (force == 0 && short_on && tkv <= 2 * kKeys)) {   // cross-attention: 77 keys; causal
     p.qblocks = (tq + 127) / 128;
     return launch_attn_short(p, batch, quant, a4, stream, causal);

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <stdint.h>
+#include <cstdlib>
+#include <type_traits>
 
 #include "../../include/mixdq_hip.h"
 
@@ -25,18 +27,108 @@ inline int launch_status() {
   return hipGetLastError() == hipSuccess ? MIXDQ_OK : MIXDQ_ERR_LAUNCH;
 }
 
-// Opt a kernel in to more than 64 KiB of dynamic LDS.  The attribute is a property of the kernel ON A
-// DEVICE: it is applied once per (instantiation, device) -- `seen` is the instantiation's own static
-// table -- so that a process that drives several devices through the C-ABI gets it on each of them.
-inline int lds_opt_in(const void* kernel, int bytes, bool (&seen)[64]) {
+// ---- launch helpers (host) --------------------------------------------------------------------
+// Every translation unit turns run-time modes into template arguments, opts kernels in to large LDS, builds device
+// tables on first use and reads tuning knobs from the environment: each of those is written here, once.
+// Rule for the dispatch code built from them: a ladder may not change the instantiation set.  Where the modes do
+// not combine freely, an `if constexpr` around the launch statement keeps exactly the combinations that exist.
+
+// f(std::integral_constant<int, V>) for the V among Vs that equals v: a runtime mode becomes a template argument.
+template <int... Vs, class F>
+inline void with_constant(int v, F&& f) {
+  ((v == Vs ? (void)f(std::integral_constant<int, Vs>{}) : (void)0), ...);
+}
+// ... and the two-way form: f(std::true_type) or f(std::false_type).
+template <class F>
+inline void with_bool(bool b, F&& f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
+}
+
+// ... and the element type an image or mask dtype code (MIXDQ_IMAGE_*) names: f(uint8_t{}), f(__half{}) or f(float{}).
+// The caller has validated the code: image_elem_size() is 0 for anything else.
+inline int image_elem_size(int dtype) {
+  return dtype == MIXDQ_IMAGE_U8 ? 1 : dtype == MIXDQ_IMAGE_F16 ? 2 : dtype == MIXDQ_IMAGE_F32 ? 4 : 0;
+}
+template <class F>
+inline void with_image_type(int dtype, F&& f) {
+  if (dtype == MIXDQ_IMAGE_U8) f(uint8_t{});
+  else if (dtype == MIXDQ_IMAGE_F16) f(__half{});
+  else f(float{});
+}
+
+// Opt Kernel in to `bytes` (more than 64 KiB) of dynamic LDS.  The attribute is a property of the kernel ON A
+// DEVICE: it is applied once per (instantiation, device) -- `seen` belongs to this function's instantiation, that
+// is, to the kernel -- so that a process that drives several devices through the C-ABI gets it on each of them.
+template <auto Kernel>
+inline int lds_opt_in(int bytes) {
+  static bool seen[64] = {};
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return MIXDQ_ERR_LAUNCH;
   if (!seen[dev]) {
-    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess)
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            bytes) != hipSuccess)
       return MIXDQ_ERR_LAUNCH;
     seen[dev] = true;
   }
   return MIXDQ_OK;
+}
+
+// A table in device memory that is built once per device by the first launch that needs it; `launch_init` launches
+// the (idempotent) kernel that writes it on `stream`.  Each table has a state of its own.
+// `done[dev]` is only set once the table IS in memory for every stream: outside a capture the init kernel runs on the
+// caller's stream and is waited for (one host synchronisation per device and process, at first use).  Inside a
+// stream capture nothing may synchronise and the kernel is only RECORDED: the init is recorded in front of the FIRST
+// consumer of that capture (idempotent: every replay rewrites the same bits; later consumers of the same capture are
+// ordered behind it by the stream -- `in_capture[dev]` remembers the capture's id, so a UNet graph captured cold
+// carries one init kernel, not seventy that rewrite the table under each other's readers) and `done` stays false --
+// an eager launch or another capture before the first replay builds the table itself.  mixdq_amd builds its tables
+// eagerly (mixdq_gelu_table / mixdq_silu_table from SDXLUNet.prepare_fused_), so its captures record none.
+struct DeviceTableState {
+  bool done[64];
+  unsigned long long in_capture[64];
+};
+template <class F>
+inline int ensure_device_table(DeviceTableState& s, hipStream_t stream, F&& launch_init) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return MIXDQ_ERR_LAUNCH;
+  if (s.done[dev]) return MIXDQ_OK;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  unsigned long long cap_id = 0;
+  if (hipStreamGetCaptureInfo(stream, &cap, &cap_id) != hipSuccess) return MIXDQ_ERR_LAUNCH;
+  if (cap != hipStreamCaptureStatusNone && cap_id != 0 && s.in_capture[dev] == cap_id) return MIXDQ_OK;
+  launch_init();
+  if (hipGetLastError() != hipSuccess) return MIXDQ_ERR_LAUNCH;
+  if (cap == hipStreamCaptureStatusNone) {
+    if (hipStreamSynchronize(stream) != hipSuccess) return MIXDQ_ERR_LAUNCH;
+    s.done[dev] = true;
+  } else {
+    s.in_capture[dev] = cap_id;
+  }
+  return MIXDQ_OK;
+}
+
+// Tuning knobs from the environment.  A site reads its knob once per process: `static const int x = env_int(...)`.
+// env_int: atoi of the value, `fallback` when the variable is not set.  env_flag: a switch that is on by default is
+// off only for a value that starts with '0'; one that is off by default is on only for a value that starts with '1'.
+inline long long env_int64(const char* name, long long fallback) {
+  const char* e = getenv(name);
+  return e ? atoll(e) : fallback;
+}
+inline int env_int(const char* name, int fallback) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : fallback;
+}
+inline bool env_flag(const char* name, bool on_by_default) {
+  const char* e = getenv(name);
+  return on_by_default ? !(e && e[0] == '0') : (e && e[0] == '1');
+}
+
+// Blocks of 256 lanes for `items` grid-stride items: at most `per_cu` per CU (the kernels stride beyond), at least 1.
+inline int grid_blocks(int64_t items, int per_cu = 8) {
+  int64_t blocks = (items + 255) / 256;
+  if (blocks > (int64_t)kNumCU * per_cu) blocks = (int64_t)kNumCU * per_cu;
+  return blocks < 1 ? 1 : (int)blocks;
 }
 
 // ---- arithmetic specification ------------------------------------------
@@ -191,5 +283,36 @@ __device__ __forceinline__ v2f erff2(v2f a) {
 __device__ __forceinline__ v2f geluf2(v2f x) {
   return (0.5f * x) * (1.0f + erff2(x * 0.70710678118654752440f));
 }
+
+// ---- eight FP16 / INT8 / FP32 values as one vector access ------------------------------------------
+// In an unnamed namespace, like everything a translation unit declares: kernels that take a Half8* keep the symbol
+// names they have always had.
+namespace {
+
+struct alignas(16) Half8 { uint32_t w[4]; };
+struct alignas(8) Char8 { uint32_t w[2]; };
+
+__device__ __forceinline__ float half_at(const Half8& h, int j) {
+  const uint32_t w = h.w[j >> 1];
+  __half_raw r;
+  r.x = (unsigned short)((j & 1) ? (w >> 16) : (w & 0xffffu));
+  return __half2float(__half(r));
+}
+
+__device__ __forceinline__ uint32_t half_bits(float v) {
+  return (uint32_t)__half_raw(f32_to_f16_rn(v)).x;
+}
+
+__device__ __forceinline__ void load8(const float* __restrict__ p, float v[8]) {
+  const float4 lo = *reinterpret_cast<const float4*>(p), hi = *reinterpret_cast<const float4*>(p + 4);
+  v[0] = lo.x, v[1] = lo.y, v[2] = lo.z, v[3] = lo.w, v[4] = hi.x, v[5] = hi.y, v[6] = hi.z, v[7] = hi.w;
+}
+
+__device__ __forceinline__ void store8(float* __restrict__ p, const float v[8]) {
+  *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+  *reinterpret_cast<float4*>(p + 4) = make_float4(v[4], v[5], v[6], v[7]);
+}
+
+}  // namespace
 
 }  // namespace mixdq

@@ -12,22 +12,11 @@
 // FP16, then the a1 quantizer on that FP16 value.  All reductions have a FIXED order, and the
 // transcendental steps are the shared specification include/mixdq_math.h, so the CPU oracle
 // (oracle/mixdq_oracle.c) reproduces every kernel bit-for-bit.  HBM-bound.
-#include <cstdlib>
 #include "common.h"
 #include "../../include/mixdq_math.h"
 
 namespace mixdq {
 namespace {
-
-struct alignas(16) Half8 { uint32_t w[4]; };
-struct alignas(8) Char8 { uint32_t w[2]; };
-
-__device__ __forceinline__ float half_at(const Half8& h, int j) {
-  const uint32_t w = h.w[j >> 1];
-  __half_raw r;
-  r.x = (unsigned short)((j & 1) ? (w >> 16) : (w & 0xffffu));
-  return __half2float(__half(r));
-}
 
 __device__ __forceinline__ float round_f16(float v) { return __half2float(f32_to_f16_rn(v)); }
 
@@ -246,27 +235,11 @@ __global__ __launch_bounds__(256) void silu_table_init_kernel() {
   g_silu_tab[i] = __half_as_ushort(f32_to_f16_rn(mixdq_siluf(__half2float(__half(r)))));
 }
 
-// Built once per device by the first launch that needs it; inside a stream capture the (idempotent) init kernel is
-// recorded in front of the first consumer of that capture only (the logic of igemm.hip's ensure_gelu_table).
+// Built once per device by the first launch that needs it (common.h: ensure_device_table).
 inline int ensure_silu_table(hipStream_t stream) {
-  static bool done[64] = {};
-  static unsigned long long in_capture[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return MIXDQ_ERR_LAUNCH;
-  if (done[dev]) return MIXDQ_OK;
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  unsigned long long cap_id = 0;
-  if (hipStreamGetCaptureInfo(stream, &cap, &cap_id) != hipSuccess) return MIXDQ_ERR_LAUNCH;
-  if (cap != hipStreamCaptureStatusNone && cap_id != 0 && in_capture[dev] == cap_id) return MIXDQ_OK;
-  silu_table_init_kernel<<<(kSiluTabBytes / 2 + 255) / 256, 256, 0, stream>>>();
-  if (hipGetLastError() != hipSuccess) return MIXDQ_ERR_LAUNCH;
-  if (cap == hipStreamCaptureStatusNone) {
-    if (hipStreamSynchronize(stream) != hipSuccess) return MIXDQ_ERR_LAUNCH;
-    done[dev] = true;
-  } else {
-    in_capture[dev] = cap_id;
-  }
-  return MIXDQ_OK;
+  static DeviceTableState state = {};
+  return ensure_device_table(state, stream,
+                             [&] { silu_table_init_kernel<<<(kSiluTabBytes / 2 + 255) / 256, 256, 0, stream>>>(); });
 }
 
 // SELF: the blocks reduce their groups' partials themselves (stats == nullptr); a template parameter because as a
@@ -669,25 +642,10 @@ __global__ __launch_bounds__(256) void gelu_table_fn_init_kernel() {
   g_gelu_tab_fn[i] = __half_as_ushort(f32_to_f16_rn(mixdq_geluf(__half2float(__half(r)))));
 }
 
-inline int ensure_gelu_table_fn(hipStream_t stream) {      // (the logic of ensure_silu_table)
-  static bool done[64] = {};
-  static unsigned long long in_capture[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return MIXDQ_ERR_LAUNCH;
-  if (done[dev]) return MIXDQ_OK;
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  unsigned long long cap_id = 0;
-  if (hipStreamGetCaptureInfo(stream, &cap, &cap_id) != hipSuccess) return MIXDQ_ERR_LAUNCH;
-  if (cap != hipStreamCaptureStatusNone && cap_id != 0 && in_capture[dev] == cap_id) return MIXDQ_OK;
-  gelu_table_fn_init_kernel<<<(2 * kGeluMagFn + 255) / 256, 256, 0, stream>>>();
-  if (hipGetLastError() != hipSuccess) return MIXDQ_ERR_LAUNCH;
-  if (cap == hipStreamCaptureStatusNone) {
-    if (hipStreamSynchronize(stream) != hipSuccess) return MIXDQ_ERR_LAUNCH;
-    done[dev] = true;
-  } else {
-    in_capture[dev] = cap_id;
-  }
-  return MIXDQ_OK;
+inline int ensure_gelu_table_fn(hipStream_t stream) {
+  static DeviceTableState state = {};
+  return ensure_device_table(state, stream,
+                             [&] { gelu_table_fn_init_kernel<<<(2 * kGeluMagFn + 255) / 256, 256, 0, stream>>>(); });
 }
 
 template <bool UNFUSED, bool A4 = false>
@@ -762,47 +720,6 @@ extern "C" size_t mixdq_groupnorm_workspace_bytes(int N, int64_t HW, int C, int 
   return ((size_t)N * g.nchunk * G + (size_t)N * G) * sizeof(float2);
 }
 
-extern "C" int mixdq_groupnorm_silu_quantize2(const void* x_nhwc, int C1, const void* x2_nhwc,
-                                              const void* gamma, const void* beta, float eps,
-                                              int apply_silu, const float* scale_inv,
-                                              const float* zero_point, int8_t* out_q_or_null,
-                                              void* out_f16_or_null, void* workspace, int N,
-                                              int64_t HW, int C, int G, int flags,
-                                              mixdq_stream_t stream_);
-extern "C" int mixdq_groupnorm_silu_quantize3(const void* x_nhwc, int C1, const void* x2_nhwc,
-                                              const void* gamma, const void* beta, float eps,
-                                              int apply_silu, const float* scale_inv,
-                                              const float* zero_point, int8_t* out_q_or_null,
-                                              void* out_f16_or_null,
-                                              const float* const* raw_scale_inv,
-                                              const float* const* raw_zero_point,
-                                              int8_t* const* raw_q, void* workspace, int N,
-                                              int64_t HW, int C, int G, int flags,
-                                              mixdq_stream_t stream_);
-
-extern "C" int mixdq_groupnorm_silu_quantize(const void* x_nhwc, const void* gamma,
-                                             const void* beta, float eps, int apply_silu,
-                                             const float* scale_inv, const float* zero_point,
-                                             int8_t* out_q_or_null, void* out_f16_or_null,
-                                             void* workspace, int N, int64_t HW, int C, int G,
-                                             int flags, mixdq_stream_t stream_) {
-  return mixdq_groupnorm_silu_quantize2(x_nhwc, C, nullptr, gamma, beta, eps, apply_silu, scale_inv,
-                                        zero_point, out_q_or_null, out_f16_or_null, workspace, N, HW,
-                                        C, G, flags, stream_);
-}
-
-extern "C" int mixdq_groupnorm_silu_quantize2(const void* x_nhwc, int C1, const void* x2_nhwc,
-                                              const void* gamma, const void* beta, float eps,
-                                              int apply_silu, const float* scale_inv,
-                                              const float* zero_point, int8_t* out_q_or_null,
-                                              void* out_f16_or_null, void* workspace, int N,
-                                              int64_t HW, int C, int G, int flags,
-                                              mixdq_stream_t stream_) {
-  return mixdq_groupnorm_silu_quantize3(x_nhwc, C1, x2_nhwc, gamma, beta, eps, apply_silu, scale_inv,
-                                        zero_point, out_q_or_null, out_f16_or_null, nullptr, nullptr,
-                                        nullptr, workspace, N, HW, C, G, flags, stream_);
-}
-
 extern "C" int mixdq_groupnorm_silu_quantize3(const void* x_nhwc, int C1, const void* x2_nhwc,
                                               const void* gamma, const void* beta, float eps,
                                               int apply_silu, const float* scale_inv,
@@ -840,18 +757,19 @@ extern "C" int mixdq_groupnorm_silu_quantize3(const void* x_nhwc, int C1, const 
   hipStream_t stream = (hipStream_t)stream_;
   float2* partial = (float2*)workspace;
   const int threads = g.OC * g.PP;
-  static const int stats_unroll = [] { const char* e = getenv("MIXDQ_GN_STATS_UNROLL"); return e ? atoi(e) : 0; }();
+  static const int stats_unroll = env_int("MIXDQ_GN_STATS_UNROLL", 0);
   const int su = stats_unroll == 1 || stats_unroll == 2 || stats_unroll == 4 ? stats_unroll : (g.ppb / g.PP <= 2 ? 2 : 4);
-  (su == 1 ? gn_stats_kernel<1> : su == 2 ? gn_stats_kernel<2> : gn_stats_kernel<4>)
-      <<<dim3(g.nchunk, N), threads, threads * 4 * sizeof(float), stream>>>(
-          (const __half*)x_nhwc, (const __half*)x2_nhwc, partial, g);
+  with_constant<1, 2, 4>(su, [&](auto unroll) {
+    gn_stats_kernel<decltype(unroll)::value><<<dim3(g.nchunk, N), threads, threads * 4 * sizeof(float), stream>>>(
+        (const __half*)x_nhwc, (const __half*)x2_nhwc, partial, g);
+  });
   // MIXDQ_GN_SLICED=1 (measured, off): with more than 64 partials per group the apply pass is cut into channel
   // slices (blockIdx.z) of whole groups, at most 8 groups each, so that a block needs -- and reduces in its
   // prologue -- only its slice's statistics (4 x 342 x 8 B at C = 640) and the finalize launch disappears (46 per
   // batch-1 step).  Bit-exact, and slower: slices are 160-320 contiguous bytes per pixel (80-byte INT8 rows), the
   // prologue's strided partial reads are one cache line per lane: batch 1 11.08 -> 11.24 ms, batch 8 47.5 -> 48.9
   // (profiles/r05_gn_finalize_ab.txt).
-  static const bool sliced_on = [] { const char* e = getenv("MIXDQ_GN_SLICED"); return e && e[0] == '1'; }();
+  static const bool sliced_on = env_flag("MIXDQ_GN_SLICED", false);
   int nslice = 1;
   if (g.nchunk > 64 && sliced_on)
     for (int s = 8; s >= 2 && nslice == 1; s >>= 1)
@@ -889,10 +807,12 @@ extern "C" int mixdq_groupnorm_silu_quantize3(const void* x_nhwc, int C1, const 
   // (1, 128 x 128, 960) 40.0 -> 30.4, (1, 64 x 64, 1920) 26.2 -> 20.2, (1, 128 x 128, 320) 21.6 -> 18.3, (1, 64 x 64, 640)
   // 15.9 -> 14.9 -- and (1, 32 x 32, 1280), 1.3 Mi elements, 12.8 -> 13.3: the threshold.
   // MIXDQ_GN_SILU_TAB=0 never / 1 wherever possible (tests).
-  static const int tab_mode = [] { const char* e = getenv("MIXDQ_GN_SILU_TAB"); return e ? atoi(e) : -1; }();
-  static const int64_t tab_min = [] { const char* e = getenv("MIXDQ_GN_SILU_TAB_MIN"); return e ? atoll(e) : (int64_t)2 << 20; }();
+  static const int tab_mode = env_int("MIXDQ_GN_SILU_TAB", -1);
+  static const int64_t tab_min = env_int64("MIXDQ_GN_SILU_TAB_MIN", (int64_t)2 << 20);
   const bool use_tab = apply_silu && stats != nullptr && nslice == 1 && tab_mode != 0 &&
                        (tab_mode == 1 || (int64_t)N * HW * C >= tab_min);
+  dim3 grid(g.nchunk_apply, N, nslice);
+  int lds = 0;
   if (use_tab) {
     if (const int st = ensure_silu_table(stream)) return st;
     // ~512 threads per block, two blocks per CU (75 KB of LDS each), every block walking several chunks of its image;
@@ -902,33 +822,55 @@ extern "C" int mixdq_groupnorm_silu_quantize3(const void* x_nhwc, int C1, const 
     g.PPa = g.OC >= 512 ? 1 : 512 / g.OC;
     g.ppb_apply = iters * g.PPa;
     g.nchunk_apply = (int)((HW + g.ppb_apply - 1) / g.ppb_apply);
-    const int threads_tab = g.OC * g.PPa;
+    threads_apply = g.OC * g.PPa;
     int gx = (2 * kNumCU + N - 1) / N;
     if (gx > g.nchunk_apply) gx = g.nchunk_apply;
     if (gx < 1) gx = 1;
-    static bool seen_t[2][64] = {};
-#define GN_APPLY_TAB(U)                                                                                         \
-    do {                                                                                                        \
-      if (const int st = lds_opt_in(reinterpret_cast<const void*>(&gn_apply_kernel<true, U, false, true>),       \
-                                    kSiluTabBytes, seen_t[U ? 1 : 0])) return st;                                \
-      gn_apply_kernel<true, U, false, true><<<dim3(gx, N, 1), threads_tab, kSiluTabBytes, stream>>>(            \
-          (const __half*)x_nhwc, (const __half*)x2_nhwc, partial, stats, eps, (const __half*)gamma,             \
-          (const __half*)beta, scale_inv, zero_point, out_q_or_null, (__half*)out_f16_or_null, g, raw);         \
-    } while (0)
-    if (unfused) GN_APPLY_TAB(true); else GN_APPLY_TAB(false);
-#undef GN_APPLY_TAB
-    return launch_status();
+    grid = dim3(gx, N, 1);
+    lds = kSiluTabBytes;
   }
-  const dim3 grid(g.nchunk_apply, N, nslice);
-#define GN_APPLY(S, U)                                                                          \
-  (stats ? gn_apply_kernel<S, U, false> : gn_apply_kernel<S, U, true>)<<<grid, threads_apply, 0, stream>>>( \
-      (const __half*)x_nhwc, (const __half*)x2_nhwc, partial, stats, eps, (const __half*)gamma, \
-      (const __half*)beta,                                                                      \
-      scale_inv, zero_point, out_q_or_null, (__half*)out_f16_or_null, g, raw)
-  if (apply_silu) { if (unfused) GN_APPLY(true, true); else GN_APPLY(true, false); }
-  else            { if (unfused) GN_APPLY(false, true); else GN_APPLY(false, false); }
-#undef GN_APPLY
-  return launch_status();
+  int status = MIXDQ_OK;
+  with_bool(apply_silu != 0, [&](auto silu) {
+    with_bool(unfused, [&](auto unf) {
+      with_bool(stats == nullptr, [&](auto self) {
+        with_bool(use_tab, [&](auto tab) {
+          constexpr bool S = decltype(silu)::value, U = decltype(unf)::value, SELF = decltype(self)::value;
+          constexpr bool TAB = decltype(tab)::value;
+          if constexpr (!TAB || (S && !SELF)) {   // the table is SiLU's, read behind the finalize launch
+            if constexpr (TAB) status = lds_opt_in<&gn_apply_kernel<S, U, SELF, TAB>>(lds);
+            if (status != MIXDQ_OK) return;
+            gn_apply_kernel<S, U, SELF, TAB><<<grid, threads_apply, lds, stream>>>(
+                (const __half*)x_nhwc, (const __half*)x2_nhwc, partial, stats, eps, (const __half*)gamma,
+                (const __half*)beta, scale_inv, zero_point, out_q_or_null, (__half*)out_f16_or_null, g, raw);
+          }
+        });
+      });
+    });
+  });
+  return status != MIXDQ_OK ? status : launch_status();
+}
+
+extern "C" int mixdq_groupnorm_silu_quantize2(const void* x_nhwc, int C1, const void* x2_nhwc,
+                                              const void* gamma, const void* beta, float eps,
+                                              int apply_silu, const float* scale_inv,
+                                              const float* zero_point, int8_t* out_q_or_null,
+                                              void* out_f16_or_null, void* workspace, int N,
+                                              int64_t HW, int C, int G, int flags,
+                                              mixdq_stream_t stream_) {
+  return mixdq_groupnorm_silu_quantize3(x_nhwc, C1, x2_nhwc, gamma, beta, eps, apply_silu, scale_inv,
+                                        zero_point, out_q_or_null, out_f16_or_null, nullptr, nullptr,
+                                        nullptr, workspace, N, HW, C, G, flags, stream_);
+}
+
+extern "C" int mixdq_groupnorm_silu_quantize(const void* x_nhwc, const void* gamma,
+                                             const void* beta, float eps, int apply_silu,
+                                             const float* scale_inv, const float* zero_point,
+                                             int8_t* out_q_or_null, void* out_f16_or_null,
+                                             void* workspace, int N, int64_t HW, int C, int G,
+                                             int flags, mixdq_stream_t stream_) {
+  return mixdq_groupnorm_silu_quantize2(x_nhwc, C, nullptr, gamma, beta, eps, apply_silu, scale_inv,
+                                        zero_point, out_q_or_null, out_f16_or_null, workspace, N, HW,
+                                        C, G, flags, stream_);
 }
 
 // The FP16 -> FP16 SiLU table of the apply pass's TAB variant (built on first use; this call builds it eagerly --
@@ -967,49 +909,29 @@ extern "C" int mixdq_layernorm_quantize(const void* x, const void* gamma, const 
     return MIXDQ_ERR_ALIGNMENT;
   hipStream_t stream = (hipStream_t)stream_;
   const bool unfused = flags & MIXDQ_FLAG_UNFUSED, want_h = out_f16_or_null != nullptr;
-  static const int rows_forced = [] { const char* e = getenv("MIXDQ_LN_ROWS"); return e ? atoi(e) : 0; }();
+  static const int rows_forced = env_int("MIXDQ_LN_ROWS", 0);
   const int rows = rows_forced == 1 || rows_forced == 2 ? rows_forced   // (tuning runs)
                                                         : (M >= 8192 ? 2 : 1);   // rows per wave (see the kernel)
   const int grid = (int)((M + 4 * rows - 1) / (4 * rows));
   const int a4m = (flags >> 16) & 7;
   if (a4m >> n_out) return MIXDQ_ERR_UNSUPPORTED;                  // an A4 bit for a slot the launch does not have
-#define LN_ARGS                                                                                      \
-  (const __half*)x, (const __half*)gamma, (const __half*)beta, eps, M, C, si[0], zp[0], q[0], si[1], \
-      zp[1], q[1], si[2], zp[2], q[2], (__half*)out_f16_or_null
-#define LN_LAUNCH(U, NQ, H, A)                                                                      \
-  do {                                                                                              \
-    if (rows == 2) ln_quant_kernel<U, NQ, H, 2, A><<<grid, 256, 0, stream>>>(LN_ARGS);              \
-    else ln_quant_kernel<U, NQ, H, 1, A><<<grid, 256, 0, stream>>>(LN_ARGS);                        \
-  } while (0)
-#define LN_BY_A(U, NQ, H)                                                                           \
-  do {                                                                                              \
-    switch (a4m) {                                                                                  \
-      case 0: LN_LAUNCH(U, NQ, H, 0); break;                                                        \
-      case 1: LN_LAUNCH(U, NQ, H, (NQ > 0 ? 1 : 0)); break;                                         \
-      case 2: LN_LAUNCH(U, NQ, H, (NQ > 1 ? 2 : 0)); break;                                         \
-      case 3: LN_LAUNCH(U, NQ, H, (NQ > 1 ? 3 : 0)); break;                                         \
-      case 4: LN_LAUNCH(U, NQ, H, (NQ > 2 ? 4 : 0)); break;                                         \
-      case 5: LN_LAUNCH(U, NQ, H, (NQ > 2 ? 5 : 0)); break;                                         \
-      case 6: LN_LAUNCH(U, NQ, H, (NQ > 2 ? 6 : 0)); break;                                         \
-      default: LN_LAUNCH(U, NQ, H, (NQ > 2 ? 7 : 0)); break;                                        \
-    }                                                                                               \
-  } while (0)
-#define LN_BY_H(U, NQ) do { if (want_h) LN_BY_A(U, NQ, true); else LN_BY_A(U, NQ, false); } while (0)
-#define LN_BY_NQ(U)                                                                \
-  do {                                                                             \
-    switch (n_out) {                                                               \
-      case 0: LN_LAUNCH(U, 0, true, 0); break;   /* n_out == 0 implies the FP16 copy */ \
-      case 1: LN_BY_H(U, 1); break;                                                \
-      case 2: LN_BY_H(U, 2); break;                                                \
-      default: LN_BY_H(U, 3); break;                                               \
-    }                                                                              \
-  } while (0)
-  if (unfused) LN_BY_NQ(true); else LN_BY_NQ(false);
-#undef LN_BY_NQ
-#undef LN_BY_H
-#undef LN_BY_A
-#undef LN_LAUNCH
-#undef LN_ARGS
+  with_bool(unfused, [&](auto unf) {
+    with_constant<0, 1, 2, 3>(n_out, [&](auto nq) {
+      with_bool(want_h, [&](auto wh) {
+        with_constant<0, 1, 2, 3, 4, 5, 6, 7>(a4m, [&](auto am) {
+          with_constant<1, 2>(rows, [&](auto r) {
+            constexpr bool U = decltype(unf)::value, H = decltype(wh)::value;
+            constexpr int NQ = decltype(nq)::value, A = decltype(am)::value, R = decltype(r)::value;
+            // n_out == 0 implies the FP16 copy, and an A4 bit needs its slot
+            if constexpr ((NQ > 0 || H) && A < (1 << NQ))
+              ln_quant_kernel<U, NQ, H, R, A><<<grid, 256, 0, stream>>>(
+                  (const __half*)x, (const __half*)gamma, (const __half*)beta, eps, M, C, si[0], zp[0], q[0], si[1],
+                  zp[1], q[1], si[2], zp[2], q[2], (__half*)out_f16_or_null);
+          });
+        });
+      });
+    });
+  });
   return launch_status();
 }
 
@@ -1026,38 +948,31 @@ extern "C" int mixdq_geglu_quantize(const void* h, int64_t M, int D, const float
     return MIXDQ_ERR_ALIGNMENT;
   if (flags & (MIXDQ_FLAG_A4_1 | MIXDQ_FLAG_A4_2)) return MIXDQ_ERR_UNSUPPORTED;   // one quantizer: slot 0
   const bool a4 = out_q_or_null && (flags & MIXDQ_FLAG_A4_0);
-  int64_t blocks = (M * (D / 8) + 255) / 256;
-  if (blocks > kNumCU * 8) blocks = kNumCU * 8;
   hipStream_t stream = (hipStream_t)stream_;
+  const bool unfused = flags & MIXDQ_FLAG_UNFUSED;
   // GELU by table from 2 Mi outputs on (MIXDQ_GEGLU_TAB=0 never / 1 always: tests and A/B runs): (1024, 5120), the
   // batch-1 ff layer of the module-swap path, is 5 Mi
-  static const int tab_mode = [] { const char* e = getenv("MIXDQ_GEGLU_TAB"); return e ? atoi(e) : -1; }();
-  if (tab_mode != 0 && (tab_mode == 1 || M * (int64_t)D >= ((int64_t)2 << 20))) {
+  static const int tab_mode = env_int("MIXDQ_GEGLU_TAB", -1);
+  const bool use_tab = tab_mode != 0 && (tab_mode == 1 || M * (int64_t)D >= ((int64_t)2 << 20));
+  if (use_tab)
     if (const int st = ensure_gelu_table_fn(stream)) return st;
-    static bool seen_g[4][64] = {};
-    const bool unf = flags & MIXDQ_FLAG_UNFUSED;
-    const void* kern = a4 ? (unf ? reinterpret_cast<const void*>(&geglu_quant_tab_kernel<true, true>)
-                                 : reinterpret_cast<const void*>(&geglu_quant_tab_kernel<false, true>))
-                          : (unf ? reinterpret_cast<const void*>(&geglu_quant_tab_kernel<true>)
-                                 : reinterpret_cast<const void*>(&geglu_quant_tab_kernel<false>));
-    if (const int st = lds_opt_in(kern, kGeluTabBytesFn, seen_g[(unf ? 1 : 0) + (a4 ? 2 : 0)])) return st;
-    int64_t tb = (M * (D / 8) + 1023) / 1024;
-    if (tb > 2 * kNumCU) tb = 2 * kNumCU;
-#define GEGLU_TAB(U, A)                                                                                    \
-    geglu_quant_tab_kernel<U, A><<<(int)tb, 1024, kGeluTabBytesFn, stream>>>(                               \
-        (const __half*)h, M, D, scale_inv, zero_point, out_q_or_null, (__half*)out_f16_or_null)
-    if (a4) { if (unf) GEGLU_TAB(true, true); else GEGLU_TAB(false, true); }
-    else if (unf) GEGLU_TAB(true, false);
-    else GEGLU_TAB(false, false);
-#undef GEGLU_TAB
-    return launch_status();
-  }
-#define GEGLU(U, A)                                                                                        \
-  geglu_quant_kernel<U, A><<<(int)blocks, 256, 0, stream>>>(                                                \
-      (const __half*)h, M, D, scale_inv, zero_point, out_q_or_null, (__half*)out_f16_or_null)
-  if (a4) { if (flags & MIXDQ_FLAG_UNFUSED) GEGLU(true, true); else GEGLU(false, true); }
-  else if (flags & MIXDQ_FLAG_UNFUSED) GEGLU(true, false);
-  else GEGLU(false, false);
-#undef GEGLU
-  return launch_status();
+  int64_t tb = (M * (D / 8) + 1023) / 1024;
+  if (tb > 2 * kNumCU) tb = 2 * kNumCU;
+  int status = MIXDQ_OK;
+  with_bool(unfused, [&](auto unf) {
+    with_bool(a4, [&](auto a) {
+      constexpr bool U = decltype(unf)::value, A4 = decltype(a)::value;
+      const auto launch = [&](auto kernel, int blocks, int threads, int lds) {
+        kernel<<<blocks, threads, lds, stream>>>((const __half*)h, M, D, scale_inv, zero_point, out_q_or_null,
+                                                 (__half*)out_f16_or_null);
+      };
+      if (use_tab) {
+        status = lds_opt_in<&geglu_quant_tab_kernel<U, A4>>(kGeluTabBytesFn);
+        if (status == MIXDQ_OK) launch(&geglu_quant_tab_kernel<U, A4>, (int)tb, 1024, kGeluTabBytesFn);
+      } else {
+        launch(&geglu_quant_kernel<U, A4>, grid_blocks(M * (D / 8)), 256, 0);
+      }
+    });
+  });
+  return status != MIXDQ_OK ? status : launch_status();
 }

@@ -477,10 +477,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo_kernel(const HaloConvArgs
 template <int TH, int TW, int BN, int CK, int WNG = 1, bool W4 = false>
 int launch_halo(const HaloConvArgs& a, hipStream_t stream) {
   using G = HaloGeom<TH, TW, BN, CK, WNG, W4>;
-  static bool seen[64] = {};
-  if (const int st = lds_opt_in(reinterpret_cast<const void*>(&conv3x3_halo_kernel<TH, TW, BN, CK, WNG, W4>),
-                                G::SMEM, seen))
-    return st;
+  if (const int st = lds_opt_in<&conv3x3_halo_kernel<TH, TW, BN, CK, WNG, W4>>(G::SMEM)) return st;
   const int64_t grid = (int64_t)a.NI * (a.H / TH) * (a.W / TW) * ((a.K + BN - 1) / BN);
   if (grid <= 0 || grid > 0x7fffffff) return MIXDQ_ERR_INVALID_ARG;
   conv3x3_halo_kernel<TH, TW, BN, CK, WNG, W4><<<dim3((unsigned)grid), 512, G::SMEM, stream>>>(a);

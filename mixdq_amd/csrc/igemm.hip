@@ -392,9 +392,7 @@ int dispatch(IgemmParams& p, hipStream_t stream, int forced_cfg) {
     if (align_k % 32 != 0 || !ptr_ok) return MIXDQ_ERR_W4_SHAPE;   // packed pieces span 32 k
   } else {
     if (align_k % 16 != 0 || !ptr_ok) {
-      int64_t blocks = (p.M * p.N + 255) / 256;
-      if (blocks > kNumCU * 16) blocks = kNumCU * 16;
-      igemm_generic_kernel<CONV><<<(int)blocks, 256, 0, stream>>>(p);
+      igemm_generic_kernel<CONV><<<grid_blocks(p.M * p.N, 16), 256, 0, stream>>>(p);
       return launch_status();
     }
   }
@@ -427,19 +425,15 @@ int launch_att(IgemmParams& p, hipStream_t stream) {
   constexpr int BM = 64, BN = 128, BK = 128, ST = 3;
   constexpr int SMEM = ((igemm_smem_bytes<BM, BN, BK, ST>() + 1023) / 1024) * 1024 + 4 * kStageBytes;
   static_assert(SMEM <= 160 * 1024, "LDS is 160 KiB per CU");
-  static bool seen[64] = {};
-  if (const int st = lds_opt_in(
-          reinterpret_cast<const void*>(
-              &igemm_kernel<BM, BN, BK, ST, 2, 4, false, true, WBITS, 1, 32, false, true, false, false, false, false, A4>),
-          SMEM, seen))
-    return st;
+  constexpr auto kernel =
+      &igemm_kernel<BM, BN, BK, ST, 2, 4, false, true, WBITS, 1, 32, false, true, false, false, false, false, A4>;
+  if (const int st = lds_opt_in<kernel>(SMEM)) return st;
   p.tiles_m = (int)((p.M + BM - 1) / BM);
   p.tiles_n = (p.N + BN - 1) / BN;
   p.gm = tile_map_gm();
   const int64_t grid = (int64_t)p.tiles_m * p.tiles_n;
   if (grid <= 0 || grid > 0x7fffffff || p.tiles_m >= (1 << 24)) return MIXDQ_ERR_INVALID_ARG;
-  igemm_kernel<BM, BN, BK, ST, 2, 4, false, true, WBITS, 1, 32, false, true, false, false, false, false, A4>
-      <<<dim3((unsigned)grid), 512, SMEM, stream>>>(MIXDQ_IGEMM_HEAD_ARGS(p) p);
+  kernel<<<dim3((unsigned)grid), 512, SMEM, stream>>>(MIXDQ_IGEMM_HEAD_ARGS(p) p);
   return launch_status();
 }
 
@@ -566,15 +560,11 @@ int dispatch_f16(IgemmParams& p, hipStream_t stream, int forced_cfg, int act = 0
                       ((uintptr_t)p.D % 16 == 0) && ((uintptr_t)p.bias % 8 == 0) &&
                       ((uintptr_t)p.res % 16 == 0);
   if (align_k % 16 != 0 || p.N % 4 != 0 || !ptr_ok) {
-    int64_t blocks = (p.M * p.N + 255) / 256;
-    if (blocks > kNumCU * 16) blocks = kNumCU * 16;
-    if constexpr (!CONV) {
-      if (act == 1) f16_generic_kernel<false, 1><<<(int)blocks, 256, 0, stream>>>(p);
-      else if (act == 2) f16_generic_kernel<false, 2><<<(int)blocks, 256, 0, stream>>>(p);
-      else f16_generic_kernel<false><<<(int)blocks, 256, 0, stream>>>(p);
-    } else {
-      f16_generic_kernel<CONV><<<(int)blocks, 256, 0, stream>>>(p);
-    }
+    with_constant<0, 1, 2>(act, [&](auto a) {
+      constexpr int ACT = decltype(a)::value;
+      if constexpr (!CONV || ACT == 0)                 // the activations are mixdq_linear_f16's
+        f16_generic_kernel<CONV, ACT><<<grid_blocks(p.M * p.N, 16), 256, 0, stream>>>(p);
+    });
     return launch_status();
   }
   const int cfg = forced_cfg > 0 ? forced_cfg : select_cfg_f16(p.M, p.N, p.Ktot);
@@ -731,11 +721,11 @@ extern "C" int mixdq_qlinear_w8a8(const int8_t* A, const int8_t* W, const float*
 // The A/B switches of the halo path, each read once per process: the launch and mixdq_conv_halo_select_flags answer
 // from the same values.
 static bool halo_conv_switch() {
-  static const bool on = [] { const char* e = getenv("MIXDQ_HALO_CONV"); return !(e && e[0] == '0'); }();
+  static const bool on = env_flag("MIXDQ_HALO_CONV", true);
   return on;
 }
 static bool halo_w4_switch() {
-  static const bool on = [] { const char* e = getenv("MIXDQ_HALO_W4"); return !(e && e[0] == '0'); }();
+  static const bool on = env_flag("MIXDQ_HALO_W4", true);
   return on;
 }
 
@@ -748,9 +738,7 @@ extern "C" int mixdq_conv_border_table(const float* wsum_krs, float* table, int 
                                        mixdq_stream_t stream) {
   if (!wsum_krs || !table || K <= 0 || R <= 0 || S <= 0) return MIXDQ_ERR_INVALID_ARG;
   const int64_t total = (int64_t)R * R * S * S * K;
-  int64_t blocks = (total + 255) / 256;
-  if (blocks > kNumCU * 8) blocks = kNumCU * 8;
-  border_table_kernel<<<(int)blocks, 256, 0, (hipStream_t)stream>>>(wsum_krs, table, K, R, S);
+  border_table_kernel<<<grid_blocks(total), 256, 0, (hipStream_t)stream>>>(wsum_krs, table, K, R, S);
   return launch_status();
 }
 
@@ -851,11 +839,8 @@ extern "C" int mixdq_conv_zero_point_propagate(const float* wsum_krs, const floa
   const int Q = (W + 2 * pad - (S - 1) - 1) / stride + 1;
   const int64_t total = (int64_t)N * P * Q * K;
   if (total <= 0) return MIXDQ_OK;
-  int64_t blocks = (total + 255) / 256;
-  if (blocks > kNumCU * 8) blocks = kNumCU * 8;
-  zp_propagate_kernel<<<(int)blocks, 256, 0, (hipStream_t)stream>>>(wsum_krs, zero_point, out, N,
-                                                                     H, W, K, R, S, P, Q, stride,
-                                                                     pad);
+  zp_propagate_kernel<<<grid_blocks(total), 256, 0, (hipStream_t)stream>>>(wsum_krs, zero_point, out, N, H, W, K, R, S,
+                                                                           P, Q, stride, pad);
   return launch_status();
 }
 
@@ -864,10 +849,8 @@ extern "C" int mixdq_gemm_f16(const void* A, const void* B, void* D, int64_t M, 
   if (M < 0 || N < 0 || K < 0) return MIXDQ_ERR_INVALID_ARG;
   if (M == 0 || N == 0) return MIXDQ_OK;
   if (!A || !B || !D) return MIXDQ_ERR_INVALID_ARG;
-  int64_t blocks = (M * N + 255) / 256;
-  if (blocks > kNumCU * 16) blocks = kNumCU * 16;
-  gemm_f16_kernel<<<(int)blocks, 256, 0, (hipStream_t)stream>>>((const __half*)A, (const __half*)B,
-                                                                (__half*)D, M, N, K);
+  gemm_f16_kernel<<<grid_blocks(M * N, 16), 256, 0, (hipStream_t)stream>>>((const __half*)A, (const __half*)B,
+                                                                           (__half*)D, M, N, K);
   return launch_status();
 }
 

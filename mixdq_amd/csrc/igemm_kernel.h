@@ -214,35 +214,11 @@ __global__ __launch_bounds__(256) void gelu_table_init_kernel() {
   g_gelu_tab[i] = __half_as_ushort(f32_to_f16_rn(mixdq_geluf(g)));
 }
 
-// The table is built once per device by the first launch that needs it.  `done[dev]` is only set once
-// the table IS in memory for every stream: outside a capture the init kernel runs on the caller's
-// stream and is waited for (one host synchronisation per device and process, at first use).  Inside a
-// stream capture nothing may synchronise and the kernel is only RECORDED: the init is recorded in front
-// of the FIRST consumer of that capture (idempotent: every replay rewrites the same bits; later
-// consumers of the same capture are ordered behind it by the stream -- `in_capture[dev]` remembers the
-// capture's id, so a UNet graph captured cold carries one init kernel, not seventy that rewrite the
-// table under each other's readers) and `done` stays false -- an eager launch or another capture before
-// the first replay builds the table itself.  mixdq_amd builds it eagerly (mixdq_gelu_table from
-// SDXLUNet.prepare_fused_), so its captures record none.
+// Built once per device by the first launch that needs it (common.h: ensure_device_table).
 inline int ensure_gelu_table(hipStream_t stream) {
-  static bool done[64] = {};
-  static unsigned long long in_capture[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return MIXDQ_ERR_LAUNCH;
-  if (done[dev]) return MIXDQ_OK;
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  unsigned long long cap_id = 0;
-  if (hipStreamGetCaptureInfo(stream, &cap, &cap_id) != hipSuccess) return MIXDQ_ERR_LAUNCH;
-  if (cap != hipStreamCaptureStatusNone && cap_id != 0 && in_capture[dev] == cap_id) return MIXDQ_OK;
-  gelu_table_init_kernel<<<(2 * kGeluTabMag + 255) / 256, 256, 0, stream>>>();
-  if (hipGetLastError() != hipSuccess) return MIXDQ_ERR_LAUNCH;
-  if (cap == hipStreamCaptureStatusNone) {
-    if (hipStreamSynchronize(stream) != hipSuccess) return MIXDQ_ERR_LAUNCH;
-    done[dev] = true;
-  } else {
-    in_capture[dev] = cap_id;
-  }
-  return MIXDQ_OK;
+  static DeviceTableState state = {};
+  return ensure_device_table(state, stream,
+                             [&] { gelu_table_init_kernel<<<(2 * kGeluTabMag + 255) / 256, 256, 0, stream>>>(); });
 }
 
 // Two GEGLU outputs at a time from packed fp16 pairs (value xw, gate gw): the bytes q0 | q1 << 8 of
@@ -2159,12 +2135,8 @@ void igemm_kernel(MIXDQ_IGEMM_HEAD_PARAMS const IgemmParams p_in) {
 // m-tiles per super-row of the blockIdx -> tile map: 8 (super-rows of 1, 2, 4, 16 measured equal or worse
 // on the UNet's shapes; MIXDQ_IGEMM_GM=<1..64> overrides it for A/B runs)
 inline int tile_map_gm() {
-  static const int gm = [] {
-    const char* e = getenv("MIXDQ_IGEMM_GM");
-    const int v = e ? atoi(e) : 8;
-    return v >= 1 && v <= 64 ? v : 8;
-  }();
-  return gm;
+  static const int v = env_int("MIXDQ_IGEMM_GM", 8);
+  return v >= 1 && v <= 64 ? v : 8;
 }
 
 // GEMM+GEGLU: whole 32-column value|gate groups per tile and per wave
@@ -2181,14 +2153,10 @@ int launch_kernel(IgemmParams& p, hipStream_t stream) {
   static_assert(SMEM <= 160 * 1024, "LDS is 160 KiB per CU");
   if (p.Dq != nullptr && !geglu_tile_ok(BN, WN))                       // whole value|gate groups per tile, per wave
     return MIXDQ_ERR_GEGLU_SHAPE;
-  if constexpr (SMEM > 64 * 1024) {   // opt in to > 64 KiB of dynamic LDS, once per instantiation and device
-    static bool seen[64] = {};
-    if (const int st = lds_opt_in(
-            reinterpret_cast<const void*>(
-                &igemm_kernel<BM, BN, BK, STAGES, WM, WN, CONV, FAST, WBITS, KSPLIT, MT, F16, false, PHASED, GROUPED, AQ, LNQ, false, ACT>),
-            SMEM, seen))
-      return st;
-  }
+  constexpr auto kernel =
+      &igemm_kernel<BM, BN, BK, STAGES, WM, WN, CONV, FAST, WBITS, KSPLIT, MT, F16, false, PHASED, GROUPED, AQ, LNQ, false, ACT>;
+  if constexpr (SMEM > 64 * 1024)     // opt in to > 64 KiB of dynamic LDS, once per instantiation and device
+    if (const int st = lds_opt_in<kernel>(SMEM)) return st;
   p.tiles_m = (int)((p.M + BM - 1) / BM);
   p.tiles_n = (p.N + BN - 1) / BN;
   p.gm = tile_map_gm();
@@ -2210,16 +2178,13 @@ int launch_kernel(IgemmParams& p, hipStream_t stream) {
     if (cus[dev] == 0) {
       int n = 0, per_cu = 0;
       if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return MIXDQ_ERR_LAUNCH;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
-              &per_cu, igemm_kernel<BM, BN, BK, STAGES, WM, WN, CONV, FAST, WBITS, KSPLIT, MT, F16, false, PHASED, GROUPED, AQ, LNQ, false, ACT>,
-              64 * WM * WN * KSPLIT, SMEM) != hipSuccess)
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 64 * WM * WN * KSPLIT, SMEM) != hipSuccess)
         return MIXDQ_ERR_LAUNCH;
       cus[dev] = per_cu >= 1 ? n : -1;
     }
     if (cus[dev] < 0 || grid > cus[dev]) return MIXDQ_ERR_SHAPE;
   }
-  igemm_kernel<BM, BN, BK, STAGES, WM, WN, CONV, FAST, WBITS, KSPLIT, MT, F16, false, PHASED, GROUPED, AQ, LNQ, false, ACT>
-      <<<dim3((unsigned)grid, (unsigned)ny), 64 * WM * WN * KSPLIT, SMEM, stream>>>(MIXDQ_IGEMM_HEAD_ARGS(p) p);
+  kernel<<<dim3((unsigned)grid, (unsigned)ny), 64 * WM * WN * KSPLIT, SMEM, stream>>>(MIXDQ_IGEMM_HEAD_ARGS(p) p);
   return launch_status();
 }
 

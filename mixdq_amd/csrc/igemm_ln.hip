@@ -3,7 +3,6 @@
 // LayerNorm reads, so the LayerNorm and its consumers' activation quantizers run in the producer's epilogue.
 // The reference runs stock nn.LayerNorm followed by its quantize launch (nn/Linear.py:162-164); round 4 ran
 // one fused LayerNorm+quantize launch per LayerNorm (210 per step).  Its own translation unit.
-#include <cstdlib>
 #include "igemm_kernel.h"
 
 namespace mixdq {
@@ -20,7 +19,7 @@ int select_ln(int64_t M, int N, int K) {
   // all of W through its L2, so its records go through the memory side instead, and that trip costs more than
   // the LayerNorm launch it replaces: (1024, 1280, 5120) 22.1 -> 24.0, (4096, 640, 2560) 18.1 -> 19.4.  Those
   // layers keep their two launches (MIXDQ_LN_MAXK overrides the bound for A/B runs).
-  static const int max_k = [] { const char* e = getenv("MIXDQ_LN_MAXK"); return e ? atoi(e) : 1280; }();
+  static const int max_k = env_int("MIXDQ_LN_MAXK", 1280);
   if (K > max_k) return -1;
   const int64_t b64 = ((M + 63) / 64) * (N / 80), b128 = ((M + 127) / 128) * (N / 80);
   if (b64 <= kNumCU) return K > 2048 ? 45 : 56;
@@ -104,7 +103,7 @@ extern "C" int mixdq_qlinear_w8a8_ln(const int8_t* A, const int8_t* W, const flo
   }
   // records through the XCD's L2 (row blocks laid out XCD by XCD) where whole row blocks fit an XCD's share of
   // the launch and K is short; MIXDQ_LN_LOCAL=0 / 1 forces either form (A/B runs)
-  static const int local_forced = [] { const char* e = getenv("MIXDQ_LN_LOCAL"); return e ? atoi(e) : -1; }();
+  static const int local_forced = env_int("MIXDQ_LN_LOCAL", -1);
   p.ln_local = local_forced >= 0 ? (local_forced != 0) : (K <= 2048);
   p.ln_cnt = (int*)workspace;
   p.ln_part = (float*)((char*)workspace + kLnCounterBytes);

@@ -464,8 +464,7 @@ __global__ __launch_bounds__(512, 2) void igemm_pp_kernel(MIXDQ_IGEMM_HEAD_PARAM
 // MIXDQ_IGEMM_PERSIST_WGS=<n> caps the grid (tests: several tiles per workgroup on small problems).
 template <bool GEGLU>
 int launch_pp(IgemmParams& p, hipStream_t stream) {
-  static bool seen[64] = {};
-  if (const int st = lds_opt_in(reinterpret_cast<const void*>(&igemm_pp_kernel<GEGLU>), 160 * 1024, seen)) return st;
+  if (const int st = lds_opt_in<&igemm_pp_kernel<GEGLU>>(160 * 1024)) return st;
   static int cus[64] = {};
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return MIXDQ_ERR_LAUNCH;
@@ -493,7 +492,7 @@ int launch_pp(IgemmParams& p, hipStream_t stream) {
 // four-phase kernel (70)?  Where a CU has more than one tile -- else there is nothing to overlap.
 // MIXDQ_IGEMM_PERSIST=0: never (A/B runs).
 inline bool pp_auto(int64_t M, int N) {
-  static const int on = [] { const char* e = getenv("MIXDQ_IGEMM_PERSIST"); return e ? atoi(e) : 1; }();
+  static const int on = env_int("MIXDQ_IGEMM_PERSIST", 1);
   return on && ((M + 255) / 256) * (int64_t)((N + 255) / 256) > kNumCU;
 }
 

@@ -258,10 +258,6 @@ __global__ __launch_bounds__(256) void mask_dilate_cols_kernel(const uint8_t* __
   }
 }
 
-int elem_size(int dtype) {
-  return dtype == MIXDQ_IMAGE_U8 ? 1 : dtype == MIXDQ_IMAGE_F16 ? 2 : dtype == MIXDQ_IMAGE_F32 ? 4 : 0;
-}
-
 bool taps_ok(int T) { return T >= 1 && T <= MIXDQ_RESAMPLE_MAX_TAPS; }
 
 dim3 tile_grid(int Hd, int Wd, int B) {
@@ -278,7 +274,7 @@ extern "C" int mixdq_resample(const void* src, int dtype, int64_t sb, int64_t sc
                               void* dst, int dst_kind, const int32_t* xs, const float* wx, int Tx, const int32_t* ys,
                               const float* wy, int Ty, int Bt, int B, int C, int Hs, int Ws, int Hd, int Wd,
                               mixdq_stream_t stream_) {
-  const int elem = elem_size(dtype);
+  const int elem = image_elem_size(dtype);
   if (B < 0 || Hs < 0 || Ws < 0 || Hd < 0 || Wd < 0 || C < 1 || C > 4 || !elem) return MIXDQ_ERR_INVALID_ARG;
   if (src_mode != MIXDQ_RESAMPLE_SRC_VALUE && src_mode != MIXDQ_RESAMPLE_SRC_MASK) return MIXDQ_ERR_INVALID_ARG;
   if (dst_kind != MIXDQ_RESAMPLE_DST_U8 && dst_kind != MIXDQ_RESAMPLE_DST_U8_UNIT && dst_kind != MIXDQ_RESAMPLE_DST_F32)
@@ -294,13 +290,13 @@ extern "C" int mixdq_resample(const void* src, int dtype, int64_t sb, int64_t sc
   hipStream_t stream = (hipStream_t)stream_;
   const dim3 grid = tile_grid(Hd, Wd, B), block(kTileW, kWaves);
   const bool mask = src_mode == MIXDQ_RESAMPLE_SRC_MASK;
-#define R_LAUNCH(T, M) \
-  resample_kernel<T, M><<<grid, block, 0, stream>>>((const T*)src, sb, sc, sh, sw, dst, dst_kind, xs, wx, Tx, ys, wy, Ty, \
-                                                    Bt, B, C, Hs, Ws, Hd, Wd)
-  if (dtype == MIXDQ_IMAGE_U8) { if (mask) R_LAUNCH(uint8_t, true); else R_LAUNCH(uint8_t, false); }
-  else if (dtype == MIXDQ_IMAGE_F16) { if (mask) R_LAUNCH(__half, true); else R_LAUNCH(__half, false); }
-  else { if (mask) R_LAUNCH(float, true); else R_LAUNCH(float, false); }
-#undef R_LAUNCH
+  with_image_type(dtype, [&](auto t) {
+    with_bool(mask, [&](auto m) {
+      using T = decltype(t);
+      resample_kernel<T, decltype(m)::value><<<grid, block, 0, stream>>>(
+          (const T*)src, sb, sc, sh, sw, dst, dst_kind, xs, wx, Tx, ys, wy, Ty, Bt, B, C, Hs, Ws, Hd, Wd);
+    });
+  });
   return launch_status();
 }
 
@@ -309,7 +305,7 @@ extern "C" int mixdq_resample_paste_u8(const void* decoded_f16, int64_t db, int6
                                        int64_t mw, int mask_mode, const int32_t* win, const int32_t* xs, const float* wx,
                                        int Tx, const int32_t* ys, const float* wy, int Ty, int Bt, int Ht, int Wt, int B,
                                        int H, int W, mixdq_stream_t stream_) {
-  const int elem = elem_size(mask_dtype);
+  const int elem = image_elem_size(mask_dtype);
   if (B < 0 || H < 0 || W < 0 || Hm < 0 || Wm < 0 || Ht < 0 || Wt < 0 || !elem) return MIXDQ_ERR_INVALID_ARG;
   if (mask_mode != MIXDQ_PASTE_MASK_BINARY && mask_mode != MIXDQ_PASTE_MASK_SOFT) return MIXDQ_ERR_INVALID_ARG;
   if (mask_mode == MIXDQ_PASTE_MASK_SOFT && mask_dtype != MIXDQ_IMAGE_U8) return MIXDQ_ERR_INVALID_ARG;
@@ -324,49 +320,47 @@ extern "C" int mixdq_resample_paste_u8(const void* decoded_f16, int64_t db, int6
   hipStream_t stream = (hipStream_t)stream_;
   const dim3 grid = tile_grid(Ht, Wt, B), block(kTileW, kWaves);
   const __half* d = (const __half*)decoded_f16;
-#define P_LAUNCH(M, S) \
-  resample_paste_kernel<M, S><<<grid, block, 0, stream>>>(d, db, dc, dh, dw, Hm, Wm, out, (const M*)mask, mb, mh, mw, win, \
-                                                          xs, wx, Tx, ys, wy, Ty, Bt, Ht, Wt, B, H, W)
-  if (mask_mode == MIXDQ_PASTE_MASK_SOFT) P_LAUNCH(uint8_t, true);
-  else if (mask_dtype == MIXDQ_IMAGE_U8) P_LAUNCH(uint8_t, false);
-  else if (mask_dtype == MIXDQ_IMAGE_F16) P_LAUNCH(__half, false);
-  else P_LAUNCH(float, false);
-#undef P_LAUNCH
+  with_image_type(mask_dtype, [&](auto t) {
+    with_bool(mask_mode == MIXDQ_PASTE_MASK_SOFT, [&](auto soft) {
+      using M = decltype(t);
+      constexpr bool S = decltype(soft)::value;
+      if constexpr (!S || std::is_same_v<M, uint8_t>)   // a soft mask is uint8 (checked above)
+        resample_paste_kernel<M, S><<<grid, block, 0, stream>>>(d, db, dc, dh, dw, Hm, Wm, out, (const M*)mask, mb, mh,
+                                                                mw, win, xs, wx, Tx, ys, wy, Ty, Bt, Ht, Wt, B, H, W);
+    });
+  });
   return launch_status();
 }
 
 extern "C" int mixdq_mask_bbox(const void* mask, int dtype, int64_t sb, int64_t sh, int64_t sw, int32_t* out, int B, int H,
                                int W, mixdq_stream_t stream_) {
-  const int elem = elem_size(dtype);
+  const int elem = image_elem_size(dtype);
   if (B < 0 || H < 0 || W < 0 || !elem) return MIXDQ_ERR_INVALID_ARG;
   if ((int64_t)B * H * W == 0) return MIXDQ_OK;      // (an empty tensor has no storage: before the pointer checks)
   if (!mask || !out) return MIXDQ_ERR_INVALID_ARG;
   if ((uintptr_t)mask % elem || (uintptr_t)out % 4) return MIXDQ_ERR_ALIGNMENT;
   hipStream_t stream = (hipStream_t)stream_;
-  if (dtype == MIXDQ_IMAGE_U8) mask_bbox_kernel<uint8_t><<<B, kBoxLanes, 0, stream>>>((const uint8_t*)mask, sb, sh, sw, out, H, W);
-  else if (dtype == MIXDQ_IMAGE_F16) mask_bbox_kernel<__half><<<B, kBoxLanes, 0, stream>>>((const __half*)mask, sb, sh, sw, out, H, W);
-  else mask_bbox_kernel<float><<<B, kBoxLanes, 0, stream>>>((const float*)mask, sb, sh, sw, out, H, W);
+  with_image_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    mask_bbox_kernel<T><<<B, kBoxLanes, 0, stream>>>((const T*)mask, sb, sh, sw, out, H, W);
+  });
   return launch_status();
 }
 
 extern "C" int mixdq_mask_dilate_u8(const void* mask, int dtype, int64_t sb, int64_t sh, int64_t sw, uint8_t* scratch,
                                     uint8_t* out, int B, int H, int W, int radius, mixdq_stream_t stream_) {
-  const int elem = elem_size(dtype);
+  const int elem = image_elem_size(dtype);
   if (B < 0 || H < 0 || W < 0 || !elem || radius < 0 || radius > 255) return MIXDQ_ERR_INVALID_ARG;
   const int64_t pixels = (int64_t)B * H * W;
   if (pixels == 0) return MIXDQ_OK;                  // (an empty tensor has no storage: before the pointer checks)
   if (!mask || !scratch || !out || scratch == out) return MIXDQ_ERR_INVALID_ARG;
   if ((uintptr_t)mask % elem) return MIXDQ_ERR_ALIGNMENT;
   hipStream_t stream = (hipStream_t)stream_;
-  int64_t blocks64 = (pixels + 255) / 256;
-  if (blocks64 > (int64_t)kNumCU * 32) blocks64 = (int64_t)kNumCU * 32;
-  const int blocks = (int)blocks64;
-  if (dtype == MIXDQ_IMAGE_U8)
-    mask_dilate_rows_kernel<uint8_t><<<blocks, 256, 0, stream>>>((const uint8_t*)mask, sb, sh, sw, scratch, pixels, H, W, radius);
-  else if (dtype == MIXDQ_IMAGE_F16)
-    mask_dilate_rows_kernel<__half><<<blocks, 256, 0, stream>>>((const __half*)mask, sb, sh, sw, scratch, pixels, H, W, radius);
-  else
-    mask_dilate_rows_kernel<float><<<blocks, 256, 0, stream>>>((const float*)mask, sb, sh, sw, scratch, pixels, H, W, radius);
+  const int blocks = grid_blocks(pixels, 32);
+  with_image_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    mask_dilate_rows_kernel<T><<<blocks, 256, 0, stream>>>((const T*)mask, sb, sh, sw, scratch, pixels, H, W, radius);
+  });
   if (launch_status() != MIXDQ_OK) return MIXDQ_ERR_LAUNCH;
   mask_dilate_cols_kernel<<<blocks, 256, 0, stream>>>(scratch, out, pixels, H, W, radius);
   return launch_status();

@@ -11,19 +11,11 @@
 namespace mixdq {
 namespace {
 
-struct alignas(16) Half8 { uint32_t w[4]; };
-struct alignas(8) Char8 { uint32_t w[2]; };
-
 template <bool UNFUSED, bool A4>
 __device__ __forceinline__ Char8 quantize8(const Half8& h, float s_inv, float zp) {
   float x[8];
 #pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const uint32_t w = h.w[j >> 1];
-    __half_raw hr;
-    hr.x = (unsigned short)((j & 1) ? (w >> 16) : (w & 0xffffu));
-    x[j] = __half2float(__half(hr));
-  }
+  for (int j = 0; j < 8; ++j) x[j] = half_at(h, j);
   const uint2 q = quantize_pack8<UNFUSED, A4>(x, s_inv, zp);     // common.h: clamp + packing by v_ashr_pk_i8_i32 / v_perm_b32
   Char8 out;
   out.w[0] = q.x;
@@ -148,14 +140,6 @@ __global__ __launch_bounds__(256) void embed_tokens_kernel(const int* __restrict
   }
 }
 
-inline int grid_for(int64_t work_items) {
-  int64_t blocks = (work_items + 255) / 256;
-  const int64_t cap = (int64_t)kNumCU * 8;   // 2048 blocks, grid-stride the rest
-  if (blocks > cap) blocks = cap;
-  if (blocks < 1) blocks = 1;
-  return (int)blocks;
-}
-
 // What one mixdq_quantize_f16_i8 call launches: the planner's answer (mixdq_quantize_f16_i8_route reports it).
 enum { kRouteNone = -1, kRouteDense = 0, kRouteRows = 1, kRouteScalar = 2 };
 struct QuantizePlan {
@@ -209,14 +193,14 @@ inline int plan_quantize(const int64_t* sizes, const int64_t* x_strides, const i
   const bool aligned = ((uintptr_t)x % 16 == 0) && ((uintptr_t)out % 8 == 0);
   if (m == 1 && xs[0] == 1 && os[0] == 1 && aligned) {
     p->route = kRouteDense;
-    p->blocks = grid_for((numel >> 3) + 1);
+    p->blocks = grid_blocks((numel >> 3) + 1);
     return MIXDQ_OK;
   }
   bool rows_ok = aligned && a.xs[3] == 1 && a.os[3] == 1 && a.size[3] % 8 == 0;
   for (int i = 0; i < 3 && rows_ok; ++i)
     if (a.size[i] > 1 && (a.xs[i] % 8 != 0 || a.os[i] % 8 != 0)) rows_ok = false;
   p->route = rows_ok ? kRouteRows : kRouteScalar;
-  p->blocks = grid_for(rows_ok ? numel >> 3 : numel);
+  p->blocks = grid_blocks(rows_ok ? numel >> 3 : numel);
   return MIXDQ_OK;
 }
 
@@ -239,17 +223,14 @@ extern "C" int mixdq_quantize_f16_i8(const void* x_f16, int8_t* out, const int64
   if (status != MIXDQ_OK || p.route == kRouteNone) return status;
   const __half* x = (const __half*)x_f16;
   const int grid = p.blocks;
-#define Q_LAUNCH(K, ...)                                                              \
-  do {                                                                                \
-    if (a4) { if (unfused) K<true, true><<<grid, 256, 0, stream>>>(__VA_ARGS__);     \
-              else K<false, true><<<grid, 256, 0, stream>>>(__VA_ARGS__); }          \
-    else if (unfused) K<true><<<grid, 256, 0, stream>>>(__VA_ARGS__);                 \
-    else K<false><<<grid, 256, 0, stream>>>(__VA_ARGS__);                             \
-  } while (0)
-  if (p.route == kRouteDense) Q_LAUNCH(quantize_dense_kernel, x, out, scale_inv, zero_point, p.numel);
-  else if (p.route == kRouteRows) Q_LAUNCH(quantize_rows_kernel, x, out, scale_inv, zero_point, p.a);
-  else Q_LAUNCH(quantize_scalar_kernel, x, out, scale_inv, zero_point, p.a);
-#undef Q_LAUNCH
+  with_bool(unfused, [&](auto u) {
+    with_bool(a4, [&](auto a) {
+      constexpr bool U = decltype(u)::value, A4 = decltype(a)::value;
+      if (p.route == kRouteDense) quantize_dense_kernel<U, A4><<<grid, 256, 0, stream>>>(x, out, scale_inv, zero_point, p.numel);
+      else if (p.route == kRouteRows) quantize_rows_kernel<U, A4><<<grid, 256, 0, stream>>>(x, out, scale_inv, zero_point, p.a);
+      else quantize_scalar_kernel<U, A4><<<grid, 256, 0, stream>>>(x, out, scale_inv, zero_point, p.a);
+    });
+  });
   return launch_status();
 }
 
@@ -278,7 +259,7 @@ extern "C" int mixdq_embed_tokens_f16(const int32_t* ids, const void* tok_f16, c
   if (!ids || !tok_f16 || !pos_f16 || !out_f16) return MIXDQ_ERR_INVALID_ARG;
   if (((uintptr_t)tok_f16 | (uintptr_t)pos_f16 | (uintptr_t)out_f16) & 15 || ((uintptr_t)ids & 3))
     return MIXDQ_ERR_ALIGNMENT;
-  embed_tokens_kernel<<<grid_for(chunks), 256, 0, (hipStream_t)stream_>>>(
+  embed_tokens_kernel<<<grid_blocks(chunks), 256, 0, (hipStream_t)stream_>>>(
       ids, (const uint4*)tok_f16, (const uint4*)pos_f16, (uint4*)out_f16, chunks, T, C / 8, V);
   return launch_status();
 }

@@ -39,35 +39,11 @@
 // The step index is read by every workgroup of the step launch and advanced by the launch BEHIND it on the same
 // stream (sampler_advance_kernel, one thread): launches of one stream run in order, so no workgroup of the step
 // can read the index after it moved, without any in-launch ticket, fence or counter to re-initialise.
-#include <type_traits>
 #include "common.h"
 #include "../../include/mixdq_math.h"
 
 namespace mixdq {
 namespace {
-
-struct alignas(16) Half8 { uint32_t w[4]; };
-
-__device__ __forceinline__ float half_at(const Half8& h, int j) {
-  const uint32_t w = h.w[j >> 1];
-  __half_raw hr;
-  hr.x = (unsigned short)((j & 1) ? (w >> 16) : (w & 0xffffu));
-  return __half2float(__half(hr));
-}
-
-__device__ __forceinline__ uint32_t half_bits(float v) {
-  return (uint32_t)__half_raw(f32_to_f16_rn(v)).x;
-}
-
-__device__ __forceinline__ void load8(const float* __restrict__ p, float v[8]) {
-  const float4 lo = *reinterpret_cast<const float4*>(p), hi = *reinterpret_cast<const float4*>(p + 4);
-  v[0] = lo.x, v[1] = lo.y, v[2] = lo.z, v[3] = lo.w, v[4] = hi.x, v[5] = hi.y, v[6] = hi.z, v[7] = hi.w;
-}
-
-__device__ __forceinline__ void store8(float* __restrict__ p, const float v[8]) {
-  *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  *reinterpret_cast<float4*>(p + 4) = make_float4(v[4], v[5], v[6], v[7]);
-}
 
 // NOISE, the step kernel's noise mode: 0 none, 1 read from a buffer, 2 and 3 computed in registers (mixdq_rng_*,
 // include/mixdq_math.h) from (seeds[image], element in the image, *step) on stream MIXDQ_RNG_STREAM_STEP.  An 8-element
@@ -350,19 +326,6 @@ int check_step(const StepArgs& a) {
       return MIXDQ_ERR_ALIGNMENT;
   }
   return MIXDQ_OK;
-}
-
-// Blocks of 256 lanes for `items` grid-stride items (8-element passes of a step, Philox calls of a fill).
-int grid_blocks(int64_t items) {
-  int64_t blocks = (items + 255) / 256;
-  if (blocks > (int64_t)kNumCU * 8) blocks = (int64_t)kNumCU * 8;
-  return blocks < 1 ? 1 : (int)blocks;
-}
-
-// f(std::integral_constant<int, V>) for the V among Vs that equals v: a runtime mode becomes a template argument.
-template <int... Vs, class F>
-void with_constant(int v, F&& f) {
-  ((v == Vs ? (void)f(std::integral_constant<int, Vs>{}) : (void)0), ...);
 }
 
 // Check, launch the instantiation the operand set asks for, then the advance.  n == 0 launches the advance alone.

@@ -32,17 +32,12 @@
 namespace mixdq {
 namespace {
 
-struct alignas(16) Half8 { uint32_t w[4]; };
 struct alignas(8) Half4 { uint32_t w[2]; };
 
 __device__ __forceinline__ float half_of(uint32_t word, int hi) {
   __half_raw hr;
   hr.x = (unsigned short)(hi ? (word >> 16) : (word & 0xffffu));
   return __half2float(__half(hr));
-}
-
-__device__ __forceinline__ uint32_t half_bits(float v) {
-  return (uint32_t)__half_raw(f32_to_f16_rn(v)).x;
 }
 
 // one source element as the FP32 value that is rounded to FP16
@@ -275,12 +270,6 @@ __global__ __launch_bounds__(256) void composite_u8_kernel(const __half* __restr
   }
 }
 
-int grid_for(int64_t items) {
-  int64_t blocks = (items + 255) / 256;
-  if (blocks > (int64_t)kNumCU * 8) blocks = (int64_t)kNumCU * 8;
-  return (int)blocks;
-}
-
 }  // namespace
 }  // namespace mixdq
 
@@ -297,13 +286,11 @@ extern "C" int mixdq_image_to_nhwc8_f16(const void* img, int dtype, int64_t sb, 
   if ((uintptr_t)out_f16 % 16 || (uintptr_t)img % elem) return MIXDQ_ERR_ALIGNMENT;
   hipStream_t stream = (hipStream_t)stream_;
   Half8* out = (Half8*)out_f16;
-  const int blocks = grid_for(pixels);
-  if (dtype == MIXDQ_IMAGE_U8)
-    image_to_nhwc8_kernel<uint8_t><<<blocks, 256, 0, stream>>>((const uint8_t*)img, sb, sc, sh, sw, out, pixels, C, H, W);
-  else if (dtype == MIXDQ_IMAGE_F16)
-    image_to_nhwc8_kernel<__half><<<blocks, 256, 0, stream>>>((const __half*)img, sb, sc, sh, sw, out, pixels, C, H, W);
-  else
-    image_to_nhwc8_kernel<float><<<blocks, 256, 0, stream>>>((const float*)img, sb, sc, sh, sw, out, pixels, C, H, W);
+  const int blocks = grid_blocks(pixels);
+  with_image_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    image_to_nhwc8_kernel<T><<<blocks, 256, 0, stream>>>((const T*)img, sb, sc, sh, sw, out, pixels, C, H, W);
+  });
   return launch_status();
 }
 
@@ -317,38 +304,33 @@ extern "C" int mixdq_vae_latent_sample(const void* moments_f16, const float* noi
   if ((uintptr_t)moments_f16 % 16 || (uintptr_t)noise_or_null % 16 || (uintptr_t)z % 16) return MIXDQ_ERR_ALIGNMENT;
   hipStream_t stream = (hipStream_t)stream_;
   const __half* m = (const __half*)moments_f16;
-  const int blocks = grid_for(groups);
-#define V_LAUNCH(NZ, L4) \
-  vae_latent_kernel<NZ, L4><<<blocks, 256, 0, stream>>>(m, noise_or_null, z, groups, L, scaling_factor)
-  if (noise_or_null) {
-    if (L == 4) V_LAUNCH(true, true); else V_LAUNCH(true, false);
-  } else {
-    if (L == 4) V_LAUNCH(false, true); else V_LAUNCH(false, false);
-  }
-#undef V_LAUNCH
+  const int blocks = grid_blocks(groups);
+  with_bool(noise_or_null != nullptr, [&](auto nz) {
+    with_bool(L == 4, [&](auto l4) {
+      vae_latent_kernel<decltype(nz)::value, decltype(l4)::value><<<blocks, 256, 0, stream>>>(
+          m, noise_or_null, z, groups, L, scaling_factor);
+    });
+  });
   return launch_status();
 }
 
 namespace {
-int image_elem_size(int dtype) {
-  return dtype == MIXDQ_IMAGE_U8 ? 1 : dtype == MIXDQ_IMAGE_F16 ? 2 : dtype == MIXDQ_IMAGE_F32 ? 4 : 0;
-}
-
 template <typename T>
 void launch_mask_to_latent(const void* mask, int64_t sb, int64_t sh, int64_t sw, float* out, int64_t pixels, int h, int w,
                            int mode, hipStream_t stream) {
   const T* m = (const T*)mask;
-  const int blocks = grid_for(pixels);
+  const int blocks = grid_blocks(pixels);
   // a row of 8 elements as one 8-byte (uint8) or 16-byte load(s): every row start must be aligned to that
   const int64_t align = sizeof(T) == 1 ? 8 : 16;
   const bool wide = sw == 1 && (uintptr_t)mask % align == 0 && (sh * (int64_t)sizeof(T)) % align == 0 &&
                     (sb * (int64_t)sizeof(T)) % align == 0;
-  if (mode == MIXDQ_MASK_NEAREST)
-    mask_to_latent_kernel<T, false, false><<<blocks, 256, 0, stream>>>(m, sb, sh, sw, out, pixels, h, w);
-  else if (wide)
-    mask_to_latent_kernel<T, true, true><<<blocks, 256, 0, stream>>>(m, sb, sh, sw, out, pixels, h, w);
-  else
-    mask_to_latent_kernel<T, true, false><<<blocks, 256, 0, stream>>>(m, sb, sh, sw, out, pixels, h, w);
+  with_bool(mode != MIXDQ_MASK_NEAREST, [&](auto any) {
+    with_bool(wide, [&](auto w8) {
+      constexpr bool ANY = decltype(any)::value, WIDE = decltype(w8)::value;
+      // (nearest reads one element per latent pixel: it has no wide form)
+      mask_to_latent_kernel<T, ANY, ANY && WIDE><<<blocks, 256, 0, stream>>>(m, sb, sh, sw, out, pixels, h, w);
+    });
+  });
 }
 }  // namespace
 
@@ -363,9 +345,9 @@ extern "C" int mixdq_mask_to_latent(const void* mask, int dtype, int64_t sb, int
   hipStream_t stream = (hipStream_t)stream_;
   const int h = H / 8, w = W / 8;
   const int64_t pixels = (int64_t)B * h * w;
-  if (dtype == MIXDQ_IMAGE_U8) launch_mask_to_latent<uint8_t>(mask, sb, sh, sw, out, pixels, h, w, mode, stream);
-  else if (dtype == MIXDQ_IMAGE_F16) launch_mask_to_latent<__half>(mask, sb, sh, sw, out, pixels, h, w, mode, stream);
-  else launch_mask_to_latent<float>(mask, sb, sh, sw, out, pixels, h, w, mode, stream);
+  with_image_type(dtype, [&](auto t) {
+    launch_mask_to_latent<decltype(t)>(mask, sb, sh, sw, out, pixels, h, w, mode, stream);
+  });
   return launch_status();
 }
 
@@ -381,14 +363,12 @@ extern "C" int mixdq_composite_u8(const void* decoded_f16, int64_t db, int64_t d
   if ((uintptr_t)decoded_f16 % 2 || (uintptr_t)mask % elem) return MIXDQ_ERR_ALIGNMENT;
   hipStream_t stream = (hipStream_t)stream_;
   const __half* d = (const __half*)decoded_f16;
-  const int blocks = grid_for(pixels);
-#define C_LAUNCH(T) \
-  composite_u8_kernel<T><<<blocks, 256, 0, stream>>>(d, db, dc, dh, dw, original, ob, oc, oh, ow, (const T*)mask, mb, mh, \
-                                                     mw, out, pixels, H, W)
-  if (mask_dtype == MIXDQ_IMAGE_U8) C_LAUNCH(uint8_t);
-  else if (mask_dtype == MIXDQ_IMAGE_F16) C_LAUNCH(__half);
-  else C_LAUNCH(float);
-#undef C_LAUNCH
+  const int blocks = grid_blocks(pixels);
+  with_image_type(mask_dtype, [&](auto t) {
+    using T = decltype(t);
+    composite_u8_kernel<T><<<blocks, 256, 0, stream>>>(d, db, dc, dh, dw, original, ob, oc, oh, ow, (const T*)mask, mb,
+                                                       mh, mw, out, pixels, H, W);
+  });
   return launch_status();
 }
 
@@ -397,14 +377,12 @@ template <typename T>
 void launch_ingest_masked(const void* img, int64_t sb, int64_t sc, int64_t sh, int64_t sw, const void* mask,
                           int mask_dtype, int64_t mb, int64_t mh, int64_t mw, Half8* out, int64_t pixels, int C, int H,
                           int W, hipStream_t stream) {
-  const int blocks = grid_for(pixels);
-#define I_LAUNCH(M) \
-  image_to_nhwc8_masked_kernel<T, M><<<blocks, 256, 0, stream>>>((const T*)img, sb, sc, sh, sw, (const M*)mask, mb, mh, \
-                                                                 mw, out, pixels, C, H, W)
-  if (mask_dtype == MIXDQ_IMAGE_U8) I_LAUNCH(uint8_t);
-  else if (mask_dtype == MIXDQ_IMAGE_F16) I_LAUNCH(__half);
-  else I_LAUNCH(float);
-#undef I_LAUNCH
+  const int blocks = grid_blocks(pixels);
+  with_image_type(mask_dtype, [&](auto mt) {
+    using M = decltype(mt);
+    image_to_nhwc8_masked_kernel<T, M><<<blocks, 256, 0, stream>>>((const T*)img, sb, sc, sh, sw, (const M*)mask, mb,
+                                                                   mh, mw, out, pixels, C, H, W);
+  });
 }
 }  // namespace
 
@@ -420,12 +398,9 @@ extern "C" int mixdq_image_to_nhwc8_f16_masked(const void* img, int dtype, int64
   if ((uintptr_t)out_f16 % 16 || (uintptr_t)img % elem || (uintptr_t)mask % melem) return MIXDQ_ERR_ALIGNMENT;
   hipStream_t stream = (hipStream_t)stream_;
   Half8* out = (Half8*)out_f16;
-  if (dtype == MIXDQ_IMAGE_U8)
-    launch_ingest_masked<uint8_t>(img, sb, sc, sh, sw, mask, mask_dtype, mb, mh, mw, out, pixels, C, H, W, stream);
-  else if (dtype == MIXDQ_IMAGE_F16)
-    launch_ingest_masked<__half>(img, sb, sc, sh, sw, mask, mask_dtype, mb, mh, mw, out, pixels, C, H, W, stream);
-  else
-    launch_ingest_masked<float>(img, sb, sc, sh, sw, mask, mask_dtype, mb, mh, mw, out, pixels, C, H, W, stream);
+  with_image_type(dtype, [&](auto t) {
+    launch_ingest_masked<decltype(t)>(img, sb, sc, sh, sw, mask, mask_dtype, mb, mh, mw, out, pixels, C, H, W, stream);
+  });
   return launch_status();
 }
 
@@ -437,11 +412,10 @@ extern "C" int mixdq_inpaint_cond_f16(const float* mask_lat, const float* zl, vo
   if ((uintptr_t)out_f16 % 16 || (uintptr_t)mask_lat % 4 || (uintptr_t)zl % 4) return MIXDQ_ERR_ALIGNMENT;
   hipStream_t stream = (hipStream_t)stream_;
   Half8* out = (Half8*)out_f16;
-  const int blocks = grid_for(pixels);
-  if (L == 4 && (uintptr_t)zl % 16 == 0)
-    inpaint_cond_kernel<true><<<blocks, 256, 0, stream>>>(mask_lat, zl, out, pixels, L);
-  else
-    inpaint_cond_kernel<false><<<blocks, 256, 0, stream>>>(mask_lat, zl, out, pixels, L);
+  const int blocks = grid_blocks(pixels);
+  with_bool(L == 4 && (uintptr_t)zl % 16 == 0, [&](auto l4) {
+    inpaint_cond_kernel<decltype(l4)::value><<<blocks, 256, 0, stream>>>(mask_lat, zl, out, pixels, L);
+  });
   return launch_status();
 }
 
@@ -455,11 +429,12 @@ extern "C" int mixdq_ip2p_cond_f16(const void* moments_f16, void* out_f16, int B
   hipStream_t stream = (hipStream_t)stream_;
   const __half* m = (const __half*)moments_f16;
   Half8* out = (Half8*)out_f16;
-  const int blocks = grid_for(total);
+  const int blocks = grid_blocks(total);
   const bool l4 = L == 4 && (uintptr_t)moments_f16 % 8 == 0;
-#define P_LAUNCH(R, V) ip2p_cond_kernel<R, V><<<blocks, 256, 0, stream>>>(m, out, total, L, scale)
-  if (rows == 3) { if (l4) P_LAUNCH(3, true); else P_LAUNCH(3, false); }
-  else { if (l4) P_LAUNCH(1, true); else P_LAUNCH(1, false); }
-#undef P_LAUNCH
+  with_constant<1, 3>(rows, [&](auto r) {
+    with_bool(l4, [&](auto v) {
+      ip2p_cond_kernel<decltype(r)::value, decltype(v)::value><<<blocks, 256, 0, stream>>>(m, out, total, L, scale);
+    });
+  });
   return launch_status();
 }

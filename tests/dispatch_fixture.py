@@ -7,6 +7,7 @@ Plain ctypes on the built library (MIXDQ_HIP_LIB or the in-tree one), no torch. 
 are dummies that are never dereferenced: multiples of 4096 where a call wants alignment, small integers where it is
 to refuse a misaligned one.  Only cases whose return precedes the first launch, LDS opt-in or table
 initialisation belong here; none may answer MIXDQ_ERR_LAUNCH (record() checks).
+What the calls that DO launch launch is pinned by tests/launch_trace.py, on the CPU against a stand-in HIP runtime.
 """
 import ctypes
 import itertools

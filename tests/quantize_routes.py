@@ -34,7 +34,7 @@ import torch
 
 from tests import detdata as dd
 
-GRID_CAP_BLOCKS = 256 * 8                 # grid_for: kNumCU * 8 blocks of 256 lanes
+GRID_CAP_BLOCKS = 256 * 8                 # grid_blocks (csrc/common.h): kNumCU * 8 blocks of 256 lanes
 GRID_CAP_LANES = GRID_CAP_BLOCKS * 256    # 524 288 work items: more than that and a lane makes a second trip
 DEEP_MIN_NUMEL = 8 * 3 * GRID_CAP_LANES   # 12 582 912: beyond it the dense kernel's four-loads-in-flight loop runs
 OK, ERR_SHAPE = 0, 9                      # include/mixdq_hip.h
