@@ -870,6 +870,34 @@ int mixdq_sampler_step3(float* x, const void* eps_f16, void* in_f16, const float
                         const int* first_or_null, const float* z, const float* noise0, const float* mask, int channels,
                         const float* blend, mixdq_stream_t stream);
 
+/* Guidance rescale (csrc/sampler_rescale.hip; diffusers' guidance_rescale, Lin et al. 2023): the step of the entry
+ * points above at two or three rows per image, with the guided model output e of every image multiplied by
+ *   r = 1 + rescale * (sqrt(M2_t / M2_e) - 1),      M2_v = sum over the image's n_image elements of (v - mean_v)^2
+ * before the update -- t the text-conditioned output (two rows: row block 1; three rows: block 0), so that sqrt(M2_t /
+ * M2_e) is std(t) / std(e) of torch's unbiased std.  r = 1 where M2_e == 0, M2_t == 0 or n_image == 1 (diffusers
+ * returns NaN there).  How M2 is summed -- chunks of 2048 elements, a fixed order inside a chunk, Chan's update across
+ * them -- is part of the specification: include/mixdq_math.h, mixdq_rescale_*.  With rescale == 0 (r == 1 exactly) the
+ * results are the sibling entry point's bit for bit.
+ * ONE entry point, the whole operand set flat as mixdq_sampler_step3 takes it (the operands of a mode null when the
+ * mode is off), and beside it: rows_per_image 2 (image_guidance is not read) or 3; rescale, phi in [0, 1]; n_image, the
+ * elements of one image (n = images * n_image; also what seeds_or_null counts by); workspace, FP32 device memory of
+ * mixdq_sampler_rescale_workspace_floats(n, n_image) floats, 16-byte aligned, the caller's: nothing is allocated here,
+ * its contents need not survive between calls.  Launches, in stream order on grids of exactly (ceil(n_image / 2048),
+ * images) workgroups: the chunk statistics, the step (which combines them per image), the advance; n == 0: the advance
+ * alone.
+ * Errors, before any launch: rows_per_image not 2 or 3, then mixdq_sampler_step3's own and the siblings' checks in
+ * their order; then rescale outside [0, 1] or NaN, n_image < 1, n % n_image != 0, a null workspace, more than 65535
+ * images (the grid's y extent): MIXDQ_ERR_INVALID_ARG; workspace not 16-byte aligned: MIXDQ_ERR_ALIGNMENT.
+ * mixdq_sampler_rescale_workspace_floats: 0 for n < 0, n_image < 1 or n % n_image != 0. */
+size_t mixdq_sampler_rescale_workspace_floats(int64_t n, int64_t n_image);
+int mixdq_sampler_step_rescaled(float* x, const void* eps_f16, void* in_f16, const float* table, int table_width,
+                                const float* t_table, int n_steps, int* step, float* timestep, float guidance,
+                                float image_guidance, float rescale, int rows_per_image, int64_t n, int64_t n_image,
+                                int64_t row_stride, float* workspace, const float* noise_or_null, int64_t noise_stride,
+                                const uint64_t* seeds_or_null, float* hist_or_null, const int* first_or_null,
+                                const float* z, const float* noise0, const float* mask, int channels,
+                                const float* blend, mixdq_stream_t stream);
+
 /* Which kernel instantiation mixdq_qlinear_w8a8 / mixdq_qconv2d_w8a8 will launch for a problem of
  * M rows x N output channels (k_align = K for Linear, C for Conv2d; k_total = K or R*S*C): the block tile BM x BN x BK
  * and LDS stage count of `igemm_kernel<BM,BN,BK,STAGES,CONV>`, or zeros for the small-alignment

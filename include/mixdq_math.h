@@ -347,4 +347,65 @@ MIXDQ_HD uint8_t mixdq_blend_u8(uint8_t m, uint8_t d, uint8_t o) {
   return (uint8_t)(s / 255u);
 }
 
+/* ---- guidance rescale (mixdq_sampler_step_rescaled, csrc/sampler_rescale.hip), same rule: Lin et al., "Common
+ * diffusion noise schedules and sample steps are flawed", diffusers' rescale_noise_cfg.  Per image, over all of its
+ * n_image storage elements, with t the text-conditioned model output (two rows: row block 1; three rows: block 0, e_t;
+ * FP16 read exactly as FP32) and e the guided output (mixdq_sampler_guided_eps / _eps3 of the same elements):
+ *   s  = sqrt(M2_t / M2_e)          M2 = sum((v - mean)^2): the n - 1 of an unbiased std cancels in the quotient
+ *   r  = 1 + phi * (s - 1)          diffusers' phi * s + (1 - phi), written so that s == 1 gives r == 1 exactly
+ *   e' = e * r                      one product (mixdq_sampler_rescaled); the rest of the step is unchanged
+ * r = 1 where M2_e == 0, M2_t == 0 or n_image == 1 (OUR definition: diffusers divides by zero there and returns NaN).
+ *
+ * M2 is NOT E[x^2] - mean^2 (which cancels: a latent with mean 64 and unit spread loses four digits in FP32).  The image
+ * is cut into CHUNKS of MIXDQ_RESCALE_CHUNK = 2048 consecutive elements (256 lanes x 8; the last chunk holds the
+ * remaining count >= 1 elements, any number).  Per chunk and tensor, two passes over the same values:
+ *   mean_c = S(v) / (float)count                 the division correctly rounded
+ *   M2_c   = S((v - mean_c) * (v - mean_c))      one difference and one product per element, each rounded
+ * where S is a sum of 2048 terms in a FIXED order, elements beyond `count` entering as +0:
+ *   lane l (0 .. 255):  p_l = ((((((v[8l] + v[8l+1]) + v[8l+2]) + ... ) + v[8l+7])       seven sums in storage order
+ *   wave w (lanes 64w .. 64w + 63): for k = 1, 2, 4, 8, 16, 32 in turn every lane replaces p_l by p_l + p_(l ^ k) --
+ *                        a balanced pairwise tree; after the six rounds all 64 lanes hold the wave's sum W_w
+ *   S = ((W_0 + W_1) + W_2) + W_3                three sums
+ * mixdq_rescale_lane_sum is the first line; the other two are adds a caller arranges (csrc/sampler_rescale.hip,
+ * tests/rescale_ref.py).  The chunks of an image are then combined IN CHUNK ORDER by Chan's update, starting from
+ * (n, mean, M2) = (0, 0, 0) -- mixdq_rescale_combine, every operation one rounding, the integers converted to FP32 by
+ * round-to-nearest:
+ *   tot = n + k                                  integers (k: the chunk's count)
+ *   d   = mean_c - mean
+ *   mean' = mean + d * ((float)k / (float)tot)                                    division, product, sum
+ *   M2'   = M2 + (M2_c + (d * d) * (((float)n * (float)k) / (float)tot))          product, product, division, product, two sums
+ * The first chunk gives (mean_0, M2_0) exactly: k / k == 1 and n == 0.  The division is the language's own (IEEE,
+ * correctly rounded: hipcc's default for gfx950 as for the host), the square root MIXDQ_SQRT_RN: no hardware estimate
+ * enters, so a device and a host compiler agree bit for bit. */
+#define MIXDQ_RESCALE_CHUNK 2048
+#define MIXDQ_DIV_RN(a, b) ((a) / (b))
+
+MIXDQ_HD float mixdq_rescale_lane_sum(const float v[8]) {
+  float s = MIXDQ_ADD_RN(v[0], v[1]);
+  for (int j = 2; j < 8; ++j) s = MIXDQ_ADD_RN(s, v[j]);
+  return s;
+}
+
+/* One element's term of the second pass. */
+MIXDQ_HD float mixdq_rescale_sqdev(float v, float mean_c) {
+  const float d = MIXDQ_SUB_RN(v, mean_c);
+  return MIXDQ_MUL_RN(d, d);
+}
+
+MIXDQ_HD void mixdq_rescale_combine(int64_t n, int64_t k, float mean_c, float m2_c, float* mean, float* m2) {
+  const float fn = (float)n, fk = (float)k, ft = (float)(n + k);
+  const float d = MIXDQ_SUB_RN(mean_c, *mean);
+  *mean = MIXDQ_ADD_RN(*mean, MIXDQ_MUL_RN(d, MIXDQ_DIV_RN(fk, ft)));
+  const float q = MIXDQ_DIV_RN(MIXDQ_MUL_RN(fn, fk), ft);
+  *m2 = MIXDQ_ADD_RN(*m2, MIXDQ_ADD_RN(m2_c, MIXDQ_MUL_RN(MIXDQ_MUL_RN(d, d), q)));
+}
+
+MIXDQ_HD float mixdq_rescale_factor(float m2_t, float m2_e, float phi, int64_t n_image) {
+  if (m2_e == 0.0f || m2_t == 0.0f || n_image == 1) return 1.0f;
+  const float s = MIXDQ_SQRT_RN(MIXDQ_DIV_RN(m2_t, m2_e));
+  return MIXDQ_ADD_RN(1.0f, MIXDQ_MUL_RN(phi, MIXDQ_SUB_RN(s, 1.0f)));
+}
+
+MIXDQ_HD float mixdq_sampler_rescaled(float e, float r) { return MIXDQ_MUL_RN(e, r); }
+
 #endif /* MIXDQ_MATH_H_ */

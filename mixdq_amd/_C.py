@@ -1415,6 +1415,14 @@ for _name, _head, _tail in (("", _STEP_ORDER1, []), ("_masked", _STEP_ORDER1, _S
 _lib.mixdq_sampler_step3.argtypes = ([_vp] * 4 + [_i32, _vp, _i32, _vp, _vp, ctypes.c_float, ctypes.c_float, _i64, _i64]
                                      + [_vp, _i64, _vp, _i64, _vp, _vp] + _STEP_MASKED + [_vp])
 _lib.mixdq_sampler_step3.restype = _i32
+# the rescaled step: step3's head with rescale, rows_per_image, n, n_image, row_stride and the workspace in it, then
+# noise, noise_stride, seeds, hist, first and the masked operands
+_lib.mixdq_sampler_step_rescaled.argtypes = (
+    [_vp] * 4 + [_i32, _vp, _i32, _vp, _vp, ctypes.c_float, ctypes.c_float, ctypes.c_float, _i32, _i64, _i64, _i64, _vp]
+    + [_vp, _i64, _vp, _vp, _vp] + _STEP_MASKED + [_vp])
+_lib.mixdq_sampler_step_rescaled.restype = _i32
+_lib.mixdq_sampler_rescale_workspace_floats.argtypes = [_i64, _i64]
+_lib.mixdq_sampler_rescale_workspace_floats.restype = ctypes.c_size_t
 _lib.mixdq_randn_f32.argtypes = [_vp, _i32, _i64, _vp, ctypes.c_uint32, ctypes.c_uint32, _vp]
 _lib.mixdq_randn_f32.restype = _i32
 _lib.mixdq_rng_normals_from_bits.argtypes = [_vp, _vp, _i64, _vp]
@@ -1477,13 +1485,18 @@ def rng_normals_from_bits(r):
 
 def _sampler_step(what, x, eps, inp, table, width, t_table, step, timestep, guidance, rows_per_image, n, row_stride, *,
                   hist=None, first=None, masked=None, channels=4, noise=None, noise_stride=None, seeds=None,
-                  n_image=None, image_guidance=None):
-    """The checks and the call of the five step bindings.  `what`: the binding's name; `table`: coef (width 4) or, for
+                  n_image=None, image_guidance=None, rescale=None, workspace=None):
+    """The checks and the call of the step bindings.  `what`: the binding's name; `table`: coef (width 4) or, for
     the multistep kinds, coef8 (width 8), which come with `hist` and `first`; masked: None or (z, noise0, mask, blend);
     noise / seeds: at most one of them, width 4 only; image_guidance: None, or the second scale of the three-row step
-    (mixdq_sampler_step3, rows_per_image == 3)."""
+    (mixdq_sampler_step3, rows_per_image == 3); rescale: None, or phi of the rescaled step
+    (mixdq_sampler_step_rescaled, rows_per_image 2 or 3), which comes with `workspace` and `n_image`."""
     if seeds is not None:
         n, n_image = _check_step_seeds(seeds, noise, n, n_image, x.numel(), what)
+    elif rescale is not None:
+        n = int(x.numel() if n is None else n)
+        n_image = n if n_image is None else int(n_image)
+        _check(n_image >= 1 and n % n_image == 0, f"{what}: n = {n} is not a multiple of n_image = {n_image}")
     f32, f16, i32 = torch.float32, torch.float16, torch.int32
     two_m = width == 8
     tname = "coef8" if two_m else "coef"
@@ -1497,6 +1510,8 @@ def _sampler_step(what, x, eps, inp, table, width, t_table, step, timestep, guid
         operands.append((noise, "noise", f32))
     if seeds is not None:
         operands.append((seeds, "seeds", torch.int64))
+    if rescale is not None:
+        operands.append((workspace, "workspace", f32))
     for t_, name, dt in operands:
         _check(torch.is_tensor(t_) and t_.is_cuda and t_.device == x.device and t_.dtype == dt,
                f"{name} should be a {dt} tensor on x's GPU")
@@ -1524,19 +1539,29 @@ def _sampler_step(what, x, eps, inp, table, width, t_table, step, timestep, guid
         if channels >= 1 and n % channels == 0:       # (anything else: the library's own error)
             _check(mask.is_contiguous() and mask.numel() >= n // channels,
                    "mask should be dense with n / channels entries")
+    if rescale is not None:
+        _check(workspace.is_contiguous() and workspace.numel() >= _lib.mixdq_sampler_rescale_workspace_floats(n, n_image),
+               "workspace is smaller than sampler_rescale_workspace(n, n_image)")
     if rows_per_image in (1, 2) or image_guidance is not None:   # (anything else: the library's own error)
         need = (rows_per_image - 1) * row_stride + n
         _check(eps.numel() >= need and inp.numel() >= need, "eps / inp are smaller than rows_per_image row blocks")
     if noise is not None:
         _check(noise.numel() >= (n_steps - 1) * noise_stride + n, "noise is smaller than n_steps blocks")
-    if image_guidance is not None:
+    if image_guidance is not None or rescale is not None:        # the two flat entry points
         args = [x.data_ptr(), eps.data_ptr(), inp.data_ptr(), table.data_ptr(), width, t_table.data_ptr(), n_steps,
-                step.data_ptr(), timestep.data_ptr(), float(guidance), float(image_guidance), n, row_stride,
-                _ptr(noise), noise_stride, _ptr(seeds), 0 if seeds is None else n_image, _ptr(hist), _ptr(first)]
+                step.data_ptr(), timestep.data_ptr(), float(guidance), float(image_guidance or 0.0)]
+        if rescale is not None:
+            entry = _lib.mixdq_sampler_step_rescaled
+            args += [float(rescale), int(rows_per_image), n, n_image, row_stride, workspace.data_ptr(), _ptr(noise),
+                     noise_stride, _ptr(seeds), _ptr(hist), _ptr(first)]
+        else:
+            entry = _lib.mixdq_sampler_step3
+            args += [n, row_stride, _ptr(noise), noise_stride, _ptr(seeds), 0 if seeds is None else n_image, _ptr(hist),
+                     _ptr(first)]
         args += [t_.data_ptr() for t_ in masked[:3]] + [channels, masked[3].data_ptr()] if masked is not None else [
             None, None, None, 1, None]
         with torch.cuda.device(x.device):
-            code = _lib.mixdq_sampler_step3(*args, _stream())
+            code = entry(*args, _stream())
         _status(code, what)
         return
     args = [x.data_ptr(), eps.data_ptr(), inp.data_ptr()]
@@ -1638,6 +1663,49 @@ def sampler_step3(x, eps, inp, table, t_table, step, timestep, guidance, image_g
                   hist=hist, first=first, masked=(z, noise0, mask, blend) if all(some) else None, channels=channels,
                   noise=noise, noise_stride=noise_stride, seeds=seeds, n_image=n_image,
                   image_guidance=image_guidance)
+
+
+def sampler_rescale_workspace(n, n_image, device):
+    """The FP32 workspace sampler_step_rescaled needs for a state of `n` elements in images of `n_image`
+    (mixdq_sampler_rescale_workspace_floats): per 2048-element chunk of an image four statistics, and one factor per
+    image.  The caller keeps it (a Sampler: one static buffer); its contents need not survive between steps."""
+    n, n_image = int(n), int(n_image)
+    _check(n >= 0 and n_image >= 1 and n % n_image == 0, f"sampler_rescale_workspace: n = {n} is not a multiple of "
+           f"n_image = {n_image}")
+    return torch.zeros(max(int(_lib.mixdq_sampler_rescale_workspace_floats(n, n_image)), 4), dtype=torch.float32,
+                       device=device)
+
+
+def sampler_step_rescaled(x, eps, inp, table, t_table, step, timestep, guidance, image_guidance, rescale, workspace, *,
+                          rows_per_image, n_image=None, noise=None, seeds=None, hist=None, first=None, z=None,
+                          noise0=None, mask=None, blend=None, channels=4, n=None, row_stride=None, noise_stride=None):
+    """One sampler step with guidance rescale (mixdq_sampler_step_rescaled; diffusers' guidance_rescale): the guided
+    output of every image is multiplied by 1 + rescale * (std(t) / std(e) - 1) before the update -- t the
+    text-conditioned output (rows_per_image 2: row block 1, sampler_step's order; 3: block 0, sampler_step3's order), e
+    the guided one, the standard deviations over the image's `n_image` elements (default: n, one image).  Where a
+    standard deviation is 0 the factor is 1 (diffusers: NaN).  rescale in [0, 1]; 0 is the plain step bit for bit.
+
+    workspace: sampler_rescale_workspace(n, n_image, device).  image_guidance: the second scale of three rows, None
+    (not read) with two.  Everything else -- table (coef, or coef8 with hist and first), noise or seeds, z / noise0 /
+    mask / blend with channels -- as sampler_step3 takes it."""
+    what = "sampler_step_rescaled"
+    _check(rows_per_image in (2, 3), f"{what}: rows_per_image should be 2 or 3 (rescale compares the guided output "
+           "with the text-conditioned one)")
+    _check(isinstance(rescale, (int, float)) and 0.0 <= float(rescale) <= 1.0, f"{what}: rescale should be in [0, 1]")
+    width = table.shape[1] if torch.is_tensor(table) and table.dim() == 2 else 4
+    _check(width in (4, 8), f"{what}: table should be coef [n_steps, 4] or coef8 [n_steps, 8]")
+    if width == 8:
+        _check(noise is None and seeds is None, f"{what}: the multistep kinds add no noise")
+        _check(hist is not None and first is not None, f"{what}: coef8 comes with hist and first")
+    else:
+        _check(hist is None and first is None, f"{what}: hist and first come with coef8")
+    some = [t_ is not None for t_ in (z, noise0, mask, blend)]
+    _check(all(some) or not any(some), f"{what}: z, noise0, mask and blend go together")
+    _sampler_step(what, x, eps, inp, table, width, t_table, step, timestep, guidance, rows_per_image, n, row_stride,
+                  hist=hist, first=first, masked=(z, noise0, mask, blend) if all(some) else None, channels=channels,
+                  noise=noise, noise_stride=noise_stride, seeds=seeds, n_image=n_image,
+                  image_guidance=image_guidance if rows_per_image == 3 else None, rescale=float(rescale),
+                  workspace=workspace)
 
 
 _lib.mixdq_image_to_nhwc8_f16.argtypes = [_vp, _i32, _i64, _i64, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _vp]

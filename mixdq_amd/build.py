@@ -13,7 +13,10 @@ CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libmixdq_hip.so")
 SOURCES = ["quantize.hip", "igemm.hip", "igemm_aq.hip", "igemm_ln.hip", "iconv.hip", "fused_norm.hip", "attention.hip",
            "sampler.hip", "vae.hip", "image.hip"]
-HEADERS = ["common.h", "attn_core.h", "iconv.h", "igemm_kernel.h", "igemm_pp.h", "f16in_table.h", os.path.join("..", "..", "include", "mixdq_hip.h"),
+# Units added behind a recorded kernel set: their objects go to _obj/ext/, so that what the objects directly inside
+# _obj/ register stays what tests/golden/launch_trace.json lists; they are linked into the same library.
+EXT_SOURCES = ["sampler_rescale.hip"]
+HEADERS = ["common.h", "attn_core.h", "iconv.h", "igemm_kernel.h", "igemm_pp.h", "f16in_table.h", "sampler_step.h", os.path.join("..", "..", "include", "mixdq_hip.h"),
            os.path.join("..", "..", "include", "mixdq_math.h")]
 # -ffp-contract=off: every fused multiply-add in the arithmetic specification is written
 # explicitly (__builtin_fmaf); the compiler must not introduce others.
@@ -32,6 +35,7 @@ EXTRA = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
          "igemm_aq.hip": ["-mllvm", "-amdgpu-kernarg-preload-count=14"],
          "igemm_ln.hip": ["-mllvm", "-amdgpu-kernarg-preload-count=14"]}
 OBJ = os.path.join(PKG, "_obj")
+OBJ_EXT = os.path.join(OBJ, "ext")
 
 
 def _hipcc():
@@ -94,19 +98,19 @@ def needs_build() -> bool:
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, s) for s in SOURCES + HEADERS] + [os.path.abspath(__file__)]
+    deps = [os.path.join(CSRC, s) for s in SOURCES + EXT_SOURCES + HEADERS] + [os.path.abspath(__file__)]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
     if force or needs_build():
-        os.makedirs(OBJ, exist_ok=True)
+        os.makedirs(OBJ_EXT, exist_ok=True)
         hdr_t = max(os.path.getmtime(os.path.join(CSRC, h)) for h in HEADERS)
         hdr_t = max(hdr_t, os.path.getmtime(os.path.abspath(__file__)))
         procs, objs = [], []
-        for src in SOURCES:
+        for src in SOURCES + EXT_SOURCES:
             path = os.path.join(CSRC, src)
-            obj = os.path.join(OBJ, src.replace(".hip", ".o"))
+            obj = os.path.join(OBJ_EXT if src in EXT_SOURCES else OBJ, src.replace(".hip", ".o"))
             objs.append(obj)
             if (not force and os.path.exists(obj)
                     and os.path.getmtime(obj) > max(hdr_t, os.path.getmtime(path))):

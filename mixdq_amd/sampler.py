@@ -69,9 +69,22 @@ _DEFAULT_SPACING = {"euler_ancestral": "trailing", "euler": "leading", "lcm": "l
                     "dpmpp_2m": "leading"}
 
 
-def alphas_cumprod() -> np.ndarray:
-    """Stable Diffusion's scaled-linear betas: cumprod(1 - linspace(sqrt(0.00085), sqrt(0.012), 1000) ** 2)."""
+def rescale_betas_zero_snr(betas: np.ndarray) -> np.ndarray:
+    """diffusers' rescale_betas_zero_snr (Lin et al., algorithm 1) in float64: sqrt(alphas_cumprod) shifted so that its
+    last value is 0 and scaled so that its first one stays, turned back into betas.  The last beta is exactly 1."""
+    bar_sqrt = np.sqrt(np.cumprod(1.0 - betas))
+    first, last = bar_sqrt[0], bar_sqrt[-1]
+    bar_sqrt = (bar_sqrt - last) * (first / (first - last))
+    bar = bar_sqrt ** 2
+    return 1.0 - np.concatenate([bar[:1], bar[1:] / bar[:-1]])
+
+
+def alphas_cumprod(zero_snr=False) -> np.ndarray:
+    """Stable Diffusion's scaled-linear betas: cumprod(1 - linspace(sqrt(0.00085), sqrt(0.012), 1000) ** 2).
+    zero_snr: of those betas through rescale_betas_zero_snr -- the last entry is then exactly 0."""
     betas = np.linspace(0.00085 ** 0.5, 0.012 ** 0.5, TRAIN_STEPS, dtype=np.float64) ** 2
+    if zero_snr:
+        betas = rescale_betas_zero_snr(betas)
     return np.cumprod(1.0 - betas)
 
 
@@ -167,6 +180,36 @@ def multistep_table(sigmas) -> np.ndarray:
     return tab
 
 
+def multistep_table_vp(alpha, hat) -> np.ndarray:
+    """multistep_table for a v-predicting model, written in the VP pair (alpha, sigma_hat) of every step (n + 1 values
+    each, ending in (1, 0)) so that a first step at zero terminal SNR -- alpha_0 = 0, sigma infinite -- forms nothing
+    infinite: x0 = u * x + v * m with u = alpha_i, v = -sigma_hat_i, and with lambda = log(alpha / sigma_hat)
+        e^-h = (alpha_i / sigma_hat_i) * (sigma_hat_{i+1} / alpha_{i+1}),      E = -alpha_{i+1} * expm1(-h)
+    where alpha_i = 0 gives e^-h = 0 and E = alpha_{i+1}.  The step behind such a first one has r = infinity: B2 = E,
+    D2 = 0, a first-order row.  Everything else is multistep_table's."""
+    alpha, hat = np.asarray(alpha, dtype=np.float64), np.asarray(hat, dtype=np.float64)
+    n = len(alpha) - 1
+    if (n < 1 or len(hat) != n + 1 or hat[-1] != 0.0 or not (hat[:-1] > 0).all() or not (alpha[1:] > 0).all()
+            or alpha[0] < 0 or not (np.diff(hat) < 0).all()):
+        raise ValueError("(alpha, sigma_hat) must fall strictly in sigma_hat to a final (alpha > 0, 0)")
+    tab = np.zeros((n, 8), dtype=np.float64)
+    lam = [np.log(a / s) if a > 0 else None for a, s in zip(alpha[:-1], hat[:-1])]
+    for i in range(n):
+        tab[i, 0], tab[i, 1], tab[i, 6] = alpha[i], -hat[i], 1.0
+        if i == n - 1:
+            tab[i, 2:6] = (0.0, 1.0, 1.0, 0.0)
+            continue
+        E = alpha[i + 1] if lam[i] is None else -alpha[i + 1] * np.expm1(-(lam[i + 1] - lam[i]))
+        tab[i, 2:6] = (hat[i + 1] / hat[i], E, E, 0.0)
+        if i > 0 and lam[i - 1] is not None:
+            r = (lam[i] - lam[i - 1]) / (lam[i + 1] - lam[i])
+            tab[i, 4:6] = (E * (1.0 + 1.0 / (2.0 * r)), -E / (2.0 * r))
+    return tab
+
+
+PREDICTION_TYPES = ("epsilon", "v_prediction")
+
+
 class Schedule:
     """What one (kind, n_steps, spacing) needs: `timesteps` int64 [n]; `sigmas` float64 [n + 1] (euler kinds; ends in
     0); `coef` FP32 [n, 4] = (a, b, c, s_next), computed in float64; `t_table` FP32 [n + 1] (the
@@ -177,17 +220,47 @@ class Schedule:
 
     'ddim' (diffusers' DDIMScheduler as Stable Diffusion configures it: eta 0, set_alpha_to_one False) is one more
     [n, 4] table.  'dpmpp_2m' (`karras`: the rho = 7 sigma ladder in place of a spacing) is the one kind of `order` 2:
-    `coef` is FP32 [n, 8], `multistep_table(sigmas)` rounded, for mixdq_sampler_step_2m; `sigmas` float64 [n + 1]."""
+    `coef` is FP32 [n, 8], `multistep_table(sigmas)` rounded, for mixdq_sampler_step_2m; `sigmas` float64 [n + 1].
 
-    def __init__(self, kind, n_steps, spacing=None, karras=False):
+    prediction_type 'v_prediction' (SD 2.x-768 and the v-prediction fine-tunes): the model returns v = sqrt(ac) * eps -
+    sqrt(1 - ac) * x0.  eps = sqrt(1 - ac) * x_vp + sqrt(ac) * v is affine in (state, model output) as every update
+    here is, so it folds into the same tables -- only (a, b), or (u, v) of 'dpmpp_2m', differ; the kernels, start(),
+    blend and the scales do not.  zero_snr (with 'v_prediction', 'ddim' or 'dpmpp_2m' without karras, and trailing
+    spacing only): the betas go through rescale_betas_zero_snr, the first step sits at ac == 0 -- pure noise, start(0)
+    == (0, 1, 1) -- and `sigmas` is None ('dpmpp_2m' keeps (alpha, sigma_hat) per step in `vp`; its second row is
+    first-order, multistep_table_vp)."""
+
+    def __init__(self, kind, n_steps, spacing=None, karras=False, prediction_type="epsilon", zero_snr=False):
+        if prediction_type not in PREDICTION_TYPES:
+            raise ValueError(f"prediction_type must be one of {PREDICTION_TYPES}, not {prediction_type!r}")
+        vpred = prediction_type == "v_prediction"
+        if zero_snr:
+            if not vpred:
+                raise ValueError("zero_snr needs prediction_type='v_prediction': at ac == 0 the state carries no "
+                                 "signal and an epsilon prediction divides by sqrt(ac)")
+            if kind not in VP_KINDS or karras:
+                raise ValueError("zero_snr needs a state kept in VP space ('ddim', or 'dpmpp_2m' without karras): a "
+                                 "sigma-space state is infinite at ac == 0")
+            if spacing != "trailing":
+                raise ValueError("zero_snr needs spacing='trailing': only then does the first step sit at ac == 0")
         self.kind, self.n_steps = kind, int(n_steps)
+        self.prediction_type, self.zero_snr = prediction_type, bool(zero_snr)
         self.timesteps = ts = timesteps(kind, n_steps, spacing, karras)
         self.order = 2 if kind == "dpmpp_2m" else 1
-        ac = alphas_cumprod()
+        self.vp = None
+        ac = alphas_cumprod(zero_snr) if zero_snr else alphas_cumprod()
         coef = np.zeros((n_steps, 4), dtype=np.float64)
-        if kind == "dpmpp_2m":
+        if kind == "dpmpp_2m" and zero_snr:
+            self.sigmas = None
+            self.vp = (np.concatenate([np.sqrt(ac[ts]), [1.0]]), np.concatenate([np.sqrt(1.0 - ac[ts]), [0.0]]))
+            coef = multistep_table_vp(*self.vp)
+            self.init_scale, self.input_scale0 = 1.0, 1.0
+        elif kind == "dpmpp_2m":
             self.sigmas = np.concatenate([karras_sigmas(n_steps) if karras else np.sqrt((1.0 - ac[ts]) / ac[ts]), [0.0]])
             coef = multistep_table(self.sigmas)
+            if vpred:                               # x0 = alpha x - sigma_hat v; the rest of the table is unchanged
+                alpha = 1.0 / np.sqrt(self.sigmas[:-1] ** 2 + 1.0)
+                coef[:, 0], coef[:, 1] = alpha, -self.sigmas[:-1] * alpha
             self.init_scale, self.input_scale0 = 1.0, 1.0
         elif kind == "ddim":
             self.sigmas = None
@@ -200,6 +273,10 @@ class Schedule:
                 ac_prev = ac[prev] if prev >= 0 else ac[0]          # set_alpha_to_one False: the final alpha is ac[0]
                 sa, s1a, sp = np.sqrt(ac[t]), np.sqrt(1.0 - ac[t]), np.sqrt(ac_prev)
                 # x0 = (x - s1a e) / sa;  x' = sp x0 + sqrt(1 - ac_prev) e
+                if vpred:                           # ... with e = s1a x + sa v: nothing is divided by sa
+                    sq = np.sqrt(1.0 - ac_prev)
+                    coef[i] = (sp * sa + sq * s1a, sq * sa - sp * s1a, 0.0, 1.0)
+                    continue
                 coef[i] = (sp / sa, np.sqrt(1.0 - ac_prev) - sp * s1a / sa, 0.0, 1.0)
             self.init_scale, self.input_scale0 = 1.0, 1.0
         elif kind == "lcm":
@@ -213,6 +290,8 @@ class Schedule:
                 # x0 = (x - s1a e) / sa;  den = c_out x0 + c_skip x;  x' = sp den + sqrt(1 - ac_prev) n
                 coef[i] = (sp * (c_out / sa + c_skip), -sp * c_out * s1a / sa,
                            0.0 if last else np.sqrt(1.0 - ac[ts[i + 1]]), 1.0)
+                if vpred:                           # x0 = sa x - s1a v
+                    coef[i, :2] = (sp * (c_out * sa + c_skip), -sp * c_out * s1a)
             self.init_scale, self.input_scale0 = 1.0, 1.0
         else:
             sig = np.concatenate([np.sqrt((1.0 - ac[ts]) / ac[ts]), [0.0]])
@@ -225,8 +304,12 @@ class Schedule:
                     coef[i] = (1.0, down - s0, up, 1.0 / np.sqrt(s1 ** 2 + 1.0))
                 else:
                     coef[i] = (1.0, s1 - s0, 0.0, 1.0 / np.sqrt(s1 ** 2 + 1.0))
+                if vpred:                           # e = s0 / (s0^2 + 1) x + v / sqrt(s0^2 + 1), x the sigma-space state
+                    delta = coef[i, 1]
+                    coef[i, :2] = (1.0 + delta * s0 / (s0 ** 2 + 1.0), delta / np.sqrt(s0 ** 2 + 1.0))
             self.init_scale = float(np.sqrt(sig[0] ** 2 + 1.0)) if kind == "euler_ancestral" else float(sig[0])
             self.input_scale0 = float(1.0 / np.sqrt(sig[0] ** 2 + 1.0))
+        self.coef64 = coef                      # the table before its FP32 rounding (tests compare it in float64)
         self.coef = coef.astype(np.float32)
         self.t_table = np.concatenate([ts.astype(np.float64), [0.0]]).astype(np.float32)
         self.uses_noise = self.order == 1 and bool((self.coef[:, 2] != 0).any())
@@ -241,8 +324,10 @@ class Schedule:
         if not 0 <= t0 < self.n_steps:
             raise ValueError(f"t0 must be in [0, {self.n_steps}), not {t0}")
         if self.kind in ("lcm", "ddim"):
-            ac = alphas_cumprod()[self.timesteps[t0]]
+            ac = (alphas_cumprod(True) if self.zero_snr else alphas_cumprod())[self.timesteps[t0]]
             return float(np.sqrt(ac)), float(np.sqrt(1.0 - ac)), 1.0
+        if self.vp is not None:
+            return float(self.vp[0][t0]), float(self.vp[1][t0]), 1.0
         sig = self.sigmas[t0]
         if self.kind == "dpmpp_2m":
             alpha = 1.0 / np.sqrt(sig ** 2 + 1.0)
@@ -250,8 +335,8 @@ class Schedule:
         return 1.0, float(sig), float(1.0 / np.sqrt(sig ** 2 + 1.0))
 
 
-def schedule(kind, n_steps, spacing=None, karras=False) -> Schedule:
-    return Schedule(kind, n_steps, spacing, karras)
+def schedule(kind, n_steps, spacing=None, karras=False, prediction_type="epsilon", zero_snr=False) -> Schedule:
+    return Schedule(kind, n_steps, spacing, karras, prediction_type, zero_snr)
 
 
 def seed_tensor(seed, B, device):
@@ -304,16 +389,32 @@ class Sampler:
     InstructPix2Pix order, cat([prompt, negative, negative]): B rows with text + image, B with the image only, B with
     neither -- NOT the two-row order, where the unconditional rows come first.  `cond` follows the same blocks
     (_C.ip2p_cond).  Every captured graph then records mixdq_sampler_step3 with both scales:
-    e = e_u + guidance_scale * (e_t - e_i) + image_guidance_scale * (e_i - e_u)."""
+    e = e_u + guidance_scale * (e_t - e_i) + image_guidance_scale * (e_i - e_u).
+
+    prediction_type / zero_snr: Schedule's keywords -- 'v_prediction' for SD 2.x-768 and the v-prediction fine-tunes
+    (other numbers in the same tables: no kernel differs), zero_snr with it for checkpoints trained on
+    rescale_betas_zero_snr ('ddim' or 'dpmpp_2m', spacing='trailing').  guidance_rescale (phi in [0, 1]; diffusers'
+    argument of that name, Lin et al. 2023): with a value > 0 every captured graph records mixdq_sampler_step_rescaled in
+    the place of the bindings above -- per image the guided output is multiplied by 1 + phi * (std(text-conditioned
+    output) / std(guided output) - 1) over all C * H * W elements (1 where a standard deviation is 0) before the
+    update; its workspace is one more static buffer.  It needs two or three rows per image (one row: ValueError).  With
+    0, exactly the bindings above are recorded."""
 
     def __init__(self, unet, kind, n_steps, guidance_scale=0.0, spacing=None, karras=False, *,
-                 image_guidance_scale=None):
+                 image_guidance_scale=None, prediction_type="epsilon", zero_snr=False, guidance_rescale=0.0):
         self.unet = unet
-        self.schedule = Schedule(kind, n_steps, spacing, karras)
+        self.schedule = Schedule(kind, n_steps, spacing, karras, prediction_type, zero_snr)
         self.kind, self.n_steps = kind, int(n_steps)
         self.guidance_scale = float(guidance_scale)
         self.image_guidance_scale = None if image_guidance_scale is None else float(image_guidance_scale)
         self.rows_per_image = 3 if image_guidance_scale is not None else 2 if self.guidance_scale > 1.0 else 1
+        self.guidance_rescale = float(guidance_rescale)
+        if not 0.0 <= self.guidance_rescale <= 1.0:
+            raise ValueError(f"guidance_rescale must be in [0, 1], not {guidance_rescale!r}")
+        if self.guidance_rescale > 0.0 and self.rows_per_image == 1:
+            raise ValueError("guidance_rescale compares the guided output with the text-conditioned one: it needs "
+                             "guidance (guidance_scale > 1 or image_guidance_scale), and this Sampler runs one row per "
+                             "image")
         self._graph = None
         self._graph_masked = None
         self._graph_rng = None
@@ -345,6 +446,9 @@ class Sampler:
         if sch.order == 2:            # the multistep state: the previous step's x0, and where this run started
             self._hist = nhwc(B, dtype=torch.float32)
             self._first = torch.zeros(1, dtype=torch.int32, device=dev)
+        if self.guidance_rescale > 0.0:   # the chunk statistics of mixdq_sampler_step_rescaled: one more static buffer
+            from mixdq_amd import _C
+            self._rescale_ws = _C.sampler_rescale_workspace(B * C * H * W, C * H * W, dev)
         self._init_scale = torch.tensor(sch.init_scale, dtype=torch.float32, device=dev)
         self._input_scale0 = torch.tensor(sch.input_scale0, dtype=torch.float32, device=dev)
         self._ehs, self._added = _clone_args((encoder_hidden_states, added_cond_kwargs))
@@ -371,10 +475,15 @@ class Sampler:
         # the binding and its operands behind (x, eps): chosen once, here, not inside one_step
         blend = (self._z, self._noise0, self._mask, self._blend) if masked else ()
         kw = dict(channels=C, n=n) if masked else dict(n=n)
-        if self.rows_per_image == 3:  # one binding for every mode: the operands of a mode that is off stay None
+        if self.rows_per_image == 3 or self.guidance_rescale > 0.0:
+            # one binding for every mode: the operands of a mode that is off stay None
             step_fn = _C.sampler_step3
             tail = (self._in, self._coef, self._t_table, self._step, self._t, self.guidance_scale,
                     self.image_guidance_scale)
+            if self.guidance_rescale > 0.0:
+                step_fn = _C.sampler_step_rescaled
+                tail += (self.guidance_rescale, self._rescale_ws)
+                kw.update(rows_per_image=self.rows_per_image, n_image=C * H * W)
             if masked:
                 kw.update(z=self._z, noise0=self._noise0, mask=self._mask, blend=self._blend)
             if self.schedule.order == 2:
@@ -393,6 +502,7 @@ class Sampler:
                     self.rows_per_image, None if rng else self._noise)
             if rng:
                 kw.update(seeds=self._seeds, n_image=C * H * W)
+        self._step_binding = step_fn.__name__       # (the binding the last capture recorded: tests read it)
 
         cond_kw = {} if self._cond_term is None else {"cond_term": self._cond_term}
 

@@ -31,7 +31,14 @@ CLIP_L_CONFIG = dict(hidden_size=768, num_hidden_layers=12, num_attention_heads=
 OPENCLIP_BIGG_CONFIG = dict(hidden_size=1280, num_hidden_layers=32, num_attention_heads=20, intermediate_size=5120,
                             hidden_act="gelu", projection_dim=1280, vocab_size=49408, max_position_embeddings=77,
                             layer_norm_eps=1e-5)
-HEAD_DIM = 64                   # both encoders; the width MIXDQ_FLAG_CAUSAL is built for
+# SD 2.x's encoder: OpenCLIP ViT-H/14's text tower (hidden 1024, 16 heads, intermediate 4096, GELU).  The tower has 24
+# layers and SD 2.x conditions on final_layer_norm of the PENULTIMATE one's output; the checkpoints ship that as a
+# CLIPTextModel without the last layer (num_hidden_layers 23), so `last_hidden_state` -- encode_sd15 -- is the
+# conditioning [B, T, 1024] mixdq_amd.unet.SD21_CONFIG reads.  Configuration alone: no code knows about it.
+OPENCLIP_H_CONFIG = dict(hidden_size=1024, num_hidden_layers=23, num_attention_heads=16, intermediate_size=4096,
+                         hidden_act="gelu", projection_dim=None, vocab_size=49408, max_position_embeddings=77,
+                         layer_norm_eps=1e-5)
+HEAD_DIM = 64                   # every encoder here; the width MIXDQ_FLAG_CAUSAL is built for
 ACTIVATIONS = ("gelu", "quick_gelu")
 
 TextEncoderOutput = namedtuple("TextEncoderOutput", ["last_hidden_state", "penultimate", "pooled"])

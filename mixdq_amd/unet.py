@@ -416,6 +416,15 @@ SD15_CONFIG = dict(
     norm_num_groups=32,
 )
 
+# The SD 2.x UNet (stable-diffusion-2-1, the 768-px v-prediction model; the 512-px base model is the same network):
+# SD 1.5's four levels and depths, but heads of 64 columns at every level (5 / 10 / 20 / 20 of them) instead of eight
+# heads, OpenCLIP-H's 1024-wide text states, and Linear proj_in / proj_out.  Nothing in it is new to the kernels: head
+# width 64 is SDXL's, and cross_attention_dim 1024 is one more K of the to_k / to_v GEMMs (K % 32 == 0, like 768 and
+# 2048: every launch form takes it, no fallback).  865 910 724 parameters.  Run it with
+# Sampler(..., prediction_type="v_prediction") (mixdq_amd/sampler.py).
+SD21_CONFIG = dict(SD15_CONFIG, head_dim=64, num_attention_heads=None, cross_attention_dim=1024,
+                   use_linear_projection=True)
+
 # The inpainting checkpoints (stable-diffusion-xl-1.0-inpainting-0.1, stable-diffusion-inpainting): the same networks
 # with a 9-channel conv_in, whose input is cat([scaled latents (4), latent-resolution mask (1), latents of the image
 # with the masked pixels blanked (4)]).  The five conditioning channels are constant over a run: SDXLUNet.cond_term.
