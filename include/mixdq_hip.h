@@ -898,6 +898,46 @@ int mixdq_sampler_step_rescaled(float* x, const void* eps_f16, void* in_f16, con
                                 const float* z, const float* noise0, const float* mask, int channels,
                                 const float* blend, mixdq_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * ControlNet glue (csrc/control.hip).  No reference counterpart: the reference's UNet wrapper passes diffusers'
+ * down_block_additional_residuals / mid_block_additional_residual through.
+ *
+ * mixdq_control_add_f16: every skip tensor of a UNet (the mid-block output included) plus the scaled residuals of K
+ * ControlNets, in ONE launch.  S segments (1..16), K nets (1..4); segment i has n[i] FP16 elements, skip[i], dst[i] and
+ * the residuals residuals[k * S + i] of net k.  skip, dst, residuals and n are HOST arrays, read during the call: the
+ * descriptors travel in the kernel arguments, so a captured graph holds them and nothing is copied to the device.
+ * scales: FP32 [K, n_steps] on the device; step: the int32 on the device that mixdq_sampler_step* advances, read by the
+ * kernel.  With c_k = scales[k * n_steps + *step], element e of segment i (include/mixdq_math.h, mixdq_control_*):
+ *   t_k = f16_rn(f32(r_k[e]) * c_k), nets in the order k = 0 .. K-1, a net with c_k == 0 skipped and its residual not read
+ *   acc = t_first;  acc = f16_rn(f32(acc) + f32(t_k)) for each later net
+ *   dst[e] = f16_rn(f32(skip[e]) + f32(acc));   every net skipped: dst[e] = skip[e]'s own bits
+ * -- diffusers' ControlNetModel / MultiControlNetModel / UNet arithmetic on FP16 tensors, except that a scale of exactly
+ * 0 skips the net where diffusers computes r * 0 (different only for a non-finite r and in the sign of a zero).  *step
+ * outside [0, n_steps) reads every scale as 0: dst = skip.  dst is always written; dst[i] may be skip[i] itself.
+ * Grid: exactly sum(ceil(n[i] / mixdq_control_chunk())) workgroups of 256 lanes; 16-byte accesses.
+ * Errors, before any launch: S or K out of range, n_steps < 1, a null array, scales or step, n[i] < 0, a null pointer of
+ * a segment with n[i] > 0: MIXDQ_ERR_INVALID_ARG; n[i] % 8 != 0, a segment pointer not 16-byte or scales / step not
+ * 4-byte aligned: MIXDQ_ERR_ALIGNMENT.  A segment with n[i] == 0 contributes no workgroup (its pointers are not looked
+ * at); all empty: nothing is launched.
+ *
+ * mixdq_silu_f16: out[e] = f16_rn(mixdq_siluf(f32(x[e]))), n elements; out may be x.  n % 8 == 0 and 16-byte aligned
+ * pointers (MIXDQ_ERR_ALIGNMENT otherwise); n < 0, null pointers: MIXDQ_ERR_INVALID_ARG; n == 0 writes nothing.  Grid:
+ * exactly ceil(n / 2048) workgroups of 256 lanes.
+ *
+ * mixdq_hint_to_nhwc8_f16: a ControlNet's image ingest -- mixdq_image_to_nhwc8_f16's interface, layouts and errors,
+ * with the [0, 1] rule:
+ *   uint8:  f16_rn(f32(u) / 255.0f)        the division correctly rounded: image.float() / 255, then .half()
+ *   float:  f16_rn(f32(v))                 no clamp
+ * Grid: exactly ceil(B * H * W / 256) workgroups of 256 lanes, one pixel and one 16-byte store per lane. */
+#define MIXDQ_CONTROL_MAX_SEGMENTS 16
+#define MIXDQ_CONTROL_MAX_NETS 4
+int mixdq_control_chunk(void);
+int mixdq_control_add_f16(const void* const* skip, void* const* dst, const void* const* residuals, const int64_t* n,
+                          int S, int K, const float* scales, int n_steps, const int* step, mixdq_stream_t stream);
+int mixdq_silu_f16(const void* x_f16, void* out_f16, int64_t n, mixdq_stream_t stream);
+int mixdq_hint_to_nhwc8_f16(const void* img, int dtype, int64_t sb, int64_t sc, int64_t sh, int64_t sw, void* out_f16,
+                            int B, int C, int H, int W, mixdq_stream_t stream);
+
 /* Which kernel instantiation mixdq_qlinear_w8a8 / mixdq_qconv2d_w8a8 will launch for a problem of
  * M rows x N output channels (k_align = K for Linear, C for Conv2d; k_total = K or R*S*C): the block tile BM x BN x BK
  * and LDS stage count of `igemm_kernel<BM,BN,BK,STAGES,CONV>`, or zeros for the small-alignment

@@ -408,4 +408,23 @@ MIXDQ_HD float mixdq_rescale_factor(float m2_t, float m2_e, float phi, int64_t n
 
 MIXDQ_HD float mixdq_sampler_rescaled(float e, float r) { return MIXDQ_MUL_RN(e, r); }
 
+/* ---- ControlNet residuals (mixdq_control_add_f16, csrc/control.hip), same rule: diffusers' arithmetic on FP16 tensors,
+ * every operation one FP32 rounding of exact FP16 operands followed by the FP16 rounding the caller applies
+ * (f32_to_f16_rn on the device, a cast on the host).  For one element, skip s, the residuals r_k of nets k = 0 .. K-1 in
+ * order, and their FP32 scales c_k of this step:
+ *   t_k = f16_rn(f32(r_k) * c_k)                 ControlNetModel: sample * conditioning_scale
+ *   acc = t_first;  acc = f16_rn(f32(acc) + f32(t_k)) for each later net        MultiControlNetModel, left to right
+ *   out = f16_rn(f32(s) + f32(acc))              the UNet's skip + residual
+ * A net whose c_k == 0 (either sign) is SKIPPED, its residual not read (diffusers multiplies by 0: the two differ for a
+ * non-finite r_k and in the sign of a zero); with every net skipped out is s's own bits.  mixdq_control_scaled and
+ * mixdq_control_sum are the two FP32 operations. */
+MIXDQ_HD float mixdq_control_scaled(float r, float c) { return MIXDQ_MUL_RN(r, c); }
+
+MIXDQ_HD float mixdq_control_sum(float a, float b) { return MIXDQ_ADD_RN(a, b); }
+
+/* ---- ControlNet hint ingest (mixdq_hint_to_nhwc8_f16, csrc/control.hip): a uint8 pixel on the [0, 1] scale, the FP32
+ * value whose FP16 rounding the conditioning embedding reads: f32(u) / 255.0f, the division correctly rounded -- what
+ * image.float() / 255 computes. */
+MIXDQ_HD float mixdq_hint_unit(uint32_t u) { return MIXDQ_DIV_RN((float)u, 255.0f); }
+
 #endif /* MIXDQ_MATH_H_ */

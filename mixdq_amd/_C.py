@@ -1751,6 +1751,120 @@ def image_to_nhwc8_f16(image, mask=None):
     return out.permute(0, 3, 1, 2)
 
 
+_lib.mixdq_control_chunk.restype = _i32
+_lib.mixdq_control_add_f16.argtypes = [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp]
+_lib.mixdq_control_add_f16.restype = _i32
+_lib.mixdq_silu_f16.argtypes = [_vp, _vp, _i64, _vp]
+_lib.mixdq_silu_f16.restype = _i32
+_lib.mixdq_hint_to_nhwc8_f16.argtypes = [_vp, _i32, _i64, _i64, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _vp]
+_lib.mixdq_hint_to_nhwc8_f16.restype = _i32
+CONTROL_CHUNK = _lib.mixdq_control_chunk()
+CONTROL_MAX_SEGMENTS, CONTROL_MAX_NETS = 16, 4                            # include/mixdq_hip.h MIXDQ_CONTROL_MAX_*
+
+
+def _dense_f16(t, what):
+    """`t` is an fp16 GPU tensor whose elements occupy one dense run of memory (contiguous or channels-last)."""
+    _check(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float16, f"{what} should be an fp16 GPU tensor")
+    _check(t.is_contiguous() or (t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last)),
+           f"{what} should be dense (contiguous or channels-last)")
+
+
+def _same_layout(a, b) -> bool:
+    """Two dense tensors of one shape whose elements lie in memory in the same order."""
+    if a.shape != b.shape:
+        return False
+    if a.is_contiguous() and b.is_contiguous():
+        return True
+    cl = torch.channels_last
+    return a.dim() == 4 and a.is_contiguous(memory_format=cl) and b.is_contiguous(memory_format=cl)
+
+
+def control_add(skips, residuals, scales, step, out=None):
+    """Every skip tensor of a UNet plus the scaled residuals of K ControlNets, one launch (mixdq_control_add_f16).
+    skips: S <= 16 fp16 tensors; residuals: K <= 4 lists of S fp16 tensors, residuals[k][i] of skips[i]'s shape AND
+    strides (the operation is elementwise over storage); scales: fp32 [K, n_steps] on the device; step: the int32
+    device tensor sampler_step* advances.  With c_k = scales[k, step]:
+    out[i] = f16(skips[i] + (f16(r_0 * c_0) + f16(r_1 * c_1) + ...)), the sum left to right in fp16; a net whose c_k is 0
+    is skipped and its residuals are not read; a step outside [0, n_steps) skips every net (out = skips).
+    out: None (fresh tensors), or S tensors like the skips -- out[i] may be skips[i] itself.  Returns the list."""
+    what = "control_add"
+    _check(isinstance(skips, (list, tuple)) and 1 <= len(skips) <= CONTROL_MAX_SEGMENTS,
+           f"{what}: skips should be a list of 1 to {CONTROL_MAX_SEGMENTS} tensors")
+    _check(isinstance(residuals, (list, tuple)) and 1 <= len(residuals) <= CONTROL_MAX_NETS,
+           f"{what}: residuals should be a list of 1 to {CONTROL_MAX_NETS} lists (one per net)")
+    S, K = len(skips), len(residuals)
+    dev = skips[0].device if torch.is_tensor(skips[0]) else None
+    for i, s in enumerate(skips):
+        _dense_f16(s, f"{what}: skips[{i}]")
+        _check(s.device == dev, f"{what}: skips[{i}] is on another device")
+        _check(s.numel() % 8 == 0 and s.data_ptr() % 16 == 0, f"{what}: skips[{i}] should have a multiple of 8 elements "
+               "and be 16-byte aligned")
+    for k, net in enumerate(residuals):
+        _check(isinstance(net, (list, tuple)) and len(net) == S, f"{what}: residuals[{k}] should hold {S} tensors, one per "
+               "skip")
+        for i, r in enumerate(net):
+            _dense_f16(r, f"{what}: residuals[{k}][{i}]")
+            _check(r.device == dev and _same_layout(r, skips[i]),
+                   f"{what}: residuals[{k}][{i}] should have the shape {tuple(skips[i].shape)}, the memory format and the "
+                   f"device of skips[{i}], got {tuple(r.shape)}")
+            _check(r.data_ptr() % 16 == 0, f"{what}: residuals[{k}][{i}] should be 16-byte aligned")
+    _check(torch.is_tensor(scales) and scales.is_cuda and scales.device == dev and scales.dtype == torch.float32
+           and scales.dim() == 2 and scales.shape[0] == K and scales.shape[1] >= 1 and scales.is_contiguous(),
+           f"{what}: scales should be a contiguous fp32 [{K}, n_steps] tensor on the skips' device")
+    _check(torch.is_tensor(step) and step.device == dev and step.dtype == torch.int32 and step.numel() == 1,
+           f"{what}: step should be one int32 on the skips' device")
+    if out is None:
+        out = [torch.empty_like(s) for s in skips]       # (preserve_format: the skips' strides)
+    else:
+        _check(isinstance(out, (list, tuple)) and len(out) == S, f"{what}: out should hold {S} tensors")
+        for i, o in enumerate(out):
+            _dense_f16(o, f"{what}: out[{i}]")
+            _check(o.device == dev and _same_layout(o, skips[i]) and o.data_ptr() % 16 == 0,
+                   f"{what}: out[{i}] should be like skips[{i}]")
+    ptrs = lambda ts: (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])        # noqa: E731
+    with torch.cuda.device(dev):
+        code = _lib.mixdq_control_add_f16(ptrs(skips), ptrs(out), ptrs([r for net in residuals for r in net]),
+                                          _i64arr([s.numel() for s in skips]), S, K, scales.data_ptr(), scales.shape[1],
+                                          step.data_ptr(), _stream())
+    _status(code, what)
+    return list(out)
+
+
+def silu_f16(x, out=None):
+    """SiLU on a dense fp16 GPU tensor (mixdq_silu_f16): f16(x / (1 + exp(-x))) on the fp32 value of every element,
+    include/mixdq_math.h mixdq_siluf.  out: None (a fresh tensor like x) or a tensor like x -- x itself runs in place."""
+    _dense_f16(x, "silu_f16: x")
+    _check(x.numel() % 8 == 0 and x.data_ptr() % 16 == 0, "silu_f16: x should have a multiple of 8 elements and be "
+           "16-byte aligned")
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        _dense_f16(out, "silu_f16: out")
+        _check(out.device == x.device and _same_layout(out, x) and out.data_ptr() % 16 == 0,
+               "silu_f16: out should be like x")
+    with torch.cuda.device(x.device):
+        code = _lib.mixdq_silu_f16(x.data_ptr(), out.data_ptr(), x.numel(), _stream())
+    _status(code, "silu_f16")
+    return out
+
+
+def hint_to_nhwc8_f16(image):
+    """A ControlNet's image ingest (mixdq_hint_to_nhwc8_f16): image [B, C <= 8, H, W], uint8, fp16 or fp32, of ANY
+    strides -> fp16 [B, 8, H, W] in channels-last storage, channels C..7 zero.  uint8: f16(f32(u) / 255), what
+    image.float().div(255).half() gives; floats: f16(v), no clamp."""
+    _check(torch.is_tensor(image) and image.is_cuda and image.dim() == 4 and image.dtype in IMAGE_DTYPES,
+           "hint_to_nhwc8_f16: image should be a 4-D uint8, fp16 or fp32 GPU tensor")
+    B, C, H, W = image.shape
+    _check(1 <= C <= 8, "hint_to_nhwc8_f16: image should have 1 to 8 channels")
+    out = torch.empty((B, H, W, 8), dtype=torch.float16, device=image.device)
+    sb, sc, sh, sw = image.stride()
+    with torch.cuda.device(image.device):
+        code = _lib.mixdq_hint_to_nhwc8_f16(image.data_ptr(), IMAGE_DTYPES[image.dtype], sb, sc, sh, sw, out.data_ptr(),
+                                            B, C, H, W, _stream())
+    _status(code, "hint_to_nhwc8_f16")
+    return out.permute(0, 3, 1, 2)
+
+
 def vae_latent_sample(moments, noise=None, scaling_factor=1.0):
     """The posterior sample of an AutoencoderKL (mixdq_vae_latent_sample): moments fp16 [B, 2L, h, w] in
     channels-last storage (channels 0..L-1 the mean, L..2L-1 the log-variance), noise fp32 [B, L, h, w]

@@ -16,6 +16,8 @@ SOURCES = ["quantize.hip", "igemm.hip", "igemm_aq.hip", "igemm_ln.hip", "iconv.h
 # Units added behind a recorded kernel set: their objects go to _obj/ext/, so that what the objects directly inside
 # _obj/ register stays what tests/golden/launch_trace.json lists; they are linked into the same library.
 EXT_SOURCES = ["sampler_rescale.hip"]
+# ... and behind the recorded kernel set of _obj/ plus _obj/ext/ (tests/golden/launch_trace_rescale.json): _obj/ext2/.
+EXT2_SOURCES = ["control.hip"]
 HEADERS = ["common.h", "attn_core.h", "iconv.h", "igemm_kernel.h", "igemm_pp.h", "f16in_table.h", "sampler_step.h", os.path.join("..", "..", "include", "mixdq_hip.h"),
            os.path.join("..", "..", "include", "mixdq_math.h")]
 # -ffp-contract=off: every fused multiply-add in the arithmetic specification is written
@@ -36,6 +38,7 @@ EXTRA = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
          "igemm_ln.hip": ["-mllvm", "-amdgpu-kernarg-preload-count=14"]}
 OBJ = os.path.join(PKG, "_obj")
 OBJ_EXT = os.path.join(OBJ, "ext")
+OBJ_EXT2 = os.path.join(OBJ, "ext2")
 
 
 def _hipcc():
@@ -98,19 +101,21 @@ def needs_build() -> bool:
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, s) for s in SOURCES + EXT_SOURCES + HEADERS] + [os.path.abspath(__file__)]
+    deps = [os.path.join(CSRC, s) for s in SOURCES + EXT_SOURCES + EXT2_SOURCES + HEADERS] + [os.path.abspath(__file__)]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
     if force or needs_build():
         os.makedirs(OBJ_EXT, exist_ok=True)
+        os.makedirs(OBJ_EXT2, exist_ok=True)
         hdr_t = max(os.path.getmtime(os.path.join(CSRC, h)) for h in HEADERS)
         hdr_t = max(hdr_t, os.path.getmtime(os.path.abspath(__file__)))
         procs, objs = [], []
-        for src in SOURCES + EXT_SOURCES:
+        for src in SOURCES + EXT_SOURCES + EXT2_SOURCES:
             path = os.path.join(CSRC, src)
-            obj = os.path.join(OBJ_EXT if src in EXT_SOURCES else OBJ, src.replace(".hip", ".o"))
+            obj_dir = OBJ_EXT if src in EXT_SOURCES else OBJ_EXT2 if src in EXT2_SOURCES else OBJ
+            obj = os.path.join(obj_dir, src.replace(".hip", ".o"))
             objs.append(obj)
             if (not force and os.path.exists(obj)
                     and os.path.getmtime(obj) > max(hdr_t, os.path.getmtime(path))):

@@ -398,10 +398,20 @@ class Sampler:
     the place of the bindings above -- per image the guided output is multiplied by 1 + phi * (std(text-conditioned
     output) / std(guided output) - 1) over all C * H * W elements (1 where a standard deviation is 0) before the
     update; its workspace is one more static buffer.  It needs two or three rows per image (one row: ValueError).  With
-    0, exactly the bindings above are recorded."""
+    0, exactly the bindings above are recorded.
+
+    controlnet (a mixdq_amd.controlnet.ControlNet, or a list of up to 4): every captured graph then records, in this
+    order, each ControlNet's forward on the UNet's own static inputs, the UNet with control= (one mixdq_control_add_f16
+    launch over all skips, the scales read from a static [K, n_steps] table at the device-side step) and the step binding
+    it recorded before.  sample(control=, control_scale=, control_start=, control_end=) then REQUIRES control= and
+    rewrites the hint terms and the table per call, outside the graph: one graph per mode serves every scale and
+    guidance window.  A ControlNet's forward still runs while its window is closed (a captured graph cannot branch);
+    only its residuals' loads are saved.  Not with three rows per image (ValueError).  Without controlnet= a Sampler
+    captures exactly what it captured before, and refuses control=."""
 
     def __init__(self, unet, kind, n_steps, guidance_scale=0.0, spacing=None, karras=False, *,
-                 image_guidance_scale=None, prediction_type="epsilon", zero_snr=False, guidance_rescale=0.0):
+                 image_guidance_scale=None, prediction_type="epsilon", zero_snr=False, guidance_rescale=0.0,
+                 controlnet=None):
         self.unet = unet
         self.schedule = Schedule(kind, n_steps, spacing, karras, prediction_type, zero_snr)
         self.kind, self.n_steps = kind, int(n_steps)
@@ -423,6 +433,20 @@ class Sampler:
         self._start = None
         self._key = None
         self._cond_term = None        # the static [R, C0, h, w] conv_in term of a UNet with conditioning channels
+        self.controlnets = []
+        if controlnet is not None:
+            from mixdq_amd.controlnet import MAX_NETS, ControlNet
+            nets = list(controlnet) if isinstance(controlnet, (list, tuple)) else [controlnet]
+            if not nets or not all(isinstance(n, ControlNet) for n in nets):
+                raise TypeError("Sampler: controlnet should be a mixdq_amd.controlnet.ControlNet or a list of them")
+            if len(nets) > MAX_NETS:
+                raise ValueError(f"Sampler: at most {MAX_NETS} ControlNets, got {len(nets)}")
+            if self.rows_per_image == 3:
+                raise ValueError("Sampler: three guidance rows (image_guidance_scale) together with controlnet= are not "
+                                 "supported yet")
+            self.controlnets = nets
+        self._hint_terms = None       # per ControlNet the static [R, C0, h, w] hint term
+        self._ctl_scales = None       # the static [K, n_steps] table of conditioning scales
 
     # ---- static buffers + capture ---------------------------------------------------------------------------
     def _setup(self, noise, encoder_hidden_states, added_cond_kwargs):
@@ -505,9 +529,15 @@ class Sampler:
         self._step_binding = step_fn.__name__       # (the binding the last capture recorded: tests read it)
 
         cond_kw = {} if self._cond_term is None else {"cond_term": self._cond_term}
+        nets = [getattr(n.forward, "__wrapped__", n.forward) for n in self.controlnets]
 
         def one_step():
-            eps = forward(self._in, self._t, self._ehs, self._added, **cond_kw)[0]
+            ctl_kw = {}
+            if nets:                                # every ControlNet on the UNet's own inputs, then the UNet with control=
+                from mixdq_amd.unet import ControlResiduals
+                res = [f(self._in, self._t, self._ehs, self._added, hint_term=h) for f, h in zip(nets, self._hint_terms)]
+                ctl_kw["control"] = ControlResiduals(res, self._ctl_scales, self._step)
+            eps = forward(self._in, self._t, self._ehs, self._added, **cond_kw, **ctl_kw)[0]
             if (eps.dtype != torch.float16 or tuple(eps.shape) != tuple(self._in.shape)
                     or any(a != b for a, b, d in zip(eps.stride(), self._in.stride(), eps.shape) if d > 1)):
                 raise RuntimeError("Sampler: the UNet's output is not an FP16 tensor of its input's shape in channels-"
@@ -600,8 +630,64 @@ class Sampler:
             for r in range(self.rows_per_image):
                 self._cond_term[r * B:(r + 1) * B].copy_(term)
 
+    def _set_control(self, control, scale, start, end, noise, t0):
+        """sample(control=...): per ControlNet the hint term (an image goes through net.hint_term, which also re-derives
+        the 8-channel conv weights in place after a reload; a term is taken as it is) into its static [R, C0, h, w]
+        buffer, B rows repeated into every row block, and the [K, n_steps] scale table of this run
+        (controlnet.control_scale_table: diffusers' keep rule over the steps t0 .. n_steps - 1) into the static table --
+        copies in stream order, outside the graph, nothing read back."""
+        import torch
+        K = len(self.controlnets)
+        if K == 0:
+            if control is not None:
+                raise TypeError("Sampler.sample: control given, but this Sampler was built without controlnet=")
+            return
+        if control is None:
+            raise TypeError("Sampler.sample: this Sampler was built with controlnet=: control= (the hint image or "
+                            "hint_term of every ControlNet) is required")
+        from mixdq_amd.controlnet import control_scale_table
+        hints = list(control) if isinstance(control, (list, tuple)) else [control]
+        if len(hints) != K:
+            raise ValueError(f"Sampler.sample: control should bring one hint per ControlNet ({K}), got {len(hints)}")
+
+        def per_net(v, what):
+            vals = list(v) if isinstance(v, (list, tuple)) else [v] * K
+            if len(vals) != K:
+                raise ValueError(f"Sampler.sample: {what} should be a number or one per ControlNet ({K})")
+            return [float(x) for x in vals]
+        table = control_scale_table(self.n_steps, t0, per_net(scale, "control_scale"), per_net(start, "control_start"),
+                                    per_net(end, "control_end"))
+        B, _, H, W = noise.shape
+        R = B * self.rows_per_image
+        terms = []
+        for k, (net, hint) in enumerate(zip(self.controlnets, hints)):
+            c0 = net.conv_in.out_channels
+            if not (torch.is_tensor(hint) and hint.dim() == 4 and hint.device == noise.device and hint.shape[0] in (B, R)):
+                raise RuntimeError(f"Sampler.sample: control[{k}] should be a 4-D tensor of {B} or {R} rows on noise's "
+                                   "device: the hint image, or what hint_term(image) returned")
+            if hint.dtype == torch.float16 and tuple(hint.shape[1:]) == (c0, H, W):
+                term = hint
+            elif tuple(hint.shape[2:]) == (8 * H, 8 * W):
+                term = net.hint_term(hint)
+            else:
+                raise RuntimeError(f"Sampler.sample: control[{k}] should be a hint image [{B} or {R}, 3, {8 * H}, {8 * W}] "
+                                   f"or an FP16 hint term [{B} or {R}, {c0}, {H}, {W}]")
+            terms.append(term)
+        if self._hint_terms is None:
+            self._hint_terms = [torch.zeros((R, H, W, t.shape[1]), dtype=torch.float16,
+                                            device=noise.device).permute(0, 3, 1, 2) for t in terms]
+            self._ctl_scales = torch.zeros((K, self.n_steps), dtype=torch.float32, device=noise.device)
+        for buf, term in zip(self._hint_terms, terms):
+            if term.shape[0] == R:
+                buf.copy_(term)
+            else:
+                for r in range(self.rows_per_image):
+                    buf[r * B:(r + 1) * B].copy_(term)
+        self._ctl_scales.copy_(torch.from_numpy(table))
+
     def sample(self, noise, encoder_hidden_states, added_cond_kwargs=None, step_noise=None, *, init_latents=None,
-               strength=None, mask=None, seed=None, cond=None):
+               strength=None, mask=None, seed=None, cond=None, control=None, control_scale=1.0, control_start=0.0,
+               control_end=1.0):
         """noise [B, C, H, W] (unit variance; FP32 or FP16), encoder_hidden_states [R, T, D] FP16 (R = B, 2B
         under guidance, or 3B with image_guidance_scale), added_cond_kwargs as the UNet takes them (R rows), step_noise [n_steps, B, C, H, W]: the
         noise each stochastic step adds (required where the schedule has a non-zero c: euler_ancestral and lcm with
@@ -636,9 +722,20 @@ class Sampler:
         no concatenated 9-channel input exists, the graphs are the four above, and calls with different `cond` replay
         the same graph objects.  Orthogonal to init_latents / strength / mask / seed.  An 8-channel InstructPix2Pix
         UNet takes the image latents here: _C.ip2p_cond(enc.moments(image), rows=3) -- R rows, zero in the third block
-        (Sampler.instruct builds it)."""
+        (Sampler.instruct builds it).
+
+        `control` (required exactly when the Sampler was built with controlnet=): per ControlNet the hint image (uint8 /
+        FP16 / FP32 [B or R, 3, 8h, 8w] in [0, 1]; uint8: 0..255) or what its hint_term(image) returned; one tensor, or
+        a list with one per net.  `control_scale`, `control_start`, `control_end`: diffusers'
+        controlnet_conditioning_scale, control_guidance_start and control_guidance_end, numbers or one per net.  They
+        fill the static hint buffers and the scale table of this run; calls with other values replay the same graph
+        objects.  Orthogonal to everything above (`cond` composes: a ControlNet reads the latent channels)."""
         import torch
         from mixdq_amd.quantize_sdxl import _copy_into
+        if control is None and self.controlnets:
+            self._set_control(None, control_scale, control_start, control_end, None, 0)      # (raises)
+        if control is not None and not self.controlnets:
+            self._set_control(control, control_scale, control_start, control_end, None, 0)   # (raises)
         seeds = None
         if seed is not None:
             from mixdq_amd import _C
@@ -697,6 +794,7 @@ class Sampler:
         elif self._shape_key(noise, encoder_hidden_states, added_cond_kwargs) != self._key:
             raise RuntimeError("Sampler.sample: inputs differ in shape from those the step graph was captured for")
         self._set_cond(cond, noise)
+        self._set_control(control, control_scale, control_start, control_end, noise, t0)
         name = "_graph" + ("_masked" if mask is not None else "") + ("_rng" if rng else "")
         if getattr(self, name) is None:
             setattr(self, name, self._capture(noise, masked=mask is not None, rng=rng))
@@ -715,12 +813,14 @@ class Sampler:
         return self._x.clone()
 
     def sample_image(self, vae, noise, encoder_hidden_states, added_cond_kwargs=None, step_noise=None, *, seed=None,
-                     cond=None):
+                     cond=None, control=None, control_scale=1.0, control_start=0.0, control_end=1.0):
         """sample(), then `vae.decode` (a mixdq_amd.vae.VAEDecoder, eager or under hip_graph_opt) of its latents on
         the same stream: nothing waits for the GPU in between.  Returns (FP32 latents, FP16 image [B, 3, 8H, 8W]).
-        `seed` and `cond` as in sample(): with seed `noise` may be the latent shape, and seed -> image is this one
-        call."""
-        latents = self.sample(noise, encoder_hidden_states, added_cond_kwargs, step_noise, seed=seed, cond=cond)
+        `seed`, `cond` and `control*` as in sample(): with seed `noise` may be the latent shape, and seed -> image is
+        this one call."""
+        latents = self.sample(noise, encoder_hidden_states, added_cond_kwargs, step_noise, seed=seed, cond=cond,
+                              control=control, control_scale=control_scale, control_start=control_start,
+                              control_end=control_end)
         return latents, vae.decode(latents)
 
     def _latent_noise(self, latent_noise, latent_seed, noise, encoder_hidden_states, stream=None):
@@ -738,16 +838,18 @@ class Sampler:
                         _C.RNG_STREAM_VAE if stream is None else stream, 0)
 
     def img2img(self, enc, dec, image, noise, encoder_hidden_states, added_cond_kwargs=None, *, strength,
-                step_noise=None, latent_noise=None, seed=None, latent_seed=None, cond=None):
+                step_noise=None, latent_noise=None, seed=None, latent_seed=None, cond=None, control=None,
+                control_scale=1.0, control_start=0.0, control_end=1.0):
         """Image to image on one stream: `enc.encode(image, latent_noise)` (a mixdq_amd.vae.VAEEncoder; latent_noise
         None: the posterior's mode), sample(init_latents=that, strength=strength), then `dec.decode` (a VAEDecoder) --
         either VAE eager or under hip_graph_opt, nothing waits for the GPU in between.  noise: [B, C, H/8, W/8], what
         is added to the encoded image.  Returns (FP32 latents, FP16 image [B, 3, H, W]).  `seed` as in sample() (noise
         may then be the latent shape); it does not touch the posterior, which stays the mode unless `latent_noise` or
-        `latent_seed` (stream 2 of those seeds) is given.  `cond` as in sample()."""
+        `latent_seed` (stream 2 of those seeds) is given.  `cond` and `control*` as in sample()."""
         z = enc.encode(image, self._latent_noise(latent_noise, latent_seed, noise, encoder_hidden_states))
         latents = self.sample(noise, encoder_hidden_states, added_cond_kwargs, step_noise, init_latents=z,
-                              strength=strength, seed=seed, cond=cond)
+                              strength=strength, seed=seed, cond=cond, control=control, control_scale=control_scale,
+                              control_start=control_start, control_end=control_end)
         return latents, dec.decode(latents)
 
     def instruct(self, enc, dec, image, noise, encoder_hidden_states, added_cond_kwargs=None, *, step_noise=None,
@@ -822,7 +924,10 @@ class Sampler:
         (blend=False is refused there: nothing else would keep the image) and False for a 9-channel one, diffusers'
         behaviour: a plain loop or, with `strength`, an image-to-image one -- with strength None the init image is not
         even encoded.  blend=True on a 9-channel UNet runs the masked graph as well.  On the crop path the blanked
-        encode reads the resized window and the resized mask."""
+        encode reads the resized window and the resized mask.
+
+        A Sampler built with controlnet= is refused here (sample() asks for control=): the signatures of inpaint and
+        inpaint_ext are pinned; a masked ControlNet run is sample(mask=, init_latents=, control=)."""
         import torch
         from mixdq_amd import _C
         if composite and not (torch.is_tensor(image) and image.dtype == torch.uint8):
@@ -851,7 +956,8 @@ class Sampler:
         return latents, (_C.composite_u8(decoded, image, mask) if composite else decoded)
 
     def _inpaint_latents(self, enc, image, mask, noise, encoder_hidden_states, added_cond_kwargs, *, strength,
-                         step_noise, latent_noise, mask_mode, seed, latent_seed, blend, cond_latent_noise):
+                         step_noise, latent_noise, mask_mode, seed, latent_seed, blend, cond_latent_noise, control=None,
+                         control_scale=1.0, control_start=0.0, control_end=1.0):
         """The model-size part of inpaint(): the encodes, the latent mask, the conditioning, the loop."""
         from mixdq_amd import _C
         m = _C.mask_to_latent(mask, mask_mode)
@@ -864,7 +970,8 @@ class Sampler:
         if blend or strength is not None:           # (a plain 9-channel run never reads the init image's latents)
             z = enc.encode(image, self._latent_noise(latent_noise, latent_seed, noise, encoder_hidden_states))
         return self.sample(noise, encoder_hidden_states, added_cond_kwargs, step_noise, init_latents=z,
-                           strength=strength, mask=m if blend else None, seed=seed, cond=cond)
+                           strength=strength, mask=m if blend else None, seed=seed, cond=cond, control=control,
+                           control_scale=control_scale, control_start=control_start, control_end=control_end)
 
     def _inpaint_crop(self, enc, dec, image, mask, noise, encoder_hidden_states, added_cond_kwargs, *, composite, crop,
                       crop_pad, mask_blur, resample, **kw):

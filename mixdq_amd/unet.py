@@ -19,6 +19,7 @@ from __future__ import annotations
 
 import functools
 import math
+import os
 import weakref
 from collections import OrderedDict
 
@@ -55,6 +56,30 @@ class defused:
     def __exit__(self, *exc):
         global DEFUSE
         DEFUSE = self.saved
+
+
+# MIXDQ_CONTROL_ADD=0: the fused forward adds ControlNet residuals with torch half operations instead of the
+# control_add launch (A/B runs and tests; read once per process).  The torch form reads the scales of the step on the
+# host, so it cannot be captured into a graph.
+CONTROL_ADD = not os.environ.get("MIXDQ_CONTROL_ADD", "1").startswith("0")
+
+
+class ControlResiduals:
+    """What SDXLUNet.forward(control=...) adds to its skip tensors and to the mid-block output.
+
+    nets:   per ControlNet (1 to 4) the pair (down residuals, mid residual) as ControlNet.forward returns it, UNSCALED:
+            one tensor per skip of the UNet (conv_in's output first) and one for the mid-block output
+    scales: fp32 [K, n_steps] on the residuals' device: scales[k, j] is net k's conditioning scale at step j (0 while its
+            guidance window is closed: the net is then skipped)
+    step:   one int32 on that device, the step counter (the one the sampler step advances)
+
+    skip_i + (f16(r_0i * c_0) + f16(r_1i * c_1) + ...) in fp16, left to right -- diffusers' arithmetic; include/mixdq_math.h,
+    mixdq_control_*."""
+
+    def __init__(self, nets, scales, step):
+        self.nets = [(list(down), mid) for down, mid in nets]
+        self.scales = scales
+        self.step = step
 
 
 def _accel(m) -> bool:
@@ -1095,47 +1120,12 @@ class UpBlock(nn.Module):
         return x
 
 
-class SDXLUNet(nn.Module):
-    """forward(sample, timestep, encoder_hidden_states, added_cond_kwargs, return_dict=False)
-    -> (noise_pred,), the call shape of quantize_sdxl.py:375-385.  `cfg`: overrides of SDXL_CONFIG; SD15_CONFIG
-    makes it the SD 1.5 UNet (same classes, diffusers' names for that network)."""
-
-    def __init__(self, cfg=None):
-        super().__init__()
-        cfg = dict(SDXL_CONFIG, **(cfg or {}))
-        self.cfg = cfg
-        boc = cfg["block_out_channels"]
-        temb = cfg["time_embed_dim"]
-        self.conv_in = nn.Conv2d(cfg["in_channels"], boc[0], 3, 1, 1)
-        # input channels beyond the latents': 0, or the 5 (mask + masked-image latents) of an inpainting checkpoint
-        self.cond_channels = cfg["in_channels"] - cfg["out_channels"]
-        self.time_embedding = TimestepEmbedding(boc[0], temb)
-        if cfg.get("addition_embed_type", "text_time") is not None:
-            self.add_embedding = TimestepEmbedding(cfg["projection_class_embeddings_input_dim"], temb)
-        n = cfg["layers_per_block"]
-        depths = cfg["transformer_layers_per_block"]
-        self.down_blocks = nn.ModuleList()
-        skip = [boc[0]]
-        cin = boc[0]
-        for i, cout in enumerate(boc):
-            last = i == len(boc) - 1
-            self.down_blocks.append(DownBlock(cin, cout, temb, n, depths[i], cfg, not last))
-            skip += [cout] * n + ([] if last else [cout])
-            cin = cout
-        self.mid_block = MidBlock(boc[-1], temb, cfg["mid_transformer_layers"], cfg)
-        self.up_blocks = nn.ModuleList()
-        prev = boc[-1]
-        for i, cout in enumerate(reversed(boc)):
-            last = i == len(boc) - 1
-            sk = [skip.pop() for _ in range(n + 1)]
-            self.up_blocks.append(UpBlock(prev, cout, sk, temb, list(reversed(depths))[i], cfg,
-                                          not last))
-            prev = cout
-        self.conv_norm_out = nn.GroupNorm(cfg["norm_num_groups"], boc[0], eps=1e-5)
-        self.conv_act = nn.SiLU()          # (diffusers' name)
-        self.conv_out = nn.Conv2d(boc[0], cfg["out_channels"], 3, 1, 1)
-        self.register_load_state_dict_post_hook(derived.after_load)
-
+class FusedGraph(nn.Module):
+    """What a network made of this file's blocks needs for the fused graph, whichever blocks it has -- the UNet, or a
+    ControlNet (its encoder half, mixdq_amd/controlnet.py): prepare_fused_ / set_fused, the time-embedding and context
+    projections issued ahead of the blocks, the holder of weight-derived tensors, the weight-prefetch plan, the
+    embedding of (timestep, added conditions) and conv_in's with-term form.  Everything here walks self.modules();
+    a subclass has `cfg`, `conv_in`, `time_embedding` and, where the config asks for it, `add_embedding`."""
     fused = False
 
     def _grouped(self, name, key, members, wbits):
@@ -1385,6 +1375,116 @@ class SDXLUNet(nn.Module):
         xp[:, :x.shape[1]] = x
         return xp
 
+    def _conv_in_with_term(self, x, term):
+        """conv_in of a step: conv(x8; Wx8) with `term` as the residual -- f16(f32(f16(sum)) + f32(T)), a torch half
+        add of the two rounded tensors."""
+        wx, _ = self._conv_in_split(refresh=False)
+        x8 = self._pad8(x)
+        if x8.is_cuda and x8.dtype == torch.float16:
+            from mixdq_amd import _C
+            return _C.conv2d_f16(x8, wx, None, 1, 1, _residual=term)
+        return F.conv2d(x8, wx, None, 1, 1) + term
+
+    def _apply(self, fn, recurse=True):          # .to() / .cuda() / .half(): the weights move, the plans go
+        self.__dict__.pop("_pf_plans", None)
+        # (... and the split conv_in weights: cond_term() / a ControlNet's hint_term() make them anew)
+        derived.drop(self.__dict__.get("_derived_tensors"))
+        return super()._apply(fn, recurse)
+
+    def load_state_dict(self, *args, **kwargs):
+        self.__dict__.pop("_pf_plans", None)
+        return super().load_state_dict(*args, **kwargs)
+
+    def _embed(self, sample, timestep, added_cond_kwargs):
+        """The time embedding of a forward, with the addition embedding where the config has one: [B, time_embed_dim]."""
+        cfg = self.cfg
+        B = sample.shape[0]
+        dtype = sample.dtype
+        t = timestep
+        if not torch.is_tensor(t):
+            t = torch.tensor([t], dtype=torch.float32, device=sample.device)
+        t = t.reshape(-1).expand(B)
+        emb = self.time_embedding(sinusoidal_embedding(t, cfg["block_out_channels"][0]).to(dtype))
+        if cfg.get("addition_embed_type", "text_time") is not None:    # (else: added_cond_kwargs is ignored)
+            time_ids = added_cond_kwargs["time_ids"]
+            text_embeds = added_cond_kwargs["text_embeds"]
+            tid = sinusoidal_embedding(time_ids.flatten(), cfg["addition_time_embed_dim"])
+            add = torch.cat([text_embeds, tid.reshape(B, -1).to(dtype)], dim=-1)
+            emb = emb + self.add_embedding(add)
+        return emb
+
+    def _with_prefetch(self, sample, body):
+        """body() -- the blocks of a forward -- under this network's weight-prefetch plan, where one applies."""
+        use_pf = bool(self.fused and PREFETCH and sample.is_cuda and _fusable_f16(sample) and not DEFUSE)
+        if not use_pf:
+            return body()
+        # Trace this forward's weight order and replay the plan of the last forward ON THIS DEVICE: the state
+        # is this call's own PrefetchContext (thread-local while it runs), the plans are kept per device in
+        # the instance and hold weak references -- a plan made for another device, or for weights that have
+        # been replaced since (`.to()`, re-quantization, load_state_dict: cleared in _apply / below, and
+        # dropped here when a reference is dead or points elsewhere), is never handed to a launch.
+        from mixdq_amd import _C
+        plans = self.__dict__.setdefault("_pf_plans", {})
+        plan = plans.get(sample.device)
+        if plan is not None and not _plan_alive(plan, sample.device):
+            plans.pop(sample.device, None)
+            plan = None
+        ctx = _C.PrefetchContext(sample.device, plan["lists"] if plan else None)
+        try:
+            with ctx:
+                return body()
+        finally:
+            if ctx._outer is None:                               # (an inner, inactive context traced nothing)
+                sig = _trace_signature(ctx.trace)
+                if plan is None or plan["sig"] != sig:           # first forward here, or the layers changed
+                    new = _build_prefetch_plan(ctx.trace)
+                    if new is None:
+                        plans.pop(sample.device, None)
+                    else:
+                        plans[sample.device] = new
+
+
+class SDXLUNet(FusedGraph):
+    """forward(sample, timestep, encoder_hidden_states, added_cond_kwargs, return_dict=False)
+    -> (noise_pred,), the call shape of quantize_sdxl.py:375-385.  `cfg`: overrides of SDXL_CONFIG; SD15_CONFIG
+    makes it the SD 1.5 UNet (same classes, diffusers' names for that network)."""
+
+    def __init__(self, cfg=None):
+        super().__init__()
+        cfg = dict(SDXL_CONFIG, **(cfg or {}))
+        self.cfg = cfg
+        boc = cfg["block_out_channels"]
+        temb = cfg["time_embed_dim"]
+        self.conv_in = nn.Conv2d(cfg["in_channels"], boc[0], 3, 1, 1)
+        # input channels beyond the latents': 0, or the 5 (mask + masked-image latents) of an inpainting checkpoint
+        self.cond_channels = cfg["in_channels"] - cfg["out_channels"]
+        self.time_embedding = TimestepEmbedding(boc[0], temb)
+        if cfg.get("addition_embed_type", "text_time") is not None:
+            self.add_embedding = TimestepEmbedding(cfg["projection_class_embeddings_input_dim"], temb)
+        n = cfg["layers_per_block"]
+        depths = cfg["transformer_layers_per_block"]
+        self.down_blocks = nn.ModuleList()
+        skip = [boc[0]]
+        cin = boc[0]
+        for i, cout in enumerate(boc):
+            last = i == len(boc) - 1
+            self.down_blocks.append(DownBlock(cin, cout, temb, n, depths[i], cfg, not last))
+            skip += [cout] * n + ([] if last else [cout])
+            cin = cout
+        self.mid_block = MidBlock(boc[-1], temb, cfg["mid_transformer_layers"], cfg)
+        self.up_blocks = nn.ModuleList()
+        prev = boc[-1]
+        for i, cout in enumerate(reversed(boc)):
+            last = i == len(boc) - 1
+            sk = [skip.pop() for _ in range(n + 1)]
+            self.up_blocks.append(UpBlock(prev, cout, sk, temb, list(reversed(depths))[i], cfg,
+                                          not last))
+            prev = cout
+        self.conv_norm_out = nn.GroupNorm(cfg["norm_num_groups"], boc[0], eps=1e-5)
+        self.conv_act = nn.SiLU()          # (diffusers' name)
+        self.conv_out = nn.Conv2d(boc[0], cfg["out_channels"], 3, 1, 1)
+        self.register_load_state_dict_post_hook(derived.after_load)
+
     @torch.no_grad()
     def cond_term(self, cond):
         """The part of conv_in's output that the conditioning channels contribute, bias included: cond [N, Cc, h, w]
@@ -1413,16 +1513,6 @@ class SDXLUNet(nn.Module):
             return _C.conv2d_f16(c8, wc, bias, 1, 1)
         return F.conv2d(c8, wc, bias, 1, 1).contiguous(memory_format=torch.channels_last)
 
-    def _conv_in_with_term(self, x, term):
-        """conv_in of a step: conv(x8; Wx8) with `term` as the residual -- f16(f32(f16(sum)) + f32(T)), a torch half
-        add of the two rounded tensors."""
-        wx, _ = self._conv_in_split(refresh=False)
-        x8 = self._pad8(x)
-        if x8.is_cuda and x8.dtype == torch.float16:
-            from mixdq_amd import _C
-            return _C.conv2d_f16(x8, wx, None, 1, 1, _residual=term)
-        return F.conv2d(x8, wx, None, 1, 1) + term
-
     def _check_cond_term(self, sample, cond_term):
         co, cc = self.cfg["out_channels"], self.cond_channels
         if cond_term is None:
@@ -1442,64 +1532,88 @@ class SDXLUNet(nn.Module):
                                f"{want} (one row per sample row) on the sample's device")
 
     def forward(self, sample, timestep, encoder_hidden_states, added_cond_kwargs=None,
-                return_dict=False, cond_term=None):
+                return_dict=False, cond_term=None, down_block_additional_residuals=None,
+                mid_block_additional_residual=None, control=None):
         """`cond_term` (UNets with cond_channels > 0): what cond_term(cond) returned, one row per row of `sample`,
         which then has out_channels channels -- conv_in runs split, without a concatenated input.  Without it such a
-        UNet takes all in_channels channels in `sample` (the drop-in form)."""
-        cfg = self.cfg
+        UNet takes all in_channels channels in `sample` (the drop-in form).
+
+        `down_block_additional_residuals` / `mid_block_additional_residual`: diffusers' keywords and meaning -- a
+        ControlNet's outputs ALREADY scaled, one tensor per skip (conv_in's output first) and one for the mid-block
+        output; every skip becomes skip + r and the mid-block output x + r, in the sample's dtype.
+        `control`: a ControlResiduals (unscaled residuals of 1 to 4 nets, a device table of per-step scales and the
+        device step counter): what a device-side sampling loop passes instead.  One or the other."""
         self._check_cond_term(sample, cond_term)
-        B = sample.shape[0]
-        dtype = sample.dtype
-        t = timestep
-        if not torch.is_tensor(t):
-            t = torch.tensor([t], dtype=torch.float32, device=sample.device)
-        t = t.reshape(-1).expand(B)
-        emb = self.time_embedding(sinusoidal_embedding(t, cfg["block_out_channels"][0]).to(dtype))
-        if cfg.get("addition_embed_type", "text_time") is not None:    # (else: added_cond_kwargs is ignored)
-            time_ids = added_cond_kwargs["time_ids"]
-            text_embeds = added_cond_kwargs["text_embeds"]
-            tid = sinusoidal_embedding(time_ids.flatten(), cfg["addition_time_embed_dim"])
-            add = torch.cat([text_embeds, tid.reshape(B, -1).to(dtype)], dim=-1)
-            emb = emb + self.add_embedding(add)
+        control = self._control_of(sample, down_block_additional_residuals, mid_block_additional_residual, control)
+        emb = self._embed(sample, timestep, added_cond_kwargs)
+        return self._with_prefetch(sample, lambda: self._forward_body(sample, emb, encoder_hidden_states, cond_term,
+                                                                      control))
 
-        use_pf = bool(self.fused and PREFETCH and sample.is_cuda and _fusable_f16(sample) and not DEFUSE)
-        if not use_pf:
-            return self._forward_body(sample, emb, encoder_hidden_states, cond_term)
-        # Trace this forward's weight order and replay the plan of the last forward ON THIS DEVICE: the state
-        # is this call's own PrefetchContext (thread-local while it runs), the plans are kept per device in
-        # the instance and hold weak references -- a plan made for another device, or for weights that have
-        # been replaced since (`.to()`, re-quantization, load_state_dict: cleared in _apply / below, and
-        # dropped here when a reference is dead or points elsewhere), is never handed to a launch.
-        from mixdq_amd import _C
-        plans = self.__dict__.setdefault("_pf_plans", {})
-        plan = plans.get(sample.device)
-        if plan is not None and not _plan_alive(plan, sample.device):
-            plans.pop(sample.device, None)
-            plan = None
-        ctx = _C.PrefetchContext(sample.device, plan["lists"] if plan else None)
-        try:
-            with ctx:
-                return self._forward_body(sample, emb, encoder_hidden_states, cond_term)
-        finally:
-            if ctx._outer is None:                               # (an inner, inactive context traced nothing)
-                sig = _trace_signature(ctx.trace)
-                if plan is None or plan["sig"] != sig:           # first forward here, or the layers changed
-                    new = _build_prefetch_plan(ctx.trace)
-                    if new is None:
-                        plans.pop(sample.device, None)
-                    else:
-                        plans[sample.device] = new
+    # ---- ControlNet residuals (DESIGN.md section 3.35) ------------------------------------------------------------
+    def n_skips(self) -> int:
+        """How many skip tensors the down path makes (conv_in's output included): a ControlNet has one residual each."""
+        return 1 + sum(len(b.resnets) + (1 if b.has_down else 0) for b in self.down_blocks)
 
-    def _apply(self, fn, recurse=True):          # .to() / .cuda() / .half(): the weights move, the plans go
-        self.__dict__.pop("_pf_plans", None)
-        derived.drop(self.__dict__.get("_derived_tensors"))   # (... and the split conv_in weights: cond_term() makes them anew)
-        return super()._apply(fn, recurse)
+    def _control_of(self, sample, down, mid, control):
+        """The ControlResiduals of a forward: `control` itself, the diffusers keywords as one net with the scale table
+        [[1.0]] at step 0 (f16(r * 1.0) is r: exactly skip + r), or None.  Counts and types are checked here, shapes
+        where the skips exist (_add_control)."""
+        if control is None and down is None and mid is None:
+            return None
+        if control is not None:
+            if down is not None or mid is not None:
+                raise RuntimeError("SDXLUNet.forward: control= and down_block_additional_residuals / "
+                                   "mid_block_additional_residual exclude each other")
+            if not isinstance(control, ControlResiduals):
+                raise RuntimeError("SDXLUNet.forward: control should be a mixdq_amd.unet.ControlResiduals")
+        else:
+            if down is None or mid is None:
+                raise RuntimeError("SDXLUNet.forward: down_block_additional_residuals and mid_block_additional_residual "
+                                   "go together")
+            if not isinstance(down, (list, tuple)):
+                raise RuntimeError("SDXLUNet.forward: down_block_additional_residuals should be a list or tuple of "
+                                   "tensors")
+            control = ControlResiduals([(down, mid)], *_unit_scale(sample.device))
+        n = self.n_skips()
+        if not 1 <= len(control.nets) <= 4:
+            raise RuntimeError(f"SDXLUNet.forward: 1 to 4 ControlNets, got {len(control.nets)}")
+        for k, (d, m) in enumerate(control.nets):
+            if len(d) != n:
+                raise RuntimeError(f"SDXLUNet.forward: this UNet has {n} skip tensors: net {k} should bring {n} down "
+                                   f"residuals, got {len(d)}")
+            if not (torch.is_tensor(m) and all(torch.is_tensor(r) for r in d)):
+                raise RuntimeError(f"SDXLUNet.forward: the residuals of net {k} should be tensors")
+        sc, st = control.scales, control.step
+        if not (torch.is_tensor(sc) and sc.dtype == torch.float32 and sc.dim() == 2 and sc.shape[0] == len(control.nets)
+                and sc.shape[1] >= 1 and sc.device == sample.device and sc.is_contiguous()):
+            raise RuntimeError(f"SDXLUNet.forward: control.scales should be a contiguous fp32 [{len(control.nets)}, "
+                               f"n_steps] tensor on the sample's device")
+        if not (torch.is_tensor(st) and st.dtype == torch.int32 and st.numel() == 1 and st.device == sample.device):
+            raise RuntimeError("SDXLUNet.forward: control.step should be one int32 on the sample's device")
+        return control
 
-    def load_state_dict(self, *args, **kwargs):
-        self.__dict__.pop("_pf_plans", None)
-        return super().load_state_dict(*args, **kwargs)
+    def _add_control(self, skips, x, control):
+        """(skips + residuals, x + mid residual) as FRESH tensors: a skip is also the next block's input and may carry
+        a handed-off INT8 operand, so nothing is written in place.  Fused: ONE control_add launch over all of them;
+        de-fused, on the CPU, for other dtypes or with MIXDQ_CONTROL_ADD=0: torch operations in the same order."""
+        segs = list(skips) + [x]
+        nets = [list(d) + [m] for d, m in control.nets]
+        for k, net in enumerate(nets):
+            for i, (s, r) in enumerate(zip(segs, net)):
+                name = f"net {k}, " + (f"down residual {i}" if i < len(skips) else "the mid residual")
+                if not (tuple(r.shape) == tuple(s.shape) and r.dtype == s.dtype and r.device == s.device
+                        and r.is_contiguous(memory_format=torch.channels_last)):
+                    raise RuntimeError(f"SDXLUNet.forward: {name} should be a channels-last {s.dtype} tensor of shape "
+                                       f"{tuple(s.shape)} on the sample's device, got {tuple(r.shape)} {r.dtype}")
+        segs = [s.contiguous(memory_format=torch.channels_last) for s in segs]
+        if self.fused and not DEFUSE and CONTROL_ADD and all(_fusable_f16(s) for s in segs):
+            from mixdq_amd import _C
+            out = _C.control_add(segs, nets, control.scales, control.step)
+        else:
+            out = _control_add_torch(segs, nets, control.scales, control.step)
+        return out[:-1], out[-1]
 
-    def _forward_body(self, sample, emb, encoder_hidden_states, cond_term=None):
+    def _forward_body(self, sample, emb, encoder_hidden_states, cond_term=None, control=None):
         if self.fused and _fusable_f16(sample) and not DEFUSE:
             self._project_temb_ahead(emb)
             self._project_context_ahead(encoder_hidden_states)
@@ -1510,6 +1624,8 @@ class SDXLUNet(nn.Module):
             x, outs = blk(x, emb, encoder_hidden_states)
             skips += outs
         x = self.mid_block(x, emb, encoder_hidden_states)
+        if control is not None:
+            skips, x = self._add_control(skips, x, control)
         for blk in self.up_blocks:
             x = blk(x, skips, emb, encoder_hidden_states)
         if self.fused and _fusable_f16(x):
@@ -1518,6 +1634,39 @@ class SDXLUNet(nn.Module):
         else:
             x = self.conv_out(self.conv_act(self.conv_norm_out(x)))
         return (x,)
+
+
+_UNIT_SCALE = {}
+
+
+def _unit_scale(device):
+    """The scale table [[1.0]] and the step 0 of the keyword form, constants of the device: made once, so that the
+    keyword form is the one control_add launch (never cached while a stream is capturing: a tensor that only a graph
+    replay fills must not outlive the capture)."""
+    got = _UNIT_SCALE.get(device)
+    if got is None:
+        got = (torch.ones((1, 1), dtype=torch.float32, device=device), torch.zeros(1, dtype=torch.int32, device=device))
+        if not (device.type == "cuda" and torch.cuda.is_current_stream_capturing()):
+            _UNIT_SCALE[device] = got
+    return got
+
+
+def _control_add_torch(segs, nets, scales, step):
+    """control_add's arithmetic as torch operations in the segments' dtype: per net r * c_k (the python float of the
+    fp32 scale), the nets summed left to right, then skip + sum; a net whose scale is 0, and every net at a step
+    outside the table, is skipped; nothing added: a copy.  Reads the scales on the host (a synchronisation)."""
+    st = int(step.item())
+    row = [float(v) for v in scales[:, st].tolist()] if 0 <= st < scales.shape[1] else [0.0] * len(nets)
+    out = []
+    for i, s in enumerate(segs):
+        acc = None
+        for k, net in enumerate(nets):
+            if row[k] == 0.0:
+                continue
+            t = net[i] * row[k]
+            acc = t if acc is None else acc + t
+        out.append(s.clone() if acc is None else s + acc)
+    return out
 
 
 # ---------------------------------------------------------------------------------------------
