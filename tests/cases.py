@@ -19,7 +19,7 @@ LINEAR_CASES = [
     ("lin_attn2_to_k", 77, 2048, 640, False, (-128, 128), 203, "SDXL attn2.to_k (77,640,2048)"),
     ("lin_attn1_1280", 256, 1280, 1280, True, (-128, 128), 204, "SDXL attn1/proj (M scaled 1024->256)"),
     ("lin_ff_geglu", 128, 640, 5120, True, (-128, 128), 205, "SDXL ff.net.0.proj (T,8c,c), M scaled"),
-    ("lin_ff_out", 96, 5120, 1280, True, (-128, 128), 206, "SDXL ff.net.2; |acc| > 2^24 exercises cvt RNE"),
+    ("lin_ff_out", 96, 5120, 1280, True, (-128, 128), 206, "SDXL ff.net.2; max |acc| 1 835 263: every f32(acc) exact (|acc| >= 2^24: heavy_acc.py)"),
     ("lin_time_emb", 1, 2816, 1280, True, (-128, 128), 207, "add_embedding.linear_1, M=1"),
     ("lin_ragged", 37, 48, 24, True, (-128, 128), 208, "K%16==0, N%8==0, ragged M"),
     ("lin_small_align", 19, 20, 12, True, (-128, 128), 209, "K%4, N%4 only: small-alignment path"),
