@@ -1398,29 +1398,26 @@ def embed_tokens_f16(ids, tok, pos):
     return out
 
 
-# The six step entry points: x, eps, in, then what the kind adds around the table, then the part they all share.
-# order 1: noise, noise_stride (_rng: seeds, n_image), coef, t_table, n_steps, step
-_STEP_ORDER1 = [_vp] * 3 + [_vp, _i64, _vp, _vp, _i32, _vp]
-# 2M: hist, coef8, t_table, n_steps, step, first
-_STEP_2M = [_vp] * 3 + [_vp, _vp, _vp, _i32, _vp, _vp]
-_STEP_SHARED = [_vp, ctypes.c_float, _i64, _i32, _i64]      # timestep, guidance, n, rows_per_image, row_stride
-_STEP_MASKED = [_vp, _vp, _vp, _i32, _vp]                   # z, noise0, mask, channels, blend
-for _name, _head, _tail in (("", _STEP_ORDER1, []), ("_masked", _STEP_ORDER1, _STEP_MASKED),
-                            ("_rng", _STEP_ORDER1, []), ("_masked_rng", _STEP_ORDER1, _STEP_MASKED),
-                            ("_2m", _STEP_2M, []), ("_2m_masked", _STEP_2M, _STEP_MASKED)):
-    getattr(_lib, "mixdq_sampler_step" + _name).argtypes = _head + _STEP_SHARED + _tail + [_vp]
+# The eight step entry points (include/mixdq_hip.h): the names of their arguments in order, the trailing stream aside.
+# The argument types are read off the names here, and _sampler_step assembles every call from them.
+_STEP_SHARED = " timestep guidance n rows_per_image row_stride"
+_STEP_MASKED = " z noise0 mask channels blend"
+_STEP_FLAT = "x eps inp table width t_table n_steps step timestep guidance image_guidance "   # (the two flat ones)
+_STEP_ARGS = {
+    "": "x eps inp noise noise_stride table t_table n_steps step" + _STEP_SHARED,
+    "_rng": "x eps inp seeds n_image table t_table n_steps step" + _STEP_SHARED,
+    "_2m": "x eps inp hist table t_table n_steps step first" + _STEP_SHARED,
+    "3": _STEP_FLAT + "n row_stride noise noise_stride seeds n_image hist first" + _STEP_MASKED,
+    "_rescaled": _STEP_FLAT + ("rescale rows_per_image n n_image row_stride workspace noise noise_stride seeds hist first"
+                               + _STEP_MASKED)}
+_STEP_ARGS.update({"_masked": _STEP_ARGS[""] + _STEP_MASKED, "_masked_rng": _STEP_ARGS["_rng"] + _STEP_MASKED,
+                   "_2m_masked": _STEP_ARGS["_2m"] + _STEP_MASKED})
+_STEP_CTYPES = {**dict.fromkeys(("n", "n_image", "row_stride", "noise_stride"), _i64),
+                **dict.fromkeys(("width", "n_steps", "rows_per_image", "channels"), _i32),
+                **dict.fromkeys(("guidance", "image_guidance", "rescale"), ctypes.c_float)}   # everything else: a pointer
+for _name, _args in _STEP_ARGS.items():
+    getattr(_lib, "mixdq_sampler_step" + _name).argtypes = [_STEP_CTYPES.get(a, _vp) for a in _args.split()] + [_vp]
     getattr(_lib, "mixdq_sampler_step" + _name).restype = _i32
-# the three-row step: x, eps, in, table, width, t_table, n_steps, step, timestep, guidance, image_guidance, n, row_stride,
-# noise, noise_stride, seeds, n_image, hist, first, then the masked operands
-_lib.mixdq_sampler_step3.argtypes = ([_vp] * 4 + [_i32, _vp, _i32, _vp, _vp, ctypes.c_float, ctypes.c_float, _i64, _i64]
-                                     + [_vp, _i64, _vp, _i64, _vp, _vp] + _STEP_MASKED + [_vp])
-_lib.mixdq_sampler_step3.restype = _i32
-# the rescaled step: step3's head with rescale, rows_per_image, n, n_image, row_stride and the workspace in it, then
-# noise, noise_stride, seeds, hist, first and the masked operands
-_lib.mixdq_sampler_step_rescaled.argtypes = (
-    [_vp] * 4 + [_i32, _vp, _i32, _vp, _vp, ctypes.c_float, ctypes.c_float, ctypes.c_float, _i32, _i64, _i64, _i64, _vp]
-    + [_vp, _i64, _vp, _vp, _vp] + _STEP_MASKED + [_vp])
-_lib.mixdq_sampler_step_rescaled.restype = _i32
 _lib.mixdq_sampler_rescale_workspace_floats.argtypes = [_i64, _i64]
 _lib.mixdq_sampler_rescale_workspace_floats.restype = ctypes.c_size_t
 _lib.mixdq_randn_f32.argtypes = [_vp, _i32, _i64, _vp, ctypes.c_uint32, ctypes.c_uint32, _vp]
@@ -1434,17 +1431,6 @@ RNG_STREAM_COND = 3                                                       # ... 
 def _check_seeds(seeds, B, what):
     _check(torch.is_tensor(seeds) and seeds.dtype == torch.int64 and seeds.dim() == 1 and seeds.shape[0] == B
            and seeds.is_contiguous(), f"{what}: seeds should be a contiguous int64 tensor of shape [{B}]")
-
-
-def _check_step_seeds(seeds, noise, n, n_image, numel, what):
-    """The checks of a step binding's `seeds=` / `n_image=`; returns (n, n_image).  They come first and look at no
-    device, so that a wrong call is refused the same way wherever it is made."""
-    _check(noise is None, f"{what}: noise and seeds exclude each other (with seeds the step makes its own noise)")
-    n = int(numel if n is None else n)
-    n_image = n if n_image is None else int(n_image)
-    _check(n_image >= 1 and n % n_image == 0, f"{what}: n = {n} is not a multiple of n_image = {n_image}")
-    _check_seeds(seeds, n // n_image, what)
-    return n, n_image
 
 
 def randn(shape, seeds, stream=0, step=0, out=None):
@@ -1491,20 +1477,24 @@ def _sampler_step(what, x, eps, inp, table, width, t_table, step, timestep, guid
     noise / seeds: at most one of them, width 4 only; image_guidance: None, or the second scale of the three-row step
     (mixdq_sampler_step3, rows_per_image == 3); rescale: None, or phi of the rescaled step
     (mixdq_sampler_step_rescaled, rows_per_image 2 or 3), which comes with `workspace` and `n_image`."""
-    if seeds is not None:
-        n, n_image = _check_step_seeds(seeds, noise, n, n_image, x.numel(), what)
-    elif rescale is not None:
-        n = int(x.numel() if n is None else n)
+    # n and n_image, once.  The checks of `seeds=` / `n_image=` come first and look at no device, so that a wrong call
+    # is refused the same way wherever it is made.
+    _check(seeds is None or noise is None,
+           f"{what}: noise and seeds exclude each other (with seeds the step makes its own noise)")
+    n = int((x.numel() if torch.is_tensor(x) else 0) if n is None else n)
+    if seeds is not None or rescale is not None:      # the modes that know of images
         n_image = n if n_image is None else int(n_image)
         _check(n_image >= 1 and n % n_image == 0, f"{what}: n = {n} is not a multiple of n_image = {n_image}")
+    if seeds is not None:
+        _check_seeds(seeds, n // n_image, what)
     f32, f16, i32 = torch.float32, torch.float16, torch.int32
     two_m = width == 8
     tname = "coef8" if two_m else "coef"
+    z, noise0, mask, blend = masked if masked is not None else (None,) * 4
     operands = [(x, "x", f32), (eps, "eps", f16), (inp, "inp", f16)] + [(hist, "hist", f32)] * two_m + [
         (table, tname, f32), (t_table, "t_table", f32), (step, "step", i32)] + [(first, "first", i32)] * two_m + [
         (timestep, "timestep", f32)]
     if masked is not None:
-        z, noise0, mask, blend = masked
         operands += [(z, "z", f32), (noise0, "noise0", f32), (mask, "mask", f32), (blend, "blend", f32)]
     if noise is not None:
         operands.append((noise, "noise", f32))
@@ -1527,7 +1517,6 @@ def _sampler_step(what, x, eps, inp, table, width, t_table, step, timestep, guid
                "step, first and timestep hold one value each")
     else:
         _check(step.numel() == 1 and timestep.numel() == 1, "step and timestep hold one value each")
-    n = x.numel() if n is None else int(n)
     row_stride = n if row_stride is None else int(row_stride)
     noise_stride = n if noise_stride is None else int(noise_stride)
     _check(0 <= n <= x.numel(), "n exceeds the state")
@@ -1547,36 +1536,17 @@ def _sampler_step(what, x, eps, inp, table, width, t_table, step, timestep, guid
         _check(eps.numel() >= need and inp.numel() >= need, "eps / inp are smaller than rows_per_image row blocks")
     if noise is not None:
         _check(noise.numel() >= (n_steps - 1) * noise_stride + n, "noise is smaller than n_steps blocks")
-    if image_guidance is not None or rescale is not None:        # the two flat entry points
-        args = [x.data_ptr(), eps.data_ptr(), inp.data_ptr(), table.data_ptr(), width, t_table.data_ptr(), n_steps,
-                step.data_ptr(), timestep.data_ptr(), float(guidance), float(image_guidance or 0.0)]
-        if rescale is not None:
-            entry = _lib.mixdq_sampler_step_rescaled
-            args += [float(rescale), int(rows_per_image), n, n_image, row_stride, workspace.data_ptr(), _ptr(noise),
-                     noise_stride, _ptr(seeds), _ptr(hist), _ptr(first)]
-        else:
-            entry = _lib.mixdq_sampler_step3
-            args += [n, row_stride, _ptr(noise), noise_stride, _ptr(seeds), 0 if seeds is None else n_image, _ptr(hist),
-                     _ptr(first)]
-        args += [t_.data_ptr() for t_ in masked[:3]] + [channels, masked[3].data_ptr()] if masked is not None else [
-            None, None, None, 1, None]
-        with torch.cuda.device(x.device):
-            code = entry(*args, _stream())
-        _status(code, what)
-        return
-    args = [x.data_ptr(), eps.data_ptr(), inp.data_ptr()]
-    if two_m:
-        args += [hist.data_ptr(), table.data_ptr(), t_table.data_ptr(), n_steps, step.data_ptr(), first.data_ptr()]
-    else:
-        args += [seeds.data_ptr(), n_image] if seeds is not None else [_ptr(noise), noise_stride]
-        args += [table.data_ptr(), t_table.data_ptr(), n_steps, step.data_ptr()]
-    args += [timestep.data_ptr(), float(guidance), n, int(rows_per_image), row_stride]
-    if masked is not None:
-        args += [z.data_ptr(), noise0.data_ptr(), mask.data_ptr(), channels, blend.data_ptr()]
-    entry = "mixdq_sampler_step" + ("_2m" if two_m else "") + ("_masked" if masked is not None else "") + (
-        "_rng" if seeds is not None else "")
+    # the entry point, and its arguments by name (_STEP_ARGS); a flat one takes a mode's operands null where it is off
+    entry = ("_rescaled" if rescale is not None else "3" if image_guidance is not None else
+             ("_2m" if two_m else "") + ("_masked" if masked is not None else "") + ("_rng" if seeds is not None else ""))
+    have = dict(x=x, eps=eps, inp=inp, table=table, width=width, t_table=t_table, n_steps=n_steps, step=step, first=first,
+                timestep=timestep, guidance=float(guidance), image_guidance=float(image_guidance or 0.0), rescale=rescale,
+                rows_per_image=int(rows_per_image), n=n, n_image=n_image or 0, row_stride=row_stride, workspace=workspace,
+                noise=noise, noise_stride=noise_stride, seeds=seeds, hist=hist, z=z, noise0=noise0, mask=mask,
+                channels=channels if masked is not None else 1, blend=blend)
+    args = [_ptr(v) if v is None or torch.is_tensor(v) else v for v in map(have.get, _STEP_ARGS[entry].split())]
     with torch.cuda.device(x.device):
-        code = getattr(_lib, entry)(*args, _stream())
+        code = getattr(_lib, "mixdq_sampler_step" + entry)(*args, _stream())
     _status(code, what)
 
 
@@ -1638,6 +1608,21 @@ def sampler_step_2m_masked(x, eps, inp, hist, coef8, t_table, step, first, times
                   row_stride, hist=hist, first=first, masked=(z, noise0, mask, blend), channels=channels)
 
 
+def _check_flat(what, table, noise, seeds, hist, first, z, noise0, mask, blend):
+    """The pre-checks of the two flat bindings, which take every mode's operands: the table's width says which kind the
+    step is, and the operands of a mode go together.  Returns (width, masked) as _sampler_step takes them."""
+    width = table.shape[1] if torch.is_tensor(table) and table.dim() == 2 else 4
+    _check(width in (4, 8), f"{what}: table should be coef [n_steps, 4] or coef8 [n_steps, 8]")
+    if width == 8:
+        _check(noise is None and seeds is None, f"{what}: the multistep kinds add no noise")
+        _check(hist is not None and first is not None, f"{what}: coef8 comes with hist and first")
+    else:
+        _check(hist is None and first is None, f"{what}: hist and first come with coef8")
+    some = [t_ is not None for t_ in (z, noise0, mask, blend)]
+    _check(all(some) or not any(some), f"{what}: z, noise0, mask and blend go together")
+    return width, (z, noise0, mask, blend) if all(some) else None
+
+
 def sampler_step3(x, eps, inp, table, t_table, step, timestep, guidance, image_guidance, *, noise=None, seeds=None,
                   n_image=None, hist=None, first=None, z=None, noise0=None, mask=None, blend=None, channels=4, n=None,
                   row_stride=None, noise_stride=None):
@@ -1650,19 +1635,10 @@ def sampler_step3(x, eps, inp, table, t_table, step, timestep, guidance, image_g
     coef8 fp32 [n_steps, 8] together with `hist` and `first` (sampler_step_2m[_masked]; no noise).  z, noise0, mask and
     blend (all four, with `channels`) add sampler_step_masked's blend.  The next FP16 input goes to all three blocks of
     `inp`; `timestep` and `step` advance as in sampler_step."""
-    width = table.shape[1] if torch.is_tensor(table) and table.dim() == 2 else 4
-    _check(width in (4, 8), "sampler_step3: table should be coef [n_steps, 4] or coef8 [n_steps, 8]")
-    if width == 8:
-        _check(noise is None and seeds is None, "sampler_step3: the multistep kinds add no noise")
-        _check(hist is not None and first is not None, "sampler_step3: coef8 comes with hist and first")
-    else:
-        _check(hist is None and first is None, "sampler_step3: hist and first come with coef8")
-    some = [t_ is not None for t_ in (z, noise0, mask, blend)]
-    _check(all(some) or not any(some), "sampler_step3: z, noise0, mask and blend go together")
+    width, masked = _check_flat("sampler_step3", table, noise, seeds, hist, first, z, noise0, mask, blend)
     _sampler_step("sampler_step3", x, eps, inp, table, width, t_table, step, timestep, guidance, 3, n, row_stride,
-                  hist=hist, first=first, masked=(z, noise0, mask, blend) if all(some) else None, channels=channels,
-                  noise=noise, noise_stride=noise_stride, seeds=seeds, n_image=n_image,
-                  image_guidance=image_guidance)
+                  hist=hist, first=first, masked=masked, channels=channels, noise=noise, noise_stride=noise_stride,
+                  seeds=seeds, n_image=n_image, image_guidance=image_guidance)
 
 
 def sampler_rescale_workspace(n, n_image, device):
@@ -1692,20 +1668,11 @@ def sampler_step_rescaled(x, eps, inp, table, t_table, step, timestep, guidance,
     _check(rows_per_image in (2, 3), f"{what}: rows_per_image should be 2 or 3 (rescale compares the guided output "
            "with the text-conditioned one)")
     _check(isinstance(rescale, (int, float)) and 0.0 <= float(rescale) <= 1.0, f"{what}: rescale should be in [0, 1]")
-    width = table.shape[1] if torch.is_tensor(table) and table.dim() == 2 else 4
-    _check(width in (4, 8), f"{what}: table should be coef [n_steps, 4] or coef8 [n_steps, 8]")
-    if width == 8:
-        _check(noise is None and seeds is None, f"{what}: the multistep kinds add no noise")
-        _check(hist is not None and first is not None, f"{what}: coef8 comes with hist and first")
-    else:
-        _check(hist is None and first is None, f"{what}: hist and first come with coef8")
-    some = [t_ is not None for t_ in (z, noise0, mask, blend)]
-    _check(all(some) or not any(some), f"{what}: z, noise0, mask and blend go together")
+    width, masked = _check_flat(what, table, noise, seeds, hist, first, z, noise0, mask, blend)
     _sampler_step(what, x, eps, inp, table, width, t_table, step, timestep, guidance, rows_per_image, n, row_stride,
-                  hist=hist, first=first, masked=(z, noise0, mask, blend) if all(some) else None, channels=channels,
-                  noise=noise, noise_stride=noise_stride, seeds=seeds, n_image=n_image,
-                  image_guidance=image_guidance if rows_per_image == 3 else None, rescale=float(rescale),
-                  workspace=workspace)
+                  hist=hist, first=first, masked=masked, channels=channels, noise=noise, noise_stride=noise_stride,
+                  seeds=seeds, n_image=n_image, image_guidance=image_guidance if rows_per_image == 3 else None,
+                  rescale=float(rescale), workspace=workspace)
 
 
 _lib.mixdq_image_to_nhwc8_f16.argtypes = [_vp, _i32, _i64, _i64, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _vp]

@@ -2,8 +2,9 @@
 // and the device-side step state (step index, the timestep the UNet reads) in a one-thread launch behind it.
 // No reference counterpart: the reference reaches the sampling loop only through diffusers' pipeline call.
 //
-// Every step is ONE kernel template, sampler_step_kernel<ROWS, ORDER, NOISE, MASK>, and one per-element function
-// (step_one) built from include/mixdq_math.h -- FP32 round-to-nearest, no contraction:
+// Every step is ONE kernel template, sampler_step_kernel<ROWS, ORDER, NOISE, MASK>: its own are the grid-stride loop
+// and the tail; the body is sampler_step.h's, shared with the rescaled step (sampler_rescale.hip), built from
+// include/mixdq_math.h -- FP32 round-to-nearest, no contraction:
 //   e   = eps_u + g * (eps_c - eps_u)                     ROWS 2 (rows_per_image; 1: e = eps_u)
 //   e   = (e_u + g * (e_t - e_i)) + gi * (e_i - e_u)      ROWS 3 (InstructPix2Pix: row blocks e_t, e_i, e_u in that order)
 //   x'  = (a*x + b*e) + c*n                               ORDER 1; NOISE 0: a*x + b*e;  (a, b, c, s_next) = coef[*step]
@@ -12,8 +13,8 @@
 //   in  = f16_rn(x'' * s_next)                            written to every UNet row of the image; x'' stored to x
 // A mode's operands are read only by the instantiations of that mode; the six mixdq_sampler_step* entry points fill
 // one operand set (StepArgs), check it (check_step) and launch (launch_step), which picks the instantiation.
-// mixdq_sampler_step3 is the one entry point of ROWS 3: it takes the whole operand set flat, a mode's operands null
-// where the mode is off.  The two-row blocks are (unconditional, conditional); the three-row blocks follow diffusers'
+// mixdq_sampler_step3 is the one entry point of ROWS 3: it takes the whole operand set flat (set_flat), a mode's operands
+// null where the mode is off.  The two-row blocks are (unconditional, conditional); the three-row blocks follow diffusers'
 // InstructPix2Pix pipelines: block 0 text + image, block 1 image only, block 2 neither.
 //
 // ORDER 1 -- Euler, Euler-ancestral, DDIM and LCM with an epsilon-predicting model -- is one affine map with per-step
@@ -81,9 +82,7 @@ __global__ __launch_bounds__(256) void normals_from_bits_kernel(const uint32_t* 
   }
 }
 
-// `table` is coef (ORDER 1) or coef8 (ORDER 2).  (noise, noise_stride): NOISE 1; (seeds, n_image): NOISE 2, 3;
-// (hist, first_p): ORDER 2, and `hist` is not read at all on a first-order step: it may hold anything there;
-// (z, noise0, mask, channels, blend): MASK 1, 2.  The other instantiations never touch them (they are passed null).
+// `table` is coef (ORDER 1) or coef8 (ORDER 2); first_p: ORDER 2; blend: MASK 1, 2; the rest as sampler_step.h says.
 template <int ROWS, int ORDER, int NOISE, int MASK>
 __global__ __launch_bounds__(256) void sampler_step_kernel(
     float* __restrict__ x, const __half* __restrict__ eps, __half* __restrict__ in, const float* __restrict__ table,
@@ -96,77 +95,23 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(
   const int step = *step_p;
   if (step < 0 || step >= n_steps) return;        // replayed past the table: nothing is read or written
   StepRow k = {};
-  k.g = g, k.gi = gi;
-  if constexpr (ORDER == 1) {
-    const float4 r = *reinterpret_cast<const float4*>(table + 4 * (int64_t)step);
-    k.a = r.x, k.b = r.y, k.c = r.z, k.s_next = r.w;
-  } else {
-    const float4 r0 = *reinterpret_cast<const float4*>(table + 8 * (int64_t)step);
-    const float4 r1 = *reinterpret_cast<const float4*>(table + 8 * (int64_t)step + 4);
-    k.u = r0.x, k.v = r0.y, k.a = r0.z, k.d = r1.y, k.s_next = r1.z;
-    k.second = step > *first_p && k.d != 0.0f;
-    k.b = k.second ? r1.x : r0.w;
-  }
-  if constexpr (MASK != 0) {
-    const float2 pq = *reinterpret_cast<const float2*>(blend + 2 * (int64_t)step);
-    k.p = pq.x, k.q = pq.y;
-  }
+  step_row<ORDER, MASK>(k, table, first_p, blend, step, g, gi);
   const float* nz = NOISE == 1 ? noise + (int64_t)step * noise_stride : nullptr;
   const int64_t nvec = n >> 3;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += stride) {
-    const int64_t o = i << 3;
-    float xs[8], ns[8] = {}, hs[8] = {}, zs[8] = {}, is[8] = {}, ms[8] = {};
-    load8(x + o, xs);
-    const Half8 e0 = *reinterpret_cast<const Half8*>(eps + o);
-    Half8 e1 = e0, e2 = e0;
-    if (ROWS >= 2) e1 = *reinterpret_cast<const Half8*>(eps + row_stride + o);
-    if (ROWS == 3) e2 = *reinterpret_cast<const Half8*>(eps + 2 * row_stride + o);
-    noise8<NOISE>(nz, seeds, n_image, o, (uint32_t)step, ns);
-    if constexpr (ORDER == 2) {
-      if (k.second) load8(hist + o, hs);
-    }
-    if constexpr (MASK != 0) {
-      load8(z + o, zs);
-      load8(noise0 + o, is);
-      mask8<MASK>(mask, channels, o, ms);
-    }
-    float y[8], p0[8];
-    Half8 out;
+    StepPass8 p = {};
+    step_load8<ROWS, ORDER, NOISE, MASK>(p, k, step, i << 3, x, eps, row_stride, nz, seeds, n_image, hist, z, noise0, mask,
+                                         channels);
 #pragma unroll
-    for (int j = 0; j < 8; ++j)
-      y[j] = step_one<ROWS, ORDER, NOISE, MASK>(k, xs[j], half_at(e0, j), half_at(e1, j), half_at(e2, j), ns[j], hs[j],
-                                                zs[j], is[j], ms[j], &p0[j]);
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      out.w[j] = half_bits(mixdq_sampler_scaled_input(y[2 * j], k.s_next)) |
-                 (half_bits(mixdq_sampler_scaled_input(y[2 * j + 1], k.s_next)) << 16);
-    if constexpr (ORDER == 2) store8(hist + o, p0);
-    store8(x + o, y);
-    *reinterpret_cast<Half8*>(in + o) = out;
-    if (ROWS >= 2) *reinterpret_cast<Half8*>(in + row_stride + o) = out;
-    if (ROWS == 3) *reinterpret_cast<Half8*>(in + 2 * row_stride + o) = out;
+    for (int j = 0; j < 8; ++j) step_elem<ROWS, ORDER, NOISE, MASK, false>(p, k, 1.0f, j);
+    step_store8<ROWS, ORDER>(p, k, i << 3, x, in, row_stride, hist);
   }
   // tail (n % 8 elements), by the first threads of block 0
   const int64_t t = (nvec << 3) + threadIdx.x;
-  if (blockIdx.x == 0 && t < n) {
-    const float e0 = __half2float(eps[t]);
-    const float e1 = ROWS >= 2 ? __half2float(eps[row_stride + t]) : e0;
-    const float e2 = ROWS == 3 ? __half2float(eps[2 * row_stride + t]) : e0;
-    float hv = 0.0f, zv = 0.0f, iv = 0.0f, mv = 0.0f, p0;
-    if constexpr (ORDER == 2) {
-      if (k.second) hv = hist[t];
-    }
-    if constexpr (MASK != 0) zv = z[t], iv = noise0[t], mv = mask[t / channels];
-    const float y = step_one<ROWS, ORDER, NOISE, MASK>(
-        k, x[t], e0, e1, e2, tail_noise<NOISE>(nz, seeds, n_image, t, (uint32_t)step), hv, zv, iv, mv, &p0);
-    const __half h = f32_to_f16_rn(mixdq_sampler_scaled_input(y, k.s_next));
-    if constexpr (ORDER == 2) hist[t] = p0;
-    x[t] = y;
-    in[t] = h;
-    if (ROWS >= 2) in[row_stride + t] = h;
-    if (ROWS == 3) in[2 * row_stride + t] = h;
-  }
+  if (blockIdx.x == 0 && t < n)
+    step_at<ROWS, ORDER, NOISE, MASK, false>(k, 1.0f, step, t, x, eps, in, row_stride, nz, seeds, n_image, hist, z, noise0,
+                                             mask, channels);
 }
 
 // Check, launch the instantiation the operand set asks for, then the advance.  n == 0 launches the advance alone.
@@ -175,22 +120,12 @@ int launch_step(const StepArgs& a, mixdq_stream_t stream_) {
   if (bad != MIXDQ_OK) return bad;
   hipStream_t stream = (hipStream_t)stream_;
   if (a.n > 0) {
-    const int noise = a.rng ? (a.n_image % 8 == 0 ? 2 : 3) : (a.noise ? 1 : 0);
-    const int mask = a.masked ? (a.channels == 4 ? 1 : 2) : 0;
-    with_constant<1, 2, 3>(a.rows_per_image, [&](auto rows) {
-      with_constant<1, 2>(a.multistep ? 2 : 1, [&](auto order) {
-        with_constant<0, 1, 2, 3>(noise, [&](auto nz) {
-          with_constant<0, 1, 2>(mask, [&](auto m) {
-            constexpr int ROWS = decltype(rows)::value, ORDER = decltype(order)::value;
-            constexpr int NOISE = decltype(nz)::value, MASK = decltype(m)::value;
-            if constexpr (ORDER == 1 || NOISE == 0)
-              sampler_step_kernel<ROWS, ORDER, NOISE, MASK><<<grid_blocks(a.n >> 3), 256, 0, stream>>>(
-                  a.x, (const __half*)a.eps_f16, (__half*)a.in_f16, a.table, a.step, a.n_steps, a.guidance,
-                  a.image_guidance, a.n, a.row_stride, a.noise, a.noise_stride, a.seeds, a.n_image, a.hist, a.first, a.z,
-                  a.noise0, a.mask, a.channels, a.blend);
-          });
-        });
-      });
+    const int blocks = grid_blocks(a.n >> 3);
+    with_step_modes<1, 2, 3>(a, [&](auto rows, auto order, auto noise, auto mask) {
+      sampler_step_kernel<decltype(rows)::value, decltype(order)::value, decltype(noise)::value, decltype(mask)::value>
+          <<<blocks, 256, 0, stream>>>(a.x, (const __half*)a.eps_f16, (__half*)a.in_f16, a.table, a.step, a.n_steps,
+                                       a.guidance, a.image_guidance, a.n, a.row_stride, a.noise, a.noise_stride, a.seeds,
+                                       a.n_image, a.hist, a.first, a.z, a.noise0, a.mask, a.channels, a.blend);
     });
     if (hipGetLastError() != hipSuccess) return MIXDQ_ERR_LAUNCH;
   }
@@ -296,13 +231,8 @@ extern "C" int mixdq_sampler_step3(float* x, const void* eps_f16, void* in_f16, 
                                    const float* mask, int channels, const float* blend, mixdq_stream_t stream_) {
   StepArgs a = {x, eps_f16, in_f16, table, t_table, n_steps, step, timestep, guidance, n, 3, row_stride};
   a.three = true, a.image_guidance = image_guidance;
-  const bool two_m = table_width == 8, stochastic = noise_or_null || seeds_or_null;
-  if (table_width != 4 && !two_m) return MIXDQ_ERR_INVALID_ARG;
-  if ((two_m && stochastic) || (noise_or_null && seeds_or_null)) return MIXDQ_ERR_INVALID_ARG;
-  if (two_m != (hist_or_null || first_or_null)) return MIXDQ_ERR_INVALID_ARG;   // (one of the pair: check_step's null check)
-  a.noise = noise_or_null, a.noise_stride = noise_stride;
-  if (seeds_or_null) a.rng = true, a.seeds = seeds_or_null, a.n_image = n_image;
-  if (two_m) a.multistep = true, a.hist = hist_or_null, a.first = first_or_null;
-  if (z || noise0 || mask || blend) a.set_masked(z, noise0, mask, channels, blend);
+  const int bad = set_flat(a, table_width, noise_or_null, noise_stride, seeds_or_null, n_image, hist_or_null, first_or_null,
+                           z, noise0, mask, channels, blend);
+  if (bad != MIXDQ_OK) return bad;
   return launch_step(a, stream_);
 }

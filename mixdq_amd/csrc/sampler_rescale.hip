@@ -13,7 +13,7 @@
 //   sampler_step_rescaled_kernel<ROWS, ORDER, NOISE, MASK>   combines the image's chunks in chunk order (Chan's update,
 //                                                      ~32 dependent updates at SDXL's latent size) in its prologue --
 //                                                      every workgroup of the image redundantly, the same bits -- then
-//                                                      the sibling's step with e * r in the place of e
+//                                                      the step's body (sampler_step.h) with e * r in the place of e
 //   sampler_advance_kernel                             the sibling's
 // Stream order is the only synchronisation (the comment at the top of sampler.hip): no atomics, no tickets, no block
 // that finalizes.  The grids are exact -- one workgroup per chunk, nothing capped, no grid-stride loop -- and no
@@ -53,11 +53,6 @@ __device__ __forceinline__ void chunk_sum2(float pa, float pb, float* red, float
   *sb = MIXDQ_ADD_RN(MIXDQ_ADD_RN(MIXDQ_ADD_RN(red[4], red[5]), red[6]), red[7]);
 }
 
-template <int ROWS>
-__device__ __forceinline__ float guided(float e0, float e1, float e2, float g, float gi) {
-  return ROWS == 3 ? mixdq_sampler_guided_eps3(e0, e1, e2, g, gi) : mixdq_sampler_guided_eps(e0, e1, g);
-}
-
 template <int ROWS, bool VEC>
 __global__ __launch_bounds__(256) void sampler_rescale_stats_kernel(const __half* __restrict__ eps,
                                                                     const int* __restrict__ step_p, int n_steps, float g,
@@ -79,7 +74,7 @@ __global__ __launch_bounds__(256) void sampler_rescale_stats_kernel(const __half
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         t[j] = ROWS == 3 ? half_at(e0, j) : half_at(e1, j);
-        e[j] = guided<ROWS>(half_at(e0, j), half_at(e1, j), half_at(e2, j), g, gi);
+        e[j] = step_guided<ROWS>(half_at(e0, j), half_at(e1, j), half_at(e2, j), g, gi);
       }
     }
   } else {
@@ -89,7 +84,7 @@ __global__ __launch_bounds__(256) void sampler_rescale_stats_kernel(const __half
         const float e0 = __half2float(eps[o + j]), e1 = __half2float(eps[row_stride + o + j]);
         const float e2 = ROWS == 3 ? __half2float(eps[2 * row_stride + o + j]) : e0;
         t[j] = ROWS == 3 ? e0 : e1;
-        e[j] = guided<ROWS>(e0, e1, e2, g, gi);
+        e[j] = step_guided<ROWS>(e0, e1, e2, g, gi);
       }
     }
   }
@@ -134,30 +129,8 @@ __global__ __launch_bounds__(64) void sampler_rescale_factor_kernel(float* __res
   if (b < images) ws[4 * images * chunks + b] = image_factor(ws, b, chunks, n_image, phi);
 }
 
-// Row `step` of the tables into a launch's scalars, as the sibling kernel reads it (written out there: its code is
-// pinned instruction by instruction); `first_p` is read by ORDER 2 only, `blend` by MASK != 0 only.
-template <int ORDER, int MASK>
-__device__ __forceinline__ void step_row(StepRow& k, const float* table, const int* first_p, const float* blend, int step,
-                                         float g, float gi) {
-  k.g = g, k.gi = gi;
-  if constexpr (ORDER == 1) {
-    const float4 r = *reinterpret_cast<const float4*>(table + 4 * (int64_t)step);
-    k.a = r.x, k.b = r.y, k.c = r.z, k.s_next = r.w;
-  } else {
-    const float4 r0 = *reinterpret_cast<const float4*>(table + 8 * (int64_t)step);
-    const float4 r1 = *reinterpret_cast<const float4*>(table + 8 * (int64_t)step + 4);
-    k.u = r0.x, k.v = r0.y, k.a = r0.z, k.d = r1.y, k.s_next = r1.z;
-    k.second = step > *first_p && k.d != 0.0f;
-    k.b = k.second ? r1.x : r0.w;
-  }
-  if constexpr (MASK != 0) {
-    const float2 pq = *reinterpret_cast<const float2*>(blend + 2 * (int64_t)step);
-    k.p = pq.x, k.q = pq.y;
-  }
-}
-
-// The sibling's step (sampler.hip: sampler_step_kernel) on chunk blockIdx.x of image blockIdx.y, with e * r in the
-// place of the guided e: step_one is entered with ROWS 1, its one "row" the rescaled value.  `factors`: r[images] where
+// The step's body (sampler_step.h) on chunk blockIdx.x of image blockIdx.y with e * r in the place of the guided e; this
+// kernel's own are the chunk arithmetic, r, and which lanes take the 8-element pass.  `factors`: r[images] where
 // the factor launch ran, else null: the combine runs here.  Operands of a mode as in the sibling.
 template <int ROWS, int ORDER, int NOISE, int MASK>
 __global__ __launch_bounds__(256) void sampler_step_rescaled_kernel(
@@ -180,58 +153,16 @@ __global__ __launch_bounds__(256) void sampler_step_rescaled_kernel(
   if (mine == 0) return;
   // NOISE 2 exists for n_image % 8 == 0 only and NOISE 3 for the rest (the entry point's choice, as the sibling's)
   if (NOISE != 3 && (NOISE == 2 || n_image % 8 == 0)) {
-    float xs[8], ns[8] = {}, hs[8] = {}, zs[8] = {}, is[8] = {}, ms[8] = {};
-    load8(x + o, xs);
-    const Half8 e0 = *reinterpret_cast<const Half8*>(eps + o);
-    const Half8 e1 = *reinterpret_cast<const Half8*>(eps + row_stride + o);
-    Half8 e2 = e0;
-    if (ROWS == 3) e2 = *reinterpret_cast<const Half8*>(eps + 2 * row_stride + o);
-    noise8<NOISE>(nz, seeds, n_image, o, (uint32_t)step, ns);
-    if constexpr (ORDER == 2) {
-      if (k.second) load8(hist + o, hs);
-    }
-    if constexpr (MASK != 0) {
-      load8(z + o, zs);
-      load8(noise0 + o, is);
-      mask8<MASK>(mask, channels, o, ms);
-    }
-    float y[8], p0[8];
-    Half8 out;
+    StepPass8 p = {};
+    step_load8<ROWS, ORDER, NOISE, MASK>(p, k, step, o, x, eps, row_stride, nz, seeds, n_image, hist, z, noise0, mask,
+                                         channels);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float e =
-          mixdq_sampler_rescaled(guided<ROWS>(half_at(e0, j), half_at(e1, j), half_at(e2, j), k.g, k.gi), r);
-      y[j] = step_one<1, ORDER, NOISE, MASK>(k, xs[j], e, e, e, ns[j], hs[j], zs[j], is[j], ms[j], &p0[j]);
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      out.w[j] = half_bits(mixdq_sampler_scaled_input(y[2 * j], k.s_next)) |
-                 (half_bits(mixdq_sampler_scaled_input(y[2 * j + 1], k.s_next)) << 16);
-    if constexpr (ORDER == 2) store8(hist + o, p0);
-    store8(x + o, y);
-    *reinterpret_cast<Half8*>(in + o) = out;
-    *reinterpret_cast<Half8*>(in + row_stride + o) = out;
-    if (ROWS == 3) *reinterpret_cast<Half8*>(in + 2 * row_stride + o) = out;
+    for (int j = 0; j < 8; ++j) step_elem<ROWS, ORDER, NOISE, MASK, true>(p, k, r, j);
+    step_store8<ROWS, ORDER>(p, k, o, x, in, row_stride, hist);
   } else if constexpr (NOISE != 2) {
-    for (int j = 0; j < mine; ++j) {               // element by element, as the sibling's tail
-      const int64_t t = o + j;                     // < (blockIdx.y + 1) * n_image <= n
-      const float e0 = __half2float(eps[t]), e1 = __half2float(eps[row_stride + t]);
-      const float e2 = ROWS == 3 ? __half2float(eps[2 * row_stride + t]) : e0;
-      const float e = mixdq_sampler_rescaled(guided<ROWS>(e0, e1, e2, k.g, k.gi), r);
-      float hv = 0.0f, zv = 0.0f, iv = 0.0f, mv = 0.0f, p0;
-      if constexpr (ORDER == 2) {
-        if (k.second) hv = hist[t];
-      }
-      if constexpr (MASK != 0) zv = z[t], iv = noise0[t], mv = mask[t / channels];
-      const float y = step_one<1, ORDER, NOISE, MASK>(
-          k, x[t], e, e, e, tail_noise<NOISE>(nz, seeds, n_image, t, (uint32_t)step), hv, zv, iv, mv, &p0);
-      const __half h = f32_to_f16_rn(mixdq_sampler_scaled_input(y, k.s_next));
-      if constexpr (ORDER == 2) hist[t] = p0;
-      x[t] = y;
-      in[t] = h;
-      in[row_stride + t] = h;
-      if (ROWS == 3) in[2 * row_stride + t] = h;
-    }
+    for (int j = 0; j < mine; ++j)                 // element by element; o + j < (blockIdx.y + 1) * n_image <= n
+      step_at<ROWS, ORDER, NOISE, MASK, true>(k, r, step, o + j, x, eps, in, row_stride, nz, seeds, n_image, hist, z,
+                                              noise0, mask, channels);
   }
 }
 
@@ -259,15 +190,11 @@ extern "C" int mixdq_sampler_step_rescaled(float* x, const void* eps_f16, void* 
   if (rows_per_image != 2 && rows_per_image != 3) return MIXDQ_ERR_INVALID_ARG;
   StepArgs a = {x, eps_f16, in_f16, table, t_table, n_steps, step, timestep, guidance, n, rows_per_image, row_stride};
   a.three = rows_per_image == 3, a.image_guidance = image_guidance;
-  const bool two_m = table_width == 8, stochastic = noise_or_null || seeds_or_null;
-  if (table_width != 4 && !two_m) return MIXDQ_ERR_INVALID_ARG;
-  if ((two_m && stochastic) || (noise_or_null && seeds_or_null)) return MIXDQ_ERR_INVALID_ARG;
-  if (two_m != (hist_or_null || first_or_null)) return MIXDQ_ERR_INVALID_ARG;   // (one of the pair: check_step's null check)
-  a.noise = noise_or_null, a.noise_stride = noise_stride, a.n_image = n_image;
-  if (seeds_or_null) a.rng = true, a.seeds = seeds_or_null;
-  if (two_m) a.multistep = true, a.hist = hist_or_null, a.first = first_or_null;
-  if (z || noise0 || mask || blend) a.set_masked(z, noise0, mask, channels, blend);
-  const int bad = check_step(a);
+  int bad = set_flat(a, table_width, noise_or_null, noise_stride, seeds_or_null, n_image, hist_or_null, first_or_null, z,
+                     noise0, mask, channels, blend);
+  if (bad != MIXDQ_OK) return bad;
+  a.n_image = n_image;                             // (with or without seeds: the statistics are per image)
+  bad = check_step(a);
   if (bad != MIXDQ_OK) return bad;
   if (!(rescale >= 0.0f && rescale <= 1.0f)) return MIXDQ_ERR_INVALID_ARG;      // (NaN compares false)
   if (n_image < 1 || n % n_image || !workspace) return MIXDQ_ERR_INVALID_ARG;
@@ -293,22 +220,11 @@ extern "C" int mixdq_sampler_step_rescaled(float* x, const void* eps_f16, void* 
                                                                                         chunks, n_image, rescale);
       if (hipGetLastError() != hipSuccess) return MIXDQ_ERR_LAUNCH;
     }
-    const int noise = a.rng ? (n_image % 8 == 0 ? 2 : 3) : (a.noise ? 1 : 0);
-    const int masked = a.masked ? (a.channels == 4 ? 1 : 2) : 0;
-    with_constant<2, 3>(rows_per_image, [&](auto rows) {
-      with_constant<1, 2>(two_m ? 2 : 1, [&](auto order) {
-        with_constant<0, 1, 2, 3>(noise, [&](auto nz) {
-          with_constant<0, 1, 2>(masked, [&](auto m) {
-            constexpr int ROWS = decltype(rows)::value, ORDER = decltype(order)::value;
-            constexpr int NOISE = decltype(nz)::value, MASK = decltype(m)::value;
-            if constexpr (ORDER == 1 || NOISE == 0)
-              sampler_step_rescaled_kernel<ROWS, ORDER, NOISE, MASK><<<grid, 256, 0, stream>>>(
-                  x, eps, (__half*)in_f16, table, step, n_steps, guidance, image_guidance, rescale, row_stride, a.noise,
-                  a.noise_stride, a.seeds, n_image, a.hist, a.first, a.z, a.noise0, a.mask, a.channels, a.blend,
-                  workspace, factors);
-          });
-        });
-      });
+    with_step_modes<2, 3>(a, [&](auto rows, auto order, auto noise, auto mask) {
+      sampler_step_rescaled_kernel<decltype(rows)::value, decltype(order)::value, decltype(noise)::value,
+                                   decltype(mask)::value><<<grid, 256, 0, stream>>>(
+          x, eps, (__half*)in_f16, table, step, n_steps, guidance, image_guidance, rescale, row_stride, a.noise,
+          a.noise_stride, a.seeds, n_image, a.hist, a.first, a.z, a.noise0, a.mask, a.channels, a.blend, workspace, factors);
     });
     if (hipGetLastError() != hipSuccess) return MIXDQ_ERR_LAUNCH;
   }

@@ -478,17 +478,42 @@ class Sampler:
         self._ehs, self._added = _clone_args((encoder_hidden_states, added_cond_kwargs))
         self._key = self._shape_key(noise, encoder_hidden_states, added_cond_kwargs)
 
+    def _step_call(self, masked, rng, channels, n):
+        """The step binding of a capture and its arguments behind (x, eps), all by name: (fn, kwargs).  The classic
+        bindings where they serve; three rows per image or guidance rescale take a flat one, which has every mode's
+        operands and leaves those of a mode that is off at None.  Each static buffer is named here, once."""
+        from mixdq_amd import _C
+        order2, rescaled, n_image = self.schedule.order == 2, self.guidance_rescale > 0.0, n // self._x.shape[0]
+        flat = rescaled or self.rows_per_image == 3
+        name = ("sampler_step_rescaled" if rescaled else "sampler_step3" if flat else
+                "sampler_step" + ("_2m" if order2 else "") + ("_masked" if masked else ""))
+        kw = dict(inp=self._in, t_table=self._t_table, step=self._step, timestep=self._t, guidance=self.guidance_scale, n=n)
+        kw["table" if flat else "coef8" if order2 else "coef"] = self._coef
+        if flat:
+            kw["image_guidance"] = self.image_guidance_scale
+        if rescaled:
+            kw.update(rescale=self.guidance_rescale, workspace=self._rescale_ws, n_image=n_image)
+        if rescaled or not flat:                    # (sampler_step3 is three rows by name)
+            kw["rows_per_image"] = self.rows_per_image
+        if masked:
+            kw.update(z=self._z, noise0=self._noise0, mask=self._mask, blend=self._blend, channels=channels)
+        if order2:
+            kw.update(hist=self._hist, first=self._first)
+        elif rng:
+            kw.update(seeds=self._seeds, n_image=n_image)
+        else:
+            kw["noise"] = self._noise
+        return getattr(_C, name), kw
+
     def _capture(self, noise, masked=False, rng=False):
         """Capture one step -- the UNet forward, then mixdq_sampler_step (masked: mixdq_sampler_step_masked, reading the
         static z / noise0 / mask buffers made here; rng: the _rng entry points, reading the static seeds in place of
-        the step-noise buffer; three rows per image: mixdq_sampler_step3 with the same operands) -- on the static
-        buffers and return the graph."""
+        the step-noise buffer; three rows per image: mixdq_sampler_step3 with the same operands; _step_call chooses) --
+        on the static buffers and return the graph."""
         import torch
-        from mixdq_amd import _C
         dev = noise.device
         B, C, H, W = noise.shape
         forward = getattr(self.unet.forward, "__wrapped__", self.unet.forward)   # (under hip_graph_opt: the eager one)
-        n = B * C * H * W
         if self.schedule.uses_noise and not rng and self._noise is None:
             self._noise = self._nhwc(self.n_steps, B, dtype=torch.float32)
         if masked and not hasattr(self, "_z"):
@@ -496,36 +521,7 @@ class Sampler:
             self._noise0 = self._nhwc(B, dtype=torch.float32)
             self._mask = torch.zeros(B, H, W, dtype=torch.float32, device=dev)
             self._blend = torch.from_numpy(self.schedule.blend).to(dev)
-        # the binding and its operands behind (x, eps): chosen once, here, not inside one_step
-        blend = (self._z, self._noise0, self._mask, self._blend) if masked else ()
-        kw = dict(channels=C, n=n) if masked else dict(n=n)
-        if self.rows_per_image == 3 or self.guidance_rescale > 0.0:
-            # one binding for every mode: the operands of a mode that is off stay None
-            step_fn = _C.sampler_step3
-            tail = (self._in, self._coef, self._t_table, self._step, self._t, self.guidance_scale,
-                    self.image_guidance_scale)
-            if self.guidance_rescale > 0.0:
-                step_fn = _C.sampler_step_rescaled
-                tail += (self.guidance_rescale, self._rescale_ws)
-                kw.update(rows_per_image=self.rows_per_image, n_image=C * H * W)
-            if masked:
-                kw.update(z=self._z, noise0=self._noise0, mask=self._mask, blend=self._blend)
-            if self.schedule.order == 2:
-                kw.update(hist=self._hist, first=self._first)
-            elif rng:
-                kw.update(seeds=self._seeds, n_image=C * H * W)
-            else:
-                kw.update(noise=self._noise)
-        elif self.schedule.order == 2:
-            step_fn = _C.sampler_step_2m_masked if masked else _C.sampler_step_2m
-            tail = (self._in, self._hist, self._coef, self._t_table, self._step, self._first, self._t, *blend,
-                    self.guidance_scale, self.rows_per_image)
-        else:
-            step_fn = _C.sampler_step_masked if masked else _C.sampler_step
-            tail = (self._in, self._coef, self._t_table, self._step, self._t, *blend, self.guidance_scale,
-                    self.rows_per_image, None if rng else self._noise)
-            if rng:
-                kw.update(seeds=self._seeds, n_image=C * H * W)
+        step_fn, step_kw = self._step_call(masked, rng, C, B * C * H * W)   # chosen once, here, not inside one_step
         self._step_binding = step_fn.__name__       # (the binding the last capture recorded: tests read it)
 
         cond_kw = {} if self._cond_term is None else {"cond_term": self._cond_term}
@@ -542,7 +538,7 @@ class Sampler:
                     or any(a != b for a, b, d in zip(eps.stride(), self._in.stride(), eps.shape) if d > 1)):
                 raise RuntimeError("Sampler: the UNet's output is not an FP16 tensor of its input's shape in channels-"
                                    f"last storage (shape {tuple(eps.shape)}, strides {eps.stride()}, {eps.dtype})")
-            step_fn(self._x, eps, *tail, **kw)
+            step_fn(self._x, eps, **step_kw)
 
         self._reset(noise, None)
         side = torch.cuda.Stream(dev)

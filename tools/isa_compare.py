@@ -19,7 +19,8 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FILES = ["quantize", "fused_norm", "attention", "igemm", "igemm_aq", "igemm_ln", "iconv", "sampler", "vae", "image"]
+FILES = ["quantize", "fused_norm", "attention", "igemm", "igemm_aq", "igemm_ln", "iconv", "sampler", "vae", "image",
+         "sampler_rescale", "control"]             # (every unit of build.py, whichever object directory it goes to)
 
 
 def assemble(tree, out, files):
