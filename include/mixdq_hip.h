@@ -938,6 +938,40 @@ int mixdq_silu_f16(const void* x_f16, void* out_f16, int64_t n, mixdq_stream_t s
 int mixdq_hint_to_nhwc8_f16(const void* img, int dtype, int64_t sb, int64_t sc, int64_t sh, int64_t sw, void* out_f16,
                             int B, int C, int H, int W, mixdq_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Decoupled cross-attention (csrc/attention_ip.hip; IP-Adapter, diffusers' IPAdapterAttnProcessor2_0).  No reference
+ * counterpart.  ONE launch computes
+ *   out = attn(q, k, v) + s_0 * attn(q, ip_k[0], ip_v[0]) + ... + s_{n_ip-1} * attn(q, ip_k[n_ip-1], ip_v[n_ip-1])
+ * where every attn() is mixdq_attention_f16's FP16 result bit for bit (a softmax of its own per key set) and the sum is
+ * half-tensor arithmetic, left to right: acc = f16_rn(f32(acc) + f32(f16_rn(f32(o_j) * s_j))) starting from the text
+ * term (include/mixdq_math.h, mixdq_ip_*).  s_j == 0 (either sign) skips adapter j, whose keys and values are then not
+ * read; every adapter skipped: mixdq_attention_f16's own bits.  out: fp16 rows, or int8 rows with out_scale_inv /
+ * out_zero_point, quantized exactly as mixdq_attention_f16 does (MIXDQ_FLAG_UNFUSED and MIXDQ_FLAG_A4_0 included).
+ * q, k, v, out and their strides: as mixdq_attention_f16.  ip_k, ip_v, ip_tokens, ip_batch_stride, ip_row_stride: HOST
+ * arrays of n_ip entries, read during the call -- the operands travel in the kernel arguments, a captured graph holds
+ * them; ip_k[j] / ip_v[j]: fp16 [batch, ip_tokens[j], heads * 64] with the adapter's batch / row strides in ELEMENTS
+ * (multiples of 8; the k | v column slices of one packed projection are fine).  ip_scale: FP32 [n_ip] ON THE DEVICE,
+ * read by the kernel: one captured graph serves every scale.
+ * Shapes (MIXDQ_ERR_SHAPE otherwise): head_dim 64; 1 <= tkv <= 128; 1 <= ip_tokens[j] <= 128; each adapter's keys are
+ * padded to blocks of 32, at most MIXDQ_IP_MAX_BLOCKS blocks per launch; bits 8..15 of flags and MIXDQ_FLAG_CAUSAL
+ * must be 0.  n_ip outside 1 .. MIXDQ_IP_MAX_ADAPTERS, null arrays or pointers: MIXDQ_ERR_INVALID_ARG; strides not
+ * multiples of 8, pointers not 16-byte (int8 out: 8-byte, ip_scale: 4-byte) aligned: MIXDQ_ERR_ALIGNMENT.
+ * Launch: 128 query rows per workgroup, 32 KB + 8 KB per image block of LDS (csrc/attention_ip.hip).
+ * mixdq_attention_f16_ip_supported: 1 when the shape is one the kernel takes, 0 otherwise; launches nothing. */
+#define MIXDQ_IP_MAX_ADAPTERS 4
+#define MIXDQ_IP_MAX_BLOCKS 4
+int mixdq_attention_f16_ip_supported(int head_dim, int tkv, int n_ip, const int* ip_tokens);
+int mixdq_attention_f16_ip(const void* q_f16, const void* k_f16, const void* v_f16, void* out,
+                           int batch, int heads, int head_dim, int tq, int tkv,
+                           int64_t q_batch_stride, int64_t q_row_stride,
+                           int64_t k_batch_stride, int64_t k_row_stride,
+                           int64_t v_batch_stride, int64_t v_row_stride,
+                           int64_t out_batch_stride, int64_t out_row_stride,
+                           int n_ip, const void* const* ip_k, const void* const* ip_v, const int* ip_tokens,
+                           const int64_t* ip_batch_stride, const int64_t* ip_row_stride, const float* ip_scale,
+                           float softmax_scale, const float* out_scale_inv_or_null,
+                           const float* out_zero_point_or_null, int flags, mixdq_stream_t stream);
+
 /* Which kernel instantiation mixdq_qlinear_w8a8 / mixdq_qconv2d_w8a8 will launch for a problem of
  * M rows x N output channels (k_align = K for Linear, C for Conv2d; k_total = K or R*S*C): the block tile BM x BN x BK
  * and LDS stage count of `igemm_kernel<BM,BN,BK,STAGES,CONV>`, or zeros for the small-alignment

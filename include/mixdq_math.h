@@ -422,6 +422,25 @@ MIXDQ_HD float mixdq_control_scaled(float r, float c) { return MIXDQ_MUL_RN(r, c
 
 MIXDQ_HD float mixdq_control_sum(float a, float b) { return MIXDQ_ADD_RN(a, b); }
 
+/* ---- Decoupled cross-attention (mixdq_attention_f16_ip, csrc/attention_ip.hip; IP-Adapter), same rule: diffusers'
+ * IPAdapterAttnProcessor2_0 on FP16 tensors with FP32 scalars, hidden_states + scale * ip_hidden_states, adapters left to
+ * right.  For one output element, with o_t = mixdq_attention_f16(q, k, v) and o_j = mixdq_attention_f16(q, ip_k[j],
+ * ip_v[j]) as the FP16 values that entry point's short-key kernel returns (softmax steps of 64 keys, absent keys masked
+ * to -inf, P rounded to FP16, the normalised output o * (1 / l) rounded to FP16 -- in that kernel and in this one output
+ * columns 0 and 3 mod 4 round the exact product ONCE to FP16 (v_fma_mixlo_f16), columns 1 and 2 mod 4 round it to FP32
+ * and then to FP16), and the FP32 scales s_j:
+ *   acc = o_t
+ *   acc = f16_rn(f32(acc) + f32(f16_rn(f32(o_j) * s_j)))      for j = 0 .. n_ip - 1 in order
+ *   out = acc, or sat8(rint(f32(acc) * scale_inv + zero_point)) exactly as mixdq_attention_f16 quantizes its output
+ * An adapter whose s_j == 0 (either sign) is SKIPPED, its keys and values not read (diffusers skips a zero scale too);
+ * with every adapter skipped out is o_t's own bits.  The kernel multiplies only the 32-key blocks of an image key set
+ * that hold a real key; an absent block would add P = +0 products, so o_j differs from the stand-alone launch only
+ * where an accumulator holds a -0 that FP32 underflow produced and every real product of the step is a zero too: then
+ * the sign of a zero output.  mixdq_ip_scaled and mixdq_ip_sum are the two FP32 operations. */
+MIXDQ_HD float mixdq_ip_scaled(float o, float s) { return MIXDQ_MUL_RN(o, s); }
+
+MIXDQ_HD float mixdq_ip_sum(float a, float b) { return MIXDQ_ADD_RN(a, b); }
+
 /* ---- ControlNet hint ingest (mixdq_hint_to_nhwc8_f16, csrc/control.hip): a uint8 pixel on the [0, 1] scale, the FP32
  * value whose FP16 rounding the conditioning embedding reads: f32(u) / 255.0f, the division correctly rounded -- what
  * image.float() / 255 computes. */

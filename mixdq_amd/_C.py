@@ -1369,6 +1369,73 @@ def attention_f16(q, k, v, heads, scale_inv=None, zero_point=None, softmax_scale
     return out
 
 
+_lib.mixdq_attention_f16_ip.argtypes = [_vp] * 4 + [_i32] * 5 + [_i64] * 8 + [
+    _i32, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int),
+    ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), _vp, ctypes.c_float, _vp, _vp, _i32, _vp]
+_lib.mixdq_attention_f16_ip.restype = _i32
+_lib.mixdq_attention_f16_ip_supported.argtypes = [_i32, _i32, _i32, ctypes.POINTER(ctypes.c_int)]
+_lib.mixdq_attention_f16_ip_supported.restype = _i32
+IP_MAX_ADAPTERS = 4
+
+
+def attention_ip_supported(head_dim, tkv, ip_tokens):
+    """Does the one-launch kernel take this shape (mixdq_attention_f16_ip_supported)?  Launches nothing."""
+    n = len(ip_tokens)
+    return bool(_lib.mixdq_attention_f16_ip_supported(int(head_dim), int(tkv), n, (ctypes.c_int * max(n, 1))(*ip_tokens)))
+
+
+def attention_ip(q, k, v, ip_kv, ip_scale, heads, scale_inv=None, zero_point=None, softmax_scale=None, _abits=8):
+    """Decoupled cross-attention (IP-Adapter; mixdq_attention_f16_ip, include/mixdq_math.h mixdq_ip_*):
+
+        acc = attention_f16(q, k, v);  acc = f16(acc + f16(attention_f16(q, k_j, v_j) * s_j))  for (k_j, v_j) in ip_kv
+
+    q, k, v, heads, scale_inv / zero_point, softmax_scale, _abits: as `attention_f16`.  ip_kv: 1 .. 4 pairs (k_j, v_j) of
+    fp16 [B, T_j, C] tensors with unit stride along C, both with the SAME batch and row strides (the k | v column slices
+    of one packed projection).  ip_scale: fp32 [len(ip_kv)] on the device, read by the kernel (a row of a table is
+    fine): s_j == 0 skips adapter j, whose keys and values are then not read.
+    One launch where the library takes the shape (head width 64, <= 128 text keys, image keys padded to 32 per adapter
+    and at most 128 in all).  Anything else -- SD 1.5's head widths, more image keys -- runs the chain of `attention_f16`
+    launches and torch operations in that order: the same bits by the specification, more launches."""
+    for t, n in ((q, "q"), (k, "k"), (v, "v")):
+        _check(t.is_cuda and t.dtype == torch.float16 and t.dim() == 3 and t.stride(-1) == 1,
+               f"{n} should be a [B, T, C] fp16 GPU tensor with unit stride along C")
+    B, Tq, C = q.shape
+    _check(k.shape == v.shape and k.shape[0] == B and k.shape[2] == C, "q/k/v shapes disagree")
+    D = C // heads if heads > 0 else 0
+    _check(C == heads * D and D in ATTENTION_HEAD_DIMS and D != 512, "head_dim must be 64, 40, 80 or 160")
+    n = len(ip_kv)
+    _check(1 <= n <= IP_MAX_ADAPTERS, "1 .. 4 image key sets")
+    for kj, vj in ip_kv:
+        for t in (kj, vj):
+            _check(t.is_cuda and t.device == q.device and t.dtype == torch.float16 and t.dim() == 3
+                   and t.stride(-1) == 1 and t.shape[0] == B and t.shape[2] == C and t.shape[1] >= 1,
+                   "image keys / values should be [B, T, C] fp16 tensors on q's device with unit stride along C")
+        _check(kj.shape == vj.shape and kj.stride() == vj.stride(), "an adapter's keys and values share shape and strides")
+    _check(ip_scale.is_cuda and ip_scale.device == q.device and ip_scale.dtype == torch.float32
+           and ip_scale.shape == (n,) and ip_scale.stride(0) == 1, "ip_scale should be an fp32 [n_ip] GPU tensor")
+    _check((scale_inv is None) == (zero_point is None), "scale_inv and zero_point come together")
+    quant = scale_inv is not None
+    sc = float(softmax_scale) if softmax_scale is not None else (0.125 if D == 64 else D ** -0.5)
+    tokens = [kj.shape[1] for kj, _ in ip_kv]
+    if not attention_ip_supported(D, k.shape[1], tokens):
+        acc = attention_f16(q, k, v, heads, softmax_scale=sc)
+        for j, (kj, vj) in enumerate(ip_kv):
+            term = (attention_f16(q, kj, vj, heads, softmax_scale=sc).float() * ip_scale[j]).half()
+            acc = torch.where(ip_scale[j] == 0, acc, (acc.float() + term.float()).half())
+        return quantize_per_tensor_to_int8(acc, scale_inv, zero_point, _abits=_abits) if quant else acc
+    out = torch.empty((B, Tq, C), dtype=torch.int8 if quant else torch.float16, device=q.device)
+    ptrs = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])
+    with torch.cuda.device(q.device):
+        code = _lib.mixdq_attention_f16_ip(
+            q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, heads, D, Tq, k.shape[1],
+            q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1), out.stride(0), out.stride(1),
+            n, ptrs([kj for kj, _ in ip_kv]), ptrs([vj for _, vj in ip_kv]), (ctypes.c_int * n)(*tokens),
+            (ctypes.c_int64 * n)(*[kj.stride(0) for kj, _ in ip_kv]), (ctypes.c_int64 * n)(*[kj.stride(1) for kj, _ in ip_kv]),
+            ip_scale.data_ptr(), sc, _ptr(scale_inv), _ptr(zero_point), FLAGS | _aflag(_abits), _stream())
+    _status(code, "attention_ip")
+    return out
+
+
 _lib.mixdq_embed_tokens_f16.argtypes = [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]
 _lib.mixdq_embed_tokens_f16.restype = _i32
 

@@ -407,11 +407,17 @@ class Sampler:
     rewrites the hint terms and the table per call, outside the graph: one graph per mode serves every scale and
     guidance window.  A ControlNet's forward still runs while its window is closed (a captured graph cannot branch);
     only its residuals' loads are saved.  Not with three rows per image (ValueError).  Without controlnet= a Sampler
-    captures exactly what it captured before, and refuses control=."""
+    captures exactly what it captured before, and refuses control=.
+
+    ip_adapter (a mixdq_amd.ip_adapter.IPAdapter, or a list of up to 4): every captured graph records the UNet with
+    ip= (one mixdq_attention_f16_ip launch per cross-attention) on static key | value buffers and a static
+    [layers, n_ip] scale table.  sample(ip_embeds= | ip_tokens=, ip_scale=) then REQUIRES one of the two and fills the
+    buffers per call, outside the graph (IPAdapter.tokens / .kv): other images and scales replay the same graph
+    objects.  Not with three rows per image (ValueError).  Without ip_adapter= nothing changes, and ip_* are refused."""
 
     def __init__(self, unet, kind, n_steps, guidance_scale=0.0, spacing=None, karras=False, *,
                  image_guidance_scale=None, prediction_type="epsilon", zero_snr=False, guidance_rescale=0.0,
-                 controlnet=None):
+                 controlnet=None, ip_adapter=None):
         self.unet = unet
         self.schedule = Schedule(kind, n_steps, spacing, karras, prediction_type, zero_snr)
         self.kind, self.n_steps = kind, int(n_steps)
@@ -445,6 +451,20 @@ class Sampler:
                 raise ValueError("Sampler: three guidance rows (image_guidance_scale) together with controlnet= are not "
                                  "supported yet")
             self.controlnets = nets
+        self.ip_adapters = []
+        if ip_adapter is not None:
+            from mixdq_amd.ip_adapter import IPAdapter
+            ads = list(ip_adapter) if isinstance(ip_adapter, (list, tuple)) else [ip_adapter]
+            if not ads or not all(isinstance(a, IPAdapter) for a in ads):
+                raise TypeError("Sampler: ip_adapter should be a mixdq_amd.ip_adapter.IPAdapter or a list of them")
+            if len(ads) > 4:
+                raise ValueError(f"Sampler: at most 4 IP-Adapters, got {len(ads)}")
+            if self.rows_per_image == 3:
+                raise ValueError("Sampler: three guidance rows (image_guidance_scale) together with ip_adapter= are not "
+                                 "supported: which rows see the image prompt is not defined")
+            self.ip_adapters = ads
+        self._ip_kv = None            # per IP-Adapter the static [R, T, sum 2 C_l] keys | values of every cross-attention
+        self._ip_scales = None        # the static [layers, n_ip] table of image-prompt scales
         self._hint_terms = None       # per ControlNet the static [R, C0, h, w] hint term
         self._ctl_scales = None       # the static [K, n_steps] table of conditioning scales
 
@@ -529,6 +549,9 @@ class Sampler:
 
         def one_step():
             ctl_kw = {}
+            if self.ip_adapters:
+                from mixdq_amd.ip_adapter import IPState
+                ctl_kw["ip"] = IPState(self._ip_kv, self._ip_scales)
             if nets:                                # every ControlNet on the UNet's own inputs, then the UNet with control=
                 from mixdq_amd.unet import ControlResiduals
                 res = [f(self._in, self._t, self._ehs, self._added, hint_term=h) for f, h in zip(nets, self._hint_terms)]
@@ -681,9 +704,60 @@ class Sampler:
                     buf[r * B:(r + 1) * B].copy_(term)
         self._ctl_scales.copy_(torch.from_numpy(table))
 
+    def _set_ip(self, embeds, tokens, scale, noise):
+        """sample(ip_embeds= | ip_tokens=, ip_scale=): per adapter the image tokens (IPAdapter.tokens of the embeddings;
+        B rows: the unconditional guidance block gets the projection of ZERO embeddings -- diffusers' default -- or, for
+        B rows of ready tokens, zero tokens; R rows are taken as given), their keys | values (IPAdapter.kv, one launch)
+        into the static buffers, and the [layers, n_ip] scale table -- in stream order, outside the graph."""
+        import torch
+        K = len(self.ip_adapters)
+        if K == 0:
+            if embeds is not None or tokens is not None:
+                raise TypeError("Sampler.sample: ip_embeds / ip_tokens given, but this Sampler was built without "
+                                "ip_adapter=")
+            return
+        if (embeds is None) == (tokens is None):
+            raise TypeError("Sampler.sample: this Sampler was built with ip_adapter=: exactly one of ip_embeds= and "
+                            "ip_tokens= is required")
+        given = embeds if embeds is not None else tokens
+        given = list(given) if isinstance(given, (list, tuple)) else [given]
+        if len(given) != K:
+            raise ValueError(f"Sampler.sample: one ip_embeds / ip_tokens tensor per IP-Adapter ({K}), got {len(given)}")
+        B = noise.shape[0]
+        R = B * self.rows_per_image
+        kvs = []
+        for j, (ad, g) in enumerate(zip(self.ip_adapters, given)):
+            if not (torch.is_tensor(g) and g.device == noise.device and g.shape[0] in (B, R)):
+                raise RuntimeError(f"Sampler.sample: ip input {j} should be a tensor of {B} or {R} rows on noise's device")
+            if g.shape[0] == B and R > B:            # rows: [unconditional | conditional]
+                g = torch.cat([torch.zeros_like(g), g], dim=0)
+            kvs.append(ad.kv(ad.tokens(g) if embeds is not None else g))
+        layers = len(self.ip_adapters[0].dims)
+        table = torch.zeros((layers, K), dtype=torch.float32)
+        def per_adapter(v):
+            vals = list(v) if isinstance(v, (list, tuple)) else [v] * K
+            if len(vals) != K:
+                raise ValueError(f"Sampler.sample: ip_scale should be a number or one per IP-Adapter ({K})")
+            return torch.tensor([float(x) for x in vals], dtype=torch.float32)
+        if isinstance(scale, dict):                   # {layer: scale}: the other layers stay at 0 (InstantStyle)
+            for layer, v in scale.items():
+                if not 0 <= int(layer) < layers:
+                    raise ValueError(f"Sampler.sample: ip_scale names layer {layer}: this UNet has {layers} cross-attentions")
+                table[int(layer)] = per_adapter(v)
+        else:
+            table[:] = per_adapter(scale)
+        if self._ip_kv is None:
+            self._ip_kv = [torch.zeros_like(t) for t in kvs]
+            self._ip_scales = torch.zeros((layers, K), dtype=torch.float32, device=noise.device)
+        for buf, t in zip(self._ip_kv, kvs):
+            if buf.shape != t.shape:
+                raise RuntimeError("Sampler.sample: ip inputs differ in shape from those the step graph was captured for")
+            buf.copy_(t)
+        self._ip_scales.copy_(table)
+
     def sample(self, noise, encoder_hidden_states, added_cond_kwargs=None, step_noise=None, *, init_latents=None,
                strength=None, mask=None, seed=None, cond=None, control=None, control_scale=1.0, control_start=0.0,
-               control_end=1.0):
+               control_end=1.0, ip_embeds=None, ip_tokens=None, ip_scale=1.0):
         """noise [B, C, H, W] (unit variance; FP32 or FP16), encoder_hidden_states [R, T, D] FP16 (R = B, 2B
         under guidance, or 3B with image_guidance_scale), added_cond_kwargs as the UNet takes them (R rows), step_noise [n_steps, B, C, H, W]: the
         noise each stochastic step adds (required where the schedule has a non-zero c: euler_ancestral and lcm with
@@ -725,9 +799,16 @@ class Sampler:
         a list with one per net.  `control_scale`, `control_start`, `control_end`: diffusers'
         controlnet_conditioning_scale, control_guidance_start and control_guidance_end, numbers or one per net.  They
         fill the static hint buffers and the scale table of this run; calls with other values replay the same graph
-        objects.  Orthogonal to everything above (`cond` composes: a ControlNet reads the latent channels)."""
+        objects.  Orthogonal to everything above (`cond` composes: a ControlNet reads the latent channels).
+
+        `ip_embeds` / `ip_tokens` (exactly one, required exactly when the Sampler was built with ip_adapter=): per
+        adapter the image embeddings [B or R, clip_embed_dim] or ready image tokens [B or R, T, cross_dim]; `ip_scale`:
+        a number, one per adapter, or {cross-attention index: either} with the other layers at 0 (_set_ip)."""
         import torch
         from mixdq_amd.quantize_sdxl import _copy_into
+        if (ip_embeds is not None or ip_tokens is not None) != bool(self.ip_adapters) or (ip_embeds is not None
+                                                                                         and ip_tokens is not None):
+            self._set_ip(ip_embeds, ip_tokens, ip_scale, None)                                # (raises)
         if control is None and self.controlnets:
             self._set_control(None, control_scale, control_start, control_end, None, 0)      # (raises)
         if control is not None and not self.controlnets:
@@ -791,6 +872,7 @@ class Sampler:
             raise RuntimeError("Sampler.sample: inputs differ in shape from those the step graph was captured for")
         self._set_cond(cond, noise)
         self._set_control(control, control_scale, control_start, control_end, noise, t0)
+        self._set_ip(ip_embeds, ip_tokens, ip_scale, noise)
         name = "_graph" + ("_masked" if mask is not None else "") + ("_rng" if rng else "")
         if getattr(self, name) is None:
             setattr(self, name, self._capture(noise, masked=mask is not None, rng=rng))
@@ -809,14 +891,15 @@ class Sampler:
         return self._x.clone()
 
     def sample_image(self, vae, noise, encoder_hidden_states, added_cond_kwargs=None, step_noise=None, *, seed=None,
-                     cond=None, control=None, control_scale=1.0, control_start=0.0, control_end=1.0):
+                     cond=None, control=None, control_scale=1.0, control_start=0.0, control_end=1.0, ip_embeds=None,
+                     ip_tokens=None, ip_scale=1.0):
         """sample(), then `vae.decode` (a mixdq_amd.vae.VAEDecoder, eager or under hip_graph_opt) of its latents on
         the same stream: nothing waits for the GPU in between.  Returns (FP32 latents, FP16 image [B, 3, 8H, 8W]).
         `seed`, `cond` and `control*` as in sample(): with seed `noise` may be the latent shape, and seed -> image is
         this one call."""
         latents = self.sample(noise, encoder_hidden_states, added_cond_kwargs, step_noise, seed=seed, cond=cond,
                               control=control, control_scale=control_scale, control_start=control_start,
-                              control_end=control_end)
+                              control_end=control_end, ip_embeds=ip_embeds, ip_tokens=ip_tokens, ip_scale=ip_scale)
         return latents, vae.decode(latents)
 
     def _latent_noise(self, latent_noise, latent_seed, noise, encoder_hidden_states, stream=None):
@@ -835,7 +918,7 @@ class Sampler:
 
     def img2img(self, enc, dec, image, noise, encoder_hidden_states, added_cond_kwargs=None, *, strength,
                 step_noise=None, latent_noise=None, seed=None, latent_seed=None, cond=None, control=None,
-                control_scale=1.0, control_start=0.0, control_end=1.0):
+                control_scale=1.0, control_start=0.0, control_end=1.0, ip_embeds=None, ip_tokens=None, ip_scale=1.0):
         """Image to image on one stream: `enc.encode(image, latent_noise)` (a mixdq_amd.vae.VAEEncoder; latent_noise
         None: the posterior's mode), sample(init_latents=that, strength=strength), then `dec.decode` (a VAEDecoder) --
         either VAE eager or under hip_graph_opt, nothing waits for the GPU in between.  noise: [B, C, H/8, W/8], what
@@ -845,7 +928,8 @@ class Sampler:
         z = enc.encode(image, self._latent_noise(latent_noise, latent_seed, noise, encoder_hidden_states))
         latents = self.sample(noise, encoder_hidden_states, added_cond_kwargs, step_noise, init_latents=z,
                               strength=strength, seed=seed, cond=cond, control=control, control_scale=control_scale,
-                              control_start=control_start, control_end=control_end)
+                              control_start=control_start, control_end=control_end, ip_embeds=ip_embeds,
+                              ip_tokens=ip_tokens, ip_scale=ip_scale)
         return latents, dec.decode(latents)
 
     def instruct(self, enc, dec, image, noise, encoder_hidden_states, added_cond_kwargs=None, *, step_noise=None,

@@ -606,6 +606,16 @@ class ResnetBlock2D(nn.Module):
         return x + self.conv2(feed)
 
 
+def _ip_sum(o, terms, scales):
+    """include/mixdq_math.h, mixdq_ip_*: acc = f16(f32(acc) + f32(f16(f32(o_j) * s_j))) left to right from acc = o, an
+    adapter whose scale is 0 left out -- with the scales read on the device (capturable).  FP32 tensors (the CPU
+    path): the same operations without the roundings to FP16."""
+    for j, t in enumerate(terms):
+        term = (t.float() * scales[j]).to(o.dtype)
+        o = torch.where(scales[j] == 0, o, (o.float() + term.float()).to(o.dtype))
+    return o
+
+
 class Attention(nn.Module):
     def __init__(self, dim, cross_dim, head_dim):
         super().__init__()
@@ -618,7 +628,12 @@ class Attention(nn.Module):
 
     def forward(self, x, context=None):
         context = x if context is None else context
-        return self.to_out[0](self.attend(self.to_q(x), self.to_k(context), self.to_v(context)))
+        ip = self.__dict__.pop("_ip", None)           # (SDXLUNet.forward(ip=): this cross-attention's image keys / values)
+        q = self.to_q(x)
+        o = self.attend(q, self.to_k(context), self.to_v(context))
+        if ip is not None:
+            o = _ip_sum(o, [self.attend(q, kj, vj) for kj, vj in ip[0]], ip[1])
+        return self.to_out[0](o)
 
     def attend(self, q, k, v):
         B, T, C = q.shape
@@ -634,6 +649,9 @@ class Attention(nn.Module):
         values (77 text tokens) fit one workgroup's LDS: to_q's INT8 GEMM, the attention core and
         to_out.0's quantizer are ONE launch; q never exists in memory.  Bit-identical to the
         three-step path it replaces (tests/test_fused_gpu.py)."""
+        ip = self.__dict__.pop("_ip", None)
+        if ip is not None:                             # decoupled cross-attention: to_q as its own GEMM
+            return self.ip_attend_out(_run(self.to_q, feed_q), k, v, ip, residual, next_ln)
         if _cross_fusable(self, feed_q, k, v, residual):
             from mixdq_amd import _C
             q, out = self.to_q, self.to_out[0]
@@ -641,6 +659,35 @@ class Attention(nn.Module):
                                          q.scale, q.bias0, k, v, *_qp(out), **q._wkw(), _abits=_abits(out))
             return _gemm_res_ln(out, o_int, residual, next_ln)
         return self.attend_out(_run(self.to_q, feed_q), k, v, residual, next_ln=next_ln)
+
+    def ip_attend_out(self, q, k, v, ip, residual, next_ln=None):
+        """residual + to_out[0](attn(q, k, v) + sum_j s_j attn(q, k_j, v_j)) (IP-Adapter): ONE
+        mixdq_attention_f16_ip launch that emits to_out[0]'s INT8 operand when it is W8A8; de-fused: the chain of
+        attention_f16 launches and torch operations it stands for, same bits."""
+        from mixdq_amd import _C
+        from mixdq_amd.nn.glue import ATTENTION_HEAD_DIMS
+        pairs, scales = ip
+        out = self.to_out[0]
+        C = q.shape[-1]
+        D = C // self.heads
+
+        def plain(y):
+            return y, (None if next_ln is None else _ln_feed(next_ln[0], y, next_ln[1]))
+        ok = (C == self.heads * D and D in ATTENTION_HEAD_DIMS
+              and all(_fusable_f16(t) and t.dim() == 3 and t.stride(-1) == 1 and t.stride(0) % 8 == 0
+                      and t.stride(1) % 8 == 0 and t.data_ptr() % 16 == 0 for t in [q, k, v] + [t for p in pairs for t in p]))
+        if not ok:
+            o = _ip_sum(self.attend(q, k, v), [self.attend(q, kj, vj) for kj, vj in pairs], scales)
+            return plain(_linear_res(out, o, residual))
+        sc = None if D == 64 else D ** -0.5
+        if DEFUSE:
+            o = _ip_sum(_C.attention_f16(q, k, v, self.heads, softmax_scale=sc),
+                        [_C.attention_f16(q, kj, vj, self.heads, softmax_scale=sc) for kj, vj in pairs], scales)
+            return plain(_linear_res(out, o, residual))
+        if _accel(out) and residual.is_contiguous():
+            o_int = _C.attention_ip(q, k, v, pairs, scales, self.heads, *_qp(out), softmax_scale=sc, _abits=_abits(out))
+            return _gemm_res_ln(out, o_int, residual, next_ln)
+        return plain(_linear_res(out, _C.attention_ip(q, k, v, pairs, scales, self.heads, softmax_scale=sc), residual))
 
     def attend_out(self, q, k, v, residual, prefetch=None, next_ln=None):
         """residual + to_out[0](attention(q, k, v)) on the fused path: the HIP FP16 attention core
@@ -1533,8 +1580,12 @@ class SDXLUNet(FusedGraph):
 
     def forward(self, sample, timestep, encoder_hidden_states, added_cond_kwargs=None,
                 return_dict=False, cond_term=None, down_block_additional_residuals=None,
-                mid_block_additional_residual=None, control=None):
-        """`cond_term` (UNets with cond_channels > 0): what cond_term(cond) returned, one row per row of `sample`,
+                mid_block_additional_residual=None, control=None, ip=None):
+        """`ip`: a mixdq_amd.ip_adapter.IPState -- per adapter (1 to 4) the keys | values IPAdapter.kv made for every
+        cross-attention, one row per row of `sample`, and the FP32 [layers, n_ip] scale table on the device; every
+        cross-attention then adds its image terms (one mixdq_attention_f16_ip launch on the fused path).
+
+        `cond_term` (UNets with cond_channels > 0): what cond_term(cond) returned, one row per row of `sample`,
         which then has out_channels channels -- conv_in runs split, without a concatenated input.  Without it such a
         UNet takes all in_channels channels in `sample` (the drop-in form).
 
@@ -1546,8 +1597,39 @@ class SDXLUNet(FusedGraph):
         self._check_cond_term(sample, cond_term)
         control = self._control_of(sample, down_block_additional_residuals, mid_block_additional_residual, control)
         emb = self._embed(sample, timestep, added_cond_kwargs)
-        return self._with_prefetch(sample, lambda: self._forward_body(sample, emb, encoder_hidden_states, cond_term,
-                                                                      control))
+        attns = self._set_ip(sample, ip)
+        try:
+            return self._with_prefetch(sample, lambda: self._forward_body(sample, emb, encoder_hidden_states, cond_term,
+                                                                          control))
+        finally:
+            for a in attns:
+                a.__dict__.pop("_ip", None)
+
+    def _set_ip(self, sample, ip):
+        """Hand every cross-attention its image keys / values and its row of the scale table (popped where it runs);
+        returns the attentions that got one."""
+        if ip is None:
+            return []
+        attns = cross_attentions(self)
+        kv, scales = getattr(ip, "kv", None), getattr(ip, "scales", None)
+        if not isinstance(kv, (list, tuple)) or not 1 <= len(kv) <= 4:
+            raise RuntimeError("SDXLUNet.forward: ip should be a mixdq_amd.ip_adapter.IPState with 1 to 4 adapters")
+        width = 2 * sum(a.to_k.out_features for a in attns)
+        for j, t in enumerate(kv):
+            if not (torch.is_tensor(t) and t.dim() == 3 and t.shape[0] == sample.shape[0] and t.shape[2] == width
+                    and t.dtype == sample.dtype and t.device == sample.device and t.stride(2) == 1):
+                raise RuntimeError(f"SDXLUNet.forward: ip.kv[{j}] should be a [{sample.shape[0]}, T, {width}] "
+                                   f"{sample.dtype} tensor on the sample's device (IPAdapter.kv, one row per sample row)")
+        if not (torch.is_tensor(scales) and scales.dtype == torch.float32 and scales.device == sample.device
+                and tuple(scales.shape) == (len(attns), len(kv)) and scales.is_contiguous()):
+            raise RuntimeError(f"SDXLUNet.forward: ip.scales should be a contiguous fp32 [{len(attns)}, {len(kv)}] tensor "
+                               "on the sample's device")
+        off = 0
+        for n, a in enumerate(attns):
+            c = a.to_k.out_features
+            a.__dict__["_ip"] = ([(t[..., off:off + c], t[..., off + c:off + 2 * c]) for t in kv], scales[n])
+            off += 2 * c
+        return attns
 
     # ---- ControlNet residuals (DESIGN.md section 3.35) ------------------------------------------------------------
     def n_skips(self) -> int:
@@ -1634,6 +1716,11 @@ class SDXLUNet(FusedGraph):
         else:
             x = self.conv_out(self.conv_act(self.conv_norm_out(x)))
         return (x,)
+
+
+def cross_attentions(unet):
+    """The cross-attentions (attn2 of every transformer block) in registration order: down, mid, up."""
+    return [m.attn2 for m in unet.modules() if isinstance(m, BasicTransformerBlock)]
 
 
 _UNIT_SCALE = {}
