@@ -971,6 +971,25 @@ int mixdq_attention_f16_ip(const void* q_f16, const void* k_f16, const void* v_f
                            const int64_t* ip_batch_stride, const int64_t* ip_row_stride, const float* ip_scale,
                            float softmax_scale, const float* out_scale_inv_or_null,
                            const float* out_zero_point_or_null, int flags, mixdq_stream_t stream);
+/* The same launch at SD 1.5's head widths (csrc/attention_ip_hd.hip): head_dim 40, 80 or 160, every term
+ * mixdq_attention_f16's FP16 result AT THAT WIDTH bit for bit; arguments, arithmetic, status codes, alignment and
+ * 32-bit offset rules exactly as mixdq_attention_f16_ip (ip_k[j] / ip_v[j]: [batch, ip_tokens[j], heads * head_dim]).
+ * Shapes (MIXDQ_ERR_SHAPE otherwise): 1 <= tkv <= 128; 1 <= ip_tokens[j] <= 128; at most MIXDQ_IP_MAX_BLOCKS blocks of
+ * 32 image keys; and the launch's LDS within a CU's 160 KB -- the text keys' 64-key stages (17 / 23 / 41 KB each at
+ * head_dim 40 / 80 / 160; at least the 18 / 26 / 42 KB of the output staging) plus 9 / 12 / 21 KB per block: every
+ * shape at 40 and 80; at 160 four blocks with tkv <= 64, three with more.  Separate names on purpose: the width-64
+ * predicate stays false at these widths.  mixdq_attention_f16_ip_hd_supported launches nothing. */
+int mixdq_attention_f16_ip_hd_supported(int head_dim, int tkv, int n_ip, const int* ip_tokens);
+int mixdq_attention_f16_ip_hd(const void* q_f16, const void* k_f16, const void* v_f16, void* out,
+                              int batch, int heads, int head_dim, int tq, int tkv,
+                              int64_t q_batch_stride, int64_t q_row_stride,
+                              int64_t k_batch_stride, int64_t k_row_stride,
+                              int64_t v_batch_stride, int64_t v_row_stride,
+                              int64_t out_batch_stride, int64_t out_row_stride,
+                              int n_ip, const void* const* ip_k, const void* const* ip_v, const int* ip_tokens,
+                              const int64_t* ip_batch_stride, const int64_t* ip_row_stride, const float* ip_scale,
+                              float softmax_scale, const float* out_scale_inv_or_null,
+                              const float* out_zero_point_or_null, int flags, mixdq_stream_t stream);
 
 /* Which kernel instantiation mixdq_qlinear_w8a8 / mixdq_qconv2d_w8a8 will launch for a problem of
  * M rows x N output channels (k_align = K for Linear, C for Conv2d; k_total = K or R*S*C): the block tile BM x BN x BK

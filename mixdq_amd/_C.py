@@ -1375,6 +1375,10 @@ _lib.mixdq_attention_f16_ip.argtypes = [_vp] * 4 + [_i32] * 5 + [_i64] * 8 + [
 _lib.mixdq_attention_f16_ip.restype = _i32
 _lib.mixdq_attention_f16_ip_supported.argtypes = [_i32, _i32, _i32, ctypes.POINTER(ctypes.c_int)]
 _lib.mixdq_attention_f16_ip_supported.restype = _i32
+_lib.mixdq_attention_f16_ip_hd.argtypes = _lib.mixdq_attention_f16_ip.argtypes
+_lib.mixdq_attention_f16_ip_hd.restype = _i32
+_lib.mixdq_attention_f16_ip_hd_supported.argtypes = _lib.mixdq_attention_f16_ip_supported.argtypes
+_lib.mixdq_attention_f16_ip_hd_supported.restype = _i32
 IP_MAX_ADAPTERS = 4
 
 
@@ -1382,6 +1386,13 @@ def attention_ip_supported(head_dim, tkv, ip_tokens):
     """Does the one-launch kernel take this shape (mixdq_attention_f16_ip_supported)?  Launches nothing."""
     n = len(ip_tokens)
     return bool(_lib.mixdq_attention_f16_ip_supported(int(head_dim), int(tkv), n, (ctypes.c_int * max(n, 1))(*ip_tokens)))
+
+
+def attention_ip_hd_supported(head_dim, tkv, ip_tokens):
+    """Does the one-launch kernel of head widths 40 / 80 / 160 take this shape (mixdq_attention_f16_ip_hd_supported)?
+    Launches nothing."""
+    n = len(ip_tokens)
+    return bool(_lib.mixdq_attention_f16_ip_hd_supported(int(head_dim), int(tkv), n, (ctypes.c_int * max(n, 1))(*ip_tokens)))
 
 
 def attention_ip(q, k, v, ip_kv, ip_scale, heads, scale_inv=None, zero_point=None, softmax_scale=None, _abits=8):
@@ -1393,9 +1404,11 @@ def attention_ip(q, k, v, ip_kv, ip_scale, heads, scale_inv=None, zero_point=Non
     fp16 [B, T_j, C] tensors with unit stride along C, both with the SAME batch and row strides (the k | v column slices
     of one packed projection).  ip_scale: fp32 [len(ip_kv)] on the device, read by the kernel (a row of a table is
     fine): s_j == 0 skips adapter j, whose keys and values are then not read.
-    One launch where the library takes the shape (head width 64, <= 128 text keys, image keys padded to 32 per adapter
-    and at most 128 in all).  Anything else -- SD 1.5's head widths, more image keys -- runs the chain of `attention_f16`
-    launches and torch operations in that order: the same bits by the specification, more launches."""
+    One launch where the library takes the shape: <= 128 text keys, image keys padded to 32 per adapter and at most 128
+    in all, at head width 64 (mixdq_attention_f16_ip) and at SD 1.5's 40 / 80 / 160 (mixdq_attention_f16_ip_hd; at 160
+    with more than 64 text keys at most 96 padded image keys: `attention_ip_hd_supported`).  Anything else -- more
+    image keys -- runs the chain of `attention_f16` launches and torch operations in that order: the same bits by the
+    specification, more launches."""
     for t, n in ((q, "q"), (k, "k"), (v, "v")):
         _check(t.is_cuda and t.dtype == torch.float16 and t.dim() == 3 and t.stride(-1) == 1,
                f"{n} should be a [B, T, C] fp16 GPU tensor with unit stride along C")
@@ -1417,7 +1430,9 @@ def attention_ip(q, k, v, ip_kv, ip_scale, heads, scale_inv=None, zero_point=Non
     quant = scale_inv is not None
     sc = float(softmax_scale) if softmax_scale is not None else (0.125 if D == 64 else D ** -0.5)
     tokens = [kj.shape[1] for kj, _ in ip_kv]
-    if not attention_ip_supported(D, k.shape[1], tokens):
+    entry = (_lib.mixdq_attention_f16_ip if attention_ip_supported(D, k.shape[1], tokens) else
+             _lib.mixdq_attention_f16_ip_hd if attention_ip_hd_supported(D, k.shape[1], tokens) else None)
+    if entry is None:
         acc = attention_f16(q, k, v, heads, softmax_scale=sc)
         for j, (kj, vj) in enumerate(ip_kv):
             term = (attention_f16(q, kj, vj, heads, softmax_scale=sc).float() * ip_scale[j]).half()
@@ -1426,7 +1441,7 @@ def attention_ip(q, k, v, ip_kv, ip_scale, heads, scale_inv=None, zero_point=Non
     out = torch.empty((B, Tq, C), dtype=torch.int8 if quant else torch.float16, device=q.device)
     ptrs = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])
     with torch.cuda.device(q.device):
-        code = _lib.mixdq_attention_f16_ip(
+        code = entry(
             q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, heads, D, Tq, k.shape[1],
             q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1), out.stride(0), out.stride(1),
             n, ptrs([kj for kj, _ in ip_kv]), ptrs([vj for _, vj in ip_kv]), (ctypes.c_int * n)(*tokens),

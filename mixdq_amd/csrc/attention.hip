@@ -131,11 +131,6 @@ __device__ __forceinline__ void glds16(const void* gsrc, char* lds_wave_base) {
       (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
 }
 
-template <int OFF>
-__device__ __forceinline__ void lds_read128_imm(v8h& d, unsigned addr) {
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF) : "memory");
-}
-
 // Running state of one wave's 32 query rows.
 struct AttnState {
   v16f o[2], lsum;               // O^T accumulators (d 0..31, 32..63); row sums, every register equal
@@ -766,39 +761,7 @@ int launch_attn(AttnParams& p, int batch, bool quant, bool a4, hipStream_t strea
 // Padding slots of an image receive a copy of the row's first chunk (every LDS-DMA lane writes; finite bytes).
 // Workgroups of WAVES x 32 query rows (4 or 2, chosen from ONE image as for head_dim 64); a wave's arithmetic does
 // not depend on WAVES or on the batch, so every form and every batch row give the same bits.
-template <int D>
-struct AttnHd {
-  static constexpr int DC = D / 8;                                   // 16-B chunks of a head row
-  static constexpr int KS = (D + 15) / 16;
-  static constexpr int DB = (D + 31) / 32;
-  static constexpr int PCK = DC | 1;
-  static constexpr int PCV = DC <= 4 ? 4 : 4 + 8 * ((DC - 4 + 7) / 8);
-  static constexpr int PK = 16 * PCK, PV = 16 * PCV;
-  static constexpr int SB = kKeys * (PK + PV);                       // one stage: K image then V image
-  static constexpr int PO = DB * 64 + 16;                            // output staging row
-  static constexpr int smem(int waves) { return 2 * SB > waves * 32 * PO ? 2 * SB : waves * 32 * PO; }
-  // the short-key form: waves per SIMD its register budget is compiled for (D = 160 keeps O^T alone in 80 registers)
-  static constexpr int SHORT_WPE = D <= 40 ? 4 : D <= 80 ? 3 : 2;
-  static constexpr int smem_short(int ntiles) { return ntiles * SB > 4 * 32 * PO ? ntiles * SB : 4 * 32 * PO; }
-  static_assert(D % 8 == 0 && DB * 64 <= PV && 2 * D <= PK, "geometry");
-};
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(f);
-  }
-}
-
-template <int OFF0, int OFF1>
-__device__ __forceinline__ void tr_read2_at(VFrag& f, unsigned addr) {
-  asm volatile("ds_read_b64_tr_b16 %0, %2 offset:%3\n\tds_read_b64_tr_b16 %1, %2 offset:%4"
-               : "=&v"(f.r.lo), "=&v"(f.r.hi)
-               : "v"(addr), "n"(OFF0), "n"(OFF1)
-               : "memory");
-}
-
+// (AttnHd<D>, static_for, tr_read2_at: csrc/attn_core.h, shared with csrc/attention_ip_hd.hip)
 template <int D, int WAVES, bool QUANT, bool A4 = false>
 __global__ __launch_bounds__(WAVES * 64) void attn_hd_kernel(const AttnParams p) {
   using G = AttnHd<D>;

@@ -3,8 +3,10 @@ attention_f16 per key set, torch half operations, quantize_per_tensor_to_int8 --
 with to_out.0's INT8 operand as the result (the chain scales with a host scalar, `acc + 0.6 * o_j`: the shortest chain a
 user could write, not `_C.attention_ip`'s capturable fallback, which has more launches).  SDXL's two cross-attention
 shapes, batch 1 and a guided pair of rows.  Then a whole SDXL UNet forward with and without an adapter (unet_steps).
+`--model sd15`: the same at SD 1.5's four cross-attention shapes at 512 px (eight heads of 40 / 80 / 160 columns:
+mixdq_attention_f16_ip_hd) and on the SD 1.5 UNet.
 
-    python tools/bench_ip_adapter.py [--out profiles/ip_adapter_bench.txt] [--rounds 7] [--replays 200]
+    python tools/bench_ip_adapter.py [--model sdxl|sd15] [--out profiles/ip_adapter[_hd]_bench.txt] [--rounds 7] [--replays 1000]
 
 Each figure is the median over `rounds` of the time of `replays` graph replays of 10 launches (device events),
 the two forms alternating within a round; the spread is min .. max of the rounds.
@@ -19,7 +21,9 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import mixdq_amd._C as C  # noqa: E402
 
-SHAPES = [(4096, 640, 10), (1024, 1280, 20)]      # (query tokens, channels, heads) of SDXL's two transformer levels
+# (query tokens, channels, heads) of the cross-attentions: SDXL's two transformer levels at 1024 px; SD 1.5's at 512 px
+SHAPES = {"sdxl": [(4096, 640, 10), (1024, 1280, 20)],
+          "sd15": [(4096, 320, 8), (1024, 640, 8), (256, 1280, 8), (64, 1280, 8)]}
 PER_GRAPH = 10
 
 
@@ -44,29 +48,32 @@ def time_us(g, replays):
 
 
 def unet_steps(dev, args):
-    """A whole SDXL UNet forward (1024 px, uniform W8A8 + BOS, fused, from a graph) without an adapter, with one 4-token
-    adapter at scale 0.6, and with that adapter at scale 0 -- every cross-attention then runs to_q as its own GEMM and
-    a text-only mixdq_attention_f16_ip launch where the plain forward has the one-launch to_q + cross-attention at
-    batch 1: that difference is the price of the lost fusion."""
+    """A whole UNet forward (SDXL at 1024 px or SD 1.5 at 512 px, uniform W8A8 + BOS, fused, from a graph) without an
+    adapter, with one 4-token adapter at scale 0.6, and with that adapter at scale 0 -- every cross-attention then runs
+    to_q as its own GEMM and a text-only mixdq_attention_f16_ip[_hd] launch where SDXL's plain forward has the one-launch
+    to_q + cross-attention at batch 1: that difference is the price of the lost fusion (SD 1.5's plain forward has no
+    such launch: nothing is lost there)."""
     import bench
     from mixdq_amd.calib import calibrate, precompute_bos
     from mixdq_amd.ip_adapter import IPState, build_ip_adapter
     from mixdq_amd.quantize_sdxl import example_inputs, quantize_unet
-    from mixdq_amd.unet import SDXL_CONFIG, build_unet, quantizable_layers
-    out = ["# whole SDXL UNet forward, ms: plain | adapter, scale 0.6 | adapter, scale 0 (text-only launches); median "
+    from mixdq_amd.unet import SD15_CONFIG, SDXL_CONFIG, build_unet, quantizable_layers
+    cfg, latent, embed = (SDXL_CONFIG, 128, 1280) if args.model == "sdxl" else (SD15_CONFIG, 64, 1024)
+    out = [f"# whole {args.model} UNet forward, ms: plain | adapter, scale 0.6 | adapter, scale 0 (text-only launches); median "
            f"[min .. max] of {args.rounds} alternating rounds of 10 replays"]
-    unet = build_unet(dev, cfg=SDXL_CONFIG)
-    adapter = build_ip_adapter(SDXL_CONFIG, 1280, device=dev)
+    unet = build_unet(dev, cfg=cfg)
+    adapter = build_ip_adapter(cfg, embed, device=dev)
     for B in (1, 2):
-        inp = example_inputs(B, 128, dev, seed=42)
+        inp = example_inputs(B, latent, dev, seed=42, cfg=cfg)
         if B == 1:
             with torch.no_grad():
                 ckpt = calibrate(unet, [inp])
             names = list(quantizable_layers(unet))
-            quantize_unet(unet, bench.Cfg({n: 8 for n in names}, {n: 8 for n in names}), ckpt, bos=True,
+            act = {n: 8 for n in names if args.model == "sdxl" or n not in ("conv_in", "conv_out")}
+            quantize_unet(unet, bench.Cfg({n: 8 for n in names}, act), ckpt, bos=True,
                           bos_dict=precompute_bos(unet, inp["encoder_hidden_states"]))
             unet.set_fused(True)
-        ip = IPState([adapter.kv(adapter.tokens(torch.randn(B, 1280, device=dev).half()))],
+        ip = IPState([adapter.kv(adapter.tokens(torch.randn(B, embed, device=dev).half()))],
                      torch.full((len(adapter.dims), 1), 0.6, device=dev))
         with torch.no_grad():
             graphs = {}
@@ -100,10 +107,12 @@ def unet_steps(dev, args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join("profiles", "ip_adapter_bench.txt"))
+    ap.add_argument("--model", choices=("sdxl", "sd15"), default="sdxl")
+    ap.add_argument("--out", default=None)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--replays", type=int, default=1000)
     args = ap.parse_args()
+    args.out = args.out or os.path.join("profiles", "ip_adapter_bench.txt" if args.model == "sdxl" else "ip_adapter_hd_bench.txt")
     assert torch.cuda.is_available(), "needs a GPU"
     dev = "cuda:0"
     gen = torch.Generator(device=dev).manual_seed(5)
@@ -112,7 +121,7 @@ def main():
     lines = [f"# {torch.cuda.get_device_name(0)}; us per cross-attention, INT8 output; median of {args.rounds} rounds "
              f"[min .. max], {args.replays} replays x {PER_GRAPH} launches per round",
              "# tq    C  B  image tokens   one launch               chain                    chain / one"]
-    for tq, ch, heads in SHAPES:
+    for tq, ch, heads in SHAPES[args.model]:
         for B in (1, 2):
             for tokens in ((4,), (16,), (4, 4), (16, 16)):
                 q, kv = rnd(B, tq, ch), rnd(B, 77, 2 * ch)
