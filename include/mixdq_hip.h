@@ -1049,6 +1049,61 @@ int mixdq_gelu_table(uint16_t* out_device, mixdq_stream_t stream);
  * (2 * (n_pos + n_neg) bytes) unless null.  No reference counterpart (stock nn.SiLU). */
 int mixdq_silu_table(uint16_t* out_device_or_null, int* n_pos, int* n_neg, mixdq_stream_t stream);
 
+/* ---- LoRA on quantized layers: merge and re-quantize in one launch (csrc/lora.hip) --------
+ * W'[n, k] = f32(W[n, k]) + sum_r f32(Bs[n, r] * Acat[r, k]),  Bs[n, r] = f16(svec[r] * f32(Bcat[n, r]))  (0 where
+ * svec[r] == 0), quantized with the layer's own quantizer and written IN PLACE into the buffers the GEMM / conv
+ * kernels read (arithmetic: include/mixdq_math.h mixdq_lora_*).  One launch serves a table of layers; every layer is
+ * a row-major matrix [N, Kf] in its stored order (Linear: Kf = K; conv: Kf = R*S*C, channels-last).  No reference
+ * counterpart (the reference merges LoRA into the float weights before it quantizes). */
+enum {
+  MIXDQ_LORA_INT8 = 0,   /* out: int8 [N, Kf]                                                             */
+  MIXDQ_LORA_W4 = 1,     /* out: MIXDQ_FLAG_W4's nibble-planar-per-8 bytes [N, Kf / 2]; Kf % 32 == 0     */
+  MIXDQ_LORA_F16 = 2,    /* out: f16(W') [N, Kf] (FP-fallback layers); no scale, no sums                  */
+  MIXDQ_LORA_W2 = 3      /* packed-W2 storage: refused (MIXDQ_ERR_SHAPE)                                  */
+};
+enum {
+  MIXDQ_LORA_KEEP = 0,   /* delta_n = weight_scales[n] as it is: one pass                                 */
+  MIXDQ_LORA_ABSMAX = 1  /* delta_n = max_k |W'[n, k]| / (2^(bits-1) - 1) (an all-zero row keeps its delta_n): two
+                            passes, the second RECOMPUTES the low-rank product                            */
+};
+typedef struct mixdq_lora_layer {
+  const void* W;                 /* f16 master: element (n, k) at W[n * ldw + w_col0 + k], n a LOGICAL row  */
+  const void* Bcat;              /* f16 [N, R]: the adapters' B factors, stacked along the rank             */
+  const void* Acat;              /* f16 [R, Kf]: the adapters' A factors in the layer's stored column order */
+  const float* svec;             /* [R]: s_j * alpha_j / r_j on adapter j's ranks; 0 contributes nothing    */
+  const int32_t* row_map;        /* [N] logical row -> stored row, or null (identity)                       */
+  void* out;                     /* by `mode`; rows at the STORED row, dense                                */
+  float* weight_scales;          /* [N] delta_n (read under KEEP and for all-zero rows; written under ABSMAX) */
+  float* wsum;                   /* [N, Kf / tap_len] or null: (float) exact integer sum of q over each tap */
+  float* bias0;                  /* [N] or null: (float)(sum of the row's q) * act_zero_point[0]            */
+  float* scale;                  /* [N]: delta_n * act_scale[0]                                             */
+  const float* act_scale;        /* [1]                                                                     */
+  const float* act_zero_point;   /* [1]                                                                     */
+  int64_t ldw;                   /* master row stride in elements, % 4 == 0                                 */
+  int32_t w_col0;                /* master column offset in elements, % 4 == 0                              */
+  int32_t N, Kf, R;              /* R % 32 == 0, 32 <= R <= 256; Kf % 4 == 0                                */
+  int32_t mode, rule;            /* MIXDQ_LORA_*                                                            */
+  int32_t bits;                  /* the quantizer's width: 8, 4 or 2 (INT8 storage), 4 or 2 (W4 storage)     */
+  int32_t tap_len;               /* columns per sum of `wsum`: Kf (Linear, 1x1 conv) or C (a padded conv's per-tap
+                                    sums); % 4 == 0, divides Kf, at most 16 taps                            */
+} mixdq_lora_layer;
+#define MIXDQ_LORA_ROWS 16       /* output rows a workgroup owns, over the whole Kf */
+/* Host only: the launch order of a table -- `order[i]` = index of the layer that comes i-th, longest rows (largest
+ * Kf) first, ties in table order -- and `prefix[i]` = first workgroup of the i-th layer in that order, prefix[n] =
+ * the grid (sum of ceil(N / MIXDQ_LORA_ROWS)).  Returns the grid, or a negative status. */
+int mixdq_lora_table(const mixdq_lora_layer* layers_host, int n_layers, int32_t* order, int32_t* prefix);
+/* Host only: the status mixdq_lora_requant would answer for these descriptors (its checks, nothing launched). */
+int mixdq_lora_status(const mixdq_lora_layer* layers_host, int n_layers);
+/* One launch over `n_layers` descriptors.  `layers_host`: the descriptors IN LAUNCH ORDER (mixdq_lora_table's), looked
+ * at on the host; `layers_device`: the same bytes in device memory; `prefix_device`: int32 [n_layers + 1].
+ * Errors, nothing launched: null pointers, n_layers < 1, N < 1, an unknown mode / rule, bits that do not fit the mode,
+ * a missing pointer of an integer mode: MIXDQ_ERR_INVALID_ARG; R % 32 != 0 or outside 32..256, Kf % 4 != 0, W4 with
+ * Kf % 32 != 0, W2 storage, tap_len that does not divide Kf into at most 16 whole groups of 4, ldw / w_col0 % 4 != 0,
+ * W / Bcat / Acat not 8-byte, out or svec (read four at a time) not 16-byte, another FP32 vector or the row map not
+ * 4-byte aligned: MIXDQ_ERR_SHAPE. */
+int mixdq_lora_requant(const mixdq_lora_layer* layers_host, const mixdq_lora_layer* layers_device,
+                       const int32_t* prefix_device, int n_layers, mixdq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

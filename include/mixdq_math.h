@@ -446,4 +446,47 @@ MIXDQ_HD float mixdq_ip_sum(float a, float b) { return MIXDQ_ADD_RN(a, b); }
  * image.float() / 255 computes. */
 MIXDQ_HD float mixdq_hint_unit(uint32_t u) { return MIXDQ_DIV_RN((float)u, 255.0f); }
 
+/* ---- LoRA merge + re-quantize (mixdq_lora_requant, csrc/lora.hip).  For row n and column k of a layer:
+ *   Bs[n, r] = f16_rn(svec[r] * f32(Bcat[n, r]))      mixdq_lora_scaled; exactly +0 where svec[r] == 0 (either sign)
+ *   W'[n, k] = f32(W[n, k]) + sum_r f32(Bs[n, r] * Acat[r, k])      each product exact in FP32, the sum accumulated in
+ *              FP32 by the FP16 MFMA from an accumulator that starts as f32(W[n, k]); the order of the additions is the
+ *              hardware's and not specified -- an exact-input test is exact in any order, a random one is bounded by
+ *              (R + 2) * 2^-24 * (|W| + sum_r |Bs * A|)
+ *   delta_n  = weight_scales[n] (KEEP), or max_k |W'[n, k]| / (2^(bits-1) - 1), the division correctly rounded, the
+ *              old weight_scales[n] where the row is all zero (ABSMAX)                          mixdq_lora_delta
+ *   q        = min(max(rint(W' / delta_n), -2^(bits-1)), 2^(bits-1) - 1), ties to even: W' * (1.0f / delta_n) for an
+ *              8-bit quantizer (torch.quantize_per_channel's own arithmetic), the correctly rounded FP32 quotient for a
+ *              4- or 2-bit one (Path A's clamp(round(w / delta))); float -> int saturating, NaN -> 0   mixdq_lora_q
+ *   wsum     = (float) of the exact integer sum of q;  bias0 = wsum * act_zero_point;  scale = delta_n * act_scale
+ *   FP16 mode: out = f16_rn(W'). */
+/* The FP32 value whose FP16 rounding (the caller's f16_rn) is Bs: the product s * b of an FP32 and an FP16 value is exact
+ * in FP64 (24 + 11 bits); it is brought to FP32 by rounding to ODD, after which the FP16 rounding is the one rounding of
+ * the exact product that the specification asks for (a round-to-nearest FP32 step in between could round twice). */
+MIXDQ_HD float mixdq_lora_scaled(float s, float b) {
+  if (s == 0.0f) return 0.0f;
+  const double d = (double)s * (double)b;
+  float f = (float)d;
+  if ((double)f != d) {
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    if ((f < 0 ? -(double)f : (double)f) > (d < 0 ? -d : d)) u -= 1;   /* towards zero */
+    u |= 1u;                                                          /* inexact: odd */
+    memcpy(&f, &u, 4);
+  }
+  return f;
+}
+
+MIXDQ_HD float mixdq_lora_delta(float row_max, int bits, float old_delta) {
+  return row_max > 0.0f ? MIXDQ_DIV_RN(row_max, (float)((1 << (bits - 1)) - 1)) : old_delta;
+}
+
+/* The rounded quotient before the clamp, ties to even.  A 4- or 2-bit quantizer is Path A's
+ * torch.round(w.float() / delta): the correctly rounded FP32 quotient.  An 8-bit one is torch.quantize_per_channel, which
+ * does NOT divide: it multiplies by the FP32 reciprocal, rint(w * (1.0f / delta)) -- w = 86.5 * delta lands on 87 where
+ * the division gives 86 -- and a layer re-quantized without an adapter must give back the integers from_float stored. */
+MIXDQ_HD float mixdq_lora_q(float w, float delta, int bits) {
+  if (bits == 8) return __builtin_rintf(MIXDQ_MUL_RN(w, MIXDQ_DIV_RN(1.0f, delta)));
+  return __builtin_rintf(MIXDQ_DIV_RN(w, delta));
+}
+
 #endif /* MIXDQ_MATH_H_ */

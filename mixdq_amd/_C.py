@@ -2155,3 +2155,66 @@ def mask_dilate(mask, radius):
                                          out.data_ptr(), B, H, W, radius, _stream())
     _status(code, "mask_dilate")
     return out
+
+
+# ---- LoRA on quantized layers: merge + re-quantize, every layer in one launch (csrc/lora.hip) --------------------
+LORA_INT8, LORA_W4, LORA_F16, LORA_W2 = 0, 1, 2, 3
+LORA_KEEP, LORA_ABSMAX = 0, 1
+LORA_ROWS = 16
+
+
+class LoraLayer(ctypes.Structure):
+    """struct mixdq_lora_layer (include/mixdq_hip.h), field for field."""
+    _fields_ = ([(n, _vp) for n in ("W", "Bcat", "Acat", "svec", "row_map", "out", "weight_scales", "wsum", "bias0",
+                                    "scale", "act_scale", "act_zero_point")]
+                + [("ldw", _i64)]
+                + [(n, ctypes.c_int32) for n in ("w_col0", "N", "Kf", "R", "mode", "rule", "bits", "tap_len")])
+
+
+_lib.mixdq_lora_table.argtypes = [_vp, _i32, _vp, _vp]
+_lib.mixdq_lora_table.restype = _i32
+_lib.mixdq_lora_requant.argtypes = [_vp, _vp, _vp, _i32, _vp]
+_lib.mixdq_lora_requant.restype = _i32
+_lib.mixdq_lora_status.argtypes = [_vp, _i32]
+_lib.mixdq_lora_status.restype = _i32
+
+
+def lora_order(layers):
+    """(order, prefix, grid) of mixdq_lora_table for a list of LoraLayer: host only."""
+    n = len(layers)
+    arr = (LoraLayer * max(n, 1))(*layers)
+    order, prefix = (ctypes.c_int32 * max(n, 1))(), (ctypes.c_int32 * (n + 1))()
+    grid = _lib.mixdq_lora_table(arr, n, order, prefix)
+    _status(-grid if grid < 0 else 0, "lora_table")
+    return list(order), list(prefix), grid
+
+
+class LoraTable:
+    """The descriptor table of lora_requant: `layers` (LoraLayer, any order) are put in launch order -- longest rows
+    first -- and copied to `device` with their prefix table, once.  `keep`: whatever owns the memory the descriptors
+    point at.  A descriptor's rule or mode does not change afterwards; the tensors behind its pointers may."""
+
+    def __init__(self, layers, device, keep=()):
+        self.order, self.prefix, self.grid = lora_order(layers)
+        self.layers = [layers[i] for i in self.order]
+        self.host = (LoraLayer * len(self.layers))(*self.layers)
+        raw = torch.frombuffer(bytearray(bytes(self.host)), dtype=torch.uint8)
+        self.device_table = raw.to(device)
+        self.device_prefix = torch.tensor(self.prefix, dtype=torch.int32).to(device)
+        self.keep = keep
+
+
+def lora_status(layers) -> int:
+    """The status code lora_requant would answer for these LoraLayer descriptors: host only, nothing launched."""
+    arr = (LoraLayer * max(len(layers), 1))(*layers)
+    return _lib.mixdq_lora_status(arr, len(layers))
+
+
+def lora_requant(table: "LoraTable"):
+    """One launch over every layer of `table` (mixdq_lora_requant): W' = W + sum_r Bs Acat re-quantized in place."""
+    dev = table.device_table.device
+    _check(dev.type == "cuda", "lora_requant: the table should be on the GPU")
+    with torch.cuda.device(dev):
+        code = _lib.mixdq_lora_requant(table.host, table.device_table.data_ptr(), table.device_prefix.data_ptr(),
+                                       len(table.layers), _stream())
+    _status(code, "lora_requant")
