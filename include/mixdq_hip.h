@@ -1104,6 +1104,28 @@ int mixdq_lora_status(const mixdq_lora_layer* layers_host, int n_layers);
 int mixdq_lora_requant(const mixdq_lora_layer* layers_host, const mixdq_lora_layer* layers_device,
                        const int32_t* prefix_device, int n_layers, mixdq_stream_t stream);
 
+/* ---- FreeU: skip Fourier filter and backbone scale of one up-block ResNet's (hidden, skip) pair in one launch
+ * (csrc/freeu.hip).  diffusers' apply_freeu / fourier_filter (utils/torch_utils.py) at the
+ * threshold diffusers always passes, 1: out_skip = the skip with the four frequencies (ky, kx) in {0, -1}^2 of every
+ * (image, channel) plane multiplied by s -- seven real sums per plane and a rank-4 correction, no FFT; out_hidden =
+ * the hidden with channels [0, C_h / 2) multiplied by b, the rest copied.  Arithmetic: include/mixdq_math.h
+ * mixdq_freeu_*.  No reference counterpart (the reference leaves FreeU to diffusers).
+ * hidden [B, H, W, C_h], skip [B, H, W, C_s]: dense FP16, channels-last; the outputs alike.  `table`: FP32 [2, 2] in
+ * DEVICE memory, row `stage` (0 or 1) = (b, s), read by the kernel: one captured graph serves every setting.  s == 1
+ * copies the skip's bits, b == 1 the hidden's.  `twiddles`: FP32 [H + W, 2] in device memory, row y = (cos, sin)(2 pi
+ * y / H), row H + x = (cos, sin)(2 pi x / W).  A plane of up to mixdq_freeu_resident_pixels() pixels stays in registers
+ * between the sums and the correction; a larger one is read twice.
+ * Errors, nothing launched: null pointers, stage outside 0..1, negative sizes, H * W beyond 2^31 - 257, an output that
+ * overlaps an input (a skip is also a down-block input: nothing is written in place): MIXDQ_ERR_INVALID_ARG; H < 2 or
+ * W < 2 (diffusers' slice is empty there), C_s % 8 != 0, C_h % 16 != 0: MIXDQ_ERR_SHAPE; a tensor not 16-byte, the
+ * twiddles not 8-byte or the table not 4-byte aligned: MIXDQ_ERR_ALIGNMENT. */
+#define MIXDQ_FREEU_LANES 256    /* lanes of a workgroup: lane l owns the pixels l, l + 256, ... of its plane octet */
+#define MIXDQ_FREEU_MAX_PPL 16   /* most pixels a lane keeps in registers (instantiations: 1, 2, 4, 8, 16)          */
+int mixdq_freeu_resident_pixels(void);   /* MIXDQ_FREEU_LANES * MIXDQ_FREEU_MAX_PPL */
+int mixdq_freeu_f16(const void* hidden_f16, const void* skip_f16, void* out_hidden_f16, void* out_skip_f16,
+                    const float* table, int stage, const float* twiddles, int B, int C_h, int C_s, int H, int W,
+                    mixdq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -489,4 +489,49 @@ MIXDQ_HD float mixdq_lora_q(float w, float delta, int bits) {
   return __builtin_rintf(MIXDQ_DIV_RN(w, delta));
 }
 
+/* ---- FreeU at threshold 1 (mixdq_freeu_f16, csrc/freeu.hip).  diffusers' fourier_filter(x, threshold=1, scale=s)
+ * multiplies the four frequencies (ky, kx) in {0, -1}^2 of every (image, channel) plane by s.  With cy = cos(2 pi y / H),
+ * sy = sin(2 pi y / H), cx, sx alike for x / W (FP32 roundings of float64 values, host-made), the seven basis values of
+ * a pixel are
+ *   w = (1, cy, sy, cx, sx, pc, ps),  pc = fma(-sy, sx, cy * cx),  ps = fma(sy, cx, cy * sx)           mixdq_freeu_basis
+ * and per plane
+ *   S_t  = sum over the pixels of x * w_t: lane l of 256 takes the pixels l, l + 256, ... in ascending order, each
+ *          step S_t = fma(x, w_t, S_t) (S_0 = S_0 + x) from +0                                     mixdq_freeu_accumulate
+ *          the lanes of a wave are then added pairwise, partner lane ^ 32, ^ 16, ^ 8, ^ 4, ^ 2, ^ 1 in that order (own
+ *          value + partner's), and the four waves left to right: ((S^0 + S^1) + S^2) + S^3
+ *   g    = (s - 1) / (float)(H * W), the division correctly rounded;  G_t = g * S_t                    mixdq_freeu_gain
+ *   y    = x + (((((((G_0) + G_1 cy) + G_2 sy) + G_3 cx) + G_4 sx) + G_5 pc) + G_6 ps), every + G w one fma, the last
+ *          sum one FP32 addition; the caller rounds y to FP16: the only FP16 rounding                 mixdq_freeu_apply
+ * s == 1 copies the plane's bits.  The backbone half is f16_rn(f32(h) * b), b == 1 a copy of the bits. */
+MIXDQ_HD void mixdq_freeu_basis(float cy, float sy, float cx, float sx, float* w) {
+  w[0] = 1.0f, w[1] = cy, w[2] = sy, w[3] = cx, w[4] = sx;
+  w[5] = __builtin_fmaf(-sy, sx, MIXDQ_MUL_RN(cy, cx));
+  w[6] = __builtin_fmaf(sy, cx, MIXDQ_MUL_RN(cy, sx));
+}
+
+MIXDQ_HD void mixdq_freeu_accumulate(float* S, float x, const float* w) {
+  S[0] = MIXDQ_ADD_RN(S[0], x);
+  S[1] = __builtin_fmaf(x, w[1], S[1]);
+  S[2] = __builtin_fmaf(x, w[2], S[2]);
+  S[3] = __builtin_fmaf(x, w[3], S[3]);
+  S[4] = __builtin_fmaf(x, w[4], S[4]);
+  S[5] = __builtin_fmaf(x, w[5], S[5]);
+  S[6] = __builtin_fmaf(x, w[6], S[6]);
+}
+
+MIXDQ_HD float mixdq_freeu_gain(float s, int64_t hw) { return MIXDQ_DIV_RN(MIXDQ_SUB_RN(s, 1.0f), (float)hw); }
+
+MIXDQ_HD float mixdq_freeu_apply(float x, const float* G, const float* w) {
+  float r = G[0];
+  r = __builtin_fmaf(G[1], w[1], r);
+  r = __builtin_fmaf(G[2], w[2], r);
+  r = __builtin_fmaf(G[3], w[3], r);
+  r = __builtin_fmaf(G[4], w[4], r);
+  r = __builtin_fmaf(G[5], w[5], r);
+  r = __builtin_fmaf(G[6], w[6], r);
+  return MIXDQ_ADD_RN(x, r);
+}
+
+MIXDQ_HD float mixdq_freeu_backbone(float h, float b) { return MIXDQ_MUL_RN(h, b); }
+
 #endif /* MIXDQ_MATH_H_ */

@@ -2218,3 +2218,46 @@ def lora_requant(table: "LoraTable"):
         code = _lib.mixdq_lora_requant(table.host, table.device_table.data_ptr(), table.device_prefix.data_ptr(),
                                        len(table.layers), _stream())
     _status(code, "lora_requant")
+
+
+# ---- FreeU: skip Fourier filter + backbone scale of one (hidden, skip) pair, one launch (csrc/freeu.hip) ---------
+_lib.mixdq_freeu_f16.argtypes = [_vp] * 5 + [_i32, _vp] + [_i32] * 5 + [_vp]
+_lib.mixdq_freeu_f16.restype = _i32
+_lib.mixdq_freeu_resident_pixels.restype = _i32
+FREEU_LANES = 256                                                         # include/mixdq_hip.h MIXDQ_FREEU_LANES
+FREEU_PPL = (1, 2, 4, 8, 16)                                              # pixels per lane of the register-resident route
+FREEU_RESIDENT_PIXELS = _lib.mixdq_freeu_resident_pixels()                # larger planes are read twice
+
+
+def freeu(hidden, skip, table, stage):
+    """diffusers' apply_freeu on the (hidden, skip) pair of one up-block ResNet, one launch (mixdq_freeu_f16):
+    -> (out_hidden, out_skip), fresh tensors.  hidden [B, C_h, H, W], skip [B, C_s, H, W]: fp16, channels-last, C_s % 8
+    == 0, C_h % 16 == 0, H, W >= 2.  table: fp32 [2, 2] on the device, row `stage` = (b, s).  out_skip = the skip with
+    the four lowest frequencies of every plane times s (fourier_filter at threshold 1); out_hidden = the hidden with
+    channels [0, C_h / 2) times b.  s == 1 / b == 1 copy bits.  No host synchronisation; capturable once the twiddle
+    table of (H, W) exists."""
+    cl = torch.channels_last
+    for t, nm in ((hidden, "hidden"), (skip, "skip")):
+        _check(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float16 and t.dim() == 4,
+               f"freeu: {nm} should be an fp16 [B, C, H, W] GPU tensor")
+        _check(t.is_contiguous(memory_format=cl), f"freeu: {nm} should be channels-last")
+        _check(t.data_ptr() % 16 == 0, f"freeu: {nm} should be 16-byte aligned")
+    B, C_h, H, W = hidden.shape
+    C_s = skip.shape[1]
+    _check(skip.device == hidden.device and (skip.shape[0], skip.shape[2], skip.shape[3]) == (B, H, W),
+           f"freeu: skip should have the hidden's batch and extent {(B, H, W)} on its device, got {tuple(skip.shape)}")
+    _check(H >= 2 and W >= 2, f"freeu: H and W should be at least 2, got {H} x {W} (diffusers' filter box is empty there)")
+    _check(C_s % 8 == 0, f"freeu: the skip's channels should be a multiple of 8, got {C_s}")
+    _check(C_h % 16 == 0, f"freeu: half the hidden's channels should be a multiple of 8, got {C_h} channels")
+    _check(torch.is_tensor(table) and table.device == hidden.device and table.dtype == torch.float32
+           and tuple(table.shape) == (2, 2) and table.is_contiguous(),
+           "freeu: table should be a contiguous fp32 [2, 2] tensor (rows (b, s)) on the hidden's device")
+    _check(stage in (0, 1), f"freeu: stage should be 0 or 1, got {stage!r}")
+    from mixdq_amd.image import freeu_twiddles_on
+    tw = freeu_twiddles_on(H, W, hidden.device)
+    out_h, out_s = torch.empty_like(hidden), torch.empty_like(skip)      # (preserve_format: channels-last)
+    with torch.cuda.device(hidden.device):
+        code = _lib.mixdq_freeu_f16(hidden.data_ptr(), skip.data_ptr(), out_h.data_ptr(), out_s.data_ptr(),
+                                    table.data_ptr(), int(stage), tw.data_ptr(), B, C_h, C_s, H, W, _stream())
+    _status(code, "freeu")
+    return out_h, out_s

@@ -24,6 +24,8 @@ EXT3_SOURCES = ["attention_ip.hip"]
 EXT4_SOURCES = ["attention_ip_hd.hip"]
 # ... and behind the kernel set of _obj/ .. _obj/ext4/: _obj/ext5/ (the LoRA merge + re-quantize launch).
 EXT5_SOURCES = ["lora.hip"]
+# ... and behind the kernel set of _obj/ .. _obj/ext5/: _obj/ext6/ (the FreeU launch).
+EXT6_SOURCES = ["freeu.hip"]
 HEADERS = ["common.h", "attn_core.h", "attn_ip.h", "iconv.h", "igemm_kernel.h", "igemm_pp.h", "f16in_table.h", "sampler_step.h", os.path.join("..", "..", "include", "mixdq_hip.h"),
            os.path.join("..", "..", "include", "mixdq_math.h")]
 # -ffp-contract=off: every fused multiply-add in the arithmetic specification is written
@@ -54,6 +56,7 @@ OBJ_EXT2 = os.path.join(OBJ, "ext2")
 OBJ_EXT3 = os.path.join(OBJ, "ext3")
 OBJ_EXT4 = os.path.join(OBJ, "ext4")
 OBJ_EXT5 = os.path.join(OBJ, "ext5")
+OBJ_EXT6 = os.path.join(OBJ, "ext6")
 
 
 def _hipcc():
@@ -116,7 +119,7 @@ def needs_build() -> bool:
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, s) for s in SOURCES + EXT_SOURCES + EXT2_SOURCES + EXT3_SOURCES + EXT4_SOURCES + EXT5_SOURCES + HEADERS] + [os.path.abspath(__file__)]
+    deps = [os.path.join(CSRC, s) for s in SOURCES + EXT_SOURCES + EXT2_SOURCES + EXT3_SOURCES + EXT4_SOURCES + EXT5_SOURCES + EXT6_SOURCES + HEADERS] + [os.path.abspath(__file__)]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -127,13 +130,14 @@ def build(force: bool = False, verbose: bool = False) -> str:
         os.makedirs(OBJ_EXT3, exist_ok=True)
         os.makedirs(OBJ_EXT4, exist_ok=True)
         os.makedirs(OBJ_EXT5, exist_ok=True)
+        os.makedirs(OBJ_EXT6, exist_ok=True)
         hdr_t = max(os.path.getmtime(os.path.join(CSRC, h)) for h in HEADERS)
         hdr_t = max(hdr_t, os.path.getmtime(os.path.abspath(__file__)))
         procs, objs = [], []
-        for src in SOURCES + EXT_SOURCES + EXT2_SOURCES + EXT3_SOURCES + EXT4_SOURCES + EXT5_SOURCES:
+        for src in SOURCES + EXT_SOURCES + EXT2_SOURCES + EXT3_SOURCES + EXT4_SOURCES + EXT5_SOURCES + EXT6_SOURCES:
             path = os.path.join(CSRC, src)
             obj_dir = (OBJ_EXT if src in EXT_SOURCES else OBJ_EXT2 if src in EXT2_SOURCES else OBJ_EXT3 if src in EXT3_SOURCES
-                       else OBJ_EXT4 if src in EXT4_SOURCES else OBJ_EXT5 if src in EXT5_SOURCES else OBJ)
+                       else OBJ_EXT4 if src in EXT4_SOURCES else OBJ_EXT5 if src in EXT5_SOURCES else OBJ_EXT6 if src in EXT6_SOURCES else OBJ)
             obj = os.path.join(obj_dir, src.replace(".hip", ".o"))
             objs.append(obj)
             if (not force and os.path.exists(obj)

@@ -99,6 +99,36 @@ def gaussian_table(n, sigma):
     return _pack(starts, rows)
 
 
+def freeu_twiddles(H, W):
+    """float32 [H + W, 2], the table of FreeU's filter (csrc/freeu.hip, unet._freeu_torch): row y = (cos, sin)(2 pi y /
+    H), row H + x = (cos, sin)(2 pi x / W), computed in float64 and rounded once; whole quarter turns are exact (0, +-1)."""
+    rows = []
+    for n in (int(H), int(W)):
+        k = np.arange(n, dtype=np.float64)
+        c, s = np.cos(2.0 * np.pi * k / n), np.sin(2.0 * np.pi * k / n)
+        quarter = (4 * np.arange(n)) % n == 0
+        rows.append(np.stack([np.where(quarter, np.rint(c), c), np.where(quarter, np.rint(s), s)], axis=1))
+    return np.concatenate(rows).astype(np.float32)
+
+
+_FREEU_TWIDDLES = {}
+
+
+def freeu_twiddles_on(H, W, device):
+    """freeu_twiddles(H, W) as a torch tensor on `device`, made once per (H, W, device) -- never while a stream is
+    capturing: a copy from the host cannot be recorded, so one eager call at the shape comes first, as for every other
+    cached table."""
+    import torch
+    key = (int(H), int(W), torch.device(device))
+    got = _FREEU_TWIDDLES.get(key)
+    if got is None:
+        if key[2].type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"freeu: the twiddle table of a {H} x {W} plane is made by the first eager call at that "
+                               "shape; run one before capturing a graph")
+        got = _FREEU_TWIDDLES[key] = torch.from_numpy(freeu_twiddles(H, W)).to(key[2])
+    return got
+
+
 def _ceil_div(a, b):
     return -((-a) // b)
 

@@ -1157,9 +1157,27 @@ class UpBlock(nn.Module):
             self.upsamplers = nn.ModuleList([Upsample2D(cout)])
         self.has_up = add_up
 
+    fused = False
+    freeu = None        # (table fp32 [2, 2] of rows (b, s), stage) while SDXLUNet.enable_freeu is in force, on up-blocks 0 and 1
+
+    def _freeu(self, x, skip):
+        """diffusers' apply_freeu on one (hidden, skip) pair, as FRESH tensors (a skip is also a down-block input and may
+        carry a handed-off INT8 operand).  Fused: ONE freeu launch, the pair stays unconcatenated and channels-last;
+        de-fused, on the CPU or for other dtypes: the same closed form as torch FP32 operations (_freeu_torch).  The
+        launch's widths (hidden % 16, skip % 8) are enable_freeu's stated limit: another width raises in _C.freeu."""
+        table, stage = self.freeu
+        if self.fused and not DEFUSE and _fusable_f16(x) and _fusable_f16(skip):
+            from mixdq_amd import _C
+            cl = torch.channels_last
+            return _C.freeu(x.contiguous(memory_format=cl), skip.contiguous(memory_format=cl), table, stage)
+        return _freeu_torch(x, skip, table[stage, 0], table[stage, 1])
+
     def forward(self, x, skips, temb, context):
         for i, res in enumerate(self.resnets):
-            x = res(x, temb, skips.pop())      # input = cat([x, skip], dim=1)
+            skip = skips.pop()
+            if self.freeu is not None:
+                x, skip = self._freeu(x, skip)
+            x = res(x, temb, skip)             # input = cat([x, skip], dim=1)
             if self.has_attn:
                 x = self.attentions[i](x, context)
         if self.has_up:
@@ -1631,6 +1649,43 @@ class SDXLUNet(FusedGraph):
             off += 2 * c
         return attns
 
+    # ---- FreeU -----------------------------------------------------------------------------
+    def enable_freeu(self, s1, s2, b1, b2):
+        """diffusers' pipe.enable_freeu(s1, s2, b1, b2), its names and argument order: in up-blocks 0 and 1 (diffusers'
+        resolution_idx) every (hidden, skip) pair is transformed before its ResNet -- the skip's four lowest
+        frequencies times s1 / s2 (fourier_filter at threshold 1), the first half of the hidden's channels times b1 / b2.
+        The values live in a device table the launches read.  The table is made once per device and lives as long as
+        the UNet: this call -- the first, a later one, one after disable_freeu() -- rewrites it IN PLACE, so a captured
+        graph follows the new values.
+        Whether FreeU runs at all is part of what a graph captured, and a Sampler captures at its first call at a shape,
+        not when it is built: what counts is the state at that first call.  A graph captured with FreeU on keeps running
+        it, with the values written last, whatever disable_freeu() says to later eager forwards and later captures;
+        changing the values is free.
+        The fused path's launch takes hidden widths that are multiples of 16 and skip widths that are multiples of 8
+        (every SD 1.5 / 2.1 / SDXL width); a fused FP16 forward of another width raises there, it does not leave the
+        kernels."""
+        values = torch.tensor([[float(b1), float(s1)], [float(b2), float(s2)]], dtype=torch.float32)
+        device = next(t for ts in (self.parameters(), self.buffers()) for t in ts).device
+        tables = self.__dict__.setdefault("_freeu_tables", {})
+        table = tables.get(device)
+        if table is None:
+            table = tables[device] = torch.empty((2, 2), dtype=torch.float32, device=device)
+        table.copy_(values)
+        for stage, blk in enumerate(self.up_blocks):
+            blk.freeu = (table, stage) if stage < 2 else None
+        return self
+
+    def disable_freeu(self):
+        """diffusers' pipe.disable_freeu(): forwards from now on, and graphs captured from now on, launch what they
+        launched before enable_freeu.  The device table stays (a graph captured with FreeU on still reads it)."""
+        for blk in self.up_blocks:
+            blk.freeu = None
+        return self
+
+    @property
+    def freeu_enabled(self) -> bool:
+        return any(blk.freeu is not None for blk in self.up_blocks)
+
     # ---- ControlNet residuals (DESIGN.md section 3.35) ------------------------------------------------------------
     def n_skips(self) -> int:
         """How many skip tensors the down path makes (conv_in's output included): a ControlNet has one residual each."""
@@ -1721,6 +1776,31 @@ class SDXLUNet(FusedGraph):
 def cross_attentions(unet):
     """The cross-attentions (attn2 of every transformer block) in registration order: down, mid, up."""
     return [m.attn2 for m in unet.modules() if isinstance(m, BasicTransformerBlock)]
+
+
+def _freeu_torch(x, skip, b, s):
+    """freeu's closed form as torch FP32 operations (b, s: 0-dim FP32 tensors on the pair's device, read by the
+    operations themselves: no host synchronisation; the twiddle table is cached per (H, W, device) by its first eager
+    call): with the basis w = (1, cos / sin of 2 pi y / H, of 2 pi x / W, of their sum) of every pixel, the plane's seven
+    sums S_t = sum x w_t and y = x + (s - 1) / (H W) * sum_t S_t w_t -- fourier_filter at threshold 1 (include/mixdq_math.h,
+    mixdq_freeu_*; the summation order is torch's) -- and channels [0, C / 2) of the hidden times b.  s == 1 / b == 1
+    return the inputs' bits.  -> (hidden', skip') in the inputs' dtype."""
+    from mixdq_amd.image import freeu_twiddles_on
+    H, W = skip.shape[2], skip.shape[3]
+    if H < 2 or W < 2:
+        raise RuntimeError(f"freeu: H and W should be at least 2, got {H} x {W} (diffusers' filter box is empty there)")
+    tw = freeu_twiddles_on(H, W, skip.device)
+    cy, sy, cx, sx = tw[:H, 0:1], tw[:H, 1:2], tw[H:, 0][None], tw[H:, 1][None]
+    full = lambda t: t.expand(H, W)                                                       # noqa: E731
+    basis = torch.stack([torch.ones(H, W, device=skip.device), full(cy), full(sy), full(cx), full(sx),
+                         cy * cx - sy * sx, sy * cx + cy * sx])
+    xf = skip.float()
+    sums = torch.einsum("bchw,thw->bct", xf, basis)
+    y = xf + (s - 1.0) / float(H * W) * torch.einsum("bct,thw->bchw", sums, basis)
+    out_s = torch.where(s == 1.0, skip, y.to(skip.dtype))
+    half = x.shape[1] // 2
+    scaled = torch.cat([(x[:, :half].float() * b).to(x.dtype), x[:, half:]], dim=1)
+    return torch.where(b == 1.0, x, scaled), out_s
 
 
 _UNIT_SCALE = {}
