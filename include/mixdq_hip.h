@@ -1104,6 +1104,54 @@ int mixdq_lora_status(const mixdq_lora_layer* layers_host, int n_layers);
 int mixdq_lora_requant(const mixdq_lora_layer* layers_host, const mixdq_lora_layer* layers_device,
                        const int32_t* prefix_device, int n_layers, mixdq_stream_t stream);
 
+/* ---- LoHa and DoRA on quantized layers: merge and re-quantize in one launch (csrc/lycoris.hip)
+ * w' = W + sum over the linear ranks of Bs Acat + sum over the Hadamard terms t of (Bs Acat)_t (.) (B2cat A2cat)_t, the two
+ * products of a term taken over ITS ranks only;  W'[n, :] = g_n w'[n, :],  g_n = magnitude[n] / ||w'[n, :]||_2, g_n = 1
+ * without a magnitude and -- our definition -- where the row's sum of squares is 0.  W' is quantized and written exactly
+ * as mixdq_lora_requant does (same modes, rules, vectors and row map; arithmetic: include/mixdq_math.h
+ * mixdq_lycoris_*).  The rank axis [0, R) of the four factor buffers is cut into ranges: [0, R_lin) holds plain LoRA
+ * pairs (LyCORIS's and PEFT's DoRA is one of them plus a magnitude), then Hadamard term t holds [had_end[t - 1],
+ * had_end[t]) with had_end[-1] = R_lin; every range is a multiple of 32, an adapter's own rank padded with zero rows;
+ * ranks from the last range's end to R are not read.  With n_had == 0 and no magnitude the launch writes
+ * mixdq_lora_requant's bytes.  No reference counterpart. */
+#define MIXDQ_LYCORIS_MAX_HADAMARD 8
+typedef struct mixdq_lycoris_layer {
+  const void* W;                 /* the fields of mixdq_lora_layer, with its meanings ...                   */
+  const void* Bcat;              /* f16 [N, R]: B of the linear ranks, B1 (LyCORIS's hada_w1_a) of the Hadamard ones */
+  const void* Acat;              /* f16 [R, Kf]: A, and A1 (hada_w1_b), in the layer's stored column order  */
+  const float* svec;             /* [R]: s_j * alpha_j / r_j; scales Bcat only                              */
+  const int32_t* row_map;
+  void* out;
+  float* weight_scales;
+  float* wsum;
+  float* bias0;
+  float* scale;
+  const float* act_scale;
+  const float* act_zero_point;
+  int64_t ldw;
+  int32_t w_col0;
+  int32_t N, Kf, R;              /* R: the factor buffers' rank extent; R % 32 == 0, 32 <= R <= 256          */
+  int32_t mode, rule;            /* MIXDQ_LORA_*                                                            */
+  int32_t bits;
+  int32_t tap_len;
+  const void* B2cat;             /* ... f16 [N, R]: B2 (hada_w2_a) on the Hadamard ranks, unscaled; null if n_had == 0 */
+  const void* A2cat;             /* f16 [R, Kf]: A2 (hada_w2_b) on the Hadamard ranks; null if n_had == 0    */
+  const float* magnitude;        /* [N] in LOGICAL row order, or null: no row norm, g = 1                    */
+  int32_t R_lin;                 /* linear ranks [0, R_lin): % 32 == 0, 0 .. R                               */
+  int32_t n_had;                 /* Hadamard terms, 0 .. MIXDQ_LYCORIS_MAX_HADAMARD                          */
+  int32_t had_end[MIXDQ_LYCORIS_MAX_HADAMARD];   /* end of term t's ranks: ascending, each range % 32 == 0, <= R */
+} mixdq_lycoris_layer;
+/* Host only: mixdq_lora_table's order, prefix and grid for these descriptors (MIXDQ_LORA_ROWS rows per workgroup). */
+int mixdq_lycoris_table(const mixdq_lycoris_layer* layers_host, int n_layers, int32_t* order, int32_t* prefix);
+/* Host only: the status mixdq_lycoris_requant would answer for these descriptors (its checks, nothing launched). */
+int mixdq_lycoris_status(const mixdq_lycoris_layer* layers_host, int n_layers);
+/* One launch over `n_layers` descriptors; the three table arguments as mixdq_lora_requant's.
+ * Errors, nothing launched: everything mixdq_lora_requant refuses, with its codes; n_had outside 0 .. 8, or n_had > 0
+ * with a null B2cat or A2cat: MIXDQ_ERR_INVALID_ARG; R_lin % 32 != 0 or outside 0 .. R, a Hadamard range that is empty,
+ * not a multiple of 32 or ends beyond R, B2cat / A2cat not 8-byte or the magnitude not 4-byte aligned: MIXDQ_ERR_SHAPE. */
+int mixdq_lycoris_requant(const mixdq_lycoris_layer* layers_host, const mixdq_lycoris_layer* layers_device,
+                          const int32_t* prefix_device, int n_layers, mixdq_stream_t stream);
+
 /* ---- FreeU: skip Fourier filter and backbone scale of one up-block ResNet's (hidden, skip) pair in one launch
  * (csrc/freeu.hip).  diffusers' apply_freeu / fourier_filter (utils/torch_utils.py) at the
  * threshold diffusers always passes, 1: out_skip = the skip with the four frequencies (ky, kx) in {0, -1}^2 of every

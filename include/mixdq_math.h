@@ -489,6 +489,31 @@ MIXDQ_HD float mixdq_lora_q(float w, float delta, int bits) {
   return __builtin_rintf(MIXDQ_DIV_RN(w, delta));
 }
 
+/* ---- LoHa / DoRA merge + re-quantize (mixdq_lycoris_requant, csrc/lycoris.hip).  For row n and column k of a layer:
+ *   w'[n, k] = f32(W[n, k]) + sum over the linear ranks r of f32(Bs[n, r] * Acat[r, k])          as mixdq_lora_requant
+ *              then, for the Hadamard terms t in table order,  w' = fma(P1_t, P2_t, w')          mixdq_lycoris_hadamard
+ *              P1_t[n, k] = sum over t's ranks of f32(Bs[n, r] * Acat[r, k]),  P2_t = the same sum of B2cat * A2cat, each
+ *              accumulated in FP32 by the FP16 MFMA from +0;  Bs = f16_rn(svec * Bcat) (mixdq_lora_scaled), B2cat as it is
+ *   sumsq_n  = sum_k w'[n, k]^2 in FP32: a lane takes 16 consecutive columns of every 256 in ascending order, each step
+ *              one fma from +0 (mixdq_lycoris_sumsq); the four lanes of a row are added (own + partner's: lane ^ 16, then
+ *              lane ^ 32), then the four waves left to right.  Every term is >= 0: the relative error is at most
+ *              (16 ceil(Kf / 256) + 5) * 2^-24 on top of that of the w' themselves
+ *   g_n      = m_n / sqrt(sumsq_n), square root and division correctly rounded; 1 without a magnitude, and 1 where
+ *              sumsq_n == 0 (OUR definition: PEFT would divide by zero)                           mixdq_lycoris_gain
+ *   W'[n, k] = g_n * w'[n, k], one FP32 rounding                                                  mixdq_lycoris_scaled
+ *   delta_n  = weight_scales[n] (KEEP), or mixdq_lora_delta of |g_n| * max_k |w'[n, k]| (one FP32 rounding; rounding is
+ *              monotonic, so this is max_k |W'[n, k]|) (ABSMAX)
+ *   q, wsum, bias0, scale and the FP16 mode: mixdq_lora_requant's, on W'. */
+MIXDQ_HD float mixdq_lycoris_hadamard(float p1, float p2, float acc) { return __builtin_fmaf(p1, p2, acc); }
+
+MIXDQ_HD float mixdq_lycoris_sumsq(float w, float ss) { return __builtin_fmaf(w, w, ss); }
+
+MIXDQ_HD float mixdq_lycoris_gain(float m, float sumsq) {
+  return sumsq > 0.0f ? MIXDQ_DIV_RN(m, MIXDQ_SQRT_RN(sumsq)) : 1.0f;
+}
+
+MIXDQ_HD float mixdq_lycoris_scaled(float g, float w) { return MIXDQ_MUL_RN(g, w); }
+
 /* ---- FreeU at threshold 1 (mixdq_freeu_f16, csrc/freeu.hip).  diffusers' fourier_filter(x, threshold=1, scale=s)
  * multiplies the four frequencies (ky, kx) in {0, -1}^2 of every (image, channel) plane by s.  With cy = cos(2 pi y / H),
  * sy = sin(2 pi y / H), cx, sx alike for x / W (FP32 roundings of float64 values, host-made), the seven basis values of

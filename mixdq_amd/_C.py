@@ -2220,6 +2220,76 @@ def lora_requant(table: "LoraTable"):
     _status(code, "lora_requant")
 
 
+# ---- LoHa / DoRA on quantized layers: the same merge with Hadamard terms and a row norm (csrc/lycoris.hip) -------
+LYCORIS_MAX_HADAMARD = 8
+
+
+class LycorisLayer(ctypes.Structure):
+    """struct mixdq_lycoris_layer (include/mixdq_hip.h), field for field: LoraLayer's, then the second factors, the
+    magnitude and the rank ranges."""
+    _fields_ = (list(LoraLayer._fields_)
+                + [(n, _vp) for n in ("B2cat", "A2cat", "magnitude")]
+                + [("R_lin", ctypes.c_int32), ("n_had", ctypes.c_int32),
+                   ("had_end", ctypes.c_int32 * LYCORIS_MAX_HADAMARD)])
+
+    @classmethod
+    def from_lora(cls, desc, **fields):
+        """A LoraLayer's fields with `fields` on top (had_end: a sequence; n_had follows from it)."""
+        d = cls()
+        ctypes.memmove(ctypes.byref(d), ctypes.byref(desc), ctypes.sizeof(LoraLayer))
+        ends = list(fields.pop("had_end", ()))
+        _check(len(ends) <= LYCORIS_MAX_HADAMARD, f"at most {LYCORIS_MAX_HADAMARD} Hadamard terms per layer")
+        d.n_had = len(ends)
+        for i, e in enumerate(ends):
+            d.had_end[i] = e
+        for k, v in fields.items():
+            setattr(d, k, v)
+        return d
+
+
+_lib.mixdq_lycoris_table.argtypes = [_vp, _i32, _vp, _vp]
+_lib.mixdq_lycoris_table.restype = _i32
+_lib.mixdq_lycoris_requant.argtypes = [_vp, _vp, _vp, _i32, _vp]
+_lib.mixdq_lycoris_requant.restype = _i32
+_lib.mixdq_lycoris_status.argtypes = [_vp, _i32]
+_lib.mixdq_lycoris_status.restype = _i32
+
+
+class LycorisTable:
+    """The descriptor table of lycoris_requant, as LoraTable: `layers` (LycorisLayer, any order) in launch order on
+    `device` with their prefix table.  The rank ranges are part of a descriptor, so a table serves one apply()."""
+
+    def __init__(self, layers, device, keep=()):
+        n = len(layers)
+        arr = (LycorisLayer * max(n, 1))(*layers)
+        order, prefix = (ctypes.c_int32 * max(n, 1))(), (ctypes.c_int32 * (n + 1))()
+        self.grid = _lib.mixdq_lycoris_table(arr, n, order, prefix)
+        _status(-self.grid if self.grid < 0 else 0, "lycoris_table")
+        self.order, self.prefix = list(order), list(prefix)
+        self.layers = [layers[i] for i in self.order]
+        self.host = (LycorisLayer * n)(*self.layers)
+        self.device_table = torch.frombuffer(bytearray(bytes(self.host)), dtype=torch.uint8).to(device)
+        self.device_prefix = torch.tensor(self.prefix, dtype=torch.int32).to(device)
+        self.keep = keep
+
+
+def lycoris_status(layers) -> int:
+    """The status code lycoris_requant would answer for these LycorisLayer descriptors: host only, nothing launched."""
+    arr = (LycorisLayer * max(len(layers), 1))(*layers)
+    return _lib.mixdq_lycoris_status(arr, len(layers))
+
+
+def lycoris_requant(table: "LycorisTable"):
+    """One launch over every layer of `table` (mixdq_lycoris_requant): W' = g (W + linear + Hadamard terms), re-quantized
+    in place."""
+    dev = table.device_table.device
+    _check(dev.type == "cuda", "lycoris_requant: the table should be on the GPU")
+    with torch.cuda.device(dev):
+        code = _lib.mixdq_lycoris_requant(table.host, table.device_table.data_ptr(), table.device_prefix.data_ptr(),
+                                          len(table.layers), _stream())
+    _status(code, "lycoris_requant")
+
+
 # ---- FreeU: skip Fourier filter + backbone scale of one (hidden, skip) pair, one launch (csrc/freeu.hip) ---------
 _lib.mixdq_freeu_f16.argtypes = [_vp] * 5 + [_i32, _vp] + [_i32] * 5 + [_vp]
 _lib.mixdq_freeu_f16.restype = _i32

@@ -8,7 +8,9 @@ without an adapter, and captured graphs read the new weights at the old addresse
     bank.set_scales([0.4]); bank.restore()
 
 The activation quantizers stay as calibrated (the reference calibrates after fusing LoRA into the float weights; here
-that is a limit).  W2-stored layers, text encoders, DoRA / LoHa / LoKr and key-format parsing are not here."""
+that is a limit).  LoHa terms and DoRA magnitudes come as dict values of apply() and go through `_C.lycoris_requant`
+(csrc/lycoris.hip).  W2-stored layers, text encoders, LoKr, Tucker forms and key-format parsing
+are not here."""
 from __future__ import annotations
 
 import torch
@@ -40,6 +42,7 @@ class _Target:
         self.Bcat = torch.zeros((self.N, rank), dtype=torch.float16, device=dev)
         self.Acat = torch.zeros((rank, kf), dtype=torch.float16, device=dev)
         self.svec = torch.zeros(rank, dtype=torch.float32, device=dev)
+        self.B2cat = self.A2cat = self.mag = None              # LoHa's second factors, DoRA's magnitude: made when first needed
         conv = isinstance(mod, QuantizedConv2d)
         get = lambda n: getattr(mod, n + sfx, None)            # noqa: E731
         self.written = []
@@ -134,6 +137,7 @@ class LoraBank:
         self.modules = {n: m for n, m in unet.named_modules() if isinstance(m, (QuantizedLinear, QuantizedConv2d))}
         self.float_state, self.w_bits = float_state, dict(w_bits or {})
         self.targets, self.table, self.keep_table, self.adapters = {}, None, None, []
+        self.lyco = None                                       # the LoHa / DoRA state of the last apply(), if it had any
 
     # ---- the static side: masters, factor buffers, descriptors -- built once per set of targeted layers
     def _row_map(self, name, mod):
@@ -185,9 +189,22 @@ class LoraBank:
 
     # ---- the dynamic side
     def apply(self, adapters, scales):
-        """adapters: list of {module name: (A [r, ...], B [N, r], alpha)}; scales: one strength per adapter."""
+        """adapters: list of {module name: (A [r, ...], B [N, r], alpha)}; scales: one strength per adapter.
+
+        A value may also be a dict (LyCORIS's hada_* tensors, PEFT's lora_magnitude_vector / kohya's dora_scale, brought
+        by module name):
+            {"kind": "lora", "A": [r, ...], "B": [N, r], "alpha": a, "magnitude": m [N]}           DoRA (magnitude optional)
+            {"kind": "loha", "w1_a": [N, r], "w1_b": [r, ...], "w2_a": [N, r], "w2_b": [r, ...], "alpha": a}
+        A dict's conv factor is [r, C, R, S] or flat [r, C*R*S] in (C, R, S) order.  W' = g (W + sum_j s_j dW_j) with
+        g[n] = m[n] / ||row n||: the strength scales dW only, as PEFT does.  An adapter whose strength is exactly 0 is
+        skipped TOGETHER WITH its magnitude: 0 means off, and all-zero strengths give what no adapter gives.  An apply()
+        of tuples only launches what it always did (_C.lora_requant); any dict routes the launch to _C.lycoris_requant
+        (csrc/lycoris.hip), where a Hadamard term takes its rank rounded up to 32 of max_rank."""
         if len(adapters) != len(scales):
             raise ValueError("one scale per adapter")
+        if any(isinstance(v, dict) for ad in adapters for v in ad.values()):
+            return self._apply_lycoris(adapters, scales)
+        self.lyco = None
         names = sorted({n for ad in adapters for n in ad})
         self._tables(names)
         self.adapters = []
@@ -224,6 +241,8 @@ class LoraBank:
             for name, (r0, r, unit) in spans.items():
                 for t in self.targets[name]:
                     t.svec[r0:r0 + r] = float(s) * unit
+        if self.lyco is not None:                              # a magnitude is on exactly while its adapter's strength is not 0
+            self.lyco["on"] = {n for n, (j, _) in self.lyco["magnitude"].items() if float(scales[j]) != 0.0}
         self._launch(self.table)
 
     def restore(self):
@@ -235,12 +254,132 @@ class LoraBank:
             for dst, src in zip(t.written, t.snapshot):          # (the scales KEEP reads; the launch rewrites the rest)
                 if src is not None and src.dtype == torch.float32:
                     dst.copy_(src)
-        self.adapters = []
+        self.adapters, self.lyco = [], None
         self._launch(self.keep_table, restoring=True)
+
+    # ---- LoHa / DoRA: the same buffers with rank ranges, second factors and a magnitude (csrc/lycoris.hip)
+    @staticmethod
+    def _term(name, v):
+        """One adapter value -> ('lin' | 'had', factors, alpha, magnitude or None)."""
+        if not isinstance(v, dict):
+            A, B, alpha = v
+            return "lin", (A, B), alpha, None
+        if any(k in v for k in ("hada_t1", "hada_t2", "t1", "t2")):
+            raise ValueError(f"LoraBank: {name}: Tucker-form LoHa (hada_t1 / hada_t2) is not supported")
+        kind = v.get("kind")
+        if kind == "lora":
+            return "lin", (v["A"], v["B"]), v["alpha"], v.get("magnitude")
+        if kind == "loha":
+            if v.get("magnitude") is not None:
+                raise ValueError(f"LoraBank: {name}: a magnitude goes with a 'lora' term")
+            return "had", (v["w1_b"], v["w1_a"], v["w2_b"], v["w2_a"]), v["alpha"], None
+        raise ValueError(f"LoraBank: {name}: adapter kind {kind!r} is not 'lora' or 'loha'")
+
+    def _stored_factor(self, name, A, r, from_dict):
+        """A down factor in the layer's stored column order [r, Kf]; a dict's flat conv factor is in (C, R, S) order."""
+        shape = tuple(self.float_state[name + ".weight"].shape)
+        if from_dict and A.dim() == 2 and len(shape) == 4 and A.shape[1] == shape[1] * shape[2] * shape[3]:
+            A = A.reshape((r,) + shape[1:])
+        return conv_factor_stored(A) if A.dim() == 4 else A
+
+    def _apply_lycoris(self, adapters, scales):
+        parsed = [{n: self._term(n, v) + (isinstance(v, dict),) for n, v in ad.items()} for ad in adapters]
+        names = sorted({n for ad in adapters for n in ad})
+        self._tables(names)
+        flat = [t for ts in self.targets.values() for t in ts]
+        for t in flat:
+            t.Bcat.zero_(), t.Acat.zero_(), t.svec.zero_()
+        lyco = dict(ranges={}, magnitude={}, on=set())
+        self.adapters = [{} for _ in adapters]
+        for name in names:
+            ts = self.targets[name]
+            N, kf = ts[0].N, sum(t.kf for t in ts)
+            terms = [(j,) + ad[name] for j, ad in enumerate(parsed) if name in ad]
+            lin = [x for x in terms if x[1] == "lin"]
+            had = [x for x in terms if x[1] == "had"]
+            r_lin = -(-sum(x[2][0].shape[0] for x in lin) // 32) * 32
+            total = r_lin + sum(-(-x[2][0].shape[0] // 32) * 32 for x in had)
+            if total > self.max_rank:
+                raise ValueError(f"LoraBank: {name}: summed rank {total} (every Hadamard term and the linear terms "
+                                 f"together each padded to 32) exceeds max_rank {self.max_rank}")
+            if len(had) > _C.LYCORIS_MAX_HADAMARD:
+                raise ValueError(f"LoraBank: {name}: more than {_C.LYCORIS_MAX_HADAMARD} Hadamard terms")
+            mags = [(j, m) for j, _, _, _, m, _ in terms if m is not None]
+            if len(mags) > 1:
+                raise ValueError(f"LoraBank: {name}: more than one magnitude on a layer")
+            if mags and len(ts) > 1:
+                raise ValueError(f"LoraBank: {name}: a magnitude on a split conv_shortcut is not supported (the row norm "
+                                 "spans both halves)")
+            if mags and mags[0][1].numel() != N:
+                raise ValueError(f"LoraBank: {name}: the magnitude has {mags[0][1].numel()} elements, the layer {N} rows")
+            if had:
+                for t in ts:
+                    if t.B2cat is None:      # the second factor buffers: the first time they are needed
+                        t.B2cat, t.A2cat = torch.zeros_like(t.Bcat), torch.zeros_like(t.Acat)
+                    t.B2cat.zero_(), t.A2cat.zero_()
+            r0, ends = 0, []
+            for j, kind, fac, alpha, _, from_dict in lin + had:
+                r = fac[0].shape[0]
+                if kind == "had":
+                    r0 = r_lin if not ends else ends[-1]
+                    ends.append(r0 + -(-r // 32) * 32)
+                downs = [self._stored_factor(name, A, r, from_dict) for A in fac[0::2]]
+                for A2, B in zip(downs, fac[1::2]):
+                    if B.shape != (N, r) or A2.shape != (r, kf):
+                        raise ValueError(f"LoraBank: {name}: factors {tuple(A2.shape)}, {tuple(B.shape)} do not fit a "
+                                         f"[{N}, {kf}] layer")
+                for t in ts:
+                    for A2, B, Bd, Ad in zip(downs, fac[1::2], (t.Bcat, t.B2cat), (t.Acat, t.A2cat)):
+                        Bd[:, r0:r0 + r] = B.to(Bd)
+                        Ad[r0:r0 + r] = A2[:, t.col0:t.col0 + t.kf].to(Ad)
+                self.adapters[j][name] = (r0, r, float(alpha) / r)
+                r0 += r
+            lyco["ranges"][name] = (r_lin, ends)
+            if mags:
+                t = ts[0]
+                if t.mag is None:
+                    t.mag = torch.zeros(N, dtype=torch.float32, device=t.Bcat.device)
+                t.mag.copy_(mags[0][1].reshape(N).to(t.mag))
+                lyco["magnitude"][name] = (mags[0][0], t.mag)
+        self.lyco = lyco
+        self.set_scales(scales)
+
+    def _lycoris_table(self):
+        """The descriptors of this state: every target's LoRA descriptor with its rank ranges, second factors and -- while
+        its adapter is on -- its magnitude.  A target the last apply() did not name has no ranges: it is re-quantized
+        from its master."""
+        flat = [t for ts in self.targets.values() for t in ts]
+        descs = []
+        for t in flat:
+            r_lin, ends = self.lyco["ranges"].get(t.name, (0, []))
+            on = t.name in self.lyco["on"]
+            d = _C.LycorisLayer.from_lora(t.desc, R_lin=r_lin, had_end=ends,
+                                          B2cat=t.B2cat.data_ptr() if ends else None, A2cat=t.A2cat.data_ptr() if ends else None,
+                                          magnitude=t.mag.data_ptr() if on else None)
+            d.rule = self.rule
+            descs.append(d)
+        return _C.LycorisTable(descs, flat[0].Bcat.device, keep=flat)
+
+    def _merged_f32(self, t):
+        """W' of a layer in FP32 torch, from the master and the factor buffers: what the BOS row of a layer with a
+        Hadamard term or a magnitude is computed from (a layer-sized temporary)."""
+        r_lin, ends = self.lyco["ranges"].get(t.name, (0, []))
+        bs = (t.svec * t.Bcat.float()).half().float()
+        w = t.keep[0].float() + bs[:, :r_lin] @ t.Acat[:r_lin].float()
+        for a, b in zip([r_lin] + ends[:-1], ends):
+            w = w + (bs[:, a:b] @ t.Acat[a:b].float()) * (t.B2cat[:, a:b].float() @ t.A2cat[a:b].float())
+        if t.name in self.lyco["on"]:
+            ss = (w * w).sum(dim=1)
+            w = w * torch.where(ss > 0, t.mag / ss.sqrt(), torch.ones_like(ss))[:, None]
+        return w
 
     @torch.no_grad()
     def _launch(self, table, restoring=False):
-        _C.lora_requant(table)
+        if self.lyco is not None and not restoring:
+            self.lyco["table"] = self._lycoris_table()
+            _C.lycoris_requant(self.lyco["table"])
+        else:
+            _C.lora_requant(table)
         for ts in self.targets.values():
             for t in ts:
                 if restoring and t.snapshot[-1] is not None:     # a weight the master does not reproduce: its copy
@@ -262,7 +401,11 @@ class LoraBank:
             t.mod.bos_pre_computed.copy_(t.bos_snapshot)
             return
         x = self.bos_embedding.reshape(1, -1).to(t.Acat.device, torch.float32)
-        if t.bos_base is None:                                  # x W^T, once (the only layer-sized FP32 temporary)
+        if self.lyco is not None and (self.lyco["ranges"].get(t.name, (0, []))[1] or t.name in self.lyco["on"]):
+            y = x @ self._merged_f32(t).t()                     # a Hadamard term or a row norm: from the merged weight
+            t.mod.bos_pre_computed.copy_(y.to(torch.float16).reshape(t.mod.bos_pre_computed.shape))
+            return
+        if t.bos_base is None:                                 # x W^T, once (the only layer-sized FP32 temporary)
             t.bos_base = x @ t.keep[0].float().t()
         y = t.bos_base + ((x @ t.Acat.float().t()) * t.svec) @ t.Bcat.float().t()
         t.mod.bos_pre_computed.copy_(y.to(torch.float16).reshape(t.mod.bos_pre_computed.shape))
