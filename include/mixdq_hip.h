@@ -1174,6 +1174,33 @@ int mixdq_freeu_f16(const void* hidden_f16, const void* skip_f16, void* out_hidd
                     const float* table, int stage, const float* twiddles, int B, int C_h, int C_s, int H, int W,
                     mixdq_stream_t stream);
 
+/* ---- The front of a CLIP vision tower in one launch (csrc/clip_vision.hip): transformers'
+ * CLIPVisionEmbeddings -- a bias-free 14 x 14 / stride-14 convolution over 3 channels, the class token, the position
+ * embedding -- and pre_layrnorm, with the image normalisation in front: raw image in, the first transformer layer's
+ * input out.  Arithmetic: include/mixdq_math.h mixdq_clip_*.  No reference counterpart.
+ *   out[b, 0,     :] = LN(f16(cls + pos[0]))
+ *   out[b, 1 + p, :] = LN(f16(f16(sum_k pix(b, p, k) * weight[n, k]) + pos[1 + p])),  pix = f16(fma(u, a_c, b_c))
+ * image: [B, 3, S, S] of uint8 (dtype MIXDQ_IMAGE_U8), FP16 or FP32 at the element strides (sb, sc, sh, sw), read in
+ * place: NCHW, channels-last or a sliced view.  S = 14 g, 1 <= g <= MIXDQ_CLIP_MAX_GRID; patch p = row-major over g x g.
+ * norm: six FP32 values in DEVICE memory, (a_c, b_c) at norm[2 c], norm[2 c + 1]: the host folds 1 / 255, mean and std.
+ * weight_f16: [N, MIXDQ_CLIP_KP], row n = the [3, 14, 14] filter flattened (k = (c * 14 + y) * 14 + x), zeros from 588 on.
+ * cls_f16 [N], pos_f16 [pos_rows, N] with pos_rows == g * g + 1, ln_weight_f16 / ln_bias_f16 [N]; both null: no
+ * LayerNorm, the embeddings themselves are stored (towers without a pre-norm).  out_f16: [B, g * g + 1, N] at row
+ * stride ldo (elements; image b starts at row b * (g * g + 1)).  Grid (ceil(g * g / 16) + 1, B), 256 lanes.
+ * Errors, nothing launched: null image / norm / weight / cls / pos / out, one of the LayerNorm pair without the other,
+ * B outside 0 .. 65535, an unknown dtype: MIXDQ_ERR_INVALID_ARG; S % 14 != 0, g outside 1 .. MIXDQ_CLIP_MAX_GRID,
+ * N % 64 != 0, N outside 64 .. MIXDQ_CLIP_MAX_N, pos_rows != g * g + 1, ldo < N or ldo % 4 != 0: MIXDQ_ERR_SHAPE;
+ * weight not 16-byte, cls / pos / LayerNorm vectors / out not 8-byte, norm not 4-byte aligned, image not aligned to its
+ * element: MIXDQ_ERR_ALIGNMENT.  B == 0 writes nothing. */
+#define MIXDQ_CLIP_PATCH 14
+#define MIXDQ_CLIP_KP 608        /* 3 * 14 * 14 = 588 taps padded to 19 MFMA steps of 32 */
+#define MIXDQ_CLIP_MAX_GRID 32   /* patches per side: images up to 448 px */
+#define MIXDQ_CLIP_MAX_N 2048
+int mixdq_clip_patch_embed_f16(const void* image, int dtype, int64_t sb, int64_t sc, int64_t sh, int64_t sw,
+                               const float* norm, const void* weight_f16, const void* cls_f16, const void* pos_f16,
+                               int pos_rows, const void* ln_weight_f16, const void* ln_bias_f16, float eps,
+                               void* out_f16, int64_t ldo, int B, int S, int N, mixdq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -559,4 +559,44 @@ MIXDQ_HD float mixdq_freeu_apply(float x, const float* G, const float* w) {
 
 MIXDQ_HD float mixdq_freeu_backbone(float h, float b) { return MIXDQ_MUL_RN(h, b); }
 
+/* ---- The front of a CLIP vision tower (mixdq_clip_patch_embed_f16, csrc/clip_vision.hip): transformers'
+ * CLIPVisionEmbeddings (a bias-free 14 x 14 / stride-14 convolution over 3 channels, the class token, the position
+ * embedding) and pre_layrnorm, with the image normalisation in front.  Per image b, patch p (raster order over the
+ * g x g patches) and output column n:
+ *   pix  = f16_rn(fma(u, a_c, b_c)): u the pixel as FP32 (uint8 and FP16 convert exactly), (a_c, b_c) = norm[2 c],
+ *          norm[2 c + 1] of its channel -- one FP32 fma, one rounding                                  mixdq_clip_pixel
+ *   acc  = sum_k pix(b, p, k) * W[n, k], k = (c * 14 + y) * 14 + x over the 588 taps (and 20 zero taps of padding):
+ *          exact FP16 x FP16 products accumulated in FP32 by v_mfma_f32_16x16x32_f16, 19 instructions of 32 taps in
+ *          ascending k; the order inside an instruction is the hardware's (tests bound it, exact inputs pin it)
+ *   e    = f16_rn(f32(f16_rn(acc)) + f32(pos[1 + p, n])): transformers' two roundings (the convolution's FP16 output,
+ *          then the FP16 addition)                                                                      mixdq_clip_embed
+ *   e    = f16_rn(f32(cls[n]) + f32(pos[0, n])) for the class-token row 0
+ * and, with a LayerNorm, over the N values e of a row (FP16 values, FP32 arithmetic, two passes):
+ *   sum  : a lane adds its columns (N / 4) w + 16 t + 4 q + {0, 1, 2, 3}, t = 0 .. N / 64 - 1, in ascending order from +0
+ *          (wave w of 4, lane group q of 4); then the groups (q ^ 1 first, then q ^ 2: own + partner's), then the
+ *          waves left to right, ((S^0 + S^1) + S^2) + S^3
+ *   mean = sum / (float)N                                                                             mixdq_clip_ln_mean
+ *   ss   = the same order over fma(d, d, ss), d = e - mean                                            mixdq_clip_ln_sq
+ *   rstd = 1 / sqrt(ss / (float)N + eps), divisions and square root correctly rounded                 mixdq_clip_ln_rstd
+ *   y    = f16_rn(fma((e - mean) * rstd, gamma, beta))                                                mixdq_clip_ln_apply
+ * Never E[x^2] - mean^2: a row with a large common offset keeps its variance. */
+MIXDQ_HD float mixdq_clip_pixel(float u, float a, float b) { return __builtin_fmaf(u, a, b); }
+
+MIXDQ_HD float mixdq_clip_embed(float acc_f16, float pos) { return MIXDQ_ADD_RN(acc_f16, pos); }
+
+MIXDQ_HD float mixdq_clip_ln_mean(float sum, int n) { return MIXDQ_DIV_RN(sum, (float)n); }
+
+MIXDQ_HD float mixdq_clip_ln_sq(float e, float mean, float ss) {
+  const float d = MIXDQ_SUB_RN(e, mean);
+  return __builtin_fmaf(d, d, ss);
+}
+
+MIXDQ_HD float mixdq_clip_ln_rstd(float ss, int n, float eps) {
+  return MIXDQ_DIV_RN(1.0f, MIXDQ_SQRT_RN(MIXDQ_ADD_RN(MIXDQ_DIV_RN(ss, (float)n), eps)));
+}
+
+MIXDQ_HD float mixdq_clip_ln_apply(float e, float mean, float rstd, float gamma, float beta) {
+  return __builtin_fmaf(MIXDQ_MUL_RN(MIXDQ_SUB_RN(e, mean), rstd), gamma, beta);
+}
+
 #endif /* MIXDQ_MATH_H_ */

@@ -2331,3 +2331,59 @@ def freeu(hidden, skip, table, stage):
                                     table.data_ptr(), int(stage), tw.data_ptr(), B, C_h, C_s, H, W, _stream())
     _status(code, "freeu")
     return out_h, out_s
+
+
+# ---- The front of a CLIP vision tower: normalise + patch conv + class token + position + pre-LayerNorm, one launch
+# (csrc/clip_vision.hip) -----------------------------------------------------------------------------------------------
+_lib.mixdq_clip_patch_embed_f16.argtypes = ([_vp, _i32] + [_i64] * 4 + [_vp] * 4 + [_i32, _vp, _vp, ctypes.c_float, _vp, _i64]
+                                            + [_i32] * 3 + [_vp])
+_lib.mixdq_clip_patch_embed_f16.restype = _i32
+CLIP_PATCH, CLIP_KP, CLIP_MAX_GRID, CLIP_MAX_N = 14, 608, 32, 2048         # include/mixdq_hip.h MIXDQ_CLIP_*
+
+
+def clip_pack_patch_weight(weight, out=None):
+    """The patch convolution's [N, 3, 14, 14] parameter as the launch reads it: fp16 [N, CLIP_KP], row n the filter
+    flattened (k = (c * 14 + y) * 14 + x), zeros from 588 on.  Done once per weight (vision.VisionEncoder._derive)."""
+    N = weight.shape[0]
+    _check(tuple(weight.shape[1:]) == (3, CLIP_PATCH, CLIP_PATCH), "clip_pack_patch_weight: weight should be [N, 3, 14, 14]")
+    if out is None:
+        out = torch.zeros((N, CLIP_KP), dtype=torch.float16, device=weight.device)
+    out[:, :3 * CLIP_PATCH * CLIP_PATCH].copy_(weight.reshape(N, -1))
+    return out
+
+
+def clip_patch_embed(image, norm, weight_packed, cls, pos, ln_weight=None, ln_bias=None, eps=1e-5):
+    """transformers' CLIPVisionEmbeddings + pre_layrnorm with the image normalisation in front, one launch
+    (mixdq_clip_patch_embed_f16) -> fp16 [B, g * g + 1, N], row 0 the class token.
+
+    image: [B, 3, S, S] uint8, fp16 or fp32 GPU tensor of ANY strides, S = 14 g, 1 <= g <= 32.  norm: fp32 [3, 2] on the
+    device, row c = (a_c, b_c): a pixel enters as f16(fma(u, a_c, b_c)).  weight_packed: clip_pack_patch_weight's
+    [N, 608]; cls [N]; pos [g * g + 1, N]; ln_weight / ln_bias [N] or both None (no LayerNorm: the embeddings
+    themselves); all fp16, contiguous.  N % 64 == 0, N <= 2048.  No host synchronisation: capturable."""
+    _check(torch.is_tensor(image) and image.is_cuda and image.dim() == 4 and image.dtype in IMAGE_DTYPES,
+           "clip_patch_embed: image should be a 4-D uint8, fp16 or fp32 GPU tensor")
+    B, C, S, S2 = image.shape
+    _check(C == 3 and S == S2, f"clip_patch_embed: image should be [B, 3, S, S], got {tuple(image.shape)}")
+    dev = image.device
+    _check(torch.is_tensor(norm) and norm.device == dev and norm.dtype == torch.float32 and tuple(norm.shape) == (3, 2)
+           and norm.is_contiguous(), "clip_patch_embed: norm should be a contiguous fp32 [3, 2] tensor on the image's device")
+    _check((ln_weight is None) == (ln_bias is None), "clip_patch_embed: ln_weight and ln_bias go together")
+    for t_, nm, nd in ((weight_packed, "weight_packed", 2), (cls, "cls", 1), (pos, "pos", 2), (ln_weight, "ln_weight", 1),
+                       (ln_bias, "ln_bias", 1)):
+        _check(t_ is None or (torch.is_tensor(t_) and t_.device == dev and t_.dtype == torch.float16 and t_.dim() == nd
+                              and t_.is_contiguous()),
+               f"clip_patch_embed: {nm} should be a contiguous fp16 {nd}-D tensor on the image's device")
+    N = weight_packed.shape[0]
+    _check(weight_packed.shape[1] == CLIP_KP, f"clip_patch_embed: weight_packed should be [N, {CLIP_KP}] (clip_pack_patch_weight)")
+    _check(cls.shape[0] == N and pos.shape[1] == N and (ln_weight is None or (ln_weight.shape[0] == N and ln_bias.shape[0] == N)),
+           f"clip_patch_embed: cls, pos and the LayerNorm vectors should have the weight's {N} columns")
+    g = S // CLIP_PATCH
+    out = torch.empty((B, g * g + 1, N), dtype=torch.float16, device=dev)
+    sb, sc, sh, sw = image.stride()
+    with torch.cuda.device(dev):
+        code = _lib.mixdq_clip_patch_embed_f16(image.data_ptr(), IMAGE_DTYPES[image.dtype], sb, sc, sh, sw, norm.data_ptr(),
+                                               weight_packed.data_ptr(), cls.data_ptr(), pos.data_ptr(), pos.shape[0],
+                                               _ptr(ln_weight), _ptr(ln_bias), float(eps), out.data_ptr(), N, B, S, N,
+                                               _stream())
+    _status(code, "clip_patch_embed")
+    return out

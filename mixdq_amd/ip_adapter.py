@@ -12,7 +12,8 @@ them once per run, outside a captured graph.
 Parameter names are the published checkpoint's: `image_proj.proj`, `image_proj.norm`, `ip_adapter.<i>.to_k_ip` /
 `to_v_ip` with i = 2 n + 1, n counting the UNet's transformer blocks (one cross-attention each) in registration order:
 down, mid, up.  diffusers is not available where this was written: that index rule is NOT verified against its loader.
-Not here: the CLIP vision encoder (the caller brings image embeddings), the Resampler of the "plus" adapters (pass its
+The image embeddings come from mixdq_amd.vision (`vision(image).image_embeds`) or from the caller.
+Not here: the Resampler of the "plus" adapters (pass its
 [B, T, cross_dim] tokens to `kv`), ip_adapter_masks, FaceID's LoRA, quantized to_k_ip / to_v_ip, real weights.
 """
 import torch
