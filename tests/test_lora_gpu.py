@@ -147,6 +147,7 @@ def _check_target(tg, rule):
     """One descriptor's buffers after apply() against the restatement on its master and factors: the random-input rule
     for the integers (under the GPU's delta_n), the vectors exactly from ITS integers; FP16: half an FP16 ulp plus the
     accumulation bound."""
+    # (reads the bank's OWN staging: it pins the launch; tests/test_lora_oracle_gpu.py pins the staging itself)
     d, rm = tg.desc, (np.arange(tg.N) if tg.keep[1] is None else tg.keep[1].cpu().numpy())
     mode = ("int8", "w4", "f16")[d.mode]
     args = [a.cpu().numpy() for a in (tg.keep[0][:, tg.col0:tg.col0 + tg.kf], tg.Bcat, tg.Acat, tg.svec)]
