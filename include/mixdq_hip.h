@@ -1201,6 +1201,48 @@ int mixdq_clip_patch_embed_f16(const void* image, int dtype, int64_t sb, int64_t
                                int pos_rows, const void* ln_weight_f16, const void* ln_bias_f16, float eps,
                                void* out_f16, int64_t ldo, int B, int S, int N, mixdq_stream_t stream);
 
+/* ---- The two launches of a perceiver Resampler (csrc/resampler.hip; IP-Adapter "plus").
+ * Arithmetic: include/mixdq_math.h mixdq_perceiver_* / mixdq_skinny_*.  No reference counterpart.
+ *
+ * mixdq_attention_f16_perceiver: out[b, t, h*64 + d] = softmax_k(q . k * softmax_scale) v per head h, the key index
+ * running over source 1 (t1 rows of k1 / v1) and then source 2 (t2 rows of k2 / v2) in ONE softmax -- attention over the
+ * concatenation [k1 ; k2], [v1 ; v2] that is never built.  All six tensors FP16 with batch / row strides in ELEMENTS
+ * (multiples of 8; column slices of packed projections are the normal case), as for mixdq_attention_f16.  Softmax in
+ * FP32, P rounded to FP16 for the second product, FP32 accumulation, FP16 output.  Grid (heads, batch), 256 lanes.
+ * Shapes (MIXDQ_ERR_SHAPE otherwise): head_dim == 64, 1 <= tq <= MIXDQ_PERCEIVER_MAX_Q, t1 >= 1, t2 >= 0,
+ * t1 + t2 <= MIXDQ_PERCEIVER_MAX_KEYS.  batch outside 0 .. 65535, heads < 1, a null q / k1 / v1 / out, a null k2 / v2
+ * with t2 > 0: MIXDQ_ERR_INVALID_ARG; a stride not a multiple of 8 or a pointer not 16-byte aligned:
+ * MIXDQ_ERR_ALIGNMENT.  Nothing is launched in any of these cases.  batch == 0 writes nothing. */
+#define MIXDQ_PERCEIVER_MAX_Q 16
+#define MIXDQ_PERCEIVER_MAX_KEYS 4096
+int mixdq_attention_f16_perceiver(const void* q_f16, const void* k1_f16, const void* v1_f16, const void* k2_f16,
+                                  const void* v2_f16, void* out_f16, int batch, int heads, int head_dim, int tq, int t1,
+                                  int t2, int64_t q_batch_stride, int64_t q_row_stride, int64_t k1_batch_stride,
+                                  int64_t k1_row_stride, int64_t v1_batch_stride, int64_t v1_row_stride,
+                                  int64_t k2_batch_stride, int64_t k2_row_stride, int64_t v2_batch_stride,
+                                  int64_t v2_row_stride, int64_t out_batch_stride, int64_t out_row_stride,
+                                  float softmax_scale, mixdq_stream_t stream);
+
+/* mixdq_linear_f16_skinny: D = [residual +] act( LN?(A) W^T + bias ) for few rows -- a launch shaped for streaming the
+ * weight once (grid (N / 16, ceil(M / 16)), 256 lanes, each workgroup a 16 x 16 tile over all of K).
+ * A [M, K] at row stride lda, W [N, K] row-major, D [M, N] at row stride ldd, residual [M, N] at row stride ldd, bias
+ * [N]; all FP16, strides in elements.  flags: MIXDQ_FLAG_ACT_GELU (the activation on the rounded FP16 value, before
+ * the residual); any other bit: MIXDQ_ERR_UNSUPPORTED.  ln_weight / ln_bias [K], both or neither: the rows of A are
+ * normalised first (two-pass FP32 statistics, affine, rounded to FP16: the numbers of a LayerNorm launch in front).
+ * Shapes (MIXDQ_ERR_SHAPE otherwise): 1 <= M <= MIXDQ_SKINNY_MAX_M, N % 16 == 0, K % 32 == 0,
+ * K <= MIXDQ_SKINNY_MAX_K, with a LayerNorm K <= MIXDQ_SKINNY_LN_MAX_K, lda >= K, ldd >= N.
+ * A null A / W / D, one LayerNorm vector without the other, D overlapping A, a residual that overlaps D without being D
+ * (residual == D is fine: each element is read and then written by the same lane): MIXDQ_ERR_INVALID_ARG;
+ * lda % 8 != 0, ldd % 4 != 0, A / W / LayerNorm vectors not 16-byte, D / bias / residual not 8-byte aligned:
+ * MIXDQ_ERR_ALIGNMENT.  Nothing is launched in any of these cases. */
+#define MIXDQ_SKINNY_MAX_M 256
+#define MIXDQ_SKINNY_MAX_K 8192
+#define MIXDQ_SKINNY_LN_MAX_K 2048
+int mixdq_linear_f16_skinny(const void* A_f16, int64_t lda, const void* W_f16, const void* bias_f16_or_null,
+                            const void* residual_f16_or_null, void* D_f16, int64_t ldd, int M, int N, int K,
+                            const void* ln_weight_f16_or_null, const void* ln_bias_f16_or_null, float eps, int flags,
+                            mixdq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

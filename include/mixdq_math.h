@@ -599,4 +599,45 @@ MIXDQ_HD float mixdq_clip_ln_apply(float e, float mean, float rstd, float gamma,
   return __builtin_fmaf(MIXDQ_MUL_RN(MIXDQ_SUB_RN(e, mean), rstd), gamma, beta);
 }
 
+/* ---- Perceiver attention (mixdq_attention_f16_perceiver, csrc/resampler.hip): one softmax over the keys of two
+ * sources.  Keys 0 .. t1 + t2 - 1 (source 1, then source 2) are cut into blocks of 32; block j belongs to wave j % 4.
+ * A wave runs the online softmax of mixdq_attention_f16 over its blocks in ascending order -- raw scores s (FP32 MFMA
+ * sums), c = softmax_scale * log2(e), p = f16_rn(exp2(fma(s, c, -(m * c)))) with m the running maximum of the raw
+ * scores, the row sum l taken over the ROUNDED p, l and the FP32 accumulator o multiplied by exp2((m_old - m_new) * c)
+ * when the maximum moves -- and leaves (m_w, l_w, o_w).  The states of the nw = min(blocks, 4) waves that received a
+ * block are combined once, per query and output column, in wave order:
+ *   M    = max_w m_w
+ *   g_w  = exp2((m_w - M) * c)                                           (the caller's: v_exp_f32 on the device)
+ *   num  = fma(g_w, o_w, num),  den = fma(g_w, l_w, den),  w = 0 .. nw - 1, both from +0
+ *   out  = f16_rn(num / den), the division correctly rounded
+ * A wave without a block takes no part (its g, l and o are not looked at). */
+MIXDQ_HD float mixdq_perceiver_combine(const float g[4], const float l[4], const float o[4], int nw) {
+  float num = 0.0f, den = 0.0f;
+  for (int w = 0; w < 4; ++w) {
+    if (w < nw) {
+      num = __builtin_fmaf(g[w], o[w], num);
+      den = __builtin_fmaf(g[w], l[w], den);
+    }
+  }
+  return MIXDQ_DIV_RN(num, den);
+}
+
+/* ---- Few-row FP16 GEMM (mixdq_linear_f16_skinny, csrc/resampler.hip).  Wave w of four accumulates the K steps of 32
+ * with step % 4 == w in ascending order (FP32, v_mfma_f32_16x16x32_f16; the order inside an instruction is the
+ * hardware's); then, per output element:
+ *   s = ((p_0 + p_1) + p_2) + p_3                                                                    mixdq_skinny_sum
+ *   y = f16_rn(s + f32(bias))          (without a bias: f16_rn(s))                                   mixdq_skinny_bias
+ *   y = f16_rn(mixdq_geluf(f32(y)))    (MIXDQ_FLAG_ACT_GELU: on the rounded value, as mixdq_linear_f16 does)
+ *   y = f16_rn(f32(y) + f32(residual)) (with a residual)                                             mixdq_skinny_residual
+ * With the LayerNorm prologue a row of A is first replaced by f16_rn(LN(row)): mixdq_clip_ln_mean / _sq / _rstd / _apply
+ * above, two passes; lane cl of the row's 16 adds the elements of its 8-element chunks cl, cl + 16, ... in ascending
+ * order from +0, then the lanes exchange (cl ^ 1, ^ 2, ^ 4, ^ 8: own + partner's). */
+MIXDQ_HD float mixdq_skinny_sum(float p0, float p1, float p2, float p3) {
+  return MIXDQ_ADD_RN(MIXDQ_ADD_RN(MIXDQ_ADD_RN(p0, p1), p2), p3);
+}
+
+MIXDQ_HD float mixdq_skinny_bias(float s, float bias) { return MIXDQ_ADD_RN(s, bias); }
+
+MIXDQ_HD float mixdq_skinny_residual(float y_f16, float residual) { return MIXDQ_ADD_RN(y_f16, residual); }
+
 #endif /* MIXDQ_MATH_H_ */

@@ -2387,3 +2387,96 @@ def clip_patch_embed(image, norm, weight_packed, cls, pos, ln_weight=None, ln_bi
                                                _stream())
     _status(code, "clip_patch_embed")
     return out
+
+
+_lib.mixdq_attention_f16_perceiver.argtypes = [_vp] * 6 + [_i32] * 6 + [_i64] * 12 + [ctypes.c_float, _vp]
+_lib.mixdq_attention_f16_perceiver.restype = _i32
+_lib.mixdq_linear_f16_skinny.argtypes = [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, ctypes.c_float,
+                                         _i32, _vp]
+_lib.mixdq_linear_f16_skinny.restype = _i32
+PERCEIVER_MAX_Q, PERCEIVER_MAX_KEYS = 16, 4096                             # include/mixdq_hip.h MIXDQ_PERCEIVER_*
+SKINNY_MAX_M, SKINNY_MAX_K, SKINNY_LN_MAX_K = 256, 8192, 2048              # include/mixdq_hip.h MIXDQ_SKINNY_*
+
+
+def attention_perceiver(q, k1, v1, k2, v2, heads, softmax_scale=None, out=None):
+    """softmax(q [k1 ; k2]^T * scale) [v1 ; v2] per head of width 64, ONE softmax over the keys of both sources, without
+    building the concatenation (mixdq_attention_f16_perceiver): a perceiver Resampler's attention.
+
+    q [B, Tq, C], k1 / v1 [B, T1, C], k2 / v2 [B, T2, C] (or both None: one source) fp16 GPU tensors with unit stride
+    along C = heads * 64 -- column slices of packed projections are read in place.  1 <= Tq <= 16, T1 >= 1,
+    T1 + T2 <= 4096; anything else is refused by the library with `out` untouched.  Returns fp16 [B, Tq, C]."""
+    _check((k2 is None) == (v2 is None), "attention_perceiver: k2 and v2 go together")
+    for t, n in ((q, "q"), (k1, "k1"), (v1, "v1"), (k2, "k2"), (v2, "v2")):
+        _check(t is None or (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float16 and t.dim() == 3
+                             and t.stride(-1) == 1 and t.device == q.device),
+               f"attention_perceiver: {n} should be a [B, T, C] fp16 GPU tensor with unit stride along C")
+    B, Tq, C = q.shape
+    _check(k1.shape == v1.shape and k1.shape[0] == B and k1.shape[2] == C, "attention_perceiver: q / k1 / v1 shapes disagree")
+    _check(k2 is None or (k2.shape == v2.shape and k2.shape[0] == B and k2.shape[2] == C),
+           "attention_perceiver: q / k2 / v2 shapes disagree")
+    D = C // heads if heads > 0 else 0
+    _check(heads > 0 and C == heads * D, "attention_perceiver: C should be heads * head_dim")
+    if out is None:
+        out = torch.empty((B, Tq, C), dtype=torch.float16, device=q.device)
+    _check(out.is_cuda and out.dtype == torch.float16 and tuple(out.shape) == (B, Tq, C) and out.stride(-1) == 1,
+           "attention_perceiver: out should be a [B, Tq, C] fp16 GPU tensor with unit stride along C")
+    sc = float(softmax_scale) if softmax_scale is not None else (0.125 if D == 64 else D ** -0.5)
+    T2 = 0 if k2 is None else k2.shape[1]
+    s2 = (0, 0, 0, 0) if k2 is None else (k2.stride(0), k2.stride(1), v2.stride(0), v2.stride(1))
+    with torch.cuda.device(q.device):
+        code = _lib.mixdq_attention_f16_perceiver(
+            q.data_ptr(), k1.data_ptr(), v1.data_ptr(), _ptr(k2), _ptr(v2), out.data_ptr(), B, heads, D, Tq, k1.shape[1],
+            T2, q.stride(0), q.stride(1), k1.stride(0), k1.stride(1), v1.stride(0), v1.stride(1), *s2,
+            out.stride(0), out.stride(1), sc, _stream())
+    _status(code, "attention_perceiver")
+    return out
+
+
+def linear_f16_skinny_supported(M, N, K, ln=False) -> bool:
+    """Does mixdq_linear_f16_skinny take this shape?  (The header's bounds; launches nothing.)"""
+    return (1 <= M <= SKINNY_MAX_M and N >= 16 and N % 16 == 0 and K >= 32 and K % 32 == 0
+            and K <= (SKINNY_LN_MAX_K if ln else SKINNY_MAX_K))
+
+
+def linear_f16_skinny(input, weight, bias=None, *, residual=None, ln=None, act=None, out=None):
+    """[residual +] act(LN?(input) weight^T + bias) for at most 256 rows, shaped for streaming the weight once
+    (mixdq_linear_f16_skinny).
+
+    input [..., K] fp16 with unit stride along K and ONE row stride (a column slice of a wider matrix is read in
+    place); weight [N, K]; bias [N]; residual [..., N] of the output's layout -- it may BE `out` (lat = lat + f(...)),
+    `out` may not overlap `input`.  ln = (weight [K], bias [K], eps): the rows are normalised first (K <= 2048).
+    act: None or "gelu" (erf form, on the rounded value, before the residual).  N % 16 == 0, K % 32 == 0, K <= 8192;
+    the library refuses anything else.  Returns fp16 [..., N] (`out` if given)."""
+    _check(act in (None, "gelu"), f"linear_f16_skinny: act should be None or 'gelu', got {act!r}")
+    _check(torch.is_tensor(input) and input.is_cuda and input.dtype == torch.float16 and input.dim() >= 1
+           and input.stride(-1) == 1, "linear_f16_skinny: input should be an fp16 GPU tensor with unit stride along K")
+    dev = input.device
+    _check(weight.dtype == torch.float16 and weight.device == dev and weight.dim() == 2 and weight.is_contiguous(),
+           "linear_f16_skinny: weight should be a contiguous fp16 [N, K] tensor on the input's device")
+    N, K = weight.shape
+    _check(input.shape[-1] == K, "linear_f16_skinny: the last dimension of input and weight should match")
+    a = input.reshape(-1, K)                                     # (a view for every layout with one row stride)
+    _check(a.data_ptr() == input.data_ptr() and a.stride(1) == 1, "linear_f16_skinny: input rows should have one stride")
+    M = a.shape[0]
+    lda = a.stride(0) if M > 1 else K
+    if out is None:
+        out = torch.empty(list(input.shape[:-1]) + [N], dtype=torch.float16, device=dev)
+    _check(out.is_cuda and out.dtype == torch.float16 and out.is_contiguous() and out.numel() == M * N,
+           "linear_f16_skinny: out should be a contiguous fp16 [..., N] tensor")
+    for t, n, cnt in ((bias, "bias", N), (residual, "residual", M * N)):
+        _check(t is None or (t.dtype == torch.float16 and t.device == dev and t.is_contiguous() and t.numel() == cnt),
+               f"linear_f16_skinny: {n} should be a contiguous fp16 tensor of {cnt} elements")
+    lw = lb = None
+    eps = 0.0
+    if ln is not None:
+        lw, lb, eps = ln
+        for t in (lw, lb):
+            _check(t is None or (t.dtype == torch.float16 and t.device == dev and t.is_contiguous() and t.numel() == K),
+                   "linear_f16_skinny: the LayerNorm vectors should be contiguous fp16 [K]")
+    _trace_w(weight)
+    with torch.cuda.device(dev):
+        code = _lib.mixdq_linear_f16_skinny(a.data_ptr(), lda, weight.data_ptr(), _ptr(bias), _ptr(residual),
+                                            out.data_ptr(), N, M, N, K, _ptr(lw), _ptr(lb), float(eps),
+                                            FLAG_ACT["gelu"] if act else 0, _stream())
+    _status(code, "linear_f16_skinny")
+    return out

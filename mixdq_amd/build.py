@@ -30,6 +30,8 @@ EXT6_SOURCES = ["freeu.hip"]
 EXT7_SOURCES = ["lycoris.hip"]
 # ... and behind the kernel set of _obj/ .. _obj/ext7/: _obj/ext8/ (the CLIP vision tower's patch-embed launch).
 EXT8_SOURCES = ["clip_vision.hip"]
+# ... and behind the kernel set of _obj/ .. _obj/ext8/: _obj/ext9/ (the Resampler's perceiver attention and few-row GEMM).
+EXT9_SOURCES = ["resampler.hip"]
 HEADERS = ["common.h", "attn_core.h", "attn_ip.h", "iconv.h", "igemm_kernel.h", "igemm_pp.h", "f16in_table.h", "sampler_step.h", os.path.join("..", "..", "include", "mixdq_hip.h"),
            os.path.join("..", "..", "include", "mixdq_math.h")]
 # -ffp-contract=off: every fused multiply-add in the arithmetic specification is written
@@ -63,6 +65,7 @@ OBJ_EXT5 = os.path.join(OBJ, "ext5")
 OBJ_EXT6 = os.path.join(OBJ, "ext6")
 OBJ_EXT7 = os.path.join(OBJ, "ext7")
 OBJ_EXT8 = os.path.join(OBJ, "ext8")
+OBJ_EXT9 = os.path.join(OBJ, "ext9")
 
 
 def _hipcc():
@@ -125,7 +128,7 @@ def needs_build() -> bool:
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, s) for s in SOURCES + EXT_SOURCES + EXT2_SOURCES + EXT3_SOURCES + EXT4_SOURCES + EXT5_SOURCES + EXT6_SOURCES + EXT7_SOURCES + EXT8_SOURCES + HEADERS] + [os.path.abspath(__file__)]
+    deps = [os.path.join(CSRC, s) for s in SOURCES + EXT_SOURCES + EXT2_SOURCES + EXT3_SOURCES + EXT4_SOURCES + EXT5_SOURCES + EXT6_SOURCES + EXT7_SOURCES + EXT8_SOURCES + EXT9_SOURCES + HEADERS] + [os.path.abspath(__file__)]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -139,14 +142,15 @@ def build(force: bool = False, verbose: bool = False) -> str:
         os.makedirs(OBJ_EXT6, exist_ok=True)
         os.makedirs(OBJ_EXT7, exist_ok=True)
         os.makedirs(OBJ_EXT8, exist_ok=True)
+        os.makedirs(OBJ_EXT9, exist_ok=True)
         hdr_t = max(os.path.getmtime(os.path.join(CSRC, h)) for h in HEADERS)
         hdr_t = max(hdr_t, os.path.getmtime(os.path.abspath(__file__)))
         procs, objs = [], []
-        for src in SOURCES + EXT_SOURCES + EXT2_SOURCES + EXT3_SOURCES + EXT4_SOURCES + EXT5_SOURCES + EXT6_SOURCES + EXT7_SOURCES + EXT8_SOURCES:
+        for src in SOURCES + EXT_SOURCES + EXT2_SOURCES + EXT3_SOURCES + EXT4_SOURCES + EXT5_SOURCES + EXT6_SOURCES + EXT7_SOURCES + EXT8_SOURCES + EXT9_SOURCES:
             path = os.path.join(CSRC, src)
             obj_dir = (OBJ_EXT if src in EXT_SOURCES else OBJ_EXT2 if src in EXT2_SOURCES else OBJ_EXT3 if src in EXT3_SOURCES
                        else OBJ_EXT4 if src in EXT4_SOURCES else OBJ_EXT5 if src in EXT5_SOURCES else OBJ_EXT6 if src in EXT6_SOURCES
-                       else OBJ_EXT7 if src in EXT7_SOURCES else OBJ_EXT8 if src in EXT8_SOURCES else OBJ)
+                       else OBJ_EXT7 if src in EXT7_SOURCES else OBJ_EXT8 if src in EXT8_SOURCES else OBJ_EXT9 if src in EXT9_SOURCES else OBJ)
             obj = os.path.join(obj_dir, src.replace(".hip", ".o"))
             objs.append(obj)
             if (not force and os.path.exists(obj)

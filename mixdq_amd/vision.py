@@ -13,10 +13,10 @@ in ViT-L), out_proj with the layer input as residual, LayerNorm, fc1 with the ac
 the residual.  The only torch operators of a forward are views and one row copy (the class-token row); none waits for
 the GPU, so `hip_graph_opt(vision)` captures it.
 
-Not here: OpenCLIP bigG's tower (head width 104, which mixdq_attention_f16 does not serve: refused), the "plus"
-adapters' Resampler (it reads `penultimate`), quantized layers, and FP16 only.  A floating-point path with no
+Not here: OpenCLIP bigG's tower (head width 104, which mixdq_attention_f16 does not serve: refused), quantized layers, and FP16 only.  A floating-point path with no
 counterpart in the reference: held to tolerance against the same network built from stock torch modules
-(tests/vision_ref.py).  DESIGN.md section 3.42.
+(tests/vision_ref.py).  DESIGN.md section 3.42.  `penultimate` is what the "plus" adapters' Resampler reads
+(mixdq_amd.ip_adapter.Resampler).
 """
 from collections import namedtuple
 
